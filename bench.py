@@ -69,6 +69,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-verify", action="store_true", help="skip the untimed single-GPU re-render that checks the N-GPU image CRC")
     ap.add_argument("--no-also", action="store_true", help="skip the `also` sub-records (the other BASELINE configs / stream modes) of the default single-GPU run")
     ap.add_argument("--init-timeout", type=float, default=180.0, help="seconds the process-group init and the first collective may take before the rank prints diagnostics and exits")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the image the last timed step produced (rank 0: the reduced frame) "
+                    "as DIR/image.npy (float32, H x W x 3); past 64 MB, a fixed seeded sample of its pixels instead (image_sample.npy + image_sample_index.npy)")
     return ap.parse_args(argv)
 
 
@@ -147,6 +149,24 @@ def utilisation_fields(live, key, kernel, src_hash):
 def pipeline_bytes(stats_sum, pixels, steps):
     """SURVEY.md §8(d) / DESIGN.md §4: algorithmic bytes of the whole pipeline = 248 B / camera sample + 352 B / expanded vertex + 12 B / pixel."""
     return 248 * stats_sum["camera_samples"] + 352 * stats_sum["vertices"] + 12 * pixels * steps
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: what the timed path handed back in its last step, for comparing two builds output for output.  The frame whole when it fits in
+    DUMP_LIMIT_BYTES, else the same seeded choice of pixels every run (their flat indices ride along, as float64: exact below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return
+    pixels = img.reshape(-1, img.shape[-1])
+    n = (DUMP_LIMIT_BYTES - 4096) // (pixels.shape[1] * 4 + 8)        # (4 KB left for the two .npy headers)
+    idx = np.sort(np.random.default_rng(0).choice(pixels.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), pixels[idx])
+    np.save(os.path.join(out_dir, "image_sample_index.npy"), idx.astype(np.float64))
 
 
 def main():
@@ -299,6 +319,8 @@ def main():
     main_rec = time_workload(ctx, args.width, args.height, spp_total, args.stream_mode, args.numerics, args.steps, args.warmup,
                              shard=(rank, world), pool=args.pool, pipe=pipeline)
     dt, agg, ms, host_img = main_rec["dt"], main_rec["agg"], main_rec["ms"], main_rec["host_img"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, host_img)
     value = main_rec["samples_per_step"] * args.steps / dt / 1e6
     agg_all = rd.sum_over_ranks(agg)
     ranks = rd.gather_objects({"rank": rank, "device": device_index, "name": torch.cuda.get_device_name(device_index), "pid": os.getpid(),

@@ -4,6 +4,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,3 +85,22 @@ def test_bench_golden_table_covers_the_timed_frames():
         crc = bench.oracle_crc(wl, w, h, spp, mode, seed)
         assert crc is not None and len(crc) == 8, (wl, w, h, spp, mode, seed)
     assert bench.oracle_crc("cbox", 1920, 1080, 128, "per_sample", 7) is None        # a frame nobody rendered on the CPU: no claim
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs DIR: the last timed frame as DIR/image.npy (float32) while it fits the 64 MB budget; past it, the same seeded pixel sample every run,
+    with the flat pixel indices it took (float64), so that two builds can be compared output for output."""
+    assert bench.parse_args([]).dump_outputs is None and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    img = np.random.default_rng(3).random((20, 30, 3), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), img)
+    got = np.load(tmp_path / "whole" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 5000)                        # below the frame's 7200 bytes
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img)
+    assert sorted(os.listdir(tmp_path / "a")) == ["image_sample.npy", "image_sample_index.npy"]
+    sample, idx = np.load(tmp_path / "a" / "image_sample.npy"), np.load(tmp_path / "a" / "image_sample_index.npy")
+    assert sample.dtype == np.float32 and idx.dtype == np.float64 and len(idx) == len(sample) > 0
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 5000
+    assert np.array_equal(sample, img.reshape(-1, 3)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "image_sample_index.npy"))
