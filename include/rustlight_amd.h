@@ -229,8 +229,15 @@ typedef enum rl_path_strategy { RL_STRATEGY_ALL = 0, RL_STRATEGY_BSDF = 1, RL_ST
  *      every lane, the true chain threaded through them), then all samples are evaluated in parallel from those states; 5x
  *      slower than RL_STREAM_PER_SAMPLE on the Cornell box at 1080p x 128 spp, same image and counters as the one-lane-per-block walk.
  *  RL_STREAM_PER_SAMPLE: the block stream is forked with the reference's own clone_box rule
- *      (samplers/independent.rs:18-22) once per pixel and once per sample — throughput mode. */
-typedef enum rl_stream_mode { RL_STREAM_REFERENCE_ORDER = 0, RL_STREAM_PER_SAMPLE = 1 } rl_stream_mode;
+ *      (samplers/independent.rs:18-22) once per pixel and once per sample — throughput mode.
+ *  RL_STREAM_STRATIFIED: rustlight's StratifiedSampler (samplers/stratified.rs, CLI `-r stratified`) on the forks of RL_STREAM_PER_SAMPLE:
+ *      n = the power of four >= spp; the first 4 next() of a camera sample each take a stratum of [0, 1) in n, the first 4 next2d()
+ *      each a cell of a sqrt(n) x sqrt(n) grid, every dimension's strata dealt to the pixel's samples by its own keyed permutation
+ *      (with spp < n only the first spp of them); later draws come from the sample's sampler.  Deterministic given the block
+ *      seeds (and seed_variant): the image does not depend on pipeline, split, sharding, frames in flight or the number of GPUs.
+ *      The reference seeds its arrays from random(): statistically the same sampler, not seed-for-seed equivalent.  spp <= 2^30;
+ *      not with numerics = RL_NUMERICS_FAST (RL_ERR_UNSUPPORTED). */
+typedef enum rl_stream_mode { RL_STREAM_REFERENCE_ORDER = 0, RL_STREAM_PER_SAMPLE = 1, RL_STREAM_STRATIFIED = 2 } rl_stream_mode;
 typedef enum rl_numerics { RL_NUMERICS_EXACT = 0, RL_NUMERICS_FAST = 1 } rl_numerics;
 
 /* struct IntegratorPathTracing (explicit/path.rs:14-20) + scene.nb_samples + sharding. */

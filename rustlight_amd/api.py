@@ -23,7 +23,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "librustlight_amd.so")
 RL_OK = 0
 RL_ERR_NO_DEVICE = -2
 STRATEGY_ALL, STRATEGY_BSDF, STRATEGY_EMITTER = 0, 1, 2
-STREAM_REFERENCE_ORDER, STREAM_PER_SAMPLE = 0, 1
+STREAM_REFERENCE_ORDER, STREAM_PER_SAMPLE, STREAM_STRATIFIED = 0, 1, 2      # rl_stream_mode; STRATIFIED: rustlight's StratifiedSampler (`-r stratified`)
 PIPELINE_AUTO, PIPELINE_WAVEFRONT, PIPELINE_FUSED = 0, 1, 2
 NUMERICS_EXACT, NUMERICS_FAST = 0, 1
 
@@ -557,13 +557,27 @@ class MultiContext:
             pass
 
 
+def stratified_draws(pixel_seeds, spp: int, pattern, seed_variant: int = 0, device: int = 0) -> np.ndarray:
+    """Test hook (rl_debug_stratified_draws): the device sampler of STREAM_STRATIFIED.  Pixel p, whose per-sample-mode seed is pixel_seeds[p], walks its
+    spp samples as the renderers do; each sample makes the calls of `pattern` (1 = next(), 2 = next2d()).  Returns float32 [n_pixels, spp, n_out]:
+    the values in the order drawn (a next2d() gives two), n_out = sum(pattern)."""
+    L = lib()
+    fn = L.rl_debug_stratified_draws
+    fn.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_uint64), C.c_uint32, C.c_int, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+    seeds = np.ascontiguousarray(pixel_seeds, dtype=np.uint64).reshape(-1)
+    pat = np.ascontiguousarray(pattern, dtype=np.int32).reshape(-1)
+    out = np.zeros((seeds.shape[0], spp, int(pat.sum())), dtype=np.float32)
+    _check(fn(device, seeds.shape[0], abi.u64ptr(seeds), spp, seed_variant, pat.shape[0], pat.ctypes.data_as(C.POINTER(C.c_int32)), abi.fptr(out)))
+    return out
+
+
 class IntegratorPathTracing:
     """struct IntegratorPathTracing (src/integrators/explicit/path.rs:14-20) + Integrator::compute."""
 
     def __init__(self, min_depth=0, max_depth=None, rr_depth=0, strategy=STRATEGY_ALL, single_scattering=False,
                  stream_mode=STREAM_REFERENCE_ORDER, device=0, numerics=NUMERICS_EXACT, frames_in_flight=1, options=None):
         """stream_mode: the plugin's default is rustlight's own per-block stream order (seed-for-seed the reference's image);
-        STREAM_PER_SAMPLE is the opt-in throughput decomposition.  frames_in_flight (MI355X-specific, not in the reference): how many
+        STREAM_PER_SAMPLE is the opt-in throughput decomposition, STREAM_STRATIFIED the stratified sampler on it.  frames_in_flight (MI355X-specific, not in the reference): how many
         independent frames `compute_frames` — and the progressive wrappers through it — keep on the GPU at once (one device context and
         one host thread each; the images are those of one frame after the other)."""
         self.min_depth, self.max_depth, self.rr_depth = min_depth, max_depth, rr_depth

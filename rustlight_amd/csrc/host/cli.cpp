@@ -1,6 +1,6 @@
 // cli.cpp — `rustlight-amd`: the reference CLI's flags for the `path` subcommand (examples/cli.rs:
 // global flags 106-145, `path` 162-169, medium 355-399, sampler 876-896, run/save 898-923).
-//   rustlight-amd <scene.pbrt|scene.xml> -n SPP -o out.pfm [-r independent:SEED] [-m s[:a[:g]]] [-s SCALE] [-t N]
+//   rustlight-amd <scene.pbrt|scene.xml> -n SPP -o out.pfm [-r independent[:SEED]|stratified[:SEED]] [-m s[:a[:g]]] [-s SCALE] [-t N]
 //                 [--device D] [--gpus N] [--frames-in-flight K] [--stream-mode reference|per-sample] [--numerics exact|fast] [--option name=value ...]
 //                 path [-m MAX|inf] [-n MIN] [-r RR|inf] [-x] [-s all|bsdf|emitter]
 //               | ao [-d DIST|inf] [-n]            (examples/cli.rs:149-154)
@@ -9,6 +9,7 @@
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 #include <chrono>
 #include <cstdio>
+#include <cerrno>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -39,6 +40,7 @@ int main(int argc, char** argv) {
     bool ao_normal_correction = false;
     size_t nb_bsdf = 1, nb_light = 1;
     rl_stream_mode mode = RL_STREAM_REFERENCE_ORDER;   // like rustlight; `--stream-mode per-sample` trades the seed-for-seed image for throughput
+    bool mode_given = false;                            // (-r stratified sets the mode itself)
     uint32_t numerics = RL_NUMERICS_EXACT;
     int frames_in_flight = 1;
     std::vector<std::pair<std::string, std::string>> options;
@@ -56,7 +58,7 @@ int main(int argc, char** argv) {
             else if (a == "--device") device = std::atoi(val().c_str());
             else if (a == "--gpus") gpus = std::atoi(val().c_str());
             else if (a == "--frames-in-flight") frames_in_flight = std::max(1, std::atoi(val().c_str()));   // -a / -e: that many independent passes on the GPU at once (same images, more of the chip busy)
-            else if (a == "--stream-mode") mode = val() == "reference" ? RL_STREAM_REFERENCE_ORDER : RL_STREAM_PER_SAMPLE;
+            else if (a == "--stream-mode") { mode = val() == "reference" ? RL_STREAM_REFERENCE_ORDER : RL_STREAM_PER_SAMPLE; mode_given = true; }
             else if (a == "--numerics") numerics = val() == "fast" ? RL_NUMERICS_FAST : RL_NUMERICS_EXACT;
             else if (a == "--option") {   // an execution option of the device context(s): name=value (rl_context_set_option; none changes an image)
                 const std::string o = val();
@@ -95,8 +97,36 @@ int main(int argc, char** argv) {
         }
     }
     if (scene_path.empty() || output.empty() || !have_cmd) {
-        std::fprintf(stderr, "usage: rustlight-amd <scene.pbrt|scene.xml> -n SPP -o out.pfm [-r independent:SEED] [-m s[:a[:g]]] path [-m max] [-n min] [-r rr] [-x] [-s all|bsdf|emitter]\n");
+        std::fprintf(stderr, "usage: rustlight-amd <scene.pbrt|scene.xml> -n SPP -o out.pfm [-r independent[:SEED]|stratified[:SEED]] [-m s[:a[:g]]] path [-m max] [-n min] [-r rr] [-x] [-s all|bsdf|emitter]\n");
         return 2;
+    }
+    // the sampler (cli.rs:876-896): the master sampler that draws the block seeds is IndependentSampler(SEED) for both kinds — OS entropy without a seed, as
+    // IndependentSampler::default() / StratifiedSampler's random() are; `stratified:SEED` is this drop-in's reproducible form.  stratified =
+    // RL_STREAM_STRATIFIED: StratifiedSampler::create(spp, 4) on every pixel (include/rustlight_amd.h)
+    uint64_t seed = 0;
+    {
+        auto parse_seed = [&](const char* t) -> bool {
+            if (!*t || *t == '-' || *t == '+' || *t == ' ') return false;
+            char* e = nullptr;
+            errno = 0;
+            const unsigned long long v = std::strtoull(t, &e, 10);
+            if (errno == ERANGE || !e || *e) return false;
+            seed = v;
+            return true;
+        };
+        if (rng == "independent") seed = std::random_device{}();   // IndependentSampler::default(): OS entropy
+        else if (rng.rfind("independent:", 0) == 0) seed = std::strtoull(rng.c_str() + 12, nullptr, 10);
+        else if (rng == "stratified" || rng.rfind("stratified:", 0) == 0) {
+            if (rng == "stratified") seed = std::random_device{}();
+            else if (!parse_seed(rng.c_str() + 11)) { std::fprintf(stderr, "stratified sampler: the seed must be an unsigned 64-bit integer (got %s)\n", rng.c_str() + 11); return 2; }
+            if (mode_given) { std::fprintf(stderr, "-r stratified sets the stream mode itself: it cannot be combined with --stream-mode\n"); return 2; }
+            if (numerics == RL_NUMERICS_FAST) { std::fprintf(stderr, "-r stratified is not built with --numerics fast\n"); return 2; }
+            mode = RL_STREAM_STRATIFIED;
+            size_t power_of4 = 1;
+            while (power_of4 < nbsamples) power_of4 *= 4;
+            if (power_of4 != nbsamples) std::fprintf(stderr, "WARN %zu is not 4 multiple (increase count to %zu), the stratified sampler will be less efficient!\n", nbsamples, power_of4);
+        }
+        else { std::fprintf(stderr, "Wrong sampler type provided %s (independent[:seed] or stratified[:seed])\n", rng.c_str()); return 2; }
     }
     try {
         std::unique_ptr<Scene> scene(Scene::load(scene_path, shading_normals));
@@ -144,10 +174,6 @@ int main(int argc, char** argv) {
         integrator.numerics = numerics;
         integrator.frames_in_flight = frames_in_flight;
         integrator.options = options;
-        uint64_t seed;
-        if (rng == "independent") seed = std::random_device{}();   // IndependentSampler::default(): OS entropy
-        else if (rng.rfind("independent:", 0) == 0) seed = std::strtoull(rng.c_str() + 12, nullptr, 10);
-        else { std::fprintf(stderr, "Wrong sampler type provided %s (only independent[:seed])\n", rng.c_str()); return 2; }
         IndependentSampler sampler(seed);
         BufferCollection img;
         double elapsed_ms = 0.0;

@@ -9,5 +9,6 @@
 #include "shading.hip.h"
 #include "trace.hip.h"
 #include "pathstate.hip.h"
+#include "sampler.hip.h"
 #include "stages.hip.h"
 #include "launch.h"

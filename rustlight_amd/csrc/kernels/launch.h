@@ -32,6 +32,13 @@ void launch_trace_batch_fast(dim3 grid, dim3 block, size_t lds_bytes, hipStream_
                              int* mesh_out, int* tri_out, int* steps_out);   // test hook: the tolerance build's BVH4 traversal, batched
 void launch_shade_type(int type, bool medium, dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const Pool& pool);
 void launch_shade_sorted(bool medium, unsigned chunks, dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const Pool& pool);
+// RL_STREAM_STRATIFIED (sampler.hip.h: StratSampler): the persistent kernel for the run-time material switch (fused_strat_*.hip), the wavefront pipeline's
+// raygen / material-sorted shade (shade_strat.hip), ao / direct (mc_strat.hip)
+void launch_fused_strat_lds(bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc);
+void launch_fused_strat_stream(bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc);
+void launch_raygen_strat(dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const Pool& pool);
+void launch_shade_sorted_strat(bool medium, unsigned chunks, dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const Pool& pool);
+void launch_pixel_mc_strat(int kind, bool lds_scene, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const McConst& mp);
 void launch_pixel_mc(int kind, bool lds_scene, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const McConst& mp);
 void launch_mc_chain(int kind, bool lds_scene, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const McConst& mp);   // first pass of reference-order streams for ao / direct
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)

@@ -25,11 +25,12 @@ RL_DEV bool trace_closest(const DeviceScene& sc, const SceneRecs& recs, const St
 template <class Stack>
 RL_DEV bool trace_visible(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, V3 p0, V3 p1) { return shadow_visible(sc, recs, stack, p0, p1); }
 
-template <int KIND, class Stack>
-RL_DEV Col mc_compute_pixel(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, const McConst& mp, unsigned px, unsigned py, Rng& rng,
+// SMP: the sampler of the draws (sampler.hip.h): Rng, or StratSampler (k_pixel_mc_strat)
+template <int KIND, class Stack, class SMP>
+RL_DEV Col mc_compute_pixel(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, const McConst& mp, unsigned px, unsigned py, SMP& rng,
                             unsigned& n_draws, unsigned& n_ext, unsigned& n_shadow, unsigned& n_vertices) {
-    float u = (float)px + rng_next_f32(rng);
-    float v = (float)py + rng_next_f32(rng);
+    float u = (float)px + smp_next(rng);
+    float v = (float)py + smp_next(rng);
     n_draws += 2;
     const V3 o = mk3(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]);
     const V3 d = camera_direction(sc, u, v);
@@ -43,7 +44,7 @@ RL_DEV Col mc_compute_pixel(const DeviceScene& sc, const SceneRecs& recs, const 
     if (KIND == 0) {
         if (!mp.normal_correction && sp.wi.z <= 0.0f) return czero();
         const bool flipped = mp.normal_correction && sp.wi.z <= 0.0f;
-        V2 s2; s2.x = rng_next_f32(rng); s2.y = rng_next_f32(rng);
+        V2 s2 = smp_next2d(rng);
         n_draws += 2;
         V3 d_local = cosine_sample_hemisphere(s2);
         V3 d_world = flipped ? to_world(sp.frame, -d_local) : to_world(sp.frame, d_local);
@@ -63,9 +64,9 @@ RL_DEV Col mc_compute_pixel(const DeviceScene& sc, const SceneRecs& recs, const 
     const float w_nb_light = mp.nb_light_samples == 0u ? 0.0f : div_rn(1.0f, (float)mp.nb_light_samples);
     n_vertices++;
     for (unsigned k = 0; k < mp.nb_light_samples; k++) {
-        float a = rng_next_f32(rng);
-        float b = rng_next_f32(rng);
-        V2 c; c.x = rng_next_f32(rng); c.y = rng_next_f32(rng);
+        float a = smp_next(rng);
+        float b = smp_next(rng);
+        V2 c = smp_next2d(rng);
         n_draws += 4;
         LightSample ls = sample_light(sc, sp.p, true, sp.n_s, a, b, c);   // Some(&its.n_s) (direct.rs:64-70)
         V3 d_out_local = to_local(sp.frame, ls.d);
@@ -78,7 +79,7 @@ RL_DEV Col mc_compute_pixel(const DeviceScene& sc, const SceneRecs& recs, const 
         l_i = l_i + weight_light * bsdf_eval<-1>(sc, mat, sp.has_uv, sp.uv, sp.wi, d_out_local, false) * w_nb_light * ls.weight;
     }
     for (unsigned k = 0; k < mp.nb_bsdf_samples; k++) {
-        V2 s2; s2.x = rng_next_f32(rng); s2.y = rng_next_f32(rng);
+        V2 s2 = smp_next2d(rng);
         n_draws += 2;
         BsdfSample bs;
         if (!bsdf_sample<-1>(sc, mat, sp.has_uv, sp.uv, sp.wi, s2, &bs)) continue;

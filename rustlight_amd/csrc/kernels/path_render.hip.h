@@ -60,6 +60,7 @@ private:
     std::vector<unsigned> owned, item_base;
     unsigned n_pixels = 0;
     bool per_sample = false, fused = false, fast_math = false, two_pass = false, medium = false;
+    bool strat = false;                // RL_STREAM_STRATIFIED: per-pixel items, the *_strat kernels (sampler.hip.h)
     bool overlap_wanted = false;       // two passes: the evaluation pass runs beside the chain pass (every chunk)
     bool one_lane_per_pixel = false;   // the per-sample parking buffer could not be allocated: one lane per pixel, no overlap
     bool overlapped = false;           // ... and did
@@ -105,7 +106,8 @@ private:
     }
 
     int choose_form() {
-        per_sample = params->stream_mode == RL_STREAM_PER_SAMPLE;
+        strat = params->stream_mode == RL_STREAM_STRATIFIED;
+        per_sample = params->stream_mode == RL_STREAM_PER_SAMPLE || strat;
         // pipeline: 1 = wavefront stage kernels, 2 = persistent fused kernel, 0 = auto = fused unless a pool size is forced (reference-order
         // streams at 1080p x 128 spp: wavefront 8.7 s, fused 2.9 s, fused with the items spread over the waves 1.7 s, fused in two passes: see
         // DESIGN.md; per-sample at 1080p x 32 spp, fused vs wavefront: 508 k-triangle / 6-BSDF scene 127 vs 202 ms, 4.9 k triangles 61 vs 153 ms,
@@ -114,6 +116,7 @@ private:
         fused = params->pipeline == 2 || (params->pipeline == 0 && params->pool_slots == 0);
         fast_math = params->numerics == RL_NUMERICS_FAST;
         if (fast_math && !fused) { rl_set_error("numerics = fast exists for the persistent kernel only (pipeline 0 or 2, pool_slots 0)"); return RL_ERR_UNSUPPORTED; }
+        if (fast_math && strat) { rl_set_error("numerics = fast is not built with the stratified sampler (stream_mode = RL_STREAM_STRATIFIED)"); return RL_ERR_UNSUPPORTED; }
         medium = ctx->ds.medium.enabled != 0;
         // Reference-order streams through the persistent kernel run in TWO passes (chain.hip.h): k_stream_chain walks every block's stream with the
         // radiance half of the integrator left out and records the sampler state at the start of each camera sample, then the per-sample form of
@@ -337,7 +340,9 @@ private:
     void launch_fused(const RenderConst& rcl, dim3 grid, hipStream_t on, const StackConf* stcl = nullptr) const {
         const int mat = ctx->single_bsdf ? ctx->bsdf_type : -1;
         const StackConf& s = stcl ? *stcl : stc;
-        if (rcl.queue_mode != 0u)       // (exact build only: the overlap is off in the tolerance build)
+        if (strat)
+            (ctx->lds_scene ? launch_fused_strat_lds : launch_fused_strat_stream)(medium, ctx->area_lights_only, grid, dim3(256), lds_fused, on, rcl, ctx->ds, s);
+        else if (rcl.queue_mode != 0u)       // (exact build only: the overlap is off in the tolerance build)
             (ctx->lds_scene ? launch_fusedq_lds : launch_fusedq_stream)(mat, medium, ctx->area_lights_only, grid, dim3(256), lds_fused, on, rcl, ctx->ds, s);
         else
             (ctx->lds_scene ? (fast_math ? launch_fused_lds_fast : launch_fused_lds) : (fast_math ? launch_fused_stream_fast : launch_fused_stream))(mat, medium, ctx->area_lights_only, grid, dim3(256), lds_fused, on, rcl, ctx->ds, s);
@@ -708,12 +713,14 @@ private:
         for (;;) {
             hipEvent_t* ev = timing ? &ctx->events[kEventsPerIter * in_batch] : nullptr;
             if (timing) hipEventRecord(ev[0], st);
-            hipLaunchKernelGGL(k_raygen, grid_persistent, block, 0, st, rc, ds, pool);
+            if (strat) launch_raygen_strat(grid_persistent, block, st, rc, ds, pool);
+            else hipLaunchKernelGGL(k_raygen, grid_persistent, block, 0, st, rc, ds, pool);
             if (timing) { hipEventRecord(ev[1], st); hipEventRecord(ev[2], st); }
             if (ctx->lds_scene) hipLaunchKernelGGL((k_extend<true>), grid_all, block, lds_trav, st, rc, ds, pool, stc);
             else hipLaunchKernelGGL((k_extend<false>), grid_all, block, lds_trav, st, rc, ds, pool, stc);
             if (timing) { hipEventRecord(ev[3], st); hipEventRecord(ev[4], st); }
-            if (use_sort) launch_shade_sorted(medium, sort_chunks, sort_chunks == 4u ? grid_sort : grid_all, block, st, rc, ds, pool);
+            if (strat) launch_shade_sorted_strat(medium, sort_chunks, sort_chunks == 4u ? grid_sort : grid_all, block, st, rc, ds, pool);     // (every scene: a specialised MAT changes no image)
+            else if (use_sort) launch_shade_sorted(medium, sort_chunks, sort_chunks == 4u ? grid_sort : grid_all, block, st, rc, ds, pool);
             else launch_shade_type(ctx->bsdf_type, medium, grid_all, block, st, rc, ds, pool);
             launches += 1;
             if (timing) { hipEventRecord(ev[5], st); hipEventRecord(ev[6], st); }

@@ -151,9 +151,10 @@ RL_DEV void queue_push(const RenderConst& rc, unsigned item) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __hip_atomic_store(&rc.done_flags[item], rc.queue_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-// internal third value of RenderConst::stream_mode (never accepted from a caller): per-pixel work items as in RL_STREAM_PER_SAMPLE, but every
-// camera sample starts from the sampler state k_stream_chain recorded for it — the image and the counters of RL_STREAM_REFERENCE_ORDER
-enum : int { kStreamGivenStates = 2 };
+// internal value of RenderConst::stream_mode, outside rl_stream_mode (0-2) so that no caller can pass it: per-pixel work items as in RL_STREAM_PER_SAMPLE,
+// but every camera sample starts from the sampler state k_stream_chain recorded for it — the image and the counters of RL_STREAM_REFERENCE_ORDER.
+// (A positive value: with -1 the compiler allocates the per-sample kernels' registers differently.)
+enum : int { kStreamGivenStates = 1000 };
 
 // k_path_fused / k_stream_chain take (RenderConst, DeviceScene, StackConf) by value and re-read the first two from the kernarg segment inside
 // their loops: the segment lays the arguments out like this struct (each at its natural alignment, in order); the kernels static_assert their

@@ -85,7 +85,8 @@ RL_DEV void raygen_chain_slot(const RenderConst& rc, const DeviceScene& sc, PS& 
 // raygen_slot — sample completion, work-item hand-out, sampler forking, Path::from_sensor (2 draws) and
 // Camera::generate for one slot that asked for regeneration.  DYNAMIC: work items come from the global
 // dispenser (wavefront pool); otherwise the slot owns exactly one item (persistent fused kernel).
-template <bool DYNAMIC, class PS>
+// SMP: the sampler the sample's draws go through (sampler.hip.h) — Rng, or StratSampler (RL_STREAM_STRATIFIED: per-pixel items only).
+template <bool DYNAMIC, class PS, class SMP = Rng>
 RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, unsigned& n_samples, unsigned& n_draws) {
     unsigned flags = PU(U_FLAGS);
     if (!(flags & ST_REGEN)) return;
@@ -95,8 +96,9 @@ RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, un
     bool need_item = fresh;
     unsigned bx = 0, by = 0, bw = 1, bh = 1;
     if (rc.stream_mode == RL_STREAM_REFERENCE_ORDER && item < rc.n_items) block_geometry(rc, rc.owned_blocks[item], &bx, &by, &bw, &bh);
-    const bool per_pixel = rc.stream_mode != RL_STREAM_REFERENCE_ORDER;    // per-pixel work items: RL_STREAM_PER_SAMPLE, or the second pass of reference-order streams
-    const bool given = rc.stream_mode == kStreamGivenStates;
+    constexpr bool STRAT = !std::is_same<SMP, Rng>::value;
+    const bool per_pixel = STRAT || rc.stream_mode != RL_STREAM_REFERENCE_ORDER;    // per-pixel work items: RL_STREAM_PER_SAMPLE / _STRATIFIED, or the second pass of reference-order streams
+    const bool given = !STRAT && rc.stream_mode == kStreamGivenStates;
     const unsigned split = per_pixel ? rc.split : 1u;
     const unsigned pitem = split > 1u ? item / split : item;         // pixel item of this lane
     if (!fresh && split > 1u) {
@@ -159,9 +161,10 @@ RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, un
     unsigned px, py;
     if (per_pixel) { unsigned pix = rc.item_pixel[split > 1u ? item / split : item]; px = pix % rc.W; py = pix / rc.W; }
     else { px = bx + cursor % bw; py = by + cursor / bw; }
+    SMP smp = SmpState<SMP>::begin(rc, rng, split > 1u ? item / split : item, s);
     // Path::from_sensor: uv = (ix + next(), iy + next())
-    float u = (float)px + rng_next_f32(rng);
-    float v = (float)py + rng_next_f32(rng);
+    float u = (float)px + smp_next(smp);
+    float v = (float)py + smp_next(smp);
     n_draws += 2;
     n_samples++;
     storec(ps, F_AR, acc);
@@ -170,7 +173,7 @@ RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, un
     const bool expand = (!rc.has_max || 1u < rc.max_depth);   // TechniquePathTracing::expand at depth 1
     if (!expand) {   // sensor not expanded: the sample is 0 (next raygen pass folds it)
         storec(ps, F_LR, czero());
-        store_rng(ps, Q_R0, rng);
+        smp_store(ps, smp);
         PU(U_FLAGS) = ST_REGEN;
         return;
     }
@@ -178,10 +181,10 @@ RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, un
     // the sensor edge's state is implied by PREV_SENSOR and never stored: origin = Camera::position(),
     // weight 1, rr_weight 1, PDF::SolidAngle(1), beta = thr = 1 (strategies/directional.rs:27-41)
     store3(ps, F_DX, d);
-    if (sc.medium.enabled) { PF(F_XI) = rng_next_f32(rng); n_draws++; }   // Edge::from_ray's medium.sample(ray, next())
-    store_rng(ps, Q_R0, rng);
+    if (sc.medium.enabled) { PF(F_XI) = smp_next(smp); n_draws++; }   // Edge::from_ray's medium.sample(ray, next())
+    smp_store(ps, smp);
     PU(U_DEPTH) = 1u;
-    PU(U_FLAGS) = ST_RAY | (PREV_SENSOR << ST_PREV_SHIFT) | ST_PDF_SA;
+    PU(U_FLAGS) = ST_RAY | (PREV_SENSOR << ST_PREV_SHIFT) | ST_PDF_SA | smp_flag_bits(smp);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -257,7 +260,8 @@ RL_DEV void shadow_slot_coop(const DeviceScene& sc, const SceneRecs& recs, const
 // DRAWS_ONLY (k_stream_chain, the first pass of reference-order streams): only what decides how the path goes on and how many
 // random numbers it takes — medium distance, surface point, BSDF / phase sample, Russian roulette — is evaluated, through the very
 // same statements as the full form; emission, MIS, light sampling (its four draws are skipped over) and the radiance fields are left out.
-template <int MAT, bool MEDIUM, int LIGHTS = LIGHTS_ANY, bool DRAWS_ONLY = false, class PS>
+// SMP: the sampler of the draws (sampler.hip.h; StratSampler: not with DRAWS_ONLY, its counters travel in U_FLAGS).
+template <int MAT, bool MEDIUM, int LIGHTS = LIGHTS_ANY, bool DRAWS_ONLY = false, class SMP = Rng, class PS>
 RL_DEV void shade_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, unsigned flags,
                        unsigned& n_vertices, unsigned& n_draws, unsigned& n_shadow, unsigned& n_ext) {
     n_ext += 1;      // every shaded slot carried exactly one extension ray through k_extend
@@ -286,6 +290,7 @@ RL_DEV void shade_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, uns
     }
     bool ended = false;
     unsigned new_flags = ST_REGEN;
+    unsigned smp_bits = 0u;
     if (!MEDIUM && !hit) {
         // edge without a next vertex: Edge::contribution = weight * rr * scene.enviroment_luminance(d) (edge.rs:201-210)
         ended = true;
@@ -359,12 +364,12 @@ RL_DEV void shade_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, uns
         const bool expand = (rc.has_max ? gen < rc.max_depth : true) && gen < kDepthCap;
         if (expand) {
             n_vertices += 1;
-            Rng rng = load_rng(ps, Q_R0);
+            SMP rng = SmpState<SMP>::load(rc, ps, flags);
             Col thr = primary ? cone() : loadc(ps, F_TR);
             const V3 vp = is_volume ? vpos : sp.p;
             const V3 d_in = -rd;
             // strategy 0: DirectionalSamplingStrategy::bounce (strategies/directional.rs:44-153)
-            V2 s2; s2.x = rng_next_f32(rng); s2.y = rng_next_f32(rng);
+            V2 s2 = smp_next2d(rng);
             n_draws += 2;
             bool has_edge = false;
             bool sampled = false;
@@ -388,14 +393,14 @@ RL_DEV void shade_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, uns
                     bool alive = true;
                     if (do_rr) {
                         float q = rmin(channel_max(thr), 0.95f);
-                        float x = rng_next_f32(rng);
+                        float x = smp_next(rng);
                         n_draws++;
                         if (q < x) alive = false; else rr_new = div_rn(1.0f, q);
                     }
                     if (alive) {
                         thr = scale_unguarded(thr, rr_new);
                         has_edge = true;
-                        if (MEDIUM) { PF(F_XI) = rng_next_f32(rng); n_draws++; }   // the new edge's medium.sample draw
+                        if (MEDIUM) { PF(F_XI) = smp_next(rng); n_draws++; }   // the new edge's medium.sample draw
                     }
                 }
             }
@@ -404,12 +409,12 @@ RL_DEV void shade_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, uns
             const bool smooth = !is_volume && mat->smooth;
             bool shadow = false;
             if (DRAWS_ONLY) {
-                if (use_light && !smooth) { rng_next_u64(rng); rng_next_u64(rng); rng_next_u64(rng); rng_next_u64(rng); n_draws += 4; }   // the light sample's four draws
+                if constexpr (std::is_same<SMP, Rng>::value) if (use_light && !smooth) { rng_next_u64(rng); rng_next_u64(rng); rng_next_u64(rng); rng_next_u64(rng); n_draws += 4; }   // the light sample's four draws
             } else
             if (use_light && !smooth) {
-                float a = rng_next_f32(rng);
-                float b = rng_next_f32(rng);
-                V2 c; c.x = rng_next_f32(rng); c.y = rng_next_f32(rng);
+                float a = smp_next(rng);
+                float b = smp_next(rng);
+                V2 c = smp_next2d(rng);
                 n_draws += 4;
                 n_shadow += 1;     // the reference always traces the shadow ray (emitters.rs:125-126)
                 LightSample ls = sample_light<LIGHTS>(sc, vp, !is_volume, is_volume ? mk3(0.0f, 0.0f, 0.0f) : sp.n_s, a, b, c);   // Some(&its.n_s) | None
@@ -453,7 +458,8 @@ RL_DEV void shade_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, uns
                     }
                 }
             }
-            store_rng(ps, Q_R0, rng);
+            smp_store(ps, rng);
+            smp_bits = smp_flag_bits(rng);
             store3(ps, F_OX, vp);
             new_flags = shadow ? ST_SHADOW : 0u;
             if (has_edge) {
@@ -474,7 +480,7 @@ RL_DEV void shade_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, uns
             storec(ps, F_LR, L);
         }
     }
-    PU(U_FLAGS) = new_flags;
+    PU(U_FLAGS) = new_flags | smp_bits;
 }
 
 }  // namespace rl

@@ -21,6 +21,10 @@ int rl_debug_trace_batch_two_level(rl_context* ctx, size_t n, const float* origi
 int rl_debug_check_two_level(const rl_scene* scene, uint64_t* out6);
 // rng_advance (kernels/rngjump.h) on the device: states_out[i] = sampler states_in[i] (4 x u64) after counts[i] more draws
 int rl_debug_rng_advance(int device, size_t n, const uint64_t* states_in, const uint32_t* counts, uint64_t* states_out);
+// the stratified sampler of RL_STREAM_STRATIFIED (sampler.hip.h) on the device: pixel p (its per-sample-mode seed pixel_seeds[p]) walks its spp samples as the
+// renderers do, each taking the call pattern (n_calls entries, 1 = next(), 2 = next2d()); out[(p * spp + s) * n_out + j] = the j-th value drawn by sample s,
+// n_out = sum of the pattern
+int rl_debug_stratified_draws(int device, size_t n_pixels, const uint64_t* pixel_seeds, uint32_t spp, int seed_variant, size_t n_calls, const int32_t* pattern, float* out);
 // host only: out[y * W + x] = 1 where every camera sample of the pixel takes exactly two draws (its rays cannot reach the scene's bounding box; k_stream_spec's shortcut)
 int rl_debug_trivial_pixels(const rl_scene* scene, int has_max_depth, uint32_t max_depth, uint8_t* out);
 int rl_debug_bvh_sizes(const rl_context* ctx, uint64_t* n_ref_nodes, uint64_t* n_prims, uint32_t* stack_depth, int* lds_scene);

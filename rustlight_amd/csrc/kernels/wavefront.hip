@@ -671,7 +671,8 @@ extern "C" int rl_render_path(rl_context* ctx, const rl_path_params* params, con
     if (n_blocks != nbx * nby) { rl_set_error("n_blocks does not match the image size"); return RL_ERR_INVALID_ARGUMENT; }
     if (params->spp == 0) { rl_set_error("spp must be > 0 (assert_ne!(scene.nb_samples, 0), mod.rs:410)"); return RL_ERR_INVALID_ARGUMENT; }
     if (params->strategy < 0 || params->strategy > 2) return RL_ERR_INVALID_ARGUMENT;
-    if (params->stream_mode != RL_STREAM_REFERENCE_ORDER && params->stream_mode != RL_STREAM_PER_SAMPLE) return RL_ERR_INVALID_ARGUMENT;
+    if (params->stream_mode < RL_STREAM_REFERENCE_ORDER || params->stream_mode > RL_STREAM_STRATIFIED) { rl_set_error("stream_mode must be 0 (reference order), 1 (per sample) or 2 (stratified)"); return RL_ERR_INVALID_ARGUMENT; }
+    if (params->stream_mode == RL_STREAM_STRATIFIED && params->spp > (1u << 30)) { rl_set_error("the stratified sampler takes at most 2^30 spp"); return RL_ERR_INVALID_ARGUMENT; }
     if (params->numerics > RL_NUMERICS_FAST) { rl_set_error("numerics must be 0 (exact) or 1 (fast)"); return RL_ERR_INVALID_ARGUMENT; }
     const uint32_t shard_count = params->shard_count ? params->shard_count : 1;
     if (params->shard_index >= shard_count) return RL_ERR_INVALID_ARGUMENT;
@@ -731,7 +732,8 @@ static int render_mc(rl_context* ctx, int kind, const rl_mc_params* params, cons
     const uint32_t W = ctx->width, H = ctx->height;
     const size_t nbx = (W + 15) / 16, nby = (H + 15) / 16;
     if (n_blocks != nbx * nby || params->spp == 0) return RL_ERR_INVALID_ARGUMENT;
-    if (params->stream_mode != RL_STREAM_REFERENCE_ORDER && params->stream_mode != RL_STREAM_PER_SAMPLE) return RL_ERR_INVALID_ARGUMENT;
+    if (params->stream_mode < RL_STREAM_REFERENCE_ORDER || params->stream_mode > RL_STREAM_STRATIFIED) { rl_set_error("stream_mode must be 0 (reference order), 1 (per sample) or 2 (stratified)"); return RL_ERR_INVALID_ARGUMENT; }
+    if (params->stream_mode == RL_STREAM_STRATIFIED && params->spp > (1u << 30)) { rl_set_error("the stratified sampler takes at most 2^30 spp"); return RL_ERR_INVALID_ARGUMENT; }
     const uint32_t shard_count = params->shard_count ? params->shard_count : 1;
     if (params->shard_index >= shard_count) return RL_ERR_INVALID_ARGUMENT;
     if (kind == 1 && params->nb_light_samples > 0 && ctx->ds.n_emitters == 0) { rl_set_error("light sampling requested but the scene has no emitter"); return RL_ERR_NO_EMITTER; }
@@ -747,7 +749,8 @@ static int render_mc(rl_context* ctx, int kind, const rl_mc_params* params, cons
         item_base.push_back(n_pixels);
         n_pixels += std::min(16u, W - bx) * std::min(16u, H - by);
     }
-    const bool per_sample = params->stream_mode == RL_STREAM_PER_SAMPLE;
+    const bool strat = params->stream_mode == RL_STREAM_STRATIFIED;
+    const bool per_sample = params->stream_mode == RL_STREAM_PER_SAMPLE || strat;      // (stratified: per-pixel items, the pixel seeds k_seed_pixels writes)
     // reference-order streams in two passes, as for `path` (chain.hip.h): k_mc_chain records where every camera sample starts in its block's stream (a sample's
     // draw count follows from its camera ray alone), then the per-pixel form evaluates all samples from those states.  One chunk: when the states do not fit
     // their budget the single-pass walk (one lane per block) runs instead, as it does under RL_REF_SINGLE_PASS.
@@ -818,7 +821,7 @@ static int render_mc(rl_context* ctx, int kind, const rl_mc_params* params, cons
         rc.stream_mode = kStreamGivenStates;
     }
     if (timing) hipEventRecord(ctx->events[2], st);
-    launch_pixel_mc(kind, ctx->lds_scene, grid, block, lds, st, rc, ctx->ds, stc, mp);
+    (strat ? launch_pixel_mc_strat : launch_pixel_mc)(kind, ctx->lds_scene, grid, block, lds, st, rc, ctx->ds, stc, mp);
     if (timing) hipEventRecord(ctx->events[3], st);
     if (!out_is_device) HIP_OK(hipMemcpyAsync(out_rgb, d_out, (size_t)3 * W * H * sizeof(float), hipMemcpyDeviceToHost, st));
     std::vector<unsigned long long> partials(n_rows * STAT_COUNT);
