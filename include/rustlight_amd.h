@@ -344,6 +344,20 @@ int rl_render_path(rl_context* ctx, const rl_path_params* params, const uint64_t
                    size_t n_blocks, float* out_rgb, int out_is_device, void* stream,
                    rl_render_stats* stats);
 
+/* Integrator::compute for IntegratorLightTracing (src/integrators/explicit/light.rs, CLI `light-tracing`): spp * W * H light paths from the emitters, every
+ * vertex splatted through the camera (Camera::sample_direct).  Takes rl_path_params: spp, the three depth options, `strategy` as rl_light_strategy, `seed_variant`;
+ * `block_seeds` as for rl_render_path.  Job b (the 16x16 blocks in creation order) traces spp x (pixels of block b) light paths; light path (b, slot p, sample s)
+ * draws from the stream RL_STREAM_PER_SAMPLE gives camera sample (b, pixel p, s).  The reference splits its paths over 4 x threads jobs, so no seed matches it
+ * path for path: the image agrees in distribution.  Splats are summed in signed 64-bit fixed point (24 fraction bits): same seeds, same bits.  A splat with a
+ * negative or NaN channel is dropped (Color::is_valid); a +inf channel makes the pixel's channel +inf; a channel >= 2^31 is clamped.  RL_ERR_UNSUPPORTED for
+ * stream_mode other than RL_STREAM_PER_SAMPLE, numerics = RL_NUMERICS_FAST, shard_count > 1 and scenes with an environment emitter; RL_ERR_NO_EMITTER without
+ * emitters.  The counters mean: camera_samples = light paths traced, vertices = expanded vertices (the light vertex included), extension_rays = closest-hit rays,
+ * shadow_rays = camera-connection visibility rays, rng_draws, kernel_launches; ms_other = k_light_fused's device time; reserved[0] = splats added,
+ * reserved[1] = splats dropped as invalid, reserved[2] = splats with a saturated (clamped or +inf) channel. */
+typedef enum rl_light_strategy { RL_LIGHT_ALL = 0, RL_LIGHT_SURFACE = 1, RL_LIGHT_VOLUME = 2 } rl_light_strategy;
+int rl_render_light(rl_context* ctx, const rl_path_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
+                    int out_is_device, void* stream, rl_render_stats* stats);
+
 /* Frames in flight behind one call (the progressive wrappers' passes, avg.rs:5-131 / equal_time.rs:4-66: N independent renders of one scene): frame f — block
  * seeds `block_seeds[f]`, host image `out_rgb[f]` (W*H*3 f32) — renders on `ctxs[f % k]` from host thread f % k, k = min(n_ctx, n_frames); `ctxs` are distinct
  * contexts of the same scene.  Returns when every frame is done; the images (and `stats[f]`, if not NULL) are those of `n_frames` rl_render_path calls one after

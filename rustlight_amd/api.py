@@ -26,6 +26,8 @@ STRATEGY_ALL, STRATEGY_BSDF, STRATEGY_EMITTER = 0, 1, 2
 STREAM_REFERENCE_ORDER, STREAM_PER_SAMPLE, STREAM_STRATIFIED = 0, 1, 2      # rl_stream_mode; STRATIFIED: rustlight's StratifiedSampler (`-r stratified`)
 PIPELINE_AUTO, PIPELINE_WAVEFRONT, PIPELINE_FUSED = 0, 1, 2
 NUMERICS_EXACT, NUMERICS_FAST = 0, 1
+LIGHT_ALL, LIGHT_SURFACE, LIGHT_VOLUME = 0, 1, 2          # rl_light_strategy: `light-tracing -s all|surface|volume`
+RL_ERR_UNSUPPORTED, RL_ERR_NO_EMITTER = -7, -8
 
 # every symbol include/rustlight_amd.h declares (tests check the .so exports all of them)
 PUBLIC_SYMBOLS = [
@@ -34,7 +36,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -103,6 +105,7 @@ def lib():
     L.rl_generate_block_seeds.argtypes = [C.POINTER(abi.Sampler), C.c_uint32, C.c_uint32, u64p, C.c_size_t]
     L.rl_render_path.argtypes = [vp, C.POINTER(abi.PathParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_render_path_frames.argtypes = [C.POINTER(vp), C.c_size_t, C.POINTER(abi.PathParams), C.POINTER(u64p), C.c_size_t, C.c_size_t, C.POINTER(C.POINTER(C.c_float)), C.POINTER(abi.RenderStats)]
+    L.rl_render_light.argtypes = [vp, C.POINTER(abi.PathParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     for fn in (L.rl_render_ao, L.rl_render_direct):
         fn.argtypes = [vp, C.POINTER(abi.McParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_multi_create.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -455,6 +458,20 @@ class Context:
         """IntegratorDirect { nb_bsdf_samples, nb_light_samples } (src/integrators/direct.rs)."""
         return self._render_mc(lib().rl_render_direct, seeds, **kw)
 
+    def render_light(self, seeds, spp=1, min_depth=0, max_depth=None, rr_depth=0, strategy=LIGHT_ALL, seed_variant=0, stream_mode=STREAM_PER_SAMPLE,
+                     numerics=NUMERICS_EXACT, shard_count=1):
+        """IntegratorLightTracing (src/integrators/explicit/light.rs) through rl_render_light: (image HxWx3 f32, stats dict).  stats: camera_samples = light
+        paths, shadow_rays = camera connections, reserved[0..2] = splats added / dropped as invalid / saturated.  stream_mode, numerics and shard_count only
+        take the values the C ABI accepts (anything else is RL_ERR_UNSUPPORTED)."""
+        p = path_params(spp, min_depth, max_depth, rr_depth, strategy, False, stream_mode, seed_variant, shard_count=shard_count, numerics=numerics)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        st = abi.RenderStats()
+        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        _check(lib().rl_render_light(self.h, C.byref(p), abi.u64ptr(seeds), seeds.shape[0], img.ctypes.data_as(C.c_void_p), 0, None, C.byref(st)))
+        d = st.as_dict()
+        d["splats"], d["splats_invalid"], d["splats_saturated"] = (int(v) for v in st.reserved[:3])
+        return img, d
+
     def trace(self, origins, directions):
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
@@ -625,6 +642,29 @@ class IntegratorPathTracing:
         if out:
             self.last_stats = out[-1][1]
         return [img for img, _ in out]
+
+
+class IntegratorLightTracing:
+    """struct IntegratorLightTracing (src/integrators/explicit/light.rs:7-13) + Integrator::compute: light paths splatted through the camera, on the
+    per-sample streams (rl_render_light).  strategy: LIGHT_ALL / LIGHT_SURFACE / LIGHT_VOLUME (render_surface / render_volume)."""
+
+    def __init__(self, min_depth=0, max_depth=None, rr_depth=0, strategy=LIGHT_ALL, device=0, options=None):
+        self.min_depth, self.max_depth, self.rr_depth, self.strategy = min_depth, max_depth, rr_depth, strategy
+        self.device = device
+        self.options = dict(options or {})
+        self.last_stats = None
+        self._ctx = None
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        """The block seeds are drawn from the master sampler as IntegratorPathTracing.compute draws them."""
+        if self._ctx is None or self._ctx.scene is not scene:
+            self._ctx = Context(scene, self.device)
+            for k, v in self.options.items():
+                self._ctx.set_option(k, v)
+        w, h = scene.size
+        seeds = sampler.block_seeds(w, h)
+        img, self.last_stats = self._ctx.render_light(seeds, nb_samples, self.min_depth, self.max_depth, self.rr_depth, self.strategy, sampler.variant)
+        return img
 
 
 def render_frames(contexts, seeds_list, params: abi.PathParams):

@@ -5,6 +5,7 @@
 //                 path [-m MAX|inf] [-n MIN] [-r RR|inf] [-x] [-s all|bsdf|emitter]
 //               | ao [-d DIST|inf] [-n]            (examples/cli.rs:149-154)
 //               | direct [-b NB_BSDF] [-l NB_LIGHT] (examples/cli.rs:155-160)
+//               | light-tracing [-m MAX|inf] [-n MIN] [-r RR|inf] [-s all|surface|volume]   (examples/cli.rs:54-61, 170-174; per-sample streams)
 // Note `-n` / `-m` / `-r` / `-s` mean spp / medium / sampler / scale before the subcommand and
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 #include <chrono>
@@ -48,7 +49,7 @@ int main(int argc, char** argv) {
         std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
         if (!have_cmd) {
-            if (a == "path" || a == "ao" || a == "direct") { have_cmd = true; cmd = a; }
+            if (a == "path" || a == "ao" || a == "direct" || a == "light-tracing") { have_cmd = true; cmd = a; }
             else if (a == "-n" || a == "--nbsamples") nbsamples = std::strtoull(val().c_str(), nullptr, 10);
             else if (a == "-o" || a == "--output") output = val();
             else if (a == "-r" || a == "--random-number-generator") rng = val();
@@ -78,7 +79,7 @@ int main(int argc, char** argv) {
             else if (a == "-l" || a == "--log") (void)val();   // log file: nothing is logged on this path
             else if (a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
             else if (scene_path.empty()) scene_path = a;
-            else { std::fprintf(stderr, "only the `path`, `ao` and `direct` subcommands are provided (got %s)\n", a.c_str()); return 2; }
+            else { std::fprintf(stderr, "only the `path`, `ao`, `direct` and `light-tracing` subcommands are provided (got %s)\n", a.c_str()); return 2; }
         } else if (cmd == "ao") {
             if (a == "-d" || a == "--distance") ao_distance = val();
             else if (a == "-n" || a == "--normal-correction") ao_normal_correction = true;
@@ -87,6 +88,12 @@ int main(int argc, char** argv) {
             if (a == "-b" || a == "--nb-bsdf-samples") nb_bsdf = std::strtoull(val().c_str(), nullptr, 10);
             else if (a == "-l" || a == "--nb-light-samples") nb_light = std::strtoull(val().c_str(), nullptr, 10);
             else { std::fprintf(stderr, "unknown direct option %s\n", a.c_str()); return 2; }
+        } else if (cmd == "light-tracing") {
+            if (a == "-m" || a == "--max-depth") max_depth = val();
+            else if (a == "-n" || a == "--min-depth") min_depth = val();
+            else if (a == "-r" || a == "--rr-depth") rr_depth = val();
+            else if (a == "-s" || a == "--strategy") strategy = val();
+            else { std::fprintf(stderr, "unknown light-tracing option %s\n", a.c_str()); return 2; }
         } else {
             if (a == "-m" || a == "--max-depth") max_depth = val();
             else if (a == "-n" || a == "--min-depth") min_depth = val();
@@ -99,6 +106,23 @@ int main(int argc, char** argv) {
     if (scene_path.empty() || output.empty() || !have_cmd) {
         std::fprintf(stderr, "usage: rustlight-amd <scene.pbrt|scene.xml> -n SPP -o out.pfm [-r independent[:SEED]|stratified[:SEED]] [-m s[:a[:g]]] path [-m max] [-n min] [-r rr] [-x] [-s all|bsdf|emitter]\n");
         return 2;
+    }
+    // light-tracing runs on per-sample streams, exact numerics, one device: what it cannot do is refused here, before a device is opened
+    IntegratorLightTracing light;
+    if (cmd == "light-tracing") {
+        if (rng == "stratified" || rng.rfind("stratified:", 0) == 0) { std::fprintf(stderr, "light-tracing: -r stratified is not supported (independent[:SEED] only)\n"); return 2; }
+        if (mode_given && mode != RL_STREAM_PER_SAMPLE) { std::fprintf(stderr, "light-tracing: --stream-mode reference is not supported (light paths use per-sample streams)\n"); return 2; }
+        if (numerics == RL_NUMERICS_FAST) { std::fprintf(stderr, "light-tracing: --numerics fast is not supported\n"); return 2; }
+        if (gpus > 1) { std::fprintf(stderr, "light-tracing: --gpus > 1 is not supported\n"); return 2; }
+        if (strategy == "all") light.strategy = RL_LIGHT_ALL;
+        else if (strategy == "surface") light.strategy = RL_LIGHT_SURFACE;
+        else if (strategy == "volume") light.strategy = RL_LIGHT_VOLUME;
+        else { std::fprintf(stderr, "invalid light-tracing strategy: %s (all, surface or volume)\n", strategy.c_str()); return 2; }
+        light.max_depth = match_infinity(max_depth);
+        light.min_depth = match_infinity(min_depth);
+        light.rr_depth = match_infinity(rr_depth);
+        light.device = device;
+        light.options = options;
     }
     // the sampler (cli.rs:876-896): the master sampler that draws the block seeds is IndependentSampler(SEED) for both kinds — OS entropy without a seed, as
     // IndependentSampler::default() / StratifiedSampler's random() are; `stratified:SEED` is this drop-in's reproducible form.  stratified =
@@ -160,6 +184,7 @@ int main(int argc, char** argv) {
         }
         scene->build_emitters(use_ats);      // scene.build_emitters(use_ats) (cli.rs:432)
         IntegratorPathTracing integrator;
+        if (cmd == "light-tracing") strategy = "all";       // (the path integrator below is not used)
         integrator.min_depth = match_infinity(min_depth);
         integrator.max_depth = match_infinity(max_depth);
         integrator.rr_depth = match_infinity(rr_depth);
@@ -186,6 +211,17 @@ int main(int argc, char** argv) {
             IntegratorDirect di;
             di.device = device; di.stream_mode = mode; di.nb_bsdf_samples = nb_bsdf; di.nb_light_samples = nb_light;
             img = di.compute(sampler, *scene); elapsed_ms = di.last_stats.render_ms;
+        } else if (cmd == "light-tracing") {
+            if (!equal_time.empty()) {
+                IntegratorEqualTime<IntegratorLightTracing> eq{light, std::strtod(equal_time.c_str(), nullptr) * 1000.0};
+                img = eq.compute(sampler, *scene);
+                std::fprintf(stderr, "INFO Number iter: %zu\nINFO Number spp: %zu\n", eq.iterations, eq.iterations * scene->nb_samples);
+            } else if (!average.empty()) {
+                IntegratorAverage<IntegratorLightTracing> av{light, std::nullopt, true};
+                if (average != "inf") av.time_out = (size_t)std::strtoull(average.c_str(), nullptr, 10);
+                img = av.compute(sampler, *scene);
+            } else img = light.compute(sampler, *scene);
+            elapsed_ms = light.last_stats.render_ms;
         } else if (!equal_time.empty()) {        // cli.rs:898-907
             IntegratorEqualTime<IntegratorPathTracing> eq{integrator, std::strtod(equal_time.c_str(), nullptr) * 1000.0};
             img = eq.compute(sampler, *scene); elapsed_ms = integrator.last_stats.render_ms;

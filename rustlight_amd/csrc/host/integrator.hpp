@@ -251,6 +251,40 @@ struct IntegratorDirect : IntegratorMC {
     }
 };
 
+// struct IntegratorLightTracing (src/integrators/explicit/light.rs:7-13): light paths splatted through the camera, on per-sample streams (rl_render_light)
+struct IntegratorLightTracing {
+    std::optional<uint32_t> max_depth, min_depth, rr_depth;
+    rl_light_strategy strategy = RL_LIGHT_ALL;     // all | surface | volume: render_surface / render_volume
+    int device = 0;
+    std::vector<std::pair<std::string, std::string>> options;
+    rl_render_stats last_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        rl_context* ctx = nullptr;
+        int rc = rl_context_create(scene.handle, device, &ctx);
+        if (rc != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
+        for (const auto& o : options)
+            if (rl_context_set_option(ctx, o.first.c_str(), o.second.c_str()) != RL_OK) { const std::string e = rl_last_error(); rl_context_destroy(ctx); throw std::runtime_error("--option " + o.first + ": " + e); }
+        BufferCollection img;
+        rl_scene_image_size(scene.handle, &img.width, &img.height);
+        img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
+        rl_path_params p;
+        rl_path_params_default(&p);
+        p.spp = (uint32_t)scene.nb_samples;
+        p.has_min_depth = min_depth.has_value(); p.min_depth = min_depth.value_or(0);
+        p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
+        p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
+        p.strategy = strategy;
+        p.stream_mode = RL_STREAM_PER_SAMPLE;
+        p.seed_variant = sampler.variant;
+        std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
+        rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
+        rc = rl_render_light(ctx, &p, seeds.data(), seeds.size(), img.primal.data(), 0, nullptr, &last_stats);
+        rl_context_destroy(ctx);
+        if (rc != RL_OK) throw std::runtime_error(std::string("render: ") + rl_last_error());
+        return img;
+    }
+};
+
 // IntegratorAverage (src/integrators/avg.rs:5-131) and IntegratorEqualTime (src/integrators/equal_time.rs:4-66):
 // host loops around any inner integrator with `compute(IndependentSampler&, Scene&)`.
 template <class T, class = void> struct has_frames_in_flight : std::false_type {};

@@ -116,12 +116,11 @@ using namespace rl;
 
 // Camera::new (src/camera.rs:31-67)
 bool rl_scene::rebuild_camera() {
-    Mat4 to_local;
     if (!to_world.inverse(&to_local)) return false;
     const float x_v = flip ? 1.0f : -1.0f;
     const float aspect = (float)width / (float)height;
     const float fov_rad = fov_axis == 0 ? fov_degrees * kPi / 180.0f : fov_degrees * aspect * kPi / 180.0f;
-    Mat4 camera_to_sample = Mat4::scale(-0.5f, -0.5f * aspect, 1.0f)
+    camera_to_sample = Mat4::scale(-0.5f, -0.5f * aspect, 1.0f)
                                 .times(Mat4::translate(-1.0f, -1.0f / aspect, 0.0f))
                                 .times(perspective(fov_rad, 1.0f, 1e-2f, 1000.0f))
                                 .times(Mat4::scale(x_v, 1.0f, -1.0f));
@@ -158,6 +157,9 @@ int rl_scene_set_camera_matrices(rl_scene* scene, uint32_t width, uint32_t heigh
     scene->fov_degrees = 0.0f; scene->fov_axis = 0; scene->flip = false;       // (not derived from: the matrices are authoritative)
     scene->to_world = Mat4::from_cols(to_world);
     scene->sample_to_camera = Mat4::from_cols(sample_to_camera);
+    // the light tracer's inverses (camera.rs:5-15); a singular matrix leaves them zero: no splat lands then
+    if (!scene->sample_to_camera.inverse(&scene->camera_to_sample)) scene->camera_to_sample = Mat4{};
+    if (!scene->to_world.inverse(&scene->to_local)) scene->to_local = Mat4{};
     scene->cam_pos = scene->to_world.xform_point({0.0f, 0.0f, 0.0f});   // Camera::position (camera.rs:140-142)
     scene->has_camera = true;
     return RL_OK;

@@ -43,6 +43,7 @@ struct rl_scene {
     int fov_axis = 1;
     bool flip = false;
     rl::Mat4 to_world, sample_to_camera;
+    rl::Mat4 camera_to_sample, to_local;     // the inverses Camera keeps for sample_direct (camera.rs:5-15): the light tracer
     rl::Vec3 cam_pos{0, 0, 0};
     // geometry
     std::vector<rl::HostMesh> meshes;

@@ -10,6 +10,17 @@ struct McConst {
     unsigned nb_bsdf_samples, nb_light_samples;
 };
 
+// IntegratorLightTracing (light.rs): what the light kernel needs beyond RenderConst / DeviceScene — the camera's inverse matrices and image
+// rectangle (camera.rs:5-15, 54-58), kept out of DeviceScene so that no other kernel's argument block changes, and the fixed-point splat image.
+struct LightConst {
+    float camera_to_sample[16];         // column-major, as CameraRecord
+    float to_local[16];
+    float rect_min[2], rect_max[2];     // image_rect_min / image_rect_max
+    int render_surface, render_volume;  // strategy all | surface | volume
+    long long* accum;                   // W*H*3 signed fixed-point sums (light.hip.h: kLightFixBits)
+    unsigned* inf_flags;                // W*H: bit c = channel c received a +inf splat
+};
+
 // mat: the scene's one BSDF type, or -1 = run-time switch per vertex.  area_only: every emitter is a mesh area light and there is no light
 // tree (the NEE code of the other emitter kinds is compiled out: same results, 84 -> 21 spilled VGPRs on the diffuse Cornell box)
 void launch_fused_lds(int mat, bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc);
@@ -41,6 +52,10 @@ void launch_shade_sorted_strat(bool medium, unsigned chunks, dim3 grid, dim3 blo
 void launch_pixel_mc_strat(int kind, bool lds_scene, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const McConst& mp);
 void launch_pixel_mc(int kind, bool lds_scene, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const McConst& mp);
 void launch_mc_chain(int kind, bool lds_scene, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const McConst& mp);   // first pass of reference-order streams for ao / direct
+// IntegratorLightTracing (light.hip.h): k_light_fused over the light-path slots (mat as for launch_fused_*), k_light_resolve turns the fixed-point sums into the f32 image
+void launch_light_lds(int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const LightConst& lc);
+void launch_light_stream(int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const LightConst& lc);
+void launch_light_resolve(dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const LightConst& lc);
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)
 void dump_stage_timers_stream();
 void dump_chain_timers_lds();      // dev-only (-DRL_STAGE_TIMERS): cycle shares of k_stream_chain's stages

@@ -44,6 +44,7 @@
 #include "../host/scene.h"
 #include "wavefront.h"
 #include "knobs.h"
+#include "light.hip.h"     // STAT_SPLATS*: the statistics slots of k_light_fused (the kernel itself is instantiated by light_*.hip)
 
 namespace rl {
 
@@ -314,6 +315,7 @@ struct rl_context {
     unsigned queue_seq = 0;
     BvhBuild bvh_dump;                // kept for rl_debug_bvh and for the two-level records (built on first use)
     Knobs knobs;                      // execution options: the environment as rl_context_create found it, then rl_context_set_option (knobs.h)
+    LightConst light_cam{};           // rl_render_light: the camera's inverses and image rectangle (the splat buffers are set per render)
 };
 
 template <typename T>
@@ -440,6 +442,14 @@ extern "C" int rl_context_create(const rl_scene* scene, int device, rl_context**
         scene->to_world.to_cols(ds.camera.to_world);
         ds.camera.position[0] = scene->cam_pos.x; ds.camera.position[1] = scene->cam_pos.y; ds.camera.position[2] = scene->cam_pos.z;
         ds.camera.width = scene->width; ds.camera.height = scene->height;
+        {   // Camera::new's image rectangle in sample space (camera.rs:54-58), for the light tracer
+            scene->camera_to_sample.to_cols(ctx->light_cam.camera_to_sample);
+            scene->to_local.to_cols(ctx->light_cam.to_local);
+            const Vec3 p0 = scene->sample_to_camera.xform_point({0.0f, 0.0f, 0.0f}), p1 = scene->sample_to_camera.xform_point({1.0f, 1.0f, 0.0f});
+            const float zmin = std::fmin(p0.z, p1.z), zmax = std::fmax(p0.z, p1.z);
+            ctx->light_cam.rect_min[0] = std::fmin(p0.x, p1.x) / zmin; ctx->light_cam.rect_min[1] = std::fmin(p0.y, p1.y) / zmin;
+            ctx->light_cam.rect_max[0] = std::fmax(p0.x, p1.x) / zmax; ctx->light_cam.rect_max[1] = std::fmax(p0.y, p1.y) / zmax;
+        }
         ds.medium = scene->medium;
         ctx->area_lights_only = scene->ats_root < 0 && !ctx->knobs.has(K_GENERIC_LIGHTS);
         for (const EmitterRecord& e : scene->emitters) if (e.kind != EMITTER_MESH) ctx->area_lights_only = false;
@@ -849,6 +859,116 @@ extern "C" int rl_render_ao(rl_context* ctx, const rl_mc_params* params, const u
                             void* stream, rl_render_stats* stats) { return render_mc(ctx, 0, params, block_seeds, n_blocks, out_rgb, out_is_device, stream, stats); }
 extern "C" int rl_render_direct(rl_context* ctx, const rl_mc_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, int out_is_device,
                                 void* stream, rl_render_stats* stats) { return render_mc(ctx, 1, params, block_seeds, n_blocks, out_rgb, out_is_device, stream, stats); }
+
+// ---- IntegratorLightTracing::compute (light.rs:219-300) through the per-sample streams: k_seed_pixels forks one stream per light-path slot, k_light_fused
+// traces spp light paths per slot and splats them into the fixed-point image, k_light_resolve writes the f32 image (light.hip.h).
+extern "C" int rl_render_light(rl_context* ctx, const rl_path_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
+                               int out_is_device, void* stream_arg, rl_render_stats* stats) {
+    if (!ctx || !params || !block_seeds || !out_rgb) return RL_ERR_INVALID_ARGUMENT;
+    const uint32_t W = ctx->width, H = ctx->height;
+    const size_t nbx = (W + 15) / 16, nby = (H + 15) / 16;
+    if (n_blocks != nbx * nby) { rl_set_error("n_blocks does not match the image size"); return RL_ERR_INVALID_ARGUMENT; }
+    if (params->spp == 0) { rl_set_error("spp must be > 0"); return RL_ERR_INVALID_ARGUMENT; }
+    if (params->strategy < RL_LIGHT_ALL || params->strategy > RL_LIGHT_VOLUME) { rl_set_error("strategy must be RL_LIGHT_ALL, RL_LIGHT_SURFACE or RL_LIGHT_VOLUME"); return RL_ERR_INVALID_ARGUMENT; }
+    if (params->stream_mode != RL_STREAM_PER_SAMPLE) { rl_set_error("the light tracer runs on per-sample streams only (stream_mode = RL_STREAM_PER_SAMPLE)"); return RL_ERR_UNSUPPORTED; }
+    if (params->numerics != RL_NUMERICS_EXACT) { rl_set_error("the light tracer has no tolerance build (numerics = RL_NUMERICS_EXACT only)"); return RL_ERR_UNSUPPORTED; }
+    if (params->shard_count > 1) { rl_set_error("the light tracer renders on one device (shard_count <= 1): every light path may splat anywhere"); return RL_ERR_UNSUPPORTED; }
+    if (ctx->ds.env_emitter >= 0) { rl_set_error("the light tracer does not sample environment emitters"); return RL_ERR_UNSUPPORTED; }
+    if (ctx->ds.n_emitters == 0) { rl_set_error("the light tracer needs an emitter"); return RL_ERR_NO_EMITTER; }
+    if ((size_t)W * H > 0x7fffff00u) { rl_set_error("image too large"); return RL_ERR_INVALID_ARGUMENT; }
+    HIP_OK(hipSetDevice(ctx->device));
+    hipStream_t st = stream_arg ? (hipStream_t)stream_arg : ctx->stream;
+    auto t_start = std::chrono::steady_clock::now();
+    std::vector<unsigned> owned, item_base;
+    unsigned n_items = 0;
+    for (size_t b = 0; b < n_blocks; b++) {
+        const unsigned bx = (unsigned)(b / nby) * 16u, by = (unsigned)(b % nby) * 16u;
+        owned.push_back((unsigned)b);
+        item_base.push_back(n_items);
+        n_items += std::min(16u, W - bx) * std::min(16u, H - by);
+    }
+    const size_t n_pix = (size_t)W * H;
+    int rcode;
+    if ((rcode = ensure(&ctx->d_owned, &ctx->owned_capacity, owned.size())) != RL_OK) return rcode;
+    if ((rcode = ensure(&ctx->d_item_base, &ctx->item_base_capacity, owned.size())) != RL_OK) return rcode;
+    if ((rcode = ensure(&ctx->d_block_seeds, &ctx->seeds_capacity, n_blocks)) != RL_OK) return rcode;
+    if ((rcode = ensure(&ctx->d_item_seed, &ctx->item_capacity, n_items)) != RL_OK) return rcode;
+    if ((rcode = ensure(&ctx->d_item_pixel, &ctx->item_pixel_capacity, n_items)) != RL_OK) return rcode;
+    // the splat image: [W*H*3] i64 sums, then [W*H] u32 inf flags — in the sample-state buffer of reference-order streams, which this call does not use
+    const size_t acc_words = (3 * n_pix + (n_pix + 1) / 2 + 3) / 4;     // in units of the buffer's 4 x u64 entries
+    if ((rcode = ensure(&ctx->d_sample_states, &ctx->sample_states_capacity, acc_words * 4)) != RL_OK) return rcode;
+    float* d_out = out_rgb;
+    if (!out_is_device) {
+        if ((rcode = ensure(&ctx->d_out, &ctx->out_capacity, 3 * n_pix)) != RL_OK) return rcode;
+        d_out = ctx->d_out;
+    }
+    // lanes per light-path slot: small frames get several (each tracing every split-th sample of the slot), so that about two rounds of the chip's resident waves run
+    int cus = 256;
+    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    const size_t want_lanes = (size_t)std::max(cus, 1) * kLightWaves * 4 * 64 * 2;
+    unsigned split = 1;
+    while (split * 2 <= params->spp && (size_t)n_items * split < want_lanes && (size_t)n_items * split * 2 <= 0x7fffff00u) split *= 2;
+    const unsigned n_threads = std::max(256u, (unsigned)(((size_t)n_items * split + 255u) / 256u * 256u));
+    const size_t n_rows = n_threads / 256;
+    if ((rcode = ensure(&ctx->d_partials, &ctx->partials_capacity, n_rows * STAT_COUNT)) != RL_OK) return rcode;
+    LightConst lc = ctx->light_cam;
+    lc.render_surface = params->strategy != RL_LIGHT_VOLUME;
+    lc.render_volume = params->strategy != RL_LIGHT_SURFACE;
+    lc.accum = reinterpret_cast<long long*>(ctx->d_sample_states);
+    lc.inf_flags = reinterpret_cast<unsigned*>(lc.accum + 3 * n_pix);
+    HIP_OK(hipMemcpyAsync(ctx->d_owned, owned.data(), owned.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(ctx->d_item_base, item_base.data(), item_base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(ctx->d_block_seeds, block_seeds, n_blocks * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(ctx->d_sample_states, 0, acc_words * 4 * sizeof(unsigned long long), st));
+    HIP_OK(hipMemsetAsync(ctx->d_partials, 0, n_rows * STAT_COUNT * sizeof(unsigned long long), st));
+    RenderConst rc{};
+    rc.spp = params->spp;
+    rc.has_min = params->has_min_depth; rc.min_depth = params->min_depth;
+    rc.has_max = params->has_max_depth; rc.max_depth = params->max_depth;
+    rc.has_rr = params->has_rr_depth; rc.rr_depth = params->rr_depth;
+    rc.stream_mode = RL_STREAM_PER_SAMPLE; rc.seed_variant = params->seed_variant;
+    rc.inv_spp = 1.0f / (float)params->spp;
+    rc.W = W; rc.H = H; rc.nby = (unsigned)nby;
+    rc.n_items = n_items;
+    rc.split = split;
+    rc.owned_blocks = ctx->d_owned; rc.block_item_base = ctx->d_item_base; rc.n_owned = (unsigned)owned.size();
+    rc.block_seeds = ctx->d_block_seeds;
+    rc.item_seed = ctx->d_item_seed; rc.item_pixel = ctx->d_item_pixel;
+    rc.out = d_out;
+    rc.counters = ctx->d_counters;
+    rc.partials = ctx->d_partials;
+    StackConf stc;
+    if ((rcode = stack_conf(ctx, n_threads, &stc)) != RL_OK) return rcode;
+    const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
+    const bool timing = stats != nullptr && !ctx->knobs.has(K_NO_EVENTS);
+    while (timing && ctx->events.size() < 4) { hipEvent_t ev; HIP_OK(hipEventCreate(&ev)); ctx->events.push_back(ev); }
+    hipLaunchKernelGGL(k_seed_pixels, dim3(((unsigned)owned.size() + 63) / 64), dim3(64), 0, st, rc);
+    if (timing) hipEventRecord(ctx->events[2], st);
+    (ctx->lds_scene ? launch_light_lds : launch_light_stream)(ctx->single_bsdf ? ctx->bsdf_type : -1, ctx->ds.medium.enabled != 0, dim3(n_threads / 256), dim3(256), lds, st, rc, ctx->ds, stc, lc);
+    if (timing) hipEventRecord(ctx->events[3], st);
+    launch_light_resolve(dim3((unsigned)((n_pix + 255) / 256)), dim3(256), st, rc, lc);
+    if (!out_is_device) HIP_OK(hipMemcpyAsync(out_rgb, d_out, 3 * n_pix * sizeof(float), hipMemcpyDeviceToHost, st));
+    std::vector<unsigned long long> partials(n_rows * STAT_COUNT);
+    HIP_OK(hipMemcpyAsync(partials.data(), ctx->d_partials, partials.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        unsigned long long totals[STAT_COUNT] = {0};
+        for (size_t r = 0; r < n_rows; r++) for (int k = 0; k < STAT_COUNT; k++) totals[k] += partials[r * STAT_COUNT + k];
+        stats->camera_samples = totals[STAT_SAMPLES]; stats->vertices = totals[STAT_VERTICES]; stats->extension_rays = totals[STAT_EXT_RAYS];
+        stats->shadow_rays = totals[STAT_SHADOW_RAYS]; stats->rng_draws = totals[STAT_DRAWS];
+        stats->reserved[0] = totals[STAT_SPLATS]; stats->reserved[1] = totals[STAT_SPLATS_INVALID]; stats->reserved[2] = totals[STAT_SPLATS_SATURATED];
+        stats->iterations = 1; stats->kernel_launches = 3;
+        if (timing) {
+            float t = 0.0f;
+            if (hipEventElapsedTime(&t, ctx->events[2], ctx->events[3]) == hipSuccess) stats->ms_other = t;
+            (void)hipGetLastError();
+        }
+        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    return RL_OK;
+}
 
 // ---- batched Acceleration::{trace, visible}
 namespace {
