@@ -13,15 +13,18 @@ through gloo — a plumbing mode, flagged in the JSON (`devices_shared`), never 
 `--scaling weak` (default): the image is fixed and spp = 128 x N, every GPU traces W*H*128 camera samples per step (N = 8 is
 BASELINE configs[3]); `--scaling strong`: 128 spp in total, the tiles split N ways.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (k_path_fused on this workload): algorithmic bytes
-per launch / mean launch duration from HIP events on the render stream.  `cpu_baseline` times the
-CPU oracle (a C++ restatement of rustlight's path integrator — NOT rustlight itself) on a bounded
-sample of the same workload on the host cores.  On the default single-GPU run the line also carries `also`: the other BASELINE
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: it sets up, warms up, times the steps, writes
+--dump-outputs and prints the line, whose `roofline` is for the dominant kernel (k_path_fused on this workload): algorithmic bytes
+per launch / mean launch duration from HIP events on the render stream of the timed steps themselves.  Everything else needs `--full`
+(`full` in the line says which it was; extras() lists the parts): `oracle_crc_match` (the last frame against the CPU oracle's CRC of it),
+`cpu_baseline`, which times the CPU oracle (a C++ restatement of rustlight's path integrator — NOT rustlight itself) on a bounded
+sample of the same workload on the host cores, the N-GPU records below, and `also`: on the default single-GPU run the other BASELINE
 configurations and stream modes timed the same way in the same process (configs[2] stand-in, configs[4], configs[1] in
 rustlight's own reference-order streams, configs[1] on a square frame), and `reference_order_value` at the top level.
 `value`, `reference_order_value` and every `ms_per_step` are ONE frame at a time (rl_render_path is synchronous, like Integrator::compute).  Next to
 them, never in their place: `reference_order_in_flight_value` and the `*_3_in_flight` records — the same frames with three of them on the GPU at once
-(three contexts of the scene, one host thread each; DESIGN.md 5 "Frames in flight") — and, for N > 1, `reference_order.three_frames_in_flight` per rank.
+(three contexts of the scene, one host thread each; DESIGN.md 5 "Frames in flight") — and, for N > 1, `reference_order.three_frames_in_flight` per rank
+(the N-GPU records of --full: `reference_order`, `strong_scaling`, and `distributed.crc_match` from a single-GPU re-render of the last frame).
 The reference-order `also` records (configs[1], configs[4], the configs[2] stand-in in rustlight's own streams: the drop-in default) are THREE timed steps each, every step
 synchronised and timed on its own: `step_ms`, `value_min` (the worst single step) / `value_median` / `value_max`, and `reference_order_worst_step_value` at the top level = the
 weakest step of the default mode over all three.  In that mode k_path_fused runs BESIDE the chain pass: its `kernel_ms` / roofline entry use its own span
@@ -65,9 +68,13 @@ def parse_args(argv=None):
                     help="per_sample: one lane per pixel / sample (throughput decomposition); reference: rustlight's own stream assignment (one sampler per 16x16 block)")
     ap.add_argument("--numerics", default="exact", choices=["exact", "fast"])
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="weak: spp x N (fixed work per GPU); strong: spp in total, tiles split N ways")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the untimed single-GPU re-render that checks the N-GPU image CRC")
-    ap.add_argument("--no-also", action="store_true", help="skip the `also` sub-records (the other BASELINE configs / stream modes) of the default single-GPU run")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need (see extras()): the CPU baseline, the `also` records, "
+                    "N > 1: the reference-order / frames-in-flight / strong-scaling records and the single-GPU re-render of the last frame, and the oracle CRC comparisons. "
+                    "Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the untimed single-GPU re-render that checks the N-GPU image CRC")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the `also` sub-records (the other BASELINE configs / stream modes) of the default single-GPU run "
+                    "and the reference-order / strong-scaling records of an N-GPU run")
     ap.add_argument("--init-timeout", type=float, default=180.0, help="seconds the process-group init and the first collective may take before the rank prints diagnostics and exits")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the image the last timed step produced (rank 0: the reduced frame) "
                     "as DIR/image.npy (float32, H x W x 3); past 64 MB, a fixed seeded sample of its pixels instead (image_sample.npy + image_sample_index.npy)")
@@ -93,9 +100,21 @@ def _respawn_under_launcher(args):
 
 
 def is_default_workload(args) -> bool:
-    """The run the driver makes (`python bench.py --gpus 1 ...`): BASELINE configs[1] untouched — only then the `also` records are added."""
+    """The driver's workload (`python bench.py --gpus 1 ...`): BASELINE configs[1] untouched — only on it (and with --full) the `also` records are added."""
     return (args.gpus == 1 and args.scene == "cbox" and (args.width, args.height, args.spp) == (1920, 1080, 128) and args.stream_mode == "per_sample"
             and args.numerics == "exact" and args.pipeline == "auto" and args.pool == 0 and args.tris == 0 and not args.no_also)
+
+
+def extras(args) -> dict:
+    """What a run does besides its headline (set-up, warm-up, the timed steps, --dump-outputs, the line with its roofline from those steps' own counters).
+    All of it needs --full: a plain run is what the driver repeats, and these cost seconds to minutes of GPU and CPU time apiece."""
+    multi = args.gpus > 1 and args.scene == "cbox" and args.stream_mode == "per_sample" and args.numerics == "exact" and not args.no_also
+    return {"also": args.full and is_default_workload(args),                                       # the other configs / stream modes, frames in flight
+            "cpu_baseline": args.full and args.gpus == 1 and not args.no_cpu_baseline,            # the CPU oracle on a bounded sample of the workload
+            "reference_order": args.full and multi,                                               # N > 1: the shards in reference-order streams, 3 frames in flight
+            "strong_scaling": args.full and multi and args.scaling == "weak",                     # N > 1: the strong-scaling pair of the same frame
+            "verify": args.full and args.gpus > 1 and not args.no_verify,                         # N > 1: the last frame re-rendered on one GPU, CRCs compared
+            "oracle_crc": args.full}                                                              # the last frame's CRC against tests/golden/bench_crcs.json
 
 
 class _Watchdog:
@@ -171,6 +190,7 @@ def dump_outputs(out_dir, img):
 
 def main():
     args = parse_args()
+    run = extras(args)          # what this run does besides its headline (only with --full)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         _respawn_under_launcher(args)
 
@@ -326,10 +346,10 @@ def main():
     ranks = rd.gather_objects({"rank": rank, "device": device_index, "name": torch.cuda.get_device_name(device_index), "pid": os.getpid(),
                                "kernel_ms_per_step": ((ms["ms_other"] + ms["ms_prepass"]) or sum(ms.values())) / max(1, args.steps),
                                "reduce_ms_per_step": main_rec["reduce_ms"]})
-    # ---- N > 1: the same shards once more in rustlight's own reference-order streams (the drop-in default), so that one multi-GPU run answers for both
+    # ---- N > 1, --full: the same shards once more in rustlight's own reference-order streams (the drop-in default), so that one multi-GPU run answers for both
     # stream modes: per rank the chain pass (k_stream_spec), the evaluation pass (k_path_fused) and the reduce
     ref_multi = None
-    if world > 1 and args.scene == "cbox" and args.stream_mode == "per_sample" and args.numerics == "exact" and not args.no_also:
+    if run["reference_order"]:
         rrec = time_workload(ctx, args.width, args.height, spp_total, "reference", "exact", 2, 1, shard=(rank, world))
         per_rank = rd.gather_objects({"rank": rank, "chain_ms": rrec["ms"]["ms_prepass"] / 2, "eval_span_ms": rrec["ms"]["ms_eval_span"] / 2, "eval_tail_after_chain_ms": rrec["ms"]["ms_other"] / 2,
                                       "overlapped": rrec["overlapped"], "reduce_ms": rrec["reduce_ms"], "chain_pass": rrec["spec"]})
@@ -383,10 +403,10 @@ def main():
                          "value": rrec["samples_per_step"] * 2 / rrec["dt"] / 1e6, "unit": "Msamples/s", "ranks": per_rank,
                          "image_crc32": f"{zlib.crc32(rrec['host_img'].tobytes()):08x}", "three_frames_in_flight": in_flight}
 
-    # ---- N > 1, weak default: the strong-scaling pair in the same invocation — the same frame as the 1-GPU run (spp in TOTAL, tiles split N ways), both
+    # ---- N > 1, weak default, --full: the strong-scaling pair in the same invocation — the same frame as the 1-GPU run (spp in TOTAL, tiles split N ways), both
     # stream modes, 3 steps each: the N-GPU images must carry the CRCs the oracle gave for the 1-GPU frames (seed 2)
     strong = None
-    if world > 1 and args.scaling == "weak" and args.scene == "cbox" and args.stream_mode == "per_sample" and args.numerics == "exact" and not args.no_also:
+    if run["strong_scaling"]:
         strong = []
         for mode in ("per_sample", "reference"):
             srec = time_workload(ctx, args.width, args.height, args.spp, mode, "exact", 3, 1, shard=(rank, world))
@@ -401,11 +421,11 @@ def main():
                                "image_crc32": crc_s, "oracle_crc32": want_s, "oracle_crc_match": None if want_s is None else want_s == crc_s})
 
     if rank == 0:
-        # ---- the N-GPU image must be the 1-GPU image, bit for bit (sums with zeros are exact): re-render the last step's
+        # ---- --full: the N-GPU image must be the 1-GPU image, bit for bit (sums with zeros are exact): re-render the last step's
         # frame on this GPU alone, untimed, and compare CRCs
         crc = zlib.crc32(host_img.tobytes())
         crc_single = None
-        if world > 1 and not args.no_verify:
+        if run["verify"]:
             seeds = api.IndependentSampler(args.steps - 1).block_seeds(args.width, args.height)
             single, _ = ctx.render(seeds, main_rec["params"](0, 1))
             crc_single = zlib.crc32(single.tobytes())
@@ -475,9 +495,9 @@ def main():
         util = utilisation_fields(live, f"{args.scene}{':tris' + str(args.tris) if args.tris else ''}:{args.width}x{args.height}x{args.spp}:{args.stream_mode}:{args.numerics}", dominant, src_hash) if world == 1 else None
         roofline.update({k: (util or {}).get(k) for k in ("valu_issue_busy", "lane_utilisation", "valu_lane_slots_used", "wave_time_waiting", "pmc_current")})
 
-        # ---- `also`: the other BASELINE configurations and stream modes, timed the same way in this process (default single-GPU run only)
+        # ---- `also`: the other BASELINE configurations and stream modes, timed the same way in this process (--full, default single-GPU run only)
         also, reference_order_value = None, None
-        if is_default_workload(args) and world == 1:
+        if run["also"]:
             also = []
 
             def sub(tag, rec, what, extra=None, scene_name="cbox"):
@@ -596,7 +616,7 @@ def main():
                 ctx2.close()
 
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if run["cpu_baseline"]:
             from oracle import orc
             orc.use_timing_build()        # -O3 / libm / FMA build of the same restatement; never the checker
             cw, ch, cspp = args.width, args.height, max(1, args.spp // 4)   # bounded sample of the same workload: same scene and resolution, 1/4 of the spp (~10 s of CPU work over three passes)
@@ -625,7 +645,7 @@ def main():
         except Exception:
             rccl = None
         out = {"metric": "Msamples/s (paths/s) at 1080p x 128spp cbox", "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+               "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "full": args.full,
                "dtype": "f32", "data": "synthetic",
                "config": {"workload": workload, "spp_total": spp_total, "stream_mode": args.stream_mode, "numerics": args.numerics,
                           "pipeline": (f"two passes: {'k_stream_spec' if main_rec['spec']['spec_group'] else 'k_stream_chain'} + k_path_fused" if ms["ms_prepass"] > 0 else "fused (k_path_fused)") if fused else "wavefront (raygen/extend/shade/shadow)",
@@ -638,7 +658,7 @@ def main():
                                "crc_match": None if crc_single is None else crc_single == crc},
                "roofline": roofline, "cpu_baseline": cpu}
         # (N > 1: the reduced N-shard frame against the oracle's render of the WHOLE frame at spp_total — BASELINE configs[3] is `--gpus 8 --steps 1`: cbox 1080p x 1024 spp, seed 0)
-        want = oracle_crc(args.scene, args.width, args.height, spp_total, args.stream_mode, args.steps - 1) if args.numerics == "exact" and args.tris == 0 else None
+        want = oracle_crc(args.scene, args.width, args.height, spp_total, args.stream_mode, args.steps - 1) if run["oracle_crc"] and args.numerics == "exact" and args.tris == 0 else None
         out["oracle_crc32"] = want
         out["oracle_crc_match"] = None if want is None else want == f"{crc:08x}"        # the last timed frame == the CPU oracle's render of the same frame (tests/golden/bench_crcs.json)
         out["distributed"]["rccl_check"] = rccl_check

@@ -1,6 +1,6 @@
 # dev: the streaming fused kernel after the conditional / packed overflow pushes: time, CRC, store / load instruction counts, bytes written; then stage shares (timers build)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/living_ac; mkdir -p $O; cd $R
-python bench.py --scene living_room --steps 3 --warmup 1 --no-cpu-baseline --no-also 2>/dev/null > $O/bench.json
+python bench.py --full --scene living_room --steps 3 --warmup 1 --no-cpu-baseline --no-also 2>/dev/null > $O/bench.json
 python -c "
 import json; d=json.loads(open('$O/bench.json').readline()); print('living', d['ms_per_step'], d['value'], d['distributed']['image_crc32'], d.get('oracle_crc_match'))"
 timeout 900 python -m pytest tests/test_gpu_parity.py -q -x -k "mixed_materials or trace_batch or visible_batch or randomized" 2>&1 | tail -3

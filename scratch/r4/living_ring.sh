@@ -1,6 +1,6 @@
 # dev: the streaming kernels with the ring stack (trace.hip.h: RL_STACK_RING): time, CRC, instruction counts, the GPU suite
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/living_ring; mkdir -p $O; cd $R
-python bench.py --scene living_room --steps 3 --warmup 1 --no-cpu-baseline --no-also 2>/dev/null > $O/bench.json
+python bench.py --full --scene living_room --steps 3 --warmup 1 --no-cpu-baseline --no-also 2>/dev/null > $O/bench.json
 python -c "
 import json; d=json.loads(open('$O/bench.json').readline()); print('living', d['ms_per_step'], d['value'], d['distributed']['image_crc32'], d.get('oracle_crc_match'))"
 python bench.py --scene living_room --tris 4000000 --steps 2 --warmup 1 --no-cpu-baseline --no-also 2>/dev/null > $O/bench4m.json

@@ -1,7 +1,7 @@
 # dev: per-XCD item dispensers on the streaming fused kernel: time with / without, L2 hit rate, the GPU suite
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/living_xcd; mkdir -p $O; cd $R
 for x in 1 0; do
-RL_XCD_DISPENSE=$x python bench.py --scene living_room --steps 3 --warmup 1 --no-cpu-baseline --no-also 2>/dev/null > $O/bench$x.json
+RL_XCD_DISPENSE=$x python bench.py --full --scene living_room --steps 3 --warmup 1 --no-cpu-baseline --no-also 2>/dev/null > $O/bench$x.json
 python -c "
 import json; d=json.loads(open('$O/bench$x.json').readline()); print('living xcd=$x', d['ms_per_step'], d['value'], d['distributed']['image_crc32'], d.get('oracle_crc_match'))"
 RL_XCD_DISPENSE=$x python bench.py --scene living_room --tris 4000000 --steps 2 --warmup 1 --no-cpu-baseline --no-also 2>/dev/null > $O/bench4m$x.json

@@ -8,11 +8,11 @@ bash scratch/pmc_collect.sh r4pmc_living k_path_fused --scene living_room > $O/p
 bash scratch/pmc_collect.sh r4pmc_living_fast k_path_fused --scene living_room --numerics fast > $O/pmc_living_fast.log 2>&1
 bash scratch/pmc_collect.sh r4pmc_medium k_path_fused --scene cbox_medium > $O/pmc_medium.log 2>&1
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o p -- python $R/bench.py --no-cpu-baseline > $O/stats_default.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o p -- python $R/bench.py --full --no-cpu-baseline > $O/stats_default.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_reference -o p -- python $R/bench.py --no-cpu-baseline --no-also --stream-mode reference --steps 3 --warmup 1 > $O/stats_reference.log 2>&1
 cd $R
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --stream-mode reference --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_reference.json 2>/dev/null
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --stream-mode reference --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_reference.json 2>/dev/null
 for t in cbox reference living living_fast medium; do cp gpurun_out/r4pmc_$t/pmc_summary.json $O/pmc_$t.json; done
 find $O -name '*kernel_stats.csv' | head
 find $O -name '*kernel_trace.csv' -size +2M -delete; find $O -name '*agent_info.csv' -delete

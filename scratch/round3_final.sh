@@ -3,25 +3,25 @@
 R=$GRAFT_REPO_ROOT; cd $R
 T=${TAG:-r3z}; O=$R/gpurun_out/$T; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|error" > $O/pytest.log; cat $O/pytest.log
-( time python bench.py ) > $O/bench_default.json 2> $O/bench_default.err; tail -3 $O/bench_default.err
-python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline 2> $O/bench_2rank.err | grep "^{" > $O/bench_2rank.json
-python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --scaling strong 2> $O/bench_2rank_strong.err | grep "^{" > $O/bench_2rank_strong.json
+( time python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err; tail -3 $O/bench_default.err
+python bench.py --full --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline 2> $O/bench_2rank.err | grep "^{" > $O/bench_2rank.json
+python bench.py --full --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --scaling strong 2> $O/bench_2rank_strong.err | grep "^{" > $O/bench_2rank_strong.json
 python bench.py --numerics fast --no-cpu-baseline > $O/bench_fast.json 2> /dev/null
 python bench.py --stream-mode reference --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_reference.json 2> /dev/null
 RL_REF_SINGLE_PASS=1 python bench.py --stream-mode reference --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_reference_single_pass.json 2> /dev/null
 python bench.py --stream-mode reference --numerics fast --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_reference_fast.json 2> /dev/null
-python bench.py --pipeline wavefront --no-cpu-baseline > $O/bench_wavefront.json 2> /dev/null
-python bench.py --scene living_room --steps 3 --warmup 1 > $O/bench_living.json 2> /dev/null
+python bench.py --full --pipeline wavefront --no-cpu-baseline > $O/bench_wavefront.json 2> /dev/null
+python bench.py --full --scene living_room --steps 3 --warmup 1 > $O/bench_living.json 2> /dev/null
 python bench.py --scene living_room --steps 3 --warmup 1 --no-cpu-baseline --numerics fast > $O/bench_living_fast.json 2> /dev/null
 python bench.py --scene living_room --spp 16 --stream-mode reference --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_living_reference_16spp.json 2> /dev/null
-python bench.py --scene cbox_medium --steps 3 --warmup 1 > $O/bench_medium.json 2> /dev/null
+python bench.py --full --scene cbox_medium --steps 3 --warmup 1 > $O/bench_medium.json 2> /dev/null
 python bench.py --scene cbox_medium --steps 2 --warmup 1 --no-cpu-baseline --numerics fast > $O/bench_medium_fast.json 2> /dev/null
 python bench.py --scene cbox_medium --spp 16 --stream-mode reference --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_medium_reference_16spp.json 2> /dev/null
 python bench.py --scene living_room --tris 4000000 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_living4m.json 2> /dev/null
 python bench.py --scene living_room --tris 4000000 --steps 2 --warmup 1 --no-cpu-baseline --numerics fast > $O/bench_living4m_fast.json 2> /dev/null
 python scratch/fast_parity.py > $O/fast_parity.json 2> $O/fast_parity.err
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o p -- python $R/bench.py --no-cpu-baseline > $O/stats_default.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o p -- python $R/bench.py --full --no-cpu-baseline > $O/stats_default.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_living_fast -o p -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --scene living_room --numerics fast > $O/stats_living_fast.log 2>&1
 cd $R
 bash scratch/pmc_collect.sh $T/pmc_cbox k_path_fused > $O/pmc_cbox.log 2>&1

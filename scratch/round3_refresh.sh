@@ -3,13 +3,13 @@
 R=$GRAFT_REPO_ROOT; cd $R
 T=${TAG:-r3x}; O=$R/gpurun_out/$T; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|error" > $O/pytest.log; cat $O/pytest.log
-( time python bench.py ) > $O/bench_default.json 2> $O/bench_default.err; tail -n 3 $O/bench_default.err
+( time python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err; tail -n 3 $O/bench_default.err
 python bench.py --stream-mode reference --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_reference.json 2> /dev/null
 python bench.py --stream-mode reference --numerics fast --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_reference_fast.json 2> /dev/null
-python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline 2> $O/bench_2rank.err | grep "^{" > $O/bench_2rank.json
+python bench.py --full --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline 2> $O/bench_2rank.err | grep "^{" > $O/bench_2rank.json
 python scratch/mc_ref_bench.py 16 > $O/mc_ref.log 2>&1
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o p -- python $R/bench.py --no-cpu-baseline > $O/stats_default.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o p -- python $R/bench.py --full --no-cpu-baseline > $O/stats_default.log 2>&1
 cd $R
 bash scratch/pmc_collect.sh $T/pmc_cbox k_path_fused > $O/pmc_cbox.log 2>&1
 bash scratch/pmc_collect.sh $T/pmc_reference k_stream_chain --stream-mode reference > $O/pmc_reference.log 2>&1

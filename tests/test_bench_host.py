@@ -57,8 +57,8 @@ def test_stored_counter_keys_follow_the_workload():
 
 
 def test_also_records_only_on_the_default_single_gpu_run():
-    """The `also` sub-records (the other BASELINE configs / stream modes, timed in the same process) ride on the run the driver makes — `python bench.py --gpus 1
-    [--steps K --warmup W]` — and on nothing else: any other scene, size, stream mode, numerics, pipeline, pool, GPU count or --no-also is a single-workload run."""
+    """The `also` sub-records (the other BASELINE configs / stream modes, timed in the same process) ride on the driver's workload — `python bench.py --gpus 1
+    [--steps K --warmup W]`, with --full (test_plain_run_does_only_the_headline) — and on nothing else: any other scene, size, stream mode, numerics, pipeline, pool, GPU count or --no-also is a single-workload run."""
     assert bench.is_default_workload(bench.parse_args([]))
     assert bench.is_default_workload(bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "3"]))
     assert bench.is_default_workload(bench.parse_args(["--no-cpu-baseline"]))
@@ -67,6 +67,25 @@ def test_also_records_only_on_the_default_single_gpu_run():
         assert not bench.is_default_workload(bench.parse_args(argv)), argv
     a = bench.parse_args(["--scaling", "strong", "--gpus", "8"])
     assert a.scaling == "strong" and bench.parse_args([]).scaling == "weak" and a.init_timeout > 0
+
+
+def test_plain_run_does_only_the_headline():
+    """A plain run (what the driver repeats) sets up, warms up, times the steps, dumps and prints the line; every other measurement or check — the CPU
+    baseline, the `also` records, the N-GPU reference-order / strong-scaling records and re-render check, the oracle CRC lookup — needs --full, where the
+    --no-* knobs still turn parts of it off."""
+    for argv in ([], ["--gpus", "1", "--steps", "20", "--warmup", "5"], ["--gpus", "4"], ["--gpus", "8", "--scaling", "strong"], ["--scene", "living_room"],
+                 ["--dump-outputs", "d"], ["--stream-mode", "reference"]):
+        a = bench.parse_args(argv)
+        assert a.full is False and not any(bench.extras(a).values()), (argv, bench.extras(a))
+    x = bench.extras(bench.parse_args(["--full"]))
+    assert x["also"] and x["cpu_baseline"] and x["oracle_crc"] and not (x["reference_order"] or x["strong_scaling"] or x["verify"])
+    x = bench.extras(bench.parse_args(["--full", "--gpus", "2"]))
+    assert x["reference_order"] and x["strong_scaling"] and x["verify"] and x["oracle_crc"] and not (x["also"] or x["cpu_baseline"])
+    assert not bench.extras(bench.parse_args(["--full", "--gpus", "2", "--scaling", "strong"]))["strong_scaling"]
+    x = bench.extras(bench.parse_args(["--full", "--no-cpu-baseline", "--no-also"]))
+    assert not (x["also"] or x["cpu_baseline"]) and x["oracle_crc"]
+    x = bench.extras(bench.parse_args(["--full", "--gpus", "4", "--no-also", "--no-verify"]))
+    assert not (x["reference_order"] or x["strong_scaling"] or x["verify"]) and x["oracle_crc"]
 
 
 def test_pipeline_bytes_is_the_survey_formula():

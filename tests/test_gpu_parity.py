@@ -1185,8 +1185,8 @@ def test_cfg4_whole_frame_on_one_gpu(built):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--spp", "256", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-also",
-                        "--no-verify"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--spp", "256", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
+                        "--no-also", "--no-verify"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -1241,7 +1241,7 @@ def test_bench_two_ranks_on_one_gpu(built):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--width", "320", "--height", "200", "--spp", "4", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
