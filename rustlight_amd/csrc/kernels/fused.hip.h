@@ -8,20 +8,8 @@
 #include <vector>
 #endif
 
-#ifndef RL_RELOAD_SCENE
-#define RL_RELOAD_SCENE 1    // persistent loop re-reads scene / render constants from the kernarg segment per iteration (see k_path_fused)
-#endif
 #ifndef RL_FUSED_QUEUE
 #define RL_FUSED_QUEUE 0    // 1 (fusedq_lds.hip / fusedq_stream.hip): this translation unit instantiates the queue-fed form of the kernel
-#endif
-#ifndef RL_FUSED_COLD_SCRATCH
-#define RL_FUSED_COLD_SCRATCH 0   // 1 (experiment, round 6, measured: profiles/NEGATIVES.md): scenes that stream their BVH keep the per-sample-cold path state in registers / scratch instead of LDS (the freed LDS takes more stack levels: -DRL_LDS_LEVELS_STREAMING)
-#endif
-#ifndef RL_SHADE_NOINLINE
-#define RL_SHADE_NOINLINE 0       // 1 (experiment, round 6, measured): the run-time-switch shading of scenes that stream their BVH as an out-of-line function, its live-in set passed by value
-#endif
-#ifndef RL_COOP_FETCH
-#define RL_COOP_FETCH 0     // 1 / 2: streaming scenes fetch BVH records wave-cooperatively (trace.hip.h: traverse_coop; 1 = LDS staging, 2 = registers + ds_bpermute) — both measured slower, kept for the record
 #endif
 
 namespace rl {
@@ -29,19 +17,12 @@ namespace rl {
 // ------------------------------------------------------------------------------------------
 // k_path_fused<MAT, MEDIUM, LDS> — the persistent form of the pipeline for scenes with one BSDF type: one
 // launch, one lane per pixel item, the four stage functions above run back-to-back per iteration
-// (raygen -> extend -> shade -> shadow) with the whole path state in registers (RegState) and the scene +
+// (raygen -> extend -> shade -> shadow) with the path state in registers and LDS (FusedState) and the scene +
 // traversal stacks in LDS.  Same functions, same order of operations, same results as the wavefront kernels;
 // what disappears is ~1.4 KB/sample of state traffic through HBM and ~2000 kernel boundaries per render.
 #ifdef RL_STAGE_TIMERS
 __device__ unsigned long long g_stage_timers[32];      // [0..3] cycles per stage, [4..7] live lanes per stage, [8] lane slots, [16..] shadow-stage occupancy (dump_stage_timers_impl)
 #endif
-// RL_SHADE_NOINLINE: shade_slot out of line — the path state and the counters go in and come back by value, so that the traversal loops' live set need not include the material switch's
-template <class PS> struct ShadeIO { PS ps; unsigned nv, nd, ns, ne; };
-template <int MAT, bool MEDIUM, int LIGHTS, class SMP, class PS>
-__device__ __attribute__((noinline)) ShadeIO<PS> shade_outlined(const RenderConst* rc, const DeviceScene* sc, ShadeIO<PS> io) {
-    shade_slot<MAT, MEDIUM, LIGHTS, false, SMP>(*rc, *sc, io.ps, io.ps.u(U_FLAGS), io.nv, io.nd, io.ns, io.ne);
-    return io;
-}
 // QUEUE: the form that takes its work from the chain pass's completion queue (the evaluation pass of reference-order streams, launched beside the chain pass): an
 // instantiation of its own (fusedq_lds.hip / fusedq_stream.hip), so that the per-sample kernel's code is exactly what it is without it.
 // The body is fused_body.inc.h: k_path_fused includes it with the independent sampler (SMP = Rng), k_path_fused_strat (fused_strat.hip.h) with StratSampler.

@@ -6,17 +6,12 @@
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneRecs recs;
     float4* after_scene = smem;
-    constexpr bool LDS2 = LDS_SCENE && RL_LDS_TWO_LEVEL;      // LDS-staged scenes: two-level node records (trace.hip.h: traverse2, stage_scene_lds2)
-    if (LDS2) {
-        stage_scene_lds2(sc, smem, smem + lds_nodes2_float4s(sc.n_nodes));
-        recs.nodes = smem; recs.tris = smem + lds_nodes2_float4s(sc.n_nodes);
-        after_scene = smem + lds_scene2_float4s(sc.n_nodes, sc.n_prims);
-    } else if (LDS_SCENE) {
+    if (LDS_SCENE) {
         stage_scene_lds(sc, smem, smem + lds_nodes_float4s(sc.n_nodes));
         recs.nodes = smem; recs.tris = smem + lds_nodes_float4s(sc.n_nodes);
         after_scene = smem + lds_scene_float4s(sc.n_nodes, sc.n_prims);
     } else {
-        recs.nodes = streamed_nodes<TravStackT<false>>(sc);   // exact build: two-level records; tolerance build: quantised BVH4 nodes
+        recs.nodes = streamed_nodes<TravStackT<false>>(sc);   // exact build: BVH2 nodes; tolerance build: quantised BVH4 nodes
         recs.tris = reinterpret_cast<const float4*>(sc.tris);
     }
     const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -24,14 +19,9 @@
     unsigned long long* cold_q = reinterpret_cast<unsigned long long*>(after_scene);
     float* cold_f = reinterpret_cast<float*>(cold_q + 256 * FusedState::kColdQ);
     unsigned* cold_u = reinterpret_cast<unsigned*>(cold_f + 256 * FusedState::kColdF);
-    using StackT = typename std::conditional<LDS2, TravStackLds2, TravStackT<LDS_SCENE>>::type;
-    constexpr bool COLD_LDS = LDS_SCENE || !RL_FUSED_COLD_SCRATCH;
-    const StackT stack(make_stack<LDS_SCENE>(stc, COLD_LDS ? cold_u + 256 * FusedState::kColdU : reinterpret_cast<unsigned*>(after_scene), tid));
-    // streaming scenes: per-wave staging area of the cooperative record fetch, after the stacks
-    constexpr bool COOP = !LDS_SCENE && RL_COOP_FETCH;
-    float4* stage = reinterpret_cast<float4*>(cold_u + 256 * FusedState::kColdU + 2 * 256 * stc.lds_levels) + (threadIdx.x >> 6) * kCoopStageFloat4s;
-    typename std::conditional<COLD_LDS, FusedState, RegState>::type ps;
-    if constexpr (COLD_LDS) { ps.cold_q = cold_q + threadIdx.x; ps.cold_f = cold_f + threadIdx.x; ps.cold_u = cold_u + threadIdx.x; }
+    const TravStackT<LDS_SCENE> stack(make_stack<LDS_SCENE>(stc, cold_u + 256 * FusedState::kColdU, tid));
+    FusedState ps;
+    ps.cold_q = cold_q + threadIdx.x; ps.cold_f = cold_f + threadIdx.x; ps.cold_u = cold_u + threadIdx.x;
 #pragma unroll
     for (int i = 0; i < F_COUNT; i++) ps.fv[i] = 0.0f;
 #pragma unroll
@@ -60,27 +50,6 @@
 #define RL_T0
 #define RL_T1(K, COND)
 #endif
-    if constexpr (COOP) {
-        // every lane of the wave stays in the loop until the whole wave has no work left: idle lanes are the loaders of the cooperative fetch
-        while (__ballot(!(PU(U_FLAGS) & ST_FINISHED)) != 0ull) {
-            RL_T0
-#ifdef RL_STAGE_TIMERS
-            ln[4] += 64;
-            const bool c0 = PU(U_FLAGS) & ST_REGEN;
-#endif
-            if (PU(U_FLAGS) & ST_REGEN) raygen_slot<true, decltype(ps), SMP>(rc, sc, ps, n_samples, n_draws);
-            RL_T1(0, c0)
-            const bool has_ray = (PU(U_FLAGS) & ST_RAY) != 0u;
-            extend_slot_coop(sc, recs, stack, ps, has_ray, stage);
-            RL_T1(1, has_ray)
-            if (has_ray) shade_slot<MAT, MEDIUM, LIGHTS, false, SMP>(rc, sc, ps, PU(U_FLAGS), n_vertices, n_draws, n_shadow, n_ext);
-            RL_T1(2, has_ray)
-            const bool has_shadow = (PU(U_FLAGS) & ST_SHADOW) != 0u;
-            shadow_slot_coop(sc, recs, stack, ps, has_shadow, stage);
-            RL_T1(3, has_shadow)
-        }
-    } else
-    {
     // ---- QUEUE form (the evaluation pass of reference-order streams beside the chain pass): the lanes take their pixel items from this launch's block list — item
     // position c = block c / (256 split) of the list, item c % (256 split) of that block — through one claim counter, like the dispenser's lanes; every block of the list is
     // complete (the host only lists blocks the chain kernel has flagged), so nothing here waits.
@@ -125,7 +94,6 @@
     }
     // (queue mode: ONE trip of the loop body, then back to the claims — a lane whose pixel is done takes its next item while the others go on, like the dispenser's lanes)
     if (!(PU(U_FLAGS) & ST_FINISHED)) do {
-#if RL_RELOAD_SCENE
         // The scene record (25 pointers, camera matrices, ...) and the render constants do not fit the scalar registers next to the saved
         // exec masks of the stage functions: kept live across the loop they are spilled to VGPR lanes (v_writelane / v_readlane were ~600 of
         // the kernel's ~4500 vector instructions, 126 spilled SGPRs).  Re-deriving their address from the kernarg segment once per iteration
@@ -136,8 +104,7 @@
         constexpr size_t sc_off = (sizeof(RenderConst) + alignof(DeviceScene) - 1) / alignof(DeviceScene) * alignof(DeviceScene);
         static_assert(sc_off == offsetof(PathKernargs, sc) && offsetof(PathKernargs, rc) == 0, "kernarg layout of k_path_fused(RenderConst, DeviceScene, StackConf)");
         const DeviceScene& sc = *(const DeviceScene*)(ka + sc_off);
-        const RenderConst& rc = (MEDIUM || RL_RELOAD_SCENE > 1) ? *(const RenderConst*)ka : rc_arg;
-#endif
+        const RenderConst& rc = MEDIUM ? *(const RenderConst*)ka : rc_arg;
         RL_T0
 #ifdef RL_STAGE_TIMERS
         ln[4] += 64;
@@ -151,11 +118,6 @@
         if (PU(U_FLAGS) & ST_RAY) {
             extend_slot(sc, recs, stack, ps);
             RL_T1(1, c1)
-            if constexpr (RL_SHADE_NOINLINE && MAT == -1 && !LDS_SCENE) {
-                ShadeIO<decltype(ps)> io{ps, n_vertices, n_draws, n_shadow, n_ext};
-                io = shade_outlined<MAT, MEDIUM, LIGHTS, SMP>(&rc, &sc, io);
-                ps = io.ps; n_vertices = io.nv; n_draws = io.nd; n_shadow = io.ns; n_ext = io.ne;
-            } else
             shade_slot<MAT, MEDIUM, LIGHTS, false, SMP>(rc, sc, ps, PU(U_FLAGS), n_vertices, n_draws, n_shadow, n_ext);
         }
         RL_T1(2, c1)
@@ -172,7 +134,6 @@
         RL_T1(3, c3)
     } while (!qmode && !(PU(U_FLAGS) & ST_FINISHED));
     if (!qmode) break;
-    }
     }
 #ifdef RL_STAGE_TIMERS
     if ((threadIdx.x & 63u) == 0u) { for (int k = 0; k < 4; k++) { atomicAdd(&g_stage_timers[k], tm[k]); atomicAdd(&g_stage_timers[4 + k], ln[k]); } atomicAdd(&g_stage_timers[8], ln[4]);

@@ -164,7 +164,7 @@ struct SpecKernargs { RenderConst rc; DeviceScene sc; StackConf stc; SpecConf sp
 
 // Path-state accessors.  The stage functions below are written once against `ps.f/u/q(field)`:
 //  * PoolState: the wavefront kernels — state lives in the HBM pool, one coalesced word per lane;
-//  * RegState:  the persistent fused kernel — the same fields are plain locals (every index is a compile-time
+//  * RegState:  the chain and spec kernels (chain.hip.h, spec.hip.h) — the same fields are plain locals (every index is a compile-time
 //    constant, so the arrays are scalarised into VGPRs and untouched fields disappear).
 struct PoolState {
     Pool pool; unsigned slot;

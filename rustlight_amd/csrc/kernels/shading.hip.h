@@ -708,9 +708,7 @@ struct MediumSample { float t; Col w; bool exited; };
 // examples/cli.rs:381-385), so the three arguments are usually equal and one evaluation of the (f64, ~40-instruction) recipe serves all of them —
 // same inputs, same bits.  The test is per lane but all lanes of a grey medium agree, so the branch never diverges.
 RL_DEV Col cexp(Col c) {
-#ifndef RL_NO_GREY_EXP
     if ((c.r == c.g) & (c.g == c.b)) { const float e = m_expf(c.r); return mkc(e, e, e); }
-#endif
     return mkc(m_expf(c.r), m_expf(c.g), m_expf(c.b));
 }
 RL_DEV MediumSample medium_sample(const MediumRecord& m, float max_t, float u) {

@@ -172,11 +172,7 @@ __global__ void __launch_bounds__(256, LDS_SCENE ? RL_SPEC_WAVES : RL_SPEC_WAVES
 #define st_spec_inc atomicAdd(&gstat[0], 1u)
 #define st_slow_inc atomicAdd(&gstat[1], 1u)
 #define st_probe_inc atomicAdd(&gstat[2], 1u)
-#ifdef RL_PROBE_NO_DENSE
-    const unsigned H = 0u;
-#else
     const unsigned H = (LDS_SCENE && G <= 64u && spc.dense > 1u) ? min(spc.dense, G) : 0u;
-#endif
     auto group_any = [&](bool p) -> bool { return G <= 64u ? (__ballot(p) & gmask) != 0ull : __syncthreads_or((int)p) != 0; };
     auto group_scan2 = [&](float& a, float& b) {      // inclusive prefix sums over the lanes of the group
         const unsigned w = G <= 64u ? G : 64u, li = G <= 64u ? gl : lane;

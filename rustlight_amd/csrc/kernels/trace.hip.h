@@ -32,13 +32,9 @@ struct Hit { float t, u, v; int prim; int steps = 0, tris = 0, fetches = 0; };  
 #define RL_LDS_TRI_STRIDE4 5
 #endif
 static constexpr int kLdsNodeStride = RL_LDS_NODE_STRIDE;      // dwords
-static constexpr int kLdsNode2Stride = 36;                     // dwords between two-level records staged in LDS (32 + 4: ds_read_b128 rows stay 16-byte aligned, consecutive records start 4 banks apart)
 static constexpr int kLdsTriStride4 = RL_LDS_TRI_STRIDE4;      // float4s
 RL_DEV __host__ unsigned lds_nodes_float4s(unsigned n_nodes) { return (n_nodes * (unsigned)kLdsNodeStride + 3u) / 4u; }
 RL_DEV __host__ unsigned lds_scene_float4s(unsigned n_nodes, unsigned n_prims) { return lds_nodes_float4s(n_nodes) + n_prims * (unsigned)kLdsTriStride4; }
-// the same scene with the nodes as two-level records (k_path_fused on LDS-staged scenes: traverse2)
-RL_DEV __host__ unsigned lds_nodes2_float4s(unsigned n_nodes) { return n_nodes * (unsigned)(kLdsNode2Stride / 4); }
-RL_DEV __host__ unsigned lds_scene2_float4s(unsigned n_nodes, unsigned n_prims) { return lds_nodes2_float4s(n_nodes) + n_prims * (unsigned)kLdsTriStride4; }
 
 // AABB::intersect (src/structure.rs:849-869) with 1/d hoisted out of the loop, restated without its per-axis
 // early exit and compare/select chains — same value, same verdict, a third fewer VALU instructions:
@@ -48,28 +44,6 @@ RL_DEV __host__ unsigned lds_scene2_float4s(unsigned n_nodes, unsigned n_prims) 
 //  * t_min only grows and t_max only shrinks, so the reference's exit `t_max <= t_min` after axis k implies the
 //    same relation after axis 3: one final test decides, and on success t_min is the returned entry distance.
 // The near/far plane choice stays a select on the sign of 1/d (min/max of t0, t1 would resurrect a NaN plane).
-#ifdef RL_SLAB_REFERENCE_FORM
-RL_DEV bool slab(V3 lo, V3 hi, V3 o, V3 inv_d, float tnear, float tfar, float* t_entry) {
-    float t_min = tnear, t_max = tfar;
-    float t0 = (lo.x - o.x) * inv_d.x, t1 = (hi.x - o.x) * inv_d.x;
-    float a0 = inv_d.x < 0.0f ? t1 : t0, a1 = inv_d.x < 0.0f ? t0 : t1;
-    t_min = a0 > t_min ? a0 : t_min;
-    t_max = a1 < t_max ? a1 : t_max;
-    bool ok = !(t_max <= t_min);
-    t0 = (lo.y - o.y) * inv_d.y; t1 = (hi.y - o.y) * inv_d.y;
-    a0 = inv_d.y < 0.0f ? t1 : t0; a1 = inv_d.y < 0.0f ? t0 : t1;
-    t_min = a0 > t_min ? a0 : t_min;
-    t_max = a1 < t_max ? a1 : t_max;
-    ok = ok && !(t_max <= t_min);
-    t0 = (lo.z - o.z) * inv_d.z; t1 = (hi.z - o.z) * inv_d.z;
-    a0 = inv_d.z < 0.0f ? t1 : t0; a1 = inv_d.z < 0.0f ? t0 : t1;
-    t_min = a0 > t_min ? a0 : t_min;
-    t_max = a1 < t_max ? a1 : t_max;
-    ok = ok && !(t_max <= t_min);
-    *t_entry = t_min;
-    return ok;
-}
-#else
 RL_DEV bool slab(V3 lo, V3 hi, V3 o, V3 inv_d, float tnear, float tfar, float* t_entry) {
     const float x0 = (lo.x - o.x) * inv_d.x, x1 = (hi.x - o.x) * inv_d.x;
     const float y0 = (lo.y - o.y) * inv_d.y, y1 = (hi.y - o.y) * inv_d.y;
@@ -80,7 +54,6 @@ RL_DEV bool slab(V3 lo, V3 hi, V3 o, V3 inv_d, float tnear, float tfar, float* t
     *t_entry = t_min;
     return !(t_max <= t_min);
 }
-#endif
 
 // Mesh::intersection_tri; returns true and updates `hit` (t, prim) if the triangle is the new closest hit.
 // The reference evaluates u, v (two sqrt + two divides) before it looks at `t < its.t && t > 1e-5`
@@ -121,12 +94,8 @@ RL_DEV bool tri_test(const float4 q0, const float4 q1, const float4 q2, const fl
 #if defined(RL_FAST_MATH)
         accept = facing & (det > 0.0f) & (__builtin_amdgcn_sqrtf(uu) + __builtin_amdgcn_sqrtf(ww) <= det);     // tolerance build: the 1-ulp estimate decides everywhere (det > 0: a degenerate triangle is rejected as the exact build's NaN barycentrics reject it)
 #else
-#if defined(RL_TRI_REFERENCE_FORM)
-        const bool in_range = false; const float s = 0.0f;
-#else
         const float s = __builtin_amdgcn_sqrtf(uu) + __builtin_amdgcn_sqrtf(ww);
         const bool in_range = __builtin_fminf(__builtin_fminf(uu, ww), det) >= 0x1p-100f;   // false for NaNs too
-#endif
         const bool sure_in = in_range & (s <= det * 0.99999f), sure_out = in_range & (s >= det * 1.00001f);
         accept = facing & sure_in;
         if (facing & !sure_in & !sure_out) {      // inside the band (or denormal-range / non-finite inputs): the reference's own arithmetic
@@ -161,13 +130,6 @@ struct SceneRecs {
 // in LDS (96 B/lane) lets 8 waves/SIMD stay resident on scenes whose BVH is 20-40 levels deep.
 struct NodeFetchLds;
 struct NodeFetchGlobal;
-#ifndef RL_TWO_LEVEL
-// 1: scenes that stream their BVH traverse the two-level records (traverse2) in the exact build.  OFF: measured slower — 508 k triangles, 1080p x 128 spp: node trips per
-// ray 19.1 -> 10.5, k_path_fused 305 -> 374 ms, same CRC (profiles/NEGATIVES.md, round 5): the kernel pays per ISSUED instruction (64-lane instructions at 22 % live lanes),
-// not per dependent round trip, and a two-level trip issues twice the loads and slab arithmetic of a one-level trip.  The construction stays tested through
-// TravStack2 / rl_debug_trace_batch_two_level.
-#define RL_TWO_LEVEL 0
-#endif
 template <bool LDS_ONLY>
 struct TravStackT {
     using NodeFetch = typename std::conditional<LDS_ONLY, NodeFetchLds, NodeFetchGlobal>::type;   // LDS-only stacks go with LDS-staged scenes
@@ -177,11 +139,7 @@ struct TravStackT {
 #else
     static constexpr bool kBvh4 = false;
 #endif
-#if RL_TWO_LEVEL && !defined(RL_FAST_MATH)
-    static constexpr bool kTwoLevel = !LDS_ONLY;   // exact build, streaming scenes: two-level records (device_types.h: BvhNode2; traverse2)
-#else
-    static constexpr bool kTwoLevel = false;
-#endif
+    static constexpr bool kTwoLevel = false;       // two-level records (traverse2): the test hook TravStack2 only
     static constexpr int kTriStride4 = LDS_ONLY ? kLdsTriStride4 : 4;                              // float4s between triangle records
     static constexpr int kNodeRefScale = LDS_ONLY ? 4 * kLdsNodeStride : 1;                        // inner-node reference = index x this (LDS: byte offset)
     static constexpr int lds_stride = 256;       // every traversal kernel runs 256-lane workgroups
@@ -226,17 +184,7 @@ struct TravStackT {
     }
 };
 using TravStack = TravStackT<false>;
-#ifndef RL_LDS_TWO_LEVEL
-// 1: k_path_fused on LDS-staged scenes traverses two-level records (one LDS round trip decides two levels; the near / far rows come pre-swizzled as six ds_read_b128,
-// no selects).  OFF: measured slower on the same box — cbox 1080p x 128 spp 50.7 -> 59.0 ms, square frame 51.6 -> 59.8, cbox + medium (32 spp) 103.1 -> 115.4, same CRCs
-// (profiles/NEGATIVES.md round 5): half the children of a 19-node tree are leaves, so half of the second-level slabs are wasted, and the kernel is bound by VALU issue.
-#define RL_LDS_TWO_LEVEL 0
-#endif
-struct TravStackLds2 : TravStackT<true> {        // LDS-staged scene, two-level records (stage_scene_lds2)
-    static constexpr bool kTwoLevel = true;
-    RL_DEV explicit TravStackLds2(const TravStackT<true>& s) : TravStackT<true>(s) {}
-};
-struct TravStack2 : TravStackT<false> {          // the same stack, traversed through the two-level records whatever RL_TWO_LEVEL says (test hook)
+struct TravStack2 : TravStackT<false> {          // the same stack, traversed through the two-level records (test hook)
     static constexpr bool kTwoLevel = true;
     static constexpr bool kBvh4 = false;
     RL_DEV explicit TravStack2(const TravStackT<false>& s) : TravStackT<false>(s) {}
@@ -303,11 +251,6 @@ struct NodeFetchGlobal {
     }
 };
 
-#ifndef RL_UNIFORM_TRIPS
-// streaming scenes: trips on which all lanes hold the same node / leaf fetch it through the scalar cache: 81.2 -> 78.7 ms on the 508 k-triangle scene at 32 spp,
-// 75.5 -> 74.4 ms in the tolerance build
-#define RL_UNIFORM_TRIPS 1
-#endif
 #ifndef RL_VOTE_NUM
 #define RL_VOTE_NUM 3      // streaming scenes: a node trip while (lanes with node / stack work) * DEN >= NUM * (lanes holding leaves)
 #define RL_VOTE_DEN 2
@@ -349,24 +292,10 @@ RL_DEV bool traverse(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V3
             hit.steps++;
             NodePlanes p;
             const int cur0 = __builtin_amdgcn_readfirstlane(cur);
-#if RL_UNIFORM_TRIPS >= 2
-            // experiment: trips on which the live lanes hold exactly TWO nodes fetch both through the scalar cache and select per lane
-            const unsigned long long other = Stack::NodeFetch::kHasUniform ? __ballot(cur != cur0) : ~0ull;
-            if (Stack::NodeFetch::kHasUniform && other == 0ull) p = fetch.uniform(cur0);
-            else if (Stack::NodeFetch::kHasUniform) {
-                const int cur1 = __builtin_amdgcn_readlane(cur, (int)__builtin_ctzll(other));
-                if (__ballot((cur != cur0) & (cur != cur1)) == 0ull) {
-                    const NodePlanes a = fetch.uniform(cur0), b = fetch.uniform(cur1);
-                    const bool f = cur == cur0;
-                    p.lnx = f ? a.lnx : b.lnx; p.lny = f ? a.lny : b.lny; p.lnz = f ? a.lnz : b.lnz; p.lfx = f ? a.lfx : b.lfx; p.lfy = f ? a.lfy : b.lfy; p.lfz = f ? a.lfz : b.lfz;
-                    p.rnx = f ? a.rnx : b.rnx; p.rny = f ? a.rny : b.rny; p.rnz = f ? a.rnz : b.rnz; p.rfx = f ? a.rfx : b.rfx; p.rfy = f ? a.rfy : b.rfy; p.rfz = f ? a.rfz : b.rfz;
-                    p.id1 = f ? a.id1 : b.id1; p.id2 = f ? a.id2 : b.id2;
-                } else p = fetch(cur);
-            } else p = fetch(cur);
-#else
-            if (Stack::NodeFetch::kHasUniform && RL_UNIFORM_TRIPS && __ballot(cur != cur0) == 0ull) p = fetch.uniform(cur0);
+            // streaming scenes: trips on which all lanes hold the same node / leaf fetch it through the scalar cache (81.2 -> 78.7 ms on the 508 k-triangle
+            // scene at 32 spp, 75.5 -> 74.4 ms in the tolerance build)
+            if (Stack::NodeFetch::kHasUniform && __ballot(cur != cur0) == 0ull) p = fetch.uniform(cur0);
             else p = fetch(cur);
-#endif
             const float d1 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf((p.lnx - o.x) * inv_d.x, (p.lny - o.y) * inv_d.y), (p.lnz - o.z) * inv_d.z), tnear);
             const float f1 = __builtin_fminf(__builtin_fminf(__builtin_fminf((p.lfx - o.x) * inv_d.x, (p.lfy - o.y) * inv_d.y), (p.lfz - o.z) * inv_d.z), hit.t);
             const float d2 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf((p.rnx - o.x) * inv_d.x, (p.rny - o.y) * inv_d.y), (p.rnz - o.z) * inv_d.z), tnear);
@@ -395,7 +324,7 @@ RL_DEV bool traverse(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V3
         // every calling lane holds the SAME leaf (wave-uniform code): its triangle records come through the scalar cache as well; one test site
         // for both forms (a second inlined copy of tri_test upset the register allocation of the whole loop: 75 -> 93 ms in the tolerance build)
         bool uni = false;
-        if (Stack::NodeFetch::kHasUniform && RL_UNIFORM_TRIPS) uni = __ballot(cur != __builtin_amdgcn_readfirstlane(cur)) == 0ull;
+        if (Stack::NodeFetch::kHasUniform) uni = __ballot(cur != __builtin_amdgcn_readfirstlane(cur)) == 0ull;
         for (int k = 0; k < count; k++) {
             hit.tris++;
             float4 q0, q1, q2, q3;
@@ -456,9 +385,10 @@ RL_DEV bool traverse(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V3
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// traverse2 — the exact build's traversal of scenes that stream their BVH (round 5): two levels of the reference's recursion per fetched record
-// (device_types.h: BvhNode2; host: two_level_nodes).  The streaming kernels are bound by the latency of a ray's DEPENDENT record fetches (~19 per ray on the
-// 508 k-triangle scene; profiles/NEGATIVES.md round 4); a record that carries the grandchildren's exact boxes halves the chain at 2 x the bytes per fetch.
+// traverse2 — scenes that stream their BVH, two levels of the reference's recursion per fetched record (round 5; device_types.h: BvhNode2; host:
+// two_level_nodes).  The streaming kernels are bound by the latency of a ray's DEPENDENT record fetches (~19 per ray on the 508 k-triangle scene;
+// profiles/NEGATIVES.md round 4); a record that carries the grandchildren's exact boxes halves the chain at 2 x the bytes per fetch.  No shipped kernel
+// uses it: measured slower than `traverse` (profiles/NEGATIVES.md round 5); reached through TravStack2 (rl_debug_trace_batch_two_level) and kept tested.
 //
 // Same visits, same order, same bits as `traverse` — by construction:
 //  * AABB::intersect (src/structure.rs:849-869) is a pure function of (ray, tnear, tfar, box); its.t enters only through `if d < its.t` (accel.rs:277-284), folded
@@ -472,10 +402,9 @@ RL_DEV bool traverse(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V3
 //  * second level: the entered child's two slots with the same tnear and the same its.t — the one-level trip at that child, operation for operation.
 template <bool ANY_HIT, class Stack>
 RL_DEV bool traverse2(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V3 o, V3 d, float tnear, float tfar, Hit& hit, const Stack& st) {
-    constexpr bool LDS = Stack::kLdsOnly;       // the records are staged in LDS (stage_scene_lds<true>: 36 dwords apart, inner references = byte offsets)
     const V3 inv_d = mk3(div_rn(1.0f, d.x), div_rn(1.0f, d.y), div_rn(1.0f, d.z));
     float dummy;
-    int cur = (LDS && root >= 0) ? root * (4 * kLdsNode2Stride) : root;
+    int cur = root;
     if (!slab(root_lo, root_hi, o, inv_d, tnear, tfar, &dummy)) cur = RL_CHILD_NONE;   // accel.rs:293-295 / 338-340
     int sp = 0;
     bool found = false;
@@ -485,34 +414,24 @@ RL_DEV bool traverse2(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V
     const float inf = f32_inf();
     const bool unsafe = !((ax > 0.0f) & (ax < inf) & (ay > 0.0f) & (ay < inf) & (az > 0.0f) & (az < inf) &
                           (__builtin_fabsf(o.x) < inf) & (__builtin_fabsf(o.y) < inf) & (__builtin_fabsf(o.z) < inf));
-    // LDS: the sign of 1 / d picks the near / far plane row once per ray (byte offsets into a record: lox 0, loy 16, loz 32, hix 48, hiy 64, hiz 80, slots 96, children 112)
-    const int onx = sx ? 48 : 0, ofx = sx ? 0 : 48, ony = sy ? 64 : 16, ofy = sy ? 16 : 64, onz = sz ? 80 : 32, ofz = sz ? 32 : 80;
     auto node_trip = [&]() {
         if (cur >= 0) {
             hit.steps++;
             f4v npx, npy, npz, fpx, fpy, fpz, sl, ch;       // near / far PLANES of the four slots per axis, slot references, child references
-            if constexpr (LDS) {
-                typedef __attribute__((address_space(3))) const char LdsBytes;
-                LdsBytes* b = (LdsBytes*)(recs.nodes) + cur;
-#define RL_ROW(off) (*reinterpret_cast<__attribute__((address_space(3))) const f4v*>(b + (off)))
-                npx = RL_ROW(onx); fpx = RL_ROW(ofx); npy = RL_ROW(ony); fpy = RL_ROW(ofy); npz = RL_ROW(onz); fpz = RL_ROW(ofz); sl = RL_ROW(96); ch = RL_ROW(112);
-#undef RL_ROW
+            f4v lox, loy, loz, hix, hiy, hiz;
+            const int cur0 = __builtin_amdgcn_readfirstlane(cur);
+            if (__ballot(cur != cur0) == 0ull) {      // every lane holds the same node: through the scalar cache
+                const F4c* q = (const F4c*)(recs.nodes) + 8 * cur0;
+                lox = q[0]; loy = q[1]; loz = q[2]; hix = q[3]; hiy = q[4]; hiz = q[5]; sl = q[6]; ch = q[7];
             } else {
-                f4v lox, loy, loz, hix, hiy, hiz;
-                const int cur0 = __builtin_amdgcn_readfirstlane(cur);
-                if (RL_UNIFORM_TRIPS && __ballot(cur != cur0) == 0ull) {      // every lane holds the same node: through the scalar cache
-                    const F4c* q = (const F4c*)(recs.nodes) + 8 * cur0;
-                    lox = q[0]; loy = q[1]; loz = q[2]; hix = q[3]; hiy = q[4]; hiz = q[5]; sl = q[6]; ch = q[7];
-                } else {
-                    const f4v* q = reinterpret_cast<const f4v*>(recs.nodes) + 8 * cur;
-                    lox = q[0]; loy = q[1]; loz = q[2]; hix = q[3]; hiy = q[4]; hiz = q[5]; sl = q[6]; ch = q[7];
-                }
+                const f4v* q = reinterpret_cast<const f4v*>(recs.nodes) + 8 * cur;
+                lox = q[0]; loy = q[1]; loz = q[2]; hix = q[3]; hiy = q[4]; hiz = q[5]; sl = q[6]; ch = q[7];
+            }
 #pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    npx[k] = sx ? hix[k] : lox[k]; fpx[k] = sx ? lox[k] : hix[k];
-                    npy[k] = sy ? hiy[k] : loy[k]; fpy[k] = sy ? loy[k] : hiy[k];
-                    npz[k] = sz ? hiz[k] : loz[k]; fpz[k] = sz ? loz[k] : hiz[k];
-                }
+            for (int k = 0; k < 4; k++) {
+                npx[k] = sx ? hix[k] : lox[k]; fpx[k] = sx ? lox[k] : hix[k];
+                npy[k] = sy ? hiy[k] : loy[k]; fpy[k] = sy ? loy[k] : hiy[k];
+                npz[k] = sz ? hiz[k] : loz[k]; fpz[k] = sz ? loz[k] : hiz[k];
             }
             float nx[4], ny[4], nz[4], fx[4], fy[4], fz[4], tn[4], tf[4];
 #pragma unroll
@@ -574,8 +493,7 @@ RL_DEV bool traverse2(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V
     auto leaf_visit = [&]() -> bool {
         const unsigned int code = (unsigned int)(~cur);
         const int first = (int)(code >> 2), count = (int)(code & 3u);
-        bool uni = false;
-        if (!LDS && RL_UNIFORM_TRIPS) uni = __ballot(cur != __builtin_amdgcn_readfirstlane(cur)) == 0ull;
+        const bool uni = __ballot(cur != __builtin_amdgcn_readfirstlane(cur)) == 0ull;
         for (int k = 0; k < count; k++) {
             hit.tris++;
             float4 q0, q1, q2, q3;
@@ -595,28 +513,21 @@ RL_DEV bool traverse2(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V
         cur = kPop;
         return false;
     };
-    if constexpr (LDS) {
-        while (cur != RL_CHILD_NONE) {          // "while-while", as in traverse
-            while (cur >= 0 || cur == kPop) node_trip();
-            if (cur != RL_CHILD_NONE && leaf_visit()) return true;
-        }
-    } else {
 #if defined(RL_TRAVERSE_SPARSE)
-        while (cur != RL_CHILD_NONE) {          // k_stream_chain: no vote (see traverse)
-            if (cur >= 0 || cur == kPop) node_trip();
-            else if (leaf_visit()) return true;
-        }
-#else
-        for (;;) {
-            const bool in_node = cur >= 0 || cur == kPop;
-            const bool in_leaf = !in_node && cur != RL_CHILD_NONE;
-            const int n_node = __popcll(__ballot(in_node)), n_leaf = __popcll(__ballot(in_leaf));
-            if (n_node + n_leaf == 0) break;
-            if (n_node > 0 && n_node * RL_VOTE_DEN >= RL_VOTE_NUM * n_leaf) { if (in_node) node_trip(); }
-            else if (in_leaf && leaf_visit()) return true;
-        }
-#endif
+    while (cur != RL_CHILD_NONE) {          // k_stream_chain: no vote (see traverse)
+        if (cur >= 0 || cur == kPop) node_trip();
+        else if (leaf_visit()) return true;
     }
+#else
+    for (;;) {
+        const bool in_node = cur >= 0 || cur == kPop;
+        const bool in_leaf = !in_node && cur != RL_CHILD_NONE;
+        const int n_node = __popcll(__ballot(in_node)), n_leaf = __popcll(__ballot(in_leaf));
+        if (n_node + n_leaf == 0) break;
+        if (n_node > 0 && n_node * RL_VOTE_DEN >= RL_VOTE_NUM * n_leaf) { if (in_node) node_trip(); }
+        else if (in_leaf && leaf_visit()) return true;
+    }
+#endif
     if (!ANY_HIT && found) {
         const float4* q = recs.tris + Stack::kTriStride4 * hit.prim;
         tri_uv(q[0], q[1], q[2], q[3], o, d, hit.t, &hit.u, &hit.v);
@@ -648,7 +559,7 @@ RL_DEV bool traverse4(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V
             hit.steps++;
             uint4 q0, q1, q2; uint2 q3;
             const int cur0 = __builtin_amdgcn_readfirstlane(cur);
-            if (RL_UNIFORM_TRIPS && __ballot(cur != cur0) == 0ull) {      // every lane holds the same node: through the scalar cache
+            if (__ballot(cur != cur0) == 0ull) {      // every lane holds the same node: through the scalar cache
                 typedef unsigned u4v __attribute__((ext_vector_type(4)));
                 typedef const u4v __attribute__((address_space(4))) U4c;
                 const U4c* q = (const U4c*)(recs.nodes) + 4 * cur0;
@@ -677,11 +588,7 @@ RL_DEV bool traverse4(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V
             // sort the four (distance, child) pairs, nearest first (5 compare-exchanges; missed children carry +inf)
 #define RL_CE(i, j) { const bool sw = dist[j] < dist[i]; const float td = sw ? dist[j] : dist[i]; dist[j] = sw ? dist[i] : dist[j]; dist[i] = td; \
                       const int tc = sw ? code[j] : code[i]; code[j] = sw ? code[i] : code[j]; code[i] = tc; }
-#if defined(RL_BVH4_NOSORT)
-            RL_CE(0, 1) RL_CE(0, 2) RL_CE(0, 3)      // experiment: only the nearest child is found, the others are pushed in slot order
-#else
             RL_CE(0, 1) RL_CE(2, 3) RL_CE(0, 2) RL_CE(1, 3) RL_CE(1, 2)
-#endif
 #undef RL_CE
             // farthest first onto the stack, so that the nearest pending child is popped first
             if (dist[3] < f32_inf()) { st.push(sp, code[3], dist[3]); sp++; }
@@ -702,7 +609,7 @@ RL_DEV bool traverse4(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V
     auto leaf_visit = [&]() -> bool {
         const unsigned int code = (unsigned int)(~cur);
         const int first = (int)(code >> 2), count = (int)(code & 3u);
-        const bool uni = RL_UNIFORM_TRIPS && __ballot(cur != __builtin_amdgcn_readfirstlane(cur)) == 0ull;
+        const bool uni = __ballot(cur != __builtin_amdgcn_readfirstlane(cur)) == 0ull;
         for (int k = 0; k < count; k++) {
             hit.tris++;
             float4 q0, q1, q2, q3;
@@ -745,182 +652,6 @@ RL_DEV bool traverse4(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// Wave-cooperative traversal for scenes that stream their BVH from L2 / HBM (the persistent kernel on the 508 k-triangle scene).
-//
-// EXPERIMENT, OFF BY DEFAULT (RL_COOP_FETCH = 0; bit-identical images, but 144 ms (LDS staging) / 145 ms (registers + ds_bpermute) vs 97-110 ms at
-// 1080p x 32 spp: DESIGN.md §4).
-// The per-lane form is bound by the instruction throughput of the CU's vector-memory address path (TA busy 81-91 % of the kernel,
-// profiles/r02_ta_living_room.json; calibrated in profiles/r02_vmem_calibration.jsonl: a wave64 `global_load_dwordx4` holds that path for >= 17
-// cycles however few lanes are live, + 0.45 / 2.3 cycles per live lane from L2 / the Infinity Cache), and a node costs four such loads.  This form
-// replaces them by one or two full ones and still loses: finding, ranking and redistributing the records costs two LDS round trips (or 14-17
-// ds_bpermute) per trip and ballot-driven loops every lane stays in, more than the saved load instructions give back.
-// Here the live lanes' 64-byte records are fetched by the WHOLE wave: the wanting lanes are ranked (ballot + mbcnt), their record indices travel to the rank slots with one ds_permute,
-// lane L then loads quarter L % 4 of the record of rank L / 4 — a quad reads 64 contiguous bytes, one request — into a per-wave LDS
-// staging area (32 records = 2 KB), and every wanting lane reads its own record back from LDS, the planes through the same
-// sign-swizzled addresses the LDS-staged scenes use.  One or two coalesced load instructions per trip instead of four scattered
-// ones; lanes ranked 32 or higher simply take their turn on the next trip (the wave is well filled then).
-// Every lane of the wave must call this in step (wave-uniform control flow): the loops below are driven by ballots and a lane
-// without a ray (or whose ray is done) stays as a loader.  Visits, order and arithmetic per ray are those of `traverse`.
-static constexpr int kCoopRecords = 32;                         // records staged per wave and trip
-static constexpr int kCoopStageFloat4s = 4 * kCoopRecords;      // per wave
-RL_DEV unsigned lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-RL_DEV const float* coop_fetch64(const float4* base, int idx, bool want, float4* stage) {
-    const unsigned long long mask = __ballot(want);
-    const unsigned lane = lane_id();
-    const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));   // wanting lanes below this one
-    const unsigned n = (unsigned)__popcll(mask);
-    // record indices by rank: wanting lanes send theirs to slots 0 .. n-1, the others fill n .. 63 (a full permutation)
-    const unsigned slot = want ? below : n + (lane - below);
-    const int by_rank = __builtin_amdgcn_ds_permute((int)(slot << 2), idx);
-    const unsigned k0 = lane >> 2, q = lane & 3u;
-    const int id0 = __builtin_amdgcn_ds_bpermute((int)(k0 << 2), by_rank);
-    int id1 = 0;
-    if (n > 16u) id1 = __builtin_amdgcn_ds_bpermute((int)((k0 + 16u) << 2), by_rank);     // wave-uniform branch
-    const bool l0 = k0 < n, l1 = k0 + 16u < n;
-    float4 v0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), v1 = v0;
-    if (l0) v0 = base[4 * (size_t)id0 + q];          // both loads are in flight before either is stored
-    if (l1) v1 = base[4 * (size_t)id1 + q];
-    if (l0) stage[lane] = v0;
-    if (l1) stage[64u + lane] = v1;
-    // the records are read back by other lanes of this wave: LDS operations of one wave execute in order, the compiler only has to keep them so
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    return (want && below < (unsigned)kCoopRecords) ? reinterpret_cast<const float*>(stage + 4u * below) : nullptr;
-}
-
-// The same fetch without LDS memory (RL_COOP_FETCH = 2): the loaded quarters stay in the loader lanes' registers and every owner pulls its NDW
-// dwords with ds_bpermute (the LDS crossbar, no storage), so the kernel's LDS budget — and with it 6 waves/SIMD — is untouched.
-template <int NDW>
-RL_DEV bool coop_fetch_regs(const float4* base, int idx, bool want, float (&out)[NDW]) {
-    const unsigned long long mask = __ballot(want);
-    const unsigned lane = lane_id();
-    const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-    const unsigned n = (unsigned)__popcll(mask);
-    const unsigned slot = want ? below : n + (lane - below);
-    const int by_rank = __builtin_amdgcn_ds_permute((int)(slot << 2), idx);
-    const unsigned k0 = lane >> 2, q = lane & 3u;
-    const int id0 = __builtin_amdgcn_ds_bpermute((int)(k0 << 2), by_rank);
-    int id1 = 0;
-    if (n > 16u) id1 = __builtin_amdgcn_ds_bpermute((int)((k0 + 16u) << 2), by_rank);
-    float4 v0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), v1 = v0;
-    if (k0 < n) v0 = base[4 * (size_t)id0 + q];
-    if (k0 + 16u < n) v1 = base[4 * (size_t)id1 + q];
-    const unsigned src = (below & 15u) << 4;                     // byte address of lane 4 * (rank % 16) in the bpermute address space
-#pragma unroll
-    for (int f = 0; f < NDW; f++) {
-        const int addr = (int)(src + (unsigned)((f >> 2) << 2));
-        const float a0 = (f & 3) == 0 ? v0.x : (f & 3) == 1 ? v0.y : (f & 3) == 2 ? v0.z : v0.w;
-        float x = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(a0)));
-        if (n > 16u) {                                           // wave-uniform
-            const float a1 = (f & 3) == 0 ? v1.x : (f & 3) == 1 ? v1.y : (f & 3) == 2 ? v1.z : v1.w;
-            const float y = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(a1)));
-            x = below >= 16u ? y : x;
-        }
-        out[f] = x;
-    }
-    return want && below < 32u;
-}
-
-template <bool ANY_HIT, class Stack>
-RL_DEV bool traverse_coop(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V3 o, V3 d, float tnear, float tfar,
-                          Hit& hit, const Stack& st, bool valid, float4* stage) {
-    const V3 inv_d = mk3(div_rn(1.0f, d.x), div_rn(1.0f, d.y), div_rn(1.0f, d.z));
-    float dummy;
-    int cur = RL_CHILD_NONE;
-    if (valid && slab(root_lo, root_hi, o, inv_d, tnear, tfar, &dummy)) cur = root;   // accel.rs:293-295 / 338-340
-    int sp = 0, leaf_k = 0;
-    bool found = false;
-    constexpr int kPop = -1;
-    const bool sx = inv_d.x < 0.0f, sy = inv_d.y < 0.0f, sz = inv_d.z < 0.0f;
-    // dword offsets of the near / far planes of the left child inside a node record (the right child's are 6 further)
-    const int onx = sx ? 3 : 0, ofx = sx ? 0 : 3, ony = sy ? 4 : 1, ofy = sy ? 1 : 4, onz = sz ? 5 : 2, ofz = sz ? 2 : 5;
-    while (__ballot(cur != RL_CHILD_NONE) != 0ull) {
-        // ---- inner nodes and stack entries
-        while (__ballot(cur >= 0 || cur == kPop) != 0ull) {
-#if RL_COOP_FETCH == 2
-            float rec[14];
-            const bool got = coop_fetch_regs<14>(recs.nodes, cur, cur >= 0, rec);
-            if (got) {
-                hit.steps++;
-                const float lnx = sx ? rec[3] : rec[0], lfx = sx ? rec[0] : rec[3], lny = sy ? rec[4] : rec[1], lfy = sy ? rec[1] : rec[4], lnz = sz ? rec[5] : rec[2], lfz = sz ? rec[2] : rec[5];
-                const float rnx = sx ? rec[9] : rec[6], rfx = sx ? rec[6] : rec[9], rny = sy ? rec[10] : rec[7], rfy = sy ? rec[7] : rec[10], rnz = sz ? rec[11] : rec[8], rfz = sz ? rec[8] : rec[11];
-                const int id1 = __float_as_int(rec[12]), id2 = __float_as_int(rec[13]);
-#else
-            const float* rec = coop_fetch64(recs.nodes, cur, cur >= 0, stage);
-            if (rec) {
-                hit.steps++;
-                const float lnx = rec[onx], rnx = rec[onx + 6], lny = rec[ony], rny = rec[ony + 6], lnz = rec[onz], rnz = rec[onz + 6];
-                const float lfx = rec[ofx], rfx = rec[ofx + 6], lfy = rec[ofy], rfy = rec[ofy + 6], lfz = rec[ofz], rfz = rec[ofz + 6];
-                const int id1 = __float_as_int(rec[12]), id2 = __float_as_int(rec[13]);
-#endif
-                const float d1 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf((lnx - o.x) * inv_d.x, (lny - o.y) * inv_d.y), (lnz - o.z) * inv_d.z), tnear);
-                const float f1 = __builtin_fminf(__builtin_fminf(__builtin_fminf((lfx - o.x) * inv_d.x, (lfy - o.y) * inv_d.y), (lfz - o.z) * inv_d.z), hit.t);
-                const float d2 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf((rnx - o.x) * inv_d.x, (rny - o.y) * inv_d.y), (rnz - o.z) * inv_d.z), tnear);
-                const float f2 = __builtin_fminf(__builtin_fminf(__builtin_fminf((rfx - o.x) * inv_d.x, (rfy - o.y) * inv_d.y), (rfz - o.z) * inv_d.z), hit.t);
-                const bool v1 = !(f1 <= d1), v2 = !(f2 <= d2);
-                const bool right_first = v2 & (!v1 | (d1 > d2));
-                st.push(sp, right_first ? id1 : id2, right_first ? d1 : d2, v1 && v2);
-                sp += (v1 && v2) ? 1 : 0;
-                cur = (v1 || v2) ? (right_first ? id2 : id1) : kPop;
-            }
-            if (cur == kPop) {
-                cur = RL_CHILD_NONE;
-                if (sp > 0) {
-                    sp--;
-                    int code; float dist;
-                    st.get(sp, &code, &dist);
-                    cur = dist < hit.t ? code : kPop;
-                }
-            }
-        }
-        // ---- leaves (<= 2 triangles, tested in order: accel.rs:245-254); every lane that still has a ray holds one now
-        while (__ballot(cur != RL_CHILD_NONE && cur != kPop) != 0ull) {
-            const bool is_leaf = cur != RL_CHILD_NONE && cur != kPop;
-            const unsigned int code = (unsigned int)(~cur);
-            const int first = (int)(code >> 2), count = (int)(code & 3u);
-#if RL_COOP_FETCH == 2
-            float rec[13];
-            const bool got = coop_fetch_regs<13>(recs.tris, first + leaf_k, is_leaf, rec);
-            if (got) {
-                hit.tris++;
-                const float4 q[4] = {make_float4(rec[0], rec[1], rec[2], rec[3]), make_float4(rec[4], rec[5], rec[6], rec[7]), make_float4(rec[8], rec[9], rec[10], rec[11]), make_float4(rec[12], 0.0f, 0.0f, 0.0f)};
-#else
-            const float* rec = coop_fetch64(recs.tris, first + leaf_k, is_leaf, stage);
-            if (rec) {
-                hit.tris++;
-                const float4* q = reinterpret_cast<const float4*>(rec);
-#endif
-                const bool accepted = tri_test(q[0], q[1], q[2], q[3], o, d, hit, first + leaf_k);
-                found = found || accepted;
-                leaf_k++;
-                if (ANY_HIT && accepted) { cur = RL_CHILD_NONE; leaf_k = 0; }
-                else if (leaf_k == count) { cur = kPop; leaf_k = 0; }
-            }
-        }
-    }
-    if (!ANY_HIT) {   // barycentrics of the closest hit (see tri_test)
-        bool need = found;
-        while (__ballot(need) != 0ull) {
-#if RL_COOP_FETCH == 2
-            float rec[13];
-            const bool got = coop_fetch_regs<13>(recs.tris, hit.prim, need, rec);
-            if (got) {
-                const float4 q[4] = {make_float4(rec[0], rec[1], rec[2], rec[3]), make_float4(rec[4], rec[5], rec[6], rec[7]), make_float4(rec[8], rec[9], rec[10], rec[11]), make_float4(rec[12], 0.0f, 0.0f, 0.0f)};
-#else
-            const float* rec = coop_fetch64(recs.tris, hit.prim, need, stage);
-            if (rec) {
-                const float4* q = reinterpret_cast<const float4*>(rec);
-#endif
-                tri_uv(q[0], q[1], q[2], q[3], o, d, hit.t, &hit.u, &hit.v);
-                need = false;
-            }
-        }
-    }
-    return found;
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------
 // Lane-parallel records + serial walk (k_stream_chain on tiny LDS-staged scenes, round 3).
 // A chain of the draw-count pass traces ONE ray at a time while the other lanes of its group (32 or 64) idle, and 2/3 of the pass is that ray's
 // traversal at one instruction per ~5 cycles.  Here the group first evaluates everything about the ray that does not depend on the traversal
@@ -942,12 +673,8 @@ RL_DEV bool tri_inside(const float4 q0, const float4 q1, const float4 q2, const 
 #if defined(RL_FAST_MATH)
     return facing & (det > 0.0f) & (__builtin_amdgcn_sqrtf(uu) + __builtin_amdgcn_sqrtf(ww) <= det);
 #else
-#if defined(RL_TRI_REFERENCE_FORM)
-    const bool in_range = false; const float s = 0.0f;
-#else
     const float s = __builtin_amdgcn_sqrtf(uu) + __builtin_amdgcn_sqrtf(ww);
     const bool in_range = __builtin_fminf(__builtin_fminf(uu, ww), det) >= 0x1p-100f;
-#endif
     const bool sure_in = in_range & (s <= det * 0.99999f), sure_out = in_range & (s >= det * 1.00001f);
     bool accept = facing & sure_in;
     if (facing & !sure_in & !sure_out) {
@@ -1153,22 +880,6 @@ RL_DEV void stage_scene_lds(const DeviceScene& sc, float4* lds_nodes, float4* ld
         float v = gn[i];
         if (f >= 12u) { const int id = __float_as_int(v); if (id >= 0) v = __int_as_float(id * 4 * kLdsNodeStride); }   // byte offset
         ln[node * (unsigned)kLdsNodeStride + f] = v;
-    }
-    for (unsigned int i = threadIdx.x; i < 4u * sc.n_prims; i += blockDim.x) lds_tris[(i >> 2) * (unsigned)kLdsTriStride4 + (i & 3u)] = gt[i];
-    __syncthreads();
-}
-
-// The same with the nodes as two-level records (device_types.h: BvhNode2) kLdsNode2Stride dwords apart; inner references (slots and children) become byte offsets.
-RL_DEV void stage_scene_lds2(const DeviceScene& sc, float4* lds_nodes, float4* lds_tris) {
-    const float* gn = reinterpret_cast<const float*>(sc.nodes2);
-    const float4* gt = reinterpret_cast<const float4*>(sc.tris);
-    float* ln = reinterpret_cast<float*>(lds_nodes);
-    for (unsigned int i = threadIdx.x; i < 32u * sc.n_nodes; i += blockDim.x) {
-        const unsigned int node = i >> 5, f = i & 31u;
-        if (f >= 30u) continue;                                  // padding words of the 128-byte record
-        float v = gn[i];
-        if (f >= 24u) { const int id = __float_as_int(v); if (id >= 0) v = __int_as_float(id * 4 * kLdsNode2Stride); }   // byte offset
-        ln[node * (unsigned)kLdsNode2Stride + f] = v;
     }
     for (unsigned int i = threadIdx.x; i < 4u * sc.n_prims; i += blockDim.x) lds_tris[(i >> 2) * (unsigned)kLdsTriStride4 + (i & 3u)] = gt[i];
     __syncthreads();

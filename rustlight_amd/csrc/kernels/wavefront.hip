@@ -40,7 +40,6 @@
 
 #include "common.hip.h"
 #include "rngjump.h"
-#include "fused.hip.h"     // RL_COOP_FETCH (LDS budget of the persistent kernel); the kernel template is not instantiated here
 #include "../host/scene.h"
 #include "wavefront.h"
 #include "knobs.h"
@@ -391,9 +390,8 @@ extern "C" int rl_context_create(const rl_scene* scene, int device, rl_context**
         ds.nodes4 = nullptr; ds.root4 = RL_CHILD_NONE; ds.stack_depth4 = 0;
         ds.nodes_t = nullptr; ds.root_t = RL_CHILD_NONE;
         ds.nodes2 = nullptr;
-        // the two-level records (traverse2; 128 B per node, twice the node array) are read by kernels built with RL_TWO_LEVEL / RL_LDS_TWO_LEVEL only — both off in
-        // the shipped build (profiles/NEGATIVES.md round 5) — and by the test hook rl_debug_trace_batch_two_level, which builds them on its first call
-        if ((RL_TWO_LEVEL || RL_LDS_TWO_LEVEL) && (rc = ensure_two_level(ctx)) != RL_OK) break;
+        // the two-level records (traverse2; 128 B per node, twice the node array) are read only by the test hook rl_debug_trace_batch_two_level, which builds them
+        // on its first call
         if ((rc = upload(ctx, flat.tri_indices, &ds.tri_indices)) != RL_OK) break;
         if ((rc = upload(ctx, flat.positions, &ds.positions)) != RL_OK) break;
         if ((rc = upload(ctx, flat.normals, &ds.normals)) != RL_OK) break;
@@ -460,14 +458,13 @@ extern "C" int rl_context_create(const rl_scene* scene, int device, rl_context**
         // stage the scene in LDS when nodes + triangles are small (<= 48 KiB leaves room for the stacks)
         ctx->scene_lds_bytes = (size_t)16 * lds_scene_float4s(ds.n_nodes, ds.n_prims);     // padded LDS layout (trace.hip.h)
         // LDS-staged scenes also keep their whole traversal stack in LDS (TravStackT<true>)
-        ctx->lds_scene = ctx->scene_lds_bytes <= 48 * 1024 && ds.stack_depth <= (uint32_t)kLdsStackLevels && (!RL_LDS_TWO_LEVEL || (size_t)16 * lds_scene2_float4s(ds.n_nodes, ds.n_prims) <= 64 * 1024);
+        ctx->lds_scene = ctx->scene_lds_bytes <= 48 * 1024 && ds.stack_depth <= (uint32_t)kLdsStackLevels;
         {   // worst-case dynamic LDS of any kernel that stages the scene: [scene][compaction list | cold path state][12 stack levels];
             // it must fit what a workgroup may ask for on this device, else the scene streams from L2 / HBM instead
             int lds_limit = 64 * 1024;
             if (hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) { (void)hipGetLastError(); lds_limit = 64 * 1024; }
             ctx->lds_limit = (size_t)std::max(lds_limit, 16 * 1024);
-            const size_t scene2 = RL_LDS_TWO_LEVEL ? (size_t)16 * lds_scene2_float4s(ds.n_nodes, ds.n_prims) : 0;      // k_path_fused's staging (two-level node records)
-            const size_t worst = std::max(ctx->scene_lds_bytes, scene2) + std::max<size_t>(272 * sizeof(unsigned), kFusedColdBytes) + (size_t)2 * kLdsStackLevels * 256 * sizeof(int);
+            const size_t worst = ctx->scene_lds_bytes + std::max<size_t>(272 * sizeof(unsigned), kFusedColdBytes) + (size_t)2 * kLdsStackLevels * 256 * sizeof(int);
             if (worst > (size_t)lds_limit) ctx->lds_scene = false;
         }
         if (ctx->knobs.has(K_FORCE_STREAMING)) ctx->lds_scene = false;     // dev / test knob: small scenes through the kernels that stream the BVH (tests/parity_fuzz.py)
