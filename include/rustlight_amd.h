@@ -348,7 +348,9 @@ int rl_render_path(rl_context* ctx, const rl_path_params* params, const uint64_t
  * vertex splatted through the camera (Camera::sample_direct).  Takes rl_path_params: spp, the three depth options, `strategy` as rl_light_strategy, `seed_variant`;
  * `block_seeds` as for rl_render_path.  Job b (the 16x16 blocks in creation order) traces spp x (pixels of block b) light paths; light path (b, slot p, sample s)
  * draws from the stream RL_STREAM_PER_SAMPLE gives camera sample (b, pixel p, s).  The reference splits its paths over 4 x threads jobs, so no seed matches it
- * path for path: the image agrees in distribution.  Splats are summed in signed 64-bit fixed point (24 fraction bits): same seeds, same bits.  A splat with a
+ * path for path: the image agrees in distribution.  Splats are summed per pixel and channel in 96-bit unsigned fixed point (24 fraction bits; a 64-bit
+ * low word and a 32-bit carry count): same seeds, same bits, exact while a channel takes fewer than 2^41 clamped splats, so no finite splat can make a pixel
+ * negative or wrap it; the pixel is the f32 of (carry * 2^64 + low) * 2^-24 / spp computed in f64.  A splat with a
  * negative or NaN channel is dropped (Color::is_valid); a +inf channel makes the pixel's channel +inf; a channel >= 2^31 is clamped.  RL_ERR_UNSUPPORTED for
  * stream_mode other than RL_STREAM_PER_SAMPLE, numerics = RL_NUMERICS_FAST, shard_count > 1 and scenes with an environment emitter; RL_ERR_NO_EMITTER without
  * emitters.  The counters mean: camera_samples = light paths traced, vertices = expanded vertices (the light vertex included), extension_rays = closest-hit rays,

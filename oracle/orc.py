@@ -39,6 +39,13 @@ class OrcStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OrcLightStats(C.Structure):
+    _fields_ = [("splats", C.c_uint64), ("splats_invalid", C.c_uint64), ("splats_saturated", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def build(force: bool = False) -> str:
     srcs = [os.path.join(_HERE, f) for f in ("rl_oracle.cpp", "rl_oracle.h", "detmath.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "rustlight_amd.h"))
@@ -95,6 +102,7 @@ def lib():
         L.orc_generate_block_seeds.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
         L.orc_math_batch.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.orc_camera_generate.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.orc_camera_sample_direct.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.orc_scene_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
         L.orc_bvh_dump.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -112,6 +120,11 @@ def lib():
                                       C.POINTER(C.c_float), C.c_int, C.POINTER(OrcStats)]
         L.orc_render_mc.argtypes = [C.c_void_p, C.c_int, C.POINTER(OrcMcParams), C.POINTER(C.c_uint64), C.c_size_t,
                                     C.POINTER(C.c_float), C.c_int, C.POINTER(OrcStats)]
+        L.orc_render_light.argtypes = [C.c_void_p, C.POINTER(OrcPathParams), C.POINTER(C.c_uint64), C.c_size_t,
+                                       C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int, C.POINTER(OrcStats),
+                                       C.POINTER(OrcLightStats)]
+        L.orc_stratified_draws.argtypes = [C.c_size_t, C.POINTER(C.c_uint64), C.c_uint32, C.c_int, C.c_size_t, C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -148,6 +161,19 @@ class Rng:
 
     def next_f32(self) -> float:
         return float(lib().orc_rng_next_f32(self.state))
+
+
+def stratified_draws(pixel_seeds, spp: int, pattern, seed_variant: int = 0) -> np.ndarray:
+    """The oracle's RL_STREAM_STRATIFIED sampler with the contract of api.stratified_draws: pixel p, whose per-sample-mode seed is pixel_seeds[p],
+    walks its spp samples; each sample makes the calls of `pattern` (1 = next(), 2 = next2d()).  float32 [n_pixels, spp, sum(pattern)]."""
+    seeds = np.ascontiguousarray(pixel_seeds, dtype=np.uint64).reshape(-1)
+    pat = np.ascontiguousarray(pattern, dtype=np.int32).reshape(-1)
+    out = np.zeros((seeds.shape[0], spp, int(pat.sum())), dtype=np.float32)
+    rc = lib().orc_stratified_draws(seeds.shape[0], abi.u64ptr(seeds), spp, seed_variant, pat.shape[0], pat.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    abi.fptr(out))
+    if rc != 0:
+        raise RuntimeError(f"orc_stratified_draws failed: {rc}")
+    return out
 
 
 def block_seeds(master_seed: int, width: int, height: int, variant: int = 0) -> np.ndarray:
@@ -242,6 +268,13 @@ class Scene:
         lib().orc_camera_generate(self.h, px, py, o, d)
         return np.array(o[:], dtype=np.float32), np.array(d[:], dtype=np.float32)
 
+    def sample_direct(self, p):
+        """Camera::sample_direct (camera.rs:94-118): None, or (importance, screen position in pixels)."""
+        pp = np.asarray(p, np.float32); out = np.zeros(3, np.float32)
+        if not lib().orc_camera_sample_direct(self.h, abi.fptr(pp), abi.fptr(out)):
+            return None
+        return float(out[0]), out[1:3]
+
     def trace(self, origins, directions, brute=False):
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
@@ -328,5 +361,30 @@ def _render_mc(self, kind, master_seed=0, threads=0, seeds=None, spp=1, stream_m
     return img, st.as_dict()
 
 
+def _render_light(self, seeds=None, spp=1, min_depth=0, max_depth=None, rr_depth=0, strategy=0, seed_variant=0, stream_mode=1, master_seed=0,
+                  threads=0, want_f64=False):
+    """IntegratorLightTracing as rl_render_light computes it (the keyword arguments of api.Context.render_light; strategy: 0 = all, 1 = surface,
+    2 = volume): (image HxWx3 f32, stats dict) or, with want_f64, (image, stats, f64 HxWx3: every pixel's clamped splats summed without
+    quantisation, times 1 / spp, counts HxW: the splats every pixel took).  stats carry splats / splats_invalid / splats_saturated as the GPU's."""
+    p = path_params(spp=spp, min_depth=min_depth, max_depth=max_depth, rr_depth=rr_depth, strategy=strategy, stream_mode=stream_mode,
+                    seed_variant=seed_variant)
+    sd = self.sd
+    if seeds is None:
+        seeds = block_seeds(master_seed, sd.width, sd.height, seed_variant)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+    img = np.zeros((sd.height, sd.width, 3), dtype=np.float32)
+    f64 = np.zeros((sd.height, sd.width, 3), dtype=np.float64) if want_f64 else None
+    cnt = np.zeros((sd.height, sd.width), dtype=np.uint32) if want_f64 else None
+    st, lst = OrcStats(), OrcLightStats()
+    rc = lib().orc_render_light(self.h, C.byref(p), abi.u64ptr(seeds), seeds.shape[0], abi.fptr(img),
+                                f64.ctypes.data_as(C.POINTER(C.c_double)) if want_f64 else None,
+                                cnt.ctypes.data_as(C.POINTER(C.c_uint32)) if want_f64 else None, threads, C.byref(st), C.byref(lst))
+    if rc != 0:
+        raise RuntimeError(f"orc_render_light failed: {rc}")
+    d = dict(st.as_dict(), **lst.as_dict())
+    return (img, d, f64, cnt) if want_f64 else (img, d)
+
+
+Scene.render_light = _render_light
 Scene.render_ao = lambda self, **kw: _render_mc(self, 0, **kw)
 Scene.render_direct = lambda self, **kw: _render_mc(self, 1, **kw)

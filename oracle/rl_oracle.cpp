@@ -40,6 +40,7 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <map>
@@ -194,15 +195,84 @@ struct Rng {
     }
 };
 
-// IndependentSampler (src/samplers/independent.rs:5-34)
+// RL_STREAM_STRATIFIED: the port's own stratified sampler (the reference's StratifiedSampler, samplers/stratified.rs, shuffles arrays it
+// fills from `random()`, so nothing matches it seed for seed).  Restated from the specification in include/rustlight_amd.h (rl_stream_mode) and
+// the header comment of the kernels' sampler, not from its code:
+//   * n = the smallest power of four >= spp; 4 one-dimensional and 4 two-dimensional dimensions per camera sample (StratifiedSampler::create(spp, 4));
+//   * per pixel a key: the SplitMix64 finaliser of (the pixel's per-sample-mode seed ^ 0x5851f42d4c957f2d);
+//   * dimension k (0-3: 1D, 4-7: 2D) hashes key + (k + 1) * 0x9e3779b97f4a7c15 with the same finaliser into h; sample s takes stratum
+//     (permute(s, n - 1, low 32 bits of h) + high 32 bits of h) mod n, permute = Kensler's keyed bijection ("Correlated Multi-Jittered Sampling", 2013);
+//   * a 1D value is (stratum + u) / n, u the next 24-bit draw of the sample's own Rng, the sum truncated (not rounded) to 24 significant bits and
+//     clamped to 1 - f32::EPSILON (stratified.rs:52); a 2D cell c of a sqrt(n) x sqrt(n) grid gives x from row c / sqrt(n), then y from column c % sqrt(n);
+//   * the k-th next() reads 1D dimension k, the k-th next2d() 2D dimension k (independent counters); past the fourth of a kind the plain Rng draws.
+namespace strat {
+static const uint32_t DIMS = 4;
+static inline uint64_t mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+static inline uint32_t log2n(uint32_t spp) {   // log2 of the smallest power of four >= spp
+    uint32_t lg = 0;
+    while ((1ull << lg) < (uint64_t)spp) lg += 2;
+    return lg;
+}
+static inline uint32_t permute(uint32_t i, uint32_t l, uint32_t p) {   // Kensler 2013, listing 3, for l = 2^k (no cycle walking needed)
+    uint32_t w = l - 1;
+    i ^= p; i *= 0xe170893d; i ^= p >> 16; i ^= (i & w) >> 4;
+    i ^= p >> 8; i *= 0x0929eb3f; i ^= p >> 23; i ^= (i & w) >> 1;
+    i *= 1 | p >> 27; i *= 0x6935fa69; i ^= (i & w) >> 11; i *= 0x74dcb303;
+    i ^= (i & w) >> 2; i *= 0x9e501cc3; i ^= (i & w) >> 2; i *= 0xc860a3df;
+    i &= w; i ^= i >> 5;
+    return i & w;
+}
+static inline float value(uint64_t stratum, Rng& rng, uint32_t lg) {   // (stratum + u) / 2^lg, truncated to 24 bits, clamped
+    uint64_t x = stratum * 16777216ull + (rng.next_u64() >> 40);
+    int bits = 0;
+    while (bits < 64 && (x >> bits) > 1) bits++;
+    bits += 1;                                                        // significant bits of x (1 for x = 0)
+    if (bits > 24) x &= ~((1ull << (bits - 24)) - 1);
+    float v = std::ldexp((float)x, -(int)(24 + lg));                  // exact: x has at most 24 significant bits
+    return std::fmin(v, 1.0f - FLT_EPSILON);
+}
+}  // namespace strat
+
+// IndependentSampler (src/samplers/independent.rs:5-34); with `strat` set, the stratified sampler above on the same Rng
 struct Sampler {
-    Rng rnd;
+    Rng rnd{};
     int variant = 0;
     uint64_t draws = 0;
-    float next() { draws++; return rnd.next_f32(); }
-    V2 next2d() { float x = next(); float y = next(); return {x, y}; }
+    bool strat = false;
+    uint64_t key = 0;             // strat::mix64(pixel seed ^ ...)
+    uint32_t s = 0, lg = 0;       // sample index, log2 n
+    uint32_t used1 = 0, used2 = 0;
+    uint32_t stratum(uint32_t dim) const {
+        uint64_t h = strat::mix64(key + (uint64_t)(dim + 1) * 0x9e3779b97f4a7c15ull);
+        uint32_t n = 1u << lg;
+        return (strat::permute(s & (n - 1), n, (uint32_t)h) + (uint32_t)(h >> 32)) & (n - 1);
+    }
+    float next() {
+        draws++;
+        if (strat && used1 < strat::DIMS) return strat::value(stratum(used1++), rnd, lg);
+        return rnd.next_f32();
+    }
+    V2 next2d() {
+        if (strat && used2 < strat::DIMS) {
+            draws += 2;
+            uint32_t cell = stratum(strat::DIMS + used2++), half = lg / 2;
+            float x = strat::value(cell >> half, rnd, half);
+            float y = strat::value(cell & ((1u << half) - 1), rnd, half);
+            return {x, y};
+        }
+        draws += 2;
+        float x = rnd.next_f32(); float y = rnd.next_f32(); return {x, y};
+    }
     Sampler clone_box() { Sampler s; s.rnd = Rng::seed_from_u64(rnd.next_u64(), variant); s.variant = variant; return s; }
 };
+// the stratified sampler of sample `s` of the pixel whose per-sample-mode seed is `pixel_seed`, on the sample's forked Rng
+static inline void strat_begin(Sampler& sm, uint64_t pixel_seed, uint32_t s, uint32_t spp) {
+    sm.strat = true; sm.key = strat::mix64(pixel_seed ^ 0x5851f42d4c957f2dull); sm.s = s; sm.lg = strat::log2n(spp); sm.used1 = sm.used2 = 0;
+}
 
 // ------------------------------------------------------------------------------------------
 // sampling math (src/math.rs:37-72, 388-394)
@@ -1041,7 +1111,38 @@ struct Camera {
                                .mul(M4::from_translation({-1.0f, -1.0f / aspect, 0.0f}))
                                .mul(perspective(fov_rad, 1.0f, 1e-2f, 1000.0f))
                                .mul(M4::from_nonuniform_scale(x_v, 1.0f, -1.0f));
-        return camera_to_sample.invert(&sample_to_camera);
+        if (!camera_to_sample.invert(&sample_to_camera)) return false;
+        // the image plane in camera space (camera.rs:53-58)
+        V3 p0 = sample_to_camera.transform_point({0.0f, 0.0f, 0.0f}), p1 = sample_to_camera.transform_point({1.0f, 1.0f, 0.0f});
+        float zmin = rmin(p0.z, p1.z), zmax = rmax(p0.z, p1.z);
+        rect_min = {rmin(p0.x, p1.x) / zmin, rmin(p0.y, p1.y) / zmin};
+        rect_max = {rmax(p0.x, p1.x) / zmax, rmax(p0.y, p1.y) / zmax};
+        return true;
+    }
+    V2 rect_min{0, 0}, rect_max{0, 0};
+    // Camera::importance (camera.rs:120-138), with the reference's `p.x > self.image_rect_max.y` (sic) in the last test
+    float importance(V3 d) const {
+        float cos_t = d.z;
+        if (cos_t <= 0.0f) return 0.0f;
+        float inv_cos = 1.0f / cos_t;
+        V2 p = {d.x * inv_cos, d.y * inv_cos};
+        if (p.x < rect_min.x || p.x > rect_max.x || p.y < rect_min.y || p.x > rect_max.y) return 0.0f;
+        float size = (rect_max.x - rect_min.x) * (rect_max.y - rect_min.y);
+        return (1.0f / size) * inv_cos * inv_cos * inv_cos;
+    }
+    // Camera::sample_direct (camera.rs:94-118): false = None; *imp = Color::value(importance) * inv_dist * inv_dist, *px = the screen position in pixels
+    bool sample_direct(V3 p, Color* imp, V2* px) const {
+        V3 ref = to_local.transform_point(p);
+        if (ref.z < 0.0f) return false;
+        V3 sp = camera_to_sample.transform_point(ref);
+        if (sp.x < 0.0f || sp.x > 1.0f || sp.y < 0.0f || sp.y > 1.0f) return false;
+        *px = {sp.x * (float)w, sp.y * (float)h};
+        float inv_dist = 1.0f / magnitude(ref);
+        V3 local_d = ref * inv_dist;
+        float imp_v = importance(local_d);
+        if (imp_v == 0.0f) return false;
+        *imp = Color::value(imp_v) * inv_dist * inv_dist;
+        return true;
     }
     V3 position() const { return to_world.transform_point({0, 0, 0}); }
     Ray generate(V2 px) const {
@@ -2064,6 +2165,200 @@ static Color direct_compute_pixel(const Scene& scene, const DirectParams& dp, ui
     return l_i;
 }
 
+// ------------------------------------------------------------------------------------------
+// IntegratorLightTracing (src/integrators/explicit/light.rs): light paths from the emitters (Path::from_light, paths/path.rs:35-55), generated by
+// DirectionalSamplingStrategy with Transport::Importance (strategies/directional.rs:13-205), every vertex splatted through Camera::sample_direct
+// (TechniqueLightTracing::evaluate, light.rs:35-210).  The jobs and their streams are the port's documented deviations (include/rustlight_amd.h,
+// rl_render_light): light path (block b, slot p, sample s) draws from the per-sample stream of camera sample (b, p, s), and the splats go into a
+// fixed-point image (LightImage) instead of the reference's f32 per-job images.  Two counting choices, neither of which changes a splat:
+//   * the reference tests Acceleration::visible before Camera::sample_direct (light.rs:61-63, 93-96, 145-146); both are pure, so this oracle asks
+//     sample_direct first and counts a camera-connection ray only for a connection that lands on the image plane (the rays a port has to trace);
+//   * `splats` counts valid splats inside the image (zero-valued ones included), `splats_invalid` splats dropped by Color::is_valid, `splats_saturated`
+//     splats with a clamped or +inf channel.
+struct LightParams { PathParams path; bool render_surface = true, render_volume = true; };
+struct LightCounters { uint64_t added = 0, invalid = 0, saturated = 0; };
+
+// The port's splat image: per pixel and channel a 96-bit unsigned fixed-point sum (24 fraction bits) of the clamped splats, an +inf flag, and
+// beside it the same clamped values summed in f64 without quantisation (the order of that sum follows the threads: use it as a bound only).
+static const int LIGHT_FIX_BITS = 24;
+static const float LIGHT_SPLAT_MAX = 2147483648.0f;   // 2^31
+struct LightImage {
+    uint32_t W = 0, H = 0;
+    std::vector<unsigned __int128> sum;
+    std::vector<double> f64;
+    std::vector<uint8_t> inf;
+    std::vector<uint32_t> count;     // splats added per pixel
+    std::vector<std::mutex> locks;
+    LightImage(uint32_t w, uint32_t h) : W(w), H(h), sum(3 * (size_t)w * h, 0), f64(3 * (size_t)w * h, 0.0), inf(3 * (size_t)w * h, 0), count((size_t)w * h, 0), locks(1024) {}
+    // BufferCollection::accumulate_safe (integrators/mod.rs:160-175) into the fixed-point image
+    void splat(Color c, V2 px, LightCounters& lc) {
+        if (!(c.r >= 0.0f && c.g >= 0.0f && c.b >= 0.0f)) { lc.invalid++; return; }   // Color::is_valid (structure.rs:156-158)
+        int32_t x = as_i32(px.x), y = as_i32(px.y);                                   // Point2::new(uv.x as i32, uv.y as i32)
+        if (x < 0 || y < 0 || x >= (int32_t)W || y >= (int32_t)H) return;
+        lc.added++;
+        size_t pix = (size_t)y * W + (size_t)x;
+        bool sat = false;
+        std::lock_guard<std::mutex> g(locks[pix % locks.size()]);
+        count[pix]++;
+        for (int k = 0; k < 3; k++) {
+            float v = c.get(k);
+            if (v == 0.0f) continue;
+            if (v == F32_INF) { inf[3 * pix + k] = 1; sat = true; continue; }
+            if (v >= LIGHT_SPLAT_MAX) { v = LIGHT_SPLAT_MAX; sat = true; }
+            sum[3 * pix + k] += (uint64_t)std::nearbyint(std::ldexp(v, LIGHT_FIX_BITS));   // round half to even, as rintf
+            f64[3 * pix + k] += (double)v;
+        }
+        if (sat) lc.saturated++;
+    }
+    // the resolve: f32 of (high * 2^64 + (double)low) * 2^-24 / spp, in f64; a flagged channel is +inf
+    void resolve(uint32_t spp, float* out, double* out_f64, uint32_t* out_count) const {
+        if (out_count) std::memcpy(out_count, count.data(), count.size() * sizeof(uint32_t));
+        for (size_t i = 0; i < sum.size(); i++) {
+            double hi = (double)(uint64_t)(sum[i] >> 64), lo = (double)(uint64_t)sum[i];
+            double v = (hi * 18446744073709551616.0 + lo) * (1.0 / 16777216.0) / (double)spp;
+            out[i] = inf[i] ? F32_INF : (float)v;
+            if (out_f64) out_f64[i] = inf[i] ? (double)F32_INF : f64[i] / (double)spp;
+        }
+    }
+};
+
+struct LightTracer {
+    const Scene& scene;
+    LightParams prm;
+    PathTracer pt;            // the path graph, Edge::from_ray and the surface / volume bounce (Transport::Importance, as explicit/path.rs)
+    Counters& cnt;
+    LightCounters lcnt;
+    LightTracer(const Scene& s, const LightParams& p) : scene(s), prm(p), pt(s, p.path), cnt(pt.cnt) {}
+
+    // DirectionalSamplingStrategy::bounce of a Vertex::Light (directional.rs:155-205): Emitter::sample_direction, no Russian roulette
+    int light_bounce(int vid, Color& throughput, Sampler& sampler) {
+        const Vertex lv = pt.path.vertices[vid];
+        const EmitterRec& em = scene.emitters[lv.emitter];
+        V2 u = sampler.next2d();
+        V3 d; PDF pdf = PDF::solid_angle(0.0f); Color weight = Color::one();
+        if (em.kind == EM_MESH) {                       // Mesh::sample_direction (emitter.rs:705-724)
+            V3 d_out = cosine_sample_hemisphere(u);
+            if (d_out.z < 0.0f) { weight = Color::zero(); pdf = PDF::solid_angle(0.0f); }
+            else pdf = PDF::solid_angle(d_out.z * FRAC_1_PI);
+            d = Frame::make(lv.n).to_world(d_out);
+        } else if (em.kind == EM_POINT) {               // PointEmitter::sample_direction (emitter.rs:231-237)
+            d = sample_uniform_sphere(u); pdf = PDF::solid_angle(FRAC_1_PI * 0.25f);
+        } else {                                        // DirectionalLight::sample_direction (emitter.rs:178-184)
+            d = lv.n; pdf = PDF::discrete(1.0f);
+        }
+        mul_assign(throughput, weight);
+        if (throughput.is_zero()) return -1;
+        int edge = -1, nv = -1;
+        pt.edge_from_ray(Ray::make(lv.pos, d), vid, pdf, weight, 1.0f, sampler, 0, &edge, &nv);
+        Vertex& v = pt.path.vertices[vid];
+        v.edge_out[v.n_out++] = edge;
+        return nv;
+    }
+    // paths/strategies/mod.rs:35-80 with TechniqueLightTracing::expand (light.rs:26-28)
+    void generate(int root, Sampler& sampler) {
+        int curr = root;
+        Color thr = Color::one();
+        uint32_t depth = 1;
+        while (curr >= 0) {
+            int next = -1;
+            bool expand = prm.path.has_max ? depth < prm.path.max_depth : true;
+            if (depth >= ORC_DEPTH_CAP) expand = false;
+            if (expand) {
+                cnt.vertices++;
+                Color t = thr;
+                int nv = pt.path.vertices[curr].kind == Vertex::Light ? light_bounce(curr, t, sampler) : pt.directional_sample(curr, t, sampler, depth);
+                if (nv >= 0) { next = nv; thr = t; }
+            }
+            curr = next;
+            depth++;
+        }
+    }
+    Color transmittance(V3 p, V3 cam) const { return scene.has_volume ? scene.volume.transmittance(magnitude(p - cam)) : Color::one(); }
+    // TechniqueLightTracing::evaluate (light.rs:35-210)
+    void evaluate(uint32_t depth, int vid, Color flux, LightImage& img) {
+        const Vertex& vx = pt.path.vertices[vid];
+        bool accumulate = prm.path.has_min ? prm.path.min_depth <= depth : true;
+        V3 cam = scene.camera.position();
+        Color imp; V2 px;
+        if (vx.kind == Vertex::Volume) {
+            if (accumulate && prm.render_volume && scene.camera.sample_direct(vx.pos, &imp, &px)) {
+                cnt.shadow_rays++;
+                if (scene.visible(vx.pos, cam)) {
+                    V3 d = normalize(cam - vx.pos);
+                    Color bsdf_value = scene.volume.phase_eval(vx.d_in, d);
+                    img.splat(flux * imp * bsdf_value * transmittance(vx.pos, cam), px, lcnt);
+                }
+            }
+        } else if (vx.kind == Vertex::Surface) {
+            const Intersection& its = vx.its;
+            const BSDF& bsdf = scene.meshes[its.mesh].bsdf;
+            if (accumulate && prm.render_surface && !bsdf.is_smooth() && scene.camera.sample_direct(its.p, &imp, &px)) {
+                cnt.shadow_rays++;
+                if (scene.visible(its.p, cam)) {
+                    V3 d = normalize(cam - its.p);
+                    V3 wo_local = its.frame.to_local(d);
+                    V3 wi_global = its.frame.to_world(its.wi);
+                    Color bsdf_value = bsdf.eval(its.has_uv, its.uv, its.wi, wo_local, DomSolidAngle);   // Transport::Radiance: only glass reads it
+                    float correction = (its.wi.z * dot(d, its.n_g)) / (wo_local.z * dot(wi_global, its.n_g));   // no abs (light.rs:107-108)
+                    img.splat(flux * imp * bsdf_value * correction * transmittance(its.p, cam), px, lcnt);
+                }
+            }
+        } else if (vx.kind == Vertex::Light) {
+            if (vx.n_out == 0) return;                  // edge_out None: "sampling failed?" (light.rs:134-137), no splat and nothing further
+            const Edge& e = pt.path.edges[vx.edge_out[0]];
+            if (accumulate && prm.render_surface && e.pdf_direction.kind != PDF::Discrete && scene.camera.sample_direct(vx.pos, &imp, &px)) {
+                cnt.shadow_rays++;
+                if (scene.visible(vx.pos, cam)) {
+                    V3 d = normalize(cam - vx.pos);
+                    img.splat(transmittance(vx.pos, cam) * flux * imp * dot(d, vx.n) * FRAC_1_PI, px, lcnt);
+                }
+            }
+        }
+        // the next vertex (light.rs:175-209): one edge per vertex here (a single strategy)
+        const Vertex& v2 = pt.path.vertices[vid];
+        for (int k = 0; k < v2.n_out; k++) {
+            const Edge& e = pt.path.edges[v2.edge_out[k]];
+            if (e.v1 < 0) continue;
+            Color f = v2.kind == Vertex::Light ? e.weight * flux * e.rr_weight : flux * e.weight * e.rr_weight;
+            evaluate(depth + 1, e.v1, f, img);
+        }
+    }
+    // one light path: IntegratorLightTracing::compute's loop body (light.rs:268-274)
+    void trace(Sampler& sampler, LightImage& img) {
+        pt.path.clear();
+        cnt.samples++;
+        // Path::from_light -> EmitterSampler::random_sample_emitter_position (emitter.rs:1752-1762)
+        float v1 = sampler.next();
+        float v2 = sampler.next();
+        V2 uv = sampler.next2d();
+        size_t id = scene.emitters_cdf.sample_discrete(v1);
+        float pdf_sel = scene.emitters_cdf.pdf(id);
+        const EmitterRec& em = scene.emitters[id];
+        Vertex lv; lv.kind = Vertex::Light; lv.emitter = (int)id;
+        Color w;
+        if (em.kind == EM_MESH) {                       // Mesh::sample_position (emitter.rs:699-703)
+            const Mesh& m = scene.meshes[em.mesh];
+            Mesh::SampledPosition sp = m.sample(v2, uv);
+            lv.pos = sp.p; lv.n = sp.n; lv.its.has_uv = sp.has_uv; lv.its.uv = sp.uv;
+            w = m.emit(sp.has_uv, sp.uv) * PI_F / sp.pdf.value();
+        } else if (em.kind == EM_POINT) {               // PointEmitter::sample_position (emitter.rs:217-229)
+            lv.pos = em.v; lv.n = {0, 0, 0};
+            w = em.c * 4.0f * PI_F;
+        } else {                                        // DirectionalLight::sample_position (emitter.rs:135-162)
+            V2 p = concentric_sample_disk(uv);
+            float area = PI_F * powi(em.bsphere.radius, 2);
+            V3 poff = Frame::make(em.v).to_world(v3(p.x, p.y, 0.0f) * em.bsphere.radius);
+            lv.pos = (em.bsphere.center - em.v * em.bsphere.radius) + poff;
+            lv.n = em.v;
+            w = em.c * area;
+        }
+        Color flux = w / pdf_sel;
+        pt.path.vertices.push_back(lv);
+        generate(0, sampler);
+        evaluate(0, 0, flux, img);
+    }
+};
+
 }  // namespace orc
 
 // ==========================================================================================
@@ -2278,6 +2573,13 @@ void orc_camera_generate(const orc_scene* sc, float px, float py, float* o, floa
     Ray r = sc->s.camera.generate({px, py});
     o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; d[0] = r.d.x; d[1] = r.d.y; d[2] = r.d.z;
 }
+// Camera::sample_direct probe: 1 = Some, out = [importance (one channel), screen x, screen y]
+int orc_camera_sample_direct(const orc_scene* sc, const float* p, float* out) {
+    Color imp; V2 px;
+    if (!sc->s.camera.sample_direct({p[0], p[1], p[2]}, &imp, &px)) return 0;
+    out[0] = imp.r; out[1] = px.x; out[2] = px.y;
+    return 1;
+}
 void orc_scene_info(const orc_scene* sc, uint64_t* n_nodes, uint64_t* n_prims, uint64_t* n_emitters, float* bsphere) {
     *n_nodes = sc->s.nodes.size(); *n_prims = sc->s.primitives.size(); *n_emitters = sc->s.emitters.size();
     bsphere[0] = sc->s.bsphere.center.x; bsphere[1] = sc->s.bsphere.center.y; bsphere[2] = sc->s.bsphere.center.z; bsphere[3] = sc->s.bsphere.radius;
@@ -2401,14 +2703,20 @@ static int render_tiles(const Scene& scene, uint32_t spp, int stream_mode, int s
             uint32_t bw = std::min(16u, W - bx), bh = std::min(16u, H - by);
             Sampler block_sampler; block_sampler.rnd = Rng::seed_from_u64(block_seeds[b], seed_variant); block_sampler.variant = seed_variant;
             std::fill(block.begin(), block.end(), Color::zero());
+            const bool per_sample = stream_mode == RL_STREAM_PER_SAMPLE || stream_mode == RL_STREAM_STRATIFIED;
             for (uint32_t iy = 0; iy < bh; iy++)
                 for (uint32_t ix = 0; ix < bw; ix++) {
                     Sampler pixel_sampler;
-                    if (stream_mode == RL_STREAM_PER_SAMPLE) pixel_sampler = block_sampler.clone_box();
+                    uint64_t pixel_seed = 0;
+                    if (per_sample) {   // = block_sampler.clone_box(), keeping the seed (the stratified sampler's pixel key)
+                        pixel_seed = block_sampler.rnd.next_u64();
+                        pixel_sampler.rnd = Rng::seed_from_u64(pixel_seed, seed_variant); pixel_sampler.variant = seed_variant;
+                    }
                     for (uint32_t s = 0; s < spp; s++) {
                         Color c;
-                        if (stream_mode == RL_STREAM_PER_SAMPLE) {
+                        if (per_sample) {
                             Sampler sample_sampler = pixel_sampler.clone_box();
+                            if (stream_mode == RL_STREAM_STRATIFIED) strat_begin(sample_sampler, pixel_seed, s, spp);
                             c = wk.pixel(ix + bx, iy + by, sample_sampler);
                             wk.cnt.draws += sample_sampler.draws;
                         } else {
@@ -2477,3 +2785,86 @@ int orc_render_mc(const orc_scene* sc, int kind, const orc_mc_params* mp, const 
 }
 
 }  // extern "C"
+
+// IntegratorLightTracing::compute (light.rs:213-290) over the port's jobs: block b (the 16x16 blocks in creation order, block_seeds[b]) forks one
+// stream per pixel slot as render_tiles does in RL_STREAM_PER_SAMPLE, and slot p traces spp light paths, path s on the slot's s-th fork.  The image
+// is the fixed-point sum * (1 / spp): light.rs scales by 1 / (paths per job), 1 / jobs and W * H, i.e. by W * H / (spp * W * H).
+extern "C" int orc_render_light(const orc_scene* sc, const orc_path_params* pp, const uint64_t* block_seeds, size_t n_blocks,
+                                float* out_rgb, double* out_f64, uint32_t* out_count, int n_threads, orc_stats* stats, orc_light_stats* light_stats) {
+    const Scene& scene = sc->s;
+    if (!scene.bvh_built || !scene.emitters_built) return -4;
+    uint32_t W = scene.camera.w, H = scene.camera.h;
+    size_t nby = (H + 15) / 16, nbx = (W + 15) / 16;
+    if (n_blocks != nbx * nby || pp->spp == 0) return -1;
+    if (pp->stream_mode != RL_STREAM_PER_SAMPLE) return -2;
+    if (pp->strategy < RL_LIGHT_ALL || pp->strategy > RL_LIGHT_VOLUME) return -1;
+    if (scene.has_env) return -3;              // rl_render_light does not sample environment emitters
+    if (scene.emitters.empty()) return -8;
+    LightParams lp;
+    lp.path.has_min = pp->has_min_depth; lp.path.min_depth = pp->min_depth; lp.path.has_max = pp->has_max_depth; lp.path.max_depth = pp->max_depth;
+    lp.path.has_rr = pp->has_rr_depth; lp.path.rr_depth = pp->rr_depth;
+    lp.render_surface = pp->strategy != RL_LIGHT_VOLUME;
+    lp.render_volume = pp->strategy != RL_LIGHT_SURFACE;
+    if (n_threads <= 0) n_threads = (int)std::thread::hardware_concurrency();
+    if (n_threads <= 0) n_threads = 1;
+    LightImage img(W, H);
+    std::atomic<size_t> next_block{0};
+    std::vector<Counters> counters(n_threads);
+    std::vector<LightCounters> lcounters(n_threads);
+    auto worker = [&](int tid) {
+        LightTracer lt(scene, lp);
+        for (;;) {
+            size_t b = next_block.fetch_add(1);
+            if (b >= n_blocks) break;
+            uint32_t bx = (uint32_t)(b / nby) * 16, by = (uint32_t)(b % nby) * 16;
+            uint32_t bw = std::min(16u, W - bx), bh = std::min(16u, H - by);
+            Sampler block_sampler; block_sampler.rnd = Rng::seed_from_u64(block_seeds[b], pp->seed_variant); block_sampler.variant = pp->seed_variant;
+            for (uint32_t slot = 0; slot < bw * bh; slot++) {
+                Sampler slot_sampler = block_sampler.clone_box();
+                for (uint32_t s = 0; s < pp->spp; s++) {
+                    Sampler sample_sampler = slot_sampler.clone_box();
+                    lt.trace(sample_sampler, img);
+                    lt.cnt.draws += sample_sampler.draws;
+                }
+            }
+        }
+        counters[tid] = lt.cnt;
+        lcounters[tid] = lt.lcnt;
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < n_threads; t++) th.emplace_back(worker, t);
+    worker(0);
+    for (auto& t : th) t.join();
+    img.resolve(pp->spp, out_rgb, out_f64, out_count);
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        for (auto& c : counters) { stats->camera_samples += c.samples; stats->vertices += c.vertices; stats->extension_rays += c.extension_rays; stats->shadow_rays += c.shadow_rays; stats->rng_draws += c.draws; }
+        stats->threads = (uint32_t)n_threads;
+    }
+    if (light_stats) {
+        std::memset(light_stats, 0, sizeof(*light_stats));
+        for (auto& c : lcounters) { light_stats->splats += c.added; light_stats->splats_invalid += c.invalid; light_stats->splats_saturated += c.saturated; }
+    }
+    return 0;
+}
+
+// the stratified sampler's raw draws, as the renderers walk them: pixel p's sampler from pixel_seeds[p], one fork per sample, then the calls
+// of `pattern` (1 = next(), 2 = next2d()); out[(p * spp + s) * n_out + j] = the j-th value of sample s of pixel p, n_out = sum(pattern)
+extern "C" int orc_stratified_draws(size_t n_pixels, const uint64_t* pixel_seeds, uint32_t spp, int seed_variant, size_t n_calls, const int32_t* pattern, float* out) {
+    if (spp == 0) return -1;
+    size_t n_out = 0;
+    for (size_t c = 0; c < n_calls; c++) n_out += pattern[c] == 2 ? 2 : 1;
+    for (size_t p = 0; p < n_pixels; p++) {
+        Sampler pixel_sampler; pixel_sampler.rnd = Rng::seed_from_u64(pixel_seeds[p], seed_variant); pixel_sampler.variant = seed_variant;
+        for (uint32_t s = 0; s < spp; s++) {
+            Sampler sm = pixel_sampler.clone_box();
+            strat_begin(sm, pixel_seeds[p], s, spp);
+            float* o = out + ((size_t)p * spp + s) * n_out;
+            for (size_t c = 0; c < n_calls; c++) {
+                if (pattern[c] == 2) { V2 v = sm.next2d(); *o++ = v.x; *o++ = v.y; }
+                else *o++ = sm.next();
+            }
+        }
+    }
+    return 0;
+}

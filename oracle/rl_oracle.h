@@ -35,6 +35,10 @@ typedef struct orc_stats {
     uint64_t camera_samples, vertices, extension_rays, shadow_rays, rng_draws;
     uint32_t threads;
 } orc_stats;
+/* orc_render_light's splat counters, kept out of orc_stats so that its layout stays what existing callers allocate */
+typedef struct orc_light_stats {
+    uint64_t splats, splats_invalid, splats_saturated;   /* splats added / dropped as invalid / with a saturated (clamped or +inf) channel */
+} orc_light_stats;
 
 orc_scene* orc_scene_create(void);
 void orc_scene_destroy(orc_scene* s);
@@ -65,6 +69,7 @@ float orc_powf(float x, float y); float orc_acosf(float x); float orc_atan2f(flo
 void orc_math_batch(int fn, size_t n, const float* a, const float* b, float* out);
 
 void orc_camera_generate(const orc_scene* sc, float px, float py, float* o, float* d);
+int orc_camera_sample_direct(const orc_scene* sc, const float* p, float* out);   /* Camera::sample_direct: 1 = Some, out = [importance, x, y] */
 void orc_scene_info(const orc_scene* sc, uint64_t* n_nodes, uint64_t* n_prims, uint64_t* n_emitters, float* bsphere);
 void orc_bvh_dump(const orc_scene* sc, float* boxes, uint64_t* info, uint64_t* count, int32_t* prim_mesh, int32_t* prim_tri);
 int orc_trace_batch(const orc_scene* sc, size_t n, const float* o, const float* d, int brute,
@@ -79,6 +84,13 @@ int orc_render_mc(const orc_scene* sc, int kind, const orc_mc_params* mp, const 
                   float* out_rgb, int n_threads, orc_stats* stats);
 int orc_render_path(const orc_scene* sc, const orc_path_params* pp, const uint64_t* block_seeds, size_t n_blocks,
                     float* out_rgb, int n_threads, orc_stats* stats);
+/* IntegratorLightTracing with the port's jobs, streams and fixed-point splats (rl_render_light): pp->strategy is an rl_light_strategy, stream_mode
+ * must be RL_STREAM_PER_SAMPLE.  out_f64 (optional, W*H*3): every pixel's clamped splats summed in f64 without quantisation, times 1 / spp;
+ * out_count (optional, W*H): the splats each pixel took. */
+int orc_render_light(const orc_scene* sc, const orc_path_params* pp, const uint64_t* block_seeds, size_t n_blocks,
+                     float* out_rgb, double* out_f64, uint32_t* out_count, int n_threads, orc_stats* stats, orc_light_stats* light_stats);
+/* RL_STREAM_STRATIFIED's sampler, the contract of rl_debug_stratified_draws */
+int orc_stratified_draws(size_t n_pixels, const uint64_t* pixel_seeds, uint32_t spp, int seed_variant, size_t n_calls, const int32_t* pattern, float* out);
 #ifdef __cplusplus
 }
 #endif

@@ -17,8 +17,9 @@ struct LightConst {
     float to_local[16];
     float rect_min[2], rect_max[2];     // image_rect_min / image_rect_max
     int render_surface, render_volume;  // strategy all | surface | volume
-    long long* accum;                   // W*H*3 signed fixed-point sums (light.hip.h: kLightFixBits)
+    unsigned long long* accum;          // W*H*3 fixed-point sums, low 64 bits (light.hip.h: kLightFixBits)
     unsigned* inf_flags;                // W*H: bit c = channel c received a +inf splat
+    unsigned* carry;                    // W*H*3 high 32 bits of the sums: how often the low word wrapped
 };
 
 // mat: the scene's one BSDF type, or -1 = run-time switch per vertex.  area_only: every emitter is a mesh area light and there is no light

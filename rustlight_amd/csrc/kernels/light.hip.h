@@ -13,19 +13,22 @@
 // sample_direction next2d(); the edge's medium draw next() (with a medium); then per expanded vertex the bounce of `path` (next2d(), the
 // Russian-roulette next() when rr applies, the medium next()).
 //
-// Accumulation.  Every splat is added to a per-pixel signed 64-bit fixed-point sum, one global atomic add (x2) per non-zero channel.  Integer
-// adds commute, so the image does not depend on the order in which lanes arrive: same seeds, same bits, in every execution form.  A channel
-// value v becomes rint(v * 2^kLightFixBits); a splat channel at or above kLightSplatMax is clamped to it and counted as saturated; a +inf
-// channel sets the pixel's flag bit for that channel (the resolve writes +inf there, as the reference's accumulate would) and is counted as
-// saturated too.  A splat with a negative or NaN channel is dropped whole (Color::is_valid, structure.rs:156) and counted as invalid.
-// A pixel's sum is exact while the magnitudes of its splats add up to less than 2^(63 - kLightFixBits) = 2^39.
+// Accumulation.  Every splat is added to a per-pixel 96-bit unsigned fixed-point sum per channel: one global 64-bit atomic add per non-zero
+// channel into the low word, and when that add carries out of 64 bits (the returned old value plus the addend wraps) one 32-bit atomic add to
+// the channel's carry word.  Integer adds commute and every addend is non-negative, so the sum and its carry count do not depend on the order
+// in which lanes arrive: same seeds, same bits, in every execution form.  A channel value v becomes rint(v * 2^kLightFixBits); a splat channel
+// at or above kLightSplatMax is clamped to it and counted as saturated; a +inf channel sets the pixel's flag bit for that channel (the resolve
+// writes +inf there, as the reference's accumulate would) and is counted as saturated too.  A splat with a negative or NaN channel is dropped
+// whole (Color::is_valid, structure.rs:156) and counted as invalid.  A channel's sum is exact while it takes fewer than 2^41 clamped splats
+// (2^96 / 2^55); no finite splat can make a pixel negative or wrap it.  The resolve writes the f32 of
+// (carry * 2^64 + (double)low) * 2^-kLightFixBits / spp, every step in f64.
 #pragma once
 
 namespace rl {
 
 static constexpr int kLightFixBits = 24;                      // fraction bits of the splat accumulator: 2^-24 ~ 6e-8 resolution
 static constexpr float kLightFixScale = 16777216.0f;          // 2^kLightFixBits
-static constexpr float kLightSplatMax = 2147483648.0f;        // 2^31: largest splat channel (2^55 in fixed point; 256 of them still fit a pixel's sum)
+static constexpr float kLightSplatMax = 2147483648.0f;        // 2^31: largest splat channel (2^55 in fixed point)
 // statistics rows (pathstate.hip.h: STAT_COUNT = 8) — the light tracer's splat counters take the three free slots
 enum { STAT_SPLATS = 5, STAT_SPLATS_INVALID = 6, STAT_SPLATS_SATURATED = 7 };
 
@@ -74,8 +77,9 @@ RL_DEV void light_splat(const RenderConst& rc, const LightConst& lc, Col c, int 
         if (v == 0.0f) continue;
         if (v == f32_inf()) { atomicOr(&lc.inf_flags[pix], 1u << k); sat = true; continue; }
         if (v >= kLightSplatMax) { v = kLightSplatMax; sat = true; }
-        const long long q = (long long)rintf(v * kLightFixScale);
-        atomicAdd(reinterpret_cast<unsigned long long*>(lc.accum) + 3 * pix + k, (unsigned long long)q);
+        const unsigned long long q = (unsigned long long)rintf(v * kLightFixScale);
+        const unsigned long long old = atomicAdd(lc.accum + 3 * pix + k, q);
+        if (old + q < old) atomicAdd(lc.carry + 3 * pix + k, 1u);       // the low word wrapped: carry into the high word
     }
     if (sat) n_sat++;
 }

@@ -4,13 +4,15 @@
 
 namespace rl {
 
-// k_light_resolve — the fixed-point sums to the f32 image, times 1 / spp (light.rs:292-296: Σ splats · W·H / paths traced); a flagged channel is +inf
+// k_light_resolve — the 96-bit fixed-point sums to the f32 image, times 1 / spp (light.rs:292-296: Σ splats · W·H / paths traced); a flagged channel
+// is +inf.  carry * 2^64 is exact in f64, so the sum's only roundings are (double)low and the add.
 __global__ void __launch_bounds__(256) k_light_resolve(RenderConst rc, LightConst lc) {
     const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= (size_t)rc.W * rc.H) return;
     const unsigned flags = lc.inf_flags[pix];
     for (int k = 0; k < 3; k++) {
-        const double v = (double)lc.accum[3 * pix + k] * (1.0 / (double)(1ll << kLightFixBits)) / (double)rc.spp;
+        const double sum = (double)lc.carry[3 * pix + k] * 18446744073709551616.0 + (double)lc.accum[3 * pix + k];
+        const double v = sum * (1.0 / (double)(1ll << kLightFixBits)) / (double)rc.spp;
         rc.out[3 * pix + k] = (flags >> k) & 1u ? f32_inf() : (float)v;
     }
 }

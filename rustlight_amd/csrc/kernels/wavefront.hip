@@ -891,8 +891,9 @@ extern "C" int rl_render_light(rl_context* ctx, const rl_path_params* params, co
     if ((rcode = ensure(&ctx->d_block_seeds, &ctx->seeds_capacity, n_blocks)) != RL_OK) return rcode;
     if ((rcode = ensure(&ctx->d_item_seed, &ctx->item_capacity, n_items)) != RL_OK) return rcode;
     if ((rcode = ensure(&ctx->d_item_pixel, &ctx->item_pixel_capacity, n_items)) != RL_OK) return rcode;
-    // the splat image: [W*H*3] i64 sums, then [W*H] u32 inf flags — in the sample-state buffer of reference-order streams, which this call does not use
-    const size_t acc_words = (3 * n_pix + (n_pix + 1) / 2 + 3) / 4;     // in units of the buffer's 4 x u64 entries
+    // the splat image: [W*H*3] u64 low words of the sums, then [W*H] u32 inf flags, then [W*H*3] u32 carry words — in the sample-state buffer of
+    // reference-order streams, which this call does not use
+    const size_t acc_words = (3 * n_pix + (4 * n_pix + 1) / 2 + 3) / 4;     // in units of the buffer's 4 x u64 entries
     if ((rcode = ensure(&ctx->d_sample_states, &ctx->sample_states_capacity, acc_words * 4)) != RL_OK) return rcode;
     float* d_out = out_rgb;
     if (!out_is_device) {
@@ -911,8 +912,9 @@ extern "C" int rl_render_light(rl_context* ctx, const rl_path_params* params, co
     LightConst lc = ctx->light_cam;
     lc.render_surface = params->strategy != RL_LIGHT_VOLUME;
     lc.render_volume = params->strategy != RL_LIGHT_SURFACE;
-    lc.accum = reinterpret_cast<long long*>(ctx->d_sample_states);
+    lc.accum = reinterpret_cast<unsigned long long*>(ctx->d_sample_states);
     lc.inf_flags = reinterpret_cast<unsigned*>(lc.accum + 3 * n_pix);
+    lc.carry = lc.inf_flags + n_pix;
     HIP_OK(hipMemcpyAsync(ctx->d_owned, owned.data(), owned.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(ctx->d_item_base, item_base.data(), item_base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(ctx->d_block_seeds, block_seeds, n_blocks * sizeof(uint64_t), hipMemcpyHostToDevice, st));

@@ -1,6 +1,6 @@
 """Randomized differential test, HIP path vs CPU oracle (bit-exact image + counters), over random scene / light / material /
 integrator-option / pipeline combinations.  `run(seconds, seed)` is used by tests/test_gpu_parity.py (short) and can be run by hand
-for longer: python tests/parity_fuzz.py [seconds] [seed] [fast]   (round 1: ~75 000 cases over eight runs on 1 x MI355X, 0 failures; round 2: 26 k + 17 k + 17 k + 34 k + 69 k + 87 k cases, the last four with a third of the
+for longer: python tests/parity_fuzz.py [seconds] [seed] [fast | light | stratified]   (round 1: ~75 000 cases over eight runs on 1 x MI355X, 0 failures; round 2: 26 k + 17 k + 17 k + 34 k + 69 k + 87 k cases, the last four with a third of the
 cases forced through the kernels that stream the BVH, 0 mismatches).
 `fast`: eligible cases are also rendered with the opt-in tolerance build (`numerics = fast`) and held to a statistical bar (vertex
 count within 2 % of the exact build at the same seeds — the path census is what a systematic error moves —, image mean within a coarse bound)."""
@@ -12,7 +12,9 @@ from oracle import orc
 S = scenes
 
 
-def run(budget=20.0, seed=0, verbose=True, fast=False):
+def run(budget=20.0, seed=0, verbose=True, fast=False, arm="path"):
+    """arm: "path" (path / ao / direct in their random stream modes), "light" (the light tracer, rl_render_light, on the scenes without an
+    environment emitter) or "stratified" (path / ao / direct with RL_STREAM_STRATIFIED)."""
     rng = np.random.default_rng(seed)
     def rand_color(lo=0.05, hi=0.9):
         return tuple(float(x) for x in rng.uniform(lo, hi, 3))
@@ -88,6 +90,22 @@ def run(budget=20.0, seed=0, verbose=True, fast=False):
                 ctx, osc = api.Context(api.Scene(sd), 0), orc.Scene(sd)
             finally:
                 os.environ.pop("RL_FORCE_STREAMING", None)
+            if arm == "light":        # IntegratorLightTracing: every random scene but those with an environment emitter (rl_render_light refuses them)
+                if sd.environment is not None or getattr(sd, "environment_map", None) is not None or not (any(m.emission for m in sd.meshes) or sd.lights):
+                    continue
+                lk = dict(spp=kw["spp"], min_depth=kw["min_depth"], max_depth=kw["max_depth"], rr_depth=kw["rr_depth"], strategy=int(rng.integers(0, 3)),
+                          seed_variant=kw["seed_variant"])
+                seeds = api.IndependentSampler(seed, kw["seed_variant"]).block_seeds(sd.width, sd.height)
+                img, st = ctx.render_light(seeds, **lk); ref, ost = osc.render_light(seeds=seeds, **lk)
+                keys = ("camera_samples", "vertices", "extension_rays", "shadow_rays", "rng_draws", "splats", "splats_invalid", "splats_saturated")
+                n += 1
+                if not (np.array_equal(img, ref) and all(st[k] == ost[k] for k in keys)):
+                    bad += 1
+                    print("MISMATCH (light)", n, dict(size=(sd.width, sd.height), tris=sd.n_triangles, streaming=streaming, seed=seed, **lk),
+                          "max abs diff", float(np.nanmax(np.abs(img - ref))), {k: (st[k], ost[k]) for k in keys}, flush=True)
+                continue
+            if arm == "stratified":
+                kw["stream_mode"] = api.STREAM_STRATIFIED
             which = rng.random()
             if which < 0.25:          # the `ao` / `direct` integrators (no medium there: src/integrators/{ao,direct}.rs ignore it)
                 seeds = api.IndependentSampler(seed, kw["seed_variant"]).block_seeds(sd.width, sd.height)
@@ -158,5 +176,7 @@ def run(budget=20.0, seed=0, verbose=True, fast=False):
 
 
 if __name__ == "__main__":
-    n, bad = run(float(sys.argv[1]) if len(sys.argv) > 1 else 120.0, int(sys.argv[2]) if len(sys.argv) > 2 else 0, fast="fast" in sys.argv[3:])
+    arms = [a for a in ("light", "stratified") if a in sys.argv[3:]]
+    n, bad = run(float(sys.argv[1]) if len(sys.argv) > 1 else 120.0, int(sys.argv[2]) if len(sys.argv) > 2 else 0, fast="fast" in sys.argv[3:],
+                 arm=arms[0] if arms else "path")
     sys.exit(1 if bad else 0)

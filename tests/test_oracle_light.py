@@ -1,0 +1,168 @@
+"""The CPU oracle's light tracer (orc_render_light) and stratified sampler (orc_stratified_draws, stream_mode 2) on their own, against the reference's
+behaviour rather than against the kernels: the furnace's closed form, the oracle's own path tracer, the exact rules of light.rs, thread-count
+independence, Camera::sample_direct, and the stratification and unbiasedness of the sampler.  CPU only."""
+import numpy as np
+import pytest
+
+from oracle import orc
+from rustlight_amd import scenes
+
+R = 8           # independent seeds per estimate
+
+
+def _block_means(img, b):
+    h, w = img.shape[:2]
+    lum = img.astype(np.float64).mean(axis=2)
+    return lum[: h // b * b, : w // b * b].reshape(h // b, b, w // b, b).mean(axis=(1, 3))
+
+
+def _estimate(render, b):
+    m = np.stack([_block_means(render(k), b) for k in range(R)])
+    return m.mean(axis=0), m.std(axis=0, ddof=1) / np.sqrt(R)
+
+
+def test_furnace_closed_form():
+    """Albedo-0.5 furnace with unit emission: L = 1 / (1 - 0.5) = 2 everywhere."""
+    osc = orc.Scene(scenes.furnace(albedo=0.5))
+    means = np.array([osc.render_light(master_seed=k, spp=8)[0].astype(np.float64).mean() for k in range(R)])
+    se = means.std(ddof=1) / np.sqrt(R)
+    assert 0 < se < 0.02
+    assert abs(means.mean() - 2.0) < 5.0 * se, (means.mean(), se)
+
+
+def _with_back_triangle(sd):
+    back = scenes.MeshData("Back", np.asarray([[0.0, 1.0, 8.0], [0.01, 1.0, 8.0], [0.0, 1.01, 8.0]], dtype=np.float32), np.asarray([[0, 1, 2]], dtype=np.uint32),
+                           None, None, scenes.matte((0.5, 0.5, 0.5)))
+    sd.meshes.insert(0, back)
+    return sd
+
+
+@pytest.mark.parametrize("which", ["cbox", "medium_hg"])
+def test_light_agrees_with_path(which):
+    """light(max) against path(max + 1), as tests/test_gpu_light_tracing.py::_compare_with_path maps the depths.  8 x 8-pixel block means of R
+    independent renders each; |z| < 6 per block.  Margin: with 16 blocks an unbiased pair exceeds |z| = 6 with probability ~1e-8 even allowing for
+    the t-distribution of an 8-seed standard error (|t_7| > 6 has p ~ 5e-4 per block, so the bound stays loose only against noise, not bias: a 3 %
+    bias in a block with 0.5 % standard error is |z| ~ 6)."""
+    sd = scenes.cbox(32, 32) if which == "cbox" else _with_back_triangle(scenes.cbox_medium(32, 32, 0.5, g=0.6))
+    max_depth = None if which == "cbox" else 5
+    osc = orc.Scene(sd)
+    ml, sl = _estimate(lambda k: osc.render_light(master_seed=100 + k, spp=32, max_depth=max_depth)[0], 8)
+    mp, sp = _estimate(lambda k: osc.render(master_seed=200 + k, spp=32, stream_mode=1, eval_order=1,
+                                            max_depth=None if max_depth is None else max_depth + 1)[0], 8)
+    se = np.sqrt(sl ** 2 + sp ** 2)
+    lit = mp > 1e-3
+    assert lit.mean() > 0.5
+    z = (ml - mp) / np.where(se > 0, se, 1.0)
+    assert np.all(np.abs(z[lit]) < 6.0), (np.abs(z).max(), ml, mp)
+    assert abs(ml.mean() / mp.mean() - 1.0) < 0.03
+
+
+def test_max_depth_one_is_black():
+    sd = scenes.cbox(16, 16)
+    img, st = orc.Scene(sd).render_light(master_seed=1, spp=4, max_depth=1)
+    assert not img.any()
+    assert st["camera_samples"] == 4 * 16 * 16 and st["splats"] == 0 and st["shadow_rays"] == 0 and st["vertices"] == 0
+    assert st["rng_draws"] == 4 * 4 * 16 * 16 and st["extension_rays"] == 0
+
+
+def test_surface_plus_volume_is_all():
+    sd = scenes.cbox_medium(24, 24, 0.5, g=-0.3)
+    osc = orc.Scene(sd)
+    a, sa = osc.render_light(master_seed=3, spp=4, strategy=0)
+    su, ss = osc.render_light(master_seed=3, spp=4, strategy=1)
+    vo, sv = osc.render_light(master_seed=3, spp=4, strategy=2)
+    assert su.any() and vo.any()
+    assert sa["rng_draws"] == ss["rng_draws"] == sv["rng_draws"] and sa["extension_rays"] == ss["extension_rays"] == sv["extension_rays"]
+    assert sa["splats"] == ss["splats"] + sv["splats"]
+    np.testing.assert_allclose(a, su.astype(np.float64) + vo, rtol=1e-6, atol=0)
+
+
+def test_thread_count_independence():
+    """Integer splat sums commute: the image and the counters do not depend on how many threads render, or in which order."""
+    sd = scenes.living_room(40, 24, n_spheres=8, tess=6)
+    osc = orc.Scene(sd)
+    ref, rst = osc.render_light(master_seed=5, spp=3, threads=1)
+    assert ref.any()
+    for t in (2, 7, 16):
+        img, st = osc.render_light(master_seed=5, spp=3, threads=t)
+        np.testing.assert_array_equal(img, ref)
+        assert all(st[k] == rst[k] for k in rst if k != "threads")
+
+
+def test_splat_rules():
+    """Counters and the f64 side accumulator: saturation with huge emission, the fixed-point image within quantisation of the f64 sums."""
+    sd = scenes.cbox(8, 8)
+    sd.meshes[-1].emission = tuple(c * 1e13 for c in sd.meshes[-1].emission)
+    spp = 32
+    img, st, f64, counts = orc.Scene(sd).render_light(master_seed=6, spp=spp, want_f64=True)
+    assert st["splats_saturated"] > 0 and counts.sum() == st["splats"]
+    assert (f64 * spp).max() > 2.0 ** 39                     # past what a signed 64-bit sum with 24 fraction bits holds
+    assert np.isfinite(img).all() and (img >= 0).all()
+    bound = counts[..., None] * 2.0 ** -25 / spp + np.abs(f64) * 2.0 ** -24
+    assert (np.abs(img - f64) <= bound).all()
+
+
+def test_camera_importance_lands_in_its_pixel():
+    """Camera::sample_direct of points along a pixel centre's own camera ray lands in that pixel, with importance > 0 (camera.rs:94-138)."""
+    sd = scenes.cbox(12, 9)
+    osc = orc.Scene(sd)
+    hits = 0
+    for y in range(sd.height):
+        for x in range(sd.width):
+            o, d = osc.camera_generate(x + 0.5, y + 0.5)
+            for t in (0.5, 2.0, 5.0):
+                r = osc.sample_direct(o + t * d)
+                if r is None:
+                    continue
+                imp, px = r
+                assert imp > 0
+                assert (int(px[0]), int(px[1])) == (x, y), (x, y, px)
+                hits += 1
+    # the last bound of Camera::importance is `p.x > image_rect_max.y` (sic): rows of a wide frame outside |p.x| <= rect_max.y are refused
+    assert hits > 0.5 * 3 * sd.width * sd.height
+
+
+# ---- the stratified sampler
+PATTERN = [1, 1, 2, 1, 1, 2, 2, 1, 2, 1, 2]
+
+
+@pytest.mark.parametrize("spp", [1, 3, 4, 16, 17, 64])
+def test_stratified_draws_are_exactly_stratified(spp):
+    rng = np.random.default_rng(99 + spp)
+    seeds = rng.integers(0, 2 ** 63, size=300, dtype=np.uint64)
+    one_minus_eps = np.float32(1.0) - np.float32(2.0 ** -23)
+    for variant in (0, 1):
+        v = orc.stratified_draws(seeds, spp, PATTERN, seed_variant=variant)
+        assert v.shape == (300, spp, sum(PATTERN))
+        assert np.all(v >= 0.0) and np.all(v <= one_minus_eps)
+        n = 1
+        while n < spp: n *= 4
+        sq = int(round(np.sqrt(n)))
+        c = np.cumsum([0] + PATTERN)[:-1]
+        d1 = [int(c[i]) for i in range(len(PATTERN)) if PATTERN[i] == 1]
+        d2 = [int(c[i]) for i in range(len(PATTERN)) if PATTERN[i] == 2]
+        for k in range(4):
+            s = np.sort(np.floor(v[:, :, d1[k]].astype(np.float64) * n).astype(np.int64), axis=1)
+            assert np.all(np.diff(s, axis=1) > 0), f"1D dimension {k}: a stratum taken twice"
+            if spp == n: assert np.all(s == np.arange(n)[None, :])
+        for k in range(4):
+            x, y = v[:, :, d2[k]].astype(np.float64), v[:, :, d2[k] + 1].astype(np.float64)
+            cell = np.sort(np.floor(x * sq).astype(np.int64) * sq + np.floor(y * sq).astype(np.int64), axis=1)
+            assert np.all(np.diff(cell, axis=1) > 0), f"2D dimension {k}: a cell taken twice"
+            if spp == n: assert np.all(cell == np.arange(n)[None, :])
+        if spp >= 16:       # past the fourth 1D dimension the plain Rng draws: collisions in nearly every pixel
+            s = np.sort(np.floor(v[:, :, d1[4]].astype(np.float64) * n).astype(np.int64), axis=1)
+            assert np.mean(np.all(np.diff(s, axis=1) > 0, axis=1)) < 0.5
+
+
+def test_stratified_ao_is_unbiased():
+    """ao with the stratified sampler against the independent sampler: per 4 x 4 block means over R seeds, |z| < 6; the stratified estimate's
+    seed-to-seed spread is not larger."""
+    sd = scenes.cbox(24, 24)
+    osc = orc.Scene(sd)
+    ms, ss = _estimate(lambda k: osc.render_ao(master_seed=300 + k, spp=16, stream_mode=2)[0], 4)
+    mi, si = _estimate(lambda k: osc.render_ao(master_seed=400 + k, spp=16, stream_mode=1)[0], 4)
+    se = np.sqrt(ss ** 2 + si ** 2)
+    z = (ms - mi) / np.where(se > 0, se, 1.0)
+    assert np.all(np.abs(z[se > 0]) < 6.0), np.abs(z).max()
+    assert ss.mean() <= si.mean() * 1.05
