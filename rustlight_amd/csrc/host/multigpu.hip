@@ -22,8 +22,7 @@
 #include <vector>
 
 #include "../../../include/rustlight_amd.h"
-
-void rl_set_error(const std::string& s);
+#include "hip_buffer.h"
 
 namespace {
 
@@ -60,11 +59,6 @@ struct rl_multi {
     int rccl_version = 0;
 };
 
-#define MG_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) { rl_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); (void)hipGetLastError(); return RL_ERR_HIP; } \
-    } while (0)
 #define MG_NCCL(expr)                                                                                  \
     do {                                                                                               \
         ncclResult_t r_ = (expr);                                                                      \
@@ -217,9 +211,9 @@ extern "C" int rl_multi_render_path(rl_multi* m, const rl_path_params* params, c
         const int r = (int)(std::find(m->comm_devices.begin(), m->comm_devices.end(), m->device_of[g]) - m->comm_devices.begin());
         const int lead = m->leader[r];
         if (lead == g) continue;
-        MG_HIP(hipSetDevice(m->device_of[g]));
+        HIP_OK(hipSetDevice(m->device_of[g]));
         hipLaunchKernelGGL(k_add_framebuffer, dim3((unsigned)((n_floats + 255) / 256)), dim3(256), 0, m->stream[lead], m->fb[lead], m->fb[g], n_floats);
-        MG_HIP(hipGetLastError());
+        HIP_OK(hipGetLastError());
     }
     m->last_stats = st;
     const int root = m->leader[0];
@@ -230,9 +224,9 @@ extern "C" int rl_multi_render_path(rl_multi* m, const rl_path_params* params, c
         m->host_tmp.resize(n_floats);
         for (size_t r = 0; r < m->comm_devices.size(); r++) {
             const int lead = m->leader[r];
-            MG_HIP(hipSetDevice(m->device_of[lead]));
-            MG_HIP(hipMemcpyAsync(m->host_tmp.data(), m->fb[lead], n_floats * sizeof(float), hipMemcpyDeviceToHost, m->stream[lead]));
-            MG_HIP(hipStreamSynchronize(m->stream[lead]));
+            HIP_OK(hipSetDevice(m->device_of[lead]));
+            HIP_OK(hipMemcpyAsync(m->host_tmp.data(), m->fb[lead], n_floats * sizeof(float), hipMemcpyDeviceToHost, m->stream[lead]));
+            HIP_OK(hipStreamSynchronize(m->stream[lead]));
             for (size_t i = 0; i < n_floats; i++) out_rgb[i] = out_rgb[i] + m->host_tmp[i];
         }
         return RL_OK;
@@ -269,9 +263,9 @@ extern "C" int rl_multi_render_path(rl_multi* m, const rl_path_params* params, c
             }
         }
         if (nccl_err.empty()) {
-            MG_HIP(hipSetDevice(m->device_of[root]));
-            MG_HIP(hipMemcpyAsync(out_rgb, m->fb_sum, n_floats * sizeof(float), hipMemcpyDeviceToHost, m->stream[root]));
-            MG_HIP(hipStreamSynchronize(m->stream[root]));
+            HIP_OK(hipSetDevice(m->device_of[root]));
+            HIP_OK(hipMemcpyAsync(out_rgb, m->fb_sum, n_floats * sizeof(float), hipMemcpyDeviceToHost, m->stream[root]));
+            HIP_OK(hipStreamSynchronize(m->stream[root]));
             merged = true;
         } else {
             if (getenv("RL_MULTI_NO_FALLBACK")) { rl_set_error(nccl_err); return RL_ERR_HIP; }

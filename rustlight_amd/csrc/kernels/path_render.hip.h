@@ -1,16 +1,16 @@
 // path_render.hip.h — the host driver behind rl_render_path: one PathRender object per call (included by wavefront.hip after rl_context and the
 // launch helpers; host code only).  Integrator::compute for IntegratorPathTracing (src/integrators/mod.rs:219-233 -> compute_mc, 403-450).
 //
-// The call in steps — each a method, none of them reads the environment (the context's options were copied when the object was built: knobs.h):
-//   decompose()        this shard's blocks in creation order (mod.rs:351-374: `b % shard_count`)
+// The call in steps — each a method, none of them reads the environment (the context's options were copied when the object was built: knobs.h); the
+// steps every render kind shares (this shard's blocks, the tables, the image, the statistics rows, the finish) are RenderFrame's (wavefront.hip):
 //   choose_form()      wavefront stage kernels | persistent kernel; reference-order streams in two passes (chain.hip.h) or one
 //   plan_chunks()      two passes: block cursors per chunk so that the recorded sampler states fit their buffer
 //   plan_lanes()       how pixel items / block chains are laid over the lanes (lanes per pixel, pool slots, item spread), buffers
-//   upload()           the shard's tables, the zeroed framebuffer, RenderConst
+//   upload()           the shard's tables, the zeroed framebuffer, the counters, RenderConst
 //   run_two_pass()     per chunk: plan_chain_pass() -> chain pass (k_stream_spec | k_stream_chain) with the evaluation pass beside it
 //                      (overlap_loop(): host-driven launches over lists of complete blocks) or after it, then the fold of parked samples
 //   run_fused() / run_wavefront()
-//   finish()           framebuffer download, statistics rows, rl_render_stats
+//   finish()           the fold of parked samples, RenderFrame::download, rl_render_stats
 #pragma once
 
 namespace {
@@ -20,15 +20,12 @@ using namespace rl;
 struct Plan { unsigned split, n_items, P, item_shift; };
 struct Chunk { unsigned c0, c1, n_pix; std::vector<unsigned> base; };
 
-class PathRender {
+class PathRender : RenderFrame {
 public:
-    PathRender(rl_context* c, const rl_path_params* p, const uint64_t* seeds, size_t nb, float* out, int out_dev, hipStream_t stream, rl_render_stats* s)
-        : ctx(c), params(p), block_seeds(seeds), n_blocks(nb), out_rgb(out), out_is_device(out_dev), st(stream), stats(s), knobs(c->knobs),
-          W(c->width), H(c->height), nby((c->height + 15) / 16), shard_count(p->shard_count ? p->shard_count : 1) {}
+    PathRender(rl_context* c, const rl_path_params* p, const uint64_t* seeds, size_t nb, float* out, int out_dev, void* stream_arg, rl_render_stats* s)
+        : RenderFrame(c, seeds, nb, out, out_dev, stream_arg, s, p->shard_index, p->shard_count), params(p) {}
 
     int run() {
-        t_start = std::chrono::steady_clock::now();
-        decompose();
         int r;
         if ((r = choose_form()) != RL_OK) return r;
         plan_chunks();
@@ -43,40 +40,22 @@ public:
 
 private:
     // ---- the call
-    rl_context* const ctx;
     const rl_path_params* const params;
-    const uint64_t* const block_seeds;
-    const size_t n_blocks;
-    float* const out_rgb;
-    const int out_is_device;
-    const hipStream_t st;
-    rl_render_stats* const stats;
-    const Knobs knobs;                 // the context's options as they stood when the render started
-    const uint32_t W, H;
-    const size_t nby;
-    const uint32_t shard_count;
-    std::chrono::steady_clock::time_point t_start;
-    // ---- work decomposition and form
-    std::vector<unsigned> owned, item_base;
-    unsigned n_pixels = 0;
+    // ---- form
     bool per_sample = false, fused = false, fast_math = false, two_pass = false, medium = false;
     bool strat = false;                // RL_STREAM_STRATIFIED: per-pixel items, the *_strat kernels (sampler.hip.h)
     bool overlap_wanted = false;       // two passes: the evaluation pass runs beside the chain pass (every chunk)
     bool one_lane_per_pixel = false;   // the per-sample parking buffer could not be allocated: one lane per pixel, no overlap
     bool overlapped = false;           // ... and did
-    int cus = 256;
-    size_t state_budget = (size_t)24 << 30;
+    size_t state_budget = 0;
     std::vector<Chunk> chunks;
     unsigned max_chunk_pix = 0;
     Plan plan{1u, 0u, 0u, 0u}, plan_chain{1u, 0u, 0u, 0u};
     unsigned split = 1, n_items = 0, item_shift = 0, P = 0, n_item_pixels = 0;
     Pool pool{};
-    float* d_out = nullptr;
-    size_t n_partial_rows = 0;
     RenderConst rc{};
     StackConf stc{};
     size_t lds_trav = 0, lds_fused = 0;
-    bool timing = false;
     // ---- results
     double ms[4] = {0, 0, 0, 0}, ms_fused = 0.0, ms_chain = 0.0, ms_eval_span = 0.0;
     uint64_t iterations = 0, launches = 2, n_extend = 0;
@@ -92,18 +71,6 @@ private:
 
     static constexpr unsigned kMaxEvalLaunches = 256u;
     static constexpr size_t kEventsPerIter = 8;
-
-    // this shard's blocks, in creation order
-    void decompose() {
-        for (size_t b = 0; b < n_blocks; b++) {
-            if (b % shard_count != params->shard_index) continue;
-            const unsigned bx = (unsigned)(b / nby) * 16u, by = (unsigned)(b % nby) * 16u;
-            const unsigned bw = std::min(16u, W - bx), bh = std::min(16u, H - by);
-            owned.push_back((unsigned)b);
-            item_base.push_back(n_pixels);
-            n_pixels += bw * bh;
-        }
-    }
 
     int choose_form() {
         strat = params->stream_mode == RL_STREAM_STRATIFIED;
@@ -124,9 +91,8 @@ private:
         // (option ref_single_pass keeps that form: a test / measurement knob).
         two_pass = !per_sample && fused && !owned.empty() && !knobs.has(K_REF_SINGLE_PASS);
         // the recorded states of ONE cursor position of every owned block must fit the budget (spp beyond ~90 000 at 1080p do not): else the single-pass walk
-        if (knobs.has(K_STATE_BUDGET_MB)) state_budget = std::max<size_t>(1, (size_t)knobs.i(K_STATE_BUDGET_MB, 0)) << 20;   // test knob: forces several chunks
+        state_budget = max_state_bytes();
         if (two_pass && (size_t)owned.size() * params->spp * 32 > state_budget) two_pass = false;
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
         return RL_OK;
     }
 
@@ -192,7 +158,7 @@ private:
     void plan_chunks() {
         if (two_pass && !knobs.has(K_STATE_BUDGET_MB)) {
             size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) state_budget = std::min(state_budget, ctx->sample_states_capacity * sizeof(unsigned long long) + free_b / 10 * 6);
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) state_budget = std::min(state_budget, ctx->d_sample_states.capacity() * sizeof(unsigned long long) + free_b / 10 * 6);
             else (void)hipGetLastError();
         }
         for (bool planned_states = false; two_pass && !planned_states;) {
@@ -204,8 +170,8 @@ private:
             for (unsigned c0 = 0; c0 < 256u; c0 += cursors_per_chunk) {
                 Chunk ch; ch.c0 = c0; ch.c1 = std::min(256u, c0 + cursors_per_chunk); ch.n_pix = 0;
                 for (size_t j = 0; j < owned.size(); j++) {
-                    const unsigned bidx = owned[j], bx = (unsigned)(bidx / nby) * 16u, by = (unsigned)(bidx % nby) * 16u;
-                    const unsigned npx = std::min(16u, W - bx) * std::min(16u, H - by);
+                    const BlockRect r = block_rect(owned[j], nby, W, H);
+                    const unsigned npx = r.w * r.h;
                     ch.base.push_back(ch.n_pix);
                     ch.n_pix += std::min(ch.c1, npx) - std::min(ch.c0, npx);
                 }
@@ -213,12 +179,8 @@ private:
             }
             size_t need = 0;
             for (const Chunk& ch : chunks) need = std::max(need, (size_t)ch.n_pix * params->spp * 4);
-            if (ctx->sample_states_capacity >= need && ctx->d_sample_states) planned_states = true;
-            else {
-                if (ctx->d_sample_states) { hipFree(ctx->d_sample_states); ctx->d_sample_states = nullptr; ctx->sample_states_capacity = 0; }
-                if (hipMalloc((void**)&ctx->d_sample_states, std::max<size_t>(need, 1) * sizeof(unsigned long long)) == hipSuccess) { ctx->sample_states_capacity = need; planned_states = true; }
-                else { (void)hipGetLastError(); ctx->d_sample_states = nullptr; state_budget /= 2; }      // fewer cursors per chunk
-            }
+            if (ctx->d_sample_states.ensure(need) == RL_OK) planned_states = true;
+            else state_budget /= 2;      // fewer cursors per chunk
         }
         max_chunk_pix = 0;
         for (const Chunk& ch : chunks) max_chunk_pix = std::max(max_chunk_pix, ch.n_pix);
@@ -243,84 +205,53 @@ private:
             if (split <= 1) break;
             // several lanes per pixel park their samples in HBM ([spp][pixel][3] floats: 3.2 GB at 1080p x 128 spp).  Where that buffer cannot be had (a full device, several
             // contexts in flight) the frame still renders: one lane per pixel, the evaluation pass after the chain pass — unless the caller asked for the lanes himself
-            if (ensure(&ctx->d_sample_buf, &ctx->sample_buf_capacity, (size_t)n_item_pixels * params->spp * 3) == RL_OK) break;
+            if (ctx->d_sample_buf.ensure((size_t)n_item_pixels * params->spp * 3) == RL_OK) break;
             if (params->sample_split || attempt == 1) return RL_ERR_HIP;
             one_lane_per_pixel = true; overlap_wanted = false;
         }
-        if ((rcode = ensure(&ctx->d_owned, &ctx->owned_capacity, owned.size())) != RL_OK) return rcode;
-        if ((rcode = ensure(&ctx->d_item_base, &ctx->item_base_capacity, owned.size())) != RL_OK) return rcode;
-        if ((rcode = ensure(&ctx->d_block_seeds, &ctx->seeds_capacity, n_blocks)) != RL_OK) return rcode;
+        if ((rcode = alloc_tables()) != RL_OK) return rcode;
         if (per_sample || two_pass) {
-            if (per_sample && (rcode = ensure(&ctx->d_item_seed, &ctx->item_capacity, n_item_pixels)) != RL_OK) return rcode;
-            if ((rcode = ensure(&ctx->d_item_pixel, &ctx->item_pixel_capacity, n_item_pixels)) != RL_OK) return rcode;
+            if (per_sample && (rcode = ctx->d_item_seed.ensure(n_item_pixels)) != RL_OK) return rcode;
+            if ((rcode = ctx->d_item_pixel.ensure(n_item_pixels)) != RL_OK) return rcode;
         }
         if (two_pass) {
-            if ((rcode = ensure(&ctx->d_sample_states, &ctx->sample_states_capacity, (size_t)max_chunk_pix * params->spp * 4)) != RL_OK) return rcode;
-            if ((rcode = ensure(&ctx->d_chain_states, &ctx->chain_states_capacity, owned.size() * 4)) != RL_OK) return rcode;
+            if ((rcode = ctx->d_sample_states.ensure((size_t)max_chunk_pix * params->spp * 4)) != RL_OK) return rcode;
+            if ((rcode = ctx->d_chain_states.ensure(owned.size() * 4)) != RL_OK) return rcode;
         }
-        if (!fused && ctx->pool_capacity < P) {
-            if (ctx->pool.f) hipFree(ctx->pool.f);
-            if (ctx->pool.u) hipFree(ctx->pool.u);
-            if (ctx->pool.q) hipFree(ctx->pool.q);
-            ctx->pool = Pool{};
-            ctx->pool_capacity = 0;          // until all three planes exist: a failed allocation must not leave a half-built pool behind
-            if (hipMalloc((void**)&ctx->pool.f, (size_t)F_COUNT * P * sizeof(float)) != hipSuccess ||
-                hipMalloc((void**)&ctx->pool.u, (size_t)U_COUNT * P * sizeof(unsigned)) != hipSuccess ||
-                hipMalloc((void**)&ctx->pool.q, (size_t)Q_COUNT * P * sizeof(unsigned long long)) != hipSuccess) {
-                (void)hipGetLastError();
-                if (ctx->pool.f) hipFree(ctx->pool.f);
-                if (ctx->pool.u) hipFree(ctx->pool.u);
-                if (ctx->pool.q) hipFree(ctx->pool.q);
-                ctx->pool = Pool{};
+        // the wavefront pipeline's pool: all three planes or none (its slots are read off the plane allocated last), so a failed allocation leaves no half-built pool
+        if (!fused && ctx->pool_q.capacity() / Q_COUNT < P) {
+            ctx->pool_f.reset(); ctx->pool_u.reset(); ctx->pool_q.reset();
+            if (ctx->pool_f.ensure((size_t)F_COUNT * P) != RL_OK || ctx->pool_u.ensure((size_t)U_COUNT * P) != RL_OK || ctx->pool_q.ensure((size_t)Q_COUNT * P) != RL_OK) {
+                ctx->pool_f.reset(); ctx->pool_u.reset(); ctx->pool_q.reset();
                 rl_set_error("out of device memory for a path-state pool of " + std::to_string(P) + " slots");
                 return RL_ERR_HIP;
             }
-            ctx->pool_capacity = P;
         }
-        pool = ctx->pool;
-        pool.P = P;
-        d_out = out_rgb;
-        if (!out_is_device) {
-            if ((rcode = ensure(&ctx->d_out, &ctx->out_capacity, (size_t)3 * W * H)) != RL_OK) return rcode;
-            d_out = ctx->d_out;
-        }
-        n_partial_rows = std::max<size_t>((P + 255) / 256, (size_t)cus * 8u * rl_context::kEvalStreams);      // (the queue-fed evaluation launches use a grid of the resident workgroups)
-        if ((rcode = ensure(&ctx->d_partials, &ctx->partials_capacity, n_partial_rows * STAT_COUNT)) != RL_OK) return rcode;
-        return RL_OK;
+        pool = Pool{ctx->pool_f.get(), ctx->pool_u.get(), ctx->pool_q.get(), P};
+        // (the queue-fed evaluation launches use a grid of the resident workgroups)
+        return alloc_output(std::max<size_t>((P + 255) / 256, (size_t)cus * 8u * rl_context::kEvalStreams));
     }
 
     int upload() {
-        HIP_OK(hipMemcpyAsync(ctx->d_owned, owned.data(), owned.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-        if (!two_pass) HIP_OK(hipMemcpyAsync(ctx->d_item_base, item_base.data(), item_base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(ctx->d_block_seeds, block_seeds, n_blocks * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(d_out, 0, (size_t)3 * W * H * sizeof(float), st));
+        int rcode;
+        if ((rcode = RenderFrame::upload(!two_pass, true)) != RL_OK) return rcode;
         Counters init{};
         init.active = std::min(plan.P, n_items);
         init.next_item = item_shift ? n_items : plan.P;
-        if (!two_pass) HIP_OK(hipMemcpyAsync(ctx->d_counters, &init, sizeof(init), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(ctx->d_partials, 0, n_partial_rows * STAT_COUNT * sizeof(unsigned long long), st));
+        if (!two_pass) HIP_OK(hipMemcpyAsync(ctx->d_counters.get(), &init, sizeof(init), hipMemcpyHostToDevice, st));
+        if ((rcode = zero_rows()) != RL_OK) return rcode;
 
-        rc.spp = params->spp;
+        rc = render_const(params->spp, params->stream_mode, params->seed_variant);
         rc.has_min = params->has_min_depth; rc.min_depth = params->min_depth;
         rc.has_max = params->has_max_depth; rc.max_depth = params->max_depth;
         rc.has_rr = params->has_rr_depth; rc.rr_depth = params->rr_depth;
         rc.strategy = params->strategy; rc.single_scattering = params->single_scattering;
-        rc.stream_mode = params->stream_mode; rc.seed_variant = params->seed_variant;
-        rc.inv_spp = 1.0f / (float)params->spp;
-        rc.W = W; rc.H = H; rc.nby = (unsigned)nby;
         rc.n_items = n_items;
         rc.item_shift = item_shift;
-        rc.split = split; rc.sample_buf = ctx->d_sample_buf;
-        rc.owned_blocks = ctx->d_owned; rc.block_item_base = ctx->d_item_base; rc.n_owned = (unsigned)owned.size();
-        rc.block_seeds = ctx->d_block_seeds;
-        rc.item_seed = ctx->d_item_seed; rc.item_pixel = ctx->d_item_pixel;
-        rc.out = d_out;
-        rc.counters = ctx->d_counters;
-        rc.partials = ctx->d_partials;
-        rc.sample_states = ctx->d_sample_states; rc.chain_states = ctx->d_chain_states;
+        rc.split = split; rc.sample_buf = ctx->d_sample_buf.get();
+        rc.sample_states = ctx->d_sample_states.get(); rc.chain_states = ctx->d_chain_states.get();
 
         lds_trav = traversal_lds_bytes(ctx, ctx->lds_scene, 256, true);
-        int rcode;
         if ((rcode = stack_conf(ctx, (size_t)((P + 255) / 256) * 256, &stc)) != RL_OK) return rcode;
         lds_fused = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false) + kFusedColdBytes;
 
@@ -329,10 +260,7 @@ private:
         if (!fused) hipLaunchKernelGGL(k_init, dim3((plan.P + 255) / 256), block, 0, st, rc, pool);
 
         // events: 4 timed kernel classes per iteration of the wavefront pipeline, 4 per chunk of the two-pass form
-        timing = stats != nullptr && !knobs.has(K_NO_EVENTS);
-        const unsigned poll_every = per_sample ? 8u : 32u;
-        if (timing) while (ctx->events.size() < kEventsPerIter * poll_every) { hipEvent_t ev; HIP_OK(hipEventCreate(&ev)); ctx->events.push_back(ev); }
-        return RL_OK;
+        return grow_events(kEventsPerIter * (per_sample ? 8u : 32u));
     }
 
     void launch_fused(const RenderConst& rcl, dim3 grid, hipStream_t on, const StackConf* stcl = nullptr) const {
@@ -434,11 +362,10 @@ private:
             // the tracks: 36 B per entry; when they do not fit what the device has free the serial walk runs instead
             const size_t need = (size_t)spec_threads * spc.cap * 36u;
             size_t free_b = 0, total_b = 0;
-            const size_t have = ctx->trk_off_capacity * 4u + ctx->trk_st_capacity * 16u;
+            const size_t have = ctx->d_trk_off.capacity() * 4u + ctx->d_trk_st.capacity() * 16u;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
             if (need > have && need - have > free_b / 2u) spec = false;
-            if (spec && (ensure(&ctx->d_trk_off, &ctx->trk_off_capacity, (size_t)spec_threads * spc.cap) != RL_OK ||
-                         ensure(&ctx->d_trk_st, &ctx->trk_st_capacity, (size_t)spec_threads * spc.cap * 2u) != RL_OK)) { (void)hipGetLastError(); spec = false; }
+            if (spec && (ctx->d_trk_off.ensure((size_t)spec_threads * spc.cap) != RL_OK || ctx->d_trk_st.ensure((size_t)spec_threads * spc.cap * 2u) != RL_OK)) spec = false;
         }
         int rcode;
         if (spec) {
@@ -446,18 +373,18 @@ private:
             const bool expand = !params->has_max_depth || 1u < params->max_depth;
             const bool no_trivial = knobs.has(K_SPEC_NO_TRIVIAL);
             const uint64_t key = ((uint64_t)params->shard_index << 33) | ((uint64_t)shard_count << 1) | (expand ? 1u : 0u);
-            if (key != ctx->trivial_key || ctx->trivial_capacity < owned.size() * 8 || no_trivial) {
+            if (key != ctx->trivial_key || ctx->d_trivial.capacity() < owned.size() * 8 || no_trivial) {
                 std::vector<unsigned> masks;
                 trivial_pixel_masks(trivial_input(ctx), params, owned, nby, no_trivial, &masks);
-                if ((rcode = ensure(&ctx->d_trivial, &ctx->trivial_capacity, masks.size())) != RL_OK) return rcode;
-                HIP_OK(hipMemcpyAsync(ctx->d_trivial, masks.data(), masks.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+                if ((rcode = ctx->d_trivial.ensure(masks.size())) != RL_OK) return rcode;
+                HIP_OK(hipMemcpyAsync(ctx->d_trivial.get(), masks.data(), masks.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
                 HIP_OK(hipStreamSynchronize(st));        // (`masks` is a local)
                 ctx->trivial_key = no_trivial ? ~0ull : key;
             }
-            if ((rcode = ensure(&ctx->d_spec_stats, &ctx->spec_stats_capacity, 32 + 8 * (size_t)(spec_threads / 64u))) != RL_OK) return rcode;
-            HIP_OK(hipMemsetAsync(ctx->d_spec_stats, 0, 32 * sizeof(unsigned long long), st));
-            spc.trk_off = ctx->d_trk_off; spc.trk_st = ctx->d_trk_st; spc.trivial = ctx->d_trivial;
-            spc.stats = (stats || knobs.has(K_SPEC_STATS)) ? ctx->d_spec_stats : nullptr;
+            if ((rcode = ctx->d_spec_stats.ensure(32 + 8 * (size_t)(spec_threads / 64u))) != RL_OK) return rcode;
+            HIP_OK(hipMemsetAsync(ctx->d_spec_stats.get(), 0, 32 * sizeof(unsigned long long), st));
+            spc.trk_off = ctx->d_trk_off.get(); spc.trk_st = ctx->d_trk_st.get(); spc.trivial = ctx->d_trivial.get();
+            spc.stats = (stats || knobs.has(K_SPEC_STATS)) ? ctx->d_spec_stats.get() : nullptr;
             // (one overflow buffer serves both passes: the stride is the larger launch; the pass with fewer LDS levels — more overflow levels — sizes it first)
             const size_t n_thr = std::max<size_t>((size_t)((P + 255) / 256) * 256, spec_threads);
             if ((rcode = stack_conf(ctx, n_thr, &stc_s, false, spec_levels)) != RL_OK) return rcode;
@@ -479,26 +406,12 @@ private:
         // mapped host memory: [0] "every chain workgroup runs", [16 + j] "block j is complete"; pinned staging of the lists
         const size_t n_dev = 16 + (size_t)kMaxEvalLaunches + owned.size(), n_flags = 16 + owned.size();
         int rcode;
-        if ((rcode = ensure(&ctx->d_queue, &ctx->done_queue_capacity, n_dev)) != RL_OK) return rcode;
-        if (ctx->flags_capacity < n_flags) {
-            if (ctx->h_flags) hipHostFree(ctx->h_flags);
-            ctx->h_flags = nullptr; ctx->d_flags = nullptr; ctx->flags_capacity = 0;
-            HIP_OK(hipHostMalloc((void**)&ctx->h_flags, n_flags * sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
-            HIP_OK(hipHostGetDevicePointer((void**)&ctx->d_flags, ctx->h_flags, 0));
-            std::memset(ctx->h_flags, 0, n_flags * sizeof(unsigned));
-            ctx->flags_capacity = n_flags;
-        }
-        if (ctx->list_capacity < owned.size()) {
-            if (ctx->h_list) hipHostFree(ctx->h_list);
-            ctx->h_list = nullptr; ctx->list_capacity = 0;
-            HIP_OK(hipHostMalloc((void**)&ctx->h_list, owned.size() * sizeof(unsigned), hipHostMallocDefault));
-            ctx->list_capacity = owned.size();
-        }
-        HIP_OK(hipMemsetAsync(ctx->d_queue, 0, (16 + (size_t)kMaxEvalLaunches) * sizeof(unsigned), st));
-        ra.queue = ctx->d_queue; ra.chain_grid = chain_grid;
-        ra.done_flags = ctx->d_flags + 16; ra.started_flag = ctx->d_flags;
+        if ((rcode = ctx->d_queue.ensure(n_dev)) != RL_OK || (rcode = ctx->h_flags.ensure(n_flags)) != RL_OK || (rcode = ctx->h_list.ensure(owned.size())) != RL_OK) return rcode;
+        HIP_OK(hipMemsetAsync(ctx->d_queue.get(), 0, (16 + (size_t)kMaxEvalLaunches) * sizeof(unsigned), st));
+        ra.queue = ctx->d_queue.get(); ra.chain_grid = chain_grid;
+        ra.done_flags = ctx->h_flags.device_ptr() + 16; ra.started_flag = ctx->h_flags.device_ptr();
         ra.queue_seq = ++ctx->queue_seq;
-        if (ra.queue_seq == 0u) { std::memset(ctx->h_flags, 0, ctx->flags_capacity * sizeof(unsigned)); ra.queue_seq = ++ctx->queue_seq; }      // (the tag wrapped: 0 is the words' idle value)
+        if (ra.queue_seq == 0u) { std::memset(ctx->h_flags.get(), 0, ctx->h_flags.capacity() * sizeof(unsigned)); ra.queue_seq = ++ctx->queue_seq; }      // (the tag wrapped: 0 is the words' idle value)
         return RL_OK;
     }
 
@@ -511,7 +424,7 @@ private:
     int overlap_loop(const RenderConst& rb, const Plan& pb, unsigned seq, dim3 grid_q, const StackConf& stc_q) {
         HIP_OK(hipEventRecord(ctx->ev_chain_done, st));
         const unsigned n_blocks_owned = (unsigned)owned.size();
-        volatile unsigned* hf = ctx->h_flags;
+        volatile unsigned* hf = ctx->h_flags.get();
         std::vector<unsigned> waiting(n_blocks_owned);          // owned blocks not listed yet (the scan below only looks at these; it shrinks as blocks complete)
         for (unsigned j = 0; j < n_blocks_owned; j++) waiting[j] = j;
         unsigned n_listed = 0, n_launches = 0, scan_from = 0;
@@ -525,9 +438,9 @@ private:
         auto launch_batch = [&](unsigned first, unsigned count) -> int {
             const unsigned k = n_launches % (unsigned)rl_context::kEvalStreams;
             hipStream_t on = ctx->eval_streams[k];
-            HIP_OK(hipMemcpyAsync(ctx->d_queue + 16 + kMaxEvalLaunches + first, ctx->h_list + first, count * sizeof(unsigned), hipMemcpyHostToDevice, on));
+            HIP_OK(hipMemcpyAsync(ctx->d_queue.get() + 16 + kMaxEvalLaunches + first, ctx->h_list.get() + first, count * sizeof(unsigned), hipMemcpyHostToDevice, on));
             RenderConst rq = rb;
-            rq.q_list = ctx->d_queue + 16 + kMaxEvalLaunches + first; rq.q_n = count; rq.q_ctr = ctx->d_queue + 16 + n_launches;
+            rq.q_list = ctx->d_queue.get() + 16 + kMaxEvalLaunches + first; rq.q_n = count; rq.q_ctr = ctx->d_queue.get() + 16 + n_launches;
             // launches on different streams run side by side: each stream has its own statistics rows and its own columns of the overflow stack levels
             rq.partials = rb.partials + (size_t)k * resident * STAT_COUNT;
             StackConf stc_k = stc_q;
@@ -551,7 +464,7 @@ private:
                 size_t keep = 0;
                 for (size_t w = 0; w < waiting.size(); w++) {
                     const unsigned j = waiting[w];
-                    if (chain_over || hf[16 + j] == seq) ctx->h_list[n_listed++] = j; else waiting[keep++] = j;
+                    if (chain_over || hf[16 + j] == seq) ctx->h_list.get()[n_listed++] = j; else waiting[keep++] = j;
                 }
                 waiting.resize(keep);
             }
@@ -575,7 +488,7 @@ private:
     int run_chunk(const Chunk& ch) {
         DrainOnError guard{this};
         const dim3 block(256);
-        HIP_OK(hipMemcpyAsync(ctx->d_item_base, ch.base.data(), ch.base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(ctx->d_item_base.get(), ch.base.data(), ch.base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
         RenderConst ra = rc;
         ra.stream_mode = RL_STREAM_REFERENCE_ORDER;
         ra.n_items = plan_chain.n_items; ra.item_shift = plan_chain.item_shift; ra.split = 1;
@@ -595,7 +508,7 @@ private:
         cinit.active = std::min(pb.P, pb.n_items);
         cinit.next_item = pb.item_shift ? pb.n_items : pb.P;
         if (overlap) cinit.next_item = pb.n_items;          // (queue-fed: the dispenser has nothing to hand out)
-        HIP_OK(hipMemcpyAsync(ctx->d_counters, &cinit, sizeof(cinit), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(ctx->d_counters.get(), &cinit, sizeof(cinit), hipMemcpyHostToDevice, st));
         // (overlapped: a grid of the workgroups the chip keeps resident; its overflow stack levels are its own — the chain kernel beside it spills into the context's
         // first buffer under the same thread indices; allocated before anything is launched: an allocation may wait for the device)
         const dim3 grid_q((unsigned)cus * (unsigned)(ctx->lds_scene ? RL_FUSED_WAVES : RL_FUSED_WAVES_STREAMING));
@@ -607,7 +520,7 @@ private:
         if (timing) hipEventRecord(ctx->events[1], st);
         HIP_OK(hipGetLastError());
         if (overlap) {
-            rb.queue = ctx->d_queue; rb.queue_mode = 1u; rb.chain_grid = chain_grid;
+            rb.queue = ctx->d_queue.get(); rb.queue_mode = 1u; rb.chain_grid = chain_grid;
             if ((rcode = overlap_loop(rb, pb, ra.queue_seq, grid_q, stc_q)) != RL_OK) return rcode;
             overlapped = true;
             if (timing) hipEventRecord(ctx->events[3], st);
@@ -645,7 +558,7 @@ private:
     // k_stream_spec's counters (rl_render_stats.reserved) and, in the dev builds, its cycle shares and wave lifetimes
     int read_spec_stats() {
         unsigned long long spec_totals[32] = {0};
-        HIP_OK(hipMemcpy(spec_totals, ctx->d_spec_stats, sizeof(spec_totals), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(spec_totals, ctx->d_spec_stats.get(), sizeof(spec_totals), hipMemcpyDeviceToHost));
         spec_group = spc.group; spec_stat[0] = spec_totals[0]; spec_stat[1] = spec_totals[1]; spec_stat[2] = spec_totals[2];
         const bool verbose = knobs.has(K_SPEC_STATS);
         if (verbose) std::fprintf(stderr, "[spec] LDS per workgroup %zu bytes (scene %zu, %d stack levels)\n", lds_spec, (size_t)(ctx->lds_scene ? ctx->scene_lds_bytes : 0), stc_s.lds_levels);
@@ -654,7 +567,7 @@ private:
             (double)(spec_totals[0] + spec_totals[1] + spec_totals[2]) / std::max(1.0, (double)n_pixels * params->spp), (double)spec_totals[1] / std::max(1u, n_pixels), spec_totals[3]);
         if (knobs.has(K_SPEC_WAVE_TIMES) && spec_totals[8]) {     // dev build: lifetime of every wave (100 MHz clock)
             std::vector<unsigned long long> wt(8 * (size_t)(spec_threads / 64u));
-            HIP_OK(hipMemcpy(wt.data(), ctx->d_spec_stats + 32, wt.size() * 8, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(wt.data(), ctx->d_spec_stats.get() + 32, wt.size() * 8, hipMemcpyDeviceToHost));
             FILE* f = std::fopen(knobs.str(K_SPEC_WAVE_TIMES), "w");
             if (f) { unsigned long long t0 = ~0ull; for (size_t w = 0; w < wt.size() / 8; w++) if (wt[8 * w]) t0 = std::min(t0, wt[8 * w]);
                      for (size_t w = 0; w < wt.size() / 8; w++) std::fprintf(f, "%zu %.3f %.3f %llu %llu %.3f %.3f %llu %llu\n", w, (wt[8 * w] - t0) * 1e-5, (wt[8 * w + 1] - t0) * 1e-5, wt[8 * w + 2], wt[8 * w + 3], wt[8 * w + 4] * 1e-5, wt[8 * w + 5] * 1e-5, wt[8 * w + 6], wt[8 * w + 7]); std::fclose(f); }
@@ -731,11 +644,11 @@ private:
             in_batch++;
             if (in_batch == poll_every) {
                 HIP_OK(hipGetLastError());      // launch-configuration errors of the batch (non-sticky): never spin on a counter no kernel updates
-                HIP_OK(hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(Counters), hipMemcpyDeviceToHost, st));
+                HIP_OK(hipMemcpyAsync(ctx->h_counters.get(), ctx->d_counters.get(), sizeof(Counters), hipMemcpyDeviceToHost, st));
                 HIP_OK(hipStreamSynchronize(st));
                 if (timing) { int r = flush_events(in_batch); if (r != RL_OK) return r; }
                 in_batch = 0;
-                if (ctx->h_counters->active == 0) break;
+                if (ctx->h_counters.get()->active == 0) break;
             }
             if (iterations > (uint64_t)1 << 28) { rl_set_error("render did not terminate"); return RL_ERR_HIP; }
         }
@@ -755,24 +668,11 @@ private:
     int finish() {
         // one more raygen pass is never needed: `active` reaches 0 inside k_raygen after the last fold.
         if (split > 1 && !two_pass) { hipLaunchKernelGGL(k_fold_samples, dim3((n_pixels + 255) / 256), dim3(256), 0, st, rc); launches += 1; }
-        if (!out_is_device) HIP_OK(hipMemcpyAsync(out_rgb, d_out, (size_t)3 * W * H * sizeof(float), hipMemcpyDeviceToHost, st));
-        std::vector<unsigned long long> partials(n_partial_rows * STAT_COUNT);
-        HIP_OK(hipMemcpyAsync(partials.data(), ctx->d_partials, partials.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        unsigned long long totals[STAT_COUNT] = {0};
-        for (size_t r = 0; r < n_partial_rows; r++) for (int k = 0; k < STAT_COUNT; k++) totals[k] += partials[r * STAT_COUNT + k];
-        HIP_OK(hipGetLastError());
-        const auto t_end = std::chrono::steady_clock::now();
+        const int rcode = download();
+        if (rcode != RL_OK) return rcode;
         if (stats) {
-            std::memset(stats, 0, sizeof(*stats));
-            stats->camera_samples = totals[STAT_SAMPLES];
-            stats->vertices = totals[STAT_VERTICES];
-            stats->extension_rays = totals[STAT_EXT_RAYS];
-            stats->shadow_rays = totals[STAT_SHADOW_RAYS];
-            stats->rng_draws = totals[STAT_DRAWS];
             stats->iterations = iterations;
             stats->kernel_launches = launches;
-            stats->render_ms = std::chrono::duration<double, std::milli>(t_end - t_start).count();
             stats->ms_raygen = ms[0]; stats->ms_extend = ms[1]; stats->ms_shade = ms[2]; stats->ms_shadow = ms[3];
             stats->ms_other = ms_fused;   // the persistent fused kernel (pipeline 2); overlapped: the part of the evaluation pass left after the chain pass had ended
             stats->ms_prepass = ms_chain;  // k_stream_chain / k_stream_spec (reference-order streams, first pass)

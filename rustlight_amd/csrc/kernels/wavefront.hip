@@ -40,6 +40,7 @@
 
 #include "common.hip.h"
 #include "rngjump.h"
+#include "../host/hip_buffer.h"
 #include "../host/scene.h"
 #include "wavefront.h"
 #include "knobs.h"
@@ -257,21 +258,11 @@ static thread_local std::string g_last_error;
 void rl_set_error(const std::string& s) { g_last_error = s; }
 extern "C" const char* rl_last_error(void) { return g_last_error.c_str(); }
 
-#define HIP_OK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            rl_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                           \
-            (void)hipGetLastError();   /* the error is reported here; do not leave it for the next call */ \
-            return RL_ERR_HIP;                                                                         \
-        }                                                                                              \
-    } while (0)
-
 struct rl_context {
     int device = 0;
     hipStream_t stream = nullptr;
     DeviceScene ds{};
-    std::vector<void*> allocs;
+    std::vector<HipBuffer<unsigned char>> allocs;      // the scene's arrays
     uint32_t width = 0, height = 0;
     bool single_bsdf = true;
     int bsdf_type = 0;
@@ -280,37 +271,33 @@ struct rl_context {
     size_t scene_lds_bytes = 0;
     size_t lds_limit = 64 * 1024;     // dynamic LDS a workgroup may ask for on this device (hipDeviceAttributeMaxSharedMemoryPerBlock)
     // render scratch (grown on demand)
-    Pool pool{};
-    size_t pool_capacity = 0;
-    unsigned* d_owned = nullptr; size_t owned_capacity = 0;
-    unsigned* d_item_base = nullptr; size_t item_base_capacity = 0;
-    unsigned long long* d_block_seeds = nullptr; size_t seeds_capacity = 0;
-    unsigned long long* d_item_seed = nullptr; size_t item_capacity = 0;
-    unsigned* d_item_pixel = nullptr; size_t item_pixel_capacity = 0;
-    unsigned* d_queues = nullptr; unsigned* d_qcounts = nullptr; size_t queue_capacity = 0;
-    float* d_out = nullptr; size_t out_capacity = 0;
-    Counters* d_counters = nullptr;
-    Counters* h_counters = nullptr;   // pinned
-    unsigned long long* d_partials = nullptr; size_t partials_capacity = 0;
-    int* d_overflow = nullptr; size_t overflow_capacity = 0;
-    int* d_overflow2 = nullptr; size_t overflow2_capacity = 0;      // the overlapped evaluation pass's own overflow levels (it runs beside the chain pass, which uses d_overflow)
-    float* d_sample_buf = nullptr; size_t sample_buf_capacity = 0;   // sample-parallel pixels: [spp][pixel item][3]
-    unsigned long long* d_sample_states = nullptr; size_t sample_states_capacity = 0;   // reference-order streams, two passes: [spp][chunk pixel][4]
-    unsigned long long* d_chain_states = nullptr; size_t chain_states_capacity = 0;     // [owned block][4]
+    HipBuffer<float> pool_f; HipBuffer<unsigned> pool_u; HipBuffer<unsigned long long> pool_q;    // the wavefront pipeline's path-state pool: all three planes or none
+    HipBuffer<unsigned> d_owned, d_item_base;
+    HipBuffer<unsigned long long> d_block_seeds, d_item_seed;
+    HipBuffer<unsigned> d_item_pixel;
+    HipBuffer<float> d_out;
+    HipBuffer<Counters> d_counters;
+    HipBuffer<Counters, Mem::Pinned> h_counters;
+    HipBuffer<unsigned long long> d_partials;
+    HipBuffer<int> d_overflow;
+    HipBuffer<int> d_overflow2;                         // the overlapped evaluation pass's own overflow levels (it runs beside the chain pass, which uses d_overflow)
+    HipBuffer<float> d_sample_buf;                      // sample-parallel pixels: [spp][pixel item][3]
+    HipBuffer<unsigned long long> d_sample_states;      // reference-order streams, two passes: [spp][chunk pixel][4]; the light tracer's splat image
+    HipBuffer<unsigned long long> d_chain_states;       // [owned block][4]
     // k_stream_spec (spec.hip.h): per-lane tracks of the speculative first pass, the trivial-pixel masks and its counters
-    unsigned* d_trk_off = nullptr; size_t trk_off_capacity = 0;
-    ulonglong2* d_trk_st = nullptr; size_t trk_st_capacity = 0;
-    unsigned* d_trivial = nullptr; size_t trivial_capacity = 0;
+    HipBuffer<unsigned> d_trk_off;
+    HipBuffer<ulonglong2> d_trk_st;
+    HipBuffer<unsigned> d_trivial;
     uint64_t trivial_key = ~0ull;         // (shard index, shard count, sensor expanded?) the masks on the device were computed for
-    unsigned long long* d_spec_stats = nullptr; size_t spec_stats_capacity = 0;
+    HipBuffer<unsigned long long> d_spec_stats;
     std::vector<hipEvent_t> events;
     // the evaluation pass overlapped with the chain pass (reference-order streams): its own low-priority stream, the completion queue, ordering events
     static constexpr int kEvalStreams = 4;      // the evaluation launches beside the chain pass go round these (a launch lasts as long as its slowest pixel: several may have to be in flight)
     hipStream_t stream2 = nullptr; hipStream_t eval_streams[kEvalStreams] = {};
-    unsigned* d_queue = nullptr; size_t done_queue_capacity = 0;       // device: [0] chain workgroups started, [16 + k] item-claim counter of the k-th evaluation launch, then the block lists
+    HipBuffer<unsigned> d_queue;                        // device: [0] chain workgroups started, [16 + k] item-claim counter of the k-th evaluation launch, then the block lists
     hipEvent_t ev_chain_done = nullptr;
-    unsigned* h_flags = nullptr; unsigned* d_flags = nullptr; size_t flags_capacity = 0;      // pinned, mapped: [0] the chain kernel's "every workgroup runs" word, [16 + j] block j's chain is complete
-    unsigned* h_list = nullptr; size_t list_capacity = 0;              // pinned: the block lists of the evaluation launches (staging of the copies to the device)
+    HipBuffer<unsigned, Mem::Mapped> h_flags;           // [0] the chain kernel's "every workgroup runs" word, [16 + j] block j's chain is complete
+    HipBuffer<unsigned, Mem::Pinned> h_list;            // the block lists of the evaluation launches (staging of the copies to the device)
     unsigned queue_seq = 0;
     BvhBuild bvh_dump;                // kept for rl_debug_bvh and for the two-level records (built on first use)
     Knobs knobs;                      // execution options: the environment as rl_context_create found it, then rl_context_set_option (knobs.h)
@@ -320,12 +307,12 @@ struct rl_context {
 template <typename T>
 static int upload(rl_context* ctx, const std::vector<T>& v, const T** out) {
     *out = nullptr;
-    size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    void* p = nullptr;
-    HIP_OK(hipMalloc(&p, bytes));
-    ctx->allocs.push_back(p);
-    if (!v.empty()) HIP_OK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = reinterpret_cast<const T*>(p);
+    ctx->allocs.emplace_back();
+    HipBuffer<unsigned char>& b = ctx->allocs.back();
+    int rcode;
+    if ((rcode = b.ensure(std::max<size_t>(v.size(), 1) * sizeof(T))) != RL_OK) return rcode;
+    if (!v.empty()) HIP_OK(hipMemcpy(b.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    *out = reinterpret_cast<const T*>(b.get());
     return RL_OK;
 }
 
@@ -481,8 +468,8 @@ extern "C" int rl_context_create(const rl_scene* scene, int device, rl_context**
             if ((rc = upload(ctx, blocks, &ds.nodes_t)) != RL_OK) break;
             ds.root_t = root_t;
         }
-        if (hipMalloc((void**)&ctx->d_counters, sizeof(Counters)) != hipSuccess) { rl_set_error("hipMalloc counters"); rc = RL_ERR_HIP; break; }
-        if (hipHostMalloc((void**)&ctx->h_counters, sizeof(Counters)) != hipSuccess) { rl_set_error("hipHostMalloc counters"); rc = RL_ERR_HIP; break; }
+        if (ctx->d_counters.ensure(1) != RL_OK) { rl_set_error("hipMalloc counters"); rc = RL_ERR_HIP; break; }
+        if (ctx->h_counters.ensure(1) != RL_OK) { rl_set_error("hipHostMalloc counters"); rc = RL_ERR_HIP; break; }
     } while (0);
     if (rc != RL_OK) { rl_context_destroy(ctx); return rc; }
     *out = ctx;
@@ -491,31 +478,13 @@ extern "C" int rl_context_create(const rl_scene* scene, int device, rl_context**
 
 extern "C" void rl_context_destroy(rl_context* ctx) {
     if (!ctx) return;
-    hipSetDevice(ctx->device);
-    for (void* p : ctx->allocs) hipFree(p);
-    void* scratch[] = {ctx->pool.f, ctx->pool.u, ctx->pool.q, ctx->d_owned, ctx->d_item_base, ctx->d_block_seeds, ctx->d_item_seed,
-                       ctx->d_item_pixel, ctx->d_queues, ctx->d_qcounts, ctx->d_out, ctx->d_counters, ctx->d_partials, ctx->d_overflow, ctx->d_sample_buf,
-                       ctx->d_sample_states, ctx->d_chain_states, ctx->d_trk_off, ctx->d_trk_st, ctx->d_trivial, ctx->d_spec_stats, ctx->d_queue, ctx->d_overflow2};
-    for (void* p : scratch) if (p) hipFree(p);
-    if (ctx->h_counters) hipHostFree(ctx->h_counters);
+    hipSetDevice(ctx->device);        // (the buffers are freed by `delete ctx`, on this device)
     for (hipEvent_t ev : ctx->events) hipEventDestroy(ev);
     if (ctx->ev_chain_done) hipEventDestroy(ctx->ev_chain_done);
-    if (ctx->h_flags) hipHostFree(ctx->h_flags);
-    if (ctx->h_list) hipHostFree(ctx->h_list);
     for (int k = 1; k < rl_context::kEvalStreams; k++) if (ctx->eval_streams[k] && ctx->eval_streams[k] != ctx->stream2) hipStreamDestroy(ctx->eval_streams[k]);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
-}
-
-template <typename T>
-static int ensure(T** p, size_t* cap, size_t n) {
-    if (*cap >= n && *p) return RL_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    HIP_OK(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
-    *cap = n;
-    return RL_OK;
 }
 
 // Scenes that stream their BVH keep only kLdsStackLevelsStreaming levels in LDS: their pools are sparse (most waves of a
@@ -532,25 +501,25 @@ static size_t traversal_lds_bytes(const rl_context* ctx, bool lds_scene, unsigne
 }
 // overflow levels beyond the LDS part, [2 * levels][n_threads] ints
 static int stack_conf(rl_context* ctx, size_t n_threads, StackConf* out, bool second = false, int lds_levels = -1) {
-    int*& d_overflow = second ? ctx->d_overflow2 : ctx->d_overflow;
-    size_t& overflow_capacity = second ? ctx->overflow2_capacity : ctx->overflow_capacity;
+    HipBuffer<int>& d_overflow = second ? ctx->d_overflow2 : ctx->d_overflow;
     out->lds_levels = lds_levels >= 0 ? std::min(lds_levels, lds_levels_of(ctx)) : lds_levels_of(ctx);
     out->pre_group = 0;          // only k_stream_chain uses it (its launch code sets it)
     out->overflow = nullptr;
     out->overflow_stride = n_threads;
     int extra = (int)std::max(ctx->ds.stack_depth, ctx->ds.stack_depth4) - out->lds_levels;     // (the tolerance build's BVH4 stacks are the deeper ones)
     if (extra > 0) {
-        size_t need = (size_t)2 * extra * n_threads;
-        if (overflow_capacity < need) {
-            if (d_overflow) hipFree(d_overflow);
-            d_overflow = nullptr;
-            overflow_capacity = 0;
-            HIP_OK(hipMalloc((void**)&d_overflow, need * sizeof(int)));
-            overflow_capacity = need;
-        }
-        out->overflow = d_overflow;
+        const int rcode = d_overflow.ensure((size_t)2 * extra * n_threads);
+        if (rcode != RL_OK) return rcode;
+        out->overflow = d_overflow.get();
     }
     return RL_OK;
+}
+
+// block b's pixels: blocks are numbered x-major, nby = ceil(H / 16) to a column (mod.rs:351-374; the kernels' block_geometry)
+struct BlockRect { unsigned x, y, w, h; };
+static BlockRect block_rect(size_t b, size_t nby, uint32_t W, uint32_t H) {
+    const unsigned x = (unsigned)(b / nby) * 16u, y = (unsigned)(b % nby) * 16u;
+    return {x, y, std::min(16u, W - x), std::min(16u, H - y)};
 }
 
 // ---- k_stream_spec: pixels whose camera samples take exactly two draws (Path::from_sensor's jitter) whatever the stream holds.
@@ -574,10 +543,7 @@ static void trivial_pixel_masks(const TrivialInput& ti, const rl_path_params* pa
     const bool expand = !params->has_max_depth || 1u < params->max_depth;
     auto all_of_block = [&](size_t j, unsigned npx) { for (unsigned c = 0; c < npx; c++) (*out)[j * 8 + (c >> 5)] |= 1u << (c & 31u); };
     if (!expand) {      // the sensor vertex is never expanded: two draws per sample everywhere
-        for (size_t j = 0; j < owned.size(); j++) {
-            const unsigned bx = (unsigned)(owned[j] / nby) * 16u, by = (unsigned)(owned[j] % nby) * 16u;
-            all_of_block(j, std::min(16u, W - bx) * std::min(16u, H - by));
-        }
+        for (size_t j = 0; j < owned.size(); j++) { const BlockRect r = block_rect(owned[j], nby, W, H); all_of_block(j, r.w * r.h); }
         return;
     }
     if (ti.medium || no_shortcut) return;      // Edge::from_ray samples the medium on a miss too: no shortcut
@@ -631,8 +597,8 @@ static void trivial_pixel_masks(const TrivialInput& ti, const rl_path_params* pa
         return false;
     };
     for (size_t j = 0; j < owned.size(); j++) {
-        const unsigned bx = (unsigned)(owned[j] / nby) * 16u, by = (unsigned)(owned[j] % nby) * 16u;
-        const unsigned bw = std::min(16u, W - bx), bh = std::min(16u, H - by);
+        const BlockRect r = block_rect(owned[j], nby, W, H);
+        const unsigned bx = r.x, by = r.y, bw = r.w, bh = r.h;
         if (misses(bx - 0.25, by - 0.25, bx + bw + 0.25, by + bh + 0.25)) { all_of_block(j, bw * bh); continue; }
         for (unsigned c = 0; c < bw * bh; c++) {
             const double x = bx + c % bw, y = by + c / bw;
@@ -662,30 +628,146 @@ extern "C" int rl_debug_trivial_pixels(const rl_scene* scene, int has_max_depth,
     trivial_pixel_masks(ti, &pp, owned, nby, false, &masks);
     std::memset(out, 0, (size_t)ti.W * ti.H);
     for (size_t b = 0; b < owned.size(); b++) {
-        const unsigned bx = (unsigned)(b / nby) * 16u, by = (unsigned)(b % nby) * 16u, bw = std::min(16u, ti.W - bx), bh = std::min(16u, ti.H - by);
-        for (unsigned c = 0; c < bw * bh; c++) if ((masks[b * 8 + (c >> 5)] >> (c & 31u)) & 1u) out[(size_t)(by + c / bw) * ti.W + bx + c % bw] = 1;
+        const BlockRect r = block_rect(b, nby, ti.W, ti.H);
+        for (unsigned c = 0; c < r.w * r.h; c++) if ((masks[b * 8 + (c >> 5)] >> (c & 31u)) & 1u) out[(size_t)(r.y + c / r.w) * ti.W + r.x + c % r.w] = 1;
     }
     return RL_OK;
 }
+
+// ---- what every render entry point does the same way, one RenderFrame per call: this shard's blocks, the tables, the image and the statistics rows, the
+// RenderConst fields they fill alike, the event pool, and the finish (image download, rows summed, the counters every kind reports)
+template <typename Params>
+static int check_frame(const rl_context* ctx, const Params* params, const uint64_t* block_seeds, size_t n_blocks, const float* out_rgb) {
+    if (!ctx || !params || !block_seeds || !out_rgb) return RL_ERR_INVALID_ARGUMENT;
+    if (n_blocks != (size_t)((ctx->width + 15) / 16) * ((ctx->height + 15) / 16)) { rl_set_error("n_blocks does not match the image size"); return RL_ERR_INVALID_ARGUMENT; }
+    if (params->spp == 0) { rl_set_error("spp must be > 0 (assert_ne!(scene.nb_samples, 0), mod.rs:410)"); return RL_ERR_INVALID_ARGUMENT; }
+    return RL_OK;
+}
+// path, ao and direct: the stream mode, the numerics (ao / direct pass RL_NUMERICS_EXACT) and the shard
+static int check_streams(int32_t stream_mode, uint32_t spp, uint32_t numerics, uint32_t shard_index, uint32_t shard_count) {
+    if (stream_mode < RL_STREAM_REFERENCE_ORDER || stream_mode > RL_STREAM_STRATIFIED) { rl_set_error("stream_mode must be 0 (reference order), 1 (per sample) or 2 (stratified)"); return RL_ERR_INVALID_ARGUMENT; }
+    if (stream_mode == RL_STREAM_STRATIFIED && spp > (1u << 30)) { rl_set_error("the stratified sampler takes at most 2^30 spp"); return RL_ERR_INVALID_ARGUMENT; }
+    if (numerics > RL_NUMERICS_FAST) { rl_set_error("numerics must be 0 (exact) or 1 (fast)"); return RL_ERR_INVALID_ARGUMENT; }
+    if (shard_index >= (shard_count ? shard_count : 1)) return RL_ERR_INVALID_ARGUMENT;
+    return RL_OK;
+}
+
+namespace {
+
+struct RenderFrame {
+    rl_context* const ctx;
+    const uint64_t* const block_seeds;
+    const size_t n_blocks;
+    float* const out_rgb;
+    const int out_is_device;
+    const hipStream_t st;
+    rl_render_stats* const stats;
+    const Knobs knobs;                 // the context's options as they stood when the render started
+    const uint32_t W, H;
+    const size_t nby;
+    const uint32_t shard_count;
+    const std::chrono::steady_clock::time_point t_start;
+    const bool timing;                 // HIP events around the kernels
+    int cus = 256;
+    std::vector<unsigned> owned, item_base;      // this shard's blocks in creation order (mod.rs:351-374: `b % shard_count`), their first pixel items
+    unsigned n_pixels = 0;
+    float* d_out = nullptr;            // the caller's buffer or the context's staging copy
+    size_t n_rows = 0;                 // statistics rows
+    unsigned long long totals[STAT_COUNT] = {};
+
+    RenderFrame(rl_context* c, const uint64_t* seeds, size_t nb, float* out, int out_dev, void* stream_arg, rl_render_stats* s, uint32_t shard_index, uint32_t n_shards)
+        : ctx(c), block_seeds(seeds), n_blocks(nb), out_rgb(out), out_is_device(out_dev), st(stream_arg ? (hipStream_t)stream_arg : c->stream), stats(s),
+          knobs(c->knobs), W(c->width), H(c->height), nby((c->height + 15) / 16), shard_count(n_shards ? n_shards : 1), t_start(std::chrono::steady_clock::now()),
+          timing(s != nullptr && !knobs.has(K_NO_EVENTS)) {
+        for (size_t b = 0; b < n_blocks; b++) {
+            if (b % shard_count != shard_index) continue;
+            const BlockRect r = block_rect(b, nby, W, H);
+            owned.push_back((unsigned)b);
+            item_base.push_back(n_pixels);
+            n_pixels += r.w * r.h;
+        }
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    }
+
+    // the recorded sampler states of reference-order streams may take this many bytes (test knob state_budget_mb: forces several chunks)
+    size_t max_state_bytes() const { return knobs.has(K_STATE_BUDGET_MB) ? std::max<size_t>(1, (size_t)knobs.i(K_STATE_BUDGET_MB, 0)) << 20 : (size_t)24 << 30; }
+
+    int alloc_tables() {
+        int rcode;
+        if ((rcode = ctx->d_owned.ensure(owned.size())) != RL_OK || (rcode = ctx->d_item_base.ensure(owned.size())) != RL_OK ||
+            (rcode = ctx->d_block_seeds.ensure(n_blocks)) != RL_OK) return rcode;
+        return RL_OK;
+    }
+    int alloc_output(size_t rows) {
+        d_out = out_rgb;
+        if (!out_is_device) {
+            const int rcode = ctx->d_out.ensure((size_t)3 * W * H);
+            if (rcode != RL_OK) return rcode;
+            d_out = ctx->d_out.get();
+        }
+        n_rows = rows;
+        return ctx->d_partials.ensure(n_rows * STAT_COUNT);
+    }
+    int upload(bool with_item_base, bool zero_image) {
+        HIP_OK(hipMemcpyAsync(ctx->d_owned.get(), owned.data(), owned.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        if (with_item_base) HIP_OK(hipMemcpyAsync(ctx->d_item_base.get(), item_base.data(), item_base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(ctx->d_block_seeds.get(), block_seeds, n_blocks * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (zero_image) HIP_OK(hipMemsetAsync(d_out, 0, (size_t)3 * W * H * sizeof(float), st));
+        return RL_OK;
+    }
+    int zero_rows() {
+        HIP_OK(hipMemsetAsync(ctx->d_partials.get(), 0, n_rows * STAT_COUNT * sizeof(unsigned long long), st));
+        return RL_OK;
+    }
+    RenderConst render_const(uint32_t spp, int32_t stream_mode, int32_t seed_variant) const {
+        RenderConst rc{};
+        rc.spp = spp;
+        rc.stream_mode = stream_mode; rc.seed_variant = seed_variant;
+        rc.inv_spp = 1.0f / (float)spp;
+        rc.W = W; rc.H = H; rc.nby = (unsigned)nby;
+        rc.owned_blocks = ctx->d_owned.get(); rc.block_item_base = ctx->d_item_base.get(); rc.n_owned = (unsigned)owned.size();
+        rc.block_seeds = ctx->d_block_seeds.get();
+        rc.item_seed = ctx->d_item_seed.get(); rc.item_pixel = ctx->d_item_pixel.get();
+        rc.out = d_out;
+        rc.counters = ctx->d_counters.get();
+        rc.partials = ctx->d_partials.get();
+        return rc;
+    }
+    int grow_events(size_t n) {
+        if (timing) while (ctx->events.size() < n) { hipEvent_t ev; HIP_OK(hipEventCreate(&ev)); ctx->events.push_back(ev); }
+        return RL_OK;
+    }
+    // the image to the caller and the statistics rows summed into `totals`; with stats: the counters every kind reports and the call's wall time
+    int download() {
+        if (!out_is_device) HIP_OK(hipMemcpyAsync(out_rgb, d_out, (size_t)3 * W * H * sizeof(float), hipMemcpyDeviceToHost, st));
+        std::vector<unsigned long long> partials(n_rows * STAT_COUNT);
+        HIP_OK(hipMemcpyAsync(partials.data(), ctx->d_partials.get(), partials.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipGetLastError());
+        for (size_t r = 0; r < n_rows; r++) for (int k = 0; k < STAT_COUNT; k++) totals[k] += partials[r * STAT_COUNT + k];
+        if (stats) {
+            std::memset(stats, 0, sizeof(*stats));
+            stats->camera_samples = totals[STAT_SAMPLES]; stats->vertices = totals[STAT_VERTICES]; stats->extension_rays = totals[STAT_EXT_RAYS];
+            stats->shadow_rays = totals[STAT_SHADOW_RAYS]; stats->rng_draws = totals[STAT_DRAWS];
+            stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        }
+        return RL_OK;
+    }
+};
+
+}  // namespace
 
 #include "path_render.hip.h"
 
 extern "C" int rl_render_path(rl_context* ctx, const rl_path_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
                               int out_is_device, void* stream_arg, rl_render_stats* stats) {
-    if (!ctx || !params || !block_seeds || !out_rgb) return RL_ERR_INVALID_ARGUMENT;
-    const uint32_t W = ctx->width, H = ctx->height;
-    const size_t nbx = (W + 15) / 16, nby = (H + 15) / 16;
-    if (n_blocks != nbx * nby) { rl_set_error("n_blocks does not match the image size"); return RL_ERR_INVALID_ARGUMENT; }
-    if (params->spp == 0) { rl_set_error("spp must be > 0 (assert_ne!(scene.nb_samples, 0), mod.rs:410)"); return RL_ERR_INVALID_ARGUMENT; }
+    int rcode;
+    if ((rcode = check_frame(ctx, params, block_seeds, n_blocks, out_rgb)) != RL_OK) return rcode;
     if (params->strategy < 0 || params->strategy > 2) return RL_ERR_INVALID_ARGUMENT;
-    if (params->stream_mode < RL_STREAM_REFERENCE_ORDER || params->stream_mode > RL_STREAM_STRATIFIED) { rl_set_error("stream_mode must be 0 (reference order), 1 (per sample) or 2 (stratified)"); return RL_ERR_INVALID_ARGUMENT; }
-    if (params->stream_mode == RL_STREAM_STRATIFIED && params->spp > (1u << 30)) { rl_set_error("the stratified sampler takes at most 2^30 spp"); return RL_ERR_INVALID_ARGUMENT; }
-    if (params->numerics > RL_NUMERICS_FAST) { rl_set_error("numerics must be 0 (exact) or 1 (fast)"); return RL_ERR_INVALID_ARGUMENT; }
-    const uint32_t shard_count = params->shard_count ? params->shard_count : 1;
-    if (params->shard_index >= shard_count) return RL_ERR_INVALID_ARGUMENT;
+    if ((rcode = check_streams(params->stream_mode, params->spp, params->numerics, params->shard_index, params->shard_count)) != RL_OK) return rcode;
     if (params->strategy != RL_STRATEGY_BSDF && ctx->ds.n_emitters == 0) { rl_set_error("light sampling requested but the scene has no emitter"); return RL_ERR_NO_EMITTER; }
     HIP_OK(hipSetDevice(ctx->device));
-    PathRender job(ctx, params, block_seeds, n_blocks, out_rgb, out_is_device, stream_arg ? (hipStream_t)stream_arg : ctx->stream, stats);
+    PathRender job(ctx, params, block_seeds, n_blocks, out_rgb, out_is_device, stream_arg, stats);
     return job.run();
 }
 
@@ -722,133 +804,77 @@ __global__ void k_debug_rng_advance(unsigned n, const unsigned long long* in, co
 extern "C" int rl_debug_rng_advance(int device, size_t n, const uint64_t* states_in, const uint32_t* counts, uint64_t* states_out) {
     if (!states_in || !counts || !states_out || n == 0 || n > (1u << 24)) return RL_ERR_INVALID_ARGUMENT;
     HIP_OK(hipSetDevice(device));
-    unsigned long long *d_in = nullptr, *d_out = nullptr; unsigned* d_c = nullptr;
-    HIP_OK(hipMalloc((void**)&d_in, n * 32)); HIP_OK(hipMalloc((void**)&d_out, n * 32)); HIP_OK(hipMalloc((void**)&d_c, n * 4));
-    HIP_OK(hipMemcpy(d_in, states_in, n * 32, hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(d_c, counts, n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(rl::k_debug_rng_advance, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, (unsigned)n, d_in, d_c, d_out);
+    HipBuffer<unsigned long long> d_in, d_out; HipBuffer<unsigned> d_c;
+    int rcode;
+    if ((rcode = d_in.ensure(4 * n)) != RL_OK || (rcode = d_out.ensure(4 * n)) != RL_OK || (rcode = d_c.ensure(n)) != RL_OK) return rcode;
+    HIP_OK(hipMemcpy(d_in.get(), states_in, n * 32, hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(d_c.get(), counts, n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(rl::k_debug_rng_advance, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, (unsigned)n, d_in.get(), d_c.get(), d_out.get());
     HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpy(states_out, d_out, n * 32, hipMemcpyDeviceToHost));
-    hipFree(d_in); hipFree(d_out); hipFree(d_c);
+    HIP_OK(hipMemcpy(states_out, d_out.get(), n * 32, hipMemcpyDeviceToHost));
     return RL_OK;
 }
 
 // ---- ao / direct: Integrator::compute through the same tiling driver (one launch)
 static int render_mc(rl_context* ctx, int kind, const rl_mc_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
                      int out_is_device, void* stream_arg, rl_render_stats* stats) {
-    if (!ctx || !params || !block_seeds || !out_rgb) return RL_ERR_INVALID_ARGUMENT;
-    const uint32_t W = ctx->width, H = ctx->height;
-    const size_t nbx = (W + 15) / 16, nby = (H + 15) / 16;
-    if (n_blocks != nbx * nby || params->spp == 0) return RL_ERR_INVALID_ARGUMENT;
-    if (params->stream_mode < RL_STREAM_REFERENCE_ORDER || params->stream_mode > RL_STREAM_STRATIFIED) { rl_set_error("stream_mode must be 0 (reference order), 1 (per sample) or 2 (stratified)"); return RL_ERR_INVALID_ARGUMENT; }
-    if (params->stream_mode == RL_STREAM_STRATIFIED && params->spp > (1u << 30)) { rl_set_error("the stratified sampler takes at most 2^30 spp"); return RL_ERR_INVALID_ARGUMENT; }
-    const uint32_t shard_count = params->shard_count ? params->shard_count : 1;
-    if (params->shard_index >= shard_count) return RL_ERR_INVALID_ARGUMENT;
+    int rcode;
+    if ((rcode = check_frame(ctx, params, block_seeds, n_blocks, out_rgb)) != RL_OK) return rcode;
+    if ((rcode = check_streams(params->stream_mode, params->spp, RL_NUMERICS_EXACT, params->shard_index, params->shard_count)) != RL_OK) return rcode;
     if (kind == 1 && params->nb_light_samples > 0 && ctx->ds.n_emitters == 0) { rl_set_error("light sampling requested but the scene has no emitter"); return RL_ERR_NO_EMITTER; }
     HIP_OK(hipSetDevice(ctx->device));
-    hipStream_t st = stream_arg ? (hipStream_t)stream_arg : ctx->stream;
-    auto t_start = std::chrono::steady_clock::now();
-    std::vector<unsigned> owned, item_base;
-    unsigned n_pixels = 0;
-    for (size_t b = 0; b < n_blocks; b++) {
-        if (b % shard_count != params->shard_index) continue;
-        unsigned bx = (unsigned)(b / nby) * 16u, by = (unsigned)(b % nby) * 16u;
-        owned.push_back((unsigned)b);
-        item_base.push_back(n_pixels);
-        n_pixels += std::min(16u, W - bx) * std::min(16u, H - by);
-    }
+    RenderFrame fr(ctx, block_seeds, n_blocks, out_rgb, out_is_device, stream_arg, stats, params->shard_index, params->shard_count);
     const bool strat = params->stream_mode == RL_STREAM_STRATIFIED;
     const bool per_sample = params->stream_mode == RL_STREAM_PER_SAMPLE || strat;      // (stratified: per-pixel items, the pixel seeds k_seed_pixels writes)
     // reference-order streams in two passes, as for `path` (chain.hip.h): k_mc_chain records where every camera sample starts in its block's stream (a sample's
     // draw count follows from its camera ray alone), then the per-pixel form evaluates all samples from those states.  One chunk: when the states do not fit
     // their budget the single-pass walk (one lane per block) runs instead, as it does under RL_REF_SINGLE_PASS.
-    const Knobs knobs = ctx->knobs;       // (the context's options as they stand now: knobs.h)
-    size_t state_budget = (size_t)24 << 30;
-    if (knobs.has(K_STATE_BUDGET_MB)) state_budget = std::max<size_t>(1, (size_t)knobs.i(K_STATE_BUDGET_MB, 0)) << 20;
-    const bool two_pass = !per_sample && !owned.empty() && !knobs.has(K_REF_SINGLE_PASS) && (size_t)n_pixels * params->spp * 32 <= state_budget;
+    const bool two_pass = !per_sample && !fr.owned.empty() && !fr.knobs.has(K_REF_SINGLE_PASS) && (size_t)fr.n_pixels * params->spp * 32 <= fr.max_state_bytes();
     const bool per_pixel = per_sample || two_pass;
-    const unsigned n_items = per_pixel ? n_pixels : (unsigned)owned.size();
+    const unsigned n_items = per_pixel ? fr.n_pixels : (unsigned)fr.owned.size();
     unsigned chain_shift = 0;
     if (two_pass) {
-        int cus = 256;
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-        while (chain_shift < 6u && (owned.size() << (chain_shift + 1u)) <= (size_t)cus * 4u * 256u) chain_shift++;
-        if (knobs.has(K_ITEM_SHIFT)) chain_shift = std::min(6u, (unsigned)std::max<long long>(0, knobs.i(K_ITEM_SHIFT, 0)));
+        while (chain_shift < 6u && (fr.owned.size() << (chain_shift + 1u)) <= (size_t)fr.cus * 4u * 256u) chain_shift++;
+        if (fr.knobs.has(K_ITEM_SHIFT)) chain_shift = std::min(6u, (unsigned)std::max<long long>(0, fr.knobs.i(K_ITEM_SHIFT, 0)));
     }
-    const unsigned chain_threads = two_pass ? std::max(256u, (unsigned)((((size_t)owned.size() << chain_shift) + 255u) / 256u * 256u)) : 0u;
+    const unsigned chain_threads = two_pass ? std::max(256u, (unsigned)((((size_t)fr.owned.size() << chain_shift) + 255u) / 256u * 256u)) : 0u;
     const unsigned n_threads = std::max(chain_threads, std::max(256u, (n_items + 255u) / 256u * 256u));
-    int rcode;
-    if ((rcode = ensure(&ctx->d_owned, &ctx->owned_capacity, owned.size())) != RL_OK) return rcode;
-    if ((rcode = ensure(&ctx->d_item_base, &ctx->item_base_capacity, owned.size())) != RL_OK) return rcode;
-    if ((rcode = ensure(&ctx->d_block_seeds, &ctx->seeds_capacity, n_blocks)) != RL_OK) return rcode;
-    if (per_pixel) {
-        if ((rcode = ensure(&ctx->d_item_seed, &ctx->item_capacity, n_pixels)) != RL_OK) return rcode;
-        if ((rcode = ensure(&ctx->d_item_pixel, &ctx->item_pixel_capacity, n_pixels)) != RL_OK) return rcode;
-    }
-    if (two_pass && (rcode = ensure(&ctx->d_sample_states, &ctx->sample_states_capacity, (size_t)n_pixels * params->spp * 4)) != RL_OK) return rcode;
-    float* d_out = out_rgb;
-    if (!out_is_device) {
-        if ((rcode = ensure(&ctx->d_out, &ctx->out_capacity, (size_t)3 * W * H)) != RL_OK) return rcode;
-        d_out = ctx->d_out;
-    }
-    const size_t n_rows = n_threads / 256;
-    if ((rcode = ensure(&ctx->d_partials, &ctx->partials_capacity, n_rows * STAT_COUNT)) != RL_OK) return rcode;
-    HIP_OK(hipMemcpyAsync(ctx->d_owned, owned.data(), owned.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(ctx->d_item_base, item_base.data(), item_base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(ctx->d_block_seeds, block_seeds, n_blocks * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemsetAsync(d_out, 0, (size_t)3 * W * H * sizeof(float), st));
-    HIP_OK(hipMemsetAsync(ctx->d_partials, 0, n_rows * STAT_COUNT * sizeof(unsigned long long), st));
-    RenderConst rc{};
-    rc.spp = params->spp;
-    rc.stream_mode = params->stream_mode; rc.seed_variant = params->seed_variant;
-    rc.inv_spp = 1.0f / (float)params->spp;
-    rc.W = W; rc.H = H; rc.nby = (unsigned)nby;
+    if ((rcode = fr.alloc_tables()) != RL_OK) return rcode;
+    if (per_pixel && ((rcode = ctx->d_item_seed.ensure(fr.n_pixels)) != RL_OK || (rcode = ctx->d_item_pixel.ensure(fr.n_pixels)) != RL_OK)) return rcode;
+    if (two_pass && (rcode = ctx->d_sample_states.ensure((size_t)fr.n_pixels * params->spp * 4)) != RL_OK) return rcode;
+    if ((rcode = fr.alloc_output(n_threads / 256)) != RL_OK) return rcode;
+    if ((rcode = fr.upload(true, true)) != RL_OK || (rcode = fr.zero_rows()) != RL_OK) return rcode;
+    RenderConst rc = fr.render_const(params->spp, params->stream_mode, params->seed_variant);
     rc.n_items = n_items;
-    rc.split = 1; rc.sample_buf = nullptr;
-    rc.owned_blocks = ctx->d_owned; rc.block_item_base = ctx->d_item_base; rc.n_owned = (unsigned)owned.size();
-    rc.block_seeds = ctx->d_block_seeds;
-    rc.item_seed = ctx->d_item_seed; rc.item_pixel = ctx->d_item_pixel;
-    rc.out = d_out;
-    rc.counters = ctx->d_counters;
-    rc.partials = ctx->d_partials;
-    rc.sample_states = ctx->d_sample_states; rc.n_state_pixels = n_pixels;
+    rc.split = 1;
+    rc.sample_states = ctx->d_sample_states.get(); rc.n_state_pixels = fr.n_pixels;
     McConst mp{params->has_max_distance, params->max_distance, params->normal_correction, params->nb_bsdf_samples, params->nb_light_samples};
     StackConf stc;
     if ((rcode = stack_conf(ctx, n_threads, &stc)) != RL_OK) return rcode;
     const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
     const dim3 grid((std::max(256u, (n_items + 255u) / 256u * 256u)) / 256), block(256);
-    const bool timing = stats != nullptr && !knobs.has(K_NO_EVENTS);
-    while (timing && ctx->events.size() < 4) { hipEvent_t ev; HIP_OK(hipEventCreate(&ev)); ctx->events.push_back(ev); }
-    if (per_pixel && !owned.empty()) hipLaunchKernelGGL(k_seed_pixels, dim3(((unsigned)owned.size() + 63) / 64), dim3(64), 0, st, rc);     // (two-pass: for item_pixel)
+    if ((rcode = fr.grow_events(4)) != RL_OK) return rcode;
+    const hipStream_t st = fr.st;
+    if (per_pixel && !fr.owned.empty()) hipLaunchKernelGGL(k_seed_pixels, dim3(((unsigned)fr.owned.size() + 63) / 64), dim3(64), 0, st, rc);     // (two-pass: for item_pixel)
     if (two_pass) {
         RenderConst ra = rc;
-        ra.n_items = (unsigned)owned.size(); ra.item_shift = chain_shift;
-        if (timing) hipEventRecord(ctx->events[0], st);
+        ra.n_items = (unsigned)fr.owned.size(); ra.item_shift = chain_shift;
+        if (fr.timing) hipEventRecord(ctx->events[0], st);
         launch_mc_chain(kind, ctx->lds_scene, dim3(chain_threads / 256), block, lds, st, ra, ctx->ds, stc, mp);
-        if (timing) hipEventRecord(ctx->events[1], st);
+        if (fr.timing) hipEventRecord(ctx->events[1], st);
         rc.stream_mode = kStreamGivenStates;
     }
-    if (timing) hipEventRecord(ctx->events[2], st);
+    if (fr.timing) hipEventRecord(ctx->events[2], st);
     (strat ? launch_pixel_mc_strat : launch_pixel_mc)(kind, ctx->lds_scene, grid, block, lds, st, rc, ctx->ds, stc, mp);
-    if (timing) hipEventRecord(ctx->events[3], st);
-    if (!out_is_device) HIP_OK(hipMemcpyAsync(out_rgb, d_out, (size_t)3 * W * H * sizeof(float), hipMemcpyDeviceToHost, st));
-    std::vector<unsigned long long> partials(n_rows * STAT_COUNT);
-    HIP_OK(hipMemcpyAsync(partials.data(), ctx->d_partials, partials.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipGetLastError());
+    if (fr.timing) hipEventRecord(ctx->events[3], st);
+    if ((rcode = fr.download()) != RL_OK) return rcode;
     if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        unsigned long long totals[STAT_COUNT] = {0};
-        for (size_t r = 0; r < n_rows; r++) for (int k = 0; k < STAT_COUNT; k++) totals[k] += partials[r * STAT_COUNT + k];
-        stats->camera_samples = totals[STAT_SAMPLES]; stats->vertices = totals[STAT_VERTICES]; stats->extension_rays = totals[STAT_EXT_RAYS];
-        stats->shadow_rays = totals[STAT_SHADOW_RAYS]; stats->rng_draws = totals[STAT_DRAWS];
         stats->iterations = 1; stats->kernel_launches = per_sample ? 2 : (two_pass ? 3 : 1);
-        if (timing) {
+        if (fr.timing) {
             float t = 0.0f;
             if (hipEventElapsedTime(&t, ctx->events[2], ctx->events[3]) == hipSuccess) stats->ms_other = t;
             if (two_pass && hipEventElapsedTime(&t, ctx->events[0], ctx->events[1]) == hipSuccess) stats->ms_prepass = t;
             (void)hipGetLastError();
         }
-        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     }
     return RL_OK;
 }
@@ -861,122 +887,71 @@ extern "C" int rl_render_direct(rl_context* ctx, const rl_mc_params* params, con
 // traces spp light paths per slot and splats them into the fixed-point image, k_light_resolve writes the f32 image (light.hip.h).
 extern "C" int rl_render_light(rl_context* ctx, const rl_path_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
                                int out_is_device, void* stream_arg, rl_render_stats* stats) {
-    if (!ctx || !params || !block_seeds || !out_rgb) return RL_ERR_INVALID_ARGUMENT;
-    const uint32_t W = ctx->width, H = ctx->height;
-    const size_t nbx = (W + 15) / 16, nby = (H + 15) / 16;
-    if (n_blocks != nbx * nby) { rl_set_error("n_blocks does not match the image size"); return RL_ERR_INVALID_ARGUMENT; }
-    if (params->spp == 0) { rl_set_error("spp must be > 0"); return RL_ERR_INVALID_ARGUMENT; }
+    int rcode;
+    if ((rcode = check_frame(ctx, params, block_seeds, n_blocks, out_rgb)) != RL_OK) return rcode;
     if (params->strategy < RL_LIGHT_ALL || params->strategy > RL_LIGHT_VOLUME) { rl_set_error("strategy must be RL_LIGHT_ALL, RL_LIGHT_SURFACE or RL_LIGHT_VOLUME"); return RL_ERR_INVALID_ARGUMENT; }
     if (params->stream_mode != RL_STREAM_PER_SAMPLE) { rl_set_error("the light tracer runs on per-sample streams only (stream_mode = RL_STREAM_PER_SAMPLE)"); return RL_ERR_UNSUPPORTED; }
     if (params->numerics != RL_NUMERICS_EXACT) { rl_set_error("the light tracer has no tolerance build (numerics = RL_NUMERICS_EXACT only)"); return RL_ERR_UNSUPPORTED; }
     if (params->shard_count > 1) { rl_set_error("the light tracer renders on one device (shard_count <= 1): every light path may splat anywhere"); return RL_ERR_UNSUPPORTED; }
     if (ctx->ds.env_emitter >= 0) { rl_set_error("the light tracer does not sample environment emitters"); return RL_ERR_UNSUPPORTED; }
     if (ctx->ds.n_emitters == 0) { rl_set_error("the light tracer needs an emitter"); return RL_ERR_NO_EMITTER; }
-    if ((size_t)W * H > 0x7fffff00u) { rl_set_error("image too large"); return RL_ERR_INVALID_ARGUMENT; }
+    if ((size_t)ctx->width * ctx->height > 0x7fffff00u) { rl_set_error("image too large"); return RL_ERR_INVALID_ARGUMENT; }
     HIP_OK(hipSetDevice(ctx->device));
-    hipStream_t st = stream_arg ? (hipStream_t)stream_arg : ctx->stream;
-    auto t_start = std::chrono::steady_clock::now();
-    std::vector<unsigned> owned, item_base;
-    unsigned n_items = 0;
-    for (size_t b = 0; b < n_blocks; b++) {
-        const unsigned bx = (unsigned)(b / nby) * 16u, by = (unsigned)(b % nby) * 16u;
-        owned.push_back((unsigned)b);
-        item_base.push_back(n_items);
-        n_items += std::min(16u, W - bx) * std::min(16u, H - by);
-    }
-    const size_t n_pix = (size_t)W * H;
-    int rcode;
-    if ((rcode = ensure(&ctx->d_owned, &ctx->owned_capacity, owned.size())) != RL_OK) return rcode;
-    if ((rcode = ensure(&ctx->d_item_base, &ctx->item_base_capacity, owned.size())) != RL_OK) return rcode;
-    if ((rcode = ensure(&ctx->d_block_seeds, &ctx->seeds_capacity, n_blocks)) != RL_OK) return rcode;
-    if ((rcode = ensure(&ctx->d_item_seed, &ctx->item_capacity, n_items)) != RL_OK) return rcode;
-    if ((rcode = ensure(&ctx->d_item_pixel, &ctx->item_pixel_capacity, n_items)) != RL_OK) return rcode;
+    RenderFrame fr(ctx, block_seeds, n_blocks, out_rgb, out_is_device, stream_arg, stats, 0, 1);      // every block (shard_index is not read)
+    const size_t n_pix = (size_t)fr.W * fr.H;
+    const unsigned n_items = fr.n_pixels;
+    if ((rcode = fr.alloc_tables()) != RL_OK) return rcode;
+    if ((rcode = ctx->d_item_seed.ensure(n_items)) != RL_OK || (rcode = ctx->d_item_pixel.ensure(n_items)) != RL_OK) return rcode;
     // the splat image: [W*H*3] u64 low words of the sums, then [W*H] u32 inf flags, then [W*H*3] u32 carry words — in the sample-state buffer of
     // reference-order streams, which this call does not use
     const size_t acc_words = (3 * n_pix + (4 * n_pix + 1) / 2 + 3) / 4;     // in units of the buffer's 4 x u64 entries
-    if ((rcode = ensure(&ctx->d_sample_states, &ctx->sample_states_capacity, acc_words * 4)) != RL_OK) return rcode;
-    float* d_out = out_rgb;
-    if (!out_is_device) {
-        if ((rcode = ensure(&ctx->d_out, &ctx->out_capacity, 3 * n_pix)) != RL_OK) return rcode;
-        d_out = ctx->d_out;
-    }
+    if ((rcode = ctx->d_sample_states.ensure(acc_words * 4)) != RL_OK) return rcode;
     // lanes per light-path slot: small frames get several (each tracing every split-th sample of the slot), so that about two rounds of the chip's resident waves run
-    int cus = 256;
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    const size_t want_lanes = (size_t)std::max(cus, 1) * kLightWaves * 4 * 64 * 2;
+    const size_t want_lanes = (size_t)std::max(fr.cus, 1) * kLightWaves * 4 * 64 * 2;
     unsigned split = 1;
     while (split * 2 <= params->spp && (size_t)n_items * split < want_lanes && (size_t)n_items * split * 2 <= 0x7fffff00u) split *= 2;
     const unsigned n_threads = std::max(256u, (unsigned)(((size_t)n_items * split + 255u) / 256u * 256u));
-    const size_t n_rows = n_threads / 256;
-    if ((rcode = ensure(&ctx->d_partials, &ctx->partials_capacity, n_rows * STAT_COUNT)) != RL_OK) return rcode;
+    if ((rcode = fr.alloc_output(n_threads / 256)) != RL_OK) return rcode;
     LightConst lc = ctx->light_cam;
     lc.render_surface = params->strategy != RL_LIGHT_VOLUME;
     lc.render_volume = params->strategy != RL_LIGHT_SURFACE;
-    lc.accum = reinterpret_cast<unsigned long long*>(ctx->d_sample_states);
+    lc.accum = ctx->d_sample_states.get();
     lc.inf_flags = reinterpret_cast<unsigned*>(lc.accum + 3 * n_pix);
     lc.carry = lc.inf_flags + n_pix;
-    HIP_OK(hipMemcpyAsync(ctx->d_owned, owned.data(), owned.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(ctx->d_item_base, item_base.data(), item_base.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(ctx->d_block_seeds, block_seeds, n_blocks * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemsetAsync(ctx->d_sample_states, 0, acc_words * 4 * sizeof(unsigned long long), st));
-    HIP_OK(hipMemsetAsync(ctx->d_partials, 0, n_rows * STAT_COUNT * sizeof(unsigned long long), st));
-    RenderConst rc{};
-    rc.spp = params->spp;
+    if ((rcode = fr.upload(true, false)) != RL_OK) return rcode;
+    HIP_OK(hipMemsetAsync(ctx->d_sample_states.get(), 0, acc_words * 4 * sizeof(unsigned long long), fr.st));
+    if ((rcode = fr.zero_rows()) != RL_OK) return rcode;
+    RenderConst rc = fr.render_const(params->spp, RL_STREAM_PER_SAMPLE, params->seed_variant);
     rc.has_min = params->has_min_depth; rc.min_depth = params->min_depth;
     rc.has_max = params->has_max_depth; rc.max_depth = params->max_depth;
     rc.has_rr = params->has_rr_depth; rc.rr_depth = params->rr_depth;
-    rc.stream_mode = RL_STREAM_PER_SAMPLE; rc.seed_variant = params->seed_variant;
-    rc.inv_spp = 1.0f / (float)params->spp;
-    rc.W = W; rc.H = H; rc.nby = (unsigned)nby;
     rc.n_items = n_items;
     rc.split = split;
-    rc.owned_blocks = ctx->d_owned; rc.block_item_base = ctx->d_item_base; rc.n_owned = (unsigned)owned.size();
-    rc.block_seeds = ctx->d_block_seeds;
-    rc.item_seed = ctx->d_item_seed; rc.item_pixel = ctx->d_item_pixel;
-    rc.out = d_out;
-    rc.counters = ctx->d_counters;
-    rc.partials = ctx->d_partials;
     StackConf stc;
     if ((rcode = stack_conf(ctx, n_threads, &stc)) != RL_OK) return rcode;
     const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
-    const bool timing = stats != nullptr && !ctx->knobs.has(K_NO_EVENTS);
-    while (timing && ctx->events.size() < 4) { hipEvent_t ev; HIP_OK(hipEventCreate(&ev)); ctx->events.push_back(ev); }
-    hipLaunchKernelGGL(k_seed_pixels, dim3(((unsigned)owned.size() + 63) / 64), dim3(64), 0, st, rc);
-    if (timing) hipEventRecord(ctx->events[2], st);
+    if ((rcode = fr.grow_events(4)) != RL_OK) return rcode;
+    const hipStream_t st = fr.st;
+    hipLaunchKernelGGL(k_seed_pixels, dim3(((unsigned)fr.owned.size() + 63) / 64), dim3(64), 0, st, rc);
+    if (fr.timing) hipEventRecord(ctx->events[2], st);
     (ctx->lds_scene ? launch_light_lds : launch_light_stream)(ctx->single_bsdf ? ctx->bsdf_type : -1, ctx->ds.medium.enabled != 0, dim3(n_threads / 256), dim3(256), lds, st, rc, ctx->ds, stc, lc);
-    if (timing) hipEventRecord(ctx->events[3], st);
+    if (fr.timing) hipEventRecord(ctx->events[3], st);
     launch_light_resolve(dim3((unsigned)((n_pix + 255) / 256)), dim3(256), st, rc, lc);
-    if (!out_is_device) HIP_OK(hipMemcpyAsync(out_rgb, d_out, 3 * n_pix * sizeof(float), hipMemcpyDeviceToHost, st));
-    std::vector<unsigned long long> partials(n_rows * STAT_COUNT);
-    HIP_OK(hipMemcpyAsync(partials.data(), ctx->d_partials, partials.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipGetLastError());
+    if ((rcode = fr.download()) != RL_OK) return rcode;
     if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        unsigned long long totals[STAT_COUNT] = {0};
-        for (size_t r = 0; r < n_rows; r++) for (int k = 0; k < STAT_COUNT; k++) totals[k] += partials[r * STAT_COUNT + k];
-        stats->camera_samples = totals[STAT_SAMPLES]; stats->vertices = totals[STAT_VERTICES]; stats->extension_rays = totals[STAT_EXT_RAYS];
-        stats->shadow_rays = totals[STAT_SHADOW_RAYS]; stats->rng_draws = totals[STAT_DRAWS];
-        stats->reserved[0] = totals[STAT_SPLATS]; stats->reserved[1] = totals[STAT_SPLATS_INVALID]; stats->reserved[2] = totals[STAT_SPLATS_SATURATED];
+        stats->reserved[0] = fr.totals[STAT_SPLATS]; stats->reserved[1] = fr.totals[STAT_SPLATS_INVALID]; stats->reserved[2] = fr.totals[STAT_SPLATS_SATURATED];
         stats->iterations = 1; stats->kernel_launches = 3;
-        if (timing) {
+        if (fr.timing) {
             float t = 0.0f;
             if (hipEventElapsedTime(&t, ctx->events[2], ctx->events[3]) == hipSuccess) stats->ms_other = t;
             (void)hipGetLastError();
         }
-        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     }
     return RL_OK;
 }
 
 // ---- batched Acceleration::{trace, visible}
 namespace {
-struct DevBuf {     // frees on every exit path of the batch entry points
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 constexpr size_t kMaxBatch = 0x7fffff00u;   // grid and kernel argument are 32-bit
 }  // namespace
 extern "C" int rl_trace_batch(rl_context* ctx, size_t n, const float* origins, const float* directions, float* t_out, float* u_out,
@@ -985,17 +960,17 @@ extern "C" int rl_trace_batch(rl_context* ctx, size_t n, const float* origins, c
     if (n == 0) return RL_OK;
     if (n > kMaxBatch) { rl_set_error("batch too large"); return RL_ERR_INVALID_ARGUMENT; }
     HIP_OK(hipSetDevice(ctx->device));
-    DevBuf b_o, b_d, b_t, b_u, b_v, b_m, b_tr;
-    HIP_OK(b_o.alloc(3 * n * 4)); HIP_OK(b_d.alloc(3 * n * 4));
-    HIP_OK(b_t.alloc(n * 4)); HIP_OK(b_u.alloc(n * 4)); HIP_OK(b_v.alloc(n * 4));
-    HIP_OK(b_m.alloc(n * 4)); HIP_OK(b_tr.alloc(n * 4));
-    float *d_o = b_o.as<float>(), *d_d = b_d.as<float>(), *d_t = b_t.as<float>(), *d_u = b_u.as<float>(), *d_v = b_v.as<float>();
-    int *d_m = b_m.as<int>(), *d_tr = b_tr.as<int>();
+    HipBuffer<float> b_o, b_d, b_t, b_u, b_v; HipBuffer<int> b_m, b_tr;
+    int rcode;
+    if ((rcode = b_o.ensure(3 * n)) != RL_OK || (rcode = b_d.ensure(3 * n)) != RL_OK || (rcode = b_t.ensure(n)) != RL_OK || (rcode = b_u.ensure(n)) != RL_OK ||
+        (rcode = b_v.ensure(n)) != RL_OK || (rcode = b_m.ensure(n)) != RL_OK || (rcode = b_tr.ensure(n)) != RL_OK) return rcode;
+    float *d_o = b_o.get(), *d_d = b_d.get(), *d_t = b_t.get(), *d_u = b_u.get(), *d_v = b_v.get();
+    int *d_m = b_m.get(), *d_tr = b_tr.get();
     HIP_OK(hipMemcpy(d_o, origins, 3 * n * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_d, directions, 3 * n * 4, hipMemcpyHostToDevice));
     size_t lds = traversal_lds_bytes(ctx, false, 256, false);
     StackConf stc;
-    { int r = stack_conf(ctx, (n + 255) / 256 * 256, &stc); if (r != RL_OK) return r; }
+    if ((rcode = stack_conf(ctx, (n + 255) / 256 * 256, &stc)) != RL_OK) return rcode;
     hipLaunchKernelGGL(k_trace_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), lds, ctx->stream, ctx->ds, stc, (unsigned)n, d_o, d_d, d_t, d_u, d_v, d_m, d_tr);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(ctx->stream));
@@ -1010,14 +985,15 @@ extern "C" int rl_visible_batch(rl_context* ctx, size_t n, const float* p0, cons
     if (n == 0) return RL_OK;
     if (n > kMaxBatch) { rl_set_error("batch too large"); return RL_ERR_INVALID_ARGUMENT; }
     HIP_OK(hipSetDevice(ctx->device));
-    DevBuf b_a, b_b, b_o;
-    HIP_OK(b_a.alloc(3 * n * 4)); HIP_OK(b_b.alloc(3 * n * 4)); HIP_OK(b_o.alloc(n));
-    float *d_a = b_a.as<float>(), *d_b = b_b.as<float>(); unsigned char* d_o = b_o.as<unsigned char>();
+    HipBuffer<float> b_a, b_b; HipBuffer<unsigned char> b_o;
+    int rcode;
+    if ((rcode = b_a.ensure(3 * n)) != RL_OK || (rcode = b_b.ensure(3 * n)) != RL_OK || (rcode = b_o.ensure(n)) != RL_OK) return rcode;
+    float *d_a = b_a.get(), *d_b = b_b.get(); unsigned char* d_o = b_o.get();
     HIP_OK(hipMemcpy(d_a, p0, 3 * n * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_b, p1, 3 * n * 4, hipMemcpyHostToDevice));
     size_t lds = traversal_lds_bytes(ctx, false, 256, false);
     StackConf stc;
-    { int r = stack_conf(ctx, (n + 255) / 256 * 256, &stc); if (r != RL_OK) return r; }
+    if ((rcode = stack_conf(ctx, (n + 255) / 256 * 256, &stc)) != RL_OK) return rcode;
     hipLaunchKernelGGL(k_visible_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), lds, ctx->stream, ctx->ds, stc, (unsigned)n, d_a, d_b, d_o);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(ctx->stream));
@@ -1031,9 +1007,10 @@ extern "C" int rl_debug_numerics(int device, size_t n, const float* a, const flo
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return RL_ERR_NO_DEVICE;
     if (n > kMaxBatch / 16) return RL_ERR_INVALID_ARGUMENT;
     HIP_OK(hipSetDevice(device));
-    DevBuf b_a, b_b, b_out;
-    HIP_OK(b_a.alloc(n * 4)); HIP_OK(b_b.alloc(n * 4)); HIP_OK(b_out.alloc(10 * n * 4));
-    float *d_a = b_a.as<float>(), *d_b = b_b.as<float>(), *d_out = b_out.as<float>();
+    HipBuffer<float> b_a, b_b, b_out;
+    int rcode;
+    if ((rcode = b_a.ensure(n)) != RL_OK || (rcode = b_b.ensure(n)) != RL_OK || (rcode = b_out.ensure(10 * n)) != RL_OK) return rcode;
+    float *d_a = b_a.get(), *d_b = b_b.get(), *d_out = b_out.get();
     HIP_OK(hipMemcpy(d_a, a, n * 4, hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(d_b, b, n * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_numerics_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (unsigned)n, d_a, d_b, d_out, d_out + n, d_out + 2 * n,
                        d_out + 3 * n, d_out + 4 * n, d_out + 5 * n, d_out + 6 * n, d_out + 7 * n, d_out + 8 * n, d_out + 9 * n);
@@ -1048,18 +1025,20 @@ extern "C" int rl_debug_trace_batch_fast(rl_context* ctx, size_t n, const float*
     if (!ctx->ds.nodes4) { rl_set_error("the scene is staged in LDS: no BVH4"); return RL_ERR_UNSUPPORTED; }
     if (n > kMaxBatch) { rl_set_error("batch too large"); return RL_ERR_INVALID_ARGUMENT; }
     HIP_OK(hipSetDevice(ctx->device));
-    DevBuf b_o, b_d, b_t, b_m, b_tr, b_s;
-    HIP_OK(b_o.alloc(3 * n * 4)); HIP_OK(b_d.alloc(3 * n * 4)); HIP_OK(b_t.alloc(n * 4)); HIP_OK(b_m.alloc(n * 4)); HIP_OK(b_tr.alloc(n * 4)); HIP_OK(b_s.alloc(n * 4));
-    HIP_OK(hipMemcpy(b_o.as<float>(), origins, 3 * n * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(b_d.as<float>(), directions, 3 * n * 4, hipMemcpyHostToDevice));
+    HipBuffer<float> b_o, b_d, b_t; HipBuffer<int> b_m, b_tr, b_s;
+    int rcode;
+    if ((rcode = b_o.ensure(3 * n)) != RL_OK || (rcode = b_d.ensure(3 * n)) != RL_OK || (rcode = b_t.ensure(n)) != RL_OK || (rcode = b_m.ensure(n)) != RL_OK ||
+        (rcode = b_tr.ensure(n)) != RL_OK || (rcode = b_s.ensure(n)) != RL_OK) return rcode;
+    HIP_OK(hipMemcpy(b_o.get(), origins, 3 * n * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(b_d.get(), directions, 3 * n * 4, hipMemcpyHostToDevice));
     StackConf stc;
-    { int r = stack_conf(ctx, (n + 255) / 256 * 256, &stc); if (r != RL_OK) return r; }
-    launch_trace_batch_fast(dim3((unsigned)((n + 255) / 256)), dim3(256), traversal_lds_bytes(ctx, false, 256, false), ctx->stream, ctx->ds, stc, (unsigned)n, b_o.as<float>(), b_d.as<float>(),
-                            b_t.as<float>(), b_m.as<int>(), b_tr.as<int>(), b_s.as<int>());
+    if ((rcode = stack_conf(ctx, (n + 255) / 256 * 256, &stc)) != RL_OK) return rcode;
+    launch_trace_batch_fast(dim3((unsigned)((n + 255) / 256)), dim3(256), traversal_lds_bytes(ctx, false, 256, false), ctx->stream, ctx->ds, stc, (unsigned)n, b_o.get(), b_d.get(),
+                            b_t.get(), b_m.get(), b_tr.get(), b_s.get());
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(ctx->stream));
-    HIP_OK(hipMemcpy(t_out, b_t.as<float>(), n * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(mesh_out, b_m.as<int>(), n * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(tri_out, b_tr.as<int>(), n * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(steps_out, b_s.as<int>(), n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(t_out, b_t.get(), n * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(mesh_out, b_m.get(), n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(tri_out, b_tr.get(), n * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(steps_out, b_s.get(), n * 4, hipMemcpyDeviceToHost));
     return RL_OK;
 }
 
@@ -1071,22 +1050,23 @@ extern "C" int rl_debug_trace_batch_two_level(rl_context* ctx, size_t n, const f
     if (n > kMaxBatch) { rl_set_error("batch too large"); return RL_ERR_INVALID_ARGUMENT; }
     HIP_OK(hipSetDevice(ctx->device));
     { const int r2 = ensure_two_level(ctx); if (r2 != RL_OK) return r2; }
-    DevBuf b_o, b_d, b_t, b_u, b_v, b_m, b_tr, b_s;
-    HIP_OK(b_o.alloc(3 * n * 4)); HIP_OK(b_d.alloc(3 * n * 4)); HIP_OK(b_t.alloc(n * 4)); HIP_OK(b_u.alloc(n * 4)); HIP_OK(b_v.alloc(n * 4));
-    HIP_OK(b_m.alloc(n * 4)); HIP_OK(b_tr.alloc(n * 4)); HIP_OK(b_s.alloc(n * 4));
-    HIP_OK(hipMemcpy(b_o.as<float>(), origins, 3 * n * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(b_d.as<float>(), directions, 3 * n * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(b_t.as<float>(), t_inout, n * 4, hipMemcpyHostToDevice));
+    HipBuffer<float> b_o, b_d, b_t, b_u, b_v; HipBuffer<int> b_m, b_tr, b_s;
+    int rcode;
+    if ((rcode = b_o.ensure(3 * n)) != RL_OK || (rcode = b_d.ensure(3 * n)) != RL_OK || (rcode = b_t.ensure(n)) != RL_OK || (rcode = b_u.ensure(n)) != RL_OK ||
+        (rcode = b_v.ensure(n)) != RL_OK || (rcode = b_m.ensure(n)) != RL_OK || (rcode = b_tr.ensure(n)) != RL_OK || (rcode = b_s.ensure(n)) != RL_OK) return rcode;
+    HIP_OK(hipMemcpy(b_o.get(), origins, 3 * n * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(b_d.get(), directions, 3 * n * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(b_t.get(), t_inout, n * 4, hipMemcpyHostToDevice));
     StackConf stc;
-    { int r = stack_conf(ctx, (n + 255) / 256 * 256, &stc); if (r != RL_OK) return r; }
+    if ((rcode = stack_conf(ctx, (n + 255) / 256 * 256, &stc)) != RL_OK) return rcode;
     hipLaunchKernelGGL(k_trace_batch_two_level, dim3((unsigned)((n + 255) / 256)), dim3(256), traversal_lds_bytes(ctx, false, 256, false), ctx->stream, ctx->ds, stc, (unsigned)n,
-                       b_o.as<float>(), b_d.as<float>(), b_t.as<float>(), b_u.as<float>(), b_v.as<float>(), b_m.as<int>(), b_tr.as<int>(), b_s.as<int>(), any_hit);
+                       b_o.get(), b_d.get(), b_t.get(), b_u.get(), b_v.get(), b_m.get(), b_tr.get(), b_s.get(), any_hit);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(ctx->stream));
-    HIP_OK(hipMemcpy(t_inout, b_t.as<float>(), n * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(steps_out, b_s.as<int>(), n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(t_inout, b_t.get(), n * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(steps_out, b_s.get(), n * 4, hipMemcpyDeviceToHost));
     if (!any_hit) {
-        HIP_OK(hipMemcpy(u_out, b_u.as<float>(), n * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(v_out, b_v.as<float>(), n * 4, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(mesh_out, b_m.as<int>(), n * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(tri_out, b_tr.as<int>(), n * 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(u_out, b_u.get(), n * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(v_out, b_v.get(), n * 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(mesh_out, b_m.get(), n * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(tri_out, b_tr.get(), n * 4, hipMemcpyDeviceToHost));
     }
     return RL_OK;
 }
