@@ -360,6 +360,42 @@ typedef enum rl_light_strategy { RL_LIGHT_ALL = 0, RL_LIGHT_SURFACE = 1, RL_LIGH
 int rl_render_light(rl_context* ctx, const rl_path_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
                     int out_is_device, void* stream, rl_render_stats* stats);
 
+/* IntegratorVPL (src/integrators/explicit/vpl.rs, CLI `vpl`): virtual point lights shot from the emitters, then gathered at every camera sample, seed for
+ * seed the reference in its reference-order streams.  IntegratorVPL::compute = rl_vpl_generate with the main sampler, rl_generate_block_seeds with the
+ * sampler it leaves, rl_render_vpl.  option_vpl / option_lt take an rl_vpl_option, as `-v` / `-l` do.
+ *
+ * rl_vpl_generate: the generation loop (vpl.rs:182-210) on one device lane, from `sampler`'s state, which it advances as the reference's main sampler is
+ * advanced.  Light paths are shot while fewer than nb_vpl VPLs are stored, so the set holds at least nb_vpl of them (all of the last path's).  Of
+ * rl_path_params it reads max_depth and rr_depth (min_depth is ignored, as by the reference).  nb_vpl is 1 .. RL_VPL_MAX; at most RL_VPL_MAX_PATHS paths
+ * are shot, and RL_ERR_UNSUPPORTED is returned (no set) when they store fewer than nb_vpl VPLs.  Refused before any kernel runs: max_depth <= 1
+ * (RL_ERR_INVALID_ARGUMENT; the reference panics at vpl.rs:138), option_vpl = RL_VPL_VOLUME without a medium and a directional light with a medium
+ * (RL_ERR_UNSUPPORTED; the reference loops forever or asserts), environment emitters (RL_ERR_UNSUPPORTED), no emitter (RL_ERR_NO_EMITTER).  Counters:
+ * camera_samples = light paths shot, vertices = expanded vertices, extension_rays, rng_draws; ms_prepass = generation kernel time.
+ *
+ * rl_vpl_read: RL_VPL_WORDS u32 per VPL in VPL order (f32 fields as their bits): [0] kind (rl_vpl_kind), [1] mesh (surface), [2] has_uv (surface), [3] 0,
+ * [4..6] position (RL_VPL_EMITTER_INFINITE: the direction d), [7..9] radiance, [10..12] wi in the shading frame (surface) / d_in (volume) / n (emitter
+ * position), [13..14] uv (surface), [15..23] the shading frame's x, y, z axes (surface); unused words are 0.  n_words must be n_vpl * RL_VPL_WORDS.
+ *
+ * rl_render_vpl: the gather (vpl.rs:212-535) with `block_seeds` as for rl_render_path.  Sample (ix, iy, s) of a block draws D numbers (2, 3 when the scene
+ * has a medium) from draw ((ix * bh + iy) * spp + s) * D of the block's stream.  Reads spp, seed_variant, shard_index / shard_count (every shard gets the
+ * whole set: each generates the same one); RL_ERR_UNSUPPORTED for stream_mode other than RL_STREAM_REFERENCE_ORDER, numerics = RL_NUMERICS_FAST and
+ * spp > RL_VPL_MAX_SPP; the set must come from the same context.  One deliberate difference: where a camera ray leaves the scene inside a medium the
+ * pixel gets +0 without a gather (the reference's `l_i *= ..` with l_i = 0, vpl.rs:483, differs only where that gather is not finite).  Counters:
+ * camera_samples = W*H*spp of the shard, extension_rays = camera rays, shadow_rays = connection rays traced (none at smooth gather points, where they add
+ * nothing), rng_draws = D * camera_samples, kernel_launches; ms_raygen = the primary passes, ms_other = the gather passes (spp <= 256); reserved[0] = gather points on
+ * surfaces, reserved[1] = gather points in the medium. */
+typedef enum rl_vpl_option { RL_VPL_ALL = 0, RL_VPL_SURFACE = 1, RL_VPL_VOLUME = 2 } rl_vpl_option;
+typedef enum rl_vpl_kind { RL_VPL_KIND_SURFACE = 0, RL_VPL_KIND_VOLUME = 1, RL_VPL_KIND_EMITTER_POSITION = 2, RL_VPL_KIND_EMITTER_INFINITE = 3 } rl_vpl_kind;
+enum { RL_VPL_WORDS = 24, RL_VPL_MAX = 1 << 20, RL_VPL_MAX_PATHS = 1 << 18, RL_VPL_MAX_SPP = 1 << 22 };
+typedef struct rl_vpl_set rl_vpl_set;       /* opaque: the VPLs of one generation, on the context's device */
+int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, rl_sampler* sampler, rl_vpl_set** out,
+                    rl_render_stats* stats);
+int rl_vpl_info(const rl_vpl_set* set, uint64_t* n_vpl, uint64_t* n_paths);
+int rl_vpl_read(const rl_vpl_set* set, uint32_t* words, size_t n_words);
+void rl_vpl_destroy(rl_vpl_set* set);
+int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_path_params* params, int option_lt, const uint64_t* block_seeds, size_t n_blocks,
+                  float* out_rgb, int out_is_device, void* stream, rl_render_stats* stats);
+
 /* Frames in flight behind one call (the progressive wrappers' passes, avg.rs:5-131 / equal_time.rs:4-66: N independent renders of one scene): frame f — block
  * seeds `block_seeds[f]`, host image `out_rgb[f]` (W*H*3 f32) — renders on `ctxs[f % k]` from host thread f % k, k = min(n_ctx, n_frames); `ctxs` are distinct
  * contexts of the same scene.  Returns when every frame is done; the images (and `stats[f]`, if not NULL) are those of `n_frames` rl_render_path calls one after

@@ -27,6 +27,8 @@ STREAM_REFERENCE_ORDER, STREAM_PER_SAMPLE, STREAM_STRATIFIED = 0, 1, 2      # rl
 PIPELINE_AUTO, PIPELINE_WAVEFRONT, PIPELINE_FUSED = 0, 1, 2
 NUMERICS_EXACT, NUMERICS_FAST = 0, 1
 LIGHT_ALL, LIGHT_SURFACE, LIGHT_VOLUME = 0, 1, 2          # rl_light_strategy: `light-tracing -s all|surface|volume`
+VPL_ALL, VPL_SURFACE, VPL_VOLUME = 0, 1, 2                # rl_vpl_option: `vpl -v / -l all|surface|volume`
+VPL_WORDS = 24                                            # RL_VPL_WORDS: u32 per VPL record (rl_vpl_read)
 RL_ERR_UNSUPPORTED, RL_ERR_NO_EMITTER = -7, -8
 
 # every symbol include/rustlight_amd.h declares (tests check the .so exports all of them)
@@ -36,7 +38,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -106,6 +108,12 @@ def lib():
     L.rl_render_path.argtypes = [vp, C.POINTER(abi.PathParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_render_path_frames.argtypes = [C.POINTER(vp), C.c_size_t, C.POINTER(abi.PathParams), C.POINTER(u64p), C.c_size_t, C.c_size_t, C.POINTER(C.POINTER(C.c_float)), C.POINTER(abi.RenderStats)]
     L.rl_render_light.argtypes = [vp, C.POINTER(abi.PathParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
+    L.rl_vpl_generate.argtypes = [vp, C.POINTER(abi.PathParams), C.c_uint32, C.c_int, C.POINTER(abi.Sampler), C.POINTER(vp), C.POINTER(abi.RenderStats)]
+    L.rl_vpl_info.argtypes = [vp, u64p, u64p]
+    L.rl_vpl_read.argtypes = [vp, u32p, C.c_size_t]
+    L.rl_vpl_destroy.argtypes = [vp]
+    L.rl_vpl_destroy.restype = None
+    L.rl_render_vpl.argtypes = [vp, vp, C.POINTER(abi.PathParams), C.c_int, u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     for fn in (L.rl_render_ao, L.rl_render_direct):
         fn.argtypes = [vp, C.POINTER(abi.McParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_multi_create.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -472,6 +480,29 @@ class Context:
         d["splats"], d["splats_invalid"], d["splats_saturated"] = (int(v) for v in st.reserved[:3])
         return img, d
 
+    def vpl_generate(self, sampler: "IndependentSampler", nb_vpl=128, max_depth=None, rr_depth=0, option_vpl=VPL_ALL):
+        """IntegratorVPL's generation (vpl.rs:182-210) through rl_vpl_generate: (VplSet, stats dict).  `sampler` is advanced as the reference's main sampler is.
+        stats: camera_samples = light paths shot, vertices, extension_rays, rng_draws, ms_prepass = the generation kernel's time."""
+        p = path_params(1, 0, max_depth, rr_depth, stream_mode=STREAM_REFERENCE_ORDER)
+        st = abi.RenderStats()
+        h = C.c_void_p()
+        _check(lib().rl_vpl_generate(self.h, C.byref(p), nb_vpl, option_vpl, C.byref(sampler.s), C.byref(h), C.byref(st)))
+        return VplSet(h, self), st.as_dict()
+
+    def render_vpl(self, vpls: "VplSet", seeds, spp=1, option_lt=VPL_ALL, seed_variant=0, shard_index=0, shard_count=1, stream_mode=STREAM_REFERENCE_ORDER,
+                   numerics=NUMERICS_EXACT):
+        """IntegratorVPL's gather (vpl.rs:212-535) through rl_render_vpl: (image HxWx3 f32, stats dict).  stats: shadow_rays = connection rays traced,
+        gather_surface / gather_volume = reserved[0] / reserved[1], ms_raygen = primary passes, ms_other = gather passes."""
+        p = path_params(spp, 0, None, 0, stream_mode=stream_mode, seed_variant=seed_variant, shard_index=shard_index, shard_count=shard_count, numerics=numerics)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        st = abi.RenderStats()
+        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        _check(lib().rl_render_vpl(self.h, vpls.h, C.byref(p), option_lt, abi.u64ptr(seeds), seeds.shape[0], img.ctypes.data_as(C.c_void_p), 0, None,
+                                   C.byref(st)))
+        d = st.as_dict()
+        d["gather_surface"], d["gather_volume"] = int(st.reserved[0]), int(st.reserved[1])
+        return img, d
+
     def trace(self, origins, directions):
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
@@ -664,6 +695,77 @@ class IntegratorLightTracing:
         w, h = scene.size
         seeds = sampler.block_seeds(w, h)
         img, self.last_stats = self._ctx.render_light(seeds, nb_samples, self.min_depth, self.max_depth, self.rr_depth, self.strategy, sampler.variant)
+        return img
+
+
+class VplSet:
+    """rl_vpl_set: the VPLs of one generation, on the device of the context that made them (kept alive with it)."""
+
+    def __init__(self, h, ctx: Context):
+        self.h, self.ctx = h, ctx
+
+    def info(self):
+        """(VPLs stored, light paths shot)."""
+        n, p = C.c_uint64(), C.c_uint64()
+        _check(lib().rl_vpl_info(self.h, C.byref(n), C.byref(p)))
+        return int(n.value), int(p.value)
+
+    def __len__(self):
+        return self.info()[0]
+
+    def words(self) -> np.ndarray:
+        """The raw records, [n_vpl, VPL_WORDS] u32 (layout: include/rustlight_amd.h, rl_vpl_read)."""
+        n = self.info()[0]
+        w = np.zeros((n, VPL_WORDS), np.uint32)
+        _check(lib().rl_vpl_read(self.h, abi.u32ptr(w), w.size))
+        return w
+
+    def records(self) -> np.ndarray:
+        """The records as a numpy structured array: kind, mesh, has_uv, pos, radiance, dir (wi / d_in / n), uv, frame (3 x 3 rows x, y, z)."""
+        return self.words().view(VPL_RECORD_DTYPE).reshape(-1)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().rl_vpl_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+VPL_RECORD_DTYPE = np.dtype([("kind", "<u4"), ("mesh", "<u4"), ("has_uv", "<u4"), ("pad", "<u4"), ("pos", "<f4", 3), ("radiance", "<f4", 3),
+                             ("dir", "<f4", 3), ("uv", "<f4", 2), ("frame", "<f4", (3, 3))])
+assert VPL_RECORD_DTYPE.itemsize == 4 * VPL_WORDS
+
+
+class IntegratorVPL:
+    """struct IntegratorVPL (src/integrators/explicit/vpl.rs:16-23) + Integrator::compute, seed for seed the reference: the VPLs from the main sampler, the
+    block seeds from the sampler they leave, the gather on reference-order streams.  clamping_factor is not a field: the reference never reads it."""
+
+    def __init__(self, nb_vpl=128, max_depth=None, rr_depth=0, option_vpl=VPL_ALL, option_lt=VPL_ALL, device=0, options=None):
+        self.nb_vpl, self.max_depth, self.rr_depth = nb_vpl, max_depth, rr_depth
+        self.option_vpl, self.option_lt = option_vpl, option_lt
+        self.device = device
+        self.options = dict(options or {})
+        self.last_stats = None
+        self.last_generation_stats = None
+        self._ctx = None
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        if self._ctx is None or self._ctx.scene is not scene:
+            self._ctx = Context(scene, self.device)
+            for k, v in self.options.items():
+                self._ctx.set_option(k, v)
+        vpls, self.last_generation_stats = self._ctx.vpl_generate(sampler, self.nb_vpl, self.max_depth, self.rr_depth, self.option_vpl)
+        try:
+            w, h = scene.size
+            seeds = sampler.block_seeds(w, h)
+            img, self.last_stats = self._ctx.render_vpl(vpls, seeds, nb_samples, self.option_lt, sampler.variant)
+        finally:
+            vpls.close()
         return img
 
 

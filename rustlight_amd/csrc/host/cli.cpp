@@ -6,6 +6,8 @@
 //               | ao [-d DIST|inf] [-n]            (examples/cli.rs:149-154)
 //               | direct [-b NB_BSDF] [-l NB_LIGHT] (examples/cli.rs:155-160)
 //               | light-tracing [-m MAX|inf] [-n MIN] [-r RR|inf] [-s all|surface|volume]   (examples/cli.rs:54-61, 170-174; per-sample streams)
+//               | vpl [-m MAX|inf] [-r RR|inf] [-b CLAMP] [--nb-vpl N] [-l all|surface|volume] [-v all|surface|volume]   (examples/cli.rs:176-184, 707-733;
+//                 -b is accepted and ignored as the reference ignores clamping_factor; -n is refused: the reference declares it twice under `vpl`)
 // Note `-n` / `-m` / `-r` / `-s` mean spp / medium / sampler / scale before the subcommand and
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 #include <chrono>
@@ -45,11 +47,12 @@ int main(int argc, char** argv) {
     uint32_t numerics = RL_NUMERICS_EXACT;
     int frames_in_flight = 1;
     std::vector<std::pair<std::string, std::string>> options;
+    std::string nb_vpl = "128", option_lt = "all", option_vpl = "all";     // vpl (cli.rs:176-184)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
         if (!have_cmd) {
-            if (a == "path" || a == "ao" || a == "direct" || a == "light-tracing") { have_cmd = true; cmd = a; }
+            if (a == "path" || a == "ao" || a == "direct" || a == "light-tracing" || a == "vpl") { have_cmd = true; cmd = a; }
             else if (a == "-n" || a == "--nbsamples") nbsamples = std::strtoull(val().c_str(), nullptr, 10);
             else if (a == "-o" || a == "--output") output = val();
             else if (a == "-r" || a == "--random-number-generator") rng = val();
@@ -79,7 +82,7 @@ int main(int argc, char** argv) {
             else if (a == "-l" || a == "--log") (void)val();   // log file: nothing is logged on this path
             else if (a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
             else if (scene_path.empty()) scene_path = a;
-            else { std::fprintf(stderr, "only the `path`, `ao`, `direct` and `light-tracing` subcommands are provided (got %s)\n", a.c_str()); return 2; }
+            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing` and `vpl` subcommands are provided (got %s)\n", a.c_str()); return 2; }
         } else if (cmd == "ao") {
             if (a == "-d" || a == "--distance") ao_distance = val();
             else if (a == "-n" || a == "--normal-correction") ao_normal_correction = true;
@@ -88,6 +91,15 @@ int main(int argc, char** argv) {
             if (a == "-b" || a == "--nb-bsdf-samples") nb_bsdf = std::strtoull(val().c_str(), nullptr, 10);
             else if (a == "-l" || a == "--nb-light-samples") nb_light = std::strtoull(val().c_str(), nullptr, 10);
             else { std::fprintf(stderr, "unknown direct option %s\n", a.c_str()); return 2; }
+        } else if (cmd == "vpl") {
+            if (a == "-m" || a == "--max-depth") max_depth = val();
+            else if (a == "-r" || a == "--rr-depth") rr_depth = val();
+            else if (a == "-b" || a == "--clamping") (void)val();           // clamping_factor: never read by the reference
+            else if (a == "--nb-vpl") nb_vpl = val();
+            else if (a == "-l" || a == "--option-lt") option_lt = val();
+            else if (a == "-v" || a == "--option-vpl") option_vpl = val();
+            else if (a == "-n") { std::fprintf(stderr, "vpl: -n is ambiguous in the reference (min_depth and nb_vpl share it); use --nb-vpl N\n"); return 2; }
+            else { std::fprintf(stderr, "unknown vpl option %s\n", a.c_str()); return 2; }
         } else if (cmd == "light-tracing") {
             if (a == "-m" || a == "--max-depth") max_depth = val();
             else if (a == "-n" || a == "--min-depth") min_depth = val();
@@ -123,6 +135,30 @@ int main(int argc, char** argv) {
         light.rr_depth = match_infinity(rr_depth);
         light.device = device;
         light.options = options;
+    }
+    // vpl runs on reference-order streams, exact numerics, one device, one pass: what it cannot do is refused here, before a device is opened
+    IntegratorVPL vpl;
+    if (cmd == "vpl") {
+        auto option = [](const std::string& v, rl_vpl_option* out) {
+            if (v == "all") *out = RL_VPL_ALL; else if (v == "surface") *out = RL_VPL_SURFACE; else if (v == "volume") *out = RL_VPL_VOLUME; else return false;
+            return true;
+        };
+        if (rng == "stratified" || rng.rfind("stratified:", 0) == 0) { std::fprintf(stderr, "vpl: -r stratified is not supported (independent[:SEED] only)\n"); return 2; }
+        if (mode_given && mode != RL_STREAM_REFERENCE_ORDER) { std::fprintf(stderr, "vpl: --stream-mode per-sample is not supported (the gather uses reference-order streams)\n"); return 2; }
+        if (numerics == RL_NUMERICS_FAST) { std::fprintf(stderr, "vpl: --numerics fast is not supported\n"); return 2; }
+        if (gpus > 1) { std::fprintf(stderr, "vpl: --gpus > 1 is not supported\n"); return 2; }
+        if (!average.empty() || !equal_time.empty()) { std::fprintf(stderr, "vpl: -a / -e are not supported\n"); return 2; }
+        if (frames_in_flight > 1) { std::fprintf(stderr, "vpl: --frames-in-flight is not supported\n"); return 2; }
+        if (!option(option_lt, &vpl.option_lt)) { std::fprintf(stderr, "invalid vpl -l option: %s (all, surface or volume)\n", option_lt.c_str()); return 2; }
+        if (!option(option_vpl, &vpl.option_vpl)) { std::fprintf(stderr, "invalid vpl -v option: %s (all, surface or volume)\n", option_vpl.c_str()); return 2; }
+        char* end = nullptr;
+        const unsigned long long n = std::strtoull(nb_vpl.c_str(), &end, 10);
+        if (nb_vpl.empty() || *end != '\0' || n == 0 || n > (unsigned long long)RL_VPL_MAX) { std::fprintf(stderr, "invalid --nb-vpl: %s (1 .. %d)\n", nb_vpl.c_str(), (int)RL_VPL_MAX); return 2; }
+        vpl.nb_vpl = (uint32_t)n;
+        vpl.max_depth = match_infinity(max_depth);
+        vpl.rr_depth = match_infinity(rr_depth);
+        vpl.device = device;
+        vpl.options = options;
     }
     // the sampler (cli.rs:876-896): the master sampler that draws the block seeds is IndependentSampler(SEED) for both kinds — OS entropy without a seed, as
     // IndependentSampler::default() / StratifiedSampler's random() are; `stratified:SEED` is this drop-in's reproducible form.  stratified =
@@ -184,7 +220,7 @@ int main(int argc, char** argv) {
         }
         scene->build_emitters(use_ats);      // scene.build_emitters(use_ats) (cli.rs:432)
         IntegratorPathTracing integrator;
-        if (cmd == "light-tracing") strategy = "all";       // (the path integrator below is not used)
+        if (cmd == "light-tracing" || cmd == "vpl") strategy = "all";       // (the path integrator below is not used)
         integrator.min_depth = match_infinity(min_depth);
         integrator.max_depth = match_infinity(max_depth);
         integrator.rr_depth = match_infinity(rr_depth);
@@ -211,6 +247,8 @@ int main(int argc, char** argv) {
             IntegratorDirect di;
             di.device = device; di.stream_mode = mode; di.nb_bsdf_samples = nb_bsdf; di.nb_light_samples = nb_light;
             img = di.compute(sampler, *scene); elapsed_ms = di.last_stats.render_ms;
+        } else if (cmd == "vpl") {
+            img = vpl.compute(sampler, *scene); elapsed_ms = vpl.last_stats.render_ms;
         } else if (cmd == "light-tracing") {
             if (!equal_time.empty()) {
                 IntegratorEqualTime<IntegratorLightTracing> eq{light, std::strtod(equal_time.c_str(), nullptr) * 1000.0};

@@ -285,6 +285,47 @@ struct IntegratorLightTracing {
     }
 };
 
+// struct IntegratorVPL (src/integrators/explicit/vpl.rs:16-23) + Integrator::compute, seed for seed the reference: the VPLs from the main sampler
+// (rl_vpl_generate), the block seeds from the sampler it leaves, the gather on reference-order streams (rl_render_vpl).  clamping_factor is not a
+// field: the reference never reads it.
+struct IntegratorVPL {
+    uint32_t nb_vpl = 128;
+    std::optional<uint32_t> max_depth, rr_depth = 0u;
+    rl_vpl_option option_vpl = RL_VPL_ALL, option_lt = RL_VPL_ALL;
+    int device = 0;
+    std::vector<std::pair<std::string, std::string>> options;
+    rl_render_stats last_stats{}, last_generation_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        rl_context* ctx = nullptr;
+        int rc = rl_context_create(scene.handle, device, &ctx);
+        if (rc != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
+        for (const auto& o : options)
+            if (rl_context_set_option(ctx, o.first.c_str(), o.second.c_str()) != RL_OK) { const std::string e = rl_last_error(); rl_context_destroy(ctx); throw std::runtime_error("--option " + o.first + ": " + e); }
+        BufferCollection img;
+        rl_scene_image_size(scene.handle, &img.width, &img.height);
+        img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
+        rl_path_params p;
+        rl_path_params_default(&p);
+        p.spp = (uint32_t)scene.nb_samples;
+        p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
+        p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
+        p.stream_mode = RL_STREAM_REFERENCE_ORDER;
+        p.seed_variant = sampler.variant;
+        rl_vpl_set* vpls = nullptr;
+        rc = rl_vpl_generate(ctx, &p, nb_vpl, option_vpl, &sampler.rnd, &vpls, &last_generation_stats);
+        if (rc == RL_OK) {
+            std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
+            rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
+            rc = rl_render_vpl(ctx, vpls, &p, option_lt, seeds.data(), seeds.size(), img.primal.data(), 0, nullptr, &last_stats);
+        }
+        const std::string err = rc == RL_OK ? std::string() : std::string(rl_last_error());
+        rl_vpl_destroy(vpls);
+        rl_context_destroy(ctx);
+        if (rc != RL_OK) throw std::runtime_error("vpl: " + err);
+        return img;
+    }
+};
+
 // IntegratorAverage (src/integrators/avg.rs:5-131) and IntegratorEqualTime (src/integrators/equal_time.rs:4-66):
 // host loops around any inner integrator with `compute(IndependentSampler&, Scene&)`.
 template <class T, class = void> struct has_frames_in_flight : std::false_type {};

@@ -22,6 +22,27 @@ struct LightConst {
     unsigned* carry;                    // W*H*3 high 32 bits of the sums: how often the low word wrapped
 };
 
+// IntegratorVPL (vpl.hip.h): the VPL records, the generation's sampler and counters, and the per-sample gather buffers
+static constexpr int kVplGatherWords = 12;       // gather point: [0] item, [1] kind bits, [2] prim, [3] u, [4] v, [5] t, [6..8] ray direction, [9..11] mrec.w
+enum { VPL_GEN_VPLS = 0, VPL_GEN_PATHS = 1, VPL_GEN_VERTICES = 2, VPL_GEN_EXT = 3, VPL_GEN_DRAWS = 4, VPL_GEN_WORDS = 5 };
+enum { STAT_VPL_SURFACE = 5, STAT_VPL_VOLUME = 6 };      // the gather's statistics rows (pathstate.hip.h: STAT_COUNT = 8): gather points on surfaces / in the medium
+struct VplConst {
+    unsigned nb_vpl, cap, max_paths;    // generation: stop once nb_vpl VPLs are stored or max_paths paths were shot; records beyond cap are not written
+    int option_vpl, option_lt;          // rl_vpl_option
+    unsigned* vpl_words;                // generation: [cap][kVplWords]
+    unsigned long long* gen_state;      // [4] the main sampler, read and written back
+    unsigned long long* gen_out;        // [VPL_GEN_WORDS] VPLs stored, paths shot, vertices, extension rays, draws
+    const unsigned* vpls;               // gather: [n_vpl][kVplWords]
+    unsigned n_vpl;
+    float norm_vpl;                     // 1 / paths shot
+    unsigned draws;                     // D: draws per camera sample (2, 3 with a medium)
+    unsigned sample;                    // the sample index of this pass
+    unsigned long long* pix_state;      // [pixel item][4] the pixel's place in its block stream
+    unsigned* gpoints;                  // [pixel item][kVplGatherWords] this pass's live gather points
+    unsigned* n_live;                   // how many
+    float* acc;                         // [pixel item][3] the pixel's sum over the samples so far
+};
+
 // mat: the scene's one BSDF type, or -1 = run-time switch per vertex.  area_only: every emitter is a mesh area light and there is no light
 // tree (the NEE code of the other emitter kinds is compiled out: same results, 84 -> 21 spilled VGPRs on the diffuse Cornell box)
 void launch_fused_lds(int mat, bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc);
@@ -57,6 +78,10 @@ void launch_mc_chain(int kind, bool lds_scene, dim3 grid, dim3 block, size_t lds
 void launch_light_lds(int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const LightConst& lc);
 void launch_light_stream(int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const LightConst& lc);
 void launch_light_resolve(dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const LightConst& lc);
+// IntegratorVPL (vpl.hip.h): which = 0 k_vpl_generate, 1 k_vpl_gather (mat as for launch_light_*), 2 k_vpl_primary; k_vpl_resolve scales the pixel sums into the image
+void launch_vpl_lds(int which, int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VplConst& vc);
+void launch_vpl_stream(int which, int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VplConst& vc);
+void launch_vpl_resolve(dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const VplConst& vc);
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)
 void dump_stage_timers_stream();
 void dump_chain_timers_lds();      // dev-only (-DRL_STAGE_TIMERS): cycle shares of k_stream_chain's stages

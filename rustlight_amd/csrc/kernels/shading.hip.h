@@ -326,7 +326,8 @@ RL_DEV Col bsdf_eval(const DeviceScene& sc, const Material& mat, bool huv, V2 uv
 }
 
 // BSDF::sample -> Option<SampledDirection>
-template <int MAT>
+// RADIANCE: Transport::Radiance (IntegratorVPL's light paths): glass transmission carries eta^2 (glass.rs:99-107); the default is Transport::Importance
+template <int MAT, bool RADIANCE = false>
 RL_DEV bool bsdf_sample(const DeviceScene& sc, const Material& mat, bool huv, V2 uv, V3 wi, V2 s, BsdfSample* out) {
     const int type = MAT >= 0 ? MAT : mat.type;
     if (type == BSDF_DIFFUSE) {
@@ -384,7 +385,7 @@ RL_DEV bool bsdf_sample(const DeviceScene& sc, const Material& mat, bool huv, V2
             out->weight = tex_color(sc, mat.specular, huv, uv);
             out->d = reflect_z(wi);
         } else {
-            float factor = 1.0f;
+            float factor = RADIANCE ? (cos_t < 0.0f ? mat.glass_inv_eta : mat.glass_eta) : 1.0f;
             float scale = cos_t < 0.0f ? -mat.glass_inv_eta : -mat.glass_eta;
             out->weight = tex_color(sc, mat.transmittance, huv, uv) * factor * factor;
             out->d = mk3(scale * wi.x, scale * wi.y, cos_t);

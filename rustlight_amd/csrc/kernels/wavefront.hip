@@ -34,6 +34,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -268,6 +269,7 @@ struct rl_context {
     int bsdf_type = 0;
     bool lds_scene = false;
     bool area_lights_only = false;   // every emitter is a mesh area light, no light tree: the fused kernel's NEE code is specialised (same results)
+    bool has_directional = false;    // a directional light among the emitters (vpl refuses it with a medium)
     size_t scene_lds_bytes = 0;
     size_t lds_limit = 64 * 1024;     // dynamic LDS a workgroup may ask for on this device (hipDeviceAttributeMaxSharedMemoryPerBlock)
     // render scratch (grown on demand)
@@ -438,6 +440,7 @@ extern "C" int rl_context_create(const rl_scene* scene, int device, rl_context**
         ds.medium = scene->medium;
         ctx->area_lights_only = scene->ats_root < 0 && !ctx->knobs.has(K_GENERIC_LIGHTS);
         for (const EmitterRecord& e : scene->emitters) if (e.kind != EMITTER_MESH) ctx->area_lights_only = false;
+        for (const EmitterRecord& e : scene->emitters) if (e.kind == EMITTER_DIRECTIONAL) ctx->has_directional = true;
         for (const HostMesh& hm : scene->meshes) if (hm.is_light && hm.emission_type != RL_EMISSION_COLOR) ctx->area_lights_only = false;      // uv-dependent emission (`-x hvs-light | texture-light`): the generic instantiation
         ctx->single_bsdf = true;
         ctx->bsdf_type = flat.materials.empty() ? 0 : flat.materials[0].type;
@@ -944,6 +947,169 @@ extern "C" int rl_render_light(rl_context* ctx, const rl_path_params* params, co
         if (fr.timing) {
             float t = 0.0f;
             if (hipEventElapsedTime(&t, ctx->events[2], ctx->events[3]) == hipSuccess) stats->ms_other = t;
+            (void)hipGetLastError();
+        }
+    }
+    return RL_OK;
+}
+
+// ---- IntegratorVPL::compute (vpl.rs:182-535): rl_vpl_generate shoots the VPLs on one lane (k_vpl_generate), rl_render_vpl gathers them per sample index
+// (k_vpl_primary, k_vpl_gather) and scales the pixel sums (k_vpl_resolve); see vpl.hip.h
+static constexpr unsigned kVplTimedPasses = 256;
+struct rl_vpl_set {
+    const rl_context* ctx;            // the context that made it (compared, never dereferenced: the context may be destroyed first)
+    int device;
+    HipBuffer<unsigned> words;        // [n_vpl][RL_VPL_WORDS]
+    uint64_t n_vpl = 0, n_paths = 0;
+};
+static int check_vpl_scene(const rl_context* ctx) {
+    if (ctx->ds.env_emitter >= 0) { rl_set_error("vpl does not sample environment emitters"); return RL_ERR_UNSUPPORTED; }
+    if (ctx->ds.n_emitters == 0) { rl_set_error("vpl needs an emitter"); return RL_ERR_NO_EMITTER; }
+    return RL_OK;
+}
+extern "C" int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, rl_sampler* sampler, rl_vpl_set** out,
+                               rl_render_stats* stats) {
+    if (!ctx || !params || !sampler || !out) return RL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (option_vpl < RL_VPL_ALL || option_vpl > RL_VPL_VOLUME) { rl_set_error("option_vpl must be RL_VPL_ALL, RL_VPL_SURFACE or RL_VPL_VOLUME"); return RL_ERR_INVALID_ARGUMENT; }
+    if (nb_vpl == 0 || nb_vpl > (uint32_t)RL_VPL_MAX) { rl_set_error("nb_vpl must be 1 .. RL_VPL_MAX"); return RL_ERR_INVALID_ARGUMENT; }
+    if (params->has_max_depth && params->max_depth <= 1) { rl_set_error("vpl needs max_depth >= 2 (the light vertex has no edge otherwise, vpl.rs:138)"); return RL_ERR_INVALID_ARGUMENT; }
+    int rcode;
+    if ((rcode = check_vpl_scene(ctx)) != RL_OK) return rcode;
+    const bool medium = ctx->ds.medium.enabled != 0;
+    if (option_vpl == RL_VPL_VOLUME && !medium) { rl_set_error("vpl -v volume needs a medium (the reference never stores a VPL)"); return RL_ERR_UNSUPPORTED; }
+    if (medium) {
+        if (ctx->has_directional) { rl_set_error("vpl does not take a directional light with a medium (vpl.rs:324, 418)"); return RL_ERR_UNSUPPORTED; }
+    }
+    HIP_OK(hipSetDevice(ctx->device));
+    auto set = std::make_unique<rl_vpl_set>();
+    set->ctx = ctx; set->device = ctx->device;
+    const unsigned cap = nb_vpl + kDepthCap + 1u;        // the last path adds at most one VPL per vertex
+    HipBuffer<unsigned long long> d_gen;                   // [4] sampler, then [VPL_GEN_WORDS] counters
+    if ((rcode = set->words.ensure((size_t)cap * RL_VPL_WORDS)) != RL_OK || (rcode = d_gen.ensure(4 + VPL_GEN_WORDS)) != RL_OK) return rcode;
+    const hipStream_t st = ctx->stream;
+    unsigned long long h_gen[4 + VPL_GEN_WORDS] = {sampler->s[0], sampler->s[1], sampler->s[2], sampler->s[3]};
+    HIP_OK(hipMemcpyAsync(d_gen.get(), h_gen, sizeof(h_gen), hipMemcpyHostToDevice, st));
+    RenderConst rc{};
+    rc.has_max = params->has_max_depth; rc.max_depth = params->max_depth;
+    rc.has_rr = params->has_rr_depth; rc.rr_depth = params->rr_depth;
+    VplConst vc{};
+    vc.nb_vpl = nb_vpl; vc.cap = cap; vc.max_paths = RL_VPL_MAX_PATHS;
+    vc.option_vpl = option_vpl;
+    vc.vpl_words = set->words.get();
+    vc.gen_state = d_gen.get(); vc.gen_out = d_gen.get() + 4;
+    StackConf stc;
+    if ((rcode = stack_conf(ctx, 256, &stc)) != RL_OK) return rcode;
+    const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timing = stats != nullptr;
+    if (timing) { HIP_OK(hipEventCreate(&ev[0])); HIP_OK(hipEventCreate(&ev[1])); HIP_OK(hipEventRecord(ev[0], st)); }
+    const auto t0 = std::chrono::steady_clock::now();
+    (ctx->lds_scene ? launch_vpl_lds : launch_vpl_stream)(0, ctx->single_bsdf ? ctx->bsdf_type : -1, medium, dim3(1), dim3(256), lds, st, rc, ctx->ds, stc, vc);
+    if (timing) HIP_OK(hipEventRecord(ev[1], st));
+    HIP_OK(hipMemcpyAsync(h_gen, d_gen.get(), sizeof(h_gen), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    float ms = 0.0f;
+    if (timing) { (void)hipEventElapsedTime(&ms, ev[0], ev[1]); (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); (void)hipGetLastError(); }
+    const unsigned long long* g = h_gen + 4;
+    if (g[VPL_GEN_VPLS] < nb_vpl) { rl_set_error("vpl: fewer than nb_vpl VPLs stored within RL_VPL_MAX_PATHS light paths"); return RL_ERR_UNSUPPORTED; }
+    sampler->s[0] = h_gen[0]; sampler->s[1] = h_gen[1]; sampler->s[2] = h_gen[2]; sampler->s[3] = h_gen[3];
+    set->n_vpl = g[VPL_GEN_VPLS]; set->n_paths = g[VPL_GEN_PATHS];
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->camera_samples = g[VPL_GEN_PATHS]; stats->vertices = g[VPL_GEN_VERTICES]; stats->extension_rays = g[VPL_GEN_EXT]; stats->rng_draws = g[VPL_GEN_DRAWS];
+        stats->iterations = 1; stats->kernel_launches = 1; stats->ms_prepass = ms;
+        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    *out = set.release();
+    return RL_OK;
+}
+extern "C" int rl_vpl_info(const rl_vpl_set* set, uint64_t* n_vpl, uint64_t* n_paths) {
+    if (!set) return RL_ERR_INVALID_ARGUMENT;
+    if (n_vpl) *n_vpl = set->n_vpl;
+    if (n_paths) *n_paths = set->n_paths;
+    return RL_OK;
+}
+extern "C" int rl_vpl_read(const rl_vpl_set* set, uint32_t* words, size_t n_words) {
+    if (!set || !words || n_words != set->n_vpl * RL_VPL_WORDS) return RL_ERR_INVALID_ARGUMENT;
+    HIP_OK(hipSetDevice(set->device));
+    HIP_OK(hipMemcpy(words, set->words.get(), n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RL_OK;
+}
+extern "C" void rl_vpl_destroy(rl_vpl_set* set) {
+    if (!set) return;
+    (void)hipSetDevice(set->device);
+    delete set;
+}
+extern "C" int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_path_params* params, int option_lt, const uint64_t* block_seeds, size_t n_blocks,
+                             float* out_rgb, int out_is_device, void* stream_arg, rl_render_stats* stats) {
+    int rcode;
+    if (!set) return RL_ERR_INVALID_ARGUMENT;
+    if ((rcode = check_frame(ctx, params, block_seeds, n_blocks, out_rgb)) != RL_OK) return rcode;
+    if (set->ctx != ctx) { rl_set_error("the VPL set belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
+    if (option_lt < RL_VPL_ALL || option_lt > RL_VPL_VOLUME) { rl_set_error("option_lt must be RL_VPL_ALL, RL_VPL_SURFACE or RL_VPL_VOLUME"); return RL_ERR_INVALID_ARGUMENT; }
+    if (params->shard_index >= (params->shard_count ? params->shard_count : 1)) return RL_ERR_INVALID_ARGUMENT;
+    if (params->stream_mode != RL_STREAM_REFERENCE_ORDER) { rl_set_error("vpl runs on reference-order streams only (stream_mode = RL_STREAM_REFERENCE_ORDER)"); return RL_ERR_UNSUPPORTED; }
+    if (params->numerics != RL_NUMERICS_EXACT) { rl_set_error("vpl has no tolerance build (numerics = RL_NUMERICS_EXACT only)"); return RL_ERR_UNSUPPORTED; }
+    if (params->spp > (uint32_t)RL_VPL_MAX_SPP) { rl_set_error("vpl takes at most RL_VPL_MAX_SPP spp (a block's stream is entered with 32-bit jumps)"); return RL_ERR_UNSUPPORTED; }
+    if ((rcode = check_vpl_scene(ctx)) != RL_OK) return rcode;
+    HIP_OK(hipSetDevice(ctx->device));
+    RenderFrame fr(ctx, block_seeds, n_blocks, out_rgb, out_is_device, stream_arg, stats, params->shard_index, params->shard_count);
+    const bool medium = ctx->ds.medium.enabled != 0;
+    const unsigned n_items = fr.n_pixels;
+    const unsigned n_owned = (unsigned)fr.owned.size();
+    const unsigned gather_threads = std::max(256u, (n_items + 255u) / 256u * 256u);
+    const unsigned n_threads = std::max(gather_threads, n_owned * 256u);
+    if ((rcode = fr.alloc_tables()) != RL_OK) return rcode;
+    // per pixel item: the stream state [4 u64], the gather point [kVplGatherWords u32], the sum [3 f32]; then the live-point counter
+    const size_t state_words = (size_t)n_items * 4, gp_u64 = ((size_t)n_items * kVplGatherWords + 1) / 2, acc_u64 = ((size_t)n_items * 3 + 1) / 2;
+    if ((rcode = ctx->d_sample_states.ensure(state_words + gp_u64 + acc_u64 + 1)) != RL_OK) return rcode;
+    if ((rcode = fr.alloc_output(std::max(n_threads / 256, 1u))) != RL_OK) return rcode;
+    if ((rcode = fr.upload(true, true)) != RL_OK || (rcode = fr.zero_rows()) != RL_OK) return rcode;
+    RenderConst rc = fr.render_const(params->spp, RL_STREAM_REFERENCE_ORDER, params->seed_variant);
+    rc.n_items = n_items;
+    VplConst vc{};
+    vc.option_lt = option_lt;
+    vc.vpls = set->words.get(); vc.n_vpl = (unsigned)set->n_vpl;
+    vc.norm_vpl = 1.0f / (float)set->n_paths;               // norm_vpl = 1.0 / nb_path_shot as f32 (vpl.rs:213)
+    vc.draws = medium ? 3u : 2u;
+    unsigned long long* base = ctx->d_sample_states.get();
+    vc.pix_state = base;
+    vc.gpoints = reinterpret_cast<unsigned*>(base + state_words);
+    vc.acc = reinterpret_cast<float*>(base + state_words + gp_u64);
+    vc.n_live = reinterpret_cast<unsigned*>(base + state_words + gp_u64 + acc_u64);
+    StackConf stc;
+    if ((rcode = stack_conf(ctx, n_threads, &stc)) != RL_OK) return rcode;
+    const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
+    const hipStream_t st = fr.st;
+    const int mat = ctx->single_bsdf ? ctx->bsdf_type : -1;
+    auto launch = ctx->lds_scene ? launch_vpl_lds : launch_vpl_stream;
+    const bool timing = fr.timing && params->spp <= kVplTimedPasses;      // per-pass events (beyond that many passes the kernel times are not taken)
+    if (timing && (rcode = fr.grow_events(2 * (size_t)params->spp + 1)) != RL_OK) return rcode;
+    for (unsigned s = 0; s < params->spp && n_owned > 0; s++) {
+        vc.sample = s;
+        HIP_OK(hipMemsetAsync(vc.n_live, 0, sizeof(unsigned), st));
+        if (timing) hipEventRecord(ctx->events[2 * s], st);
+        launch(2, mat, medium, dim3(n_owned), dim3(256), lds, st, rc, ctx->ds, stc, vc);
+        if (timing) hipEventRecord(ctx->events[2 * s + 1], st);
+        launch(1, mat, medium, dim3(gather_threads / 256), dim3(256), lds, st, rc, ctx->ds, stc, vc);
+    }
+    if (timing) hipEventRecord(ctx->events[2 * (size_t)params->spp], st);
+    if (n_owned > 0) launch_vpl_resolve(dim3(n_owned), dim3(256), st, rc, vc);
+    if ((rcode = fr.download()) != RL_OK) return rcode;
+    if (stats) {
+        stats->reserved[0] = fr.totals[STAT_VPL_SURFACE]; stats->reserved[1] = fr.totals[STAT_VPL_VOLUME];
+        stats->iterations = params->spp; stats->kernel_launches = n_owned > 0 ? 2ull * params->spp + 1 : 0;
+        if (timing && n_owned > 0) {
+            double raygen = 0.0, gather = 0.0;
+            for (unsigned s = 0; s < params->spp; s++) {
+                float t = 0.0f;
+                if (hipEventElapsedTime(&t, ctx->events[2 * s], ctx->events[2 * s + 1]) == hipSuccess) raygen += t;
+                hipEvent_t end = s + 1 < params->spp ? ctx->events[2 * (s + 1)] : ctx->events[2 * (size_t)params->spp];
+                if (hipEventElapsedTime(&t, ctx->events[2 * s + 1], end) == hipSuccess) gather += t;
+            }
+            stats->ms_raygen = raygen; stats->ms_other = gather;
             (void)hipGetLastError();
         }
     }
