@@ -89,6 +89,17 @@ int orc_render_path(const orc_scene* sc, const orc_path_params* pp, const uint64
  * out_count (optional, W*H): the splats each pixel took. */
 int orc_render_light(const orc_scene* sc, const orc_path_params* pp, const uint64_t* block_seeds, size_t n_blocks,
                      float* out_rgb, double* out_f64, uint32_t* out_count, int n_threads, orc_stats* stats, orc_light_stats* light_stats);
+/* IntegratorVPL (rl_vpl_generate / rl_render_vpl).  Generation: light paths drawn from the main sampler `state` (4 words, advanced in place) until
+ * nb_vpl records are stored; of pp only has_max_depth / max_depth / has_rr_depth / rr_depth are read.  words takes the records (RL_VPL_WORDS each, at
+ * most cap), counts = [VPLs, paths, vertices, extension rays, draws].  Returns the number of VPLs, or -1 when cap records do not hold them or
+ * RL_VPL_MAX_PATHS paths store fewer than nb_vpl.  The counters have out-parameters of their own: orc_stats keeps its layout. */
+long orc_vpl_generate(const orc_scene* sc, const orc_path_params* pp, uint32_t nb_vpl, int option_vpl, uint64_t* state, uint32_t* words, size_t cap,
+                      uint64_t* counts);
+/* The gather (serial) over the blocks b % shard_count == shard_index (others stay 0); literal_miss = 1: the reference's own form for a camera ray
+ * that leaves the scene inside a medium.  counts = [camera samples, extension rays, shadow rays, draws, gather points on surfaces, in the medium]. */
+int orc_render_vpl(const orc_scene* sc, const uint32_t* words, uint64_t n_vpl, uint64_t n_paths, int option_lt, const uint64_t* block_seeds,
+                   size_t n_blocks, uint32_t spp, int seed_variant, uint32_t shard_index, uint32_t shard_count, int literal_miss, float* out_rgb,
+                   uint64_t* counts);
 /* RL_STREAM_STRATIFIED's sampler, the contract of rl_debug_stratified_draws */
 int orc_stratified_draws(size_t n_pixels, const uint64_t* pixel_seeds, uint32_t spp, int seed_variant, size_t n_calls, const int32_t* pattern, float* out);
 #ifdef __cplusplus

@@ -2,13 +2,12 @@
 from src/integrators/explicit/light.rs): image bits and every counter both sides report, over scenes that reach each instantiation of k_light_fused,
 the depth and strategy options, ragged and split-1 frame sizes, lane splits, LDS-staged and streamed scenes and both seed variants.  The edges of
 the fixed-point splat image — invalid, saturated, overflowing and dim splats — are held to the oracle's f64 sums as well.  One process, no child."""
-import os
-
 import numpy as np
 import pytest
 
 from oracle import orc
 from rustlight_amd import api, scenes
+from tests.scene_helpers import context as _context, glass_and_mirror as _glass_and_mirror, single_bsdf as _single_bsdf, with_back_triangle as _with_back_triangle
 
 pytestmark = pytest.mark.gpu
 
@@ -17,19 +16,6 @@ KEYS = ("camera_samples", "vertices", "extension_rays", "shadow_rays", "rng_draw
 
 def _seeds(sd, k, variant=0):
     return api.IndependentSampler(300 + k, variant).block_seeds(sd.width, sd.height)
-
-
-def _context(sd, streaming):
-    """streaming: the BVH streamed from L2 / HBM instead of staged in LDS (RL_FORCE_STREAMING is read when the context is created)."""
-    old = os.environ.pop("RL_FORCE_STREAMING", None)
-    if streaming:
-        os.environ["RL_FORCE_STREAMING"] = "1"
-    try:
-        return api.Context(api.Scene(sd), 0)
-    finally:
-        os.environ.pop("RL_FORCE_STREAMING", None)
-        if old is not None:
-            os.environ["RL_FORCE_STREAMING"] = old
 
 
 def _exact(sd, ctx=None, seed=0, want_f64=False, streaming=False, **kw):
@@ -48,28 +34,6 @@ def _exact(sd, ctx=None, seed=0, want_f64=False, streaming=False, **kw):
 
 def _exercised(img, st, counter="splats"):
     assert img.any() and st["splats"] > 0 and st[counter] > 0, (counter, st)
-
-
-def _with_back_triangle(sd):
-    # as test_cbox_medium: a triangle behind the camera stretches the root box over the camera, so that medium vertices can reach it
-    back = scenes.MeshData("Back", np.asarray([[0.0, 1.0, 8.0], [0.01, 1.0, 8.0], [0.0, 1.01, 8.0]], dtype=np.float32), np.asarray([[0, 1, 2]], dtype=np.uint32),
-                           None, None, scenes.matte((0.5, 0.5, 0.5)))
-    sd.meshes.insert(0, back)
-    return sd
-
-
-def _single_bsdf(w, h, bsdf):
-    sd = scenes.cbox(w, h)
-    for m in sd.meshes:
-        m.bsdf = bsdf
-    return sd
-
-
-def _glass_and_mirror(w, h):
-    sd = scenes.cbox(w, h)
-    sd.meshes[5].bsdf = scenes.Bsdf(type=scenes.GLASS)                                                   # the short box
-    sd.meshes[6].bsdf = scenes.Bsdf(type=scenes.METAL, specular=scenes.const_color((1, 1, 1)), distribution=scenes.MF_NONE)   # the tall box
-    return sd
 
 
 def _scene(name, w=24, h=24):

@@ -1,17 +1,16 @@
-"""IntegratorVPL (rl_vpl_generate / rl_render_vpl, kernels/vpl.hip.h) held bit for bit to the CPU restatement tests/vpl_ref.cpp: the VPL records, the
-path count and the advanced sampler, then the image and every counter both sides report, over scenes that reach each instantiation (BSDF types, the
-medium, point / directional lights, uv emission), every -l x -v combination with a medium, LDS-staged and streamed BVHs, a ragged frame, spp 1 and 5,
-both seed variants and two shards.  The refused inputs return their codes.  One process, no child."""
+"""IntegratorVPL (rl_vpl_generate / rl_render_vpl, kernels/vpl.hip.h) held bit for bit to the CPU oracle's restatement (oracle/rl_oracle.cpp:
+orc_vpl_generate, orc_render_vpl, written from src/integrators/explicit/vpl.rs): the VPL records, the path count and the advanced sampler, then the
+image and every counter both sides report, over scenes that reach each instantiation (BSDF types, the medium, point / directional lights, uv
+emission), every -l x -v combination with a medium, LDS-staged and streamed BVHs, a ragged frame, spp 1 and 5, both seed variants and two shards.
+The refused inputs return their codes.  One process, no child."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
+from oracle import orc
 from rustlight_amd import api, scenes
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import vpl_ref  # noqa: E402
+from tests.scene_helpers import context as _context, glass_and_mirror as _glass_and_mirror, single_bsdf as _single_bsdf, with_back_triangle as _with_back_triangle
 
 pytestmark = pytest.mark.gpu
 
@@ -20,23 +19,10 @@ GEN_KEYS = ("camera_samples", "vertices", "extension_rays", "rng_draws")
 KEYS = ("camera_samples", "extension_rays", "shadow_rays", "rng_draws", "gather_surface", "gather_volume")
 
 
-def _context(sd, streaming=False):
-    """streaming: the BVH streamed from L2 / HBM instead of staged in LDS (RL_FORCE_STREAMING is read when the context is created)."""
-    old = os.environ.pop("RL_FORCE_STREAMING", None)
-    if streaming:
-        os.environ["RL_FORCE_STREAMING"] = "1"
-    try:
-        return api.Context(api.Scene(sd), 0)
-    finally:
-        os.environ.pop("RL_FORCE_STREAMING", None)
-        if old is not None:
-            os.environ["RL_FORCE_STREAMING"] = old
-
-
 def _exact(sd, seed=0, nb_vpl=32, spp=1, max_depth=None, rr_depth=0, option_vpl=api.VPL_ALL, option_lt=api.VPL_ALL, seed_variant=0, streaming=False, ctx=None):
     """IntegratorVPL::compute on the GPU and in the restatement, step by step.  Returns (image, gather stats, generation stats)."""
     ctx = ctx or _context(sd, streaming)
-    ref = vpl_ref.compute(sd, seed, nb_vpl, spp, max_depth, rr_depth, option_vpl, option_lt, seed_variant)
+    ref = orc.vpl_compute(sd, seed, nb_vpl, spp, max_depth, rr_depth, option_vpl, option_lt, seed_variant)
     sampler = api.IndependentSampler(seed, seed_variant)
     vpls, gst = ctx.vpl_generate(sampler, nb_vpl, max_depth, rr_depth, option_vpl)
     np.testing.assert_array_equal(vpls.words(), ref["records"])
@@ -55,21 +41,6 @@ def _exact(sd, seed=0, nb_vpl=32, spp=1, max_depth=None, rr_depth=0, option_vpl=
     return img, st, gst
 
 
-def _with_back_triangle(sd):
-    # a triangle behind the camera stretches the root box over it, so that medium vertices can see the camera side (as test_gpu_light_exact.py)
-    back = scenes.MeshData("Back", np.asarray([[0.0, 1.0, 8.0], [0.01, 1.0, 8.0], [0.0, 1.01, 8.0]], dtype=np.float32), np.asarray([[0, 1, 2]], dtype=np.uint32),
-                           None, None, scenes.matte((0.5, 0.5, 0.5)))
-    sd.meshes.insert(0, back)
-    return sd
-
-
-def _single_bsdf(w, h, bsdf):
-    sd = scenes.cbox(w, h)
-    for m in sd.meshes:
-        m.bsdf = bsdf
-    return sd
-
-
 def _scene(name, w=24, h=24):
     if name == "cbox": return scenes.cbox(w, h)
     if name == "medium": return _with_back_triangle(scenes.cbox_medium(w, h, 0.5, g=0.6))
@@ -80,11 +51,7 @@ def _scene(name, w=24, h=24):
         sd = scenes.cbox(w, h)
         sd.bitmaps.append((4, 4, np.linspace(0.1, 2.0, 48, dtype=np.float32).reshape(4, 4, 3)))
         return scenes.override_light_emission(sd, "texture", bitmap_id=0)
-    if name == "glass_and_mirror":          # several BSDF types: the run-time switch; glass transmission carries eta^2 into the RR
-        sd = scenes.cbox(w, h)
-        sd.meshes[5].bsdf = scenes.Bsdf(type=scenes.GLASS)
-        sd.meshes[6].bsdf = scenes.Bsdf(type=scenes.METAL, specular=scenes.const_color((1, 1, 1)), distribution=scenes.MF_NONE)
-        return sd
+    if name == "glass_and_mirror": return _glass_and_mirror(w, h)          # several BSDF types: the run-time switch; glass transmission carries eta^2 into the RR
     if name == "glass": return _single_bsdf(w, h, scenes.Bsdf(type=scenes.GLASS))
     if name == "phong": return _single_bsdf(w, h, scenes.living_room_materials()[1])
     if name == "rough_metal": return _single_bsdf(w, h, scenes.Bsdf(type=scenes.METAL, specular=scenes.const_color((0.9, 0.8, 0.7)), distribution=scenes.MF_GGX, alpha_u=0.3, alpha_v=0.3))
@@ -184,7 +151,7 @@ def test_integrator_compute_and_records(built):
     sd = scenes.cbox(24, 16)
     integ = api.IntegratorVPL(nb_vpl=40)
     img = integ.compute(api.IndependentSampler(9), api.Scene(sd), 2)
-    ref = vpl_ref.compute(sd, 9, 40, 2)
+    ref = orc.vpl_compute(sd, 9, 40, 2)
     np.testing.assert_array_equal(img, ref["image"])
     ctx = _context(sd)
     vpls, _ = ctx.vpl_generate(api.IndependentSampler(9), 40)

@@ -6,6 +6,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import scenes
+from tests.scene_helpers import with_back_triangle as _with_back_triangle
 
 R = 8           # independent seeds per estimate
 
@@ -28,13 +29,6 @@ def test_furnace_closed_form():
     se = means.std(ddof=1) / np.sqrt(R)
     assert 0 < se < 0.02
     assert abs(means.mean() - 2.0) < 5.0 * se, (means.mean(), se)
-
-
-def _with_back_triangle(sd):
-    back = scenes.MeshData("Back", np.asarray([[0.0, 1.0, 8.0], [0.01, 1.0, 8.0], [0.0, 1.01, 8.0]], dtype=np.float32), np.asarray([[0, 1, 2]], dtype=np.uint32),
-                           None, None, scenes.matte((0.5, 0.5, 0.5)))
-    sd.meshes.insert(0, back)
-    return sd
 
 
 @pytest.mark.parametrize("which", ["cbox", "medium_hg"])

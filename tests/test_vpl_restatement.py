@@ -1,17 +1,16 @@
 """IntegratorVPL without a GPU: the header's rl_vpl_option / record constants against Python, the new entry points among the library's exports, and the
-CPU restatement tests/vpl_ref.cpp — against the oracle's path tracer in distribution, and on the reference's quirks."""
+CPU oracle's restatement (oracle/rl_oracle.cpp: orc_vpl_generate, orc_render_vpl) — against a pinned fixture bit for bit, against the oracle's path
+tracer in distribution, and on the reference's quirks."""
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
+from oracle import orc
 from rustlight_amd import api, scenes
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import vpl_ref  # noqa: E402
+from tests.golden import make_vpl_restatement as fixture
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rustlight_amd.h")
 NEW = ("rl_vpl_generate", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl")
@@ -31,9 +30,9 @@ def test_header_enums_match_python():
     h = _header_values(["RL_VPL_ALL", "RL_VPL_SURFACE", "RL_VPL_VOLUME", "RL_VPL_WORDS", "RL_VPL_MAX_PATHS", "RL_VPL_KIND_SURFACE", "RL_VPL_KIND_VOLUME",
                         "RL_VPL_KIND_EMITTER_POSITION", "RL_VPL_KIND_EMITTER_INFINITE"])
     assert (h["RL_VPL_ALL"], h["RL_VPL_SURFACE"], h["RL_VPL_VOLUME"]) == (api.VPL_ALL, api.VPL_SURFACE, api.VPL_VOLUME)
-    assert (api.VPL_ALL, api.VPL_SURFACE, api.VPL_VOLUME) == (vpl_ref.VPL_ALL, vpl_ref.VPL_SURFACE, vpl_ref.VPL_VOLUME)
-    assert h["RL_VPL_WORDS"] == api.VPL_WORDS == vpl_ref.VPL_WORDS and api.VPL_RECORD_DTYPE.itemsize == 4 * h["RL_VPL_WORDS"]
-    assert h["RL_VPL_MAX_PATHS"] == vpl_ref.VPL_MAX_PATHS
+    assert (api.VPL_ALL, api.VPL_SURFACE, api.VPL_VOLUME) == (orc.VPL_ALL, orc.VPL_SURFACE, orc.VPL_VOLUME)
+    assert h["RL_VPL_WORDS"] == api.VPL_WORDS == orc.VPL_WORDS and api.VPL_RECORD_DTYPE.itemsize == 4 * h["RL_VPL_WORDS"]
+    assert h["RL_VPL_MAX_PATHS"] == orc.VPL_MAX_PATHS
     assert [h[k] for k in ("RL_VPL_KIND_SURFACE", "RL_VPL_KIND_VOLUME", "RL_VPL_KIND_EMITTER_POSITION", "RL_VPL_KIND_EMITTER_INFINITE")] == [0, 1, 2, 3]
 
 
@@ -45,9 +44,23 @@ def test_new_symbols_are_declared_and_exported(built):
         getattr(lib, name)
 
 
+def test_oracle_reproduces_the_pinned_fixture():
+    """tests/golden/vpl_restatement.npz (made by tests/golden/make_vpl_restatement.py): records, path counts, sampler states, images and the ten
+    counters of five small cases, every array bit for bit."""
+    want = np.load(fixture.OUT)
+    got = fixture.arrays(orc.vpl_compute)
+    assert sorted(got) == sorted(want.files) and len(got) == 5 * len(fixture.CASES)
+    for k in sorted(got):
+        a, b = np.asarray(got[k]), want[k]
+        assert a.dtype == b.dtype and a.shape == b.shape, k
+        assert a.tobytes() == b.tobytes(), k
+    kinds = set(np.concatenate([want[n + "_records"][:, 0] for n in fixture.CASES]).tolist())
+    assert kinds == {0, 1, 2, 3} and all(want[n + "_image"].any() for n in fixture.CASES)
+
+
 @pytest.fixture(scope="module")
 def box():
-    return vpl_ref.compute(scenes.cbox(24, 24), seed=1, nb_vpl=64, spp=2)
+    return orc.vpl_compute(scenes.cbox(24, 24), seed=1, nb_vpl=64, spp=2)
 
 
 def test_generation_keeps_the_last_path(box):
@@ -60,11 +73,11 @@ def test_generation_keeps_the_last_path(box):
 
 def test_surface_option_stores_no_volume_vpl():
     sd = scenes.cbox_medium(16, 12, 0.5, g=0.6)
-    sc = vpl_ref.Scene(sd)
+    sc = orc.Scene(sd)
     st = np.array([1, 2, 3, 4], np.uint64)
-    rec_all, _, _, _ = sc.generate(st, 48, option_vpl=vpl_ref.VPL_ALL)
-    rec_surf, _, _, _ = sc.generate(st, 48, option_vpl=vpl_ref.VPL_SURFACE)
-    rec_vol, _, _, _ = sc.generate(st, 48, option_vpl=vpl_ref.VPL_VOLUME)
+    rec_all, _, _, _ = sc.vpl_generate(st, 48, option_vpl=orc.VPL_ALL)
+    rec_surf, _, _, _ = sc.vpl_generate(st, 48, option_vpl=orc.VPL_SURFACE)
+    rec_vol, _, _, _ = sc.vpl_generate(st, 48, option_vpl=orc.VPL_VOLUME)
     assert (rec_all[:, 0] == 1).any()
     assert not (rec_surf[:, 0] == 1).any() and rec_surf.shape[0] >= 48
     assert (rec_vol[:, 0] == 1).all() and rec_vol.shape[0] >= 48
@@ -72,20 +85,20 @@ def test_surface_option_stores_no_volume_vpl():
 
 def test_surface_lt_option_without_medium_is_black(box):
     """Quirk 3: without a medium the option_lt test is inverted (vpl.rs:527): `-l surface` gathers nothing, not even self emission."""
-    r = vpl_ref.compute(scenes.cbox(24, 24), seed=1, nb_vpl=64, spp=2, option_lt=vpl_ref.VPL_SURFACE)
+    r = orc.vpl_compute(scenes.cbox(24, 24), seed=1, nb_vpl=64, spp=2, option_lt=orc.VPL_SURFACE)
     assert not r["image"].any() and r["stats"]["shadow_rays"] == 0
-    r = vpl_ref.compute(scenes.cbox(24, 24), seed=1, nb_vpl=64, spp=2, option_lt=vpl_ref.VPL_VOLUME)
+    r = orc.vpl_compute(scenes.cbox(24, 24), seed=1, nb_vpl=64, spp=2, option_lt=orc.VPL_VOLUME)
     np.testing.assert_array_equal(r["image"], box["image"])
 
 
 def test_point_light_emitter_vpls_add_nothing():
     """Quirk 1: a point light's n is 0, so its emitter VPLs weigh n.dot(-d).max(0) = 0; the image is the same without them."""
     sd = scenes.cbox_other_lights(16, 16, point=True, directional=False, environment=False, keep_area_light=False)
-    r = vpl_ref.compute(sd, seed=2, nb_vpl=48)
+    r = orc.vpl_compute(sd, seed=2, nb_vpl=48)
     rec = r["records"]
     assert (rec[:, 0] == 2).sum() == r["n_paths"] and (rec[:, 0] == 0).any()
-    sc = vpl_ref.Scene(sd)
-    img, st = sc.render(rec[rec[:, 0] != 2], r["n_paths"], r["seeds"])
+    sc = orc.Scene(sd)
+    img, st = sc.render_vpl(rec[rec[:, 0] != 2], r["n_paths"], r["seeds"])
     np.testing.assert_array_equal(img, r["image"])
     assert img.any() and st["shadow_rays"] < r["stats"]["shadow_rays"]
 
@@ -94,19 +107,28 @@ def test_port_miss_rule_equals_the_literal_reference_form():
     """The one deliberate difference: a camera ray that leaves the box inside the medium gives +0 without a gather, where the reference computes
     `l_i *= gather * w` with l_i = 0 (vpl.rs:483).  On a small box with a medium both give the same image."""
     sd = scenes.cbox_medium(24, 16, 0.5, g=0.6)
-    ours = vpl_ref.compute(sd, seed=4, nb_vpl=32, spp=2)
-    lit = vpl_ref.compute(sd, seed=4, nb_vpl=32, spp=2, literal_miss=True)
+    ours = orc.vpl_compute(sd, seed=4, nb_vpl=32, spp=2)
+    lit = orc.vpl_compute(sd, seed=4, nb_vpl=32, spp=2, literal_miss=True)
     np.testing.assert_array_equal(ours["image"], lit["image"])
     assert lit["stats"]["gather_volume"] > ours["stats"]["gather_volume"] and ours["image"].any()
+
+
+def test_environment_emitters_are_refused():
+    """vpl refuses environment emitters: the checker fails loudly on one rather than give an image."""
+    sd = scenes.cbox_other_lights(8, 8, point=False, directional=False, environment=True, keep_area_light=True)
+    assert sd.environment is not None or sd.environment_map is not None
+    with pytest.raises(AssertionError):
+        orc.vpl_compute(sd, seed=0, nb_vpl=8)
+    with pytest.raises(AssertionError):
+        orc.Scene(sd).render_vpl(np.zeros((1, orc.VPL_WORDS), np.uint32), 1, orc.block_seeds(0, 8, 8))
 
 
 def test_vpl_agrees_with_the_path_tracer_in_the_mean():
     """Diffuse box, no medium, unlimited depth: the per-channel whole-image mean of VPL against the oracle's path tracer.  Calibration (32 x 32,
     1024 VPLs, 1 spp, against path at 64 spp): the relative error of the mean over seeds 0-5 spans -9.7 % .. +10.9 % per channel (the unclamped
     VPL estimate is heavy-tailed: most seeds land 5-9 % low, some high); seed 0 gives -5.8 / -6.6 / -6.5 %.  The bound is 15 %."""
-    from oracle import orc
     sd = scenes.cbox(32, 32)
     path, _ = orc.Scene(sd).render(master_seed=0, spp=64, stream_mode=1, eval_order=1)
     ref = path.reshape(-1, 3).mean(axis=0)
-    v = vpl_ref.compute(sd, seed=0, nb_vpl=1024, spp=1)["image"].reshape(-1, 3).mean(axis=0)
+    v = orc.vpl_compute(sd, seed=0, nb_vpl=1024, spp=1)["image"].reshape(-1, 3).mean(axis=0)
     assert np.all(np.abs(v / ref - 1.0) < 0.15), (v, ref)
