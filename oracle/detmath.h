@@ -12,7 +12,12 @@
 // operations (rustlight_amd/csrc/kernels/detmath.hip.h), so oracle and GPU agree bit-for-bit.
 // Each result is the correctly rounded f32 value except when the exact value lies within
 // ~1e-15 (relative) of a rounding boundary; tests/test_oracle_math.py measures the distance to
-// glibc's sinf/cosf/expf/logf/powf (<= 1 ulp, >99.9 % identical).
+// glibc's sinf/cosf/expf/logf/powf (<= 1 ulp, >99.9 % identical) and, over the input sets of
+// tests/math_sweep.py, to the f64 value rounded to f32 (<= 1 ulp, NaN / inf / signed zeros in place).
+// Measured over all 2^32 inputs: expf, logf, acosf, asinf hold that everywhere.
+// sinf / cosf hold it for |x| <= X = 2^23 = 8388608: the two-term pi/2 reduction below runs out there
+// (first result more than 1 ulp off: cos(8388654)).  Beyond X the two functions are defined by this
+// restatement only — the device copy must still equal it bit for bit, nothing is claimed about accuracy.
 //
 // Compile with -ffp-contract=off (no FMA contraction) — the Makefile does.
 #pragma once
@@ -76,6 +81,7 @@ static inline float sinf_det(float x) {
 #endif
 
     if (!(x - x == 0.0f)) return x - x;  // NaN / inf -> NaN
+    if (x == 0.0f) return x;             // sin(-0) = -0 (f32::sin): k_sin(-0) = -0 + (-0 * S1...) = +0 would lose the sign
     double s, c; sincos_d((double)x, &s, &c); return (float)s;
 }
 static inline float cosf_det(float x) {
@@ -92,6 +98,7 @@ static inline void sincosf_det(float x, float* s, float* c) {
 #endif
 
     if (!(x - x == 0.0f)) { *s = *c = x - x; return; }
+    if (x == 0.0f) { *s = x; *c = 1.0f; return; }   // the sign of a zero argument survives in the sine
     double sd, cd; sincos_d((double)x, &sd, &cd); *s = (float)sd; *c = (float)cd;
 }
 
@@ -181,6 +188,9 @@ static inline float logf_det(float x) {
     return (float)log_d((double)x);
 }
 // powf for the cases rustlight produces (x >= 0; see phong.rs:27-30,81-83,107-110).
+// Deliberate deviations from f32::powf, stated by tests/test_oracle_math.py: x < 0 gives NaN for EVERY y != 0 (Rust: a real number for integer y) and
+// x = -0 is treated as +0 (Rust: pow(-0, 3) = -0, pow(-0, -1) = -inf).  No caller reaches either: phong.rs raises a random number of [0, 1) (lines 27-30) or a
+// cosine it has tested to be > 0 (lines 80-83, 107-110).
 static inline float powf_det(float x, float y) {
 #ifdef ORC_TIMING_BUILD
     return std::pow(x, y);
@@ -228,6 +238,8 @@ static inline double atan_d(double x) {
     if (inv) r = 1.57079632679489655800 - r;
     return neg ? -r : r;
 }
+// Deliberate deviation, stated by tests/test_oracle_math.py: atan2f_det(+-inf, +-inf) is NaN (inf / inf) where IEEE 754 has +-pi/4, +-3pi/4.  The one caller,
+// to_spherical_coordinates (emitter.rs:318-326), passes two components of a normalised direction: never reached.
 static inline float atan2f_det(float y, float x) {
 #ifdef ORC_TIMING_BUILD
     return std::atan2(y, x);

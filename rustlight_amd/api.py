@@ -130,6 +130,7 @@ def lib():
     L.rl_build_info.restype = C.c_char_p
     # test hooks
     L.rl_debug_numerics.argtypes = [C.c_int, C.c_size_t, f32p, f32p, f32p]
+    L.rl_debug_math_sweep.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, f32p, C.c_size_t, C.c_int, f32p]
     L.rl_debug_bvh.argtypes = [vp, u64p, u64p, f32p, u64p, u64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rl_debug_bvh_sizes.argtypes = [vp, u64p, u64p, u32p, C.POINTER(C.c_int)]
     L.rl_debug_camera_ray.argtypes = [vp, C.c_float, C.c_float, f32p, f32p]
@@ -931,4 +932,25 @@ def numerics_probe(a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:
     b = np.ascontiguousarray(b, np.float32)
     out = np.zeros((10, a.shape[0]), np.float32)
     _check(lib().rl_debug_numerics(device, a.shape[0], abi.fptr(a), abi.fptr(b), abi.fptr(out)))
+    return out
+
+
+# rl_math_fn / rl_math_where (csrc/kernels/wavefront.h); codes 0 ... 7 are orc_math_batch's
+MATH_FN = {"sinf": 0, "cosf": 1, "expf": 2, "logf": 3, "powf": 4, "acosf": 5, "atan2f": 6, "asinf": 7, "sqrt_rn": 8, "div_rn": 9, "mul_add": 10}
+MATH_ON_DEVICE, MATH_ON_HOST = 0, 1
+MATH_HOST_FNS = ("sinf", "cosf", "acosf", "atan2f", "asinf")      # what detmath_shared.h holds: the host arm knows nothing else
+
+
+def math_sweep(fn: str, first_bits: int, stride: int, n: int, b=None, swap: bool = False, period: int = 0, where: int = MATH_ON_DEVICE, device: int = 0) -> np.ndarray:
+    """Test hook (rl_debug_math_sweep): out[i] = fn(g_i, b_i), or fn(b_i, g_i) with swap, where g_i is the f32 whose bits are first_bits + (i mod period) * stride
+    (mod 2^32; period 0 = no wrap) and b is None (unary), one number or an array of n.  where = MATH_ON_HOST runs the host compiler's copy of
+    detmath_shared.h (MATH_HOST_FNS) and touches no GPU."""
+    out = np.empty(n, np.float32)
+    if b is None:
+        bp, nb = None, 0
+    else:
+        b = np.ascontiguousarray(np.atleast_1d(b), np.float32)
+        assert b.shape in ((1,), (n,)), (b.shape, n)
+        bp, nb = abi.fptr(b), b.shape[0]
+    _check(lib().rl_debug_math_sweep(device, where, MATH_FN[fn], first_bits & 0xffffffff, stride & 0xffffffff, period, n, bp, nb, int(swap), abi.fptr(out)))
     return out

@@ -30,6 +30,8 @@ RL_HD double k_cos(double r) {
     p = C4 + z * p; p = C3 + z * p; p = C2 + z * p; p = C1 + z * p;
     return (1.0 - 0.5 * z) + (z * z) * p;
 }
+// within 1 ulp of the f64 value for |x| <= 2^23 (measured over every f32); beyond that the two-term reduction runs out and the result is
+// whatever this text gives — equal to the oracle's, bit for bit, but no longer a sine
 RL_HD void sincos_d(double x, double* s, double* c) {
     const double INV_PIO2 = 6.36619772367581382433e-01, PIO2_HI = 1.57079632673412561417e+00, PIO2_LO = 6.07710050650619224932e-11;
     double kd = __builtin_floor(x * INV_PIO2 + 0.5);
@@ -42,6 +44,7 @@ RL_HD void sincos_d(double x, double* s, double* c) {
 }
 RL_HD void sincosf_det(float x, float* s, float* c) {
     if (!(x - x == 0.0f)) { *s = *c = x - x; return; }
+    if (x == 0.0f) { *s = x; *c = 1.0f; return; }   // sin(-0) = -0 (f32::sin): k_sin(-0) = -0 + (-0 * S1...) = +0 would lose the sign
     double sd, cd;
     sincos_d((double)x, &sd, &cd);
     *s = (float)sd; *c = (float)cd;
@@ -76,6 +79,7 @@ RL_HD double sqrt_d(double a) {
     s = 0.5 * (s + a / s);
     return s;
 }
+// (+-inf, +-inf) gives NaN, not IEEE's +-pi/4, +-3pi/4, as in oracle/detmath.h: the arguments are components of a normalised direction
 RL_HD float atan2f_det(float y, float x) {
     if (x != x || y != y) return x + y;
     const double PI = 3.14159265358979311600;

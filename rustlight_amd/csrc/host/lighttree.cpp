@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "../detmath_shared.h"
+#include "../kernels/wavefront.h"     // rl_math_fn
 #include "scene.h"
 
 namespace rl {
@@ -222,6 +223,26 @@ int build_light_tree(rl_scene* scene, std::string* err) {
         scene->ats_leaf_of[scene->ats_emitter_base[p.emitter] + (uint32_t)p.prim] = (uint32_t)i;   // query_to_nodes
     }
     for (const Proxy& p : lights) { scene->ats_light_emitter.push_back(p.emitter); scene->ats_light_prim.push_back(p.prim); }
+    return RL_OK;
+}
+
+// test hook (rl_debug_math_sweep, where = RL_MATH_ON_HOST): this translation unit's instantiation of detmath_shared.h — the one the tree above is built with
+int host_math_sweep(int fn, uint32_t first_bits, uint32_t stride, uint32_t period, size_t n, const float* b, size_t n_b, int swap, float* out) {
+    if (fn != RL_MATH_SINF && fn != RL_MATH_COSF && fn != RL_MATH_ACOSF && fn != RL_MATH_ATAN2F && fn != RL_MATH_ASINF) return RL_ERR_UNSUPPORTED;      // what the shared header holds
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t bits = first_bits + (uint32_t)(period ? i % period : i) * stride;
+        float g;
+        std::memcpy(&g, &bits, 4);
+        const float c = n_b == 0 ? 0.0f : (n_b == 1 ? b[0] : b[i]);
+        const float x = swap ? c : g, y = swap ? g : c;
+        switch (fn) {
+            case RL_MATH_SINF: out[i] = dm::sinf_det(x); break;
+            case RL_MATH_COSF: out[i] = dm::cosf_det(x); break;
+            case RL_MATH_ACOSF: out[i] = dm::acosf_det(x); break;
+            case RL_MATH_ATAN2F: out[i] = dm::atan2f_det(x, y); break;
+            default: out[i] = dm::asinf_det(x); break;      // RL_MATH_ASINF
+        }
+    }
     return RL_OK;
 }
 

@@ -118,6 +118,7 @@ struct FlatScene {
 void flatten_scene(const rl_scene& scene, FlatScene* out);
 
 int build_light_tree(rl_scene* scene, std::string* err);   // lighttree.cpp
+int host_math_sweep(int fn, uint32_t first_bits, uint32_t stride, uint32_t period, size_t n, const float* b, size_t n_b, int swap, float* out);   // lighttree.cpp: test hook
 int read_pfm(const char* path, uint32_t* w, uint32_t* h, std::vector<float>* rgb);   // Bitmap::read_pfm
 int load_pbrt(const char* path, bool use_shading_normals, rl_scene** out, std::string* err);
 

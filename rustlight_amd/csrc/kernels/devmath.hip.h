@@ -155,6 +155,7 @@ RL_DEV float logf_det(float x) {
     if (x - x != 0.0f) return x;
     return (float)log_d((double)x);
 }
+// x < 0 gives NaN for every y != 0 and x = -0 counts as +0, as in oracle/detmath.h: the Phong lobe raises numbers of (0, 1] only
 RL_DEV float powf_det(float x, float y) {
     if (y == 0.0f) return 1.0f;
     if (x == 1.0f) return 1.0f;

@@ -11,6 +11,14 @@ void rl_set_error(const std::string& s);
 extern "C" {
 // runs div/sqrt/mul-add and the deterministic transcendentals on the device: out8 = 8 arrays of n
 int rl_debug_numerics(int device, size_t n, const float* a, const float* b, float* out8);
+// one function of the numerics contract (fn: rl_math_fn) over an arithmetic progression of f32 bit patterns: out[i] = f(g_i, c_i), or f(c_i, g_i) when swap != 0,
+// with g_i = the float whose bits are first_bits + (period ? i % period : i) * stride (mod 2^32; made where the function runs, nothing is uploaded for it) and
+// c_i = b[i] (n_b == n), b[0] (n_b == 1) or 0 (n_b == 0: unary functions).  where = RL_MATH_ON_DEVICE: the kernels' own dm::*_det / div_rn / sqrt_rn on `device`;
+// RL_MATH_ON_HOST: the host compiler's instantiation of detmath_shared.h in lighttree.cpp (sin, cos, acos, asin, atan2; RL_ERR_UNSUPPORTED for the rest), no GPU touched
+enum rl_math_fn { RL_MATH_SINF = 0, RL_MATH_COSF = 1, RL_MATH_EXPF = 2, RL_MATH_LOGF = 3, RL_MATH_POWF = 4, RL_MATH_ACOSF = 5, RL_MATH_ATAN2F = 6, RL_MATH_ASINF = 7,
+                  RL_MATH_SQRT_RN = 8, RL_MATH_DIV_RN = 9, RL_MATH_MUL_ADD = 10 /* a * b + a, uncontracted */, RL_MATH_COUNT = 11 };   // 0 ... 7 = orc_math_batch's codes
+enum rl_math_where { RL_MATH_ON_DEVICE = 0, RL_MATH_ON_HOST = 1 };
+int rl_debug_math_sweep(int device, int where, int fn, uint32_t first_bits, uint32_t stride, uint32_t period, size_t n, const float* b, size_t n_b, int swap, float* out);
 // closest hits of a batch of rays through the tolerance build's traversal of a streaming scene (quantised BVH4, numerics = fast); steps = node trips per ray.
 // RL_ERR_UNSUPPORTED for scenes staged in LDS (they have no BVH4).
 int rl_debug_trace_batch_fast(rl_context* ctx, size_t n, const float* origins, const float* directions, float* t_out, int32_t* mesh_out, int32_t* tri_out, int32_t* steps_out);

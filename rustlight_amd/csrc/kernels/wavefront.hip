@@ -248,6 +248,31 @@ __global__ void k_numerics_probe(unsigned n, const float* a, const float* b, flo
     out_atan2[i] = dm::atan2f_det(a[i], b[i]);
 }
 
+// rl_debug_math_sweep: ONE function of the numerics contract per launch, its swept argument made from bit patterns (nothing is uploaded for it) —
+// the functions are the ones the kernels call (dm::*_det, div_rn, sqrt_rn of this exact build); there is no second text of them here
+__global__ void k_math_sweep(int fn, int swap, unsigned first_bits, unsigned stride, unsigned period, unsigned n, const float* b, float b_const, float* out) {
+    unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float g = __uint_as_float(first_bits + (period ? i % period : i) * stride);
+    const float c = b ? b[i] : b_const;
+    const float x = swap ? c : g, y = swap ? g : c;
+    float r;
+    switch (fn) {
+        case RL_MATH_SINF: r = dm::sinf_det(x); break;
+        case RL_MATH_COSF: r = dm::cosf_det(x); break;
+        case RL_MATH_EXPF: r = dm::expf_det(x); break;
+        case RL_MATH_LOGF: r = dm::logf_det(x); break;
+        case RL_MATH_POWF: r = dm::powf_det(x, y); break;
+        case RL_MATH_ACOSF: r = dm::acosf_det(x); break;
+        case RL_MATH_ATAN2F: r = dm::atan2f_det(x, y); break;
+        case RL_MATH_ASINF: r = dm::asinf_det(x); break;
+        case RL_MATH_SQRT_RN: r = sqrt_rn(x); break;
+        case RL_MATH_DIV_RN: r = div_rn(x, y); break;
+        default: r = x * y + x; break;      // RL_MATH_MUL_ADD: two roundings (k_numerics_probe's out_mad)
+    }
+    out[i] = r;
+}
+
 }  // namespace rl
 
 // ==========================================================================================
@@ -1183,6 +1208,28 @@ extern "C" int rl_debug_numerics(int device, size_t n, const float* a, const flo
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(out8, d_out, 10 * n * 4, hipMemcpyDeviceToHost));
+    return RL_OK;
+}
+
+extern "C" int rl_debug_math_sweep(int device, int where, int fn, uint32_t first_bits, uint32_t stride, uint32_t period, size_t n, const float* b, size_t n_b,
+                                   int swap, float* out) {
+    if (fn < 0 || fn >= RL_MATH_COUNT || !out || n == 0 || (n_b != 0 && !b) || (n_b != 0 && n_b != 1 && n_b != n)) return RL_ERR_INVALID_ARGUMENT;
+    if (n > kMaxBatch) { rl_set_error("batch too large"); return RL_ERR_INVALID_ARGUMENT; }
+    if (where == RL_MATH_ON_HOST) return host_math_sweep(fn, first_bits, stride, period, n, b, n_b, swap, out);     // no HIP call on this arm
+    if (where != RL_MATH_ON_DEVICE) return RL_ERR_INVALID_ARGUMENT;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return RL_ERR_NO_DEVICE;
+    HIP_OK(hipSetDevice(device));
+    HipBuffer<float> b_b, b_out;
+    int rcode;
+    if ((rcode = b_out.ensure(n)) != RL_OK || (n_b == n && n > 1 && (rcode = b_b.ensure(n)) != RL_OK)) return rcode;
+    const float* d_b = nullptr;
+    if (n_b == n && n > 1) { HIP_OK(hipMemcpy(b_b.get(), b, n * 4, hipMemcpyHostToDevice)); d_b = b_b.get(); }
+    hipLaunchKernelGGL(k_math_sweep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, fn, swap, (unsigned)first_bits, (unsigned)stride, (unsigned)period, (unsigned)n,
+                       d_b, n_b ? b[0] : 0.0f, b_out.get());
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out, b_out.get(), n * 4, hipMemcpyDeviceToHost));
     return RL_OK;
 }
 

@@ -84,6 +84,34 @@ def test_error_codes(built):
         api.Scene.load_pbrt("/nonexistent.pbrt")
 
 
+def test_math_sweep_hook_is_exported_and_its_host_arm_needs_no_gpu(built):
+    """rl_debug_math_sweep (csrc/kernels/wavefront.h): the swept argument is made from bit patterns where the function runs; where = host evaluates the host
+    compiler's copy of detmath_shared.h and makes no HIP call; what that header does not hold is refused there, and a bad argument anywhere."""
+    import torch
+
+    assert hasattr(ctypes.CDLL(api.LIB_PATH), "rl_debug_math_sweep")
+    one = 0x3f800000
+    got = api.math_sweep("acosf", one - 2, 1, 4, where=api.MATH_ON_HOST)                           # 1 - 2 ulp, 1 - 1 ulp, 1, 1 + 1 ulp
+    assert got[2] == 0.0 and got[0] > got[1] > 0.0 and np.isnan(got[3])
+    y = np.array([0.0, -0.0, 1.0, -1.0], np.float32)
+    np.testing.assert_array_equal(api.math_sweep("atan2f", one, 0, 4, y, swap=True, where=api.MATH_ON_HOST),      # atan2(y_i, 1)
+                                  np.arctan2(y.astype(np.float64), 1.0).astype(np.float32))
+    np.testing.assert_array_equal(api.math_sweep("atan2f", 0, one, 4, 1.0, period=2, where=api.MATH_ON_HOST).view(np.uint32),      # atan2(0, 1), atan2(1, 1), again
+                                  np.array([0.0, np.pi / 4, 0.0, np.pi / 4], np.float32).view(np.uint32))
+    for fn in ("expf", "logf", "powf", "sqrt_rn", "div_rn", "mul_add"):
+        with pytest.raises(api.RustlightError) as e:
+            api.math_sweep(fn, 0, 1, 4, 1.0, where=api.MATH_ON_HOST)
+        assert e.value.args[0].startswith(f"rustlight_amd error {api.RL_ERR_UNSUPPORTED}")
+    L, out = api.lib(), np.zeros(4, np.float32)
+    assert L.rl_debug_math_sweep(0, api.MATH_ON_HOST, 11, 0, 1, 0, 4, None, 0, 0, api.abi.fptr(out)) == -1      # no such function
+    assert L.rl_debug_math_sweep(0, 2, 0, 0, 1, 0, 4, None, 0, 0, api.abi.fptr(out)) == -1                       # no such place
+    assert L.rl_debug_math_sweep(0, api.MATH_ON_HOST, 6, 0, 1, 0, 4, api.abi.fptr(out), 3, 0, api.abi.fptr(out)) == -1   # b: 0, 1 or n values
+    assert L.rl_debug_math_sweep(0, api.MATH_ON_HOST, 0, 0, 1, 0, 0, None, 0, 0, api.abi.fptr(out)) == -1
+    if not torch.cuda.is_available():
+        with pytest.raises(api.NoDeviceError):
+            api.math_sweep("sinf", 0, 1, 4)
+
+
 @pytest.mark.parametrize("maker", [lambda: scenes.cbox(96, 64), lambda: scenes.living_room(64, 64, n_spheres=12, tess=8), scenes.single_triangle])
 def test_host_bvh_and_camera_equal_oracle(built, maker):
     sd = maker()
