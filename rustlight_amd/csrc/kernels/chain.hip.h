@@ -43,6 +43,7 @@ template <int MAT, bool MEDIUM, bool LDS_SCENE, int NUM>
 __global__ void __launch_bounds__(256, LDS_SCENE ? RL_CHAIN_WAVES : RL_CHAIN_WAVES_STREAMING) k_stream_chain(RenderConst rc_arg, DeviceScene sc_arg, StackConf stc) {
     const DeviceScene& sc0 = sc_arg;
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
+    // (open_scene of stages.hip.h, written out: called as a function it gives this kernel other instructions, and the published numbers are this kernel's)
     SceneRecs recs;
     float4* after_scene = smem;
     if (LDS_SCENE) {
@@ -213,21 +214,11 @@ static void dump_chain_timers_impl() {
 #endif
 }
 
-template <bool LDS_SCENE, int MAT>
-static void launch_chain_mat(bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc) {
-    if (medium) hipLaunchKernelGGL((k_stream_chain<MAT, true, LDS_SCENE, RL_NUMERICS_ID>), grid, block, lds_bytes, st, rc, ds, stc);
-    else hipLaunchKernelGGL((k_stream_chain<MAT, false, LDS_SCENE, RL_NUMERICS_ID>), grid, block, lds_bytes, st, rc, ds, stc);
-}
 template <bool LDS_SCENE>
 static void launch_chain_impl(int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc) {
-    switch (mat) {
-        case BSDF_DIFFUSE: launch_chain_mat<LDS_SCENE, BSDF_DIFFUSE>(medium, grid, block, lds_bytes, st, rc, ds, stc); break;
-        case BSDF_PHONG: launch_chain_mat<LDS_SCENE, BSDF_PHONG>(medium, grid, block, lds_bytes, st, rc, ds, stc); break;
-        case BSDF_METAL: launch_chain_mat<LDS_SCENE, BSDF_METAL>(medium, grid, block, lds_bytes, st, rc, ds, stc); break;
-        case BSDF_GLASS: launch_chain_mat<LDS_SCENE, BSDF_GLASS>(medium, grid, block, lds_bytes, st, rc, ds, stc); break;
-        case -1: launch_chain_mat<LDS_SCENE, -1>(medium, grid, block, lds_bytes, st, rc, ds, stc); break;
-        default: launch_chain_mat<LDS_SCENE, BSDF_SUBSTRATE>(medium, grid, block, lds_bytes, st, rc, ds, stc); break;
-    }
+    with_bsdf(mat, [&](auto M) { with_flag(medium, [&](auto MED) {
+        hipLaunchKernelGGL((k_stream_chain<decltype(M)::value, decltype(MED)::value, LDS_SCENE, RL_NUMERICS_ID>), grid, block, lds_bytes, st, rc, ds, stc);
+    }); });
 }
 
 }  // namespace rl

@@ -33,23 +33,12 @@ __global__ void __launch_bounds__(256, LDS_SCENE ? RL_FUSED_WAVES : RL_FUSED_WAV
 }
 
 
-template <bool LDS_SCENE, int MAT>
-static void launch_fused_mat(bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc) {
-    if (medium) { if (area_only) hipLaunchKernelGGL((k_path_fused<MAT, true, LDS_SCENE, LIGHTS_AREA_ONLY, RL_NUMERICS_ID, RL_FUSED_QUEUE != 0>), grid, block, lds_bytes, st, rc, ds, stc);
-                  else hipLaunchKernelGGL((k_path_fused<MAT, true, LDS_SCENE, LIGHTS_ANY, RL_NUMERICS_ID, RL_FUSED_QUEUE != 0>), grid, block, lds_bytes, st, rc, ds, stc); }
-    else { if (area_only) hipLaunchKernelGGL((k_path_fused<MAT, false, LDS_SCENE, LIGHTS_AREA_ONLY, RL_NUMERICS_ID, RL_FUSED_QUEUE != 0>), grid, block, lds_bytes, st, rc, ds, stc);
-           else hipLaunchKernelGGL((k_path_fused<MAT, false, LDS_SCENE, LIGHTS_ANY, RL_NUMERICS_ID, RL_FUSED_QUEUE != 0>), grid, block, lds_bytes, st, rc, ds, stc); }
-}
 template <bool LDS_SCENE>
 static void launch_fused_impl(int mat, bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc) {
-    switch (mat) {
-        case BSDF_DIFFUSE: launch_fused_mat<LDS_SCENE, BSDF_DIFFUSE>(medium, area_only, grid, block, lds_bytes, st, rc, ds, stc); break;
-        case BSDF_PHONG: launch_fused_mat<LDS_SCENE, BSDF_PHONG>(medium, area_only, grid, block, lds_bytes, st, rc, ds, stc); break;
-        case BSDF_METAL: launch_fused_mat<LDS_SCENE, BSDF_METAL>(medium, area_only, grid, block, lds_bytes, st, rc, ds, stc); break;
-        case BSDF_GLASS: launch_fused_mat<LDS_SCENE, BSDF_GLASS>(medium, area_only, grid, block, lds_bytes, st, rc, ds, stc); break;
-        case -1: launch_fused_mat<LDS_SCENE, -1>(medium, area_only, grid, block, lds_bytes, st, rc, ds, stc); break;      // several BSDF types: run-time switch per vertex
-        default: launch_fused_mat<LDS_SCENE, BSDF_SUBSTRATE>(medium, area_only, grid, block, lds_bytes, st, rc, ds, stc); break;
-    }
+    with_bsdf(mat, [&](auto M) { with_flag(medium, [&](auto MED) { with_flag(area_only, [&](auto AREA) {
+        constexpr int MAT = decltype(M)::value, LIGHTS = decltype(AREA)::value ? LIGHTS_AREA_ONLY : LIGHTS_ANY;
+        hipLaunchKernelGGL((k_path_fused<MAT, decltype(MED)::value, LDS_SCENE, LIGHTS, RL_NUMERICS_ID, RL_FUSED_QUEUE != 0>), grid, block, lds_bytes, st, rc, ds, stc);
+    }); }); });
 }
 template <bool LDS_SCENE>
 static void dump_stage_timers_impl() {

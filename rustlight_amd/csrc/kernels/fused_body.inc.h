@@ -4,6 +4,7 @@
     const RenderConst& rc = rc_arg;
     const DeviceScene& sc = sc_arg;
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
+    // (open_scene of stages.hip.h, written out: called as a function it gives this kernel other instructions, and the published numbers are this kernel's)
     SceneRecs recs;
     float4* after_scene = smem;
     if (LDS_SCENE) {

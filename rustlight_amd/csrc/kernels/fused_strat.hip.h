@@ -16,10 +16,10 @@ __global__ void __launch_bounds__(256, LDS_SCENE ? RL_FUSED_WAVES : RL_FUSED_WAV
 
 template <bool LDS_SCENE>
 static void launch_fused_strat_impl(bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc) {
-    if (medium) { if (area_only) hipLaunchKernelGGL((k_path_fused_strat<true, LDS_SCENE, LIGHTS_AREA_ONLY>), grid, block, lds_bytes, st, rc, ds, stc);
-                  else hipLaunchKernelGGL((k_path_fused_strat<true, LDS_SCENE, LIGHTS_ANY>), grid, block, lds_bytes, st, rc, ds, stc); }
-    else { if (area_only) hipLaunchKernelGGL((k_path_fused_strat<false, LDS_SCENE, LIGHTS_AREA_ONLY>), grid, block, lds_bytes, st, rc, ds, stc);
-           else hipLaunchKernelGGL((k_path_fused_strat<false, LDS_SCENE, LIGHTS_ANY>), grid, block, lds_bytes, st, rc, ds, stc); }
+    with_flag(medium, [&](auto MED) { with_flag(area_only, [&](auto AREA) {
+        constexpr int LIGHTS = decltype(AREA)::value ? LIGHTS_AREA_ONLY : LIGHTS_ANY;
+        hipLaunchKernelGGL((k_path_fused_strat<decltype(MED)::value, LDS_SCENE, LIGHTS>), grid, block, lds_bytes, st, rc, ds, stc);
+    }); });
 }
 
 }  // namespace rl

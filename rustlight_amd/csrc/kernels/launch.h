@@ -1,8 +1,33 @@
-// launch.h — host-side launchers of the kernel families that live in their own translation units (fused_lds.hip, fused_stream.hip,
-// shade.hip, mc.hip), so that the families compile in parallel.  Launch errors are picked up by the caller's hipGetLastError().
+// launch.h — host-side launchers of the kernel families that live in their own translation units (fused_*.hip, fusedq_*.hip, fused_strat_*.hip,
+// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip), so that the families compile in parallel, and
+// the dispatcher every one of them maps its run-time arguments to template arguments with (with_bsdf, with_flag).  Launch errors are picked up by
+// the caller's hipGetLastError().
 #pragma once
+#include <type_traits>
 
 namespace rl {
+
+// with_bsdf(mat, f): f(std::integral_constant<int, MAT>{}) for the scene's one BSDF type, MAT = -1 (the run-time switch per vertex) for a scene
+// that mixes types.  Any other value also gets -1, in every family: the run-time switch is correct for any scene.
+// The order of the cases is load-bearing: the kernels are instantiated, and so laid out in the code objects, in this order, and with `default`
+// (-1) before BSDF_SUBSTRATE the objects of fused_*, fusedq_*, chain_* and spec_* disassemble exactly as before this dispatcher existed.  It is not
+// a misplaced label; do not sort it to the end.
+template <class F>
+static void with_bsdf(int mat, F&& f) {
+    switch (mat) {
+        case BSDF_DIFFUSE: f(std::integral_constant<int, BSDF_DIFFUSE>{}); break;
+        case BSDF_PHONG: f(std::integral_constant<int, BSDF_PHONG>{}); break;
+        case BSDF_METAL: f(std::integral_constant<int, BSDF_METAL>{}); break;
+        case BSDF_GLASS: f(std::integral_constant<int, BSDF_GLASS>{}); break;
+        default: f(std::integral_constant<int, -1>{}); break;
+        case BSDF_SUBSTRATE: f(std::integral_constant<int, BSDF_SUBSTRATE>{}); break;
+    }
+}
+// with_flag(b, f): f(std::true_type{}) or f(std::false_type{})
+template <class F>
+static void with_flag(bool b, F&& f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
 
 // IntegratorAO / IntegratorDirect parameters (ao.rs:4-7, direct.rs:5-8)
 struct McConst {

@@ -126,17 +126,8 @@ template <int MAT, bool LDS_SCENE, bool MEDIUM>
 __global__ void __launch_bounds__(256, kLightWaves) k_light_fused(RenderConst rc, DeviceScene sc, StackConf stc, LightConst lc) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneRecs recs;
-    float4* after_scene = smem;
-    if (LDS_SCENE) {
-        stage_scene_lds(sc, smem, smem + lds_nodes_float4s(sc.n_nodes));
-        recs.nodes = smem; recs.tris = smem + lds_nodes_float4s(sc.n_nodes);
-        after_scene = smem + lds_scene_float4s(sc.n_nodes, sc.n_prims);
-    } else {
-        recs.nodes = streamed_nodes<TravStackT<false>>(sc);
-        recs.tris = reinterpret_cast<const float4*>(sc.tris);
-    }
     const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const TravStackT<LDS_SCENE> stack = make_stack<LDS_SCENE>(stc, reinterpret_cast<unsigned*>(after_scene), tid);
+    const TravStackT<LDS_SCENE> stack = open_scene<LDS_SCENE>(sc, stc, smem, tid, &recs);
     // rc.split lanes per slot (small images: enough lanes to fill the chip): lane `sub` of the slot traces samples sub, sub + split, ...
     const unsigned item = tid / rc.split, sub = tid - item * rc.split;
     unsigned n_paths = 0, n_draws = 0, n_ext = 0, n_shadow = 0, n_vertices = 0, n_add = 0, n_invalid = 0, n_sat = 0;
@@ -206,10 +197,8 @@ __global__ void __launch_bounds__(256, kLightWaves) k_light_fused(RenderConst rc
             unsigned gen = 1u;                                         // generate depth of the edge's origin = evaluate depth of the vertex it reaches
             for (;;) {
                 n_ext++;
-                Hit hit; hit.t = kF32Max; hit.u = 0.0f; hit.v = 0.0f; hit.prim = -1;
-                traverse<false>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
-                                ro, rd, kEps, kF32Max, hit, stack);
-                const bool is_hit = hit.prim >= 0;
+                Hit hit;
+                const bool is_hit = trace_closest(sc, recs, stack, ro, rd, hit);
                 bool is_volume = false;
                 V3 vp = mk3(0.0f, 0.0f, 0.0f);
                 if (MEDIUM) {
@@ -298,21 +287,11 @@ __global__ void __launch_bounds__(256, kLightWaves) k_light_fused(RenderConst rc
     }
 }
 
-template <int MAT, bool LDS_SCENE>
-static void launch_light_mat(bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const LightConst& lc) {
-    if (medium) hipLaunchKernelGGL((k_light_fused<MAT, LDS_SCENE, true>), grid, block, lds_bytes, st, rc, ds, stc, lc);
-    else hipLaunchKernelGGL((k_light_fused<MAT, LDS_SCENE, false>), grid, block, lds_bytes, st, rc, ds, stc, lc);
-}
 template <bool LDS_SCENE>
 static void launch_light_impl(int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const LightConst& lc) {
-    switch (mat) {
-        case BSDF_DIFFUSE: launch_light_mat<BSDF_DIFFUSE, LDS_SCENE>(medium, grid, block, lds_bytes, st, rc, ds, stc, lc); break;
-        case BSDF_PHONG: launch_light_mat<BSDF_PHONG, LDS_SCENE>(medium, grid, block, lds_bytes, st, rc, ds, stc, lc); break;
-        case BSDF_METAL: launch_light_mat<BSDF_METAL, LDS_SCENE>(medium, grid, block, lds_bytes, st, rc, ds, stc, lc); break;
-        case BSDF_GLASS: launch_light_mat<BSDF_GLASS, LDS_SCENE>(medium, grid, block, lds_bytes, st, rc, ds, stc, lc); break;
-        case BSDF_SUBSTRATE: launch_light_mat<BSDF_SUBSTRATE, LDS_SCENE>(medium, grid, block, lds_bytes, st, rc, ds, stc, lc); break;
-        default: launch_light_mat<-1, LDS_SCENE>(medium, grid, block, lds_bytes, st, rc, ds, stc, lc); break;       // several BSDF types: run-time switch per vertex
-    }
+    with_bsdf(mat, [&](auto M) { with_flag(medium, [&](auto MED) {
+        hipLaunchKernelGGL((k_light_fused<decltype(M)::value, LDS_SCENE, decltype(MED)::value>), grid, block, lds_bytes, st, rc, ds, stc, lc);
+    }); });
 }
 
 }  // namespace rl

@@ -8,6 +8,7 @@ namespace rl {
 // 508 k triangles 36.1 vs 22.2 / 21.4 ms)
 template <int KIND, bool LDS_SCENE>
 __global__ void __launch_bounds__(256, LDS_SCENE ? RL_FUSED_WAVES : RL_FUSED_WAVES_STREAMING) k_pixel_mc(RenderConst rc, DeviceScene sc, StackConf stc, McConst mp) {
+    // (open_scene of stages.hip.h, written out: called as a function it makes k_pixel_mc<1, true> spill 17 more SGPRs and two more VGPRs)
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneRecs recs;
     float4* after_scene = smem;
@@ -71,17 +72,8 @@ template <int KIND, bool LDS_SCENE>
 __global__ void __launch_bounds__(256, LDS_SCENE ? RL_FUSED_WAVES : RL_FUSED_WAVES_STREAMING) k_mc_chain(RenderConst rc, DeviceScene sc, StackConf stc, McConst mp) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneRecs recs;
-    float4* after_scene = smem;
-    if (LDS_SCENE) {
-        stage_scene_lds(sc, smem, smem + lds_nodes_float4s(sc.n_nodes));
-        recs.nodes = smem; recs.tris = smem + lds_nodes_float4s(sc.n_nodes);
-        after_scene = smem + lds_scene_float4s(sc.n_nodes, sc.n_prims);
-    } else {
-        recs.nodes = streamed_nodes<TravStackT<false>>(sc);
-        recs.tris = reinterpret_cast<const float4*>(sc.tris);
-    }
     const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const TravStackT<LDS_SCENE> stack = make_stack<LDS_SCENE>(stc, reinterpret_cast<unsigned*>(after_scene), tid);
+    const TravStackT<LDS_SCENE> stack = open_scene<LDS_SCENE>(sc, stc, smem, tid, &recs);
     const unsigned item = (tid & ((1u << rc.item_shift) - 1u)) == 0u ? (tid >> rc.item_shift) : 0xffffffffu;
     if (item >= rc.n_items) return;
     unsigned bx, by, bw, bh;
@@ -108,13 +100,15 @@ __global__ void __launch_bounds__(256, LDS_SCENE ? RL_FUSED_WAVES : RL_FUSED_WAV
 }
 
 void launch_mc_chain(int kind, bool lds_scene, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const McConst& mp) {
-    if (kind == 0) { if (lds_scene) hipLaunchKernelGGL((k_mc_chain<0, true>), grid, block, lds_bytes, st, rc, ds, stc, mp); else hipLaunchKernelGGL((k_mc_chain<0, false>), grid, block, lds_bytes, st, rc, ds, stc, mp); }
-    else { if (lds_scene) hipLaunchKernelGGL((k_mc_chain<1, true>), grid, block, lds_bytes, st, rc, ds, stc, mp); else hipLaunchKernelGGL((k_mc_chain<1, false>), grid, block, lds_bytes, st, rc, ds, stc, mp); }
+    with_flag(kind != 0, [&](auto K) { with_flag(lds_scene, [&](auto LDS) {
+        hipLaunchKernelGGL((k_mc_chain<decltype(K)::value ? 1 : 0, decltype(LDS)::value>), grid, block, lds_bytes, st, rc, ds, stc, mp);
+    }); });
 }
 
 void launch_pixel_mc(int kind, bool lds_scene, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const McConst& mp) {
-    if (kind == 0) { if (lds_scene) hipLaunchKernelGGL((k_pixel_mc<0, true>), grid, block, lds_bytes, st, rc, ds, stc, mp); else hipLaunchKernelGGL((k_pixel_mc<0, false>), grid, block, lds_bytes, st, rc, ds, stc, mp); }
-    else { if (lds_scene) hipLaunchKernelGGL((k_pixel_mc<1, true>), grid, block, lds_bytes, st, rc, ds, stc, mp); else hipLaunchKernelGGL((k_pixel_mc<1, false>), grid, block, lds_bytes, st, rc, ds, stc, mp); }
+    with_flag(kind != 0, [&](auto K) { with_flag(lds_scene, [&](auto LDS) {
+        hipLaunchKernelGGL((k_pixel_mc<decltype(K)::value ? 1 : 0, decltype(LDS)::value>), grid, block, lds_bytes, st, rc, ds, stc, mp);
+    }); });
 }
 
 }  // namespace rl

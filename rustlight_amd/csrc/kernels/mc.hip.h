@@ -16,13 +16,6 @@ RL_DEV float mis_weight_power(float pdf_a, float pdf_b) {
     return finite_f(w) ? w : 0.0f;
 }
 template <class Stack>
-RL_DEV bool trace_closest(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, V3 o, V3 d, Hit& hit) {
-    hit.t = kF32Max; hit.u = 0.0f; hit.v = 0.0f; hit.prim = -1;
-    traverse<false>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
-                    o, d, kEps, kF32Max, hit, stack);
-    return hit.prim >= 0;
-}
-template <class Stack>
 RL_DEV bool trace_visible(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, V3 p0, V3 p1) { return shadow_visible(sc, recs, stack, p0, p1); }
 
 // SMP: the sampler of the draws (sampler.hip.h): Rng, or StratSampler (k_pixel_mc_strat)

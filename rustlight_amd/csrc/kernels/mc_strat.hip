@@ -14,17 +14,8 @@ template <int KIND, bool LDS_SCENE>
 __global__ void __launch_bounds__(256, LDS_SCENE ? RL_FUSED_WAVES : RL_FUSED_WAVES_STREAMING) k_pixel_mc_strat(RenderConst rc, DeviceScene sc, StackConf stc, McConst mp) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneRecs recs;
-    float4* after_scene = smem;
-    if (LDS_SCENE) {
-        stage_scene_lds(sc, smem, smem + lds_nodes_float4s(sc.n_nodes));
-        recs.nodes = smem; recs.tris = smem + lds_nodes_float4s(sc.n_nodes);
-        after_scene = smem + lds_scene_float4s(sc.n_nodes, sc.n_prims);
-    } else {
-        recs.nodes = streamed_nodes<TravStackT<false>>(sc);
-        recs.tris = reinterpret_cast<const float4*>(sc.tris);
-    }
     const unsigned item = blockIdx.x * blockDim.x + threadIdx.x;
-    const TravStackT<LDS_SCENE> stack = make_stack<LDS_SCENE>(stc, reinterpret_cast<unsigned*>(after_scene), item);
+    const TravStackT<LDS_SCENE> stack = open_scene<LDS_SCENE>(sc, stc, smem, item, &recs);
     unsigned n_samples = 0, n_draws = 0, n_ext = 0, n_shadow = 0, n_vertices = 0;
     if (item < rc.n_items) {
         Rng pixel_rng = rng_seed(rc.item_seed[item], rc.seed_variant);
@@ -48,8 +39,9 @@ __global__ void __launch_bounds__(256, LDS_SCENE ? RL_FUSED_WAVES : RL_FUSED_WAV
 }
 
 void launch_pixel_mc_strat(int kind, bool lds_scene, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const McConst& mp) {
-    if (kind == 0) { if (lds_scene) hipLaunchKernelGGL((k_pixel_mc_strat<0, true>), grid, block, lds_bytes, st, rc, ds, stc, mp); else hipLaunchKernelGGL((k_pixel_mc_strat<0, false>), grid, block, lds_bytes, st, rc, ds, stc, mp); }
-    else { if (lds_scene) hipLaunchKernelGGL((k_pixel_mc_strat<1, true>), grid, block, lds_bytes, st, rc, ds, stc, mp); else hipLaunchKernelGGL((k_pixel_mc_strat<1, false>), grid, block, lds_bytes, st, rc, ds, stc, mp); }
+    with_flag(kind != 0, [&](auto K) { with_flag(lds_scene, [&](auto LDS) {
+        hipLaunchKernelGGL((k_pixel_mc_strat<decltype(K)::value ? 1 : 0, decltype(LDS)::value>), grid, block, lds_bytes, st, rc, ds, stc, mp);
+    }); });
 }
 
 // test probe: one lane per pixel walks its samples as the renderers do (pixel sampler from seeds[p], one fork per sample) and takes the call pattern

@@ -26,30 +26,18 @@ __global__ void __launch_bounds__(256, RL_SORT_WAVES) k_shade_sorted(RenderConst
 #include "shade_sorted_body.inc.h"
 }
 
-template <int MAT>
-static void launch_shade(bool medium, dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const Pool& pool) {
-    if (medium) hipLaunchKernelGGL((k_shade<MAT, true>), grid, block, 0, st, rc, ds, pool);
-    else hipLaunchKernelGGL((k_shade<MAT, false>), grid, block, 0, st, rc, ds, pool);
-}
+// (no k_shade<-1>: a scene that mixes BSDF types, or a type this build does not know, is shaded by the material sort, one slot per lane)
 void launch_shade_type(int type, bool medium, dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const Pool& pool) {
-    switch (type) {
-        case BSDF_DIFFUSE: launch_shade<BSDF_DIFFUSE>(medium, grid, block, st, rc, ds, pool); break;
-        case BSDF_PHONG: launch_shade<BSDF_PHONG>(medium, grid, block, st, rc, ds, pool); break;
-        case BSDF_METAL: launch_shade<BSDF_METAL>(medium, grid, block, st, rc, ds, pool); break;
-        case BSDF_GLASS: launch_shade<BSDF_GLASS>(medium, grid, block, st, rc, ds, pool); break;
-        default: launch_shade<BSDF_SUBSTRATE>(medium, grid, block, st, rc, ds, pool); break;
-    }
+    with_bsdf(type, [&](auto M) {
+        if constexpr (decltype(M)::value < 0) launch_shade_sorted(medium, 1u, grid, block, st, rc, ds, pool);
+        else with_flag(medium, [&](auto MED) { hipLaunchKernelGGL((k_shade<decltype(M)::value, decltype(MED)::value>), grid, block, 0, st, rc, ds, pool); });
+    });
 }
-
 
 void launch_shade_sorted(bool medium, unsigned chunks, dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const Pool& pool) {
-    if (chunks == 4u) {
-        if (medium) hipLaunchKernelGGL((k_shade_sorted<true, 4>), grid, block, 0, st, rc, ds, pool);
-        else hipLaunchKernelGGL((k_shade_sorted<false, 4>), grid, block, 0, st, rc, ds, pool);
-    } else {
-        if (medium) hipLaunchKernelGGL((k_shade_sorted<true, 1>), grid, block, 0, st, rc, ds, pool);
-        else hipLaunchKernelGGL((k_shade_sorted<false, 1>), grid, block, 0, st, rc, ds, pool);
-    }
+    with_flag(chunks == 4u, [&](auto FOUR) { with_flag(medium, [&](auto MED) {
+        hipLaunchKernelGGL((k_shade_sorted<decltype(MED)::value, decltype(FOUR)::value ? 4u : 1u>), grid, block, 0, st, rc, ds, pool);
+    }); });
 }
 
 }  // namespace rl

@@ -68,6 +68,7 @@ __global__ void __launch_bounds__(256, LDS_SCENE ? RL_SPEC_WAVES : RL_SPEC_WAVES
     const SpecConf* spcp = &spc_arg;      // (inside the loop: re-read from the kernarg segment like rc and sc, so that none of its fields is kept in a register across the traversal)
 #define spc (*spcp)
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
+    // (open_scene of stages.hip.h, written out: called as a function it gives this kernel other instructions, and the published numbers are this kernel's)
     SceneRecs recs;
     float4* after_scene = smem;
     if (LDS_SCENE) {
@@ -679,21 +680,11 @@ __global__ void __launch_bounds__(256, LDS_SCENE ? RL_SPEC_WAVES : RL_SPEC_WAVES
 #undef COLD_OF
 }
 
-template <bool LDS_SCENE, int MAT>
-static void launch_spec_mat(bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const SpecConf& spc) {
-    if (medium) hipLaunchKernelGGL((k_stream_spec<MAT, true, LDS_SCENE, 0>), grid, block, lds_bytes, st, rc, ds, stc, spc);
-    else hipLaunchKernelGGL((k_stream_spec<MAT, false, LDS_SCENE, 0>), grid, block, lds_bytes, st, rc, ds, stc, spc);
-}
 template <bool LDS_SCENE>
 static void launch_spec_impl(int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const SpecConf& spc) {
-    switch (mat) {
-        case BSDF_DIFFUSE: launch_spec_mat<LDS_SCENE, BSDF_DIFFUSE>(medium, grid, block, lds_bytes, st, rc, ds, stc, spc); break;
-        case BSDF_PHONG: launch_spec_mat<LDS_SCENE, BSDF_PHONG>(medium, grid, block, lds_bytes, st, rc, ds, stc, spc); break;
-        case BSDF_METAL: launch_spec_mat<LDS_SCENE, BSDF_METAL>(medium, grid, block, lds_bytes, st, rc, ds, stc, spc); break;
-        case BSDF_GLASS: launch_spec_mat<LDS_SCENE, BSDF_GLASS>(medium, grid, block, lds_bytes, st, rc, ds, stc, spc); break;
-        case -1: launch_spec_mat<LDS_SCENE, -1>(medium, grid, block, lds_bytes, st, rc, ds, stc, spc); break;
-        default: launch_spec_mat<LDS_SCENE, BSDF_SUBSTRATE>(medium, grid, block, lds_bytes, st, rc, ds, stc, spc); break;
-    }
+    with_bsdf(mat, [&](auto M) { with_flag(medium, [&](auto MED) {
+        hipLaunchKernelGGL((k_stream_spec<decltype(M)::value, decltype(MED)::value, LDS_SCENE, 0>), grid, block, lds_bytes, st, rc, ds, stc, spc);
+    }); });
 }
 
 }  // namespace rl

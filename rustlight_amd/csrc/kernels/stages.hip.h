@@ -188,6 +188,25 @@ RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, un
 }
 
 // ------------------------------------------------------------------------------------------
+// open_scene — a kernel's prologue: the scene staged into the dynamic LDS `smem` (LDS_SCENE; every lane of the workgroup takes part) or *recs pointed
+// at the streamed arrays, and the lane's traversal stack behind it.  LDS: [scene][per-lane stacks].  k_path_fused, k_stream_chain and k_stream_spec
+// keep this text written out (an inlined function with the same statements gives them other instructions), and so do k_pixel_mc and k_vpl_gather
+// (it makes k_pixel_mc<1, true> and k_vpl_gather<0, true, false> spill more); trace_kernel_body has another layout.
+template <bool LDS_SCENE>
+RL_DEV TravStackT<LDS_SCENE> open_scene(const DeviceScene& sc, const StackConf& stc, float4* smem, unsigned tid, SceneRecs* recs) {
+    float4* after_scene = smem;
+    if (LDS_SCENE) {
+        stage_scene_lds(sc, smem, smem + lds_nodes_float4s(sc.n_nodes));
+        recs->nodes = smem; recs->tris = smem + lds_nodes_float4s(sc.n_nodes);
+        after_scene = smem + lds_scene_float4s(sc.n_nodes, sc.n_prims);
+    } else {
+        recs->nodes = streamed_nodes<TravStackT<false>>(sc);
+        recs->tris = reinterpret_cast<const float4*>(sc.tris);
+    }
+    return make_stack<LDS_SCENE>(stc, reinterpret_cast<unsigned*>(after_scene), tid);
+}
+
+// ------------------------------------------------------------------------------------------
 // extend_slot / shadow_slot — Acceleration::trace and Acceleration::visible for one slot.
 template <class PS, class Stack>
 RL_DEV void extend_slot(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, PS& ps, int* dbg = nullptr) {
@@ -216,6 +235,21 @@ RL_DEV bool shadow_visible(const DeviceScene& sc, const SceneRecs& recs, const S
         return false;   // root box missed => "occluded" (accel.rs:338-340)
     return !traverse<true>(recs, Stack::kBvh4 ? sc.root4 : sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
                            p0, d, kEps, tfar, hit, stack);
+}
+// Acceleration::trace(o, d) of the kernels that keep no path state: the closest hit in `hit`, true if there is one
+template <class Stack>
+RL_DEV bool trace_closest(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, V3 o, V3 d, Hit& hit) {
+    hit.t = kF32Max; hit.u = 0.0f; hit.v = 0.0f; hit.prim = -1;
+    traverse<false>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
+                    o, d, kEps, kF32Max, hit, stack);
+    return hit.prim >= 0;
+}
+// ... .is_none(): its any-hit form, true if the ray from o along d meets nothing
+template <class Stack>
+RL_DEV bool trace_none(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, V3 o, V3 d) {
+    Hit hit; hit.t = kF32Max; hit.u = 0.0f; hit.v = 0.0f; hit.prim = -1;
+    return !traverse<true>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
+                           o, d, kEps, kF32Max, hit, stack);
 }
 template <class PS, class Stack>
 RL_DEV void shadow_slot(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, PS& ps) {

@@ -1,6 +1,7 @@
 // vpl.hip.h — IntegratorVPL (src/integrators/explicit/vpl.rs): virtual point lights shot from the emitters, then gathered at every camera sample.
-// Instantiated by vpl_lds.hip (scene staged in LDS) and vpl_stream.hip (BVH streamed from L2 / HBM).  The shared headers are only called (bsdf_sample
-// with RADIANCE = true is a new instantiation), so no other kernel's code or register allocation changes.
+// Instantiated by vpl_lds.hip (scene staged in LDS) and vpl_stream.hip (BVH streamed from L2 / HBM).  The scene is opened and traced through the helpers
+// every secondary kernel uses (stages.hip.h: open_scene, trace_closest, trace_none, shadow_visible) except where a kernel says why it keeps a block
+// written out; the light-path walk of k_vpl_generate is k_light_fused's (light.hip.h), restated with Transport::Radiance (bsdf_sample<MAT, true>).
 //
 // Generation (vpl.rs:182-210): k_vpl_generate, one lane, walks the main sampler's serial stream as the reference does — Path::from_light, `generate`
 // with TechniqueVPL and DirectionalSamplingStrategy { transport: Radiance } (the shading-normal correction scales the throughput, which only the
@@ -55,17 +56,8 @@ template <int MAT, bool LDS_SCENE, bool MEDIUM>
 __global__ void __launch_bounds__(256) k_vpl_generate(RenderConst rc, DeviceScene sc, StackConf stc, VplConst vc) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneRecs recs;
-    float4* after_scene = smem;
-    if (LDS_SCENE) {
-        stage_scene_lds(sc, smem, smem + lds_nodes_float4s(sc.n_nodes));
-        recs.nodes = smem; recs.tris = smem + lds_nodes_float4s(sc.n_nodes);
-        after_scene = smem + lds_scene_float4s(sc.n_nodes, sc.n_prims);
-    } else {
-        recs.nodes = streamed_nodes<TravStackT<false>>(sc);
-        recs.tris = reinterpret_cast<const float4*>(sc.tris);
-    }
     const unsigned tid = threadIdx.x;
-    const TravStackT<LDS_SCENE> stack = make_stack<LDS_SCENE>(stc, reinterpret_cast<unsigned*>(after_scene), tid);
+    const TravStackT<LDS_SCENE> stack = open_scene<LDS_SCENE>(sc, stc, smem, tid, &recs);
     if (tid != 0u) return;
     Rng rng; rng.s0 = vc.gen_state[0]; rng.s1 = vc.gen_state[1]; rng.s2 = vc.gen_state[2]; rng.s3 = vc.gen_state[3];
     unsigned n_vpl = 0, n_paths = 0, n_vertices = 0, n_ext = 0, n_draws = 0;
@@ -120,6 +112,7 @@ __global__ void __launch_bounds__(256) k_vpl_generate(RenderConst rc, DeviceScen
         unsigned gen = 1u;
         for (;;) {
             n_ext++;
+            // (trace_closest of stages.hip.h, written out: called as a function it costs k_vpl_generate<4, true, true> its fourth wave per SIMD)
             Hit hit; hit.t = kF32Max; hit.u = 0.0f; hit.v = 0.0f; hit.prim = -1;
             traverse<false>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
                             ro, rd, kEps, kF32Max, hit, stack);
@@ -184,17 +177,8 @@ template <bool LDS_SCENE, bool MEDIUM>
 __global__ void __launch_bounds__(256) k_vpl_primary(RenderConst rc, DeviceScene sc, StackConf stc, VplConst vc) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneRecs recs;
-    float4* after_scene = smem;
-    if (LDS_SCENE) {
-        stage_scene_lds(sc, smem, smem + lds_nodes_float4s(sc.n_nodes));
-        recs.nodes = smem; recs.tris = smem + lds_nodes_float4s(sc.n_nodes);
-        after_scene = smem + lds_scene_float4s(sc.n_nodes, sc.n_prims);
-    } else {
-        recs.nodes = streamed_nodes<TravStackT<false>>(sc);
-        recs.tris = reinterpret_cast<const float4*>(sc.tris);
-    }
     const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const TravStackT<LDS_SCENE> stack = make_stack<LDS_SCENE>(stc, reinterpret_cast<unsigned*>(after_scene), tid);
+    const TravStackT<LDS_SCENE> stack = open_scene<LDS_SCENE>(sc, stc, smem, tid, &recs);
     const unsigned ob = blockIdx.x, c = threadIdx.x;
     unsigned bx, by, bw, bh;
     block_geometry(rc, rc.owned_blocks[ob], &bx, &by, &bw, &bh);
@@ -220,9 +204,7 @@ __global__ void __launch_bounds__(256) k_vpl_primary(RenderConst rc, DeviceScene
         const float v = (float)(by + iy) + rng_next_f32(rng);
         rd = camera_direction(sc, u, v);
         const V3 cam = mk3(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]);
-        traverse<false>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
-                        cam, rd, kEps, kF32Max, hit, stack);
-        const bool is_hit = hit.prim >= 0;
+        const bool is_hit = trace_closest(sc, recs, stack, cam, rd, hit);
         t = hit.t;
         if (MEDIUM) {
             const float xi = rng_next_f32(rng);                          // taken on every branch (vpl.rs:470, 492)
@@ -259,13 +241,6 @@ __global__ void __launch_bounds__(256) k_vpl_primary(RenderConst rc, DeviceScene
     }
 }
 
-// Acceleration::visible(p0, p1) / trace(..).is_none() of the gather (vpl.rs:288, 300, 353)
-template <class Stack>
-RL_DEV bool vpl_trace_none(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, V3 o, V3 d) {
-    Hit hit; hit.t = kF32Max; hit.u = 0.0f; hit.v = 0.0f; hit.prim = -1;
-    return !traverse<true>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
-                           o, d, kEps, kF32Max, hit, stack);
-}
 template <bool MEDIUM>
 RL_DEV Col vpl_transmittance(const DeviceScene& sc, float dist) { return MEDIUM ? medium_transmittance(sc.medium, dist) : cone(); }
 
@@ -275,6 +250,7 @@ RL_DEV Col vpl_transmittance(const DeviceScene& sc, float dist) { return MEDIUM 
 // (a smooth gather point).
 template <int MAT, bool LDS_SCENE, bool MEDIUM>
 __global__ void __launch_bounds__(256) k_vpl_gather(RenderConst rc, DeviceScene sc, StackConf stc, VplConst vc) {
+    // (open_scene of stages.hip.h, written out: called as a function it makes k_vpl_gather<0, true, false> spill four more SGPRs)
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneRecs recs;
     float4* after_scene = smem;
@@ -312,7 +288,7 @@ __global__ void __launch_bounds__(256) k_vpl_gather(RenderConst rc, DeviceScene 
                     const Col rad = vpl_getc(r + 7);
                     if (vk == VPL_EMITTER_INF) {
                         n_shadow++;
-                        if (vpl_trace_none(sc, recs, stack, sp.p, -vpos)) {
+                        if (trace_none(sc, recs, stack, sp.p, -vpos)) {
                             const Col f = bsdf_eval<MAT>(sc, mat, sp.has_uv, sp.uv, sp.wi, to_local(sp.frame, -vpos), false);
                             l = l + (norm * rad) * f;
                         }
@@ -388,32 +364,17 @@ __global__ void __launch_bounds__(256) k_vpl_gather(RenderConst rc, DeviceScene 
     }
 }
 
-template <int MAT, bool LDS_SCENE>
-static void launch_vpl_mat(int which, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VplConst& vc) {
-    if (which == 0) {
-        if (medium) hipLaunchKernelGGL((k_vpl_generate<MAT, LDS_SCENE, true>), grid, block, lds_bytes, st, rc, ds, stc, vc);
-        else hipLaunchKernelGGL((k_vpl_generate<MAT, LDS_SCENE, false>), grid, block, lds_bytes, st, rc, ds, stc, vc);
-    } else {
-        if (medium) hipLaunchKernelGGL((k_vpl_gather<MAT, LDS_SCENE, true>), grid, block, lds_bytes, st, rc, ds, stc, vc);
-        else hipLaunchKernelGGL((k_vpl_gather<MAT, LDS_SCENE, false>), grid, block, lds_bytes, st, rc, ds, stc, vc);
-    }
-}
 // which: 0 = k_vpl_generate, 1 = k_vpl_gather, 2 = k_vpl_primary (mat not read)
 template <bool LDS_SCENE>
 static void launch_vpl_impl(int which, int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VplConst& vc) {
-    if (which == 2) {
-        if (medium) hipLaunchKernelGGL((k_vpl_primary<LDS_SCENE, true>), grid, block, lds_bytes, st, rc, ds, stc, vc);
-        else hipLaunchKernelGGL((k_vpl_primary<LDS_SCENE, false>), grid, block, lds_bytes, st, rc, ds, stc, vc);
-        return;
-    }
-    switch (mat) {
-        case BSDF_DIFFUSE: launch_vpl_mat<BSDF_DIFFUSE, LDS_SCENE>(which, medium, grid, block, lds_bytes, st, rc, ds, stc, vc); break;
-        case BSDF_PHONG: launch_vpl_mat<BSDF_PHONG, LDS_SCENE>(which, medium, grid, block, lds_bytes, st, rc, ds, stc, vc); break;
-        case BSDF_METAL: launch_vpl_mat<BSDF_METAL, LDS_SCENE>(which, medium, grid, block, lds_bytes, st, rc, ds, stc, vc); break;
-        case BSDF_GLASS: launch_vpl_mat<BSDF_GLASS, LDS_SCENE>(which, medium, grid, block, lds_bytes, st, rc, ds, stc, vc); break;
-        case BSDF_SUBSTRATE: launch_vpl_mat<BSDF_SUBSTRATE, LDS_SCENE>(which, medium, grid, block, lds_bytes, st, rc, ds, stc, vc); break;
-        default: launch_vpl_mat<-1, LDS_SCENE>(which, medium, grid, block, lds_bytes, st, rc, ds, stc, vc); break;
-    }
+    with_flag(medium, [&](auto MED) {
+        constexpr bool MEDIUM = decltype(MED)::value;
+        if (which == 2) { hipLaunchKernelGGL((k_vpl_primary<LDS_SCENE, MEDIUM>), grid, block, lds_bytes, st, rc, ds, stc, vc); return; }
+        with_bsdf(mat, [&](auto M) {
+            if (which == 0) hipLaunchKernelGGL((k_vpl_generate<decltype(M)::value, LDS_SCENE, MEDIUM>), grid, block, lds_bytes, st, rc, ds, stc, vc);
+            else hipLaunchKernelGGL((k_vpl_gather<decltype(M)::value, LDS_SCENE, MEDIUM>), grid, block, lds_bytes, st, rc, ds, stc, vc);
+        });
+    });
 }
 
 }  // namespace rl

@@ -181,9 +181,8 @@ __global__ void __launch_bounds__(256) k_trace_batch(DeviceScene sc, StackConf s
     const TravStack stack = make_stack(stc, reinterpret_cast<unsigned*>(smem), i);
     if (i >= n) return;
     V3 ro = mk3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
-    Hit hit; hit.t = kF32Max; hit.u = 0.0f; hit.v = 0.0f; hit.prim = -1;
-    traverse<false>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
-                    ro, rd, kEps, kF32Max, hit, stack);
+    Hit hit;
+    trace_closest(sc, recs, stack, ro, rd, hit);
     t_out[i] = hit.t; u_out[i] = hit.u; v_out[i] = hit.v;
     if (hit.prim >= 0) { mesh_out[i] = sc.tris[hit.prim].mesh; tri_out[i] = sc.tris[hit.prim].tri; }
     else { mesh_out[i] = -1; tri_out[i] = -1; }
@@ -201,9 +200,13 @@ __global__ void __launch_bounds__(256) k_trace_batch_two_level(DeviceScene sc, S
     if (i >= n) return;
     V3 ro = mk3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
     Hit hit; hit.t = kF32Max; hit.u = 0.0f; hit.v = 0.0f; hit.prim = -1;
-    const V3 lo = mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), hi = mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]);
-    if (any_hit) { hit.t = t_out[i]; const bool f = traverse<true>(recs, sc.root, lo, hi, ro, rd, kEps, hit.t, hit, stack); t_out[i] = f ? 1.0f : 0.0f; steps_out[i] = hit.steps; return; }   // t_out in: the segment length
-    traverse<false>(recs, sc.root, lo, hi, ro, rd, kEps, kF32Max, hit, stack);
+    if (any_hit) {   // t_out in: the segment length (not trace_none's whole ray)
+        hit.t = t_out[i];
+        const bool f = traverse<true>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]), ro, rd, kEps, hit.t, hit, stack);
+        t_out[i] = f ? 1.0f : 0.0f; steps_out[i] = hit.steps;
+        return;
+    }
+    trace_closest(sc, recs, stack, ro, rd, hit);
     t_out[i] = hit.t; u_out[i] = hit.u; v_out[i] = hit.v; steps_out[i] = hit.steps;
     if (hit.prim >= 0) { mesh_out[i] = sc.tris[hit.prim].mesh; tri_out[i] = sc.tris[hit.prim].tri; }
     else { mesh_out[i] = -1; tri_out[i] = -1; }
@@ -218,17 +221,7 @@ __global__ void __launch_bounds__(256) k_visible_batch(DeviceScene sc, StackConf
     const TravStack stack = make_stack(stc, reinterpret_cast<unsigned*>(smem), i);
     if (i >= n) return;
     V3 p0 = mk3(p0a[3 * i], p0a[3 * i + 1], p0a[3 * i + 2]), p1 = mk3(p1a[3 * i], p1a[3 * i + 1], p1a[3 * i + 2]);
-    V3 d = p1 - p0;
-    float len = length(d);
-    d = d / len;
-    float tfar = len * (1.0f - 0.00001f);
-    Hit hit; hit.t = tfar; hit.u = 0.0f; hit.v = 0.0f; hit.prim = -1;
-    bool occluded = traverse<true>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
-                                   p0, d, kEps, tfar, hit, stack);
-    V3 inv_d = mk3(div_rn(1.0f, d.x), div_rn(1.0f, d.y), div_rn(1.0f, d.z));
-    float te;
-    bool root_hit = slab(mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]), p0, inv_d, kEps, tfar, &te);
-    out[i] = (root_hit && !occluded) ? 1 : 0;
+    out[i] = shadow_visible(sc, recs, stack, p0, p1) ? 1 : 0;
 }
 
 // device self-test of the numerics contract: IEEE divide / sqrt, denormals, no contraction
