@@ -396,6 +396,36 @@ void rl_vpl_destroy(rl_vpl_set* set);
 int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_path_params* params, int option_lt, const uint64_t* block_seeds, size_t n_blocks,
                   float* out_rgb, int out_is_device, void* stream, rl_render_stats* stats);
 
+/* ---- IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: BRE } (src/integrators/explicit/vol_primitives.rs; CLI `vol-primitivies -p bre`,
+ * examples/cli.rs:189-196, 692-716): the beam radiance estimate.  Beams, planes and VRL are not built.
+ * The photons are the records of a set generated by rl_vpl_generate with option_vpl = RL_VPL_VOLUME and nb_vpl = nb_primitive: convert_photons
+ * (vol_primitives.rs:525-565) stores at every Vertex::Volume what convert_vpl stores under `-v volume`, from the same light paths, and the shooting stops on the
+ * same count — words 4..6 = pos, 7..9 = radiance, 10..12 = d_in; the set's path count is nb_path_shot.
+ * rl_photon_map_build sorts them into BHVAccel's tree (src/accel.rs:458-543: leaves of at most 4, otherwise sorted along the longest axis of the node's box and
+ * split in the middle) on the host and uploads it.  `radius`: the photon radius; the reference hard-codes RL_PHOTON_RADIUS_DEFAULT (vol_primitives.rs:618).
+ * Two deliberate differences: the sort is stable (the reference's sort_unstable_by leaves the order of equal keys unspecified) and a non-finite position is
+ * RL_ERR_INVALID_ARGUMENT (the reference panics).  Also refused: a scene without a medium (RL_ERR_UNSUPPORTED), a set that holds a record of another kind or
+ * belongs to another context, a radius that is not finite and > 0 (RL_ERR_INVALID_ARGUMENT).
+ * rl_render_bre (vol_primitives.rs:712-790): per camera sample 2 draws (the jitter), the camera ray with tfar = its closest hit's distance (f32::MAX on a miss:
+ * the ray still gathers), BHVAccel::gather in the reference's visiting order (node, right subtree, left subtree; a leaf's photons in index order) and
+ * c += radiance * exp(-sigma_t * t) * phase(-d, d_in) * 1 / (PI r^2) * 1 / nb_path_shot per photon whose sphere the ray meets; samples are added in order and
+ * scaled by 1 / spp.  Reference-order streams (sample (ix, iy, s) of a block starts at draw ((ix * bh + iy) * spp + s) * 2 of its stream), exact numerics, one
+ * device, host output; shards as rl_render_vpl; spp > RL_VPL_MAX_SPP is RL_ERR_UNSUPPORTED.  Counters: camera_samples, extension_rays = camera_samples,
+ * rng_draws = 2 * camera_samples, kernel_launches, ms_other = the gather kernel; reserved[0] = photon-tree nodes entered, reserved[1] = photons gathered.
+ * rl_photon_tree_build: the host part alone, no GPU — the tree of `n_photons` records (RL_VPL_WORDS u32 each, only words 4..6 are read) as the device walks
+ * it: nodes in visiting order, node_boxes [n][6] = p_min, p_max, node_links [n][3] = skip (the node to go on with when the box is missed; entered: the next
+ * one), first, count (count = 0: inner node; a leaf holds places first .. first + count - 1), order[place] = index of the record that stands there.  With the
+ * three arrays NULL only *n_nodes is written (at most 2 * n_photons). */
+#define RL_PHOTON_RADIUS_DEFAULT 0.001f
+typedef struct rl_photon_map rl_photon_map;       /* opaque: photon tree and photons, on the context's device */
+int rl_photon_map_build(rl_context* ctx, const rl_vpl_set* set, float radius, rl_photon_map** out);
+int rl_photon_map_info(const rl_photon_map* map, uint64_t* n_photons, uint64_t* n_nodes, uint64_t* n_paths, float* radius);
+void rl_photon_map_destroy(rl_photon_map* map);
+int rl_render_bre(rl_context* ctx, const rl_photon_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
+                  const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
+int rl_photon_tree_build(const uint32_t* words, size_t n_photons, float radius, size_t node_capacity, size_t* n_nodes, float* node_boxes,
+                         uint32_t* node_links, uint32_t* order);
+
 /* Frames in flight behind one call (the progressive wrappers' passes, avg.rs:5-131 / equal_time.rs:4-66: N independent renders of one scene): frame f — block
  * seeds `block_seeds[f]`, host image `out_rgb[f]` (W*H*3 f32) — renders on `ctxs[f % k]` from host thread f % k, k = min(n_ctx, n_frames); `ctxs` are distinct
  * contexts of the same scene.  Returns when every frame is done; the images (and `stats[f]`, if not NULL) are those of `n_frames` rl_render_path calls one after

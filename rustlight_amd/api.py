@@ -29,6 +29,7 @@ NUMERICS_EXACT, NUMERICS_FAST = 0, 1
 LIGHT_ALL, LIGHT_SURFACE, LIGHT_VOLUME = 0, 1, 2          # rl_light_strategy: `light-tracing -s all|surface|volume`
 VPL_ALL, VPL_SURFACE, VPL_VOLUME = 0, 1, 2                # rl_vpl_option: `vpl -v / -l all|surface|volume`
 VPL_WORDS = 24                                            # RL_VPL_WORDS: u32 per VPL record (rl_vpl_read)
+PHOTON_RADIUS_DEFAULT = 0.001                             # RL_PHOTON_RADIUS_DEFAULT: the radius the reference hard-codes (vol_primitives.rs:618)
 RL_ERR_UNSUPPORTED, RL_ERR_NO_EMITTER = -7, -8
 
 # every symbol include/rustlight_amd.h declares (tests check the .so exports all of them)
@@ -38,7 +39,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -114,6 +115,12 @@ def lib():
     L.rl_vpl_destroy.argtypes = [vp]
     L.rl_vpl_destroy.restype = None
     L.rl_render_vpl.argtypes = [vp, vp, C.POINTER(abi.PathParams), C.c_int, u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
+    L.rl_photon_map_build.argtypes = [vp, vp, C.c_float, C.POINTER(vp)]
+    L.rl_photon_map_info.argtypes = [vp, u64p, u64p, u64p, f32p]
+    L.rl_photon_map_destroy.argtypes = [vp]
+    L.rl_photon_map_destroy.restype = None
+    L.rl_render_bre.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
+    L.rl_photon_tree_build.argtypes = [u32p, C.c_size_t, C.c_float, C.c_size_t, C.POINTER(C.c_size_t), f32p, u32p, u32p]
     for fn in (L.rl_render_ao, L.rl_render_direct):
         fn.argtypes = [vp, C.POINTER(abi.McParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_multi_create.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -504,6 +511,24 @@ class Context:
         d["gather_surface"], d["gather_volume"] = int(st.reserved[0]), int(st.reserved[1])
         return img, d
 
+    def photon_map(self, vpls: "VplSet", radius=PHOTON_RADIUS_DEFAULT):
+        """rl_photon_map_build: the photon tree of the beam radiance estimate over a set generated with option_vpl = VPL_VOLUME (its records are the reference's
+        photons).  radius: the reference hard-codes PHOTON_RADIUS_DEFAULT."""
+        h = C.c_void_p()
+        _check(lib().rl_photon_map_build(self.h, vpls.h, radius, C.byref(h)))
+        return PhotonMap(h, self)
+
+    def render_bre(self, photons: "PhotonMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
+        """The beam radiance estimate's gather (vol_primitives.rs:712-790) through rl_render_bre: (image HxWx3 f32, stats dict).  stats: nodes_entered /
+        photons_gathered = reserved[0] / reserved[1], ms_other = the gather kernel."""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        st = abi.RenderStats()
+        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        _check(lib().rl_render_bre(self.h, photons.h, spp, seed_variant, shard_index, shard_count, abi.u64ptr(seeds), seeds.shape[0], abi.fptr(img), C.byref(st)))
+        d = st.as_dict()
+        d["nodes_entered"], d["photons_gathered"] = int(st.reserved[0]), int(st.reserved[1])
+        return img, d
+
     def trace(self, origins, directions):
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
@@ -740,6 +765,75 @@ class VplSet:
 VPL_RECORD_DTYPE = np.dtype([("kind", "<u4"), ("mesh", "<u4"), ("has_uv", "<u4"), ("pad", "<u4"), ("pos", "<f4", 3), ("radiance", "<f4", 3),
                              ("dir", "<f4", 3), ("uv", "<f4", 2), ("frame", "<f4", (3, 3))])
 assert VPL_RECORD_DTYPE.itemsize == 4 * VPL_WORDS
+
+
+class PhotonMap:
+    """rl_photon_map: photon tree and photons of one generation, on the device of the context that made them (kept alive with it)."""
+
+    def __init__(self, h, ctx: Context):
+        self.h, self.ctx = h, ctx
+
+    def info(self):
+        """(photons, tree nodes, light paths shot, radius)."""
+        n, m, p, r = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _check(lib().rl_photon_map_info(self.h, C.byref(n), C.byref(m), C.byref(p), C.byref(r)))
+        return int(n.value), int(m.value), int(p.value), float(r.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().rl_photon_map_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def photon_tree_build(words, radius):
+    """rl_photon_tree_build, host only: (boxes [n, 6] f32, links [n, 3] u32 = skip, first, count, order [n_photons] u32) of the photon tree over records
+    `words` ([n_photons, VPL_WORDS] u32), nodes in the order the gather visits them."""
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, VPL_WORDS)
+    n = C.c_size_t()
+    _check(lib().rl_photon_tree_build(abi.u32ptr(w), w.shape[0], radius, 0, C.byref(n), None, None, None))
+    boxes, links, order = np.zeros((n.value, 6), np.float32), np.zeros((n.value, 3), np.uint32), np.zeros(w.shape[0], np.uint32)
+    _check(lib().rl_photon_tree_build(abi.u32ptr(w), w.shape[0], radius, n.value, C.byref(n), abi.fptr(boxes), abi.u32ptr(links), abi.u32ptr(order)))
+    return boxes, links, order
+
+
+class IntegratorVolPrimitives:
+    """struct IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute for
+    primitives = BRE, seed for seed the reference: the photons from the main sampler, the block seeds from the sampler they leave, the gather on
+    reference-order streams.  radius: the reference's constant unless given."""
+
+    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, primitives="bre", radius=PHOTON_RADIUS_DEFAULT, device=0, options=None):
+        if primitives != "bre":
+            raise RustlightError(RL_ERR_UNSUPPORTED, f"vol-primitives: {primitives} is not built (bre only)")
+        self.nb_primitive, self.max_depth, self.rr_depth, self.radius = nb_primitive, max_depth, rr_depth, radius
+        self.device = device
+        self.options = dict(options or {})
+        self.last_stats = None
+        self.last_generation_stats = None
+        self._ctx = None
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        if self._ctx is None or self._ctx.scene is not scene:
+            self._ctx = Context(scene, self.device)
+            for k, v in self.options.items():
+                self._ctx.set_option(k, v)
+        vpls, self.last_generation_stats = self._ctx.vpl_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, VPL_VOLUME)
+        photons = None
+        try:
+            photons = self._ctx.photon_map(vpls, self.radius)
+            w, h = scene.size
+            seeds = sampler.block_seeds(w, h)
+            img, self.last_stats = self._ctx.render_bre(photons, seeds, nb_samples, sampler.variant)
+        finally:
+            if photons is not None:
+                photons.close()
+            vpls.close()
+        return img
 
 
 class IntegratorVPL:

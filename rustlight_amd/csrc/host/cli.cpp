@@ -8,6 +8,10 @@
 //               | light-tracing [-m MAX|inf] [-n MIN] [-r RR|inf] [-s all|surface|volume]   (examples/cli.rs:54-61, 170-174; per-sample streams)
 //               | vpl [-m MAX|inf] [-r RR|inf] [-b CLAMP] [--nb-vpl N] [-l all|surface|volume] [-v all|surface|volume]   (examples/cli.rs:176-184, 707-733;
 //                 -b is accepted and ignored as the reference ignores clamping_factor; -n is refused: the reference declares it twice under `vpl`)
+//               | vol-primitivies [-m MAX|inf] [-n MIN] [-r RR|inf] [--nb-primitive N] [-p bre] [--radius R]   (examples/cli.rs:189-196, 692-716; sic, `vol-primitives`
+//                 is accepted too.  -p defaults to bre: the reference's default "BRE" matches none of its own arms and panics; beam | plane | vrl are not
+//                 built.  -n is min_depth, parsed and ignored as the reference ignores it here — its short form of --nb-primitive clashes with it.  --radius: the
+//                 photon radius, the reference's hard-coded 0.001 unless given)
 // Note `-n` / `-m` / `-r` / `-s` mean spp / medium / sampler / scale before the subcommand and
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 #include <chrono>
@@ -48,11 +52,13 @@ int main(int argc, char** argv) {
     int frames_in_flight = 1;
     std::vector<std::pair<std::string, std::string>> options;
     std::string nb_vpl = "128", option_lt = "all", option_vpl = "all";     // vpl (cli.rs:176-184)
+    std::string nb_primitive = "128", primitives = "bre", radius = "0.001";     // vol-primitivies (cli.rs:189-196)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
         if (!have_cmd) {
             if (a == "path" || a == "ao" || a == "direct" || a == "light-tracing" || a == "vpl") { have_cmd = true; cmd = a; }
+            else if (a == "vol-primitivies" || a == "vol-primitives") { have_cmd = true; cmd = "vol-primitivies"; }
             else if (a == "-n" || a == "--nbsamples") nbsamples = std::strtoull(val().c_str(), nullptr, 10);
             else if (a == "-o" || a == "--output") output = val();
             else if (a == "-r" || a == "--random-number-generator") rng = val();
@@ -82,7 +88,7 @@ int main(int argc, char** argv) {
             else if (a == "-l" || a == "--log") (void)val();   // log file: nothing is logged on this path
             else if (a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
             else if (scene_path.empty()) scene_path = a;
-            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing` and `vpl` subcommands are provided (got %s)\n", a.c_str()); return 2; }
+            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl` and `vol-primitivies` subcommands are provided (got %s)\n", a.c_str()); return 2; }
         } else if (cmd == "ao") {
             if (a == "-d" || a == "--distance") ao_distance = val();
             else if (a == "-n" || a == "--normal-correction") ao_normal_correction = true;
@@ -100,6 +106,14 @@ int main(int argc, char** argv) {
             else if (a == "-v" || a == "--option-vpl") option_vpl = val();
             else if (a == "-n") { std::fprintf(stderr, "vpl: -n is ambiguous in the reference (min_depth and nb_vpl share it); use --nb-vpl N\n"); return 2; }
             else { std::fprintf(stderr, "unknown vpl option %s\n", a.c_str()); return 2; }
+        } else if (cmd == "vol-primitivies") {
+            if (a == "-m" || a == "--max-depth") max_depth = val();
+            else if (a == "-n" || a == "--min-depth") (void)val();          // `_min_depth` (cli.rs:697): never read
+            else if (a == "-r" || a == "--rr-depth") rr_depth = val();
+            else if (a == "--nb-primitive") nb_primitive = val();
+            else if (a == "-p" || a == "--primitives") primitives = val();
+            else if (a == "--radius") radius = val();
+            else { std::fprintf(stderr, "unknown vol-primitivies option %s\n", a.c_str()); return 2; }
         } else if (cmd == "light-tracing") {
             if (a == "-m" || a == "--max-depth") max_depth = val();
             else if (a == "-n" || a == "--min-depth") min_depth = val();
@@ -159,6 +173,28 @@ int main(int argc, char** argv) {
         vpl.rr_depth = match_infinity(rr_depth);
         vpl.device = device;
         vpl.options = options;
+    }
+    // vol-primitivies: the same limits as vpl; the primitives that are not built are refused here
+    IntegratorVolPrimitives volp;
+    if (cmd == "vol-primitivies") {
+        if (primitives == "beam" || primitives == "plane" || primitives == "vrl") { std::fprintf(stderr, "vol-primitivies: -p %s is not built (bre only)\n", primitives.c_str()); return 2; }
+        if (primitives != "bre") { std::fprintf(stderr, "%s is not a correct primitive (bre, beam, plane, vrl)\n", primitives.c_str()); return 2; }
+        if (rng == "stratified" || rng.rfind("stratified:", 0) == 0) { std::fprintf(stderr, "vol-primitivies: -r stratified is not supported (independent[:SEED] only)\n"); return 2; }
+        if (mode_given && mode != RL_STREAM_REFERENCE_ORDER) { std::fprintf(stderr, "vol-primitivies: --stream-mode per-sample is not supported (the gather uses reference-order streams)\n"); return 2; }
+        if (numerics == RL_NUMERICS_FAST) { std::fprintf(stderr, "vol-primitivies: --numerics fast is not supported\n"); return 2; }
+        if (gpus > 1) { std::fprintf(stderr, "vol-primitivies: --gpus > 1 is not supported\n"); return 2; }
+        if (!average.empty() || !equal_time.empty()) { std::fprintf(stderr, "vol-primitivies: -a / -e are not supported\n"); return 2; }
+        if (frames_in_flight > 1) { std::fprintf(stderr, "vol-primitivies: --frames-in-flight is not supported\n"); return 2; }
+        char* end = nullptr;
+        const unsigned long long n = std::strtoull(nb_primitive.c_str(), &end, 10);
+        if (nb_primitive.empty() || *end != '\0' || n == 0 || n > (unsigned long long)RL_VPL_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", nb_primitive.c_str(), (int)RL_VPL_MAX); return 2; }
+        volp.nb_primitive = (uint32_t)n;
+        volp.radius = std::strtof(radius.c_str(), &end);
+        if (radius.empty() || *end != '\0' || !(volp.radius > 0.0f) || volp.radius > 3.0e38f) { std::fprintf(stderr, "invalid --radius: %s (a finite number > 0)\n", radius.c_str()); return 2; }
+        volp.max_depth = match_infinity(max_depth);
+        volp.rr_depth = match_infinity(rr_depth);
+        volp.device = device;
+        volp.options = options;
     }
     // the sampler (cli.rs:876-896): the master sampler that draws the block seeds is IndependentSampler(SEED) for both kinds — OS entropy without a seed, as
     // IndependentSampler::default() / StratifiedSampler's random() are; `stratified:SEED` is this drop-in's reproducible form.  stratified =
@@ -220,7 +256,7 @@ int main(int argc, char** argv) {
         }
         scene->build_emitters(use_ats);      // scene.build_emitters(use_ats) (cli.rs:432)
         IntegratorPathTracing integrator;
-        if (cmd == "light-tracing" || cmd == "vpl") strategy = "all";       // (the path integrator below is not used)
+        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies") strategy = "all";       // (the path integrator below is not used)
         integrator.min_depth = match_infinity(min_depth);
         integrator.max_depth = match_infinity(max_depth);
         integrator.rr_depth = match_infinity(rr_depth);
@@ -249,6 +285,8 @@ int main(int argc, char** argv) {
             img = di.compute(sampler, *scene); elapsed_ms = di.last_stats.render_ms;
         } else if (cmd == "vpl") {
             img = vpl.compute(sampler, *scene); elapsed_ms = vpl.last_stats.render_ms;
+        } else if (cmd == "vol-primitivies") {
+            img = volp.compute(sampler, *scene); elapsed_ms = volp.last_stats.render_ms;
         } else if (cmd == "light-tracing") {
             if (!equal_time.empty()) {
                 IntegratorEqualTime<IntegratorLightTracing> eq{light, std::strtod(equal_time.c_str(), nullptr) * 1000.0};

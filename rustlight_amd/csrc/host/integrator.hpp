@@ -326,6 +326,53 @@ struct IntegratorVPL {
     }
 };
 
+// struct IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives } (src/integrators/explicit/vol_primitives.rs:12-24) + Integrator::compute
+// for the beam radiance estimate, seed for seed the reference: the photons from the main sampler (rl_vpl_generate with RL_VPL_VOLUME: the records convert_photons
+// stores), the photon tree (rl_photon_map_build), the block seeds from the sampler the generation leaves, the gather on reference-order streams (rl_render_bre).
+// Beams, Planes and VRL are not built.  radius: the reference hard-codes 0.001 (vol_primitives.rs:618).
+enum class VolPrimitivies { BRE, Beams, Planes, VRL };
+struct IntegratorVolPrimitives {
+    uint32_t nb_primitive = 128;
+    std::optional<uint32_t> max_depth, rr_depth = 0u;
+    VolPrimitivies primitives = VolPrimitivies::BRE;
+    float radius = RL_PHOTON_RADIUS_DEFAULT;
+    int device = 0;
+    std::vector<std::pair<std::string, std::string>> options;
+    rl_render_stats last_stats{}, last_generation_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        if (primitives != VolPrimitivies::BRE) throw std::runtime_error("vol-primitives: only the beam radiance estimate (bre) is built");
+        rl_context* ctx = nullptr;
+        int rc = rl_context_create(scene.handle, device, &ctx);
+        if (rc != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
+        for (const auto& o : options)
+            if (rl_context_set_option(ctx, o.first.c_str(), o.second.c_str()) != RL_OK) { const std::string e = rl_last_error(); rl_context_destroy(ctx); throw std::runtime_error("--option " + o.first + ": " + e); }
+        BufferCollection img;
+        rl_scene_image_size(scene.handle, &img.width, &img.height);
+        img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
+        rl_path_params p;
+        rl_path_params_default(&p);
+        p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
+        p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
+        p.stream_mode = RL_STREAM_REFERENCE_ORDER;
+        p.seed_variant = sampler.variant;
+        rl_vpl_set* photons = nullptr;
+        rl_photon_map* map = nullptr;
+        rc = rl_vpl_generate(ctx, &p, nb_primitive, RL_VPL_VOLUME, &sampler.rnd, &photons, &last_generation_stats);
+        if (rc == RL_OK) rc = rl_photon_map_build(ctx, photons, radius, &map);
+        if (rc == RL_OK) {
+            std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
+            rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
+            rc = rl_render_bre(ctx, map, (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), img.primal.data(), &last_stats);
+        }
+        const std::string err = rc == RL_OK ? std::string() : std::string(rl_last_error());
+        rl_photon_map_destroy(map);
+        rl_vpl_destroy(photons);
+        rl_context_destroy(ctx);
+        if (rc != RL_OK) throw std::runtime_error("vol-primitives: " + err);
+        return img;
+    }
+};
+
 // IntegratorAverage (src/integrators/avg.rs:5-131) and IntegratorEqualTime (src/integrators/equal_time.rs:4-66):
 // host loops around any inner integrator with `compute(IndependentSampler&, Scene&)`.
 template <class T, class = void> struct has_frames_in_flight : std::false_type {};

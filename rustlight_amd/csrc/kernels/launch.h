@@ -1,5 +1,5 @@
 // launch.h — host-side launchers of the kernel families that live in their own translation units (fused_*.hip, fusedq_*.hip, fused_strat_*.hip,
-// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip), so that the families compile in parallel, and
+// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, bre_*.hip), so that the families compile in parallel, and
 // the dispatcher every one of them maps its run-time arguments to template arguments with (with_bsdf, with_flag).  Launch errors are picked up by
 // the caller's hipGetLastError().
 #pragma once
@@ -68,6 +68,18 @@ struct VplConst {
     float* acc;                         // [pixel item][3] the pixel's sum over the samples so far
 };
 
+// The beam radiance estimate (bre.hip.h): the photon tree in visiting order and the photons in leaf order (host/photontree.cpp), the kernel's constants
+enum { STAT_BRE_NODES = 5, STAT_BRE_PHOTONS = 6,           // its statistics rows: photon-tree nodes entered, photons gathered — bits 0..23 of each lane's count ...
+       STAT_BRE_NODES_HI = 1, STAT_BRE_PHOTONS_HI = 3 };   // ... and the bits from 24 up, in the rows of STAT_VERTICES / STAT_SHADOW_RAYS, which the estimate leaves empty
+struct BreConst {
+    const float4* nodes;                // [n_nodes][2]: p_min.xyz, p_max.x | p_max.yz, skip, first << 3 | count
+    const float4* photons;              // [n_photons][3]: pos | radiance | d_in
+    unsigned n_nodes;
+    float radius2;                      // radius * radius (radius.powi(2))
+    float kernel;                       // 1 / (PI * radius^2)
+    float norm_photon;                  // 1 / paths shot
+};
+
 // mat: the scene's one BSDF type, or -1 = run-time switch per vertex.  area_only: every emitter is a mesh area light and there is no light
 // tree (the NEE code of the other emitter kinds is compiled out: same results, 84 -> 21 spilled VGPRs on the diffuse Cornell box)
 void launch_fused_lds(int mat, bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc);
@@ -107,6 +119,9 @@ void launch_light_resolve(dim3 grid, dim3 block, hipStream_t st, const RenderCon
 void launch_vpl_lds(int which, int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VplConst& vc);
 void launch_vpl_stream(int which, int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VplConst& vc);
 void launch_vpl_resolve(dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const VplConst& vc);
+// IntegratorVolPrimitives' beam radiance estimate (bre.hip.h): k_bre_gather over the owned blocks; hg: the medium's phase function is Henyey-Greenstein
+void launch_bre_lds(bool hg, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BreConst& bc);
+void launch_bre_stream(bool hg, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BreConst& bc);
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)
 void dump_stage_timers_stream();
 void dump_chain_timers_lds();      // dev-only (-DRL_STAGE_TIMERS): cycle shares of k_stream_chain's stages

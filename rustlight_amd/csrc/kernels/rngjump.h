@@ -49,7 +49,7 @@ static __constant__ unsigned long long c_rng_jump[32][4] = {
 };
 
 // one application of a table entry: 256 state steps, the states at the polynomial's set bits XORed together
-static __device__ __noinline__ void rng_jump(Rng& r, int b) {
+RL_DEV void rng_jump_steps(Rng& r, int b) {
     unsigned long long a0 = 0ull, a1 = 0ull, a2 = 0ull, a3 = 0ull;
 #pragma unroll 1
     for (int w = 0; w < 4; w++) {
@@ -64,11 +64,14 @@ static __device__ __noinline__ void rng_jump(Rng& r, int b) {
     }
     r.s0 = a0; r.s1 = a1; r.s2 = a2; r.s3 = a3;
 }
-// the sampler after n more draws (n may differ per lane: lanes whose bit b is clear wait while the others apply entry b)
+static __device__ __noinline__ void rng_jump(Rng& r, int b) { rng_jump_steps(r, b); }
+// the sampler after n more draws (n may differ per lane: lanes whose bit b is clear wait while the others apply entry b).  CALL = false puts the table
+// step in line: a kernel that calls rng_jump gets a private segment for the call's frame, which k_bre_gather (bre.hip.h) is held not to have.
+template <bool CALL = true>
 RL_DEV void rng_advance(Rng& r, unsigned n) {
     for (unsigned k = n & 255u; k > 0u; k--) rng_next_u64(r);
     for (int b = 8; b < 32 && (n >> b) != 0u; b++)
-        if ((n >> b) & 1u) rng_jump(r, b);
+        if ((n >> b) & 1u) { if (CALL) rng_jump(r, b); else rng_jump_steps(r, b); }
 }
 
 }  // namespace rl

@@ -42,6 +42,7 @@
 #include "common.hip.h"
 #include "rngjump.h"
 #include "../host/hip_buffer.h"
+#include "../host/photontree.h"
 #include "../host/scene.h"
 #include "wavefront.h"
 #include "knobs.h"
@@ -1128,6 +1129,120 @@ extern "C" int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_pa
                 if (hipEventElapsedTime(&t, ctx->events[2 * s + 1], end) == hipSuccess) gather += t;
             }
             stats->ms_raygen = raygen; stats->ms_other = gather;
+            (void)hipGetLastError();
+        }
+    }
+    return RL_OK;
+}
+
+// ---- IntegratorVolPrimitives' beam radiance estimate (vol_primitives.rs:568-805): the photons are the records of an rl_vpl_generate(RL_VPL_VOLUME) set
+// (convert_photons stores what convert_vpl stores under `-v volume`, from the same light paths, and stops on the same count); rl_photon_map_build sorts them into
+// the photon tree on the host (host/photontree.cpp) and uploads tree and photons, rl_render_bre gathers them along every camera ray (k_bre_gather, bre.hip.h)
+struct rl_photon_map {
+    const rl_context* ctx;            // the context that made it (compared, never dereferenced)
+    int device;
+    HipBuffer<float4> nodes;          // [n_nodes][2]
+    HipBuffer<float4> photons;        // [n_photons][3], in leaf order
+    uint64_t n_photons = 0, n_nodes = 0, n_paths = 0;
+    float radius = 0.0f;
+};
+static int check_bre_scene(const rl_context* ctx) {
+    if (ctx->ds.medium.enabled == 0) { rl_set_error("the beam radiance estimate needs a medium (add -m; the reference panics, vol_primitives.rs:575)"); return RL_ERR_UNSUPPORTED; }
+    return RL_OK;
+}
+extern "C" int rl_photon_map_build(rl_context* ctx, const rl_vpl_set* set, float radius, rl_photon_map** out) {
+    if (!ctx || !set || !out) return RL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    int rcode;
+    if ((rcode = check_bre_scene(ctx)) != RL_OK) return rcode;
+    if (set->ctx != ctx) { rl_set_error("the VPL set belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
+    if (!std::isfinite(radius) || !(radius > 0.0f)) { rl_set_error("the photon radius must be finite and > 0"); return RL_ERR_INVALID_ARGUMENT; }
+    HIP_OK(hipSetDevice(ctx->device));
+    std::vector<uint32_t> words((size_t)set->n_vpl * RL_VPL_WORDS);
+    HIP_OK(hipMemcpy(words.data(), set->words.get(), words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < set->n_vpl; i++)
+        if (words[i * RL_VPL_WORDS] != (uint32_t)RL_VPL_KIND_VOLUME) { rl_set_error("a photon map takes volume records only: generate the set with RL_VPL_VOLUME"); return RL_ERR_INVALID_ARGUMENT; }
+    PhotonTree tree;
+    if ((rcode = build_photon_tree(words.data(), set->n_vpl, radius, &tree)) != RL_OK) return rcode;
+    const size_t n_nodes = tree.n_nodes();
+    std::vector<float4> h_nodes(2 * n_nodes), h_photons(3 * (size_t)set->n_vpl);
+    for (size_t i = 0; i < n_nodes; i++) {
+        const float* b = &tree.boxes[6 * i];
+        const uint32_t skip = tree.links[3 * i], fc = tree.links[3 * i + 1] << 3 | tree.links[3 * i + 2];
+        float fs, ff;
+        std::memcpy(&fs, &skip, sizeof fs); std::memcpy(&ff, &fc, sizeof ff);
+        h_nodes[2 * i] = make_float4(b[0], b[1], b[2], b[3]);
+        h_nodes[2 * i + 1] = make_float4(b[4], b[5], fs, ff);
+    }
+    for (size_t i = 0; i < set->n_vpl; i++) {
+        float f[9];
+        std::memcpy(f, &words[(size_t)tree.order[i] * RL_VPL_WORDS + 4], sizeof f);     // pos, radiance, d_in
+        h_photons[3 * i] = make_float4(f[0], f[1], f[2], 0.0f);
+        h_photons[3 * i + 1] = make_float4(f[3], f[4], f[5], 0.0f);
+        h_photons[3 * i + 2] = make_float4(f[6], f[7], f[8], 0.0f);
+    }
+    auto map = std::make_unique<rl_photon_map>();
+    map->ctx = ctx; map->device = ctx->device;
+    if ((rcode = map->nodes.ensure(h_nodes.size())) != RL_OK || (rcode = map->photons.ensure(h_photons.size())) != RL_OK) return rcode;
+    HIP_OK(hipMemcpy(map->nodes.get(), h_nodes.data(), h_nodes.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(map->photons.get(), h_photons.data(), h_photons.size() * sizeof(float4), hipMemcpyHostToDevice));
+    map->n_photons = set->n_vpl; map->n_nodes = n_nodes; map->n_paths = set->n_paths; map->radius = radius;
+    *out = map.release();
+    return RL_OK;
+}
+extern "C" int rl_photon_map_info(const rl_photon_map* map, uint64_t* n_photons, uint64_t* n_nodes, uint64_t* n_paths, float* radius) {
+    if (!map) return RL_ERR_INVALID_ARGUMENT;
+    if (n_photons) *n_photons = map->n_photons;
+    if (n_nodes) *n_nodes = map->n_nodes;
+    if (n_paths) *n_paths = map->n_paths;
+    if (radius) *radius = map->radius;
+    return RL_OK;
+}
+extern "C" void rl_photon_map_destroy(rl_photon_map* map) {
+    if (!map) return;
+    (void)hipSetDevice(map->device);
+    delete map;
+}
+namespace { struct BreFrameParams { uint32_t spp; }; }      // what check_frame reads
+extern "C" int rl_render_bre(rl_context* ctx, const rl_photon_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
+                             const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats) {
+    int rcode;
+    if (!map) return RL_ERR_INVALID_ARGUMENT;
+    const BreFrameParams fp{spp};
+    if ((rcode = check_frame(ctx, &fp, block_seeds, n_blocks, out_rgb)) != RL_OK) return rcode;
+    if ((rcode = check_bre_scene(ctx)) != RL_OK) return rcode;
+    if (map->ctx != ctx) { rl_set_error("the photon map belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
+    if (shard_index >= (shard_count ? shard_count : 1)) return RL_ERR_INVALID_ARGUMENT;
+    if (spp > (uint32_t)RL_VPL_MAX_SPP) { rl_set_error("bre takes at most RL_VPL_MAX_SPP spp (a block's stream is entered with 32-bit jumps, 2 draws per sample)"); return RL_ERR_UNSUPPORTED; }
+    HIP_OK(hipSetDevice(ctx->device));
+    RenderFrame fr(ctx, block_seeds, n_blocks, out_rgb, 0, nullptr, stats, shard_index, shard_count);
+    const unsigned n_owned = (unsigned)fr.owned.size();
+    if ((rcode = fr.alloc_tables()) != RL_OK || (rcode = fr.alloc_output(std::max(n_owned, 1u))) != RL_OK) return rcode;
+    if ((rcode = fr.upload(false, true)) != RL_OK || (rcode = fr.zero_rows()) != RL_OK) return rcode;
+    RenderConst rc = fr.render_const(spp, RL_STREAM_REFERENCE_ORDER, seed_variant);
+    rc.n_items = fr.n_pixels;
+    BreConst bc{};
+    bc.nodes = map->nodes.get(); bc.photons = map->photons.get(); bc.n_nodes = (unsigned)map->n_nodes;
+    bc.radius2 = map->radius * map->radius;                                 // self.radius * self.radius
+    bc.kernel = 1.0f / (3.14159265358979323846f * (map->radius * map->radius));       // 1.0 / (PI * self.radius.powi(2))
+    bc.norm_photon = 1.0f / (float)map->n_paths;                            // 1.0 / nb_path_shot as f32 (vol_primitives.rs:707)
+    StackConf stc;
+    if ((rcode = stack_conf(ctx, std::max(n_owned, 1u) * 256u, &stc)) != RL_OK) return rcode;
+    const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
+    const hipStream_t st = fr.st;
+    if ((rcode = fr.grow_events(2)) != RL_OK) return rcode;
+    if (fr.timing) hipEventRecord(ctx->events[0], st);
+    if (n_owned > 0) (ctx->lds_scene ? launch_bre_lds : launch_bre_stream)(ctx->ds.medium.phase != 0, dim3(n_owned), dim3(256), lds, st, rc, ctx->ds, stc, bc);
+    if (fr.timing) hipEventRecord(ctx->events[1], st);
+    if ((rcode = fr.download()) != RL_OK) return rcode;
+    if (stats) {
+        stats->vertices = 0; stats->shadow_rays = 0;      // (their rows carried the high parts of the two tree counters)
+        stats->reserved[0] = fr.totals[STAT_BRE_NODES] + (fr.totals[STAT_BRE_NODES_HI] << 24);
+        stats->reserved[1] = fr.totals[STAT_BRE_PHOTONS] + (fr.totals[STAT_BRE_PHOTONS_HI] << 24);
+        stats->iterations = 1; stats->kernel_launches = n_owned > 0 ? 1 : 0;
+        if (fr.timing) {
+            float t = 0.0f;
+            if (hipEventElapsedTime(&t, ctx->events[0], ctx->events[1]) == hipSuccess) stats->ms_other = t;
             (void)hipGetLastError();
         }
     }
