@@ -31,6 +31,7 @@
  *   state_budget_mb = n       MB the recorded sampler states of the two-pass form may take (default 24 GB): small values force several chunks
  *   fused_dynamic = 0|1       persistent kernel: static tile order / work items from the atomic dispenser
  *   no_events = 1             no HIP events around the kernels (rl_render_stats.ms_* stay 0)
+ *   vpl_batch_paths = n       rl_vpl_generate_paths: every batch of a generation holds n light paths (default: sized from the records per path measured so far)
  * rl_multi_* reads RL_MULTI_FORCE_HOST_MERGE=1, RL_MULTI_NO_FALLBACK=1, RL_MULTI_REDUCE_TIMEOUT_S=s when the communicator is built / a reduce runs: see rl_multi_describe.
  */
 #ifndef RUSTLIGHT_AMD_H
@@ -390,6 +391,25 @@ enum { RL_VPL_WORDS = 24, RL_VPL_MAX = 1 << 20, RL_VPL_MAX_PATHS = 1 << 18, RL_V
 typedef struct rl_vpl_set rl_vpl_set;       /* opaque: the VPLs of one generation, on the context's device */
 int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, rl_sampler* sampler, rl_vpl_set** out,
                     rl_render_stats* stats);
+/* rl_vpl_generate_paths: the generation with one light path per device lane, each on its own sampler stream — an opt-in, as RL_STREAM_PER_SAMPLE is for the
+ * camera passes; rl_vpl_generate stays the drop-in default.  Statistically, not seed-for-seed, the same image as the serial mode's.  The stream contract:
+ *   - light path k = 0, 1, 2, .. draws from the sampler the k-th clone_box() call on the main sampler returns (src/samplers/independent.rs:18-22): seed_k is the
+ *     k-th next_u64() of `sampler` counted from its incoming state, the path's stream is rl_sampler_seed(seed_k, params->seed_variant);
+ *   - inside its stream a path draws exactly what a path of rl_vpl_generate draws (kernels/light.hip.h lists the order);
+ *   - the set holds paths 0 .. K-1, K the smallest count at which at least nb_vpl records are stored: the reference's `while stored < nb` on this path
+ *     sequence (all of the last path's records are kept); n_paths = K;
+ *   - records stand in path order, and in vertex order within a path; record layout and option_vpl filter are rl_vpl_generate's;
+ *   - `sampler` leaves advanced by exactly K next_u64(); the block seeds are then drawn from it as after rl_vpl_generate;
+ *   - paths walked speculatively beyond K leave no trace in the records, the counters or the sampler;
+ *   - nothing in the result depends on batch size, launch geometry, lane assignment or run: the same incoming state gives the same bits.
+ * Of rl_path_params it reads max_depth, rr_depth and seed_variant; stream_mode is not read (it is about the gather).  Refuses what rl_vpl_generate refuses, with the
+ * same codes, and returns RL_ERR_UNSUPPORTED when RL_VPL_MAX_PATHS paths store fewer than nb_vpl records.  The set is an ordinary rl_vpl_set: rl_vpl_info,
+ * rl_vpl_read, rl_render_vpl and rl_photon_map_build take it unchanged.  It runs in rounds: a count pass walks a batch of paths and stores four counts per path,
+ * the host takes the prefix sum and looks for K, a further batch follows when the first did not reach nb_vpl, and a write pass walks paths 0 .. K-1 again, each
+ * to its own offset.  Counters: camera_samples = K; vertices, extension_rays, rng_draws = sums over the K kept paths (the K fork draws are not counted);
+ * iterations = rounds; kernel_launches; ms_prepass = the summed kernel time; reserved[0] = paths walked in the count passes, discarded ones included. */
+int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, rl_sampler* sampler, rl_vpl_set** out,
+                          rl_render_stats* stats);
 int rl_vpl_info(const rl_vpl_set* set, uint64_t* n_vpl, uint64_t* n_paths);
 int rl_vpl_read(const rl_vpl_set* set, uint32_t* words, size_t n_words);
 void rl_vpl_destroy(rl_vpl_set* set);

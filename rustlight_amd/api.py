@@ -28,6 +28,7 @@ PIPELINE_AUTO, PIPELINE_WAVEFRONT, PIPELINE_FUSED = 0, 1, 2
 NUMERICS_EXACT, NUMERICS_FAST = 0, 1
 LIGHT_ALL, LIGHT_SURFACE, LIGHT_VOLUME = 0, 1, 2          # rl_light_strategy: `light-tracing -s all|surface|volume`
 VPL_ALL, VPL_SURFACE, VPL_VOLUME = 0, 1, 2                # rl_vpl_option: `vpl -v / -l all|surface|volume`
+LIGHT_STREAMS = ("reference", "per_path")                 # how the light paths of vpl / vol-primitivies draw: rl_vpl_generate | rl_vpl_generate_paths
 VPL_WORDS = 24                                            # RL_VPL_WORDS: u32 per VPL record (rl_vpl_read)
 PHOTON_RADIUS_DEFAULT = 0.001                             # RL_PHOTON_RADIUS_DEFAULT: the radius the reference hard-codes (vol_primitives.rs:618)
 RL_ERR_UNSUPPORTED, RL_ERR_NO_EMITTER = -7, -8
@@ -39,7 +40,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -110,6 +111,7 @@ def lib():
     L.rl_render_path_frames.argtypes = [C.POINTER(vp), C.c_size_t, C.POINTER(abi.PathParams), C.POINTER(u64p), C.c_size_t, C.c_size_t, C.POINTER(C.POINTER(C.c_float)), C.POINTER(abi.RenderStats)]
     L.rl_render_light.argtypes = [vp, C.POINTER(abi.PathParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_vpl_generate.argtypes = [vp, C.POINTER(abi.PathParams), C.c_uint32, C.c_int, C.POINTER(abi.Sampler), C.POINTER(vp), C.POINTER(abi.RenderStats)]
+    L.rl_vpl_generate_paths.argtypes = L.rl_vpl_generate.argtypes
     L.rl_vpl_info.argtypes = [vp, u64p, u64p]
     L.rl_vpl_read.argtypes = [vp, u32p, C.c_size_t]
     L.rl_vpl_destroy.argtypes = [vp]
@@ -488,14 +490,23 @@ class Context:
         d["splats"], d["splats_invalid"], d["splats_saturated"] = (int(v) for v in st.reserved[:3])
         return img, d
 
-    def vpl_generate(self, sampler: "IndependentSampler", nb_vpl=128, max_depth=None, rr_depth=0, option_vpl=VPL_ALL):
-        """IntegratorVPL's generation (vpl.rs:182-210) through rl_vpl_generate: (VplSet, stats dict).  `sampler` is advanced as the reference's main sampler is.
-        stats: camera_samples = light paths shot, vertices, extension_rays, rng_draws, ms_prepass = the generation kernel's time."""
-        p = path_params(1, 0, max_depth, rr_depth, stream_mode=STREAM_REFERENCE_ORDER)
+    def vpl_generate(self, sampler: "IndependentSampler", nb_vpl=128, max_depth=None, rr_depth=0, option_vpl=VPL_ALL, streams="reference"):
+        """IntegratorVPL's generation (vpl.rs:182-210): (VplSet, stats dict).  streams="reference": rl_vpl_generate, one lane on the main sampler's serial stream,
+        seed for seed the reference; `sampler` is advanced as the reference's main sampler is.  streams="per_path": rl_vpl_generate_paths, one light path per lane
+        on the stream of the k-th clone_box of `sampler` (include/rustlight_amd.h has the contract): statistically, not seed-for-seed, the
+        same image; `sampler` is advanced by one next_u64 per kept path.  stats: camera_samples = light paths shot (kept), vertices, extension_rays, rng_draws,
+        ms_prepass = the generation kernels' time; per_path adds iterations = rounds and paths_walked = reserved[0]."""
+        if streams not in LIGHT_STREAMS:
+            raise ValueError(f"streams must be one of {LIGHT_STREAMS}, not {streams!r}")
+        p = path_params(1, 0, max_depth, rr_depth, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=sampler.variant)
         st = abi.RenderStats()
         h = C.c_void_p()
-        _check(lib().rl_vpl_generate(self.h, C.byref(p), nb_vpl, option_vpl, C.byref(sampler.s), C.byref(h), C.byref(st)))
-        return VplSet(h, self), st.as_dict()
+        fn = lib().rl_vpl_generate if streams == "reference" else lib().rl_vpl_generate_paths
+        _check(fn(self.h, C.byref(p), nb_vpl, option_vpl, C.byref(sampler.s), C.byref(h), C.byref(st)))
+        d = st.as_dict()
+        if streams == "per_path":
+            d["paths_walked"] = int(st.reserved[0])
+        return VplSet(h, self), d
 
     def render_vpl(self, vpls: "VplSet", seeds, spp=1, option_lt=VPL_ALL, seed_variant=0, shard_index=0, shard_count=1, stream_mode=STREAM_REFERENCE_ORDER,
                    numerics=NUMERICS_EXACT):
@@ -805,11 +816,15 @@ def photon_tree_build(words, radius):
 class IntegratorVolPrimitives:
     """struct IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute for
     primitives = BRE, seed for seed the reference: the photons from the main sampler, the block seeds from the sampler they leave, the gather on
-    reference-order streams.  radius: the reference's constant unless given."""
+    reference-order streams.  radius: the reference's constant unless given.  light_streams="per_path": the photons from rl_vpl_generate_paths (one light path
+    per lane, each on its own stream): statistically, not seed-for-seed, the same image."""
 
-    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, primitives="bre", radius=PHOTON_RADIUS_DEFAULT, device=0, options=None):
+    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, primitives="bre", radius=PHOTON_RADIUS_DEFAULT, device=0, options=None, light_streams="reference"):
         if primitives != "bre":
             raise RustlightError(RL_ERR_UNSUPPORTED, f"vol-primitives: {primitives} is not built (bre only)")
+        if light_streams not in LIGHT_STREAMS:
+            raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
+        self.light_streams = light_streams
         self.nb_primitive, self.max_depth, self.rr_depth, self.radius = nb_primitive, max_depth, rr_depth, radius
         self.device = device
         self.options = dict(options or {})
@@ -822,7 +837,7 @@ class IntegratorVolPrimitives:
             self._ctx = Context(scene, self.device)
             for k, v in self.options.items():
                 self._ctx.set_option(k, v)
-        vpls, self.last_generation_stats = self._ctx.vpl_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, VPL_VOLUME)
+        vpls, self.last_generation_stats = self._ctx.vpl_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, VPL_VOLUME, self.light_streams)
         photons = None
         try:
             photons = self._ctx.photon_map(vpls, self.radius)
@@ -838,9 +853,13 @@ class IntegratorVolPrimitives:
 
 class IntegratorVPL:
     """struct IntegratorVPL (src/integrators/explicit/vpl.rs:16-23) + Integrator::compute, seed for seed the reference: the VPLs from the main sampler, the
-    block seeds from the sampler they leave, the gather on reference-order streams.  clamping_factor is not a field: the reference never reads it."""
+    block seeds from the sampler they leave, the gather on reference-order streams.  clamping_factor is not a field: the reference never reads it.  light_streams="per_path": the VPLs from
+    rl_vpl_generate_paths (one light path per lane, each on its own stream): statistically, not seed-for-seed, the same image."""
 
-    def __init__(self, nb_vpl=128, max_depth=None, rr_depth=0, option_vpl=VPL_ALL, option_lt=VPL_ALL, device=0, options=None):
+    def __init__(self, nb_vpl=128, max_depth=None, rr_depth=0, option_vpl=VPL_ALL, option_lt=VPL_ALL, device=0, options=None, light_streams="reference"):
+        if light_streams not in LIGHT_STREAMS:
+            raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
+        self.light_streams = light_streams
         self.nb_vpl, self.max_depth, self.rr_depth = nb_vpl, max_depth, rr_depth
         self.option_vpl, self.option_lt = option_vpl, option_lt
         self.device = device
@@ -854,7 +873,7 @@ class IntegratorVPL:
             self._ctx = Context(scene, self.device)
             for k, v in self.options.items():
                 self._ctx.set_option(k, v)
-        vpls, self.last_generation_stats = self._ctx.vpl_generate(sampler, self.nb_vpl, self.max_depth, self.rr_depth, self.option_vpl)
+        vpls, self.last_generation_stats = self._ctx.vpl_generate(sampler, self.nb_vpl, self.max_depth, self.rr_depth, self.option_vpl, self.light_streams)
         try:
             w, h = scene.size
             seeds = sampler.block_seeds(w, h)

@@ -6,12 +6,14 @@
 //               | ao [-d DIST|inf] [-n]            (examples/cli.rs:149-154)
 //               | direct [-b NB_BSDF] [-l NB_LIGHT] (examples/cli.rs:155-160)
 //               | light-tracing [-m MAX|inf] [-n MIN] [-r RR|inf] [-s all|surface|volume]   (examples/cli.rs:54-61, 170-174; per-sample streams)
-//               | vpl [-m MAX|inf] [-r RR|inf] [-b CLAMP] [--nb-vpl N] [-l all|surface|volume] [-v all|surface|volume]   (examples/cli.rs:176-184, 707-733;
+//               | vpl [-m MAX|inf] [-r RR|inf] [-b CLAMP] [--nb-vpl N] [-l all|surface|volume] [-v all|surface|volume] [--light-streams reference|per-path]   (examples/cli.rs:176-184, 707-733;
 //                 -b is accepted and ignored as the reference ignores clamping_factor; -n is refused: the reference declares it twice under `vpl`)
-//               | vol-primitivies [-m MAX|inf] [-n MIN] [-r RR|inf] [--nb-primitive N] [-p bre] [--radius R]   (examples/cli.rs:189-196, 692-716; sic, `vol-primitives`
+//               | vol-primitivies [-m MAX|inf] [-n MIN] [-r RR|inf] [--nb-primitive N] [-p bre] [--radius R] [--light-streams reference|per-path]   (examples/cli.rs:189-196, 692-716; sic, `vol-primitives`
 //                 is accepted too.  -p defaults to bre: the reference's default "BRE" matches none of its own arms and panics; beam | plane | vrl are not
 //                 built.  -n is min_depth, parsed and ignored as the reference ignores it here — its short form of --nb-primitive clashes with it.  --radius: the
 //                 photon radius, the reference's hard-coded 0.001 unless given)
+//                 --light-streams (vpl, vol-primitivies): reference = the light paths on the main sampler's serial stream, seed for seed the reference (default);
+//                 per-path = one light path per GPU lane, each on its own stream (rl_vpl_generate_paths): statistically, not seed-for-seed, the same image
 // Note `-n` / `-m` / `-r` / `-s` mean spp / medium / sampler / scale before the subcommand and
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 #include <chrono>
@@ -53,6 +55,7 @@ int main(int argc, char** argv) {
     std::vector<std::pair<std::string, std::string>> options;
     std::string nb_vpl = "128", option_lt = "all", option_vpl = "all";     // vpl (cli.rs:176-184)
     std::string nb_primitive = "128", primitives = "bre", radius = "0.001";     // vol-primitivies (cli.rs:189-196)
+    std::string light_streams = "reference";            // vpl, vol-primitivies: `--light-streams per-path` shoots the light paths in parallel, each on its own stream
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -86,9 +89,12 @@ int main(int argc, char** argv) {
                 else { std::fprintf(stderr, "extra option %s is not supported by this drop-in (ats, no-shading, hvs-light, texture-light)\n", o.c_str()); return 2; }
             }
             else if (a == "-l" || a == "--log") (void)val();   // log file: nothing is logged on this path
+            else if (a == "--light-streams") { std::fprintf(stderr, "--light-streams is an option of the vpl and vol-primitivies subcommands: give it after the subcommand\n"); return 2; }
             else if (a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
             else if (scene_path.empty()) scene_path = a;
             else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl` and `vol-primitivies` subcommands are provided (got %s)\n", a.c_str()); return 2; }
+        } else if (a == "--light-streams" && cmd != "vpl" && cmd != "vol-primitivies") {
+            std::fprintf(stderr, "%s: --light-streams is not supported (vpl and vol-primitivies only)\n", cmd.c_str()); return 2;
         } else if (cmd == "ao") {
             if (a == "-d" || a == "--distance") ao_distance = val();
             else if (a == "-n" || a == "--normal-correction") ao_normal_correction = true;
@@ -104,6 +110,7 @@ int main(int argc, char** argv) {
             else if (a == "--nb-vpl") nb_vpl = val();
             else if (a == "-l" || a == "--option-lt") option_lt = val();
             else if (a == "-v" || a == "--option-vpl") option_vpl = val();
+            else if (a == "--light-streams") light_streams = val();
             else if (a == "-n") { std::fprintf(stderr, "vpl: -n is ambiguous in the reference (min_depth and nb_vpl share it); use --nb-vpl N\n"); return 2; }
             else { std::fprintf(stderr, "unknown vpl option %s\n", a.c_str()); return 2; }
         } else if (cmd == "vol-primitivies") {
@@ -113,6 +120,7 @@ int main(int argc, char** argv) {
             else if (a == "--nb-primitive") nb_primitive = val();
             else if (a == "-p" || a == "--primitives") primitives = val();
             else if (a == "--radius") radius = val();
+            else if (a == "--light-streams") light_streams = val();
             else { std::fprintf(stderr, "unknown vol-primitivies option %s\n", a.c_str()); return 2; }
         } else if (cmd == "light-tracing") {
             if (a == "-m" || a == "--max-depth") max_depth = val();
@@ -150,6 +158,12 @@ int main(int argc, char** argv) {
         light.device = device;
         light.options = options;
     }
+    // vpl, vol-primitivies: how the light paths draw (the gather stays in reference order either way)
+    LightStreams light_streams_mode = LightStreams::Reference;
+    if (cmd == "vpl" || cmd == "vol-primitivies") {
+        if (light_streams == "per-path") light_streams_mode = LightStreams::PerPath;
+        else if (light_streams != "reference") { std::fprintf(stderr, "invalid --light-streams: %s (reference or per-path)\n", light_streams.c_str()); return 2; }
+    }
     // vpl runs on reference-order streams, exact numerics, one device, one pass: what it cannot do is refused here, before a device is opened
     IntegratorVPL vpl;
     if (cmd == "vpl") {
@@ -171,6 +185,7 @@ int main(int argc, char** argv) {
         vpl.nb_vpl = (uint32_t)n;
         vpl.max_depth = match_infinity(max_depth);
         vpl.rr_depth = match_infinity(rr_depth);
+        vpl.light_streams = light_streams_mode;
         vpl.device = device;
         vpl.options = options;
     }
@@ -193,6 +208,7 @@ int main(int argc, char** argv) {
         if (radius.empty() || *end != '\0' || !(volp.radius > 0.0f) || volp.radius > 3.0e38f) { std::fprintf(stderr, "invalid --radius: %s (a finite number > 0)\n", radius.c_str()); return 2; }
         volp.max_depth = match_infinity(max_depth);
         volp.rr_depth = match_infinity(rr_depth);
+        volp.light_streams = light_streams_mode;
         volp.device = device;
         volp.options = options;
     }

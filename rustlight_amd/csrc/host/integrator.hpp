@@ -285,6 +285,10 @@ struct IntegratorLightTracing {
     }
 };
 
+// How the light paths of IntegratorVPL / IntegratorVolPrimitives draw.  Reference: rl_vpl_generate, one lane on the main sampler's serial stream, seed for seed
+// the reference (the default).  PerPath: rl_vpl_generate_paths, one light path per lane on the stream of the k-th clone_box of the main sampler — statistically,
+// not seed-for-seed, the same image (`--light-streams per-path`).  The gather is the same either way.
+enum class LightStreams { Reference, PerPath };
 // struct IntegratorVPL (src/integrators/explicit/vpl.rs:16-23) + Integrator::compute, seed for seed the reference: the VPLs from the main sampler
 // (rl_vpl_generate), the block seeds from the sampler it leaves, the gather on reference-order streams (rl_render_vpl).  clamping_factor is not a
 // field: the reference never reads it.
@@ -292,6 +296,7 @@ struct IntegratorVPL {
     uint32_t nb_vpl = 128;
     std::optional<uint32_t> max_depth, rr_depth = 0u;
     rl_vpl_option option_vpl = RL_VPL_ALL, option_lt = RL_VPL_ALL;
+    LightStreams light_streams = LightStreams::Reference;
     int device = 0;
     std::vector<std::pair<std::string, std::string>> options;
     rl_render_stats last_stats{}, last_generation_stats{};
@@ -312,7 +317,7 @@ struct IntegratorVPL {
         p.stream_mode = RL_STREAM_REFERENCE_ORDER;
         p.seed_variant = sampler.variant;
         rl_vpl_set* vpls = nullptr;
-        rc = rl_vpl_generate(ctx, &p, nb_vpl, option_vpl, &sampler.rnd, &vpls, &last_generation_stats);
+        rc = (light_streams == LightStreams::PerPath ? rl_vpl_generate_paths : rl_vpl_generate)(ctx, &p, nb_vpl, option_vpl, &sampler.rnd, &vpls, &last_generation_stats);
         if (rc == RL_OK) {
             std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
             rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
@@ -336,6 +341,7 @@ struct IntegratorVolPrimitives {
     std::optional<uint32_t> max_depth, rr_depth = 0u;
     VolPrimitivies primitives = VolPrimitivies::BRE;
     float radius = RL_PHOTON_RADIUS_DEFAULT;
+    LightStreams light_streams = LightStreams::Reference;
     int device = 0;
     std::vector<std::pair<std::string, std::string>> options;
     rl_render_stats last_stats{}, last_generation_stats{};
@@ -357,7 +363,7 @@ struct IntegratorVolPrimitives {
         p.seed_variant = sampler.variant;
         rl_vpl_set* photons = nullptr;
         rl_photon_map* map = nullptr;
-        rc = rl_vpl_generate(ctx, &p, nb_primitive, RL_VPL_VOLUME, &sampler.rnd, &photons, &last_generation_stats);
+        rc = (light_streams == LightStreams::PerPath ? rl_vpl_generate_paths : rl_vpl_generate)(ctx, &p, nb_primitive, RL_VPL_VOLUME, &sampler.rnd, &photons, &last_generation_stats);
         if (rc == RL_OK) rc = rl_photon_map_build(ctx, photons, radius, &map);
         if (rc == RL_OK) {
             std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));

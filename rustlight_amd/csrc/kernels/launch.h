@@ -1,5 +1,5 @@
 // launch.h — host-side launchers of the kernel families that live in their own translation units (fused_*.hip, fusedq_*.hip, fused_strat_*.hip,
-// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, bre_*.hip), so that the families compile in parallel, and
+// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip), so that the families compile in parallel, and
 // the dispatcher every one of them maps its run-time arguments to template arguments with (with_bsdf, with_flag).  Launch errors are picked up by
 // the caller's hipGetLastError().
 #pragma once
@@ -68,6 +68,18 @@ struct VplConst {
     float* acc;                         // [pixel item][3] the pixel's sum over the samples so far
 };
 
+// Light-path generation on per-path streams (vpl_paths.hip.h): one round's batch of path indices, the main sampler they fork from, and where the two passes write
+enum { VPL_PATH_RECORDS = 0, VPL_PATH_VERTICES = 1, VPL_PATH_EXT = 2, VPL_PATH_DRAWS = 3, VPL_PATH_WORDS = 4 };
+struct VplPathsConst {
+    unsigned long long main[4];         // the main sampler's incoming state: path k is seeded by its k-th next_u64
+    unsigned first, count;              // this launch walks paths first .. first + count - 1
+    int option_vpl;                     // rl_vpl_option
+    unsigned cap;                       // write pass: records vpl_words holds (records beyond it are not written)
+    unsigned* vpl_words;                // write pass: [cap][kVplWords]
+    const unsigned* offsets;            // write pass: [path] the record index the path's first record gets
+    unsigned* counts;                   // count pass: [path - first][VPL_PATH_WORDS] records kept, vertices, extension rays, draws
+};
+
 // The beam radiance estimate (bre.hip.h): the photon tree in visiting order and the photons in leaf order (host/photontree.cpp), the kernel's constants
 enum { STAT_BRE_NODES = 5, STAT_BRE_PHOTONS = 6,           // its statistics rows: photon-tree nodes entered, photons gathered — bits 0..23 of each lane's count ...
        STAT_BRE_NODES_HI = 1, STAT_BRE_PHOTONS_HI = 3 };   // ... and the bits from 24 up, in the rows of STAT_VERTICES / STAT_SHADOW_RAYS, which the estimate leaves empty
@@ -119,6 +131,9 @@ void launch_light_resolve(dim3 grid, dim3 block, hipStream_t st, const RenderCon
 void launch_vpl_lds(int which, int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VplConst& vc);
 void launch_vpl_stream(int which, int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VplConst& vc);
 void launch_vpl_resolve(dim3 grid, dim3 block, hipStream_t st, const RenderConst& rc, const VplConst& vc);
+// rl_vpl_generate_paths (vpl_paths.hip.h): k_vpl_shoot over a batch of light paths, write = false the count pass, true the write pass (mat as for launch_vpl_*)
+void launch_vpl_paths_lds(bool write, int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VplPathsConst& pc);
+void launch_vpl_paths_stream(bool write, int mat, bool medium, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VplPathsConst& pc);
 // IntegratorVolPrimitives' beam radiance estimate (bre.hip.h): k_bre_gather over the owned blocks; hg: the medium's phase function is Henyey-Greenstein
 void launch_bre_lds(bool hg, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BreConst& bc);
 void launch_bre_stream(bool hg, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BreConst& bc);

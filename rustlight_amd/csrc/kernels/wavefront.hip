@@ -986,8 +986,8 @@ static int check_vpl_scene(const rl_context* ctx) {
     if (ctx->ds.n_emitters == 0) { rl_set_error("vpl needs an emitter"); return RL_ERR_NO_EMITTER; }
     return RL_OK;
 }
-extern "C" int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, rl_sampler* sampler, rl_vpl_set** out,
-                               rl_render_stats* stats) {
+// what both generation entry points refuse before any kernel runs
+static int check_vpl_generate(const rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, const rl_sampler* sampler, rl_vpl_set** out) {
     if (!ctx || !params || !sampler || !out) return RL_ERR_INVALID_ARGUMENT;
     *out = nullptr;
     if (option_vpl < RL_VPL_ALL || option_vpl > RL_VPL_VOLUME) { rl_set_error("option_vpl must be RL_VPL_ALL, RL_VPL_SURFACE or RL_VPL_VOLUME"); return RL_ERR_INVALID_ARGUMENT; }
@@ -1000,6 +1000,13 @@ extern "C" int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, ui
     if (medium) {
         if (ctx->has_directional) { rl_set_error("vpl does not take a directional light with a medium (vpl.rs:324, 418)"); return RL_ERR_UNSUPPORTED; }
     }
+    return RL_OK;
+}
+extern "C" int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, rl_sampler* sampler, rl_vpl_set** out,
+                               rl_render_stats* stats) {
+    int rcode;
+    if ((rcode = check_vpl_generate(ctx, params, nb_vpl, option_vpl, sampler, out)) != RL_OK) return rcode;
+    const bool medium = ctx->ds.medium.enabled != 0;
     HIP_OK(hipSetDevice(ctx->device));
     auto set = std::make_unique<rl_vpl_set>();
     set->ctx = ctx; set->device = ctx->device;
@@ -1039,6 +1046,112 @@ extern "C" int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, ui
         std::memset(stats, 0, sizeof(*stats));
         stats->camera_samples = g[VPL_GEN_PATHS]; stats->vertices = g[VPL_GEN_VERTICES]; stats->extension_rays = g[VPL_GEN_EXT]; stats->rng_draws = g[VPL_GEN_DRAWS];
         stats->iterations = 1; stats->kernel_launches = 1; stats->ms_prepass = ms;
+        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    *out = set.release();
+    return RL_OK;
+}
+// rl_vpl_generate_paths: the same generation with one light path per lane, each on its own stream (vpl_paths.hip.h has the contract).  Rounds: a count pass
+// over a batch of path indices, the counts brought to the host, which takes their prefix sum and looks for K (the smallest path count that stores nb_vpl
+// records); when the batch did not reach it, the next one is sized from the records per path measured so far.  Then one write pass over paths 0 .. K-1.
+static constexpr unsigned kVplFirstBatch = 4096, kVplShootGroupsPerCu = 2;
+extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, rl_sampler* sampler, rl_vpl_set** out,
+                                     rl_render_stats* stats) {
+    int rcode;
+    if ((rcode = check_vpl_generate(ctx, params, nb_vpl, option_vpl, sampler, out)) != RL_OK) return rcode;
+    const bool medium = ctx->ds.medium.enabled != 0;
+    HIP_OK(hipSetDevice(ctx->device));
+    auto set = std::make_unique<rl_vpl_set>();
+    set->ctx = ctx; set->device = ctx->device;
+    const hipStream_t st = ctx->stream;
+    const long long forced = ctx->knobs.has(K_VPL_BATCH_PATHS) ? std::max<long long>(1, ctx->knobs.i(K_VPL_BATCH_PATHS, 0)) : 0;
+    int cus = 256;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) { (void)hipGetLastError(); cus = 256; }
+    const unsigned max_groups = (unsigned)std::max(cus, 1) * kVplShootGroupsPerCu;
+    RenderConst rc{};
+    rc.has_max = params->has_max_depth; rc.max_depth = params->max_depth;
+    rc.has_rr = params->has_rr_depth; rc.rr_depth = params->rr_depth;
+    rc.seed_variant = params->seed_variant;
+    VplPathsConst pc{};
+    for (int i = 0; i < 4; i++) pc.main[i] = sampler->s[i];
+    pc.option_vpl = option_vpl;
+    const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
+    const int mat = ctx->single_bsdf ? ctx->bsdf_type : -1;
+    const auto launch = ctx->lds_scene ? launch_vpl_paths_lds : launch_vpl_paths_stream;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timing = stats != nullptr;
+    if (timing) { HIP_OK(hipEventCreate(&ev[0])); HIP_OK(hipEventCreate(&ev[1])); }
+    struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); (void)hipGetLastError(); } } guard{ev};
+    const auto t0 = std::chrono::steady_clock::now();
+    float ms_kernels = 0.0f;
+    unsigned launches = 0, rounds = 0;
+    // one launch over paths first .. first + count - 1: persistent workgroups stride over the batch
+    auto shoot = [&](bool write, unsigned first, unsigned count) -> int {
+        const unsigned groups = std::min((count + 255u) / 256u, max_groups);
+        StackConf stc;
+        int r = stack_conf(ctx, (size_t)groups * 256, &stc);
+        if (r != RL_OK) return r;
+        pc.first = first; pc.count = count;
+        if (timing) HIP_OK(hipEventRecord(ev[0], st));
+        launch(write, mat, medium, dim3(groups), dim3(256), lds, st, rc, ctx->ds, stc, pc);
+        if (timing) HIP_OK(hipEventRecord(ev[1], st));
+        launches++;
+        return RL_OK;
+    };
+    auto add_kernel_time = [&]() { float ms = 0.0f; if (timing && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ms_kernels += ms; (void)hipGetLastError(); };
+    // ---- count rounds
+    HipBuffer<unsigned> d_counts;
+    std::vector<unsigned> counts;                    // [path][VPL_PATH_WORDS], every path walked so far
+    std::vector<unsigned> offsets;                   // [path] exclusive prefix sum of the record counts, paths 0 .. K-1 once K is known
+    unsigned long long stored = 0;
+    unsigned walked = 0, K = 0;
+    while (K == 0 && walked < (unsigned)RL_VPL_MAX_PATHS) {
+        unsigned batch;
+        if (forced) batch = (unsigned)std::min<long long>(forced, RL_VPL_MAX_PATHS);
+        else if (walked == 0) batch = std::max(kVplFirstBatch, nb_vpl / 8u);       // a light path seldom stores more than 8 records
+        else {
+            // the measured records per path, plus a margin of an eighth and 64 paths; when nothing was stored yet, twice what was walked
+            const double per_path = (double)stored / (double)walked;
+            batch = stored ? (unsigned)std::min<double>((double)RL_VPL_MAX_PATHS, (double)(nb_vpl - stored) / per_path * 1.125 + 64.0) : 2u * walked;
+        }
+        batch = std::min(batch, (unsigned)RL_VPL_MAX_PATHS - walked);
+        if ((rcode = d_counts.ensure((size_t)batch * VPL_PATH_WORDS)) != RL_OK) return rcode;
+        pc.counts = d_counts.get();
+        if ((rcode = shoot(false, walked, batch)) != RL_OK) return rcode;
+        counts.resize((size_t)(walked + batch) * VPL_PATH_WORDS);
+        HIP_OK(hipMemcpyAsync(counts.data() + (size_t)walked * VPL_PATH_WORDS, d_counts.get(), (size_t)batch * VPL_PATH_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipGetLastError());
+        add_kernel_time();
+        rounds++;
+        for (unsigned k = walked; k < walked + batch && K == 0; k++) {            // the cut: `while stored < nb` on this path sequence
+            offsets.push_back((unsigned)stored);
+            stored += counts[(size_t)k * VPL_PATH_WORDS + VPL_PATH_RECORDS];
+            if (stored >= nb_vpl) K = k + 1u;
+        }
+        walked += batch;
+    }
+    if (K == 0) { rl_set_error("vpl: fewer than nb_vpl VPLs stored within RL_VPL_MAX_PATHS light paths"); return RL_ERR_UNSUPPORTED; }
+    // ---- write pass: paths 0 .. K-1 again, each to its own offset
+    HipBuffer<unsigned> d_offsets;
+    if ((rcode = set->words.ensure((size_t)stored * RL_VPL_WORDS)) != RL_OK || (rcode = d_offsets.ensure(K)) != RL_OK) return rcode;
+    HIP_OK(hipMemcpyAsync(d_offsets.get(), offsets.data(), (size_t)K * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    pc.cap = (unsigned)stored; pc.vpl_words = set->words.get(); pc.offsets = d_offsets.get(); pc.counts = nullptr;
+    if ((rcode = shoot(true, 0u, K)) != RL_OK) return rcode;
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    add_kernel_time();
+    for (unsigned k = 0; k < K; k++) (void)rl_sampler_next_u64(sampler);           // the K clone_box calls
+    set->n_vpl = stored; set->n_paths = K;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->camera_samples = K;
+        for (unsigned k = 0; k < K; k++) {
+            const unsigned* c = &counts[(size_t)k * VPL_PATH_WORDS];
+            stats->vertices += c[VPL_PATH_VERTICES]; stats->extension_rays += c[VPL_PATH_EXT]; stats->rng_draws += c[VPL_PATH_DRAWS];
+        }
+        stats->iterations = rounds; stats->kernel_launches = launches; stats->ms_prepass = ms_kernels;
+        stats->reserved[0] = walked;
         stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     *out = set.release();
