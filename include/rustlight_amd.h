@@ -435,8 +435,19 @@ int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_path_params* 
  * rl_photon_tree_build: the host part alone, no GPU — the tree of `n_photons` records (RL_VPL_WORDS u32 each, only words 4..6 are read) as the device walks
  * it: nodes in visiting order, node_boxes [n][6] = p_min, p_max, node_links [n][3] = skip (the node to go on with when the box is missed; entered: the next
  * one), first, count (count = 0: inner node; a leaf holds places first .. first + count - 1), order[place] = index of the record that stands there.  With the
- * three arrays NULL only *n_nodes is written (at most 2 * n_photons). */
+ * three arrays NULL only *n_nodes is written (at most 2 * n_photons).
+ * rl_photon_map_build_device: what rl_photon_map_build does, built where the records are — device kernels (kernels/phototree.hip.h) check the records, sort
+ * every level and write tree and photons; no record, node or photon crosses to the host, only the flag word of the check pass.  The map is the same type and
+ * holds the same bytes as the host build's (the topology depends on the photon count alone, a stable sort equals any sort by (key, place before the sort), and
+ * float min / max is exact in any order); refusals, codes and rl_last_error texts are the same.  ms_kernels (may be NULL): the summed HIP-event time of the
+ * launches, 0 under the option no_events.  Ranges of at most RL_PHOTON_TREE_GROUP_PHOTONS photons are finished by one workgroup each in LDS; the option
+ * photon_tree_group_photons = n forces a smaller group (4 .. RL_PHOTON_TREE_GROUP_PHOTONS; tests) and changes no result.
+ * rl_photon_tree_build_device: rl_photon_tree_build's contract, the size-only call included, computed by the same device kernels: the words are uploaded, the
+ * arrays downloaded.  `ctx` names the device (and carries the options); the scene needs no medium.
+ * rl_photon_map_read: a map of either build as host arrays — node_boxes [n_nodes][6], node_links [n_nodes][3] = skip, first, count as rl_photon_tree_build
+ * writes them, photons [n_photons][9] = pos, radiance, d_in in leaf order.  The capacities are in nodes / photons and must cover rl_photon_map_info's counts. */
 #define RL_PHOTON_RADIUS_DEFAULT 0.001f
+enum { RL_PHOTON_TREE_GROUP_PHOTONS = 2048 };
 typedef struct rl_photon_map rl_photon_map;       /* opaque: photon tree and photons, on the context's device */
 int rl_photon_map_build(rl_context* ctx, const rl_vpl_set* set, float radius, rl_photon_map** out);
 int rl_photon_map_info(const rl_photon_map* map, uint64_t* n_photons, uint64_t* n_nodes, uint64_t* n_paths, float* radius);
@@ -445,6 +456,10 @@ int rl_render_bre(rl_context* ctx, const rl_photon_map* map, uint32_t spp, int32
                   const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
 int rl_photon_tree_build(const uint32_t* words, size_t n_photons, float radius, size_t node_capacity, size_t* n_nodes, float* node_boxes,
                          uint32_t* node_links, uint32_t* order);
+int rl_photon_map_build_device(rl_context* ctx, const rl_vpl_set* set, float radius, rl_photon_map** out, float* ms_kernels);
+int rl_photon_tree_build_device(rl_context* ctx, const uint32_t* words, size_t n_photons, float radius, size_t node_capacity, size_t* n_nodes, float* node_boxes,
+                                uint32_t* node_links, uint32_t* order);
+int rl_photon_map_read(const rl_photon_map* map, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t photon_capacity, float* photons);
 
 /* Frames in flight behind one call (the progressive wrappers' passes, avg.rs:5-131 / equal_time.rs:4-66: N independent renders of one scene): frame f — block
  * seeds `block_seeds[f]`, host image `out_rgb[f]` (W*H*3 f32) — renders on `ctxs[f % k]` from host thread f % k, k = min(n_ctx, n_frames); `ctxs` are distinct

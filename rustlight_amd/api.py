@@ -10,6 +10,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
+import time
 from typing import Optional
 
 import numpy as np
@@ -30,6 +31,8 @@ LIGHT_ALL, LIGHT_SURFACE, LIGHT_VOLUME = 0, 1, 2          # rl_light_strategy: `
 VPL_ALL, VPL_SURFACE, VPL_VOLUME = 0, 1, 2                # rl_vpl_option: `vpl -v / -l all|surface|volume`
 LIGHT_STREAMS = ("reference", "per_path")                 # how the light paths of vpl / vol-primitivies draw: rl_vpl_generate | rl_vpl_generate_paths
 VPL_WORDS = 24                                            # RL_VPL_WORDS: u32 per VPL record (rl_vpl_read)
+TREE_BUILDS = ("host", "device")                          # where the photon tree of vol-primitivies is built: rl_photon_map_build | rl_photon_map_build_device
+PHOTON_TREE_GROUP_PHOTONS = 2048                          # RL_PHOTON_TREE_GROUP_PHOTONS: photons one workgroup of the device build finishes in LDS
 PHOTON_RADIUS_DEFAULT = 0.001                             # RL_PHOTON_RADIUS_DEFAULT: the radius the reference hard-codes (vol_primitives.rs:618)
 RL_ERR_UNSUPPORTED, RL_ERR_NO_EMITTER = -7, -8
 
@@ -40,7 +43,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -123,6 +126,9 @@ def lib():
     L.rl_photon_map_destroy.restype = None
     L.rl_render_bre.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
     L.rl_photon_tree_build.argtypes = [u32p, C.c_size_t, C.c_float, C.c_size_t, C.POINTER(C.c_size_t), f32p, u32p, u32p]
+    L.rl_photon_map_build_device.argtypes = [vp, vp, C.c_float, C.POINTER(vp), f32p]
+    L.rl_photon_tree_build_device.argtypes = [vp, u32p, C.c_size_t, C.c_float, C.c_size_t, C.POINTER(C.c_size_t), f32p, u32p, u32p]
+    L.rl_photon_map_read.argtypes = [vp, C.c_size_t, f32p, u32p, C.c_size_t, f32p]
     for fn in (L.rl_render_ao, L.rl_render_direct):
         fn.argtypes = [vp, C.POINTER(abi.McParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_multi_create.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -522,12 +528,32 @@ class Context:
         d["gather_surface"], d["gather_volume"] = int(st.reserved[0]), int(st.reserved[1])
         return img, d
 
-    def photon_map(self, vpls: "VplSet", radius=PHOTON_RADIUS_DEFAULT):
+    def photon_map(self, vpls: "VplSet", radius=PHOTON_RADIUS_DEFAULT, build="host"):
         """rl_photon_map_build: the photon tree of the beam radiance estimate over a set generated with option_vpl = VPL_VOLUME (its records are the reference's
-        photons).  radius: the reference hard-codes PHOTON_RADIUS_DEFAULT."""
+        photons).  radius: the reference hard-codes PHOTON_RADIUS_DEFAULT.  build="device": rl_photon_map_build_device, the same map byte for byte from device
+        kernels, no record leaving the GPU.  PhotonMap.ms_build: wall clock of the call; PhotonMap.ms_kernels: the device build's kernel time (None: host)."""
+        if build not in TREE_BUILDS:
+            raise ValueError(f"build must be one of {TREE_BUILDS}, not {build!r}")
         h = C.c_void_p()
-        _check(lib().rl_photon_map_build(self.h, vpls.h, radius, C.byref(h)))
-        return PhotonMap(h, self)
+        ms = C.c_float(0.0)
+        t0 = time.perf_counter()
+        if build == "device":
+            _check(lib().rl_photon_map_build_device(self.h, vpls.h, radius, C.byref(h), C.byref(ms)))
+        else:
+            _check(lib().rl_photon_map_build(self.h, vpls.h, radius, C.byref(h)))
+        m = PhotonMap(h, self)
+        m.ms_build = (time.perf_counter() - t0) * 1e3
+        m.ms_kernels = float(ms.value) if build == "device" else None
+        return m
+
+    def photon_tree_build_device(self, words, radius):
+        """rl_photon_tree_build_device: photon_tree_build's arrays, computed by the kernels of the device build on this context's device."""
+        w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, VPL_WORDS)
+        n = C.c_size_t()
+        _check(lib().rl_photon_tree_build_device(self.h, abi.u32ptr(w), w.shape[0], radius, 0, C.byref(n), None, None, None))
+        boxes, links, order = np.zeros((n.value, 6), np.float32), np.zeros((n.value, 3), np.uint32), np.zeros(w.shape[0], np.uint32)
+        _check(lib().rl_photon_tree_build_device(self.h, abi.u32ptr(w), w.shape[0], radius, n.value, C.byref(n), abi.fptr(boxes), abi.u32ptr(links), abi.u32ptr(order)))
+        return boxes, links, order
 
     def render_bre(self, photons: "PhotonMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
         """The beam radiance estimate's gather (vol_primitives.rs:712-790) through rl_render_bre: (image HxWx3 f32, stats dict).  stats: nodes_entered /
@@ -783,6 +809,15 @@ class PhotonMap:
 
     def __init__(self, h, ctx: Context):
         self.h, self.ctx = h, ctx
+        self.ms_build = None        # Context.photon_map: wall clock of the build call, ms
+        self.ms_kernels = None      # the device build's kernel time, ms
+
+    def read(self):
+        """rl_photon_map_read: (boxes [n, 6] f32, links [n, 3] u32 = skip, first, count, photons [n_photons, 9] f32 = pos, radiance, d_in in leaf order)."""
+        n_photons, n_nodes, _, _ = self.info()
+        boxes, links, photons = np.zeros((n_nodes, 6), np.float32), np.zeros((n_nodes, 3), np.uint32), np.zeros((n_photons, 9), np.float32)
+        _check(lib().rl_photon_map_read(self.h, n_nodes, abi.fptr(boxes), abi.u32ptr(links), n_photons, abi.fptr(photons)))
+        return boxes, links, photons
 
     def info(self):
         """(photons, tree nodes, light paths shot, radius)."""
@@ -817,14 +852,19 @@ class IntegratorVolPrimitives:
     """struct IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute for
     primitives = BRE, seed for seed the reference: the photons from the main sampler, the block seeds from the sampler they leave, the gather on
     reference-order streams.  radius: the reference's constant unless given.  light_streams="per_path": the photons from rl_vpl_generate_paths (one light path
-    per lane, each on its own stream): statistically, not seed-for-seed, the same image."""
+    per lane, each on its own stream): statistically, not seed-for-seed, the same image.  tree_build="device": the photon tree from rl_photon_map_build_device
+    (the same tree byte for byte, built on the GPU)."""
 
-    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, primitives="bre", radius=PHOTON_RADIUS_DEFAULT, device=0, options=None, light_streams="reference"):
+    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, primitives="bre", radius=PHOTON_RADIUS_DEFAULT, device=0, options=None, light_streams="reference",
+                 tree_build="host"):
         if primitives != "bre":
             raise RustlightError(RL_ERR_UNSUPPORTED, f"vol-primitives: {primitives} is not built (bre only)")
         if light_streams not in LIGHT_STREAMS:
             raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
+        if tree_build not in TREE_BUILDS:
+            raise ValueError(f"tree_build must be one of {TREE_BUILDS}, not {tree_build!r}")
         self.light_streams = light_streams
+        self.tree_build = tree_build
         self.nb_primitive, self.max_depth, self.rr_depth, self.radius = nb_primitive, max_depth, rr_depth, radius
         self.device = device
         self.options = dict(options or {})
@@ -840,7 +880,7 @@ class IntegratorVolPrimitives:
         vpls, self.last_generation_stats = self._ctx.vpl_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, VPL_VOLUME, self.light_streams)
         photons = None
         try:
-            photons = self._ctx.photon_map(vpls, self.radius)
+            photons = self._ctx.photon_map(vpls, self.radius, self.tree_build)
             w, h = scene.size
             seeds = sampler.block_seeds(w, h)
             img, self.last_stats = self._ctx.render_bre(photons, seeds, nb_samples, sampler.variant)

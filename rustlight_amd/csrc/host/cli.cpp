@@ -8,12 +8,14 @@
 //               | light-tracing [-m MAX|inf] [-n MIN] [-r RR|inf] [-s all|surface|volume]   (examples/cli.rs:54-61, 170-174; per-sample streams)
 //               | vpl [-m MAX|inf] [-r RR|inf] [-b CLAMP] [--nb-vpl N] [-l all|surface|volume] [-v all|surface|volume] [--light-streams reference|per-path]   (examples/cli.rs:176-184, 707-733;
 //                 -b is accepted and ignored as the reference ignores clamping_factor; -n is refused: the reference declares it twice under `vpl`)
-//               | vol-primitivies [-m MAX|inf] [-n MIN] [-r RR|inf] [--nb-primitive N] [-p bre] [--radius R] [--light-streams reference|per-path]   (examples/cli.rs:189-196, 692-716; sic, `vol-primitives`
+//               | vol-primitivies [-m MAX|inf] [-n MIN] [-r RR|inf] [--nb-primitive N] [-p bre] [--radius R] [--light-streams reference|per-path] [--tree-build host|device]   (examples/cli.rs:189-196, 692-716; sic, `vol-primitives`
 //                 is accepted too.  -p defaults to bre: the reference's default "BRE" matches none of its own arms and panics; beam | plane | vrl are not
 //                 built.  -n is min_depth, parsed and ignored as the reference ignores it here — its short form of --nb-primitive clashes with it.  --radius: the
 //                 photon radius, the reference's hard-coded 0.001 unless given)
 //                 --light-streams (vpl, vol-primitivies): reference = the light paths on the main sampler's serial stream, seed for seed the reference (default);
 //                 per-path = one light path per GPU lane, each on its own stream (rl_vpl_generate_paths): statistically, not seed-for-seed, the same image
+//                 --tree-build (vol-primitivies): host = the photon tree built on the host (default); device = the same tree, byte for byte, built by device
+//                 kernels with no record leaving the GPU (rl_photon_map_build_device)
 // Note `-n` / `-m` / `-r` / `-s` mean spp / medium / sampler / scale before the subcommand and
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 #include <chrono>
@@ -56,6 +58,7 @@ int main(int argc, char** argv) {
     std::string nb_vpl = "128", option_lt = "all", option_vpl = "all";     // vpl (cli.rs:176-184)
     std::string nb_primitive = "128", primitives = "bre", radius = "0.001";     // vol-primitivies (cli.rs:189-196)
     std::string light_streams = "reference";            // vpl, vol-primitivies: `--light-streams per-path` shoots the light paths in parallel, each on its own stream
+    std::string tree_build = "host";                    // vol-primitivies: `--tree-build device` builds the photon tree on the GPU
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -90,11 +93,14 @@ int main(int argc, char** argv) {
             }
             else if (a == "-l" || a == "--log") (void)val();   // log file: nothing is logged on this path
             else if (a == "--light-streams") { std::fprintf(stderr, "--light-streams is an option of the vpl and vol-primitivies subcommands: give it after the subcommand\n"); return 2; }
+            else if (a == "--tree-build") { std::fprintf(stderr, "--tree-build is an option of the vol-primitivies subcommand: give it after the subcommand\n"); return 2; }
             else if (a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
             else if (scene_path.empty()) scene_path = a;
             else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl` and `vol-primitivies` subcommands are provided (got %s)\n", a.c_str()); return 2; }
         } else if (a == "--light-streams" && cmd != "vpl" && cmd != "vol-primitivies") {
             std::fprintf(stderr, "%s: --light-streams is not supported (vpl and vol-primitivies only)\n", cmd.c_str()); return 2;
+        } else if (a == "--tree-build" && cmd != "vol-primitivies") {
+            std::fprintf(stderr, "%s: --tree-build is not supported (vol-primitivies only)\n", cmd.c_str()); return 2;
         } else if (cmd == "ao") {
             if (a == "-d" || a == "--distance") ao_distance = val();
             else if (a == "-n" || a == "--normal-correction") ao_normal_correction = true;
@@ -121,6 +127,7 @@ int main(int argc, char** argv) {
             else if (a == "-p" || a == "--primitives") primitives = val();
             else if (a == "--radius") radius = val();
             else if (a == "--light-streams") light_streams = val();
+            else if (a == "--tree-build") tree_build = val();
             else { std::fprintf(stderr, "unknown vol-primitivies option %s\n", a.c_str()); return 2; }
         } else if (cmd == "light-tracing") {
             if (a == "-m" || a == "--max-depth") max_depth = val();
@@ -209,6 +216,8 @@ int main(int argc, char** argv) {
         volp.max_depth = match_infinity(max_depth);
         volp.rr_depth = match_infinity(rr_depth);
         volp.light_streams = light_streams_mode;
+        if (tree_build == "device") volp.tree_build = TreeBuild::Device;
+        else if (tree_build != "host") { std::fprintf(stderr, "invalid --tree-build: %s (host or device)\n", tree_build.c_str()); return 2; }
         volp.device = device;
         volp.options = options;
     }

@@ -334,14 +334,17 @@ struct IntegratorVPL {
 // struct IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives } (src/integrators/explicit/vol_primitives.rs:12-24) + Integrator::compute
 // for the beam radiance estimate, seed for seed the reference: the photons from the main sampler (rl_vpl_generate with RL_VPL_VOLUME: the records convert_photons
 // stores), the photon tree (rl_photon_map_build), the block seeds from the sampler the generation leaves, the gather on reference-order streams (rl_render_bre).
-// Beams, Planes and VRL are not built.  radius: the reference hard-codes 0.001 (vol_primitives.rs:618).
+// Beams, Planes and VRL are not built.  radius: the reference hard-codes 0.001 (vol_primitives.rs:618).  tree_build: Host = rl_photon_map_build (the records
+// go to the host and the tree comes back), Device = rl_photon_map_build_device (the same tree, byte for byte, from device kernels; `--tree-build device`).
 enum class VolPrimitivies { BRE, Beams, Planes, VRL };
+enum class TreeBuild { Host, Device };
 struct IntegratorVolPrimitives {
     uint32_t nb_primitive = 128;
     std::optional<uint32_t> max_depth, rr_depth = 0u;
     VolPrimitivies primitives = VolPrimitivies::BRE;
     float radius = RL_PHOTON_RADIUS_DEFAULT;
     LightStreams light_streams = LightStreams::Reference;
+    TreeBuild tree_build = TreeBuild::Host;
     int device = 0;
     std::vector<std::pair<std::string, std::string>> options;
     rl_render_stats last_stats{}, last_generation_stats{};
@@ -364,7 +367,7 @@ struct IntegratorVolPrimitives {
         rl_vpl_set* photons = nullptr;
         rl_photon_map* map = nullptr;
         rc = (light_streams == LightStreams::PerPath ? rl_vpl_generate_paths : rl_vpl_generate)(ctx, &p, nb_primitive, RL_VPL_VOLUME, &sampler.rnd, &photons, &last_generation_stats);
-        if (rc == RL_OK) rc = rl_photon_map_build(ctx, photons, radius, &map);
+        if (rc == RL_OK) rc = tree_build == TreeBuild::Device ? rl_photon_map_build_device(ctx, photons, radius, &map, nullptr) : rl_photon_map_build(ctx, photons, radius, &map);
         if (rc == RL_OK) {
             std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
             rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());

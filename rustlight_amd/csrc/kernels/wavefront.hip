@@ -43,6 +43,7 @@
 #include "rngjump.h"
 #include "../host/hip_buffer.h"
 #include "../host/photontree.h"
+#include "phototree.h"
 #include "../host/scene.h"
 #include "wavefront.h"
 #include "knobs.h"
@@ -1301,6 +1302,93 @@ extern "C" int rl_photon_map_build(rl_context* ctx, const rl_vpl_set* set, float
     HIP_OK(hipMemcpy(map->photons.get(), h_photons.data(), h_photons.size() * sizeof(float4), hipMemcpyHostToDevice));
     map->n_photons = set->n_vpl; map->n_nodes = n_nodes; map->n_paths = set->n_paths; map->radius = radius;
     *out = map.release();
+    return RL_OK;
+}
+// The device build (kernels/phototree.hip.h): the same map from kernels alone.  photon_tree_run's check pass stands for the host's loops over downloaded words.
+static unsigned photon_tree_group(const rl_context* ctx) {
+    if (!ctx->knobs.has(K_PHOTON_TREE_GROUP_PHOTONS)) return (unsigned)RL_PHOTON_TREE_GROUP_PHOTONS;
+    return (unsigned)std::min<long long>(std::max<long long>(4, ctx->knobs.i(K_PHOTON_TREE_GROUP_PHOTONS, 0)), RL_PHOTON_TREE_GROUP_PHOTONS);
+}
+extern "C" int rl_photon_map_build_device(rl_context* ctx, const rl_vpl_set* set, float radius, rl_photon_map** out, float* ms_kernels) {
+    if (!ctx || !set || !out) return RL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (ms_kernels) *ms_kernels = 0.0f;
+    int rcode;
+    if ((rcode = check_bre_scene(ctx)) != RL_OK) return rcode;
+    if (set->ctx != ctx) { rl_set_error("the VPL set belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
+    if (!std::isfinite(radius) || !(radius > 0.0f)) { rl_set_error("the photon radius must be finite and > 0"); return RL_ERR_INVALID_ARGUMENT; }
+    if (set->n_vpl > (uint64_t)RL_VPL_MAX + 4096) { rl_set_error("too many photons"); return RL_ERR_INVALID_ARGUMENT; }
+    HIP_OK(hipSetDevice(ctx->device));
+    const unsigned n = (unsigned)set->n_vpl, n_nodes = photon_tree_node_count(n);
+    auto map = std::make_unique<rl_photon_map>();
+    map->ctx = ctx; map->device = ctx->device;
+    if ((rcode = map->nodes.ensure(2 * (size_t)n_nodes)) != RL_OK || (rcode = map->photons.ensure(3 * (size_t)n)) != RL_OK) return rcode;
+    const PhotonTreeJob job{set->words.get(), n, radius, photon_tree_group(ctx), true, map->nodes.get(), nullptr, map->photons.get()};
+    if ((rcode = photon_tree_run(job, ctx->stream, !ctx->knobs.has(K_NO_EVENTS), ms_kernels)) != RL_OK) return rcode;
+    map->n_photons = n; map->n_nodes = n_nodes; map->n_paths = set->n_paths; map->radius = radius;
+    *out = map.release();
+    return RL_OK;
+}
+// nodes in the gather's format -> the arrays rl_photon_tree_build writes
+static void unpack_photon_nodes(const std::vector<float4>& h_nodes, size_t n_nodes, float* node_boxes, uint32_t* node_links) {
+    for (size_t i = 0; i < n_nodes; i++) {
+        const float4 a = h_nodes[2 * i], b = h_nodes[2 * i + 1];
+        const float box[6] = {a.x, a.y, a.z, a.w, b.x, b.y};
+        std::memcpy(node_boxes + 6 * i, box, sizeof box);
+        uint32_t skip, fc;
+        std::memcpy(&skip, &b.z, sizeof skip); std::memcpy(&fc, &b.w, sizeof fc);
+        node_links[3 * i] = skip; node_links[3 * i + 1] = fc >> 3; node_links[3 * i + 2] = fc & 7u;
+    }
+}
+extern "C" int rl_photon_tree_build_device(rl_context* ctx, const uint32_t* words, size_t n_photons, float radius, size_t node_capacity, size_t* n_nodes,
+                                           float* node_boxes, uint32_t* node_links, uint32_t* order) {
+    if (!ctx || !n_nodes || (n_photons && !words)) return RL_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(radius) || !(radius > 0.0f)) { rl_set_error("the photon radius must be finite and > 0"); return RL_ERR_INVALID_ARGUMENT; }
+    if (n_photons > (size_t)RL_VPL_MAX + 4096) { rl_set_error("too many photons"); return RL_ERR_INVALID_ARGUMENT; }      // before any allocation
+    const bool size_only = !node_boxes && !node_links && !order;
+    if (!size_only && (!node_boxes || !node_links || !order)) return RL_ERR_INVALID_ARGUMENT;
+    if (n_photons == 0) { *n_nodes = 0; return RL_OK; }
+    HIP_OK(hipSetDevice(ctx->device));
+    const unsigned n = (unsigned)n_photons, count = photon_tree_node_count(n);
+    int rcode;
+    HipBuffer<unsigned> d_words, d_order;
+    HipBuffer<float4> d_nodes;
+    if ((rcode = d_words.ensure(n_photons * RL_VPL_WORDS)) != RL_OK) return rcode;
+    HIP_OK(hipMemcpyAsync(d_words.get(), words, n_photons * RL_VPL_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (size_only || node_capacity < count) {
+        // the host build refuses a bad record before it looks at the capacity: the check pass alone
+        const PhotonTreeJob check{d_words.get(), n, radius, photon_tree_group(ctx), false, nullptr, nullptr, nullptr};
+        if ((rcode = photon_tree_run(check, ctx->stream, false, nullptr)) != RL_OK) return rcode;
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        *n_nodes = count;
+        if (size_only) return RL_OK;
+        rl_set_error("rl_photon_tree_build_device: node_capacity is too small");
+        return RL_ERR_INVALID_ARGUMENT;
+    }
+    if ((rcode = d_order.ensure(n)) != RL_OK || (rcode = d_nodes.ensure(2 * (size_t)count)) != RL_OK) return rcode;
+    const PhotonTreeJob job{d_words.get(), n, radius, photon_tree_group(ctx), false, d_nodes.get(), d_order.get(), nullptr};
+    if ((rcode = photon_tree_run(job, ctx->stream, false, nullptr)) != RL_OK) return rcode;
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    *n_nodes = count;
+    std::vector<float4> h_nodes(2 * (size_t)count);
+    HIP_OK(hipMemcpy(h_nodes.data(), d_nodes.get(), h_nodes.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(order, d_order.get(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    unpack_photon_nodes(h_nodes, count, node_boxes, node_links);
+    return RL_OK;
+}
+extern "C" int rl_photon_map_read(const rl_photon_map* map, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t photon_capacity, float* photons) {
+    if (!map || !node_boxes || !node_links || !photons) return RL_ERR_INVALID_ARGUMENT;
+    if (node_capacity < map->n_nodes || photon_capacity < map->n_photons) { rl_set_error("rl_photon_map_read: a capacity is too small"); return RL_ERR_INVALID_ARGUMENT; }
+    HIP_OK(hipSetDevice(map->device));
+    std::vector<float4> h_nodes(2 * (size_t)map->n_nodes), h_photons(3 * (size_t)map->n_photons);
+    HIP_OK(hipMemcpy(h_nodes.data(), map->nodes.get(), h_nodes.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(h_photons.data(), map->photons.get(), h_photons.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    unpack_photon_nodes(h_nodes, (size_t)map->n_nodes, node_boxes, node_links);
+    for (size_t i = 0; i < (size_t)map->n_photons; i++)
+        for (int q = 0; q < 3; q++) {
+            const float4 v = h_photons[3 * i + q];
+            photons[9 * i + 3 * q] = v.x; photons[9 * i + 3 * q + 1] = v.y; photons[9 * i + 3 * q + 2] = v.z;
+        }
     return RL_OK;
 }
 extern "C" int rl_photon_map_info(const rl_photon_map* map, uint64_t* n_photons, uint64_t* n_nodes, uint64_t* n_paths, float* radius) {
