@@ -461,6 +461,52 @@ int rl_photon_tree_build_device(rl_context* ctx, const uint32_t* words, size_t n
                                 uint32_t* node_links, uint32_t* order);
 int rl_photon_map_read(const rl_photon_map* map, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t photon_capacity, float* photons);
 
+/* ---- IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs; CLI `plane-single`, examples/cli.rs:197-202, 664-691): single
+ * scattering from rectangular area lights, estimated with photon planes under one of seven sampling strategies.
+ * The lights: RectangularLightSource::from_shape (plane_single.rs:38-75) of every emissive mesh, in mesh order — o = v[0], u = v[1] - v[0], v = v[3] - v[0],
+ * normalised by their lengths, n = u x v.  Point, directional and environment lights are ignored, as the reference ignores them.  Refused before any kernel
+ * runs, by every entry point below that takes a context: a scene without a medium (RL_ERR_UNSUPPORTED; the reference panics), without an emissive mesh
+ * (RL_ERR_NO_EMITTER), with an emissive mesh that is not 2 triangles over at least 4 vertices, or whose emission is HSV or textured (RL_ERR_UNSUPPORTED).
+ * rl_plane_generate: the loop `while planes.len() < nb_primitive` (plane_single.rs:363-427) on the main sampler, seed for seed — per iteration one draw for
+ * id_emitter, then one plane (UV / VT / UT / UALPHA / CMIS) or the three planes UV, VT, UT (AVERAGE / DISCRETE_MIS); a plane takes 2 draws for its direction
+ * (drawn again while the direction's z is 0), 1 for the distance, 2 for `sample`, 1 for alpha.  It runs on one device lane (the pass needs the deterministic
+ * log / sin / cos the kernels hold).  nb_primitive is 1 .. RL_VPL_MAX; `sampler` leaves advanced exactly as the reference's main sampler is.  One deliberate
+ * difference: id_emitter is clamped to the last light where the reference would index out of range.  A plane with a non-finite corner is
+ * RL_ERR_INVALID_ARGUMENT (the sampler is then left as it was).  Counters: camera_samples = iterations (number_plane_gen), vertices = planes, rng_draws,
+ * kernel_launches, ms_prepass = the kernel.
+ * rl_plane_read: the planes as records of RL_PLANE_WORDS u32 — [0..2] o, [3..5] d0, [6..8] d1, [9] length0, [10] length1, [11..13] weight, [14..15] sample,
+ * [16] rl_plane_type, [17] id_emitter.  n_words must be n_planes * RL_PLANE_WORDS.
+ * rl_plane_map_build sorts them into BHVAccel's tree on the host — box = the union of the plane's four corners, sort key = the plane's middle
+ * (plane_single.rs:101-117), otherwise rl_photon_map_build's tree with its two deliberate differences (a stable sort; a non-finite corner is
+ * RL_ERR_INVALID_ARGUMENT) — and uploads the tree, the planes in leaf order as 64-byte records and the lights.  The set must come from the same context.
+ * rl_plane_tree_build: the host part alone, no GPU, with rl_photon_tree_build's calling convention over records of RL_PLANE_WORDS u32.
+ * rl_plane_map_read: node_boxes / node_links as rl_photon_map_read writes them, planes [n_planes][16] f32 = o, length0 | d0, length1 | d1, the bits of
+ * type + 4 * id_emitter | weight, 0, in leaf order.
+ * rl_render_plane_single (plane_single.rs:436-611): per camera sample 2 draws (the jitter), the camera ray with tfar = its closest hit's distance (f32::MAX on
+ * a miss), BHVAccel::gather in the reference's visiting order; per plane the ray meets (tnear = 1e-4): the point on the light, one visibility ray, and
+ * c += w * rho * transmittance * sigma_s * flux * n_lights * (1 / number_plane_gen) with the strategy's w and flux (DISCRETE_MIS: the balance heuristic over the
+ * three planes re-made through the point; CMIS: its closed-form weight).  rho is the isotropic phase function whatever the medium's is: the reference
+ * hard-codes it.  Samples are added in order and scaled by 1 / spp.  Reference-order streams, exact numerics, one device, host output; shards, spp limit and
+ * their codes as rl_render_bre.  Counters: camera_samples, extension_rays = camera_samples, shadow_rays = planes intersected, rng_draws = 2 * camera_samples,
+ * kernel_launches, ms_other = the gather kernel; reserved[0] = plane-tree nodes entered, reserved[1] = planes intersected, reserved[2] = of those, visible. */
+typedef enum rl_plane_type { RL_PLANE_UV = 0, RL_PLANE_VT = 1, RL_PLANE_UT = 2, RL_PLANE_UALPHAT = 3 } rl_plane_type;
+typedef enum rl_plane_strategy { RL_PLANE_STRATEGY_UV = 0, RL_PLANE_STRATEGY_VT = 1, RL_PLANE_STRATEGY_UT = 2, RL_PLANE_STRATEGY_AVERAGE = 3,
+                                 RL_PLANE_STRATEGY_DISCRETE_MIS = 4, RL_PLANE_STRATEGY_UALPHA = 5, RL_PLANE_STRATEGY_CMIS = 6 } rl_plane_strategy;
+enum { RL_PLANE_WORDS = 18 };
+typedef struct rl_plane_set rl_plane_set;       /* opaque: the planes of one generation */
+typedef struct rl_plane_map rl_plane_map;       /* opaque: plane tree, planes and lights, on the context's device */
+int rl_plane_generate(rl_context* ctx, uint32_t nb_primitive, int strategy, rl_sampler* sampler, rl_plane_set** out, rl_render_stats* stats);
+int rl_plane_info(const rl_plane_set* set, uint64_t* n_planes, uint64_t* number_plane_gen, int* strategy);
+int rl_plane_read(const rl_plane_set* set, uint32_t* words, size_t n_words);
+void rl_plane_destroy(rl_plane_set* set);
+int rl_plane_tree_build(const uint32_t* words, size_t n_planes, size_t node_capacity, size_t* n_nodes, float* node_boxes, uint32_t* node_links, uint32_t* order);
+int rl_plane_map_build(rl_context* ctx, const rl_plane_set* set, rl_plane_map** out);
+int rl_plane_map_info(const rl_plane_map* map, uint64_t* n_planes, uint64_t* n_nodes, uint64_t* number_plane_gen, int* strategy);
+int rl_plane_map_read(const rl_plane_map* map, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t plane_capacity, float* planes);
+void rl_plane_map_destroy(rl_plane_map* map);
+int rl_render_plane_single(rl_context* ctx, const rl_plane_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
+                           const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
+
 /* Frames in flight behind one call (the progressive wrappers' passes, avg.rs:5-131 / equal_time.rs:4-66: N independent renders of one scene): frame f — block
  * seeds `block_seeds[f]`, host image `out_rgb[f]` (W*H*3 f32) — renders on `ctxs[f % k]` from host thread f % k, k = min(n_ctx, n_frames); `ctxs` are distinct
  * contexts of the same scene.  Returns when every frame is done; the images (and `stats[f]`, if not NULL) are those of `n_frames` rl_render_path calls one after

@@ -34,6 +34,9 @@ VPL_WORDS = 24                                            # RL_VPL_WORDS: u32 pe
 TREE_BUILDS = ("host", "device")                          # where the photon tree of vol-primitivies is built: rl_photon_map_build | rl_photon_map_build_device
 PHOTON_TREE_GROUP_PHOTONS = 2048                          # RL_PHOTON_TREE_GROUP_PHOTONS: photons one workgroup of the device build finishes in LDS
 PHOTON_RADIUS_DEFAULT = 0.001                             # RL_PHOTON_RADIUS_DEFAULT: the radius the reference hard-codes (vol_primitives.rs:618)
+PLANE_WORDS = 18                                          # RL_PLANE_WORDS: u32 per plane record (rl_plane_read)
+PLANE_UV, PLANE_VT, PLANE_UT, PLANE_UALPHAT = 0, 1, 2, 3  # rl_plane_type
+PLANE_STRATEGIES = ("uv", "vt", "ut", "average", "discrete_mis", "ualpha", "cmis")      # rl_plane_strategy, by value: `plane-single -s`
 RL_ERR_UNSUPPORTED, RL_ERR_NO_EMITTER = -7, -8
 
 # every symbol include/rustlight_amd.h declares (tests check the .so exports all of them)
@@ -43,7 +46,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_render_plane_single", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -129,6 +132,18 @@ def lib():
     L.rl_photon_map_build_device.argtypes = [vp, vp, C.c_float, C.POINTER(vp), f32p]
     L.rl_photon_tree_build_device.argtypes = [vp, u32p, C.c_size_t, C.c_float, C.c_size_t, C.POINTER(C.c_size_t), f32p, u32p, u32p]
     L.rl_photon_map_read.argtypes = [vp, C.c_size_t, f32p, u32p, C.c_size_t, f32p]
+    L.rl_plane_generate.argtypes = [vp, C.c_uint32, C.c_int, C.POINTER(abi.Sampler), C.POINTER(vp), C.POINTER(abi.RenderStats)]
+    L.rl_plane_info.argtypes = [vp, u64p, u64p, C.POINTER(C.c_int)]
+    L.rl_plane_read.argtypes = [vp, u32p, C.c_size_t]
+    L.rl_plane_destroy.argtypes = [vp]
+    L.rl_plane_destroy.restype = None
+    L.rl_plane_tree_build.argtypes = [u32p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), f32p, u32p, u32p]
+    L.rl_plane_map_build.argtypes = [vp, vp, C.POINTER(vp)]
+    L.rl_plane_map_info.argtypes = [vp, u64p, u64p, u64p, C.POINTER(C.c_int)]
+    L.rl_plane_map_read.argtypes = [vp, C.c_size_t, f32p, u32p, C.c_size_t, f32p]
+    L.rl_plane_map_destroy.argtypes = [vp]
+    L.rl_plane_map_destroy.restype = None
+    L.rl_render_plane_single.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
     for fn in (L.rl_render_ao, L.rl_render_direct):
         fn.argtypes = [vp, C.POINTER(abi.McParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_multi_create.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -566,6 +581,34 @@ class Context:
         d["nodes_entered"], d["photons_gathered"] = int(st.reserved[0]), int(st.reserved[1])
         return img, d
 
+    def plane_generate(self, sampler: "IndependentSampler", nb_primitive=128, strategy="average"):
+        """IntegratorSinglePlane's plane pass (plane_single.rs:363-427) through rl_plane_generate: (PlaneSet, stats dict).  `sampler` is advanced as the
+        reference's main sampler is.  stats: camera_samples = iterations (number_plane_gen), vertices = planes, rng_draws, ms_prepass = the kernel."""
+        st = abi.RenderStats()
+        h = C.c_void_p()
+        _check(lib().rl_plane_generate(self.h, nb_primitive, plane_strategy(strategy), C.byref(sampler.s), C.byref(h), C.byref(st)))
+        return PlaneSet(h, self), st.as_dict()
+
+    def plane_map(self, planes: "PlaneSet"):
+        """rl_plane_map_build: the plane tree over a generated set, built on the host and uploaded.  PlaneMap.ms_build: wall clock of the call, ms."""
+        h = C.c_void_p()
+        t0 = time.perf_counter()
+        _check(lib().rl_plane_map_build(self.h, planes.h, C.byref(h)))
+        m = PlaneMap(h, self)
+        m.ms_build = (time.perf_counter() - t0) * 1e3
+        return m
+
+    def render_plane_single(self, planes: "PlaneMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
+        """IntegratorSinglePlane's gather (plane_single.rs:436-611) through rl_render_plane_single: (image HxWx3 f32, stats dict).  stats: nodes_entered /
+        planes_intersected / planes_visible = reserved[0..2], shadow_rays = planes_intersected, ms_other = the gather kernel."""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        st = abi.RenderStats()
+        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        _check(lib().rl_render_plane_single(self.h, planes.h, spp, seed_variant, shard_index, shard_count, abi.u64ptr(seeds), seeds.shape[0], abi.fptr(img), C.byref(st)))
+        d = st.as_dict()
+        d["nodes_entered"], d["planes_intersected"], d["planes_visible"] = int(st.reserved[0]), int(st.reserved[1]), int(st.reserved[2])
+        return img, d
+
     def trace(self, origins, directions):
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
@@ -888,6 +931,122 @@ class IntegratorVolPrimitives:
             if photons is not None:
                 photons.close()
             vpls.close()
+        return img
+
+
+def plane_strategy(strategy):
+    """rl_plane_strategy of a name of PLANE_STRATEGIES (or of its value)."""
+    if isinstance(strategy, str):
+        if strategy not in PLANE_STRATEGIES:
+            raise ValueError(f"{strategy} is not a correct strategy choice (uv, ut, vt, average, discrete_mis, valpha, cmis)")
+        return PLANE_STRATEGIES.index(strategy)
+    return int(strategy)
+
+
+class PlaneSet:
+    """rl_plane_set: the planes of one rl_plane_generate."""
+
+    def __init__(self, h, ctx: Context):
+        self.h, self.ctx = h, ctx
+
+    def info(self):
+        """(planes stored, number_plane_gen, strategy name)."""
+        n, g, s = C.c_uint64(), C.c_uint64(), C.c_int()
+        _check(lib().rl_plane_info(self.h, C.byref(n), C.byref(g), C.byref(s)))
+        return int(n.value), int(g.value), PLANE_STRATEGIES[s.value]
+
+    def __len__(self):
+        return self.info()[0]
+
+    def words(self) -> np.ndarray:
+        """The raw records, [n_planes, PLANE_WORDS] u32 (layout: include/rustlight_amd.h, rl_plane_read)."""
+        w = np.zeros((self.info()[0], PLANE_WORDS), np.uint32)
+        _check(lib().rl_plane_read(self.h, abi.u32ptr(w), w.size))
+        return w
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().rl_plane_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PlaneMap:
+    """rl_plane_map: plane tree, planes and lights of one generation, on the device of the context that made them (kept alive with it)."""
+
+    def __init__(self, h, ctx: Context):
+        self.h, self.ctx = h, ctx
+        self.ms_build = None        # Context.plane_map: wall clock of the build call, ms
+
+    def info(self):
+        """(planes, tree nodes, number_plane_gen, strategy name)."""
+        n, m, g, s = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
+        _check(lib().rl_plane_map_info(self.h, C.byref(n), C.byref(m), C.byref(g), C.byref(s)))
+        return int(n.value), int(m.value), int(g.value), PLANE_STRATEGIES[s.value]
+
+    def read(self):
+        """rl_plane_map_read: (boxes [n, 6] f32, links [n, 3] u32 = skip, first, count, planes [n_planes, 16] f32 in leaf order)."""
+        n_planes, n_nodes, _, _ = self.info()
+        boxes, links, planes = np.zeros((n_nodes, 6), np.float32), np.zeros((n_nodes, 3), np.uint32), np.zeros((n_planes, 16), np.float32)
+        _check(lib().rl_plane_map_read(self.h, n_nodes, abi.fptr(boxes), abi.u32ptr(links), n_planes, abi.fptr(planes)))
+        return boxes, links, planes
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().rl_plane_map_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def plane_tree_build(words):
+    """rl_plane_tree_build, host only: (boxes [n, 6] f32, links [n, 3] u32 = skip, first, count, order [n_planes] u32) of the plane tree over records
+    `words` ([n_planes, PLANE_WORDS] u32), nodes in the order the gather visits them."""
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, PLANE_WORDS)
+    n = C.c_size_t()
+    _check(lib().rl_plane_tree_build(abi.u32ptr(w), w.shape[0], 0, C.byref(n), None, None, None))
+    boxes, links, order = np.zeros((n.value, 6), np.float32), np.zeros((n.value, 3), np.uint32), np.zeros(w.shape[0], np.uint32)
+    _check(lib().rl_plane_tree_build(abi.u32ptr(w), w.shape[0], n.value, C.byref(n), abi.fptr(boxes), abi.u32ptr(links), abi.u32ptr(order)))
+    return boxes, links, order
+
+
+class IntegratorSinglePlane:
+    """struct IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs:291-294) + Integrator::compute, seed for seed the
+    reference: the planes from the main sampler, the plane tree, the block seeds from the sampler the generation leaves, the gather on reference-order streams."""
+
+    def __init__(self, nb_primitive=128, strategy="average", device=0, options=None):
+        self.nb_primitive, self.strategy = nb_primitive, PLANE_STRATEGIES[plane_strategy(strategy)]
+        self.device = device
+        self.options = dict(options or {})
+        self.last_stats = None
+        self.last_generation_stats = None
+        self._ctx = None
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        if self._ctx is None or self._ctx.scene is not scene:
+            self._ctx = Context(scene, self.device)
+            for k, v in self.options.items():
+                self._ctx.set_option(k, v)
+        planes, self.last_generation_stats = self._ctx.plane_generate(sampler, self.nb_primitive, self.strategy)
+        pmap = None
+        try:
+            pmap = self._ctx.plane_map(planes)
+            w, h = scene.size
+            seeds = sampler.block_seeds(w, h)
+            img, self.last_stats = self._ctx.render_plane_single(pmap, seeds, nb_samples, sampler.variant)
+        finally:
+            if pmap is not None:
+                pmap.close()
+            planes.close()
         return img
 
 

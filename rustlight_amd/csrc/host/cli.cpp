@@ -16,6 +16,8 @@
 //                 per-path = one light path per GPU lane, each on its own stream (rl_vpl_generate_paths): statistically, not seed-for-seed, the same image
 //                 --tree-build (vol-primitivies): host = the photon tree built on the host (default); device = the same tree, byte for byte, built by device
 //                 kernels with no record leaving the GPU (rl_photon_map_build_device)
+//               | plane-single [-n|--nb-primitive N] [-s|--strategy uv|ut|vt|average|discrete_mis|ualpha|cmis]   (examples/cli.rs:197-202, 664-691; needs -m;
+//                 the limits of vol-primitivies: independent sampler, reference-order streams, exact numerics, one device, one pass)
 // Note `-n` / `-m` / `-r` / `-s` mean spp / medium / sampler / scale before the subcommand and
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 #include <chrono>
@@ -59,12 +61,14 @@ int main(int argc, char** argv) {
     std::string nb_primitive = "128", primitives = "bre", radius = "0.001";     // vol-primitivies (cli.rs:189-196)
     std::string light_streams = "reference";            // vpl, vol-primitivies: `--light-streams per-path` shoots the light paths in parallel, each on its own stream
     std::string tree_build = "host";                    // vol-primitivies: `--tree-build device` builds the photon tree on the GPU
+    std::string plane_nb = "128", plane_strategy = "average";     // plane-single (cli.rs:197-202)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
         if (!have_cmd) {
             if (a == "path" || a == "ao" || a == "direct" || a == "light-tracing" || a == "vpl") { have_cmd = true; cmd = a; }
             else if (a == "vol-primitivies" || a == "vol-primitives") { have_cmd = true; cmd = "vol-primitivies"; }
+            else if (a == "plane-single") { have_cmd = true; cmd = a; }
             else if (a == "-n" || a == "--nbsamples") nbsamples = std::strtoull(val().c_str(), nullptr, 10);
             else if (a == "-o" || a == "--output") output = val();
             else if (a == "-r" || a == "--random-number-generator") rng = val();
@@ -96,7 +100,7 @@ int main(int argc, char** argv) {
             else if (a == "--tree-build") { std::fprintf(stderr, "--tree-build is an option of the vol-primitivies subcommand: give it after the subcommand\n"); return 2; }
             else if (a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
             else if (scene_path.empty()) scene_path = a;
-            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl` and `vol-primitivies` subcommands are provided (got %s)\n", a.c_str()); return 2; }
+            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl`, `vol-primitivies` and `plane-single` subcommands are provided (got %s)\n", a.c_str()); return 2; }
         } else if (a == "--light-streams" && cmd != "vpl" && cmd != "vol-primitivies") {
             std::fprintf(stderr, "%s: --light-streams is not supported (vpl and vol-primitivies only)\n", cmd.c_str()); return 2;
         } else if (a == "--tree-build" && cmd != "vol-primitivies") {
@@ -129,6 +133,10 @@ int main(int argc, char** argv) {
             else if (a == "--light-streams") light_streams = val();
             else if (a == "--tree-build") tree_build = val();
             else { std::fprintf(stderr, "unknown vol-primitivies option %s\n", a.c_str()); return 2; }
+        } else if (cmd == "plane-single") {
+            if (a == "-n" || a == "--nb-primitive") plane_nb = val();
+            else if (a == "-s" || a == "--strategy") plane_strategy = val();
+            else { std::fprintf(stderr, "unknown plane-single option %s\n", a.c_str()); return 2; }
         } else if (cmd == "light-tracing") {
             if (a == "-m" || a == "--max-depth") max_depth = val();
             else if (a == "-n" || a == "--min-depth") min_depth = val();
@@ -221,6 +229,34 @@ int main(int argc, char** argv) {
         volp.device = device;
         volp.options = options;
     }
+    // plane-single: the same limits as vol-primitivies, and it needs the medium
+    IntegratorSinglePlane plane;
+    if (cmd == "plane-single") {
+        static const char* const names[] = {"uv", "vt", "ut", "average", "discrete_mis", "ualpha", "cmis"};      // rl_plane_strategy, by value
+        int which = -1;
+        for (int k = 0; k < 7; k++) if (plane_strategy == names[k]) which = k;
+        if (which < 0) { std::fprintf(stderr, "%s is not a correct strategy choice (uv, ut, vt, average, discrete_mis, valpha, cmis)\n", plane_strategy.c_str()); return 2; }
+        plane.strategy = (rl_plane_strategy)which;
+        if (rng == "stratified" || rng.rfind("stratified:", 0) == 0) { std::fprintf(stderr, "plane-single: -r stratified is not supported (independent[:SEED] only)\n"); return 2; }
+        if (mode_given && mode != RL_STREAM_REFERENCE_ORDER) { std::fprintf(stderr, "plane-single: --stream-mode per-sample is not supported (the gather uses reference-order streams)\n"); return 2; }
+        if (numerics == RL_NUMERICS_FAST) { std::fprintf(stderr, "plane-single: --numerics fast is not supported\n"); return 2; }
+        if (gpus > 1) { std::fprintf(stderr, "plane-single: --gpus > 1 is not supported\n"); return 2; }
+        if (!average.empty() || !equal_time.empty()) { std::fprintf(stderr, "plane-single: -a / -e are not supported\n"); return 2; }
+        if (frames_in_flight > 1) { std::fprintf(stderr, "plane-single: --frames-in-flight is not supported\n"); return 2; }
+        char* end = nullptr;
+        const unsigned long long n = std::strtoull(plane_nb.c_str(), &end, 10);
+        if (plane_nb.empty() || *end != '\0' || n == 0 || n > (unsigned long long)RL_VPL_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", plane_nb.c_str(), (int)RL_VPL_MAX); return 2; }
+        plane.nb_primitive = (uint32_t)n;
+        {   // "Volume integrator need a volume (add -m )": the medium string as it is parsed below
+            std::vector<std::string> parts;
+            std::stringstream ss(medium);
+            for (std::string tok; std::getline(ss, tok, ':');) parts.push_back(tok);
+            const float sigma_s = parts.size() > 0 ? std::strtof(parts[0].c_str(), nullptr) : 0.0f, sigma_a = parts.size() > 1 ? std::strtof(parts[1].c_str(), nullptr) : 0.0f;
+            if (sigma_a + sigma_s == 0.0f) { std::fprintf(stderr, "plane-single: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n"); return 2; }
+        }
+        plane.device = device;
+        plane.options = options;
+    }
     // the sampler (cli.rs:876-896): the master sampler that draws the block seeds is IndependentSampler(SEED) for both kinds — OS entropy without a seed, as
     // IndependentSampler::default() / StratifiedSampler's random() are; `stratified:SEED` is this drop-in's reproducible form.  stratified =
     // RL_STREAM_STRATIFIED: StratifiedSampler::create(spp, 4) on every pixel (include/rustlight_amd.h)
@@ -281,7 +317,7 @@ int main(int argc, char** argv) {
         }
         scene->build_emitters(use_ats);      // scene.build_emitters(use_ats) (cli.rs:432)
         IntegratorPathTracing integrator;
-        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies") strategy = "all";       // (the path integrator below is not used)
+        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies" || cmd == "plane-single") strategy = "all";       // (the path integrator below is not used)
         integrator.min_depth = match_infinity(min_depth);
         integrator.max_depth = match_infinity(max_depth);
         integrator.rr_depth = match_infinity(rr_depth);
@@ -312,6 +348,8 @@ int main(int argc, char** argv) {
             img = vpl.compute(sampler, *scene); elapsed_ms = vpl.last_stats.render_ms;
         } else if (cmd == "vol-primitivies") {
             img = volp.compute(sampler, *scene); elapsed_ms = volp.last_stats.render_ms;
+        } else if (cmd == "plane-single") {
+            img = plane.compute(sampler, *scene); elapsed_ms = plane.last_stats.render_ms;
         } else if (cmd == "light-tracing") {
             if (!equal_time.empty()) {
                 IntegratorEqualTime<IntegratorLightTracing> eq{light, std::strtod(equal_time.c_str(), nullptr) * 1000.0};

@@ -382,6 +382,42 @@ struct IntegratorVolPrimitives {
     }
 };
 
+// struct IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs:280-294) + Integrator::compute, seed for seed the reference:
+// the planes from the main sampler (rl_plane_generate), the plane tree (rl_plane_map_build), the block seeds from the sampler the generation leaves, the
+// gather on reference-order streams (rl_render_plane_single).
+struct IntegratorSinglePlane {
+    uint32_t nb_primitive = 128;
+    rl_plane_strategy strategy = RL_PLANE_STRATEGY_AVERAGE;
+    int device = 0;
+    std::vector<std::pair<std::string, std::string>> options;
+    rl_render_stats last_stats{}, last_generation_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        rl_context* ctx = nullptr;
+        int rc = rl_context_create(scene.handle, device, &ctx);
+        if (rc != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
+        for (const auto& o : options)
+            if (rl_context_set_option(ctx, o.first.c_str(), o.second.c_str()) != RL_OK) { const std::string e = rl_last_error(); rl_context_destroy(ctx); throw std::runtime_error("--option " + o.first + ": " + e); }
+        BufferCollection img;
+        rl_scene_image_size(scene.handle, &img.width, &img.height);
+        img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
+        rl_plane_set* planes = nullptr;
+        rl_plane_map* map = nullptr;
+        rc = rl_plane_generate(ctx, nb_primitive, strategy, &sampler.rnd, &planes, &last_generation_stats);
+        if (rc == RL_OK) rc = rl_plane_map_build(ctx, planes, &map);
+        if (rc == RL_OK) {
+            std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
+            rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
+            rc = rl_render_plane_single(ctx, map, (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), img.primal.data(), &last_stats);
+        }
+        const std::string err = rc == RL_OK ? std::string() : std::string(rl_last_error());
+        rl_plane_map_destroy(map);
+        rl_plane_destroy(planes);
+        rl_context_destroy(ctx);
+        if (rc != RL_OK) throw std::runtime_error("plane-single: " + err);
+        return img;
+    }
+};
+
 // IntegratorAverage (src/integrators/avg.rs:5-131) and IntegratorEqualTime (src/integrators/equal_time.rs:4-66):
 // host loops around any inner integrator with `compute(IndependentSampler&, Scene&)`.
 template <class T, class = void> struct has_frames_in_flight : std::false_type {};

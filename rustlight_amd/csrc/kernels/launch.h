@@ -1,5 +1,5 @@
 // launch.h — host-side launchers of the kernel families that live in their own translation units (fused_*.hip, fusedq_*.hip, fused_strat_*.hip,
-// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip), so that the families compile in parallel, and
+// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, plane_*.hip), so that the families compile in parallel, and
 // the dispatcher every one of them maps its run-time arguments to template arguments with (with_bsdf, with_flag).  Launch errors are picked up by
 // the caller's hipGetLastError().
 #pragma once
@@ -92,6 +92,33 @@ struct BreConst {
     float norm_photon;                  // 1 / paths shot
 };
 
+// IntegratorSinglePlane (plane.hip.h): the rectangular lights, the generation's constants, and for the gather the plane tree in visiting order with the
+// planes in leaf order (host/planetree.cpp)
+struct PlaneLight { float o[3], u_l, u[3], v_l, v[3], pad0, n[3], pad1, emission[3], pad2; };      // RectangularLightSource, 5 float4
+enum { PLANE_GEN_PLANES = 0, PLANE_GEN_ITERATIONS = 1, PLANE_GEN_DRAWS = 2, PLANE_GEN_WORDS = 3 };
+struct PlaneGenConst {
+    unsigned nb_primitive, cap;         // stop once nb_primitive planes are stored; records beyond cap are not written
+    int strategy;                       // rl_plane_strategy
+    unsigned n_lights;
+    const PlaneLight* lights;
+    float sigma_t[3], sigma_s[3];       // the medium's
+    unsigned* words;                    // [cap][RL_PLANE_WORDS]
+    unsigned long long* gen_state;      // [4] the main sampler, read and written back
+    unsigned long long* gen_out;        // [PLANE_GEN_WORDS] planes stored, iterations (number_plane_gen), draws
+};
+enum { STAT_PLANE_NODES = 5, STAT_PLANE_ISECT = 6, STAT_PLANE_VISIBLE = 7,            // the gather's statistics rows: plane-tree nodes entered, planes intersected, of those visible — bits 0..23 ...
+       STAT_PLANE_NODES_HI = 1, STAT_PLANE_ISECT_HI = 2, STAT_PLANE_VISIBLE_HI = 3 };  // ... and the bits from 24 up, in the rows of STAT_VERTICES / STAT_EXT_RAYS / STAT_SHADOW_RAYS (the host derives those counters)
+enum { PLANE_MODE_PLAIN = 0, PLANE_MODE_DISCRETE_MIS = 1, PLANE_MODE_CMIS = 2 };      // k_plane_gather's instantiations: a constant weight, DiscreteMIS, ContinousMIS
+struct PlaneConst {
+    const float4* nodes;                // [n_nodes][2]: p_min.xyz, p_max.x | p_max.yz, skip, first << 3 | count
+    const float4* planes;               // [n_planes][4]: o, length0 | d0, length1 | d1, type + 4 * id_emitter | weight, 0
+    const PlaneLight* lights;
+    unsigned n_nodes;
+    float w;                            // the strategy's constant weight: 1, or 1 / 3 for Average (DiscreteMIS computes its own)
+    float n_lights_f;                   // emitters.len() as f32
+    float inv_gen;                      // 1.0 / number_plane_gen as f32
+};
+
 // mat: the scene's one BSDF type, or -1 = run-time switch per vertex.  area_only: every emitter is a mesh area light and there is no light
 // tree (the NEE code of the other emitter kinds is compiled out: same results, 84 -> 21 spilled VGPRs on the diffuse Cornell box)
 void launch_fused_lds(int mat, bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc);
@@ -137,6 +164,10 @@ void launch_vpl_paths_stream(bool write, int mat, bool medium, dim3 grid, dim3 b
 // IntegratorVolPrimitives' beam radiance estimate (bre.hip.h): k_bre_gather over the owned blocks; hg: the medium's phase function is Henyey-Greenstein
 void launch_bre_lds(bool hg, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BreConst& bc);
 void launch_bre_stream(bool hg, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BreConst& bc);
+// IntegratorSinglePlane (plane.hip.h): k_plane_generate on one lane (plane_generate.hip); k_plane_gather over the owned blocks, mode = PLANE_MODE_*
+void launch_plane_generate(hipStream_t st, const PlaneGenConst& gc);
+void launch_plane_lds(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PlaneConst& pc);
+void launch_plane_stream(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PlaneConst& pc);
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)
 void dump_stage_timers_stream();
 void dump_chain_timers_lds();      // dev-only (-DRL_STAGE_TIMERS): cycle shares of k_stream_chain's stages

@@ -1,0 +1,68 @@
+// plane_generate.hip — IntegratorSinglePlane's plane pass (plane_single.rs:326-427): k_plane_generate, one lane, walks the main sampler's serial stream as
+// the reference does.  It runs on the device because the pass needs the deterministic logf / sinf / cosf, which only devmath.hip.h holds; it traces nothing,
+// so it opens no scene.  The state of the sampler comes from the host and goes back to it.
+//
+// Per iteration of `while planes.len() < nb_primitive`: one draw for id_emitter = (next() * n_lights as f32) as usize — clamped to n_lights - 1, where the
+// reference would index out of range: the one deliberate difference —, then one plane (UV / VT / UT / UAlpha / CMIS) or the three planes UV, VT, UT
+// (Average / DiscreteMIS).  A plane draws cosine_sample_hemisphere(next2d()) again while its z is 0, then next() for the medium's distance (of which
+// continued_t is used), next2d() for `sample` and next() for alpha.
+// Record (RL_PLANE_WORDS u32, the layout rl_plane_read documents): [0..2] o, [3..5] d0, [6..8] d1, [9] length0, [10] length1, [11..13] weight,
+// [14..15] sample, [16] plane type, [17] id_emitter.
+#include "common.hip.h"
+#include "plane.hip.h"
+
+namespace rl {
+
+__global__ void __launch_bounds__(64) k_plane_generate(PlaneGenConst gc) {
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    Rng rng; rng.s0 = gc.gen_state[0]; rng.s1 = gc.gen_state[1]; rng.s2 = gc.gen_state[2]; rng.s3 = gc.gen_state[3];
+    const Col sigma_t = mkc(gc.sigma_t[0], gc.sigma_t[1], gc.sigma_t[2]), sigma_s = mkc(gc.sigma_s[0], gc.sigma_s[1], gc.sigma_s[2]);
+    const bool three = gc.strategy == RL_PLANE_STRATEGY_AVERAGE || gc.strategy == RL_PLANE_STRATEGY_DISCRETE_MIS;
+    const unsigned single = gc.strategy == RL_PLANE_STRATEGY_UV ? RL_PLANE_UV : gc.strategy == RL_PLANE_STRATEGY_VT ? RL_PLANE_VT
+                          : gc.strategy == RL_PLANE_STRATEGY_UT ? RL_PLANE_UT : RL_PLANE_UALPHAT;
+    unsigned long long n_planes = 0, n_gen = 0, n_draws = 0;
+    while (n_planes < gc.nb_primitive) {
+        unsigned id = (unsigned)(rng_next_f32(rng) * (float)gc.n_lights);
+        n_draws++;
+        if (id >= gc.n_lights) id = gc.n_lights - 1u;
+        const PlaneLight& light = gc.lights[id];
+        for (unsigned k = 0; k < (three ? 3u : 1u); k++) {
+            const unsigned type = three ? (k == 0 ? RL_PLANE_UV : k == 1 ? RL_PLANE_VT : RL_PLANE_UT) : single;
+            // generate_plane (326-361)
+            V3 d_out = cosine_sample_hemisphere(smp_next2d(rng));
+            n_draws += 2;
+            while (d_out.z == 0.0f) { d_out = cosine_sample_hemisphere(smp_next2d(rng)); n_draws += 2; }
+            const V3 d = to_world(make_frame(pl3(light.n)), d_out);
+            // HomogenousVolume::sample on Ray::new(light.o, d) (volume.rs:95-135): continued_t, the distance sampled whatever the ray's tfar is
+            float xi = rng_next_f32(rng);
+            const float u3 = xi * 3.0f;
+            const int component = u3 != u3 ? 0 : (u3 <= 0.0f ? 0 : (u3 >= 255.0f ? 255 : (int)u3));   // `as u8`
+            xi = xi * 3.0f - (float)component;
+            const float t_sampled = div_rn(-m_logf(1.0f - xi), cget(sigma_t, component));
+            const V2 sample = smp_next2d(rng);
+            const float alpha = rng_next_f32(rng);
+            n_draws += 4;
+            const Plane p = plane_new(type, light, d, sample, alpha, t_sampled, sigma_s);
+            if (n_planes < gc.cap) {
+                unsigned* w = gc.words + (size_t)n_planes * RL_PLANE_WORDS;
+                w[0] = __float_as_uint(p.o.x); w[1] = __float_as_uint(p.o.y); w[2] = __float_as_uint(p.o.z);
+                w[3] = __float_as_uint(p.d0.x); w[4] = __float_as_uint(p.d0.y); w[5] = __float_as_uint(p.d0.z);
+                w[6] = __float_as_uint(p.d1.x); w[7] = __float_as_uint(p.d1.y); w[8] = __float_as_uint(p.d1.z);
+                w[9] = __float_as_uint(p.l0); w[10] = __float_as_uint(p.l1);
+                w[11] = __float_as_uint(p.weight.r); w[12] = __float_as_uint(p.weight.g); w[13] = __float_as_uint(p.weight.b);
+                w[14] = __float_as_uint(sample.x); w[15] = __float_as_uint(sample.y);
+                w[16] = type; w[17] = id;
+            }
+            n_planes++;
+        }
+        n_gen++;
+    }
+    gc.gen_state[0] = rng.s0; gc.gen_state[1] = rng.s1; gc.gen_state[2] = rng.s2; gc.gen_state[3] = rng.s3;
+    gc.gen_out[PLANE_GEN_PLANES] = n_planes; gc.gen_out[PLANE_GEN_ITERATIONS] = n_gen; gc.gen_out[PLANE_GEN_DRAWS] = n_draws;
+}
+
+void launch_plane_generate(hipStream_t st, const PlaneGenConst& gc) {
+    hipLaunchKernelGGL(k_plane_generate, dim3(1), dim3(64), 0, st, gc);
+}
+
+}  // namespace rl

@@ -324,6 +324,9 @@ struct rl_context {
     BvhBuild bvh_dump;                // kept for rl_debug_bvh and for the two-level records (built on first use)
     Knobs knobs;                      // execution options: the environment as rl_context_create found it, then rl_context_set_option (knobs.h)
     LightConst light_cam{};           // rl_render_light: the camera's inverses and image rectangle (the splat buffers are set per render)
+    std::vector<RectLight> rect_lights;      // plane-single: the light meshes as RectangularLightSource, or why they are refused
+    int rect_lights_rc = RL_OK;
+    std::string rect_lights_err;
 };
 
 template <typename T>
@@ -458,6 +461,10 @@ extern "C" int rl_context_create(const rl_scene* scene, int device, rl_context**
             ctx->light_cam.rect_max[0] = std::fmax(p0.x, p1.x) / zmax; ctx->light_cam.rect_max[1] = std::fmax(p0.y, p1.y) / zmax;
         }
         ds.medium = scene->medium;
+        {
+            const char* why = "";
+            if ((ctx->rect_lights_rc = build_rect_lights(*scene, &ctx->rect_lights, &why)) != RL_OK) ctx->rect_lights_err = why;
+        }
         ctx->area_lights_only = scene->ats_root < 0 && !ctx->knobs.has(K_GENERIC_LIGHTS);
         for (const EmitterRecord& e : scene->emitters) if (e.kind != EMITTER_MESH) ctx->area_lights_only = false;
         for (const EmitterRecord& e : scene->emitters) if (e.kind == EMITTER_DIRECTIONAL) ctx->has_directional = true;
@@ -1440,6 +1447,219 @@ extern "C" int rl_render_bre(rl_context* ctx, const rl_photon_map* map, uint32_t
         stats->vertices = 0; stats->shadow_rays = 0;      // (their rows carried the high parts of the two tree counters)
         stats->reserved[0] = fr.totals[STAT_BRE_NODES] + (fr.totals[STAT_BRE_NODES_HI] << 24);
         stats->reserved[1] = fr.totals[STAT_BRE_PHOTONS] + (fr.totals[STAT_BRE_PHOTONS_HI] << 24);
+        stats->iterations = 1; stats->kernel_launches = n_owned > 0 ? 1 : 0;
+        if (fr.timing) {
+            float t = 0.0f;
+            if (hipEventElapsedTime(&t, ctx->events[0], ctx->events[1]) == hipSuccess) stats->ms_other = t;
+            (void)hipGetLastError();
+        }
+    }
+    return RL_OK;
+}
+
+// ---- IntegratorSinglePlane (plane_single.rs): rl_plane_generate makes the planes on one lane (k_plane_generate, plane_generate.hip) and brings them to the
+// host, rl_plane_map_build sorts them into the plane tree there (host/planetree.cpp) and uploads tree, planes and lights, rl_render_plane_single gathers them
+// along every camera ray (k_plane_gather, plane.hip.h)
+struct rl_plane_set {
+    const rl_context* ctx;            // the context that made it (compared, never dereferenced)
+    std::vector<uint32_t> words;      // [n_planes][RL_PLANE_WORDS]
+    uint64_t n_planes = 0, n_gen = 0;
+    int strategy = 0;
+};
+struct rl_plane_map {
+    const rl_context* ctx;
+    int device;
+    HipBuffer<float4> nodes;          // [n_nodes][2]
+    HipBuffer<float4> planes;         // [n_planes][4], in leaf order
+    HipBuffer<PlaneLight> lights;
+    uint64_t n_planes = 0, n_nodes = 0, n_gen = 0, n_lights = 0;
+    int strategy = 0;
+};
+// what every plane entry point refuses before any kernel runs
+static int check_plane_scene(const rl_context* ctx) {
+    if (ctx->ds.medium.enabled == 0) { rl_set_error("plane-single needs a medium (add -m; the reference panics, plane_single.rs:303)"); return RL_ERR_UNSUPPORTED; }
+    if (ctx->rect_lights_rc != RL_OK) { rl_set_error(ctx->rect_lights_err); return ctx->rect_lights_rc; }
+    return RL_OK;
+}
+static std::vector<PlaneLight> plane_lights(const rl_context* ctx) {
+    std::vector<PlaneLight> out;
+    for (const RectLight& r : ctx->rect_lights) {
+        PlaneLight l{};
+        for (int k = 0; k < 3; k++) { l.o[k] = r.o[k]; l.u[k] = r.u[k]; l.v[k] = r.v[k]; l.n[k] = r.n[k]; l.emission[k] = r.emission[k]; }
+        l.u_l = r.u_l; l.v_l = r.v_l;
+        out.push_back(l);
+    }
+    return out;
+}
+extern "C" int rl_plane_generate(rl_context* ctx, uint32_t nb_primitive, int strategy, rl_sampler* sampler, rl_plane_set** out, rl_render_stats* stats) {
+    if (!ctx || !sampler || !out) return RL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (strategy < RL_PLANE_STRATEGY_UV || strategy > RL_PLANE_STRATEGY_CMIS) { rl_set_error("strategy must be one of RL_PLANE_STRATEGY_*"); return RL_ERR_INVALID_ARGUMENT; }
+    if (nb_primitive == 0 || nb_primitive > (uint32_t)RL_VPL_MAX) { rl_set_error("nb_primitive must be 1 .. RL_VPL_MAX"); return RL_ERR_INVALID_ARGUMENT; }
+    int rcode;
+    if ((rcode = check_plane_scene(ctx)) != RL_OK) return rcode;
+    HIP_OK(hipSetDevice(ctx->device));
+    const std::vector<PlaneLight> lights = plane_lights(ctx);
+    const unsigned cap = nb_primitive + 2u;              // Average / DiscreteMIS store three planes per iteration
+    HipBuffer<unsigned> d_words;
+    HipBuffer<PlaneLight> d_lights;
+    HipBuffer<unsigned long long> d_gen;                 // [4] sampler, then [PLANE_GEN_WORDS] counters
+    if ((rcode = d_words.ensure((size_t)cap * RL_PLANE_WORDS)) != RL_OK || (rcode = d_lights.ensure(lights.size())) != RL_OK ||
+        (rcode = d_gen.ensure(4 + PLANE_GEN_WORDS)) != RL_OK) return rcode;
+    const hipStream_t st = ctx->stream;
+    unsigned long long h_gen[4 + PLANE_GEN_WORDS] = {sampler->s[0], sampler->s[1], sampler->s[2], sampler->s[3]};
+    HIP_OK(hipMemcpyAsync(d_gen.get(), h_gen, sizeof(h_gen), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_lights.get(), lights.data(), lights.size() * sizeof(PlaneLight), hipMemcpyHostToDevice, st));
+    PlaneGenConst gc{};
+    gc.nb_primitive = nb_primitive; gc.cap = cap; gc.strategy = strategy;
+    gc.n_lights = (unsigned)lights.size(); gc.lights = d_lights.get();
+    for (int k = 0; k < 3; k++) { gc.sigma_t[k] = ctx->ds.medium.sigma_t[k]; gc.sigma_s[k] = ctx->ds.medium.sigma_s[k]; }
+    gc.words = d_words.get(); gc.gen_state = d_gen.get(); gc.gen_out = d_gen.get() + 4;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timing = stats != nullptr && !ctx->knobs.has(K_NO_EVENTS);
+    if (timing) { HIP_OK(hipEventCreate(&ev[0])); HIP_OK(hipEventCreate(&ev[1])); HIP_OK(hipEventRecord(ev[0], st)); }
+    const auto t0 = std::chrono::steady_clock::now();
+    launch_plane_generate(st, gc);
+    if (timing) HIP_OK(hipEventRecord(ev[1], st));
+    HIP_OK(hipMemcpyAsync(h_gen, d_gen.get(), sizeof(h_gen), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    float ms = 0.0f;
+    if (timing) { (void)hipEventElapsedTime(&ms, ev[0], ev[1]); (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); (void)hipGetLastError(); }
+    const unsigned long long* g = h_gen + 4;
+    if (g[PLANE_GEN_PLANES] < nb_primitive || g[PLANE_GEN_PLANES] > cap) { rl_set_error("plane-single: the generation stored an unexpected number of planes"); return RL_ERR_HIP; }
+    auto set = std::make_unique<rl_plane_set>();
+    set->ctx = ctx;
+    set->n_planes = g[PLANE_GEN_PLANES]; set->n_gen = g[PLANE_GEN_ITERATIONS]; set->strategy = strategy;
+    set->words.resize((size_t)set->n_planes * RL_PLANE_WORDS);
+    HIP_OK(hipMemcpy(set->words.data(), d_words.get(), set->words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if ((rcode = check_plane_records(set->words.data(), (size_t)set->n_planes)) != RL_OK) return rcode;
+    sampler->s[0] = h_gen[0]; sampler->s[1] = h_gen[1]; sampler->s[2] = h_gen[2]; sampler->s[3] = h_gen[3];
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->camera_samples = set->n_gen; stats->vertices = set->n_planes; stats->rng_draws = g[PLANE_GEN_DRAWS];
+        stats->iterations = 1; stats->kernel_launches = 1; stats->ms_prepass = ms;
+        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    *out = set.release();
+    return RL_OK;
+}
+extern "C" int rl_plane_info(const rl_plane_set* set, uint64_t* n_planes, uint64_t* number_plane_gen, int* strategy) {
+    if (!set) return RL_ERR_INVALID_ARGUMENT;
+    if (n_planes) *n_planes = set->n_planes;
+    if (number_plane_gen) *number_plane_gen = set->n_gen;
+    if (strategy) *strategy = set->strategy;
+    return RL_OK;
+}
+extern "C" int rl_plane_read(const rl_plane_set* set, uint32_t* words, size_t n_words) {
+    if (!set || !words || n_words != set->words.size()) return RL_ERR_INVALID_ARGUMENT;
+    std::copy(set->words.begin(), set->words.end(), words);
+    return RL_OK;
+}
+extern "C" void rl_plane_destroy(rl_plane_set* set) { delete set; }
+extern "C" int rl_plane_map_build(rl_context* ctx, const rl_plane_set* set, rl_plane_map** out) {
+    if (!ctx || !set || !out) return RL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    int rcode;
+    if ((rcode = check_plane_scene(ctx)) != RL_OK) return rcode;
+    if (set->ctx != ctx) { rl_set_error("the plane set belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
+    PhotonTree tree;
+    if ((rcode = build_plane_tree(set->words.data(), (size_t)set->n_planes, &tree)) != RL_OK) return rcode;
+    const size_t n_nodes = tree.n_nodes(), n_planes = (size_t)set->n_planes;
+    std::vector<float4> h_nodes(2 * n_nodes), h_planes(4 * n_planes);
+    for (size_t i = 0; i < n_nodes; i++) {
+        const float* b = &tree.boxes[6 * i];
+        const uint32_t skip = tree.links[3 * i], fc = tree.links[3 * i + 1] << 3 | tree.links[3 * i + 2];
+        float fs, ff;
+        std::memcpy(&fs, &skip, sizeof fs); std::memcpy(&ff, &fc, sizeof ff);
+        h_nodes[2 * i] = make_float4(b[0], b[1], b[2], b[3]);
+        h_nodes[2 * i + 1] = make_float4(b[4], b[5], fs, ff);
+    }
+    for (size_t i = 0; i < n_planes; i++) {
+        const uint32_t* w = &set->words[(size_t)tree.order[i] * RL_PLANE_WORDS];
+        float f[14];
+        std::memcpy(f, w, sizeof f);                                   // o, d0, d1, length0, length1, weight
+        const uint32_t tb = w[16] | w[17] << 2;
+        float ft;
+        std::memcpy(&ft, &tb, sizeof ft);
+        h_planes[4 * i] = make_float4(f[0], f[1], f[2], f[9]);
+        h_planes[4 * i + 1] = make_float4(f[3], f[4], f[5], f[10]);
+        h_planes[4 * i + 2] = make_float4(f[6], f[7], f[8], ft);
+        h_planes[4 * i + 3] = make_float4(f[11], f[12], f[13], 0.0f);
+    }
+    const std::vector<PlaneLight> lights = plane_lights(ctx);
+    HIP_OK(hipSetDevice(ctx->device));
+    auto map = std::make_unique<rl_plane_map>();
+    map->ctx = ctx; map->device = ctx->device;
+    if ((rcode = map->nodes.ensure(h_nodes.size())) != RL_OK || (rcode = map->planes.ensure(h_planes.size())) != RL_OK || (rcode = map->lights.ensure(lights.size())) != RL_OK) return rcode;
+    HIP_OK(hipMemcpy(map->nodes.get(), h_nodes.data(), h_nodes.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(map->planes.get(), h_planes.data(), h_planes.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(map->lights.get(), lights.data(), lights.size() * sizeof(PlaneLight), hipMemcpyHostToDevice));
+    map->n_planes = n_planes; map->n_nodes = n_nodes; map->n_gen = set->n_gen; map->n_lights = lights.size(); map->strategy = set->strategy;
+    *out = map.release();
+    return RL_OK;
+}
+extern "C" int rl_plane_map_info(const rl_plane_map* map, uint64_t* n_planes, uint64_t* n_nodes, uint64_t* number_plane_gen, int* strategy) {
+    if (!map) return RL_ERR_INVALID_ARGUMENT;
+    if (n_planes) *n_planes = map->n_planes;
+    if (n_nodes) *n_nodes = map->n_nodes;
+    if (number_plane_gen) *number_plane_gen = map->n_gen;
+    if (strategy) *strategy = map->strategy;
+    return RL_OK;
+}
+extern "C" int rl_plane_map_read(const rl_plane_map* map, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t plane_capacity, float* planes) {
+    if (!map || !node_boxes || !node_links || !planes) return RL_ERR_INVALID_ARGUMENT;
+    if (node_capacity < map->n_nodes || plane_capacity < map->n_planes) { rl_set_error("rl_plane_map_read: a capacity is too small"); return RL_ERR_INVALID_ARGUMENT; }
+    HIP_OK(hipSetDevice(map->device));
+    std::vector<float4> h_nodes(2 * (size_t)map->n_nodes);
+    HIP_OK(hipMemcpy(h_nodes.data(), map->nodes.get(), h_nodes.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(planes, map->planes.get(), (size_t)map->n_planes * 4 * sizeof(float4), hipMemcpyDeviceToHost));
+    unpack_photon_nodes(h_nodes, (size_t)map->n_nodes, node_boxes, node_links);
+    return RL_OK;
+}
+extern "C" void rl_plane_map_destroy(rl_plane_map* map) {
+    if (!map) return;
+    (void)hipSetDevice(map->device);
+    delete map;
+}
+extern "C" int rl_render_plane_single(rl_context* ctx, const rl_plane_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
+                                      const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats) {
+    int rcode;
+    if (!map) return RL_ERR_INVALID_ARGUMENT;
+    const BreFrameParams fp{spp};
+    if ((rcode = check_frame(ctx, &fp, block_seeds, n_blocks, out_rgb)) != RL_OK) return rcode;
+    if ((rcode = check_plane_scene(ctx)) != RL_OK) return rcode;
+    if (map->ctx != ctx) { rl_set_error("the plane map belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
+    if (shard_index >= (shard_count ? shard_count : 1)) return RL_ERR_INVALID_ARGUMENT;
+    if (spp > (uint32_t)RL_VPL_MAX_SPP) { rl_set_error("plane-single takes at most RL_VPL_MAX_SPP spp (a block's stream is entered with 32-bit jumps, 2 draws per sample)"); return RL_ERR_UNSUPPORTED; }
+    HIP_OK(hipSetDevice(ctx->device));
+    RenderFrame fr(ctx, block_seeds, n_blocks, out_rgb, 0, nullptr, stats, shard_index, shard_count);
+    const unsigned n_owned = (unsigned)fr.owned.size();
+    if ((rcode = fr.alloc_tables()) != RL_OK || (rcode = fr.alloc_output(std::max(n_owned, 1u))) != RL_OK) return rcode;
+    if ((rcode = fr.upload(false, true)) != RL_OK || (rcode = fr.zero_rows()) != RL_OK) return rcode;
+    RenderConst rc = fr.render_const(spp, RL_STREAM_REFERENCE_ORDER, seed_variant);
+    rc.n_items = fr.n_pixels;
+    PlaneConst pc{};
+    pc.nodes = map->nodes.get(); pc.planes = map->planes.get(); pc.lights = map->lights.get(); pc.n_nodes = (unsigned)map->n_nodes;
+    pc.w = map->strategy == RL_PLANE_STRATEGY_AVERAGE ? 1.0f / 3.0f : 1.0f;
+    pc.n_lights_f = (float)map->n_lights;                                   // emitters.len() as f32
+    pc.inv_gen = 1.0f / (float)map->n_gen;                                  // 1.0 / number_plane_gen as f32
+    const int mode = map->strategy == RL_PLANE_STRATEGY_DISCRETE_MIS ? PLANE_MODE_DISCRETE_MIS : map->strategy == RL_PLANE_STRATEGY_CMIS ? PLANE_MODE_CMIS : PLANE_MODE_PLAIN;
+    StackConf stc;
+    if ((rcode = stack_conf(ctx, std::max(n_owned, 1u) * 256u, &stc)) != RL_OK) return rcode;
+    const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
+    const hipStream_t st = fr.st;
+    if ((rcode = fr.grow_events(2)) != RL_OK) return rcode;
+    if (fr.timing) hipEventRecord(ctx->events[0], st);
+    if (n_owned > 0) (ctx->lds_scene ? launch_plane_lds : launch_plane_stream)(mode, dim3(n_owned), dim3(256), lds, st, rc, ctx->ds, stc, pc);
+    if (fr.timing) hipEventRecord(ctx->events[1], st);
+    if ((rcode = fr.download()) != RL_OK) return rcode;
+    if (stats) {
+        // (the rows of vertices / extension_rays / shadow_rays carried the high parts of the three walk counters)
+        stats->reserved[0] = fr.totals[STAT_PLANE_NODES] + (fr.totals[STAT_PLANE_NODES_HI] << 24);
+        stats->reserved[1] = fr.totals[STAT_PLANE_ISECT] + (fr.totals[STAT_PLANE_ISECT_HI] << 24);
+        stats->reserved[2] = fr.totals[STAT_PLANE_VISIBLE] + (fr.totals[STAT_PLANE_VISIBLE_HI] << 24);
+        stats->vertices = 0; stats->extension_rays = stats->camera_samples; stats->shadow_rays = stats->reserved[1]; stats->rng_draws = 2 * stats->camera_samples;
         stats->iterations = 1; stats->kernel_launches = n_owned > 0 ? 1 : 0;
         if (fr.timing) {
             float t = 0.0f;

@@ -1,0 +1,16 @@
+"""Register budgets of the photon-plane gather (kernels/plane.hip.h), read from the code-object notes like tests/test_vpl_paths_resources.py does: every
+instantiation of k_plane_gather without spill and without a private segment, at three waves per SIMD or more — the bar k_vpl_shoot is held to."""
+from rustlight_amd import resources
+
+
+def test_every_k_plane_gather_keeps_its_budget(built):
+    rows = {(r["object"], r["kernel"]): r for r in resources.kernel_resources()}
+    seen = 0
+    for obj, lds in (("plane_lds.hip.o", "true"), ("plane_stream.hip.o", "false")):
+        for mode in (0, 1, 2):                                 # a constant weight, DiscreteMIS, ContinousMIS
+            r = rows[(obj, f"k_plane_gather<{lds}, {mode}>")]
+            assert r["vgpr_spill"] == 0, r
+            assert r["scratch_bytes_per_lane"] == 0, r
+            assert r["max_waves_per_simd_by_vgpr"] >= 3, r
+            seen += 1
+    assert seen == 6 == sum(1 for (_, k) in rows if k.startswith("k_plane_gather<"))
