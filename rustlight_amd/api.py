@@ -564,22 +564,22 @@ class Context:
     def photon_tree_build_device(self, words, radius):
         """rl_photon_tree_build_device: photon_tree_build's arrays, computed by the kernels of the device build on this context's device."""
         w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, VPL_WORDS)
-        n = C.c_size_t()
-        _check(lib().rl_photon_tree_build_device(self.h, abi.u32ptr(w), w.shape[0], radius, 0, C.byref(n), None, None, None))
-        boxes, links, order = np.zeros((n.value, 6), np.float32), np.zeros((n.value, 3), np.uint32), np.zeros(w.shape[0], np.uint32)
-        _check(lib().rl_photon_tree_build_device(self.h, abi.u32ptr(w), w.shape[0], radius, n.value, C.byref(n), abi.fptr(boxes), abi.u32ptr(links), abi.u32ptr(order)))
-        return boxes, links, order
+        return _tree_arrays(lambda *out: lib().rl_photon_tree_build_device(self.h, abi.u32ptr(w), w.shape[0], radius, *out), w.shape[0])
+
+    def _render_gather(self, fn, handle, seeds, spp, seed_variant, shard_index, shard_count, names):
+        """rl_render_bre / rl_render_plane_single: (image HxWx3 f32, stats dict with reserved[k] under names[k])."""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        st = abi.RenderStats()
+        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        _check(fn(self.h, handle, spp, seed_variant, shard_index, shard_count, abi.u64ptr(seeds), seeds.shape[0], abi.fptr(img), C.byref(st)))
+        d = st.as_dict()
+        d.update((name, int(st.reserved[k])) for k, name in enumerate(names))
+        return img, d
 
     def render_bre(self, photons: "PhotonMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
         """The beam radiance estimate's gather (vol_primitives.rs:712-790) through rl_render_bre: (image HxWx3 f32, stats dict).  stats: nodes_entered /
         photons_gathered = reserved[0] / reserved[1], ms_other = the gather kernel."""
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        st = abi.RenderStats()
-        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        _check(lib().rl_render_bre(self.h, photons.h, spp, seed_variant, shard_index, shard_count, abi.u64ptr(seeds), seeds.shape[0], abi.fptr(img), C.byref(st)))
-        d = st.as_dict()
-        d["nodes_entered"], d["photons_gathered"] = int(st.reserved[0]), int(st.reserved[1])
-        return img, d
+        return self._render_gather(lib().rl_render_bre, photons.h, seeds, spp, seed_variant, shard_index, shard_count, ("nodes_entered", "photons_gathered"))
 
     def plane_generate(self, sampler: "IndependentSampler", nb_primitive=128, strategy="average"):
         """IntegratorSinglePlane's plane pass (plane_single.rs:363-427) through rl_plane_generate: (PlaneSet, stats dict).  `sampler` is advanced as the
@@ -601,13 +601,8 @@ class Context:
     def render_plane_single(self, planes: "PlaneMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
         """IntegratorSinglePlane's gather (plane_single.rs:436-611) through rl_render_plane_single: (image HxWx3 f32, stats dict).  stats: nodes_entered /
         planes_intersected / planes_visible = reserved[0..2], shadow_rays = planes_intersected, ms_other = the gather kernel."""
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        st = abi.RenderStats()
-        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        _check(lib().rl_render_plane_single(self.h, planes.h, spp, seed_variant, shard_index, shard_count, abi.u64ptr(seeds), seeds.shape[0], abi.fptr(img), C.byref(st)))
-        d = st.as_dict()
-        d["nodes_entered"], d["planes_intersected"], d["planes_visible"] = int(st.reserved[0]), int(st.reserved[1]), int(st.reserved[2])
-        return img, d
+        return self._render_gather(lib().rl_render_plane_single, planes.h, seeds, spp, seed_variant, shard_index, shard_count,
+                                   ("nodes_entered", "planes_intersected", "planes_visible"))
 
     def trace(self, origins, directions):
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
@@ -804,11 +799,38 @@ class IntegratorLightTracing:
         return img
 
 
-class VplSet:
-    """rl_vpl_set: the VPLs of one generation, on the device of the context that made them (kept alive with it)."""
+class _DeviceHandle:
+    """A handle a Context made (kept alive with it), destroyed through the library function `_destroy` names."""
+    _destroy = None
 
-    def __init__(self, h, ctx: Context):
+    def __init__(self, h, ctx: "Context"):
         self.h, self.ctx = h, ctx
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(lib(), self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _tree_arrays(build, n_elements):
+    """The two calls of a tree build: build(capacity, n_nodes, boxes, links, order) first asks the node count with no arrays, then fills
+    (boxes [n, 6] f32, links [n, 3] u32, order [n_elements] u32)."""
+    n = C.c_size_t()
+    _check(build(0, C.byref(n), None, None, None))
+    boxes, links, order = np.zeros((n.value, 6), np.float32), np.zeros((n.value, 3), np.uint32), np.zeros(n_elements, np.uint32)
+    _check(build(n.value, C.byref(n), abi.fptr(boxes), abi.u32ptr(links), abi.u32ptr(order)))
+    return boxes, links, order
+
+
+class VplSet(_DeviceHandle):
+    """rl_vpl_set: the VPLs of one generation, on the device of the context that made them (kept alive with it)."""
+    _destroy = "rl_vpl_destroy"
 
     def info(self):
         """(VPLs stored, light paths shot)."""
@@ -830,28 +852,18 @@ class VplSet:
         """The records as a numpy structured array: kind, mesh, has_uv, pos, radiance, dir (wi / d_in / n), uv, frame (3 x 3 rows x, y, z)."""
         return self.words().view(VPL_RECORD_DTYPE).reshape(-1)
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().rl_vpl_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 VPL_RECORD_DTYPE = np.dtype([("kind", "<u4"), ("mesh", "<u4"), ("has_uv", "<u4"), ("pad", "<u4"), ("pos", "<f4", 3), ("radiance", "<f4", 3),
                              ("dir", "<f4", 3), ("uv", "<f4", 2), ("frame", "<f4", (3, 3))])
 assert VPL_RECORD_DTYPE.itemsize == 4 * VPL_WORDS
 
 
-class PhotonMap:
+class PhotonMap(_DeviceHandle):
     """rl_photon_map: photon tree and photons of one generation, on the device of the context that made them (kept alive with it)."""
+    _destroy = "rl_photon_map_destroy"
 
     def __init__(self, h, ctx: Context):
-        self.h, self.ctx = h, ctx
+        super().__init__(h, ctx)
         self.ms_build = None        # Context.photon_map: wall clock of the build call, ms
         self.ms_kernels = None      # the device build's kernel time, ms
 
@@ -868,27 +880,12 @@ class PhotonMap:
         _check(lib().rl_photon_map_info(self.h, C.byref(n), C.byref(m), C.byref(p), C.byref(r)))
         return int(n.value), int(m.value), int(p.value), float(r.value)
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().rl_photon_map_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def photon_tree_build(words, radius):
     """rl_photon_tree_build, host only: (boxes [n, 6] f32, links [n, 3] u32 = skip, first, count, order [n_photons] u32) of the photon tree over records
     `words` ([n_photons, VPL_WORDS] u32), nodes in the order the gather visits them."""
     w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, VPL_WORDS)
-    n = C.c_size_t()
-    _check(lib().rl_photon_tree_build(abi.u32ptr(w), w.shape[0], radius, 0, C.byref(n), None, None, None))
-    boxes, links, order = np.zeros((n.value, 6), np.float32), np.zeros((n.value, 3), np.uint32), np.zeros(w.shape[0], np.uint32)
-    _check(lib().rl_photon_tree_build(abi.u32ptr(w), w.shape[0], radius, n.value, C.byref(n), abi.fptr(boxes), abi.u32ptr(links), abi.u32ptr(order)))
-    return boxes, links, order
+    return _tree_arrays(lambda *out: lib().rl_photon_tree_build(abi.u32ptr(w), w.shape[0], radius, *out), w.shape[0])
 
 
 class IntegratorVolPrimitives:
@@ -943,11 +940,9 @@ def plane_strategy(strategy):
     return int(strategy)
 
 
-class PlaneSet:
+class PlaneSet(_DeviceHandle):
     """rl_plane_set: the planes of one rl_plane_generate."""
-
-    def __init__(self, h, ctx: Context):
-        self.h, self.ctx = h, ctx
+    _destroy = "rl_plane_destroy"
 
     def info(self):
         """(planes stored, number_plane_gen, strategy name)."""
@@ -964,23 +959,13 @@ class PlaneSet:
         _check(lib().rl_plane_read(self.h, abi.u32ptr(w), w.size))
         return w
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().rl_plane_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PlaneMap:
+class PlaneMap(_DeviceHandle):
     """rl_plane_map: plane tree, planes and lights of one generation, on the device of the context that made them (kept alive with it)."""
+    _destroy = "rl_plane_map_destroy"
 
     def __init__(self, h, ctx: Context):
-        self.h, self.ctx = h, ctx
+        super().__init__(h, ctx)
         self.ms_build = None        # Context.plane_map: wall clock of the build call, ms
 
     def info(self):
@@ -996,27 +981,12 @@ class PlaneMap:
         _check(lib().rl_plane_map_read(self.h, n_nodes, abi.fptr(boxes), abi.u32ptr(links), n_planes, abi.fptr(planes)))
         return boxes, links, planes
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().rl_plane_map_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def plane_tree_build(words):
     """rl_plane_tree_build, host only: (boxes [n, 6] f32, links [n, 3] u32 = skip, first, count, order [n_planes] u32) of the plane tree over records
     `words` ([n_planes, PLANE_WORDS] u32), nodes in the order the gather visits them."""
     w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, PLANE_WORDS)
-    n = C.c_size_t()
-    _check(lib().rl_plane_tree_build(abi.u32ptr(w), w.shape[0], 0, C.byref(n), None, None, None))
-    boxes, links, order = np.zeros((n.value, 6), np.float32), np.zeros((n.value, 3), np.uint32), np.zeros(w.shape[0], np.uint32)
-    _check(lib().rl_plane_tree_build(abi.u32ptr(w), w.shape[0], n.value, C.byref(n), abi.fptr(boxes), abi.u32ptr(links), abi.u32ptr(order)))
-    return boxes, links, order
+    return _tree_arrays(lambda *out: lib().rl_plane_tree_build(abi.u32ptr(w), w.shape[0], *out), w.shape[0])
 
 
 class IntegratorSinglePlane:

@@ -14,9 +14,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 
 #include "../kernels/wavefront.h"     // rl_set_error
-#include "../../../include/rustlight_amd.h"
 
 namespace rl {
 namespace {
@@ -43,10 +43,26 @@ struct PhotonElems {
 
 }  // namespace
 
-int build_photon_tree(const uint32_t* words, size_t n, float radius, PhotonTree* out) {
-    if (!out || (n && !words)) return RL_ERR_INVALID_ARGUMENT;
+int check_photon_radius(float radius) {
     if (!std::isfinite(radius) || !(radius > 0.0f)) { rl_set_error("the photon radius must be finite and > 0"); return RL_ERR_INVALID_ARGUMENT; }
-    if (n > (size_t)RL_VPL_MAX + 4096) { rl_set_error("too many photons"); return RL_ERR_INVALID_ARGUMENT; }
+    return RL_OK;
+}
+
+int copy_tree_out(const ElementTree& tree, size_t node_capacity, size_t* n_nodes, float* node_boxes, uint32_t* node_links, uint32_t* order, const char* who) {
+    *n_nodes = tree.n_nodes();
+    if (!node_boxes && !node_links && !order) return RL_OK;      // the size only
+    if (!node_boxes || !node_links || !order) return RL_ERR_INVALID_ARGUMENT;
+    if (node_capacity < tree.n_nodes()) { rl_set_error(std::string(who) + ": node_capacity is too small"); return RL_ERR_INVALID_ARGUMENT; }
+    std::copy(tree.boxes.begin(), tree.boxes.end(), node_boxes);
+    std::copy(tree.links.begin(), tree.links.end(), node_links);
+    std::copy(tree.order.begin(), tree.order.end(), order);
+    return RL_OK;
+}
+
+int build_photon_tree(const uint32_t* words, size_t n, float radius, ElementTree* out) {
+    if (!out || (n && !words)) return RL_ERR_INVALID_ARGUMENT;
+    if (check_photon_radius(radius) != RL_OK) return RL_ERR_INVALID_ARGUMENT;
+    if (n > kElementTreeMax) { rl_set_error("too many photons"); return RL_ERR_INVALID_ARGUMENT; }
     const PhotonElems e{words, radius};
     for (size_t i = 0; i < n; i++)
         for (int a = 0; a < 3; a++)
@@ -60,15 +76,8 @@ int build_photon_tree(const uint32_t* words, size_t n, float radius, PhotonTree*
 extern "C" int rl_photon_tree_build(const uint32_t* words, size_t n_photons, float radius, size_t node_capacity, size_t* n_nodes, float* node_boxes,
                                     uint32_t* node_links, uint32_t* order) {
     if (!n_nodes) return RL_ERR_INVALID_ARGUMENT;
-    rl::PhotonTree t;
+    rl::ElementTree t;
     const int rcode = rl::build_photon_tree(words, n_photons, radius, &t);
     if (rcode != RL_OK) return rcode;
-    *n_nodes = t.n_nodes();
-    if (!node_boxes && !node_links && !order) return RL_OK;      // the size only
-    if (!node_boxes || !node_links || !order) return RL_ERR_INVALID_ARGUMENT;
-    if (node_capacity < t.n_nodes()) { rl_set_error("rl_photon_tree_build: node_capacity is too small"); return RL_ERR_INVALID_ARGUMENT; }
-    std::copy(t.boxes.begin(), t.boxes.end(), node_boxes);
-    std::copy(t.links.begin(), t.links.end(), node_links);
-    std::copy(t.order.begin(), t.order.end(), order);
-    return RL_OK;
+    return rl::copy_tree_out(t, node_capacity, n_nodes, node_boxes, node_links, order, "rl_photon_tree_build");
 }

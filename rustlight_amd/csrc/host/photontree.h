@@ -1,6 +1,7 @@
 // photontree.h — the element trees the volumetric gathers walk (BHVAccel, src/accel.rs:458-581): the photon tree of the beam radiance estimate
 // (photontree.cpp) and the plane tree of the single-scattering photon planes (planetree.cpp), as the host hands them to the device and to
-// rl_photon_tree_build / rl_plane_tree_build.  Both are built by build_element_tree below; what differs is an element's box and its sort key.
+// rl_photon_tree_build / rl_plane_tree_build.  Both are ElementTrees built by build_element_tree below; what differs is an element's box and its sort key.
+// The device walks either with one loop (kernels/gather.hip.h); kernels/gather_render.hip.h packs the nodes for it.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -8,11 +9,16 @@
 #include <cstdint>
 #include <vector>
 
+#include "../../../include/rustlight_amd.h"
+
 namespace rl {
+
+// the most elements a tree takes: a generation stops at RL_VPL_MAX records and may overshoot by one path's
+constexpr size_t kElementTreeMax = (size_t)RL_VPL_MAX + 4096;
 
 // Nodes in the order the reference's gather visits them (node, right subtree, left subtree), so a walk needs no stack:
 // `i = entered ? i + 1 : skip[i]`, done at i == number of nodes.
-struct PhotonTree {
+struct ElementTree {
     std::vector<float> boxes;          // [node][6]: p_min, p_max
     std::vector<uint32_t> links;       // [node][3]: skip, first, count (count = 0: an inner node; first indexes `order`)
     std::vector<uint32_t> order;       // [element]: the record that stands at this place once every sort is done
@@ -26,7 +32,7 @@ struct PhotonTree {
 template <class E>
 struct ElementTreeBuilder {
     const E& e;
-    PhotonTree* t;
+    ElementTree* t;
     void build(size_t begin, size_t end) {
         float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};   // AABB::default()
         for (size_t i = begin; i < end; i++) {
@@ -51,7 +57,7 @@ struct ElementTreeBuilder {
     }
 };
 template <class E>
-void build_element_tree(const E& e, size_t n, PhotonTree* out) {
+void build_element_tree(const E& e, size_t n, ElementTree* out) {
     out->boxes.clear(); out->links.clear();
     out->order.resize(n);
     for (size_t i = 0; i < n; i++) out->order[i] = (uint32_t)i;
@@ -60,12 +66,16 @@ void build_element_tree(const E& e, size_t n, PhotonTree* out) {
 }
 
 // words: n records of RL_VPL_WORDS u32 (only the position, words 4..6, is read).  RL_OK, or RL_ERR_INVALID_ARGUMENT with rl_last_error set.
-int build_photon_tree(const uint32_t* words, size_t n, float radius, PhotonTree* out);
+int build_photon_tree(const uint32_t* words, size_t n, float radius, ElementTree* out);
+// what every photon entry point asks of the radius: RL_ERR_INVALID_ARGUMENT with rl_last_error set unless it is finite and > 0
+int check_photon_radius(float radius);
+// the tail of rl_photon_tree_build / rl_plane_tree_build (`who`): the node count, then — unless all three arrays are null — the tree into the caller's arrays
+int copy_tree_out(const ElementTree& tree, size_t node_capacity, size_t* n_nodes, float* node_boxes, uint32_t* node_links, uint32_t* order, const char* who);
 
 // The rectangular lights of the photon-plane integrators (planetree.cpp: RectangularLightSource::from_shape, plane_single.rs:38-75), in mesh order
 struct RectLight { float o[3], n[3], u[3], v[3], u_l, v_l, emission[3]; };
 // words: n records of RL_PLANE_WORDS u32 (o, d0, d1, length0, length1 are read).  RL_OK, or RL_ERR_INVALID_ARGUMENT with rl_last_error set.
-int build_plane_tree(const uint32_t* words, size_t n, PhotonTree* out);
+int build_plane_tree(const uint32_t* words, size_t n, ElementTree* out);
 // what build_plane_tree refuses, alone: RL_ERR_INVALID_ARGUMENT with rl_last_error set when a plane has a non-finite corner
 int check_plane_records(const uint32_t* words, size_t n);
 

@@ -4,7 +4,7 @@
 // (o + d0 l0) + d1 l1; its sort key is the plane's middle ((o + (d0 l0) 0.5) + (d1 l1) 0.5)[axis].
 //
 // The deviations are the photon tree's: a stable sort, and a plane with a non-finite corner is refused where the reference's
-// partial_cmp().unwrap() panics.  Node order and skip links are the photon tree's too, so the device walks both trees with the same loop.
+// partial_cmp().unwrap() panics.  Node order and skip links are the photon tree's too: both are ElementTrees, and the device walks them with one loop (kernels/gather.hip.h).
 #include <cmath>
 #include <cstring>
 
@@ -55,9 +55,9 @@ int check_plane_records(const uint32_t* words, size_t n) {
     return RL_OK;
 }
 
-int build_plane_tree(const uint32_t* words, size_t n, PhotonTree* out) {
+int build_plane_tree(const uint32_t* words, size_t n, ElementTree* out) {
     if (!out || (n && !words)) return RL_ERR_INVALID_ARGUMENT;
-    if (n > (size_t)RL_VPL_MAX + 4096) { rl_set_error("too many planes"); return RL_ERR_INVALID_ARGUMENT; }
+    if (n > kElementTreeMax) { rl_set_error("too many planes"); return RL_ERR_INVALID_ARGUMENT; }
     const int rcode = check_plane_records(words, n);
     if (rcode != RL_OK) return rcode;
     build_element_tree(PlaneElems{words}, n, out);
@@ -90,15 +90,8 @@ int build_rect_lights(const rl_scene& scene, std::vector<RectLight>* out, const 
 extern "C" int rl_plane_tree_build(const uint32_t* words, size_t n_planes, size_t node_capacity, size_t* n_nodes, float* node_boxes, uint32_t* node_links,
                                    uint32_t* order) {
     if (!n_nodes) return RL_ERR_INVALID_ARGUMENT;
-    rl::PhotonTree t;
+    rl::ElementTree t;
     const int rcode = rl::build_plane_tree(words, n_planes, &t);
     if (rcode != RL_OK) return rcode;
-    *n_nodes = t.n_nodes();
-    if (!node_boxes && !node_links && !order) return RL_OK;      // the size only
-    if (!node_boxes || !node_links || !order) return RL_ERR_INVALID_ARGUMENT;
-    if (node_capacity < t.n_nodes()) { rl_set_error("rl_plane_tree_build: node_capacity is too small"); return RL_ERR_INVALID_ARGUMENT; }
-    std::copy(t.boxes.begin(), t.boxes.end(), node_boxes);
-    std::copy(t.links.begin(), t.links.end(), node_links);
-    std::copy(t.order.begin(), t.order.end(), order);
-    return RL_OK;
+    return rl::copy_tree_out(t, node_capacity, n_nodes, node_boxes, node_links, order, "rl_plane_tree_build");
 }

@@ -80,9 +80,16 @@ struct VplPathsConst {
     unsigned* counts;                   // count pass: [path - first][VPL_PATH_WORDS] records kept, vertices, extension rays, draws
 };
 
+// The camera-beam gather (gather.hip.h) the beam radiance estimate and the photon planes share.  block_stats sums 32-bit values over the workgroup, and a lane
+// may enter more than 2^32 nodes over its samples: each 64-bit walk counter goes through it as its bits 0..23 in one statistics row and the bits from 24 up
+// in another.  Nodes entered takes rows STAT_GATHER_NODES / _HI; a leaf's own counters take the rows it names.  The high rows are those of STAT_VERTICES /
+// STAT_EXT_RAYS / STAT_SHADOW_RAYS, which the gather leaves empty (the host derives those counters).
+enum { STAT_GATHER_NODES = 5, STAT_GATHER_NODES_HI = 1 };
+RL_DEV void gather_split24(unsigned long long n, unsigned* lo, unsigned* hi) { *lo = (unsigned)n & 0xffffffu; *hi = (unsigned)(n >> 24); }
+inline unsigned long long gather_merge24(const unsigned long long* totals, int lo, int hi) { return totals[lo] + (totals[hi] << 24); }
+
 // The beam radiance estimate (bre.hip.h): the photon tree in visiting order and the photons in leaf order (host/photontree.cpp), the kernel's constants
-enum { STAT_BRE_NODES = 5, STAT_BRE_PHOTONS = 6,           // its statistics rows: photon-tree nodes entered, photons gathered — bits 0..23 of each lane's count ...
-       STAT_BRE_NODES_HI = 1, STAT_BRE_PHOTONS_HI = 3 };   // ... and the bits from 24 up, in the rows of STAT_VERTICES / STAT_SHADOW_RAYS, which the estimate leaves empty
+enum { STAT_BRE_PHOTONS = 6, STAT_BRE_PHOTONS_HI = 3 };    // its leaf's statistics rows: photons gathered
 struct BreConst {
     const float4* nodes;                // [n_nodes][2]: p_min.xyz, p_max.x | p_max.yz, skip, first << 3 | count
     const float4* photons;              // [n_photons][3]: pos | radiance | d_in
@@ -106,8 +113,7 @@ struct PlaneGenConst {
     unsigned long long* gen_state;      // [4] the main sampler, read and written back
     unsigned long long* gen_out;        // [PLANE_GEN_WORDS] planes stored, iterations (number_plane_gen), draws
 };
-enum { STAT_PLANE_NODES = 5, STAT_PLANE_ISECT = 6, STAT_PLANE_VISIBLE = 7,            // the gather's statistics rows: plane-tree nodes entered, planes intersected, of those visible — bits 0..23 ...
-       STAT_PLANE_NODES_HI = 1, STAT_PLANE_ISECT_HI = 2, STAT_PLANE_VISIBLE_HI = 3 };  // ... and the bits from 24 up, in the rows of STAT_VERTICES / STAT_EXT_RAYS / STAT_SHADOW_RAYS (the host derives those counters)
+enum { STAT_PLANE_ISECT = 6, STAT_PLANE_VISIBLE = 7, STAT_PLANE_ISECT_HI = 2, STAT_PLANE_VISIBLE_HI = 3 };      // its leaf's statistics rows: planes intersected, of those visible
 enum { PLANE_MODE_PLAIN = 0, PLANE_MODE_DISCRETE_MIS = 1, PLANE_MODE_CMIS = 2 };      // k_plane_gather's instantiations: a constant weight, DiscreteMIS, ContinousMIS
 struct PlaneConst {
     const float4* nodes;                // [n_nodes][2]: p_min.xyz, p_max.x | p_max.yz, skip, first << 3 | count

@@ -3,13 +3,10 @@
 // seven strategies —, then the gather kernel, instantiated by plane_lds.hip (scene staged in LDS) and plane_stream.hip (BVH streamed from L2 / HBM).  The
 // generation kernel (k_plane_generate, plane_generate.hip) is built from the same pieces.
 //
-// The gather's layout is k_bre_gather's (bre.hip.h): a camera sample takes exactly 2 draws (the pixel jitter), so sample (ix, iy, s) of a block starts at draw
-// ((ix * bh + iy) * spp + s) * 2 of the block's stream; a lane enters its pixel's place with one rng_advance and walks the pixel's samples in order.  The plane
-// tree (host/planetree.cpp) has the photon tree's node format — 2 float4 = p_min.xyz, p_max.x | p_max.yz, skip, first << 3 | count, in the order
-// BHVAccel::gather visits them — and is walked without a stack; a leaf tests its planes in index order and the contributions are added in that order.
-// Plane: 4 float4 = o, length0 | d0, length1 | d1, type + 4 * id_emitter | weight, 0; the weight is loaded for visible planes only.
+// The gather is beam_gather (gather.hip.h) over the leaf below, through the plane tree (host/planetree.cpp).  Plane: 4 float4 = o, length0 | d0, length1 |
+// d1, type + 4 * id_emitter | weight, 0; the weight is loaded for visible planes only.
 #pragma once
-#include "rngjump.h"        // rng_advance
+#include "gather.hip.h"
 
 namespace rl {
 
@@ -109,84 +106,45 @@ RL_DEV float plane_w_cmis(const PlaneLight& l, V3 d1, V3 rd) {
     return div_rn(1.0f, div_rn(2.0f, kPi) * sqrt_rn(a * a + b * b));
 }
 
-// k_plane_gather<LDS_SCENE, MODE> — workgroup = one owned block, lane c = ix * bh + iy of it.  MODE: PLAIN = a run-time w (1 for UV / VT / UT / UAlpha,
-// 1 / 3 for Average: 1.0 * rho is exact), DISCRETE_MIS, CMIS
+// MODE: PLAIN = a run-time w (1 for UV / VT / UT / UAlpha, 1 / 3 for Average: 1.0 * rho is exact), DISCRETE_MIS, CMIS
+template <int MODE>
+struct PlaneLeaf {
+    PlaneConst c;
+    static constexpr int kCounters = 2;                                     // planes intersected, of those visible
+    static constexpr int kLo[2] = {STAT_PLANE_ISECT, STAT_PLANE_VISIBLE}, kHi[2] = {STAT_PLANE_ISECT_HI, STAT_PLANE_VISIBLE_HI};
+    template <class STACK>
+    RL_DEV void element(unsigned idx, V3 cam, V3 rd, float tfar, const DeviceScene& sc, const SceneRecs& recs, const STACK& stack, Col& cs, unsigned long long (&n)[2]) const {
+        const float4* pl = c.planes + 4u * (size_t)idx;
+        const float4 q0 = pl[0], q1 = pl[1], q2 = pl[2];
+        const V3 po = mk3(q0.x, q0.y, q0.z), d0 = mk3(q1.x, q1.y, q1.z), d1 = mk3(q2.x, q2.y, q2.z);
+        PlaneIts its;
+        if (!plane_intersect(po, d0, d1, q0.w, q1.w, cam, rd, kEps, tfar, &its)) return;
+        n[0]++;
+        const unsigned tb = __float_as_uint(q2.w), type = tb & 3u;
+        const PlaneLight& light = c.lights[tb >> 2];
+        const V3 p_hit = cam + rd * its.t_cam;
+        const V3 p_light = plane_light_position(type, po, d0, light, its);
+        if (!shadow_visible(sc, recs, stack, p_hit, p_light)) return;
+        n[1]++;
+        const float4 q3 = pl[3];
+        const Col weight = mkc(q3.x, q3.y, q3.z);
+        const Col trans = medium_transmittance(sc.medium, its.t_cam);
+        const Col sigma_s = mkc(sc.medium.sigma_s[0], sc.medium.sigma_s[1], sc.medium.sigma_s[2]);
+        const Col rho = cval(div_rn(1.0f, kPi * 4.0f));                 // PhaseFunction::Isotropic(), whatever the medium's phase function is (plane_single.rs:440)
+        float w = c.w;
+        if (MODE == PLANE_MODE_DISCRETE_MIS) w = plane_discrete_mis(type, light, sigma_s, p_hit, p_light, rd);
+        Col flux;
+        if (MODE == PLANE_MODE_CMIS) flux = plane_w_cmis(light, d1, rd) * weight;
+        else flux = plane_contrib(weight, d0, d1, rd);
+        // c += w * rho * transmittance * sigma_s * flux * (emitters.len() as f32) * (1.0 / number_plane_gen as f32)
+        cs = cs + (((((w * rho) * trans) * sigma_s) * flux) * c.n_lights_f) * c.inv_gen;
+    }
+};
+
 template <bool LDS_SCENE, int MODE>
 __global__ void __launch_bounds__(256) k_plane_gather(RenderConst rc, DeviceScene sc, StackConf stc, PlaneConst pc) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
-    SceneRecs recs;
-    const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const TravStackT<LDS_SCENE> stack = open_scene<LDS_SCENE>(sc, stc, smem, tid, &recs);
-    const unsigned ob = blockIdx.x, c = threadIdx.x;
-    unsigned bx, by, bw, bh;
-    block_geometry(rc, rc.owned_blocks[ob], &bx, &by, &bw, &bh);
-    const bool active = c < bw * bh;
-    unsigned n_samples = 0;
-    unsigned long long n_entered = 0, n_isect = 0, n_visible = 0;
-    if (active) {
-        Rng rng = rng_seed(rc.block_seeds[rc.owned_blocks[ob]], rc.seed_variant);
-        rng_advance<false>(rng, c * rc.spp * 2u);
-        const unsigned ix = c / bh, iy = c - (c / bh) * bh;
-        const V3 cam = mk3(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]);
-        const Col sigma_s = mkc(sc.medium.sigma_s[0], sc.medium.sigma_s[1], sc.medium.sigma_s[2]);
-        const Col rho = cval(div_rn(1.0f, kPi * 4.0f));                 // PhaseFunction::Isotropic(), whatever the medium's phase function is (plane_single.rs:440)
-        Col sum = czero();
-        for (unsigned s = 0; s < rc.spp; s++) {
-            n_samples++;
-            const float u = (float)(bx + ix) + rng_next_f32(rng);
-            const float v = (float)(by + iy) + rng_next_f32(rng);
-            const V3 rd = camera_direction(sc, u, v);
-            Hit hit;
-            const float tfar = trace_closest(sc, recs, stack, cam, rd, hit) ? hit.t : kF32Max;     // ray.tfar = max_dist; a miss still gathers
-            const V3 inv_d = mk3(div_rn(1.0f, rd.x), div_rn(1.0f, rd.y), div_rn(1.0f, rd.z));
-            Col cs = czero();
-            unsigned i = 0u;
-            while (i < pc.n_nodes) {
-                const float4 a = pc.nodes[2u * i], b = pc.nodes[2u * i + 1u];
-                float te;
-                if (!slab(mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y), cam, inv_d, kEps, tfar, &te)) { i = __float_as_uint(b.z); continue; }
-                n_entered++;
-                const unsigned fc = __float_as_uint(b.w), first = fc >> 3, count = fc & 7u;
-                for (unsigned k = 0; k < count; k++) {
-                    const float4* pl = pc.planes + 4u * (size_t)(first + k);
-                    const float4 q0 = pl[0], q1 = pl[1], q2 = pl[2];
-                    const V3 po = mk3(q0.x, q0.y, q0.z), d0 = mk3(q1.x, q1.y, q1.z), d1 = mk3(q2.x, q2.y, q2.z);
-                    PlaneIts its;
-                    if (!plane_intersect(po, d0, d1, q0.w, q1.w, cam, rd, kEps, tfar, &its)) continue;
-                    n_isect++;
-                    const unsigned tb = __float_as_uint(q2.w), type = tb & 3u;
-                    const PlaneLight& light = pc.lights[tb >> 2];
-                    const V3 p_hit = cam + rd * its.t_cam;
-                    const V3 p_light = plane_light_position(type, po, d0, light, its);
-                    if (!shadow_visible(sc, recs, stack, p_hit, p_light)) continue;
-                    n_visible++;
-                    const float4 q3 = pl[3];
-                    const Col weight = mkc(q3.x, q3.y, q3.z);
-                    const Col trans = medium_transmittance(sc.medium, its.t_cam);
-                    float w = pc.w;
-                    if (MODE == PLANE_MODE_DISCRETE_MIS) w = plane_discrete_mis(type, light, sigma_s, p_hit, p_light, rd);
-                    Col flux;
-                    if (MODE == PLANE_MODE_CMIS) flux = plane_w_cmis(light, d1, rd) * weight;
-                    else flux = plane_contrib(weight, d0, d1, rd);
-                    // c += w * rho * transmittance * sigma_s * flux * (emitters.len() as f32) * (1.0 / number_plane_gen as f32)
-                    cs = cs + (((((w * rho) * trans) * sigma_s) * flux) * pc.n_lights_f) * pc.inv_gen;
-                }
-                i++;
-            }
-            sum = sum + cs;                                                 // im_block.accumulate, in sample order
-        }
-        const Col px = scale_unguarded(sum, rc.inv_spp);                    // im_block.scale(1 / spp)
-        const size_t pix = (size_t)(by + iy) * rc.W + (bx + ix);
-        rc.out[3 * pix] = px.r; rc.out[3 * pix + 1] = px.g; rc.out[3 * pix + 2] = px.b;
-    }
-    {
-        // block_stats sums 32-bit values over the workgroup: the three walk counters go through it as 24 low bits and the rest (rows STAT_PLANE_*_HI); extension
-        // rays and draws follow from the samples on the host
-        const int which[7] = {STAT_SAMPLES, STAT_PLANE_NODES, STAT_PLANE_ISECT, STAT_PLANE_VISIBLE, STAT_PLANE_NODES_HI, STAT_PLANE_ISECT_HI, STAT_PLANE_VISIBLE_HI};
-        const unsigned vals[7] = {n_samples, (unsigned)n_entered & 0xffffffu, (unsigned)n_isect & 0xffffffu, (unsigned)n_visible & 0xffffffu,
-                                  (unsigned)(n_entered >> 24), (unsigned)(n_isect >> 24), (unsigned)(n_visible >> 24)};
-        block_stats<7>(rc.partials, which, vals);
-    }
+    beam_gather<LDS_SCENE>(rc, sc, stc, smem, PlaneLeaf<MODE>{pc});
 }
 
 template <bool LDS_SCENE>
