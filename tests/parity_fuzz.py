@@ -1,63 +1,283 @@
 """Randomized differential test, HIP path vs CPU oracle (bit-exact image + counters), over random scene / light / material /
 integrator-option / pipeline combinations.  `run(seconds, seed)` is used by tests/test_gpu_parity.py (short) and can be run by hand
-for longer: python tests/parity_fuzz.py [seconds] [seed] [fast | light | stratified]   (round 1: ~75 000 cases over eight runs on 1 x MI355X, 0 failures; round 2: 26 k + 17 k + 17 k + 34 k + 69 k + 87 k cases, the last four with a third of the
+for longer: python tests/parity_fuzz.py [seconds] [seed] [fast | light | stratified | vpl | bre | plane]   (round 1: ~75 000 cases over eight runs on 1 x MI355X, 0 failures; round 2: 26 k + 17 k + 17 k + 34 k + 69 k + 87 k cases, the last four with a third of the
 cases forced through the kernels that stream the BVH, 0 mismatches).
 `fast`: eligible cases are also rendered with the opt-in tolerance build (`numerics = fast`) and held to a statistical bar (vertex
-count within 2 % of the exact build at the same seeds — the path census is what a systematic error moves —, image mean within a coarse bound)."""
+count within 2 % of the exact build at the same seeds — the path census is what a systematic error moves —, image mean within a coarse bound).
+`vpl`, `bre`, `plane`: the light-pass integrators against orc.vpl_compute's entry points, tests/vpl_paths_restatement.py, tests/bre_restatement.py and
+tests/plane_single_restatement.py, over frames from 1x1 to 48x40, coloured media with either phase function, random BSDFs, streamed BVHs, per-path light
+streams, both photon-tree builds, every plane strategy, two lights and shards of 2-4; draw_gather_case / gather_scene / gather_reference need no GPU
+(tests/test_gather_fuzz_cases.py), and a printed MISMATCH case replays through run_gather_case."""
 import os, sys, time, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from rustlight_amd import api, scenes
 from oracle import orc
+from tests import gather_exact as G
+from tests.scene_helpers import add_second_light, context
 S = scenes
 
 
+def rand_color(rng, lo=0.05, hi=0.9):
+    return tuple(float(x) for x in rng.uniform(lo, hi, 3))
+
+
+def rand_bsdf(rng):
+    k = rng.integers(0, 9)
+    tex = lambda: ({"type": S.TEX_CHECKERBOARD, "color0": rand_color(rng), "color1": rand_color(rng), "scale": (float(rng.uniform(1, 6)), float(rng.uniform(1, 6)))}
+                   if rng.random() < 0.3 else S.const_color(rand_color(rng)))
+    if k <= 2: return S.Bsdf(type=S.DIFFUSE, diffuse=tex())
+    if k == 3: return S.Bsdf(type=S.PHONG, diffuse=tex(), specular=S.const_color(rand_color(rng, 0.05, 0.5)), exponent=float(rng.uniform(2, 80)), weight_specular=float(rng.uniform(0.1, 0.9)))
+    if k == 4: return S.Bsdf(type=S.METAL, distribution=S.MF_NONE)
+    if k == 5: return S.Bsdf(type=S.METAL, distribution=int(rng.choice([S.MF_BECKMANN, S.MF_GGX])), alpha_u=float(rng.uniform(0.05, 0.6)), alpha_v=float(rng.uniform(0.05, 0.6)))
+    if k == 6: return S.Bsdf(type=S.GLASS)
+    return S.Bsdf(type=S.SUBSTRATE, diffuse=tex(), specular=S.const_color(rand_color(rng, 0.02, 0.1)), distribution=int(rng.choice([S.MF_NONE, S.MF_GGX, S.MF_BECKMANN])),
+                  alpha_u=float(rng.uniform(0.05, 0.5)), alpha_v=float(rng.uniform(0.05, 0.5)))
+
+
+def rand_scene(rng, size=None):
+    """size: the frame, drawn (5..48 x 5..40) when None."""
+    w, h = size if size is not None else (int(rng.integers(5, 49)), int(rng.integers(5, 41)))
+    kind = rng.integers(0, 6)
+    if kind == 0: sd = S.cbox(w, h)
+    elif kind == 1: sd = S.cbox_other_lights(w, h, point=bool(rng.integers(2)), directional=bool(rng.integers(2)), environment=bool(rng.integers(2)), keep_area_light=bool(rng.integers(2)))
+    elif kind == 2: sd = S.sky_scene(w, h, keep_area_light=bool(rng.integers(2)))
+    elif kind == 3: sd = S.many_lights(w, h, n=int(rng.integers(2, 5)), use_ats=bool(rng.integers(2)), glowing_spheres=int(rng.integers(0, 3)))
+    elif kind == 4: sd = S.living_room(w, h, n_spheres=int(rng.choice([8, 27])), tess=int(rng.integers(4, 12)))
+    else: sd = S.cbox_medium(w, h, float(rng.uniform(0.1, 1.0)), float(rng.uniform(0.0, 0.3)), g=float(rng.choice([0.0, 0.5, -0.3])))
+    if kind != 4 and rng.random() < 0.6:
+        for m in sd.meshes:
+            if m.emission is None and rng.random() < 0.5: m.bsdf = rand_bsdf(rng)
+    if kind in (0, 1, 3) and rng.random() < 0.2:
+        sd.medium = S.Medium(rand_color(rng, 0.0, 0.2), rand_color(rng, 0.1, 0.8), int(rng.choice([S.PHASE_ISOTROPIC, S.PHASE_HG])), float(rng.uniform(-0.6, 0.6)))
+        sd.environment = None; sd.environment_map = None      # (no environment with a medium)
+    # `-x hvs-light` / `-x texture-light` (cli.rs:410-429): the light meshes' emission becomes uv-dependent (EmissionType::HSV / Texture) — when they all carry uv
+    lights = [m for m in sd.meshes if m.emission is not None]
+    if lights and all(m.uv is not None for m in lights) and rng.random() < 0.15:
+        kind_e = "hsv" if rng.random() < 0.5 else "texture"
+        bid = -1
+        if kind_e == "texture":
+            tw, th = int(rng.integers(1, 6)), int(rng.integers(1, 6))
+            sd.bitmaps.append((tw, th, rng.uniform(0.0, 3.0, (tw * th, 3)).astype(np.float32)))
+            bid = len(sd.bitmaps) - 1
+        S.override_light_emission(sd, kind_e, bitmap_id=bid)
+    return sd
+
+
+# ---- the light-pass integrators: vpl, the beam radiance estimate, the single-scattering photon planes
+GATHER_ARMS = ("vpl", "bre", "plane")
+EDGE_SIZES = (1, 2, 15, 16, 17)                # widths / heights a quarter of the cases force: a single column or row, one block and its neighbours
+TREE_GROUPS = (None, 4, 8, 64, 2048)           # photon_tree_group_photons: 4 .. RL_PHOTON_TREE_GROUP_PHOTONS (gather_render.hip.h clamps to it), None = unset
+VPL_BATCHES = (None, 1, 7, 64, 4096)           # vpl_batch_paths: any count >= 1, None = the default sizing
+RL_ERR_INVALID_ARGUMENT = -1
+VPL_GEN_KEYS = ("camera_samples", "vertices", "extension_rays", "rng_draws")
+VPL_KEYS = ("camera_samples", "extension_rays", "shadow_rays", "rng_draws", "gather_surface", "gather_volume")
+
+
+def draw_gather_case(rng, arm):
+    """One random case of a light-pass arm as a dict of plain values: everything run_gather_case needs, so a printed case replays.  Needs no GPU."""
+    c = {"arm": arm}
+    w, h = int(rng.integers(1, 49)), int(rng.integers(1, 41))
+    if rng.random() < 0.25:
+        if rng.random() < 0.5: w = int(rng.choice(EDGE_SIZES))
+        else: h = int(rng.choice(EDGE_SIZES))
+    c["size"] = (w, h)
+    c["scene_seed"] = int(rng.integers(0, 1 << 31))            # the scene's own generator: scene kind and random BSDFs (gather_scene)
+    c["medium"] = None
+    if arm != "vpl" or rng.random() < 1.0 / 3.0:
+        sigma_a = [float(x) for x in rng.uniform(0.0, 0.3, 3)]
+        sigma_s = tuple(float(x) for x in rng.uniform(0.1, 1.5, 3))
+        if rng.random() < 0.1: sigma_a[int(rng.integers(3))] = 0.0
+        hg = bool(rng.integers(2))
+        c["medium"] = dict(sigma_a=tuple(sigma_a), sigma_s=sigma_s, hg=hg, g=float(rng.uniform(-0.7, 0.7)) if hg else 0.0)
+    c["streaming"] = bool(rng.random() < 1.0 / 3.0)
+    c["seed"], c["seed_variant"], c["spp"] = int(rng.integers(0, 1000)), int(rng.integers(0, 2)), int(rng.integers(1, 6))
+    c["shard_index"], c["shard_count"] = 0, 1
+    if rng.random() < 0.25:
+        c["shard_count"] = int(rng.integers(2, 5))               # (a shard that owns a block: small frames have fewer blocks than shards)
+        c["shard_index"] = int(rng.integers(0, min(c["shard_count"], ((w + 15) // 16) * ((h + 15) // 16))))
+    if arm == "plane":
+        c["strategy"] = api.PLANE_STRATEGIES[int(rng.integers(0, len(api.PLANE_STRATEGIES)))]
+        c["nb_primitive"] = int(rng.integers(3, 201))
+        c["two_lights"] = bool(rng.random() < 0.25)
+        c["bsdfs"] = bool(rng.random() < 0.6)
+        return c
+    c["max_depth"] = None if rng.random() < 0.4 else int(rng.integers(2, 9))
+    c["rr_depth"] = None if rng.random() < 0.2 else int(rng.integers(0, 5))
+    if c["max_depth"] is None and c["rr_depth"] is None: c["rr_depth"] = 2        # keep paths finite
+    c["per_path"] = bool(rng.random() < 1.0 / 3.0)
+    c["vpl_batch_paths"] = VPL_BATCHES[int(rng.integers(0, len(VPL_BATCHES)))] if c["per_path"] else None
+    if arm == "vpl":
+        c["nb_vpl"] = int(rng.integers(1, 129))
+        c["option_vpl"], c["option_lt"] = int(rng.integers(0, 3)), int(rng.integers(0, 3))
+    else:
+        c["nb_primitive"] = int(rng.integers(1, 401))
+        c["radius"] = float(np.float32(rng.uniform(0.02, 0.5)))
+        c["device_build"] = bool(rng.random() < 0.5)
+        c["photon_tree_group_photons"] = TREE_GROUPS[int(rng.integers(0, len(TREE_GROUPS)))] if c["device_build"] else None
+        c["bsdfs"] = bool(rng.random() < 0.6)
+    if (arm == "bre" or c["option_vpl"] == api.VPL_VOLUME) and c["max_depth"] is not None:
+        c["max_depth"] = max(3, c["max_depth"])                 # a volume record needs a path that reaches the medium past the light vertex
+    return c
+
+
+def gather_scene(c):
+    """The scene of a case, a function of the case alone."""
+    rng = np.random.default_rng(c["scene_seed"])
+    w, h = c["size"]
+    m = c["medium"]
+    med = None if m is None else S.Medium(m["sigma_a"], m["sigma_s"], S.PHASE_HG if m["hg"] else S.PHASE_ISOTROPIC, m["g"])
+    if c["arm"] != "vpl":
+        sd = S.cbox_medium(w, h, 1.0)
+        sd.medium = med
+        if c.get("two_lights"): add_second_light(sd)
+        if c["bsdfs"]:
+            for mesh in sd.meshes:
+                if mesh.emission is None and rng.random() < 0.5: mesh.bsdf = rand_bsdf(rng)
+        return sd
+    for _ in range(256):          # rand_scene's kinds, redrawn until rl_vpl_generate accepts one: an emitter, no environment, no directional light in a medium
+        sd = rand_scene(rng, (w, h))
+        if med is not None:
+            sd.medium = med; sd.environment = None; sd.environment_map = None
+        if sd.environment is not None or getattr(sd, "environment_map", None) is not None: continue
+        if not (any(mesh.emission is not None for mesh in sd.meshes) or sd.lights): continue
+        if sd.medium is not None and any(l.get("type") == "directional" for l in sd.lights): continue
+        if sd.medium is None and c["option_vpl"] == api.VPL_VOLUME: continue
+        return sd
+    raise RuntimeError("no scene for the case")
+
+
+def owned_samples(c):
+    """Camera samples of the case's shard: the blocks b with b % shard_count == shard_index, columns first (bre_restatement.camera_samples)."""
+    w, h = c["size"]
+    nby = (h + 15) // 16
+    n = 0
+    for b in range(((w + 15) // 16) * nby):
+        if b % c["shard_count"] == c["shard_index"]:
+            n += min(16, w - (b // nby) * 16) * min(16, h - (b % nby) * 16)
+    return n * c["spp"]
+
+
+def gather_reference(c, sd=None):
+    """The CPU side of a case: {"refused": True} or {"records", "state", "seeds", "image", "stats", "n_paths" | "n_gen", "gen_stats"}."""
+    from tests import bre_restatement as B, plane_single_restatement as PL, vpl_paths_restatement as VR
+    sd = sd or gather_scene(c)
+    sc = orc.Scene(sd)
+    state = orc.Rng(c["seed"], c["seed_variant"]).state
+    shard = (c["shard_index"], c["shard_count"])
+    if c["arm"] == "plane":
+        planes, words, n_gen, after, draws, _ = PL.generate(sd, [int(v) for v in state], c["nb_primitive"], c["strategy"])
+        if not all(np.isfinite(p.corners()).all() for p in planes):
+            return {"refused": True}
+        seeds = VR.block_seeds_after(sd, after)
+        img, st, _ = PL.render(sc, sd, words, n_gen, c["strategy"], seeds, c["spp"], c["seed_variant"], *shard)
+        return {"records": words, "n_gen": n_gen, "state": after, "seeds": seeds, "image": img, "stats": st,
+                "gen_stats": {"camera_samples": n_gen, "vertices": words.shape[0], "rng_draws": draws}}
+    option = api.VPL_VOLUME if c["arm"] == "bre" else c["option_vpl"]
+    nb = c["nb_primitive"] if c["arm"] == "bre" else c["nb_vpl"]
+    if c["per_path"]:
+        gen = VR.generate(sc, state, nb, c["max_depth"], c["rr_depth"], option, c["seed_variant"])
+        rec, n_paths, after, gst = gen["records"], gen["n_paths"], gen["state"], gen["gen_stats"]
+    else:
+        rec, n_paths, after, gst = sc.vpl_generate(state, nb, c["max_depth"], c["rr_depth"], option)
+    seeds = VR.block_seeds_after(sd, after)
+    if c["arm"] == "vpl":
+        img, st = sc.render_vpl(rec, n_paths, seeds, c["spp"], c["option_lt"], c["seed_variant"], *shard)
+    else: img, st, _ = B.render(sc, sd, rec, n_paths, seeds, c["spp"], c["radius"], c["seed_variant"], *shard)
+    return {"records": rec, "n_paths": n_paths, "state": after, "seeds": seeds, "image": img, "stats": st, "gen_stats": gst}
+
+
+def run_gather_case(c):
+    """One case on the device against gather_reference: ("ok" | "skipped" | "bad", what differed).  Bit-exact: np.array_equal on records, seeds and image
+    (NaNs in the same places count as equal), the sampler state, every counter both sides report."""
+    sd = gather_scene(c)
+    ref = gather_reference(c, sd)
+    ctx = context(sd, c["streaming"])
+    sampler = api.IndependentSampler(c["seed"], c["seed_variant"])
+    before = list(sampler.s.s)
+    shard = dict(shard_index=c["shard_index"], shard_count=c["shard_count"])
+    bad = []
+    def same(a, b): return np.array_equal(a, b, equal_nan=True)
+    def check(name, ok):
+        if not ok: bad.append(name)
+    if c["arm"] == "plane":
+        try:
+            pset, gst = ctx.plane_generate(sampler, c["nb_primitive"], c["strategy"])
+        except api.RustlightError as e:      # non-finite plane corners: both sides refuse, the device with its documented code and the sampler as it was
+            if ref.get("refused") and e.code == RL_ERR_INVALID_ARGUMENT and list(sampler.s.s) == before: return "skipped", []
+            return "bad", ["the device alone refused: " + str(e)]
+        if ref.get("refused"): return "bad", ["the restatement alone refused"]
+        check("records", same(pset.words(), ref["records"]))
+        check("set info", pset.info() == (ref["records"].shape[0], ref["n_gen"], c["strategy"]))
+        check("sampler", list(sampler.s.s) == [int(v) for v in ref["state"]])
+        for k, v in ref["gen_stats"].items(): check("generation " + k, gst[k] == v)
+        seeds = sampler.block_seeds(sd.width, sd.height)
+        check("seeds", same(seeds, ref["seeds"]))
+        img, st = ctx.render_plane_single(ctx.plane_map(pset), seeds, c["spp"], c["seed_variant"], **shard)
+        keys = G.PLANE_KEYS
+    else:
+        option = api.VPL_VOLUME if c["arm"] == "bre" else c["option_vpl"]
+        nb = c["nb_primitive"] if c["arm"] == "bre" else c["nb_vpl"]
+        with ctx.options(vpl_batch_paths=c["vpl_batch_paths"]):
+            vpls, gst = ctx.vpl_generate(sampler, nb, c["max_depth"], c["rr_depth"], option, streams="per_path" if c["per_path"] else "reference")
+        check("records", same(vpls.words(), ref["records"]))
+        check("set info", vpls.info() == (ref["records"].shape[0], ref["n_paths"]) and ref["records"].shape[0] >= nb)
+        check("sampler", list(sampler.s.s) == [int(v) for v in ref["state"]])
+        for k in VPL_GEN_KEYS: check("generation " + k, gst[k] == ref["gen_stats"][k])
+        if c["per_path"]: check("rounds", gst["iterations"] >= 1 and gst["kernel_launches"] == gst["iterations"] + 1 and gst["paths_walked"] >= ref["n_paths"])
+        seeds = sampler.block_seeds(sd.width, sd.height)
+        check("seeds", same(seeds, ref["seeds"]))
+        if c["arm"] == "vpl":
+            img, st = ctx.render_vpl(vpls, seeds, c["spp"], c["option_lt"], c["seed_variant"], **shard)
+            keys = VPL_KEYS
+        else:
+            photons = ctx.photon_map(vpls, c["radius"])
+            img, st = ctx.render_bre(photons, seeds, c["spp"], c["seed_variant"], **shard)
+            keys = G.BRE_KEYS
+            if c["device_build"]:
+                with ctx.options(photon_tree_group_photons=c["photon_tree_group_photons"]):
+                    dev = ctx.photon_map(vpls, c["radius"], build="device")
+                check("device map info", dev.info() == photons.info())
+                for name, a, b in zip(("boxes", "links", "photons"), photons.read(), dev.read()):
+                    check("device map " + name, np.array_equal(a.view(np.uint32), b.view(np.uint32)))
+                img_d, st_d = ctx.render_bre(dev, seeds, c["spp"], c["seed_variant"], **shard)
+                check("device map image", same(img_d, ref["image"]))
+                for k in keys: check("device map " + k, st_d[k] == ref["stats"][k])
+    check("image", same(img, ref["image"]))
+    for k in keys: check(k, st[k] == ref["stats"][k])
+    check("camera_samples of the shard", st["camera_samples"] == owned_samples(c))
+    return ("bad" if bad else "ok"), bad
+
+
+def run_gather(budget, rng, arm, verbose=True):
+    t_end = time.time() + budget
+    n = bad = skipped = 0
+    while time.time() < t_end:
+        c = None
+        try:
+            c = draw_gather_case(rng, arm)
+            verdict, what = run_gather_case(c)
+            if verdict == "skipped": skipped += 1; continue
+            n += 1
+            if verdict == "bad":
+                bad += 1
+                print(f"MISMATCH ({arm})", n, c, what, flush=True)
+        except Exception as e:
+            bad += 1
+            print(f"ERROR ({arm})", n, c, repr(e), flush=True); traceback.print_exc()
+    if 10 * skipped > n + skipped:              # more than a tenth of the drawn cases refused on both sides: the arm compares too little
+        bad += 1
+        print(f"SKIPPED ({arm}): {skipped} of {n + skipped} drawn cases", flush=True)
+    if verbose:
+        print(f"fuzz: {n} cases ({arm}; {skipped} skipped), {bad} failures", flush=True)
+    return n, bad
+
 def run(budget=20.0, seed=0, verbose=True, fast=False, arm="path"):
     """arm: "path" (path / ao / direct in their random stream modes), "light" (the light tracer, rl_render_light, on the scenes without an
-    environment emitter) or "stratified" (path / ao / direct with RL_STREAM_STRATIFIED)."""
+    environment emitter), "stratified" (path / ao / direct with RL_STREAM_STRATIFIED) or one of GATHER_ARMS ("vpl", "bre", "plane": run_gather)."""
     rng = np.random.default_rng(seed)
-    def rand_color(lo=0.05, hi=0.9):
-        return tuple(float(x) for x in rng.uniform(lo, hi, 3))
-
-    def rand_bsdf():
-        k = rng.integers(0, 9)
-        tex = lambda: ({"type": S.TEX_CHECKERBOARD, "color0": rand_color(), "color1": rand_color(), "scale": (float(rng.uniform(1, 6)), float(rng.uniform(1, 6)))}
-                       if rng.random() < 0.3 else S.const_color(rand_color()))
-        if k <= 2: return S.Bsdf(type=S.DIFFUSE, diffuse=tex())
-        if k == 3: return S.Bsdf(type=S.PHONG, diffuse=tex(), specular=S.const_color(rand_color(0.05, 0.5)), exponent=float(rng.uniform(2, 80)), weight_specular=float(rng.uniform(0.1, 0.9)))
-        if k == 4: return S.Bsdf(type=S.METAL, distribution=S.MF_NONE)
-        if k == 5: return S.Bsdf(type=S.METAL, distribution=int(rng.choice([S.MF_BECKMANN, S.MF_GGX])), alpha_u=float(rng.uniform(0.05, 0.6)), alpha_v=float(rng.uniform(0.05, 0.6)))
-        if k == 6: return S.Bsdf(type=S.GLASS)
-        return S.Bsdf(type=S.SUBSTRATE, diffuse=tex(), specular=S.const_color(rand_color(0.02, 0.1)), distribution=int(rng.choice([S.MF_NONE, S.MF_GGX, S.MF_BECKMANN])),
-                      alpha_u=float(rng.uniform(0.05, 0.5)), alpha_v=float(rng.uniform(0.05, 0.5)))
-
-    def rand_scene():
-        w, h = int(rng.integers(5, 49)), int(rng.integers(5, 41))
-        kind = rng.integers(0, 6)
-        if kind == 0: sd = S.cbox(w, h)
-        elif kind == 1: sd = S.cbox_other_lights(w, h, point=bool(rng.integers(2)), directional=bool(rng.integers(2)), environment=bool(rng.integers(2)), keep_area_light=bool(rng.integers(2)))
-        elif kind == 2: sd = S.sky_scene(w, h, keep_area_light=bool(rng.integers(2)))
-        elif kind == 3: sd = S.many_lights(w, h, n=int(rng.integers(2, 5)), use_ats=bool(rng.integers(2)), glowing_spheres=int(rng.integers(0, 3)))
-        elif kind == 4: sd = S.living_room(w, h, n_spheres=int(rng.choice([8, 27])), tess=int(rng.integers(4, 12)))
-        else: sd = S.cbox_medium(w, h, float(rng.uniform(0.1, 1.0)), float(rng.uniform(0.0, 0.3)), g=float(rng.choice([0.0, 0.5, -0.3])))
-        if kind != 4 and rng.random() < 0.6:
-            for m in sd.meshes:
-                if m.emission is None and rng.random() < 0.5: m.bsdf = rand_bsdf()
-        if kind in (0, 1, 3) and rng.random() < 0.2:
-            sd.medium = S.Medium(rand_color(0.0, 0.2), rand_color(0.1, 0.8), int(rng.choice([S.PHASE_ISOTROPIC, S.PHASE_HG])), float(rng.uniform(-0.6, 0.6)))
-            sd.environment = None; sd.environment_map = None      # (no environment with a medium)
-        # `-x hvs-light` / `-x texture-light` (cli.rs:410-429): the light meshes' emission becomes uv-dependent (EmissionType::HSV / Texture) — when they all carry uv
-        lights = [m for m in sd.meshes if m.emission is not None]
-        if lights and all(m.uv is not None for m in lights) and rng.random() < 0.15:
-            kind_e = "hsv" if rng.random() < 0.5 else "texture"
-            bid = -1
-            if kind_e == "texture":
-                tw, th = int(rng.integers(1, 6)), int(rng.integers(1, 6))
-                sd.bitmaps.append((tw, th, rng.uniform(0.0, 3.0, (tw * th, 3)).astype(np.float32)))
-                bid = len(sd.bitmaps) - 1
-            S.override_light_emission(sd, kind_e, bitmap_id=bid)
-        return sd
-
+    if arm in GATHER_ARMS:
+        return run_gather(budget, rng, arm, verbose)
     def rand_params(sd):
         has_emitter = any(m.emission for m in sd.meshes) or bool(sd.lights) or sd.environment is not None or getattr(sd, "environment_map", None) is not None
         kw = dict(spp=int(rng.integers(1, 6)))
@@ -78,7 +298,7 @@ def run(budget=20.0, seed=0, verbose=True, fast=False, arm="path"):
     while time.time() < t_end:
         state = rng.bit_generator.state
         try:
-            sd = rand_scene()
+            sd = rand_scene(rng)
             kw = rand_params(sd)
             seed = int(rng.integers(0, 1000))
             pipe = int(rng.choice([0, 1, 2])); split = int(rng.choice([0, 0, 1, 2, 3])); pool = int(rng.choice([0, 0, 512, 4096])) if pipe != 2 else 0
@@ -176,7 +396,7 @@ def run(budget=20.0, seed=0, verbose=True, fast=False, arm="path"):
 
 
 if __name__ == "__main__":
-    arms = [a for a in ("light", "stratified") if a in sys.argv[3:]]
+    arms = [a for a in ("light", "stratified") + GATHER_ARMS if a in sys.argv[3:]]
     n, bad = run(float(sys.argv[1]) if len(sys.argv) > 1 else 120.0, int(sys.argv[2]) if len(sys.argv) > 2 else 0, fast="fast" in sys.argv[3:],
                  arm=arms[0] if arms else "path")
     sys.exit(1 if bad else 0)

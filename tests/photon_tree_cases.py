@@ -1,4 +1,5 @@
-"""Shared by the photon-tree tests: the position families the device build is held to the host build on, records made from positions, and a numpy
+"""Shared by the photon-tree tests: the position families the device build is held to the host build on (random, heavily tied, all equal, and mixed
+scales from denormals to 1e30), records made from positions, and a numpy
 level-by-level build — the CPU-side model of kernels/phototree.hip.h.  The model uses only what the kernels use: the closed-form topology (a function of n
 alone) and, per range, an UNSTABLE sort by the unique pair (ordered key of pos[axis], place before the sort)."""
 import numpy as np
@@ -6,7 +7,7 @@ import numpy as np
 from rustlight_amd import api
 
 RADIUS = 0.2
-FAMILIES = ("normal", "tied", "point")
+FAMILIES = ("normal", "tied", "point", "scales")
 
 
 def positions(family, n, seed=0):
@@ -19,6 +20,14 @@ def positions(family, n, seed=0):
         return p
     if family == "point":                      # every sort is all ties, every extent equal
         return np.tile(np.array([[0.25, -1.5, 3.0]], np.float32), (n, 1))
+    if family == "scales":                     # f32 denormals, values near +-1e30 and ordinary ones mixed per coordinate, all finite: a denormal p gives p - r == -r and
+        kind = rng.integers(0, 3, (n, 3))      # p + r == r exactly, so boxes tie where the sort keys do not, and beside 1e30 every other extent vanishes
+        sign = np.where(rng.integers(0, 2, (n, 3)) == 1, np.uint32(0x80000000), np.uint32(0))
+        tiny = (rng.integers(1, 1 << 23, (n, 3)).astype(np.uint32) | sign).view(np.float32)
+        huge = (np.float32(1.0e30) * (1.0 + 0.01 * rng.standard_normal((n, 3))).astype(np.float32)) * np.where(sign != 0, np.float32(-1.0), np.float32(1.0))
+        p = np.where(kind == 0, tiny, np.where(kind == 1, huge.astype(np.float32), rng.standard_normal((n, 3)).astype(np.float32))).astype(np.float32)
+        assert np.isfinite(p).all()
+        return p
     raise ValueError(family)
 
 

@@ -27,6 +27,20 @@ def with_back_triangle(sd):
     return sd
 
 
+def add_second_light(sd):
+    """A second emissive quad on the left wall; its u x v = (0, 0, 1) x (0, -1, 0) = (1, 0, 0) points into the room."""
+    quad = [-0.98, 0.8, -0.3, -0.98, 0.8, 0.3, -0.98, 0.4, 0.3, -0.98, 0.4, -0.3]
+    sd.meshes.append(scenes.MeshData("Light2", np.asarray(quad, np.float32).reshape(4, 3), np.asarray([[0, 1, 2], [0, 2, 3]], np.uint32),
+                                     np.asarray([1.0, 0.0, 0.0] * 4, np.float32).reshape(4, 3), np.asarray([0, 0, 1, 0, 1, 1, 0, 1], np.float32).reshape(4, 2),
+                                     scenes.matte((0.0, 0.0, 0.0)), (4.0, 6.0, 9.0)))
+    return sd
+
+
+def two_lights(w, h):
+    """The box with its medium plus the second emissive quad of add_second_light."""
+    return add_second_light(scenes.cbox_medium(w, h, 1.0))
+
+
 def single_bsdf(w, h, bsdf):
     sd = scenes.cbox(w, h)
     for m in sd.meshes:

@@ -2,7 +2,9 @@
 (tests/bre_restatement.py): first the photon records, the path count and the advanced sampler against the oracle's orc_vpl_generate, then the image
 (assert_array_equal) and every counter, over both phase functions, LDS-staged and streamed BVHs, a ragged frame, spp 1 and 5, both seed variants, trees whose
 root is a leaf, depth options and two shards.  The refused inputs return their codes; the CLI (which goes through the C++ mirror's
-IntegratorVolPrimitives::compute) writes the bytes the API renders.  One process; only the CLI test starts a child."""
+IntegratorVolPrimitives::compute) writes the bytes the API renders.  The step-by-step comparison (_exact) lives in tests/gather_exact.py, shared with
+tests/test_gpu_gather_edges.py; the randomized arm of tests/parity_fuzz.py ("bre": coloured media, random BSDFs, both tree builds, per-path sets, shards of
+2-4) runs from here.  One process; only the CLI test starts a child."""
 import os
 import subprocess
 
@@ -12,40 +14,12 @@ import pytest
 from oracle import orc
 from rustlight_amd import api, scenes
 from tests import bre_restatement as R
+from tests.gather_exact import BRE_KEYS as KEYS, bre_exact as _exact
 from tests.scene_helpers import context as _context
 
 pytestmark = pytest.mark.gpu
 
 RL_ERR_INVALID_ARGUMENT = -1
-GEN_KEYS = ("camera_samples", "vertices", "extension_rays", "rng_draws")
-KEYS = ("camera_samples", "extension_rays", "rng_draws", "nodes_entered", "photons_gathered")
-
-
-def _exact(sd, seed=3, nb_primitive=300, spp=3, radius=0.2, max_depth=None, rr_depth=0, seed_variant=0, streaming=False):
-    """IntegratorVolPrimitives::compute (BRE) on the GPU and in the restatement, step by step.  Returns (image, gather stats, the restatement's result)."""
-    ctx = _context(sd, streaming)
-    ref = R.compute(sd, seed, nb_primitive, spp, max_depth, rr_depth, radius, seed_variant)
-    sampler = api.IndependentSampler(seed, seed_variant)
-    vpls, gst = ctx.vpl_generate(sampler, nb_primitive, max_depth, rr_depth, api.VPL_VOLUME)
-    np.testing.assert_array_equal(vpls.words(), ref["records"])
-    assert vpls.info() == (ref["records"].shape[0], ref["n_paths"]) and ref["records"].shape[0] >= nb_primitive
-    assert list(sampler.s.s) == [int(v) for v in ref["state"]]
-    for k in GEN_KEYS:
-        assert gst[k] == ref["gen_stats"][k], (k, gst[k], ref["gen_stats"][k])
-    seeds = sampler.block_seeds(sd.width, sd.height)
-    np.testing.assert_array_equal(seeds, ref["seeds"])
-    photons = ctx.photon_map(vpls, radius)
-    n_photons, n_nodes, n_paths, r = photons.info()
-    assert (n_photons, n_nodes, n_paths) == (ref["records"].shape[0], len(ref["detail"]["tree"]["nodes"]), ref["n_paths"]) and r == np.float32(radius)
-    img, st = ctx.render_bre(photons, seeds, spp, seed_variant)
-    for k in KEYS:
-        print(k, st[k], ref["stats"][k])
-    print("pixels that differ:", int(np.count_nonzero((img != ref["image"]).any(axis=-1))), "of", img.shape[0] * img.shape[1])
-    for k in KEYS:
-        assert st[k] == ref["stats"][k], (k, st[k], ref["stats"][k])
-    np.testing.assert_array_equal(img, ref["image"])
-    assert st["camera_samples"] == spp * sd.width * sd.height and st["rng_draws"] == 2 * st["camera_samples"]
-    return img, st, ref
 
 
 @pytest.mark.parametrize("g", [None, 0.6])
@@ -97,6 +71,14 @@ def test_two_shards_sum_to_the_frame(built):
         np.testing.assert_array_equal(parts[k][0], ref_img)
         for key in KEYS:
             assert parts[k][1][key] == ref_st[key], (k, key)
+
+
+def test_randomized_bre_parity(built):
+    """A short run of the differential fuzzer's bre arm (tests/parity_fuzz.py): random frames from 1x1, coloured media with either phase function, random BSDFs,
+    streamed BVHs, depth options, per-path photon sets, the device-built tree under random group sizes (its map equal to the host's array for array), one shard of 2-4."""
+    from tests.parity_fuzz import run
+    n, bad = run(budget=15.0, seed=21, arm="bre")
+    assert bad == 0 and n >= 20, (n, bad)
 
 
 def test_refused_inputs(built):

@@ -3,7 +3,9 @@ restatement of the reference's text (tests/plane_single_restatement.py): the pla
 scene with two lights, the redraw loop on a crafted sampler state; then the image (assert_array_equal) and every counter over all seven strategies and, for
 average and discrete_mis, a streamed BVH, a ragged frame at spp 1 and 3 with both seed variants, trees of 4 and 5 planes, two lights and two shards.  The
 refused inputs return their codes; the Python mirror equals the restatement's compute, and the CLI (which goes through the C++ mirror's
-IntegratorSinglePlane::compute) writes the bytes the Python mirror renders.  One process; only the CLI test starts a child."""
+IntegratorSinglePlane::compute) writes the bytes the Python mirror renders.  The step-by-step comparison (_exact) lives in tests/gather_exact.py, shared with
+tests/test_gpu_gather_edges.py, and two_lights in tests/scene_helpers.py; the randomized arm of tests/parity_fuzz.py ("plane": every strategy, coloured
+media, random BSDFs, two lights, shards of 2-4) runs from here.  One process; only the CLI test starts a child."""
 import os
 import subprocess
 
@@ -13,22 +15,12 @@ import pytest
 from oracle import orc
 from rustlight_amd import abi, api, scenes
 from tests import plane_single_restatement as R
-from tests.scene_helpers import context as _context
+from tests.gather_exact import PLANE_KEYS as KEYS, plane_exact as _exact
+from tests.scene_helpers import context as _context, two_lights
 
 pytestmark = pytest.mark.gpu
 
 RL_ERR_INVALID_ARGUMENT = -1
-KEYS = ("camera_samples", "extension_rays", "shadow_rays", "rng_draws", "nodes_entered", "planes_intersected", "planes_visible")
-
-
-def two_lights(w, h):
-    """The box with its medium plus a second emissive quad on the left wall; its u x v = (0, 0, 1) x (0, -1, 0) = (1, 0, 0) points into the room."""
-    sd = scenes.cbox_medium(w, h, 1.0)
-    quad = [-0.98, 0.8, -0.3, -0.98, 0.8, 0.3, -0.98, 0.4, 0.3, -0.98, 0.4, -0.3]
-    sd.meshes.append(scenes.MeshData("Light2", np.asarray(quad, np.float32).reshape(4, 3), np.asarray([[0, 1, 2], [0, 2, 3]], np.uint32),
-                                     np.asarray([1.0, 0.0, 0.0] * 4, np.float32).reshape(4, 3), np.asarray([0, 0, 1, 0, 1, 1, 0, 1], np.float32).reshape(4, 2),
-                                     scenes.matte((0.0, 0.0, 0.0)), (4.0, 6.0, 9.0)))
-    return sd
 
 
 def _set_state(sampler, state):
@@ -49,30 +41,6 @@ def _generation(ctx, sd, strategy, nb, seed=3, seed_variant=0, state=None):
     assert list(sampler.s.s) == [int(v) for v in after]
     assert (gst["camera_samples"], gst["vertices"], gst["rng_draws"]) == (n_gen, words.shape[0], draws)
     return pset, sampler, {"words": words, "n_gen": n_gen, "after": after, "redraws": redraws}
-
-
-def _exact(sd, strategy, nb, seed=3, spp=2, seed_variant=0, streaming=False, ref=None):
-    """IntegratorSinglePlane::compute on the GPU and in the restatement, step by step.  Returns (image, gather stats, the restatement's result)."""
-    ctx = _context(sd, streaming)
-    if ref is None:
-        ref = R.compute(sd, seed, nb, strategy, spp, seed_variant)
-    sampler = api.IndependentSampler(seed, seed_variant)
-    pset, _ = ctx.plane_generate(sampler, nb, strategy)
-    np.testing.assert_array_equal(pset.words(), ref["records"])
-    assert list(sampler.s.s) == [int(v) for v in ref["state"]]
-    seeds = sampler.block_seeds(sd.width, sd.height)
-    np.testing.assert_array_equal(seeds, ref["seeds"])
-    pmap = ctx.plane_map(pset)
-    assert pmap.info() == (ref["records"].shape[0], len(ref["detail"]["tree"]["nodes"]), ref["n_gen"], strategy)
-    img, st = ctx.render_plane_single(pmap, seeds, spp, seed_variant)
-    for k in KEYS:
-        print(strategy, k, st[k], ref["stats"][k])
-    print("pixels that differ:", int(np.count_nonzero((img != ref["image"]).any(axis=-1))), "of", img.shape[0] * img.shape[1])
-    for k in KEYS:
-        assert st[k] == ref["stats"][k], (k, st[k], ref["stats"][k])
-    np.testing.assert_array_equal(img, ref["image"])
-    assert st["camera_samples"] == spp * sd.width * sd.height and st["rng_draws"] == 2 * st["camera_samples"] and st["kernel_launches"] == 1
-    return img, st, ref
 
 
 # ---- generation
@@ -185,6 +153,14 @@ def test_map_read_is_the_host_tree(built):
     w = words[order]
     np.testing.assert_array_equal(planes.view(np.uint32)[:, [0, 1, 2, 4, 5, 6, 8, 9, 10, 3, 7, 12, 13, 14]], w[:, :14])      # o, d0, d1, length0, length1, weight
     np.testing.assert_array_equal(planes.view(np.uint32)[:, 11], w[:, 16] + 4 * w[:, 17])
+
+
+def test_randomized_plane_parity(built):
+    """A short run of the differential fuzzer's plane arm (tests/parity_fuzz.py): every strategy on random frames from 1x1, coloured media, random BSDFs, streamed BVHs, a
+    second light, one shard of 2-4; a case both sides refuse (non-finite plane corners) is skipped, and at most a tenth may be."""
+    from tests.parity_fuzz import run
+    n, bad = run(budget=15.0, seed=22, arm="plane")
+    assert bad == 0 and n >= 20, (n, bad)
 
 
 # ---- refusals

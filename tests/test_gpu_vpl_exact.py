@@ -2,7 +2,7 @@
 orc_vpl_generate, orc_render_vpl, written from src/integrators/explicit/vpl.rs): the VPL records, the path count and the advanced sampler, then the
 image and every counter both sides report, over scenes that reach each instantiation (BSDF types, the medium, point / directional lights, uv
 emission), every -l x -v combination with a medium, LDS-staged and streamed BVHs, a ragged frame, spp 1 and 5, both seed variants and two shards.
-The refused inputs return their codes.  One process, no child."""
+The refused inputs return their codes.  The randomized arm of tests/parity_fuzz.py ("vpl") runs from here.  One process, no child."""
 import os
 
 import numpy as np
@@ -110,6 +110,14 @@ def test_two_shards_sum_to_the_frame(built):
     assert not np.logical_and(parts[0][0].any(axis=-1), parts[1][0].any(axis=-1)).any()
     for k in KEYS:
         assert parts[0][1][k] + parts[1][1][k] == st[k], k
+
+
+def test_randomized_vpl_parity(built):
+    """A short run of the differential fuzzer's vpl arm (tests/parity_fuzz.py): the fuzzer's scene kinds that the generation accepts, a coloured medium on a third of them, every
+    -v x -l pair, depth options, streamed BVHs, a third of the sets from per-path streams under a random batch size, one shard of 2-4."""
+    from tests.parity_fuzz import run
+    n, bad = run(budget=15.0, seed=23, arm="vpl")
+    assert bad == 0 and n >= 20, (n, bad)
 
 
 def test_refused_inputs(built):
