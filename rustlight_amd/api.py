@@ -416,7 +416,20 @@ def path_params(spp=1, min_depth=0, max_depth=None, rr_depth=0, strategy=STRATEG
     return p
 
 
-class Context:
+class _ImageCalls:
+    """What Context and MultiContext share: the call that fills one image of the owner's width x height."""
+
+    def _image_call(self, seeds, call, out=None):
+        """One ABI call that renders an image: call(seeds pointer, n, image pointer, stats reference) -> rc.  Returns (image HxWx3 f32, abi.RenderStats); with
+        `out`, a pointer of the caller's, the image goes there and None comes back for it."""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        st = abi.RenderStats()
+        img = np.zeros((self.height, self.width, 3), dtype=np.float32) if out is None else None
+        _check(call(abi.u64ptr(seeds), seeds.shape[0], abi.fptr(img) if out is None else out, C.byref(st)))
+        return img, st
+
+
+class Context(_ImageCalls):
     """Device context = BVHAccel::new(scene) + the scene uploaded to one MI355X."""
 
     def __init__(self, scene: Scene, device: int = 0):
@@ -461,20 +474,11 @@ class Context:
 
     def render(self, seeds: np.ndarray, params: abi.PathParams, out_device_ptr: Optional[int] = None, stream: Optional[int] = None, out_host_ptr: Optional[int] = None):
         """Integrator::compute.  Returns (image HxWx3 f32 | None when rendering into a device pointer or a caller's (e.g. pinned) host buffer, stats dict)."""
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        st = abi.RenderStats()
-        if out_host_ptr is not None:
-            _check(lib().rl_render_path(self.h, C.byref(params), abi.u64ptr(seeds), seeds.shape[0], C.c_void_p(out_host_ptr), 0,
-                                        C.c_void_p(stream) if stream else None, C.byref(st)))
-            return None, st.as_dict()
-        if out_device_ptr is None:
-            img = np.zeros((self.height, self.width, 3), dtype=np.float32)
-            _check(lib().rl_render_path(self.h, C.byref(params), abi.u64ptr(seeds), seeds.shape[0], img.ctypes.data_as(C.c_void_p), 0,
-                                        C.c_void_p(stream) if stream else None, C.byref(st)))
-            return img, st.as_dict()
-        _check(lib().rl_render_path(self.h, C.byref(params), abi.u64ptr(seeds), seeds.shape[0], C.c_void_p(out_device_ptr), 1,
-                                    C.c_void_p(stream) if stream else None, C.byref(st)))
-        return None, st.as_dict()
+        on_device = out_host_ptr is None and out_device_ptr is not None
+        ptr = out_device_ptr if on_device else out_host_ptr
+        img, st = self._image_call(seeds, lambda sp, n, out, st: lib().rl_render_path(self.h, C.byref(params), sp, n, out, int(on_device), C.c_void_p(stream) if stream else None, st),
+                                   None if ptr is None else C.c_void_p(ptr))
+        return img, st.as_dict()
 
     def _render_mc(self, fn, seeds, spp=1, stream_mode=STREAM_PER_SAMPLE, seed_variant=0, shard_index=0, shard_count=1,
                    max_distance=1.0, normal_correction=False, nb_bsdf_samples=1, nb_light_samples=1):
@@ -483,10 +487,7 @@ class Context:
         p.has_max_distance, p.max_distance = (0, 0.0) if max_distance is None else (1, max_distance)
         p.normal_correction = int(normal_correction)
         p.nb_bsdf_samples, p.nb_light_samples = nb_bsdf_samples, nb_light_samples
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        st = abi.RenderStats()
-        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        _check(fn(self.h, C.byref(p), abi.u64ptr(seeds), seeds.shape[0], img.ctypes.data_as(C.c_void_p), 0, None, C.byref(st)))
+        img, st = self._image_call(seeds, lambda sp, n, out, st: fn(self.h, C.byref(p), sp, n, out, 0, None, st))
         return img, st.as_dict()
 
     def render_ao(self, seeds, **kw):
@@ -503,10 +504,7 @@ class Context:
         paths, shadow_rays = camera connections, reserved[0..2] = splats added / dropped as invalid / saturated.  stream_mode, numerics and shard_count only
         take the values the C ABI accepts (anything else is RL_ERR_UNSUPPORTED)."""
         p = path_params(spp, min_depth, max_depth, rr_depth, strategy, False, stream_mode, seed_variant, shard_count=shard_count, numerics=numerics)
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        st = abi.RenderStats()
-        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        _check(lib().rl_render_light(self.h, C.byref(p), abi.u64ptr(seeds), seeds.shape[0], img.ctypes.data_as(C.c_void_p), 0, None, C.byref(st)))
+        img, st = self._image_call(seeds, lambda sp, n, out, st: lib().rl_render_light(self.h, C.byref(p), sp, n, out, 0, None, st))
         d = st.as_dict()
         d["splats"], d["splats_invalid"], d["splats_saturated"] = (int(v) for v in st.reserved[:3])
         return img, d
@@ -534,11 +532,7 @@ class Context:
         """IntegratorVPL's gather (vpl.rs:212-535) through rl_render_vpl: (image HxWx3 f32, stats dict).  stats: shadow_rays = connection rays traced,
         gather_surface / gather_volume = reserved[0] / reserved[1], ms_raygen = primary passes, ms_other = gather passes."""
         p = path_params(spp, 0, None, 0, stream_mode=stream_mode, seed_variant=seed_variant, shard_index=shard_index, shard_count=shard_count, numerics=numerics)
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        st = abi.RenderStats()
-        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        _check(lib().rl_render_vpl(self.h, vpls.h, C.byref(p), option_lt, abi.u64ptr(seeds), seeds.shape[0], img.ctypes.data_as(C.c_void_p), 0, None,
-                                   C.byref(st)))
+        img, st = self._image_call(seeds, lambda sp, n, out, st: lib().rl_render_vpl(self.h, vpls.h, C.byref(p), option_lt, sp, n, out, 0, None, st))
         d = st.as_dict()
         d["gather_surface"], d["gather_volume"] = int(st.reserved[0]), int(st.reserved[1])
         return img, d
@@ -568,10 +562,7 @@ class Context:
 
     def _render_gather(self, fn, handle, seeds, spp, seed_variant, shard_index, shard_count, names):
         """rl_render_bre / rl_render_plane_single: (image HxWx3 f32, stats dict with reserved[k] under names[k])."""
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        st = abi.RenderStats()
-        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        _check(fn(self.h, handle, spp, seed_variant, shard_index, shard_count, abi.u64ptr(seeds), seeds.shape[0], abi.fptr(img), C.byref(st)))
+        img, st = self._image_call(seeds, lambda sp, n, out, st: fn(self.h, handle, spp, seed_variant, shard_index, shard_count, sp, n, out, st))
         d = st.as_dict()
         d.update((name, int(st.reserved[k])) for k, name in enumerate(names))
         return img, d
@@ -657,7 +648,7 @@ class Context:
         return {"ref_nodes": a.value, "prims": b.value, "stack_depth": d.value, "lds_scene": bool(l.value)}
 
 
-class MultiContext:
+class MultiContext(_ImageCalls):
     """N device contexts of one node + an RCCL communicator clique in ONE process (rl_multi_*): shard renders on one host thread
     per GPU, a single ncclReduce over xGMI, one download from the root."""
 
@@ -688,10 +679,7 @@ class MultiContext:
         return dev.value, st.as_dict()
 
     def render(self, seeds: np.ndarray, params: abi.PathParams):
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        st = abi.RenderStats()
-        img = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        _check(lib().rl_multi_render_path(self.h, C.byref(params), abi.u64ptr(seeds), seeds.shape[0], img.ctypes.data_as(C.c_void_p), C.byref(st)))
+        img, st = self._image_call(seeds, lambda sp, n, out, st: lib().rl_multi_render_path(self.h, C.byref(params), sp, n, out, st))
         return img, st.as_dict()
 
     def close(self):
@@ -720,7 +708,30 @@ def stratified_draws(pixel_seeds, spp: int, pattern, seed_variant: int = 0, devi
     return out
 
 
-class IntegratorPathTracing:
+class _Integrator:
+    """What the integrator classes share: the device, the execution options of every context they create (Context.set_option; none changes an image), the
+    stats of the last render and the context of the last scene (the BVH is built once per scene, like BVHAccel::new in IntegratorType::compute)."""
+
+    def __init__(self, device=0, options=None):
+        self.device = device
+        self.options = dict(options or {})
+        self.last_stats = None
+        self._ctx = None
+
+    def _new_context(self, scene: Scene) -> "Context":
+        c = Context(scene, self.device)
+        for k, v in self.options.items():
+            c.set_option(k, v)
+        return c
+
+    def _context(self, scene: Scene) -> "Context":
+        """The context of `scene`: the last one while the scene stays, else a new one."""
+        if self._ctx is None or self._ctx.scene is not scene:
+            self._ctx = self._new_context(scene)
+        return self._ctx
+
+
+class IntegratorPathTracing(_Integrator):
     """struct IntegratorPathTracing (src/integrators/explicit/path.rs:14-20) + Integrator::compute."""
 
     def __init__(self, min_depth=0, max_depth=None, rr_depth=0, strategy=STRATEGY_ALL, single_scattering=False,
@@ -731,28 +742,19 @@ class IntegratorPathTracing:
         one host thread each; the images are those of one frame after the other)."""
         self.min_depth, self.max_depth, self.rr_depth = min_depth, max_depth, rr_depth
         self.strategy, self.single_scattering = strategy, single_scattering
-        self.stream_mode, self.device, self.numerics = stream_mode, device, numerics
+        super().__init__(device, options)
+        self.stream_mode, self.numerics = stream_mode, numerics
         self.frames_in_flight = max(1, int(frames_in_flight))
-        self.options = dict(options or {})          # execution options of every context this integrator creates (Context.set_option; none changes an image)
-        self.last_stats = None
-        self._ctx = None
         self._extra = []
-
-    def _new_context(self, scene: Scene) -> "Context":
-        c = Context(scene, self.device)
-        for k, v in self.options.items():
-            c.set_option(k, v)
-        return c
 
     def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
         """IntegratorType::compute (integrators/mod.rs:274-338): BVH build (untimed) then the render."""
-        if self._ctx is None or self._ctx.scene is not scene:
-            self._ctx = self._new_context(scene)
+        ctx = self._context(scene)
         w, h = scene.size
         seeds = sampler.block_seeds(w, h)
         p = path_params(nb_samples, self.min_depth, self.max_depth, self.rr_depth, self.strategy, self.single_scattering,
                         self.stream_mode, sampler.variant, numerics=self.numerics)
-        img, self.last_stats = self._ctx.render(seeds, p)
+        img, self.last_stats = ctx.render(seeds, p)
         return img
 
     def compute_frames(self, sampler: IndependentSampler, scene: Scene, nb_samples: int, n_frames: int):
@@ -760,8 +762,8 @@ class IntegratorPathTracing:
         as that many sequential calls would draw them — with up to `frames_in_flight` of them on the GPU at once.  A frame's render is a
         chain of dependent launches that leaves much of the chip idle at its tail (reference-order streams: the chain pass ends with its
         slowest wave); another context's frame fills it.  Returns the images in frame order."""
-        if self._ctx is None or self._ctx.scene is not scene:
-            self._ctx = self._new_context(scene)
+        before = self._ctx
+        if self._context(scene) is not before:
             self._extra = []
         k = min(self.frames_in_flight, max(1, n_frames))
         while len(self._extra) < k - 1:
@@ -776,26 +778,20 @@ class IntegratorPathTracing:
         return [img for img, _ in out]
 
 
-class IntegratorLightTracing:
+class IntegratorLightTracing(_Integrator):
     """struct IntegratorLightTracing (src/integrators/explicit/light.rs:7-13) + Integrator::compute: light paths splatted through the camera, on the
     per-sample streams (rl_render_light).  strategy: LIGHT_ALL / LIGHT_SURFACE / LIGHT_VOLUME (render_surface / render_volume)."""
 
     def __init__(self, min_depth=0, max_depth=None, rr_depth=0, strategy=LIGHT_ALL, device=0, options=None):
+        super().__init__(device, options)
         self.min_depth, self.max_depth, self.rr_depth, self.strategy = min_depth, max_depth, rr_depth, strategy
-        self.device = device
-        self.options = dict(options or {})
-        self.last_stats = None
-        self._ctx = None
 
     def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
         """The block seeds are drawn from the master sampler as IntegratorPathTracing.compute draws them."""
-        if self._ctx is None or self._ctx.scene is not scene:
-            self._ctx = Context(scene, self.device)
-            for k, v in self.options.items():
-                self._ctx.set_option(k, v)
+        ctx = self._context(scene)
         w, h = scene.size
         seeds = sampler.block_seeds(w, h)
-        img, self.last_stats = self._ctx.render_light(seeds, nb_samples, self.min_depth, self.max_depth, self.rr_depth, self.strategy, sampler.variant)
+        img, self.last_stats = ctx.render_light(seeds, nb_samples, self.min_depth, self.max_depth, self.rr_depth, self.strategy, sampler.variant)
         return img
 
 
@@ -888,7 +884,7 @@ def photon_tree_build(words, radius):
     return _tree_arrays(lambda *out: lib().rl_photon_tree_build(abi.u32ptr(w), w.shape[0], radius, *out), w.shape[0])
 
 
-class IntegratorVolPrimitives:
+class IntegratorVolPrimitives(_Integrator):
     """struct IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute for
     primitives = BRE, seed for seed the reference: the photons from the main sampler, the block seeds from the sampler they leave, the gather on
     reference-order streams.  radius: the reference's constant unless given.  light_streams="per_path": the photons from rl_vpl_generate_paths (one light path
@@ -903,27 +899,21 @@ class IntegratorVolPrimitives:
             raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
         if tree_build not in TREE_BUILDS:
             raise ValueError(f"tree_build must be one of {TREE_BUILDS}, not {tree_build!r}")
+        super().__init__(device, options)
         self.light_streams = light_streams
         self.tree_build = tree_build
         self.nb_primitive, self.max_depth, self.rr_depth, self.radius = nb_primitive, max_depth, rr_depth, radius
-        self.device = device
-        self.options = dict(options or {})
-        self.last_stats = None
         self.last_generation_stats = None
-        self._ctx = None
 
     def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
-        if self._ctx is None or self._ctx.scene is not scene:
-            self._ctx = Context(scene, self.device)
-            for k, v in self.options.items():
-                self._ctx.set_option(k, v)
-        vpls, self.last_generation_stats = self._ctx.vpl_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, VPL_VOLUME, self.light_streams)
+        ctx = self._context(scene)
+        vpls, self.last_generation_stats = ctx.vpl_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, VPL_VOLUME, self.light_streams)
         photons = None
         try:
-            photons = self._ctx.photon_map(vpls, self.radius, self.tree_build)
+            photons = ctx.photon_map(vpls, self.radius, self.tree_build)
             w, h = scene.size
             seeds = sampler.block_seeds(w, h)
-            img, self.last_stats = self._ctx.render_bre(photons, seeds, nb_samples, sampler.variant)
+            img, self.last_stats = ctx.render_bre(photons, seeds, nb_samples, sampler.variant)
         finally:
             if photons is not None:
                 photons.close()
@@ -989,30 +979,24 @@ def plane_tree_build(words):
     return _tree_arrays(lambda *out: lib().rl_plane_tree_build(abi.u32ptr(w), w.shape[0], *out), w.shape[0])
 
 
-class IntegratorSinglePlane:
+class IntegratorSinglePlane(_Integrator):
     """struct IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs:291-294) + Integrator::compute, seed for seed the
     reference: the planes from the main sampler, the plane tree, the block seeds from the sampler the generation leaves, the gather on reference-order streams."""
 
     def __init__(self, nb_primitive=128, strategy="average", device=0, options=None):
+        super().__init__(device, options)
         self.nb_primitive, self.strategy = nb_primitive, PLANE_STRATEGIES[plane_strategy(strategy)]
-        self.device = device
-        self.options = dict(options or {})
-        self.last_stats = None
         self.last_generation_stats = None
-        self._ctx = None
 
     def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
-        if self._ctx is None or self._ctx.scene is not scene:
-            self._ctx = Context(scene, self.device)
-            for k, v in self.options.items():
-                self._ctx.set_option(k, v)
-        planes, self.last_generation_stats = self._ctx.plane_generate(sampler, self.nb_primitive, self.strategy)
+        ctx = self._context(scene)
+        planes, self.last_generation_stats = ctx.plane_generate(sampler, self.nb_primitive, self.strategy)
         pmap = None
         try:
-            pmap = self._ctx.plane_map(planes)
+            pmap = ctx.plane_map(planes)
             w, h = scene.size
             seeds = sampler.block_seeds(w, h)
-            img, self.last_stats = self._ctx.render_plane_single(pmap, seeds, nb_samples, sampler.variant)
+            img, self.last_stats = ctx.render_plane_single(pmap, seeds, nb_samples, sampler.variant)
         finally:
             if pmap is not None:
                 pmap.close()
@@ -1020,7 +1004,7 @@ class IntegratorSinglePlane:
         return img
 
 
-class IntegratorVPL:
+class IntegratorVPL(_Integrator):
     """struct IntegratorVPL (src/integrators/explicit/vpl.rs:16-23) + Integrator::compute, seed for seed the reference: the VPLs from the main sampler, the
     block seeds from the sampler they leave, the gather on reference-order streams.  clamping_factor is not a field: the reference never reads it.  light_streams="per_path": the VPLs from
     rl_vpl_generate_paths (one light path per lane, each on its own stream): statistically, not seed-for-seed, the same image."""
@@ -1028,25 +1012,19 @@ class IntegratorVPL:
     def __init__(self, nb_vpl=128, max_depth=None, rr_depth=0, option_vpl=VPL_ALL, option_lt=VPL_ALL, device=0, options=None, light_streams="reference"):
         if light_streams not in LIGHT_STREAMS:
             raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
+        super().__init__(device, options)
         self.light_streams = light_streams
         self.nb_vpl, self.max_depth, self.rr_depth = nb_vpl, max_depth, rr_depth
         self.option_vpl, self.option_lt = option_vpl, option_lt
-        self.device = device
-        self.options = dict(options or {})
-        self.last_stats = None
         self.last_generation_stats = None
-        self._ctx = None
 
     def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
-        if self._ctx is None or self._ctx.scene is not scene:
-            self._ctx = Context(scene, self.device)
-            for k, v in self.options.items():
-                self._ctx.set_option(k, v)
-        vpls, self.last_generation_stats = self._ctx.vpl_generate(sampler, self.nb_vpl, self.max_depth, self.rr_depth, self.option_vpl, self.light_streams)
+        ctx = self._context(scene)
+        vpls, self.last_generation_stats = ctx.vpl_generate(sampler, self.nb_vpl, self.max_depth, self.rr_depth, self.option_vpl, self.light_streams)
         try:
             w, h = scene.size
             seeds = sampler.block_seeds(w, h)
-            img, self.last_stats = self._ctx.render_vpl(vpls, seeds, nb_samples, self.option_lt, sampler.variant)
+            img, self.last_stats = ctx.render_vpl(vpls, seeds, nb_samples, self.option_lt, sampler.variant)
         finally:
             vpls.close()
         return img

@@ -41,6 +41,28 @@ static std::optional<uint32_t> match_infinity(const std::string& s) {   // cli.r
     return (uint32_t)v;
 }
 
+// --nb-vpl / --nb-primitive: 1 .. RL_VPL_MAX
+static bool parse_count(const char* flag, const std::string& s, uint32_t* out) {
+    char* end = nullptr;
+    const unsigned long long n = std::strtoull(s.c_str(), &end, 10);
+    if (s.empty() || *end != '\0' || n == 0 || n > (unsigned long long)RL_VPL_MAX) { std::fprintf(stderr, "invalid %s: %s (1 .. %d)\n", flag, s.c_str(), (int)RL_VPL_MAX); return false; }
+    *out = (uint32_t)n;
+    return true;
+}
+// -m sigma_s[:sigma_a[:g]] (cli.rs:355-399)
+struct Medium { size_t n_parts = 0; float sigma_s = 0.0f, sigma_a = 0.0f, g = 0.0f; };
+static Medium parse_medium(const std::string& s) {
+    std::vector<std::string> parts;
+    std::stringstream ss(s);
+    for (std::string tok; std::getline(ss, tok, ':');) parts.push_back(tok);
+    Medium m;
+    m.n_parts = parts.size();
+    if (parts.size() > 0) m.sigma_s = std::strtof(parts[0].c_str(), nullptr);
+    if (parts.size() > 1) m.sigma_a = std::strtof(parts[1].c_str(), nullptr);
+    if (parts.size() > 2) m.g = std::strtof(parts[2].c_str(), nullptr);
+    return m;
+}
+
 int main(int argc, char** argv) {
     std::string scene_path, output, medium = "0.0", rng = "independent", strategy = "all";
     std::string max_depth = "inf", min_depth = "0", rr_depth = "0";
@@ -56,7 +78,7 @@ int main(int argc, char** argv) {
     bool mode_given = false;                            // (-r stratified sets the mode itself)
     uint32_t numerics = RL_NUMERICS_EXACT;
     int frames_in_flight = 1;
-    std::vector<std::pair<std::string, std::string>> options;
+    Options options;
     std::string nb_vpl = "128", option_lt = "all", option_vpl = "all";     // vpl (cli.rs:176-184)
     std::string nb_primitive = "128", primitives = "bre", radius = "0.001";     // vol-primitivies (cli.rs:189-196)
     std::string light_streams = "reference";            // vpl, vol-primitivies: `--light-streams per-path` shoots the light paths in parallel, each on its own stream
@@ -156,13 +178,22 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "usage: rustlight-amd <scene.pbrt|scene.xml> -n SPP -o out.pfm [-r independent[:SEED]|stratified[:SEED]] [-m s[:a[:g]]] path [-m max] [-n min] [-r rr] [-x] [-s all|bsdf|emitter]\n");
         return 2;
     }
-    // light-tracing runs on per-sample streams, exact numerics, one device: what it cannot do is refused here, before a device is opened
+    // A light-pass command runs on the independent sampler, one kind of streams (`streams`: per-sample for light-tracing, reference order for the gathers), exact
+    // numerics and one device, and all but light-tracing (`one_pass`) in one pass: what it cannot do is refused here, before a device is opened
+    auto refused = [&](const char* name, rl_stream_mode streams, bool one_pass) -> bool {
+        const char* why = nullptr;
+        if (rng == "stratified" || rng.rfind("stratified:", 0) == 0) why = "-r stratified is not supported (independent[:SEED] only)";
+        else if (mode_given && mode != streams) why = streams == RL_STREAM_PER_SAMPLE ? "--stream-mode reference is not supported (light paths use per-sample streams)" : "--stream-mode per-sample is not supported (the gather uses reference-order streams)";
+        else if (numerics == RL_NUMERICS_FAST) why = "--numerics fast is not supported";
+        else if (gpus > 1) why = "--gpus > 1 is not supported";
+        else if (one_pass && (!average.empty() || !equal_time.empty())) why = "-a / -e are not supported";
+        else if (one_pass && frames_in_flight > 1) why = "--frames-in-flight is not supported";
+        if (why) std::fprintf(stderr, "%s: %s\n", name, why);
+        return why != nullptr;
+    };
     IntegratorLightTracing light;
     if (cmd == "light-tracing") {
-        if (rng == "stratified" || rng.rfind("stratified:", 0) == 0) { std::fprintf(stderr, "light-tracing: -r stratified is not supported (independent[:SEED] only)\n"); return 2; }
-        if (mode_given && mode != RL_STREAM_PER_SAMPLE) { std::fprintf(stderr, "light-tracing: --stream-mode reference is not supported (light paths use per-sample streams)\n"); return 2; }
-        if (numerics == RL_NUMERICS_FAST) { std::fprintf(stderr, "light-tracing: --numerics fast is not supported\n"); return 2; }
-        if (gpus > 1) { std::fprintf(stderr, "light-tracing: --gpus > 1 is not supported\n"); return 2; }
+        if (refused("light-tracing", RL_STREAM_PER_SAMPLE, false)) return 2;
         if (strategy == "all") light.strategy = RL_LIGHT_ALL;
         else if (strategy == "surface") light.strategy = RL_LIGHT_SURFACE;
         else if (strategy == "volume") light.strategy = RL_LIGHT_VOLUME;
@@ -179,46 +210,30 @@ int main(int argc, char** argv) {
         if (light_streams == "per-path") light_streams_mode = LightStreams::PerPath;
         else if (light_streams != "reference") { std::fprintf(stderr, "invalid --light-streams: %s (reference or per-path)\n", light_streams.c_str()); return 2; }
     }
-    // vpl runs on reference-order streams, exact numerics, one device, one pass: what it cannot do is refused here, before a device is opened
     IntegratorVPL vpl;
     if (cmd == "vpl") {
         auto option = [](const std::string& v, rl_vpl_option* out) {
             if (v == "all") *out = RL_VPL_ALL; else if (v == "surface") *out = RL_VPL_SURFACE; else if (v == "volume") *out = RL_VPL_VOLUME; else return false;
             return true;
         };
-        if (rng == "stratified" || rng.rfind("stratified:", 0) == 0) { std::fprintf(stderr, "vpl: -r stratified is not supported (independent[:SEED] only)\n"); return 2; }
-        if (mode_given && mode != RL_STREAM_REFERENCE_ORDER) { std::fprintf(stderr, "vpl: --stream-mode per-sample is not supported (the gather uses reference-order streams)\n"); return 2; }
-        if (numerics == RL_NUMERICS_FAST) { std::fprintf(stderr, "vpl: --numerics fast is not supported\n"); return 2; }
-        if (gpus > 1) { std::fprintf(stderr, "vpl: --gpus > 1 is not supported\n"); return 2; }
-        if (!average.empty() || !equal_time.empty()) { std::fprintf(stderr, "vpl: -a / -e are not supported\n"); return 2; }
-        if (frames_in_flight > 1) { std::fprintf(stderr, "vpl: --frames-in-flight is not supported\n"); return 2; }
+        if (refused("vpl", RL_STREAM_REFERENCE_ORDER, true)) return 2;
         if (!option(option_lt, &vpl.option_lt)) { std::fprintf(stderr, "invalid vpl -l option: %s (all, surface or volume)\n", option_lt.c_str()); return 2; }
         if (!option(option_vpl, &vpl.option_vpl)) { std::fprintf(stderr, "invalid vpl -v option: %s (all, surface or volume)\n", option_vpl.c_str()); return 2; }
-        char* end = nullptr;
-        const unsigned long long n = std::strtoull(nb_vpl.c_str(), &end, 10);
-        if (nb_vpl.empty() || *end != '\0' || n == 0 || n > (unsigned long long)RL_VPL_MAX) { std::fprintf(stderr, "invalid --nb-vpl: %s (1 .. %d)\n", nb_vpl.c_str(), (int)RL_VPL_MAX); return 2; }
-        vpl.nb_vpl = (uint32_t)n;
+        if (!parse_count("--nb-vpl", nb_vpl, &vpl.nb_vpl)) return 2;
         vpl.max_depth = match_infinity(max_depth);
         vpl.rr_depth = match_infinity(rr_depth);
         vpl.light_streams = light_streams_mode;
         vpl.device = device;
         vpl.options = options;
     }
-    // vol-primitivies: the same limits as vpl; the primitives that are not built are refused here
+    // vol-primitivies: the primitives that are not built are refused here
     IntegratorVolPrimitives volp;
     if (cmd == "vol-primitivies") {
         if (primitives == "beam" || primitives == "plane" || primitives == "vrl") { std::fprintf(stderr, "vol-primitivies: -p %s is not built (bre only)\n", primitives.c_str()); return 2; }
         if (primitives != "bre") { std::fprintf(stderr, "%s is not a correct primitive (bre, beam, plane, vrl)\n", primitives.c_str()); return 2; }
-        if (rng == "stratified" || rng.rfind("stratified:", 0) == 0) { std::fprintf(stderr, "vol-primitivies: -r stratified is not supported (independent[:SEED] only)\n"); return 2; }
-        if (mode_given && mode != RL_STREAM_REFERENCE_ORDER) { std::fprintf(stderr, "vol-primitivies: --stream-mode per-sample is not supported (the gather uses reference-order streams)\n"); return 2; }
-        if (numerics == RL_NUMERICS_FAST) { std::fprintf(stderr, "vol-primitivies: --numerics fast is not supported\n"); return 2; }
-        if (gpus > 1) { std::fprintf(stderr, "vol-primitivies: --gpus > 1 is not supported\n"); return 2; }
-        if (!average.empty() || !equal_time.empty()) { std::fprintf(stderr, "vol-primitivies: -a / -e are not supported\n"); return 2; }
-        if (frames_in_flight > 1) { std::fprintf(stderr, "vol-primitivies: --frames-in-flight is not supported\n"); return 2; }
+        if (refused("vol-primitivies", RL_STREAM_REFERENCE_ORDER, true)) return 2;
+        if (!parse_count("--nb-primitive", nb_primitive, &volp.nb_primitive)) return 2;
         char* end = nullptr;
-        const unsigned long long n = std::strtoull(nb_primitive.c_str(), &end, 10);
-        if (nb_primitive.empty() || *end != '\0' || n == 0 || n > (unsigned long long)RL_VPL_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", nb_primitive.c_str(), (int)RL_VPL_MAX); return 2; }
-        volp.nb_primitive = (uint32_t)n;
         volp.radius = std::strtof(radius.c_str(), &end);
         if (radius.empty() || *end != '\0' || !(volp.radius > 0.0f) || volp.radius > 3.0e38f) { std::fprintf(stderr, "invalid --radius: %s (a finite number > 0)\n", radius.c_str()); return 2; }
         volp.max_depth = match_infinity(max_depth);
@@ -229,7 +244,7 @@ int main(int argc, char** argv) {
         volp.device = device;
         volp.options = options;
     }
-    // plane-single: the same limits as vol-primitivies, and it needs the medium
+    // plane-single needs the medium
     IntegratorSinglePlane plane;
     if (cmd == "plane-single") {
         static const char* const names[] = {"uv", "vt", "ut", "average", "discrete_mis", "ualpha", "cmis"};      // rl_plane_strategy, by value
@@ -237,23 +252,11 @@ int main(int argc, char** argv) {
         for (int k = 0; k < 7; k++) if (plane_strategy == names[k]) which = k;
         if (which < 0) { std::fprintf(stderr, "%s is not a correct strategy choice (uv, ut, vt, average, discrete_mis, valpha, cmis)\n", plane_strategy.c_str()); return 2; }
         plane.strategy = (rl_plane_strategy)which;
-        if (rng == "stratified" || rng.rfind("stratified:", 0) == 0) { std::fprintf(stderr, "plane-single: -r stratified is not supported (independent[:SEED] only)\n"); return 2; }
-        if (mode_given && mode != RL_STREAM_REFERENCE_ORDER) { std::fprintf(stderr, "plane-single: --stream-mode per-sample is not supported (the gather uses reference-order streams)\n"); return 2; }
-        if (numerics == RL_NUMERICS_FAST) { std::fprintf(stderr, "plane-single: --numerics fast is not supported\n"); return 2; }
-        if (gpus > 1) { std::fprintf(stderr, "plane-single: --gpus > 1 is not supported\n"); return 2; }
-        if (!average.empty() || !equal_time.empty()) { std::fprintf(stderr, "plane-single: -a / -e are not supported\n"); return 2; }
-        if (frames_in_flight > 1) { std::fprintf(stderr, "plane-single: --frames-in-flight is not supported\n"); return 2; }
-        char* end = nullptr;
-        const unsigned long long n = std::strtoull(plane_nb.c_str(), &end, 10);
-        if (plane_nb.empty() || *end != '\0' || n == 0 || n > (unsigned long long)RL_VPL_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", plane_nb.c_str(), (int)RL_VPL_MAX); return 2; }
-        plane.nb_primitive = (uint32_t)n;
-        {   // "Volume integrator need a volume (add -m )": the medium string as it is parsed below
-            std::vector<std::string> parts;
-            std::stringstream ss(medium);
-            for (std::string tok; std::getline(ss, tok, ':');) parts.push_back(tok);
-            const float sigma_s = parts.size() > 0 ? std::strtof(parts[0].c_str(), nullptr) : 0.0f, sigma_a = parts.size() > 1 ? std::strtof(parts[1].c_str(), nullptr) : 0.0f;
-            if (sigma_a + sigma_s == 0.0f) { std::fprintf(stderr, "plane-single: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n"); return 2; }
-        }
+        if (refused("plane-single", RL_STREAM_REFERENCE_ORDER, true)) return 2;
+        if (!parse_count("--nb-primitive", plane_nb, &plane.nb_primitive)) return 2;
+        // "Volume integrator need a volume (add -m )": the medium string as the scene setup below parses it
+        const Medium m = parse_medium(medium);
+        if (m.sigma_a + m.sigma_s == 0.0f) { std::fprintf(stderr, "plane-single: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n"); return 2; }
         plane.device = device;
         plane.options = options;
     }
@@ -289,18 +292,11 @@ int main(int argc, char** argv) {
         std::unique_ptr<Scene> scene(Scene::load(scene_path, shading_normals));
         scene->nb_samples = nbsamples;
         scene->output_img_path = output;
-        {   // medium: sigma_s[:sigma_a[:g]] (cli.rs:355-399)
-            std::vector<std::string> parts;
-            std::stringstream ss(medium);
-            for (std::string tok; std::getline(ss, tok, ':');) parts.push_back(tok);
-            float sigma_s = parts.size() > 0 ? std::strtof(parts[0].c_str(), nullptr) : 0.0f;
-            float sigma_a = parts.size() > 1 ? std::strtof(parts[1].c_str(), nullptr) : 0.0f;
-            if (parts.size() > 3) { std::fprintf(stderr, "invalid medium_density\n"); return 2; }
-            if (sigma_a + sigma_s != 0.0f) {
-                float sa[3] = {sigma_a, sigma_a, sigma_a}, s3[3] = {sigma_s, sigma_s, sigma_s};
-                float g = parts.size() > 2 ? std::strtof(parts[2].c_str(), nullptr) : 0.0f;
-                if (rl_scene_set_medium(scene->handle, sa, s3, parts.size() > 2 ? RL_PHASE_HG : RL_PHASE_ISOTROPIC, g) != RL_OK) { std::fprintf(stderr, "invalid medium_density\n"); return 2; }
-            }
+        const Medium m = parse_medium(medium);
+        if (m.n_parts > 3) { std::fprintf(stderr, "invalid medium_density\n"); return 2; }
+        if (m.sigma_a + m.sigma_s != 0.0f) {
+            float sa[3] = {m.sigma_a, m.sigma_a, m.sigma_a}, s3[3] = {m.sigma_s, m.sigma_s, m.sigma_s};
+            if (rl_scene_set_medium(scene->handle, sa, s3, m.n_parts > 2 ? RL_PHASE_HG : RL_PHASE_ISOTROPIC, m.g) != RL_OK) { std::fprintf(stderr, "invalid medium_density\n"); return 2; }
         }
         if (scale_image != 1.0f && rl_scene_scale_image(scene->handle, scale_image) != RL_OK) { std::fprintf(stderr, "invalid image scale: %s\n", rl_last_error()); return 2; }
         if (light_override != RL_EMISSION_COLOR) {   // "Overide light is needed" (cli.rs:410-429): every light mesh becomes HSV { scale } / Texture { scale, butterfly.jpg }

@@ -1,4 +1,4 @@
-// hip_buffer.h — host only: HIP_OK and the owned buffers of the host driver (device memory, pinned host memory, mapped host memory).
+// hip_buffer.h — host only: HIP_OK, the owned buffers of the host driver (device memory, pinned host memory, mapped host memory) and its owned event pair.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,6 +67,20 @@ private:
     T* p_ = nullptr;
     T* d_ = nullptr;     // Mapped: the device's address of p_
     size_t n_ = 0;
+};
+
+// Two events around the launches of a call that has no RenderFrame.  After open(false) every member does nothing; add(), after a synchronisation, adds the time to ms.
+struct __attribute__((visibility("hidden"))) EventPair {      // (host-internal, like the driver's other helpers: not a symbol of the library)
+    hipEvent_t e[2] = {nullptr, nullptr};
+    float ms = 0.0f;
+    int open(bool timing) {
+        if (timing) { HIP_OK(hipEventCreate(&e[0])); HIP_OK(hipEventCreate(&e[1])); }
+        return RL_OK;
+    }
+    void begin(hipStream_t st) { if (e[0]) (void)hipEventRecord(e[0], st); }
+    void end(hipStream_t st) { if (e[1]) (void)hipEventRecord(e[1], st); }
+    void add() { float t = 0.0f; if (e[1] && hipEventElapsedTime(&t, e[0], e[1]) == hipSuccess) ms += t; (void)hipGetLastError(); }
+    ~EventPair() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); (void)hipGetLastError(); }
 };
 
 }  // namespace rl

@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -60,6 +61,51 @@ struct BufferCollection {   // only the "primal" buffer exists on this path
     void accumulate_bitmap(const BufferCollection& o) { for (size_t i = 0; i < primal.size(); i++) primal[i] += o.primal[i]; }
 };
 
+// ---- what every integrator's compute() does around its own ABI calls, written once
+using Options = std::vector<std::pair<std::string, std::string>>;   // execution options of a device context: `rustlight-amd --option name=value`
+inline void check(int rc, const char* what) {   // "<what>: <the library's message>"
+    if (rc != RL_OK) throw std::runtime_error(std::string(what) + ": " + rl_last_error());
+}
+// the ABI's handles, destroyed with their owner: also when what runs after their creation throws
+template <class T, void (*Destroy)(T*)> struct HandleDeleter { void operator()(T* h) const { Destroy(h); } };
+template <class T, void (*Destroy)(T*)> using Handle = std::unique_ptr<T, HandleDeleter<T, Destroy>>;
+using ContextHandle = Handle<rl_context, rl_context_destroy>;
+using VplSetHandle = Handle<rl_vpl_set, rl_vpl_destroy>;
+using PhotonMapHandle = Handle<rl_photon_map, rl_photon_map_destroy>;
+using PlaneSetHandle = Handle<rl_plane_set, rl_plane_destroy>;
+using PlaneMapHandle = Handle<rl_plane_map, rl_plane_map_destroy>;
+inline ContextHandle create_context(const Scene& scene, int device) {
+    rl_context* c = nullptr;
+    check(rl_context_create(scene.handle, device, &c), "rl_context_create");
+    return ContextHandle(c);
+}
+// `named`: the message names the option ("--option NAME: ...") instead of the call
+inline void apply_options(rl_context* c, const Options& options, bool named) {
+    for (const auto& o : options) check(rl_context_set_option(c, o.first.c_str(), o.second.c_str()), (named ? "--option " + o.first : std::string("rl_context_set_option")).c_str());
+}
+inline BufferCollection zeroed_image(const Scene& scene) {
+    BufferCollection img;
+    rl_scene_image_size(scene.handle, &img.width, &img.height);
+    img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
+    return img;
+}
+inline std::vector<uint64_t> draw_block_seeds(IndependentSampler& sampler, const BufferCollection& img) {   // generate_img_blocks
+    std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
+    rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
+    return seeds;
+}
+// One render's device context: created on (scene, device) with the options applied, destroyed with the render; img is the zeroed image of the scene's size
+struct RenderContext {
+    ContextHandle ctx;
+    BufferCollection img;
+    RenderContext(const Scene& scene, int device, const Options& options = {}) : ctx(create_context(scene, device)) {
+        apply_options(ctx.get(), options, true);
+        img = zeroed_image(scene);
+    }
+    operator rl_context*() const { return ctx.get(); }
+    std::vector<uint64_t> block_seeds(IndependentSampler& sampler) const { return draw_block_seeds(sampler, img); }
+};
+
 enum class IntegratorPathTracingStrategies { All = RL_STRATEGY_ALL, BSDF = RL_STRATEGY_BSDF, Emitter = RL_STRATEGY_EMITTER };
 
 struct IntegratorPathTracing {
@@ -84,13 +130,10 @@ struct IntegratorPathTracing {
     // streams: the chain pass ends with its slowest wave); another context's frame fills it.  The images are those of one frame after the other.
     int frames_in_flight = 1;
 
-    // execution options handed to every device context this integrator creates (rl_context_set_option: test / measurement hooks, none changes an image;
+    // execution options handed to every device context this integrator creates (Options above: test / measurement hooks, none changes an image;
     // e.g. {"spec_draws_per_sample", "40"}); `rustlight-amd --option name=value`
-    std::vector<std::pair<std::string, std::string>> options;
-    void apply_options(rl_context* c) const {
-        for (const auto& o : options)
-            if (rl_context_set_option(c, o.first.c_str(), o.second.c_str()) != RL_OK) throw std::runtime_error(std::string("rl_context_set_option: ") + rl_last_error());
-    }
+    Options options;
+    void apply_options(rl_context* c) const { rustlight::apply_options(c, options, false); }
 
     // the device contexts (BVH + uploaded scene) are built once per scene, like `BVHAccel::new` in IntegratorType::compute
     rl_context* ctx = nullptr;
@@ -135,24 +178,20 @@ struct IntegratorPathTracing {
         }
         if (ctx_scene != &scene || ctx_gpus != 1 || !ctx) {
             release();
-            if (rl_context_create(scene.handle, device, &ctx) != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
+            ctx = create_context(scene, device).release();
             apply_options(ctx);
             ctx_scene = &scene; ctx_gpus = 1;
         }
         while (extra_ctx.size() + 1 < k) {
-            rl_context* c = nullptr;
-            if (rl_context_create(scene.handle, device, &c) != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
-            extra_ctx.push_back(c);
-            apply_options(c);
+            extra_ctx.push_back(create_context(scene, device).release());
+            apply_options(extra_ctx.back());
         }
         const rl_path_params p = params_for(sampler, scene);
         out.resize(n_frames);
         std::vector<std::vector<uint64_t>> seeds(n_frames);
         for (size_t j = 0; j < n_frames; j++) {
-            rl_scene_image_size(scene.handle, &out[j].width, &out[j].height);
-            out[j].primal.assign((size_t)3 * out[j].width * out[j].height, 0.0f);
-            seeds[j].resize(rl_block_count(out[j].width, out[j].height));
-            rl_generate_block_seeds(&sampler.rnd, out[j].width, out[j].height, seeds[j].data(), seeds[j].size());   // generate_img_blocks, in frame order
+            out[j] = zeroed_image(scene);
+            seeds[j] = draw_block_seeds(sampler, out[j]);   // in frame order
         }
         std::vector<std::string> errors(k);
         std::vector<rl_render_stats> stats(k);
@@ -176,33 +215,26 @@ struct IntegratorPathTracing {
         if (ctx_scene != &scene || ctx_gpus != n || (!ctx && !multi)) {
             release();
             if (n == 1) {
-                int rc = rl_context_create(scene.handle, device, &ctx);
-                if (rc != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
+                ctx = create_context(scene, device).release();
                 apply_options(ctx);
             } else {
                 int n_dev = 0;
                 rl_device_count(&n_dev);
                 std::vector<int> devs(n);
                 for (int g = 0; g < n; g++) devs[g] = n_dev > 0 ? (device + g) % n_dev : device + g;
-                int rc = rl_multi_create(scene.handle, devs.data(), n, &multi);
-                if (rc != RL_OK) throw std::runtime_error(std::string("rl_multi_create: ") + rl_last_error());
+                check(rl_multi_create(scene.handle, devs.data(), n, &multi), "rl_multi_create");
             }
             ctx_scene = &scene; ctx_gpus = n;
         }
-        BufferCollection img;
-        rl_scene_image_size(scene.handle, &img.width, &img.height);
-        img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
+        BufferCollection img = zeroed_image(scene);
         rl_path_params p = params_for(sampler, scene);
-        std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
-        rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());   // generate_img_blocks
+        const std::vector<uint64_t> seeds = draw_block_seeds(sampler, img);
         if (n == 1) {
-            int rc = rl_render_path(ctx, &p, seeds.data(), seeds.size(), img.primal.data(), 0, nullptr, &last_stats);
-            if (rc != RL_OK) throw std::runtime_error(std::string("rl_render_path: ") + rl_last_error());
+            check(rl_render_path(ctx, &p, seeds.data(), seeds.size(), img.primal.data(), 0, nullptr, &last_stats), "rl_render_path");
             return img;
         }
         p.shard_index = 0; p.shard_count = 1;      // (rl_multi deals the blocks itself)
-        int rc = rl_multi_render_path(multi, &p, seeds.data(), seeds.size(), img.primal.data(), &last_stats);
-        if (rc != RL_OK) throw std::runtime_error(std::string("rl_multi_render_path: ") + rl_last_error());
+        check(rl_multi_render_path(multi, &p, seeds.data(), seeds.size(), img.primal.data(), &last_stats), "rl_multi_render_path");
         return img;
     }
 };
@@ -214,22 +246,14 @@ struct IntegratorMC {
     rl_render_stats last_stats{};
   protected:
     BufferCollection run(bool direct, rl_mc_params p, IndependentSampler& sampler, Scene& scene) {
-        rl_context* ctx = nullptr;
-        int rc = rl_context_create(scene.handle, device, &ctx);
-        if (rc != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
-        BufferCollection img;
-        rl_scene_image_size(scene.handle, &img.width, &img.height);
-        img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
+        RenderContext ctx(scene, device);
         p.spp = (uint32_t)scene.nb_samples;
         p.stream_mode = stream_mode;
         p.seed_variant = sampler.variant;
         p.shard_index = 0; p.shard_count = 1;
-        std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
-        rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
-        rc = (direct ? rl_render_direct : rl_render_ao)(ctx, &p, seeds.data(), seeds.size(), img.primal.data(), 0, nullptr, &last_stats);
-        rl_context_destroy(ctx);
-        if (rc != RL_OK) throw std::runtime_error(std::string("render: ") + rl_last_error());
-        return img;
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        check((direct ? rl_render_direct : rl_render_ao)(ctx, &p, seeds.data(), seeds.size(), ctx.img.primal.data(), 0, nullptr, &last_stats), "render");
+        return std::move(ctx.img);
     }
 };
 struct IntegratorAO : IntegratorMC {
@@ -256,17 +280,10 @@ struct IntegratorLightTracing {
     std::optional<uint32_t> max_depth, min_depth, rr_depth;
     rl_light_strategy strategy = RL_LIGHT_ALL;     // all | surface | volume: render_surface / render_volume
     int device = 0;
-    std::vector<std::pair<std::string, std::string>> options;
+    Options options;
     rl_render_stats last_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
-        rl_context* ctx = nullptr;
-        int rc = rl_context_create(scene.handle, device, &ctx);
-        if (rc != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
-        for (const auto& o : options)
-            if (rl_context_set_option(ctx, o.first.c_str(), o.second.c_str()) != RL_OK) { const std::string e = rl_last_error(); rl_context_destroy(ctx); throw std::runtime_error("--option " + o.first + ": " + e); }
-        BufferCollection img;
-        rl_scene_image_size(scene.handle, &img.width, &img.height);
-        img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
+        RenderContext ctx(scene, device, options);
         rl_path_params p;
         rl_path_params_default(&p);
         p.spp = (uint32_t)scene.nb_samples;
@@ -276,12 +293,9 @@ struct IntegratorLightTracing {
         p.strategy = strategy;
         p.stream_mode = RL_STREAM_PER_SAMPLE;
         p.seed_variant = sampler.variant;
-        std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
-        rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
-        rc = rl_render_light(ctx, &p, seeds.data(), seeds.size(), img.primal.data(), 0, nullptr, &last_stats);
-        rl_context_destroy(ctx);
-        if (rc != RL_OK) throw std::runtime_error(std::string("render: ") + rl_last_error());
-        return img;
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        check(rl_render_light(ctx, &p, seeds.data(), seeds.size(), ctx.img.primal.data(), 0, nullptr, &last_stats), "render");
+        return std::move(ctx.img);
     }
 };
 
@@ -289,6 +303,12 @@ struct IntegratorLightTracing {
 // the reference (the default).  PerPath: rl_vpl_generate_paths, one light path per lane on the stream of the k-th clone_box of the main sampler — statistically,
 // not seed-for-seed, the same image (`--light-streams per-path`).  The gather is the same either way.
 enum class LightStreams { Reference, PerPath };
+inline VplSetHandle generate_light_records(LightStreams streams, rl_context* ctx, const rl_path_params& p, uint32_t n, rl_vpl_option option, IndependentSampler& sampler,
+                                           rl_render_stats* stats, const char* who) {
+    rl_vpl_set* set = nullptr;
+    check((streams == LightStreams::PerPath ? rl_vpl_generate_paths : rl_vpl_generate)(ctx, &p, n, option, &sampler.rnd, &set, stats), who);
+    return VplSetHandle(set);
+}
 // struct IntegratorVPL (src/integrators/explicit/vpl.rs:16-23) + Integrator::compute, seed for seed the reference: the VPLs from the main sampler
 // (rl_vpl_generate), the block seeds from the sampler it leaves, the gather on reference-order streams (rl_render_vpl).  clamping_factor is not a
 // field: the reference never reads it.
@@ -298,17 +318,10 @@ struct IntegratorVPL {
     rl_vpl_option option_vpl = RL_VPL_ALL, option_lt = RL_VPL_ALL;
     LightStreams light_streams = LightStreams::Reference;
     int device = 0;
-    std::vector<std::pair<std::string, std::string>> options;
+    Options options;
     rl_render_stats last_stats{}, last_generation_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
-        rl_context* ctx = nullptr;
-        int rc = rl_context_create(scene.handle, device, &ctx);
-        if (rc != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
-        for (const auto& o : options)
-            if (rl_context_set_option(ctx, o.first.c_str(), o.second.c_str()) != RL_OK) { const std::string e = rl_last_error(); rl_context_destroy(ctx); throw std::runtime_error("--option " + o.first + ": " + e); }
-        BufferCollection img;
-        rl_scene_image_size(scene.handle, &img.width, &img.height);
-        img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
+        RenderContext ctx(scene, device, options);
         rl_path_params p;
         rl_path_params_default(&p);
         p.spp = (uint32_t)scene.nb_samples;
@@ -316,18 +329,10 @@ struct IntegratorVPL {
         p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
         p.stream_mode = RL_STREAM_REFERENCE_ORDER;
         p.seed_variant = sampler.variant;
-        rl_vpl_set* vpls = nullptr;
-        rc = (light_streams == LightStreams::PerPath ? rl_vpl_generate_paths : rl_vpl_generate)(ctx, &p, nb_vpl, option_vpl, &sampler.rnd, &vpls, &last_generation_stats);
-        if (rc == RL_OK) {
-            std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
-            rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
-            rc = rl_render_vpl(ctx, vpls, &p, option_lt, seeds.data(), seeds.size(), img.primal.data(), 0, nullptr, &last_stats);
-        }
-        const std::string err = rc == RL_OK ? std::string() : std::string(rl_last_error());
-        rl_vpl_destroy(vpls);
-        rl_context_destroy(ctx);
-        if (rc != RL_OK) throw std::runtime_error("vpl: " + err);
-        return img;
+        const VplSetHandle vpls = generate_light_records(light_streams, ctx, p, nb_vpl, option_vpl, sampler, &last_generation_stats, "vpl");
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        check(rl_render_vpl(ctx, vpls.get(), &p, option_lt, seeds.data(), seeds.size(), ctx.img.primal.data(), 0, nullptr, &last_stats), "vpl");
+        return std::move(ctx.img);
     }
 };
 
@@ -346,39 +351,24 @@ struct IntegratorVolPrimitives {
     LightStreams light_streams = LightStreams::Reference;
     TreeBuild tree_build = TreeBuild::Host;
     int device = 0;
-    std::vector<std::pair<std::string, std::string>> options;
+    Options options;
     rl_render_stats last_stats{}, last_generation_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
         if (primitives != VolPrimitivies::BRE) throw std::runtime_error("vol-primitives: only the beam radiance estimate (bre) is built");
-        rl_context* ctx = nullptr;
-        int rc = rl_context_create(scene.handle, device, &ctx);
-        if (rc != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
-        for (const auto& o : options)
-            if (rl_context_set_option(ctx, o.first.c_str(), o.second.c_str()) != RL_OK) { const std::string e = rl_last_error(); rl_context_destroy(ctx); throw std::runtime_error("--option " + o.first + ": " + e); }
-        BufferCollection img;
-        rl_scene_image_size(scene.handle, &img.width, &img.height);
-        img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
+        RenderContext ctx(scene, device, options);
         rl_path_params p;
         rl_path_params_default(&p);
         p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
         p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
         p.stream_mode = RL_STREAM_REFERENCE_ORDER;
         p.seed_variant = sampler.variant;
-        rl_vpl_set* photons = nullptr;
-        rl_photon_map* map = nullptr;
-        rc = (light_streams == LightStreams::PerPath ? rl_vpl_generate_paths : rl_vpl_generate)(ctx, &p, nb_primitive, RL_VPL_VOLUME, &sampler.rnd, &photons, &last_generation_stats);
-        if (rc == RL_OK) rc = tree_build == TreeBuild::Device ? rl_photon_map_build_device(ctx, photons, radius, &map, nullptr) : rl_photon_map_build(ctx, photons, radius, &map);
-        if (rc == RL_OK) {
-            std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
-            rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
-            rc = rl_render_bre(ctx, map, (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), img.primal.data(), &last_stats);
-        }
-        const std::string err = rc == RL_OK ? std::string() : std::string(rl_last_error());
-        rl_photon_map_destroy(map);
-        rl_vpl_destroy(photons);
-        rl_context_destroy(ctx);
-        if (rc != RL_OK) throw std::runtime_error("vol-primitives: " + err);
-        return img;
+        const VplSetHandle photons = generate_light_records(light_streams, ctx, p, nb_primitive, RL_VPL_VOLUME, sampler, &last_generation_stats, "vol-primitives");
+        rl_photon_map* built = nullptr;
+        check(tree_build == TreeBuild::Device ? rl_photon_map_build_device(ctx, photons.get(), radius, &built, nullptr) : rl_photon_map_build(ctx, photons.get(), radius, &built), "vol-primitives");
+        const PhotonMapHandle map(built);
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        check(rl_render_bre(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "vol-primitives");
+        return std::move(ctx.img);
     }
 };
 
@@ -389,32 +379,19 @@ struct IntegratorSinglePlane {
     uint32_t nb_primitive = 128;
     rl_plane_strategy strategy = RL_PLANE_STRATEGY_AVERAGE;
     int device = 0;
-    std::vector<std::pair<std::string, std::string>> options;
+    Options options;
     rl_render_stats last_stats{}, last_generation_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
-        rl_context* ctx = nullptr;
-        int rc = rl_context_create(scene.handle, device, &ctx);
-        if (rc != RL_OK) throw std::runtime_error(std::string("rl_context_create: ") + rl_last_error());
-        for (const auto& o : options)
-            if (rl_context_set_option(ctx, o.first.c_str(), o.second.c_str()) != RL_OK) { const std::string e = rl_last_error(); rl_context_destroy(ctx); throw std::runtime_error("--option " + o.first + ": " + e); }
-        BufferCollection img;
-        rl_scene_image_size(scene.handle, &img.width, &img.height);
-        img.primal.assign((size_t)3 * img.width * img.height, 0.0f);
-        rl_plane_set* planes = nullptr;
-        rl_plane_map* map = nullptr;
-        rc = rl_plane_generate(ctx, nb_primitive, strategy, &sampler.rnd, &planes, &last_generation_stats);
-        if (rc == RL_OK) rc = rl_plane_map_build(ctx, planes, &map);
-        if (rc == RL_OK) {
-            std::vector<uint64_t> seeds(rl_block_count(img.width, img.height));
-            rl_generate_block_seeds(&sampler.rnd, img.width, img.height, seeds.data(), seeds.size());
-            rc = rl_render_plane_single(ctx, map, (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), img.primal.data(), &last_stats);
-        }
-        const std::string err = rc == RL_OK ? std::string() : std::string(rl_last_error());
-        rl_plane_map_destroy(map);
-        rl_plane_destroy(planes);
-        rl_context_destroy(ctx);
-        if (rc != RL_OK) throw std::runtime_error("plane-single: " + err);
-        return img;
+        RenderContext ctx(scene, device, options);
+        rl_plane_set* generated = nullptr;
+        check(rl_plane_generate(ctx, nb_primitive, strategy, &sampler.rnd, &generated, &last_generation_stats), "plane-single");
+        const PlaneSetHandle planes(generated);
+        rl_plane_map* built = nullptr;
+        check(rl_plane_map_build(ctx, planes.get(), &built), "plane-single");
+        const PlaneMapHandle map(built);
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        check(rl_render_plane_single(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "plane-single");
+        return std::move(ctx.img);
     }
 };
 

@@ -276,30 +276,20 @@ extern "C" int rl_plane_generate(rl_context* ctx, uint32_t nb_primitive, int str
     const unsigned cap = nb_primitive + 2u;              // Average / DiscreteMIS store three planes per iteration
     HipBuffer<unsigned> d_words;
     HipBuffer<PlaneLight> d_lights;
-    HipBuffer<unsigned long long> d_gen;                 // [4] sampler, then [PLANE_GEN_WORDS] counters
-    if ((rcode = d_words.ensure((size_t)cap * RL_PLANE_WORDS)) != RL_OK || (rcode = d_lights.ensure(lights.size())) != RL_OK ||
-        (rcode = d_gen.ensure(4 + PLANE_GEN_WORDS)) != RL_OK) return rcode;
+    if ((rcode = d_words.ensure((size_t)cap * RL_PLANE_WORDS)) != RL_OK || (rcode = d_lights.ensure(lights.size())) != RL_OK) return rcode;
     const hipStream_t st = ctx->stream;
-    unsigned long long h_gen[4 + PLANE_GEN_WORDS] = {sampler->s[0], sampler->s[1], sampler->s[2], sampler->s[3]};
-    HIP_OK(hipMemcpyAsync(d_gen.get(), h_gen, sizeof(h_gen), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_lights.get(), lights.data(), lights.size() * sizeof(PlaneLight), hipMemcpyHostToDevice, st));
     PlaneGenConst gc{};
     gc.nb_primitive = nb_primitive; gc.cap = cap; gc.strategy = strategy;
     gc.n_lights = (unsigned)lights.size(); gc.lights = d_lights.get();
     for (int k = 0; k < 3; k++) { gc.sigma_t[k] = ctx->ds.medium.sigma_t[k]; gc.sigma_s[k] = ctx->ds.medium.sigma_s[k]; }
-    gc.words = d_words.get(); gc.gen_state = d_gen.get(); gc.gen_out = d_gen.get() + 4;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timing = stats != nullptr && !ctx->knobs.has(K_NO_EVENTS);
-    if (timing) { HIP_OK(hipEventCreate(&ev[0])); HIP_OK(hipEventCreate(&ev[1])); HIP_OK(hipEventRecord(ev[0], st)); }
-    const auto t0 = std::chrono::steady_clock::now();
-    launch_plane_generate(st, gc);
-    if (timing) HIP_OK(hipEventRecord(ev[1], st));
-    HIP_OK(hipMemcpyAsync(h_gen, d_gen.get(), sizeof(h_gen), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipGetLastError());
-    float ms = 0.0f;
-    if (timing) { (void)hipEventElapsedTime(&ms, ev[0], ev[1]); (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); (void)hipGetLastError(); }
-    const unsigned long long* g = h_gen + 4;
+    gc.words = d_words.get();
+    LaneRun run;
+    if ((rcode = run_one_lane(st, stats != nullptr && !ctx->knobs.has(K_NO_EVENTS), sampler, PLANE_GEN_WORDS, &run, [&](unsigned long long* d_gen) {
+            gc.gen_state = d_gen; gc.gen_out = d_gen + 4;
+            launch_plane_generate(st, gc);
+        })) != RL_OK) return rcode;
+    const unsigned long long* g = run.words.data() + 4;
     if (g[PLANE_GEN_PLANES] < nb_primitive || g[PLANE_GEN_PLANES] > cap) { rl_set_error("plane-single: the generation stored an unexpected number of planes"); return RL_ERR_HIP; }
     auto set = std::make_unique<rl_plane_set>();
     set->ctx = ctx;
@@ -307,12 +297,12 @@ extern "C" int rl_plane_generate(rl_context* ctx, uint32_t nb_primitive, int str
     set->words.resize((size_t)set->n_planes * RL_PLANE_WORDS);
     HIP_OK(hipMemcpy(set->words.data(), d_words.get(), set->words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if ((rcode = check_plane_records(set->words.data(), (size_t)set->n_planes)) != RL_OK) return rcode;
-    sampler->s[0] = h_gen[0]; sampler->s[1] = h_gen[1]; sampler->s[2] = h_gen[2]; sampler->s[3] = h_gen[3];
+    for (int i = 0; i < 4; i++) sampler->s[i] = run.words[i];
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->camera_samples = set->n_gen; stats->vertices = set->n_planes; stats->rng_draws = g[PLANE_GEN_DRAWS];
-        stats->iterations = 1; stats->kernel_launches = 1; stats->ms_prepass = ms;
-        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->iterations = 1; stats->kernel_launches = 1; stats->ms_prepass = run.ev.ms;
+        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - run.t0).count();
     }
     *out = set.release();
     return RL_OK;

@@ -21,20 +21,6 @@ void finish_roots(unsigned b, unsigned e, unsigned node, unsigned group, std::ve
     finish_roots(split, e, node + 1u, group, out);
     finish_roots(b, split, node + 1u + pt_node_count(m - m / 2u), group, out);
 }
-struct Events {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    bool on = false;
-    float ms = 0.0f;
-    int open(bool timing) {
-        on = timing;
-        if (on) { HIP_OK(hipEventCreate(&e[0])); HIP_OK(hipEventCreate(&e[1])); }
-        return RL_OK;
-    }
-    void begin(hipStream_t st) { if (on) (void)hipEventRecord(e[0], st); }
-    void end(hipStream_t st) { if (on) (void)hipEventRecord(e[1], st); }
-    void add() { float t = 0.0f; if (on && hipEventElapsedTime(&t, e[0], e[1]) == hipSuccess) ms += t; (void)hipGetLastError(); }      // after a synchronisation
-    ~Events() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); (void)hipGetLastError(); }
-};
 }  // namespace
 
 int photon_tree_run(const PhotonTreeJob& job, hipStream_t st, bool timing, float* ms_kernels) {
@@ -42,7 +28,7 @@ int photon_tree_run(const PhotonTreeJob& job, hipStream_t st, bool timing, float
     if (ms_kernels) *ms_kernels = 0.0f;
     if (n == 0) return RL_OK;
     const unsigned blocks = (n + kPtThreads - 1u) / kPtThreads;
-    Events ev;
+    EventPair ev;
     int rcode;
     if ((rcode = ev.open(timing)) != RL_OK) return rcode;
     // ---- check pass: the one word that comes back

@@ -789,6 +789,31 @@ struct RenderFrame {
     }
 };
 
+// The one-lane generation run of rl_vpl_generate and rl_plane_generate: the sampler's four words go up in front of n_counters zeroed words, launch(d_gen) — the
+// kernel reads and leaves its sampler in d_gen[0..4) and counts into d_gen[4..) — runs between the event pair, and the block comes back once the stream is idle.
+struct LaneRun {
+    std::vector<unsigned long long> words;               // [4] the sampler the lane left (the callers store it once every check has passed), then the counters
+    EventPair ev;                                        // ev.ms: the kernel, 0 without timing
+    std::chrono::steady_clock::time_point t0;            // just before the launch: the callers' render_ms counts from here
+};
+template <class Launch>
+int run_one_lane(hipStream_t st, bool timing, const rl_sampler* sampler, size_t n_counters, LaneRun* run, Launch&& launch) {
+    int rcode;
+    HipBuffer<unsigned long long> d_gen;
+    if ((rcode = d_gen.ensure(4 + n_counters)) != RL_OK || (rcode = run->ev.open(timing)) != RL_OK) return rcode;
+    run->words.assign(4 + n_counters, 0ull);
+    for (int i = 0; i < 4; i++) run->words[i] = sampler->s[i];
+    HIP_OK(hipMemcpyAsync(d_gen.get(), run->words.data(), run->words.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    run->ev.begin(st);
+    run->t0 = std::chrono::steady_clock::now();
+    launch(d_gen.get());
+    run->ev.end(st);
+    HIP_OK(hipMemcpyAsync(run->words.data(), d_gen.get(), run->words.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    run->ev.add();
+    return RL_OK;
+}
 }  // namespace
 
 #include "path_render.hip.h"
@@ -1018,16 +1043,11 @@ extern "C" int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, ui
                                rl_render_stats* stats) {
     int rcode;
     if ((rcode = check_vpl_generate(ctx, params, nb_vpl, option_vpl, sampler, out)) != RL_OK) return rcode;
-    const bool medium = ctx->ds.medium.enabled != 0;
     HIP_OK(hipSetDevice(ctx->device));
     auto set = std::make_unique<rl_vpl_set>();
     set->ctx = ctx; set->device = ctx->device;
     const unsigned cap = nb_vpl + kDepthCap + 1u;        // the last path adds at most one VPL per vertex
-    HipBuffer<unsigned long long> d_gen;                   // [4] sampler, then [VPL_GEN_WORDS] counters
-    if ((rcode = set->words.ensure((size_t)cap * RL_VPL_WORDS)) != RL_OK || (rcode = d_gen.ensure(4 + VPL_GEN_WORDS)) != RL_OK) return rcode;
-    const hipStream_t st = ctx->stream;
-    unsigned long long h_gen[4 + VPL_GEN_WORDS] = {sampler->s[0], sampler->s[1], sampler->s[2], sampler->s[3]};
-    HIP_OK(hipMemcpyAsync(d_gen.get(), h_gen, sizeof(h_gen), hipMemcpyHostToDevice, st));
+    if ((rcode = set->words.ensure((size_t)cap * RL_VPL_WORDS)) != RL_OK) return rcode;
     RenderConst rc{};
     rc.has_max = params->has_max_depth; rc.max_depth = params->max_depth;
     rc.has_rr = params->has_rr_depth; rc.rr_depth = params->rr_depth;
@@ -1035,30 +1055,23 @@ extern "C" int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, ui
     vc.nb_vpl = nb_vpl; vc.cap = cap; vc.max_paths = RL_VPL_MAX_PATHS;
     vc.option_vpl = option_vpl;
     vc.vpl_words = set->words.get();
-    vc.gen_state = d_gen.get(); vc.gen_out = d_gen.get() + 4;
     StackConf stc;
     if ((rcode = stack_conf(ctx, 256, &stc)) != RL_OK) return rcode;
     const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timing = stats != nullptr;
-    if (timing) { HIP_OK(hipEventCreate(&ev[0])); HIP_OK(hipEventCreate(&ev[1])); HIP_OK(hipEventRecord(ev[0], st)); }
-    const auto t0 = std::chrono::steady_clock::now();
-    (ctx->lds_scene ? launch_vpl_lds : launch_vpl_stream)(0, ctx->single_bsdf ? ctx->bsdf_type : -1, medium, dim3(1), dim3(256), lds, st, rc, ctx->ds, stc, vc);
-    if (timing) HIP_OK(hipEventRecord(ev[1], st));
-    HIP_OK(hipMemcpyAsync(h_gen, d_gen.get(), sizeof(h_gen), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipGetLastError());
-    float ms = 0.0f;
-    if (timing) { (void)hipEventElapsedTime(&ms, ev[0], ev[1]); (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); (void)hipGetLastError(); }
-    const unsigned long long* g = h_gen + 4;
+    LaneRun run;
+    if ((rcode = run_one_lane(ctx->stream, stats != nullptr && !ctx->knobs.has(K_NO_EVENTS), sampler, VPL_GEN_WORDS, &run, [&](unsigned long long* d_gen) {
+            vc.gen_state = d_gen; vc.gen_out = d_gen + 4;
+            (ctx->lds_scene ? launch_vpl_lds : launch_vpl_stream)(0, ctx->single_bsdf ? ctx->bsdf_type : -1, ctx->ds.medium.enabled != 0, dim3(1), dim3(256), lds, ctx->stream, rc, ctx->ds, stc, vc);
+        })) != RL_OK) return rcode;
+    const unsigned long long* g = run.words.data() + 4;
     if (g[VPL_GEN_VPLS] < nb_vpl) { rl_set_error("vpl: fewer than nb_vpl VPLs stored within RL_VPL_MAX_PATHS light paths"); return RL_ERR_UNSUPPORTED; }
-    sampler->s[0] = h_gen[0]; sampler->s[1] = h_gen[1]; sampler->s[2] = h_gen[2]; sampler->s[3] = h_gen[3];
+    for (int i = 0; i < 4; i++) sampler->s[i] = run.words[i];
     set->n_vpl = g[VPL_GEN_VPLS]; set->n_paths = g[VPL_GEN_PATHS];
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->camera_samples = g[VPL_GEN_PATHS]; stats->vertices = g[VPL_GEN_VERTICES]; stats->extension_rays = g[VPL_GEN_EXT]; stats->rng_draws = g[VPL_GEN_DRAWS];
-        stats->iterations = 1; stats->kernel_launches = 1; stats->ms_prepass = ms;
-        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->iterations = 1; stats->kernel_launches = 1; stats->ms_prepass = run.ev.ms;
+        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - run.t0).count();
     }
     *out = set.release();
     return RL_OK;
@@ -1090,12 +1103,9 @@ extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* para
     const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
     const int mat = ctx->single_bsdf ? ctx->bsdf_type : -1;
     const auto launch = ctx->lds_scene ? launch_vpl_paths_lds : launch_vpl_paths_stream;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timing = stats != nullptr;
-    if (timing) { HIP_OK(hipEventCreate(&ev[0])); HIP_OK(hipEventCreate(&ev[1])); }
-    struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); (void)hipGetLastError(); } } guard{ev};
+    EventPair ev;
+    if ((rcode = ev.open(stats != nullptr && !ctx->knobs.has(K_NO_EVENTS))) != RL_OK) return rcode;
     const auto t0 = std::chrono::steady_clock::now();
-    float ms_kernels = 0.0f;
     unsigned launches = 0, rounds = 0;
     // one launch over paths first .. first + count - 1: persistent workgroups stride over the batch
     auto shoot = [&](bool write, unsigned first, unsigned count) -> int {
@@ -1104,13 +1114,12 @@ extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* para
         int r = stack_conf(ctx, (size_t)groups * 256, &stc);
         if (r != RL_OK) return r;
         pc.first = first; pc.count = count;
-        if (timing) HIP_OK(hipEventRecord(ev[0], st));
+        ev.begin(st);
         launch(write, mat, medium, dim3(groups), dim3(256), lds, st, rc, ctx->ds, stc, pc);
-        if (timing) HIP_OK(hipEventRecord(ev[1], st));
+        ev.end(st);
         launches++;
         return RL_OK;
     };
-    auto add_kernel_time = [&]() { float ms = 0.0f; if (timing && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ms_kernels += ms; (void)hipGetLastError(); };
     // ---- count rounds
     HipBuffer<unsigned> d_counts;
     std::vector<unsigned> counts;                    // [path][VPL_PATH_WORDS], every path walked so far
@@ -1134,7 +1143,7 @@ extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* para
         HIP_OK(hipMemcpyAsync(counts.data() + (size_t)walked * VPL_PATH_WORDS, d_counts.get(), (size_t)batch * VPL_PATH_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         HIP_OK(hipGetLastError());
-        add_kernel_time();
+        ev.add();
         rounds++;
         for (unsigned k = walked; k < walked + batch && K == 0; k++) {            // the cut: `while stored < nb` on this path sequence
             offsets.push_back((unsigned)stored);
@@ -1152,7 +1161,7 @@ extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* para
     if ((rcode = shoot(true, 0u, K)) != RL_OK) return rcode;
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
-    add_kernel_time();
+    ev.add();
     for (unsigned k = 0; k < K; k++) (void)rl_sampler_next_u64(sampler);           // the K clone_box calls
     set->n_vpl = stored; set->n_paths = K;
     if (stats) {
@@ -1162,7 +1171,7 @@ extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* para
             const unsigned* c = &counts[(size_t)k * VPL_PATH_WORDS];
             stats->vertices += c[VPL_PATH_VERTICES]; stats->extension_rays += c[VPL_PATH_EXT]; stats->rng_draws += c[VPL_PATH_DRAWS];
         }
-        stats->iterations = rounds; stats->kernel_launches = launches; stats->ms_prepass = ms_kernels;
+        stats->iterations = rounds; stats->kernel_launches = launches; stats->ms_prepass = ev.ms;
         stats->reserved[0] = walked;
         stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }

@@ -52,3 +52,27 @@ def test_interleaved_render_kinds_match_fresh_contexts(built):
         if kind == "light":
             assert st["splats"] > 0, what
     shared.close()
+
+
+# ---- generation under the `no_events` option: the three entry points time their kernels unless the context says not to, and the option changes nothing else
+def _generate(ctx, case):
+    sampler = api.IndependentSampler(3)
+    if case == "plane":
+        made, st = ctx.plane_generate(sampler, 64, "average")
+    else:
+        made, st = ctx.vpl_generate(sampler, nb_vpl=300, option_vpl=api.VPL_VOLUME, streams=case)
+    return made.words(), made.info(), tuple(int(w) for w in sampler.s.s), st
+
+
+@pytest.mark.parametrize("case", ["reference", "per_path", "plane"])
+def test_generation_obeys_no_events(built, case):
+    ctx = api.Context(api.Scene(scenes.cbox_medium(32, 24, 1.0)), 0)
+    words, info, state, st = _generate(ctx, case)
+    assert st["ms_prepass"] > 0, st
+    with ctx.options(no_events=1):
+        words_off, info_off, state_off, st_off = _generate(ctx, case)
+    assert st_off["ms_prepass"] == 0.0, st_off
+    np.testing.assert_array_equal(words_off, words)
+    assert info_off == info and state_off == state
+    assert state != tuple(int(w) for w in api.IndependentSampler(3).s.s)      # (the call did advance the sampler)
+    ctx.close()
