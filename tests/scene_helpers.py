@@ -36,6 +36,13 @@ def add_second_light(sd):
     return sd
 
 
+def black_walls(sd):
+    """Every surface black (the lights' own BSDF is black already): no light path and no camera path continues past a surface."""
+    for m in sd.meshes:
+        m.bsdf = scenes.matte((0.0, 0.0, 0.0))
+    return sd
+
+
 def two_lights(w, h):
     """The box with its medium plus the second emissive quad of add_second_light."""
     return add_second_light(scenes.cbox_medium(w, h, 1.0))
