@@ -488,11 +488,24 @@ int rl_photon_map_read(const rl_photon_map* map, size_t node_capacity, float* no
  * three planes re-made through the point; CMIS: its closed-form weight).  rho is the isotropic phase function whatever the medium's is: the reference
  * hard-codes it.  Samples are added in order and scaled by 1 / spp.  Reference-order streams, exact numerics, one device, host output; shards, spp limit and
  * their codes as rl_render_bre.  Counters: camera_samples, extension_rays = camera_samples, shadow_rays = planes intersected, rng_draws = 2 * camera_samples,
- * kernel_launches, ms_other = the gather kernel; reserved[0] = plane-tree nodes entered, reserved[1] = planes intersected, reserved[2] = of those, visible. */
+ * kernel_launches, ms_other = the gather kernel; reserved[0] = plane-tree nodes entered, reserved[1] = planes intersected, reserved[2] = of those, visible.
+ * The device forms (opt-in; each is byte for byte the form above, so the options plane_generate_lanes / plane_tree_device = 1 make rl_plane_generate /
+ * rl_plane_map_build forward to them):
+ * rl_plane_generate_lanes: rl_plane_generate's arguments, refusals, set, sampler state and counters, one device lane per iteration of the loop.  An
+ * iteration takes D = 1 + 6 k draws (k = 3 planes for AVERAGE / DISCRETE_MIS, else 1) unless a direction is drawn again, so lane i starts D i draws down
+ * the main sampler's stream (jump-ahead); a lane that meets such a redraw raises a flag, and the call then runs rl_plane_generate's serial kernel from the
+ * original state instead.  The set keeps its records on the device as well: rl_plane_map_build_device uploads nothing, rl_plane_read and the host build
+ * download them on first use.
+ * rl_plane_map_build_device: rl_plane_map_build's map — nodes, planes, lights, counts, strategy — built by the kernels of kernels/phototree.hip.h over the
+ * plane element: a prepass takes every plane's box and keys with the host's separately rounded operations, the levels sort as for photons, a last kernel
+ * writes the planes in leaf order.  A set made by rl_plane_generate is uploaded once.  ms_kernels as for rl_photon_map_build_device.  Ranges of at most
+ * RL_PLANE_TREE_GROUP_PLANES planes are finished by one workgroup in LDS; the option plane_tree_group_planes = n forces a smaller group (tests).
+ * rl_plane_tree_build_device: rl_plane_tree_build's contract (codes, size-only call, refusals) computed by the same kernels, with
+ * rl_photon_tree_build_device's calling convention. */
 typedef enum rl_plane_type { RL_PLANE_UV = 0, RL_PLANE_VT = 1, RL_PLANE_UT = 2, RL_PLANE_UALPHAT = 3 } rl_plane_type;
 typedef enum rl_plane_strategy { RL_PLANE_STRATEGY_UV = 0, RL_PLANE_STRATEGY_VT = 1, RL_PLANE_STRATEGY_UT = 2, RL_PLANE_STRATEGY_AVERAGE = 3,
                                  RL_PLANE_STRATEGY_DISCRETE_MIS = 4, RL_PLANE_STRATEGY_UALPHA = 5, RL_PLANE_STRATEGY_CMIS = 6 } rl_plane_strategy;
-enum { RL_PLANE_WORDS = 18 };
+enum { RL_PLANE_WORDS = 18, RL_PLANE_TREE_GROUP_PLANES = 1024 };
 typedef struct rl_plane_set rl_plane_set;       /* opaque: the planes of one generation */
 typedef struct rl_plane_map rl_plane_map;       /* opaque: plane tree, planes and lights, on the context's device */
 int rl_plane_generate(rl_context* ctx, uint32_t nb_primitive, int strategy, rl_sampler* sampler, rl_plane_set** out, rl_render_stats* stats);
@@ -504,6 +517,10 @@ int rl_plane_map_build(rl_context* ctx, const rl_plane_set* set, rl_plane_map** 
 int rl_plane_map_info(const rl_plane_map* map, uint64_t* n_planes, uint64_t* n_nodes, uint64_t* number_plane_gen, int* strategy);
 int rl_plane_map_read(const rl_plane_map* map, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t plane_capacity, float* planes);
 void rl_plane_map_destroy(rl_plane_map* map);
+int rl_plane_generate_lanes(rl_context* ctx, uint32_t nb_primitive, int strategy, rl_sampler* sampler, rl_plane_set** out, rl_render_stats* stats);
+int rl_plane_map_build_device(rl_context* ctx, const rl_plane_set* set, rl_plane_map** out, float* ms_kernels);
+int rl_plane_tree_build_device(rl_context* ctx, const uint32_t* words, size_t n_planes, size_t node_capacity, size_t* n_nodes, float* node_boxes,
+                               uint32_t* node_links, uint32_t* order);
 int rl_render_plane_single(rl_context* ctx, const rl_plane_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
                            const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
 

@@ -34,6 +34,8 @@ VPL_WORDS = 24                                            # RL_VPL_WORDS: u32 pe
 TREE_BUILDS = ("host", "device")                          # where the photon tree of vol-primitivies is built: rl_photon_map_build | rl_photon_map_build_device
 PHOTON_TREE_GROUP_PHOTONS = 2048                          # RL_PHOTON_TREE_GROUP_PHOTONS: photons one workgroup of the device build finishes in LDS
 PHOTON_RADIUS_DEFAULT = 0.001                             # RL_PHOTON_RADIUS_DEFAULT: the radius the reference hard-codes (vol_primitives.rs:618)
+PLANE_FORMS = ("serial", "lanes")                         # how the plane pass of plane-single runs: rl_plane_generate | rl_plane_generate_lanes
+PLANE_TREE_GROUP_PLANES = 1024                            # RL_PLANE_TREE_GROUP_PLANES: planes one workgroup of the device build finishes in LDS
 PLANE_WORDS = 18                                          # RL_PLANE_WORDS: u32 per plane record (rl_plane_read)
 PLANE_UV, PLANE_VT, PLANE_UT, PLANE_UALPHAT = 0, 1, 2, 3  # rl_plane_type
 PLANE_STRATEGIES = ("uv", "vt", "ut", "average", "discrete_mis", "ualpha", "cmis")      # rl_plane_strategy, by value: `plane-single -s`
@@ -46,7 +48,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_render_plane_single", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -139,6 +141,9 @@ def lib():
     L.rl_plane_destroy.restype = None
     L.rl_plane_tree_build.argtypes = [u32p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), f32p, u32p, u32p]
     L.rl_plane_map_build.argtypes = [vp, vp, C.POINTER(vp)]
+    L.rl_plane_generate_lanes.argtypes = L.rl_plane_generate.argtypes
+    L.rl_plane_map_build_device.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_float)]
+    L.rl_plane_tree_build_device.argtypes = [vp, u32p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), f32p, u32p, u32p]
     L.rl_plane_map_info.argtypes = [vp, u64p, u64p, u64p, C.POINTER(C.c_int)]
     L.rl_plane_map_read.argtypes = [vp, C.c_size_t, f32p, u32p, C.c_size_t, f32p]
     L.rl_plane_map_destroy.argtypes = [vp]
@@ -572,22 +577,39 @@ class Context(_ImageCalls):
         photons_gathered = reserved[0] / reserved[1], ms_other = the gather kernel."""
         return self._render_gather(lib().rl_render_bre, photons.h, seeds, spp, seed_variant, shard_index, shard_count, ("nodes_entered", "photons_gathered"))
 
-    def plane_generate(self, sampler: "IndependentSampler", nb_primitive=128, strategy="average"):
+    def plane_generate(self, sampler: "IndependentSampler", nb_primitive=128, strategy="average", form="serial"):
         """IntegratorSinglePlane's plane pass (plane_single.rs:363-427) through rl_plane_generate: (PlaneSet, stats dict).  `sampler` is advanced as the
-        reference's main sampler is.  stats: camera_samples = iterations (number_plane_gen), vertices = planes, rng_draws, ms_prepass = the kernel."""
+        reference's main sampler is.  stats: camera_samples = iterations (number_plane_gen), vertices = planes, rng_draws, ms_prepass = the kernel.
+        form="lanes": rl_plane_generate_lanes, one lane per iteration, the same set, sampler and counters; its records stay on the device."""
+        if form not in PLANE_FORMS:
+            raise ValueError(f"form must be one of {PLANE_FORMS}, not {form!r}")
         st = abi.RenderStats()
         h = C.c_void_p()
-        _check(lib().rl_plane_generate(self.h, nb_primitive, plane_strategy(strategy), C.byref(sampler.s), C.byref(h), C.byref(st)))
+        fn = lib().rl_plane_generate_lanes if form == "lanes" else lib().rl_plane_generate
+        _check(fn(self.h, nb_primitive, plane_strategy(strategy), C.byref(sampler.s), C.byref(h), C.byref(st)))
         return PlaneSet(h, self), st.as_dict()
 
-    def plane_map(self, planes: "PlaneSet"):
-        """rl_plane_map_build: the plane tree over a generated set, built on the host and uploaded.  PlaneMap.ms_build: wall clock of the call, ms."""
+    def plane_map(self, planes: "PlaneSet", build="host"):
+        """rl_plane_map_build: the plane tree over a generated set, built on the host and uploaded.  build="device": rl_plane_map_build_device, the same map
+        byte for byte from device kernels.  PlaneMap.ms_build: wall clock of the call, ms; PlaneMap.ms_kernels: the device build's kernel time (None: host)."""
+        if build not in TREE_BUILDS:
+            raise ValueError(f"build must be one of {TREE_BUILDS}, not {build!r}")
         h = C.c_void_p()
+        ms = C.c_float(0.0)
         t0 = time.perf_counter()
-        _check(lib().rl_plane_map_build(self.h, planes.h, C.byref(h)))
+        if build == "device":
+            _check(lib().rl_plane_map_build_device(self.h, planes.h, C.byref(h), C.byref(ms)))
+        else:
+            _check(lib().rl_plane_map_build(self.h, planes.h, C.byref(h)))
         m = PlaneMap(h, self)
         m.ms_build = (time.perf_counter() - t0) * 1e3
+        m.ms_kernels = float(ms.value) if build == "device" else None
         return m
+
+    def plane_tree_build_device(self, words):
+        """rl_plane_tree_build_device: plane_tree_build's arrays, computed by the kernels of the device build on this context's device."""
+        w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, PLANE_WORDS)
+        return _tree_arrays(lambda *out: lib().rl_plane_tree_build_device(self.h, abi.u32ptr(w), w.shape[0], *out), w.shape[0])
 
     def render_plane_single(self, planes: "PlaneMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
         """IntegratorSinglePlane's gather (plane_single.rs:436-611) through rl_render_plane_single: (image HxWx3 f32, stats dict).  stats: nodes_entered /
@@ -957,6 +979,7 @@ class PlaneMap(_DeviceHandle):
     def __init__(self, h, ctx: Context):
         super().__init__(h, ctx)
         self.ms_build = None        # Context.plane_map: wall clock of the build call, ms
+        self.ms_kernels = None      # build="device": HIP-event time of its launches, ms
 
     def info(self):
         """(planes, tree nodes, number_plane_gen, strategy name)."""
@@ -981,19 +1004,25 @@ def plane_tree_build(words):
 
 class IntegratorSinglePlane(_Integrator):
     """struct IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs:291-294) + Integrator::compute, seed for seed the
-    reference: the planes from the main sampler, the plane tree, the block seeds from the sampler the generation leaves, the gather on reference-order streams."""
+    reference: the planes from the main sampler, the plane tree, the block seeds from the sampler the generation leaves, the gather on reference-order streams.
+    generate="lanes" / tree_build="device": the plane pass on one lane per iteration and the tree from device kernels, byte for byte the same planes and map."""
 
-    def __init__(self, nb_primitive=128, strategy="average", device=0, options=None):
+    def __init__(self, nb_primitive=128, strategy="average", device=0, options=None, generate="serial", tree_build="host"):
         super().__init__(device, options)
+        if generate not in PLANE_FORMS:
+            raise ValueError(f"generate must be one of {PLANE_FORMS}, not {generate!r}")
+        if tree_build not in TREE_BUILDS:
+            raise ValueError(f"tree_build must be one of {TREE_BUILDS}, not {tree_build!r}")
+        self.generate, self.tree_build = generate, tree_build
         self.nb_primitive, self.strategy = nb_primitive, PLANE_STRATEGIES[plane_strategy(strategy)]
         self.last_generation_stats = None
 
     def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
         ctx = self._context(scene)
-        planes, self.last_generation_stats = ctx.plane_generate(sampler, self.nb_primitive, self.strategy)
+        planes, self.last_generation_stats = ctx.plane_generate(sampler, self.nb_primitive, self.strategy, self.generate)
         pmap = None
         try:
-            pmap = ctx.plane_map(planes)
+            pmap = ctx.plane_map(planes, self.tree_build)
             w, h = scene.size
             seeds = sampler.block_seeds(w, h)
             img, self.last_stats = ctx.render_plane_single(pmap, seeds, nb_samples, sampler.variant)

@@ -374,16 +374,23 @@ struct IntegratorVolPrimitives {
 
 // struct IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs:280-294) + Integrator::compute, seed for seed the reference:
 // the planes from the main sampler (rl_plane_generate), the plane tree (rl_plane_map_build), the block seeds from the sampler the generation leaves, the
-// gather on reference-order streams (rl_render_plane_single).
+// gather on reference-order streams (rl_render_plane_single).  generate = Lanes and tree_build = Device set the context options plane_generate_lanes and
+// plane_tree_device, under which the two calls forward to rl_plane_generate_lanes (one lane per iteration) and rl_plane_map_build_device (the tree from
+// device kernels): the same planes and the same map, byte for byte.
+enum class PlaneGenerate { Serial, Lanes };
 struct IntegratorSinglePlane {
     uint32_t nb_primitive = 128;
     rl_plane_strategy strategy = RL_PLANE_STRATEGY_AVERAGE;
+    PlaneGenerate generate{PlaneGenerate::Serial};
+    TreeBuild tree_build{TreeBuild::Host};
     int device = 0;
     Options options;
     rl_render_stats last_stats{}, last_generation_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
         RenderContext ctx(scene, device, options);
         rl_plane_set* generated = nullptr;
+        if (generate == PlaneGenerate::Lanes) check(rl_context_set_option(ctx, "plane_generate_lanes", "1"), "plane-single");
+        if (tree_build == TreeBuild::Device) check(rl_context_set_option(ctx, "plane_tree_device", "1"), "plane-single");
         check(rl_plane_generate(ctx, nb_primitive, strategy, &sampler.rnd, &generated, &last_generation_stats), "plane-single");
         const PlaneSetHandle planes(generated);
         rl_plane_map* built = nullptr;

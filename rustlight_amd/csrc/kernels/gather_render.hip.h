@@ -232,12 +232,25 @@ extern "C" int rl_render_bre(rl_context* ctx, const rl_photon_map* map, uint32_t
 
 // ---- IntegratorSinglePlane (plane_single.rs): rl_plane_generate makes the planes on one lane (k_plane_generate, plane_generate.hip) and brings them to the
 // host, rl_plane_map_build sorts them into the plane tree there (host/planetree.cpp) and uploads tree, planes and lights, rl_render_plane_single gathers them
-// along every camera ray (k_plane_gather, plane.hip.h)
+// along every camera ray (k_plane_gather, plane.hip.h).  The device forms give the same bytes: rl_plane_generate_lanes (k_plane_generate_lanes, one lane per
+// iteration) leaves the records on the device, rl_plane_map_build_device builds the tree there (kernels/planetree.hip).
 struct rl_plane_set {
     const rl_context* ctx;            // the context that made it (compared, never dereferenced)
-    std::vector<uint32_t> words;      // [n_planes][RL_PLANE_WORDS]
+    int device = 0;
+    // [n_planes][RL_PLANE_WORDS]: on the host (rl_plane_generate), or on the device (rl_plane_generate_lanes) and on the host once something has asked for them
+    mutable std::vector<uint32_t> words;
+    HipBuffer<unsigned> d_words;
+    bool on_device = false;
     uint64_t n_planes = 0, n_gen = 0;
     int strategy = 0;
+    int host_words() const {
+        if (!on_device || !words.empty() || n_planes == 0) return RL_OK;
+        HIP_OK(hipSetDevice(device));
+        std::vector<uint32_t> w((size_t)n_planes * RL_PLANE_WORDS);
+        HIP_OK(hipMemcpy(w.data(), d_words.get(), w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        words.swap(w);
+        return RL_OK;
+    }
 };
 struct rl_plane_map {
     const rl_context* ctx;
@@ -248,6 +261,7 @@ struct rl_plane_map {
     uint64_t n_planes = 0, n_nodes = 0, n_gen = 0, n_lights = 0;
     int strategy = 0;
 };
+static int plane_generate_serial(rl_context* ctx, uint32_t nb_primitive, int strategy, rl_sampler* sampler, rl_plane_set** out, rl_render_stats* stats);
 // what every plane entry point refuses before any kernel runs
 static int check_plane_scene(const rl_context* ctx) {
     if (ctx->ds.medium.enabled == 0) { rl_set_error("plane-single needs a medium (add -m; the reference panics, plane_single.rs:303)"); return RL_ERR_UNSUPPORTED; }
@@ -264,7 +278,12 @@ static std::vector<PlaneLight> plane_lights(const rl_context* ctx) {
     }
     return out;
 }
+static bool knob_on(const rl_context* ctx, int k) { return ctx->knobs.i(k, 0) != 0; }
 extern "C" int rl_plane_generate(rl_context* ctx, uint32_t nb_primitive, int strategy, rl_sampler* sampler, rl_plane_set** out, rl_render_stats* stats) {
+    if (ctx && knob_on(ctx, K_PLANE_GENERATE_LANES)) return rl_plane_generate_lanes(ctx, nb_primitive, strategy, sampler, out, stats);
+    return plane_generate_serial(ctx, nb_primitive, strategy, sampler, out, stats);
+}
+static int plane_generate_serial(rl_context* ctx, uint32_t nb_primitive, int strategy, rl_sampler* sampler, rl_plane_set** out, rl_render_stats* stats) {
     if (!ctx || !sampler || !out) return RL_ERR_INVALID_ARGUMENT;
     *out = nullptr;
     if (strategy < RL_PLANE_STRATEGY_UV || strategy > RL_PLANE_STRATEGY_CMIS) { rl_set_error("strategy must be one of RL_PLANE_STRATEGY_*"); return RL_ERR_INVALID_ARGUMENT; }
@@ -292,7 +311,7 @@ extern "C" int rl_plane_generate(rl_context* ctx, uint32_t nb_primitive, int str
     const unsigned long long* g = run.words.data() + 4;
     if (g[PLANE_GEN_PLANES] < nb_primitive || g[PLANE_GEN_PLANES] > cap) { rl_set_error("plane-single: the generation stored an unexpected number of planes"); return RL_ERR_HIP; }
     auto set = std::make_unique<rl_plane_set>();
-    set->ctx = ctx;
+    set->ctx = ctx; set->device = ctx->device;
     set->n_planes = g[PLANE_GEN_PLANES]; set->n_gen = g[PLANE_GEN_ITERATIONS]; set->strategy = strategy;
     set->words.resize((size_t)set->n_planes * RL_PLANE_WORDS);
     HIP_OK(hipMemcpy(set->words.data(), d_words.get(), set->words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -307,6 +326,49 @@ extern "C" int rl_plane_generate(rl_context* ctx, uint32_t nb_primitive, int str
     *out = set.release();
     return RL_OK;
 }
+// One lane per iteration (k_plane_generate_lanes): the serial call's checks, then the lanes; a redraw anywhere hands the whole call to the serial kernel
+extern "C" int rl_plane_generate_lanes(rl_context* ctx, uint32_t nb_primitive, int strategy, rl_sampler* sampler, rl_plane_set** out, rl_render_stats* stats) {
+    if (!ctx || !sampler || !out) return RL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (strategy < RL_PLANE_STRATEGY_UV || strategy > RL_PLANE_STRATEGY_CMIS) { rl_set_error("strategy must be one of RL_PLANE_STRATEGY_*"); return RL_ERR_INVALID_ARGUMENT; }
+    if (nb_primitive == 0 || nb_primitive > (uint32_t)RL_VPL_MAX) { rl_set_error("nb_primitive must be 1 .. RL_VPL_MAX"); return RL_ERR_INVALID_ARGUMENT; }
+    int rcode;
+    if ((rcode = check_plane_scene(ctx)) != RL_OK) return rcode;
+    HIP_OK(hipSetDevice(ctx->device));
+    const std::vector<PlaneLight> lights = plane_lights(ctx);
+    const unsigned per = (strategy == RL_PLANE_STRATEGY_AVERAGE || strategy == RL_PLANE_STRATEGY_DISCRETE_MIS) ? 3u : 1u, draws = 1u + 6u * per;
+    const unsigned n_gen = (nb_primitive + per - 1u) / per, n_planes = n_gen * per;      // n_gen * draws < 2^32: rng_advance's range
+    auto set = std::make_unique<rl_plane_set>();
+    set->ctx = ctx; set->device = ctx->device;
+    HipBuffer<PlaneLight> d_lights;
+    if ((rcode = set->d_words.ensure((size_t)n_planes * RL_PLANE_WORDS)) != RL_OK || (rcode = d_lights.ensure(lights.size())) != RL_OK) return rcode;
+    const hipStream_t st = ctx->stream;
+    HIP_OK(hipMemcpyAsync(d_lights.get(), lights.data(), lights.size() * sizeof(PlaneLight), hipMemcpyHostToDevice, st));
+    PlaneGenConst gc{};
+    gc.nb_primitive = nb_primitive; gc.cap = n_planes; gc.strategy = strategy;
+    gc.n_lights = (unsigned)lights.size(); gc.lights = d_lights.get();
+    for (int k = 0; k < 3; k++) { gc.sigma_t[k] = ctx->ds.medium.sigma_t[k]; gc.sigma_s[k] = ctx->ds.medium.sigma_s[k]; }
+    gc.words = set->d_words.get();
+    LaneRun run;
+    if ((rcode = run_one_lane(st, stats != nullptr && !ctx->knobs.has(K_NO_EVENTS), sampler, PLANE_LANES_WORDS, &run, [&](unsigned long long* d_gen) {
+            gc.gen_state = d_gen; gc.gen_out = d_gen + 4;
+            launch_plane_generate_lanes(st, gc, n_gen);
+        })) != RL_OK) return rcode;
+    const unsigned long long flag = run.words[4 + PLANE_LANES_FLAG];
+    if (flag & 1u) return plane_generate_serial(ctx, nb_primitive, strategy, sampler, out, stats);      // a direction was drawn again: the stream is the serial walk's alone
+    if (flag & 2u) { rl_set_error("a plane corner is not finite"); return RL_ERR_INVALID_ARGUMENT; }
+    set->on_device = true;
+    set->n_planes = n_planes; set->n_gen = n_gen; set->strategy = strategy;
+    for (int i = 0; i < 4; i++) sampler->s[i] = run.words[4 + i];
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->camera_samples = n_gen; stats->vertices = n_planes; stats->rng_draws = (uint64_t)n_gen * draws;
+        stats->iterations = 1; stats->kernel_launches = 1; stats->ms_prepass = run.ev.ms;
+        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - run.t0).count();
+    }
+    *out = set.release();
+    return RL_OK;
+}
 extern "C" int rl_plane_info(const rl_plane_set* set, uint64_t* n_planes, uint64_t* number_plane_gen, int* strategy) {
     if (!set) return RL_ERR_INVALID_ARGUMENT;
     if (n_planes) *n_planes = set->n_planes;
@@ -315,17 +377,25 @@ extern "C" int rl_plane_info(const rl_plane_set* set, uint64_t* n_planes, uint64
     return RL_OK;
 }
 extern "C" int rl_plane_read(const rl_plane_set* set, uint32_t* words, size_t n_words) {
-    if (!set || !words || n_words != set->words.size()) return RL_ERR_INVALID_ARGUMENT;
+    if (!set || !words || n_words != (size_t)set->n_planes * RL_PLANE_WORDS) return RL_ERR_INVALID_ARGUMENT;
+    const int rcode = set->host_words();
+    if (rcode != RL_OK) return rcode;
     std::copy(set->words.begin(), set->words.end(), words);
     return RL_OK;
 }
-extern "C" void rl_plane_destroy(rl_plane_set* set) { delete set; }
+extern "C" void rl_plane_destroy(rl_plane_set* set) {
+    if (!set) return;
+    if (set->on_device) (void)hipSetDevice(set->device);
+    delete set;
+}
 extern "C" int rl_plane_map_build(rl_context* ctx, const rl_plane_set* set, rl_plane_map** out) {
+    if (ctx && knob_on(ctx, K_PLANE_TREE_DEVICE)) return rl_plane_map_build_device(ctx, set, out, nullptr);
     if (!ctx || !set || !out) return RL_ERR_INVALID_ARGUMENT;
     *out = nullptr;
     int rcode;
     if ((rcode = check_plane_scene(ctx)) != RL_OK) return rcode;
     if (set->ctx != ctx) { rl_set_error("the plane set belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
+    if ((rcode = set->host_words()) != RL_OK) return rcode;
     ElementTree tree;
     if ((rcode = build_plane_tree(set->words.data(), (size_t)set->n_planes, &tree)) != RL_OK) return rcode;
     const size_t n_nodes = tree.n_nodes(), n_planes = (size_t)set->n_planes;
@@ -353,6 +423,71 @@ extern "C" int rl_plane_map_build(rl_context* ctx, const rl_plane_set* set, rl_p
     HIP_OK(hipMemcpy(map->lights.get(), lights.data(), lights.size() * sizeof(PlaneLight), hipMemcpyHostToDevice));
     map->n_planes = n_planes; map->n_nodes = n_nodes; map->n_gen = set->n_gen; map->n_lights = lights.size(); map->strategy = set->strategy;
     *out = map.release();
+    return RL_OK;
+}
+// The device build (kernels/planetree.hip): the same map from kernels alone.  plane_tree_run's prepass stands for check_plane_records.
+static unsigned plane_tree_group(const rl_context* ctx) {
+    if (!ctx->knobs.has(K_PLANE_TREE_GROUP_PLANES)) return (unsigned)RL_PLANE_TREE_GROUP_PLANES;
+    return (unsigned)std::min<long long>(std::max<long long>(4, ctx->knobs.i(K_PLANE_TREE_GROUP_PLANES, 0)), RL_PLANE_TREE_GROUP_PLANES);
+}
+extern "C" int rl_plane_map_build_device(rl_context* ctx, const rl_plane_set* set, rl_plane_map** out, float* ms_kernels) {
+    if (!ctx || !set || !out) return RL_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (ms_kernels) *ms_kernels = 0.0f;
+    int rcode;
+    if ((rcode = check_plane_scene(ctx)) != RL_OK) return rcode;
+    if (set->ctx != ctx) { rl_set_error("the plane set belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
+    if (set->n_planes > kElementTreeMax) { rl_set_error("too many planes"); return RL_ERR_INVALID_ARGUMENT; }
+    HIP_OK(hipSetDevice(ctx->device));
+    const unsigned n = (unsigned)set->n_planes, n_nodes = photon_tree_node_count(n);
+    HipBuffer<unsigned> uploaded;                     // a set made on the host: its one upload
+    const unsigned* d_words = set->d_words.get();
+    if (!set->on_device) {
+        if ((rcode = uploaded.ensure(set->words.size())) != RL_OK) return rcode;
+        HIP_OK(hipMemcpyAsync(uploaded.get(), set->words.data(), set->words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        d_words = uploaded.get();
+    }
+    const std::vector<PlaneLight> lights = plane_lights(ctx);
+    auto map = std::make_unique<rl_plane_map>();
+    map->ctx = ctx; map->device = ctx->device;
+    if ((rcode = map->nodes.ensure(2 * (size_t)n_nodes)) != RL_OK || (rcode = map->planes.ensure(4 * (size_t)n)) != RL_OK || (rcode = map->lights.ensure(lights.size())) != RL_OK) return rcode;
+    HIP_OK(hipMemcpyAsync(map->lights.get(), lights.data(), lights.size() * sizeof(PlaneLight), hipMemcpyHostToDevice, ctx->stream));
+    const PlaneTreeJob job{d_words, n, plane_tree_group(ctx), map->nodes.get(), nullptr, map->planes.get()};
+    if ((rcode = plane_tree_run(job, ctx->stream, !ctx->knobs.has(K_NO_EVENTS), ms_kernels)) != RL_OK) return rcode;      // returns synchronised: `lights` and `uploaded` may go
+    map->n_planes = n; map->n_nodes = n_nodes; map->n_gen = set->n_gen; map->n_lights = lights.size(); map->strategy = set->strategy;
+    *out = map.release();
+    return RL_OK;
+}
+extern "C" int rl_plane_tree_build_device(rl_context* ctx, const uint32_t* words, size_t n_planes, size_t node_capacity, size_t* n_nodes, float* node_boxes,
+                                          uint32_t* node_links, uint32_t* order) {
+    if (!ctx || !n_nodes || (n_planes && !words)) return RL_ERR_INVALID_ARGUMENT;
+    int rcode;
+    if (n_planes > kElementTreeMax) { rl_set_error("too many planes"); return RL_ERR_INVALID_ARGUMENT; }      // before any allocation
+    const bool size_only = !node_boxes && !node_links && !order;
+    if (n_planes == 0) { *n_nodes = 0; return RL_OK; }
+    HIP_OK(hipSetDevice(ctx->device));
+    const unsigned n = (unsigned)n_planes, count = photon_tree_node_count(n);
+    HipBuffer<unsigned> d_words, d_order;
+    HipBuffer<float4> d_nodes;
+    if ((rcode = d_words.ensure(n_planes * RL_PLANE_WORDS)) != RL_OK) return rcode;
+    HIP_OK(hipMemcpyAsync(d_words.get(), words, n_planes * RL_PLANE_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (size_only || node_capacity < count || !node_boxes || !node_links || !order) {
+        // the host build refuses a bad record before it looks at the capacity or the arrays: the prepass alone
+        const PlaneTreeJob check{d_words.get(), n, plane_tree_group(ctx), nullptr, nullptr, nullptr};
+        if ((rcode = plane_tree_run(check, ctx->stream, false, nullptr)) != RL_OK) return rcode;
+        *n_nodes = count;
+        if (size_only) return RL_OK;
+        if (node_capacity < count) rl_set_error("rl_plane_tree_build_device: node_capacity is too small");
+        return RL_ERR_INVALID_ARGUMENT;
+    }
+    if ((rcode = d_order.ensure(n)) != RL_OK || (rcode = d_nodes.ensure(2 * (size_t)count)) != RL_OK) return rcode;
+    const PlaneTreeJob job{d_words.get(), n, plane_tree_group(ctx), d_nodes.get(), d_order.get(), nullptr};
+    if ((rcode = plane_tree_run(job, ctx->stream, false, nullptr)) != RL_OK) return rcode;
+    *n_nodes = count;
+    std::vector<float4> h_nodes(2 * (size_t)count);
+    HIP_OK(hipMemcpy(h_nodes.data(), d_nodes.get(), h_nodes.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(order, d_order.get(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    unpack_tree_nodes(h_nodes, count, node_boxes, node_links);
     return RL_OK;
 }
 extern "C" int rl_plane_map_info(const rl_plane_map* map, uint64_t* n_planes, uint64_t* n_nodes, uint64_t* number_plane_gen, int* strategy) {

@@ -102,7 +102,7 @@ struct BreConst {
 // IntegratorSinglePlane (plane.hip.h): the rectangular lights, the generation's constants, and for the gather the plane tree in visiting order with the
 // planes in leaf order (host/planetree.cpp)
 struct PlaneLight { float o[3], u_l, u[3], v_l, v[3], pad0, n[3], pad1, emission[3], pad2; };      // RectangularLightSource, 5 float4
-enum { PLANE_GEN_PLANES = 0, PLANE_GEN_ITERATIONS = 1, PLANE_GEN_DRAWS = 2, PLANE_GEN_WORDS = 3 };
+enum { PLANE_GEN_PLANES = 0, PLANE_GEN_ITERATIONS = 1, PLANE_GEN_DRAWS = 2, PLANE_GEN_WORDS = 3, PLANE_LANES_FLAG = 4, PLANE_LANES_WORDS = 5 };
 struct PlaneGenConst {
     unsigned nb_primitive, cap;         // stop once nb_primitive planes are stored; records beyond cap are not written
     int strategy;                       // rl_plane_strategy
@@ -111,7 +111,7 @@ struct PlaneGenConst {
     float sigma_t[3], sigma_s[3];       // the medium's
     unsigned* words;                    // [cap][RL_PLANE_WORDS]
     unsigned long long* gen_state;      // [4] the main sampler, read and written back
-    unsigned long long* gen_out;        // [PLANE_GEN_WORDS] planes stored, iterations (number_plane_gen), draws
+    unsigned long long* gen_out;        // [PLANE_GEN_WORDS] planes stored, iterations (number_plane_gen), draws; k_plane_generate_lanes: [PLANE_LANES_WORDS] the sampler it leaves, the flag word
 };
 enum { STAT_PLANE_ISECT = 6, STAT_PLANE_VISIBLE = 7, STAT_PLANE_ISECT_HI = 2, STAT_PLANE_VISIBLE_HI = 3 };      // its leaf's statistics rows: planes intersected, of those visible
 enum { PLANE_MODE_PLAIN = 0, PLANE_MODE_DISCRETE_MIS = 1, PLANE_MODE_CMIS = 2 };      // k_plane_gather's instantiations: a constant weight, DiscreteMIS, ContinousMIS
@@ -170,8 +170,9 @@ void launch_vpl_paths_stream(bool write, int mat, bool medium, dim3 grid, dim3 b
 // IntegratorVolPrimitives' beam radiance estimate (bre.hip.h): k_bre_gather over the owned blocks; hg: the medium's phase function is Henyey-Greenstein
 void launch_bre_lds(bool hg, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BreConst& bc);
 void launch_bre_stream(bool hg, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BreConst& bc);
-// IntegratorSinglePlane (plane.hip.h): k_plane_generate on one lane (plane_generate.hip); k_plane_gather over the owned blocks, mode = PLANE_MODE_*
+// IntegratorSinglePlane (plane.hip.h): k_plane_generate on one lane, k_plane_generate_lanes on one lane per iteration (plane_generate.hip); k_plane_gather over the owned blocks, mode = PLANE_MODE_*
 void launch_plane_generate(hipStream_t st, const PlaneGenConst& gc);
+void launch_plane_generate_lanes(hipStream_t st, const PlaneGenConst& gc, unsigned n_gen);      // k_plane_generate_lanes: one lane per iteration, n_gen of them
 void launch_plane_lds(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PlaneConst& pc);
 void launch_plane_stream(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PlaneConst& pc);
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)

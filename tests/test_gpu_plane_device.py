@@ -1,0 +1,308 @@
+"""The device forms of plane-single's set-up — rl_plane_generate_lanes (one lane per iteration of the plane pass), rl_plane_map_build_device and
+rl_plane_tree_build_device (the plane tree from the kernels of kernels/phototree.hip.h) — held to the forms they restate: rl_plane_generate and the host
+build, which tests/test_plane_single_restatement.py and tests/test_gpu_plane_single_exact.py hold to the reference's text.  Everything is equality of bytes:
+the tree arrays over sizes around the leaf size and the group T, with the group forced down so that a few hundred planes pass through five and more global
+levels, on the families of tests/plane_tree_cases.py (signed zeros in the boxes included) and on generated planes of every strategy; the refusals; the lane
+form's records, sampler and counters over every strategy, counts around a wave and one and two lights; the redraw of a direction, on a crafted sampler state,
+where the lanes' jump-ahead does not hold and the call must notice; then whole maps, images and counters across {serial, lanes} x {host, device}, through the
+options on the old entry points, the Python mirror and the CLI.  One process; only the CLI test starts a child."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import orc
+from rustlight_amd import abi, api, scenes
+from tests import plane_single_restatement as R
+from tests import plane_tree_cases as P
+from tests.scene_helpers import context as _context, two_lights
+
+pytestmark = pytest.mark.gpu
+
+RL_ERR_INVALID_ARGUMENT = -1
+RL_VPL_MAX = 1 << 20
+T = api.PLANE_TREE_GROUP_PLANES
+SIZES = (0, 1, 4, 5, 8, 9, 17, T - 1, T, T + 1, 2 * T + 1)
+KNOB = "plane_tree_group_planes"
+GEN_KEYS = ("camera_samples", "vertices", "rng_draws")
+MAP_KEYS = ("camera_samples", "extension_rays", "shadow_rays", "rng_draws", "nodes_entered", "planes_intersected", "planes_visible")
+
+
+@functools.lru_cache(maxsize=None)
+def _plain_ctx():
+    return _context(scenes.cbox(16, 16))                    # the tree entry point needs a device only: no medium here
+
+
+@functools.lru_cache(maxsize=None)
+def _medium_ctx(lights=1):
+    return _context(two_lights(32, 24) if lights == 2 else scenes.cbox_medium(32, 24, 1.0))
+
+
+@functools.lru_cache(maxsize=None)
+def _host_tree(family, n):
+    return api.plane_tree_build(P.planes(family, n))
+
+
+# ---- the tree arrays
+@pytest.mark.parametrize("family", P.FAMILIES)
+def test_tree_arrays_equal_the_host_build(built, family):
+    ctx = _plain_ctx()
+    for n in SIZES:
+        got = ctx.plane_tree_build_device(P.planes(family, n))
+        P.assert_trees_equal(got, _host_tree(family, n), f"{family} n={n}")
+        if family == "equal":
+            np.testing.assert_array_equal(got[2], np.arange(n, dtype=np.uint32))
+
+
+@pytest.mark.parametrize("group", [8, 64])
+@pytest.mark.parametrize("family", P.FAMILIES)
+def test_tree_arrays_through_several_global_levels(built, family, group):
+    ctx = _plain_ctx()
+    with ctx.options(**{KNOB: group}):
+        for n in (9, 17, 100, 300):
+            P.assert_trees_equal(ctx.plane_tree_build_device(P.planes(family, n)), _host_tree(family, n), f"{family} n={n} group={group}")
+
+
+@pytest.mark.parametrize("strategy", api.PLANE_STRATEGIES)
+def test_tree_arrays_of_generated_planes(built, strategy):
+    ctx = _medium_ctx()
+    pset, _ = ctx.plane_generate(api.IndependentSampler(5), 300, strategy)
+    words = pset.words()
+    want = api.plane_tree_build(words)
+    for group in (None, 8):
+        with ctx.options(**{KNOB: group}):
+            P.assert_trees_equal(ctx.plane_tree_build_device(words), want, f"{strategy} group={group}")
+
+
+def test_nothing_depends_on_the_group_or_the_run(built):
+    ctx = _plain_ctx()
+    n = 2 * T + 1
+    for family in ("zeros", "tied"):
+        words, want = P.planes(family, n), _host_tree(family, n)
+        for group in (None, None, 8, 64):
+            with ctx.options(**{KNOB: group}):
+                P.assert_trees_equal(ctx.plane_tree_build_device(words), want, f"{family} group={group}")
+
+
+def _raw_build(ctx, words, capacity, arrays):
+    """One raw call of both tree entry points: [(code, n_nodes, message)] for the host build and the device build."""
+    w = np.ascontiguousarray(words, np.uint32).reshape(-1, api.PLANE_WORDS)
+    out = []
+    for device in (False, True):
+        n = C.c_size_t(12345)
+        boxes, links, order = np.zeros((max(capacity, 1), 6), np.float32), np.zeros((max(capacity, 1), 3), np.uint32), np.zeros(max(w.shape[0], 1), np.uint32)
+        tail = (abi.fptr(boxes), abi.u32ptr(links), abi.u32ptr(order)) if arrays else (None, None, None)
+        if device:
+            code = api.lib().rl_plane_tree_build_device(ctx.h, abi.u32ptr(w), w.shape[0], capacity, C.byref(n), *tail)
+        else:
+            code = api.lib().rl_plane_tree_build(abi.u32ptr(w), w.shape[0], capacity, C.byref(n), *tail)
+        out.append((code, n.value, api.lib().rl_last_error().decode() if code != api.RL_OK else ""))
+    return out
+
+
+def test_tree_refusals(built):
+    ctx = _plain_ctx()
+    n = 2 * T + 1
+    good = P.planes("random", n)
+    for bad in (np.nan, np.inf, -np.inf):
+        for rec, word in ((0, 0), (n // 2, 4), (n - 1, 10)):                  # o.x, d0.y, length1: a corner that is not finite
+            w = good.copy()
+            w[rec, word] = np.float32(bad).view(np.uint32)
+            host, dev = _raw_build(ctx, w, 4 * n, True)
+            assert host[0] == RL_ERR_INVALID_ARGUMENT and "not finite" in host[2] and dev == host, (bad, rec, host, dev)
+            host, dev = _raw_build(ctx, w, 0, False)                          # the size-only call checks the records too
+            assert host[0] == RL_ERR_INVALID_ARGUMENT and dev == host
+    w = good.copy()
+    w[7, 0] = np.float32(np.nan).view(np.uint32)
+    host, dev = _raw_build(ctx, w, 1, True)                                   # the record check comes before the capacity
+    assert "not finite" in host[2] and dev == host
+    host, dev = _raw_build(ctx, good, 1, True)                                # a capacity that is too small: the count comes back with the refusal
+    assert host[0] == RL_ERR_INVALID_ARGUMENT and "node_capacity is too small" in host[2] and host[1] == len(_host_tree("random", n)[0])
+    assert dev[:2] == host[:2] and "node_capacity is too small" in dev[2]
+    host, dev = _raw_build(ctx, good, 0, False)                               # the size-only call
+    assert host == (api.RL_OK, len(_host_tree("random", n)[0]), "") and dev == host
+    host, dev = _raw_build(ctx, np.zeros((RL_VPL_MAX + 4097, api.PLANE_WORDS), np.uint32), 0, False)
+    assert host[0] == RL_ERR_INVALID_ARGUMENT and "too many" in host[2] and dev == host
+
+
+# ---- the lane-parallel plane pass
+def _generate(ctx, form, nb, strategy, seed=3, state=None):
+    sampler = api.IndependentSampler(seed)
+    if state is not None:
+        for k in range(4):
+            sampler.s.s[k] = int(state[k])
+    pset, st = ctx.plane_generate(sampler, nb, strategy, form=form)
+    return pset.words(), pset.info(), list(sampler.s.s), tuple(st[k] for k in GEN_KEYS)
+
+
+def _assert_same_generation(lanes, serial, what):
+    np.testing.assert_array_equal(lanes[0], serial[0], err_msg=str(what))
+    assert lanes[1:] == serial[1:], (what, lanes[1:], serial[1:])
+
+
+@pytest.mark.parametrize("lights", [1, 2])
+@pytest.mark.parametrize("strategy", api.PLANE_STRATEGIES)
+def test_lanes_equal_the_serial_pass(built, strategy, lights):
+    ctx = _medium_ctx(lights)
+    for seed in (3, 11):
+        for nb in (1, 2, 3, 4, 64, 65, 1000):
+            serial = _generate(ctx, "serial", nb, strategy, seed)
+            _assert_same_generation(_generate(ctx, "lanes", nb, strategy, seed), serial, (strategy, lights, seed, nb))
+            per = 3 if strategy in ("average", "discrete_mis") else 1
+            n_gen = -(-nb // per)
+            assert serial[1] == (n_gen * per, n_gen, strategy) and serial[3] == (n_gen, n_gen * per, n_gen * (1 + 6 * per))
+    if lights == 2:
+        assert set(int(v) for v in serial[0][:, 17]) == {0, 1}                # both id_emitter values occur
+
+
+# From (0, REDRAW_S1, s2, 0) the next two draws are exactly 0.0 and 0.5 (s0 = s3 = 0 makes the first output 0; the second depends on s1 alone, found by
+# trying multiples of 0x9E3779B97F4A7C15 until its top 24 bits were 0x800000: 19,238,003 tries).  cosine_sample_hemisphere(0.0, 0.5) = (-1, 0, 0): z == 0.
+REDRAW_S1 = 13460080819902757231
+
+
+@pytest.mark.parametrize("j", [0, 5])
+@pytest.mark.parametrize("strategy", ["uv", "average", "cmis"])
+def test_lanes_notice_a_redrawn_direction(built, strategy, j):
+    """The one place where the jump-ahead is wrong: iteration j draws its first direction again, so every later iteration starts 2 draws further down the
+    stream than D * i.  The sampler is handed over in a state whose draws 1 and 2 of iteration j are (0.0, 0.5); the restatement says on the CPU that this
+    direction lies in the light's plane and that the serial walk then takes more than n_gen * D draws.  The lanes form must give the serial form's bytes."""
+    probe = orc.Rng.from_state([0, REDRAW_S1, 0x0123456789abcdef, 0])
+    ux, uy = probe.next_f32(), probe.next_f32()
+    assert (ux, uy) == (0.0, 0.5) and R.cosine_sample_hemisphere(np.float32(ux), np.float32(uy))[2] == 0.0
+    per = 3 if strategy == "average" else 1
+    draws = 1 + 6 * per                                                       # the emitter, then per plane 2 + 1 + 2 + 1
+    state = [0, REDRAW_S1, 0x0123456789abcdef, 0]
+    for _ in range(j * draws + 1):                                            # the emitter draw of iteration j, and the j iterations before it
+        state = R.state_before(state)
+    nb = 24
+    n_gen = -(-nb // per)
+    sd = scenes.cbox_medium(32, 24, 1.0)
+    _, words, ref_gen, after, ref_draws, redraws = R.generate(sd, state, nb, strategy)
+    assert redraws >= 1 and ref_gen == n_gen and ref_draws > n_gen * draws
+    ctx = _medium_ctx()
+    serial = _generate(ctx, "serial", nb, strategy, state=state)
+    np.testing.assert_array_equal(serial[0], words)
+    assert serial[2] == [int(v) for v in after] and serial[3] == (n_gen, n_gen * per, ref_draws)
+    _assert_same_generation(_generate(ctx, "lanes", nb, strategy, state=state), serial, (strategy, j))
+
+
+def test_lanes_refusals(built):
+    """What tests/test_gpu_plane_single_exact.py sees from rl_plane_generate: the same codes and messages, the sampler left as it was."""
+    sd = scenes.cbox_medium(16, 16, 1.0)
+    ctx = _context(sd)
+    s = api.IndependentSampler(0)
+    before = list(s.s.s)
+    for form in api.PLANE_FORMS:
+        for args in ((0, "average"), ((1 << 20) + 1, "average"), (8, -1), (8, 7)):
+            with pytest.raises(api.RustlightError) as e:
+                ctx.plane_generate(s, *args, form=form)
+            assert e.value.code == RL_ERR_INVALID_ARGUMENT, (form, args)
+    with pytest.raises(api.RustlightError) as e:
+        _context(scenes.cbox(16, 16)).plane_generate(s, 8, form="lanes")                         # no medium
+    assert e.value.code == api.RL_ERR_UNSUPPORTED
+    thin = _context(scenes.cbox_medium(16, 16, 1.2e-38))                                         # sampled distances overflow f32: corners that are not finite
+    messages = []
+    for form in api.PLANE_FORMS:
+        with pytest.raises(api.RustlightError) as e:
+            thin.plane_generate(s, 512, "ut", form=form)
+        assert e.value.code == RL_ERR_INVALID_ARGUMENT
+        messages.append(str(e.value))
+    assert messages[0] == messages[1] and "not finite" in messages[0]
+    assert list(s.s.s) == before
+    with pytest.raises(ValueError):
+        ctx.plane_generate(s, 8, form="waves")
+    with pytest.raises(ValueError):
+        ctx.plane_map(None, build="gpu")
+
+
+# ---- whole maps and images
+def _map_and_image(ctx, sd, strategy, form, build, options=None):
+    """(map.read() arrays, map.info(), image, counters) of 128 planes at 2 spp; options: the knobs, on the old entry points."""
+    sampler = api.IndependentSampler(7)
+    with ctx.options(**(options or {})):
+        pset, _ = ctx.plane_generate(sampler, 128, strategy, form=form)
+        pmap = ctx.plane_map(pset, build=build)
+    words = pset.words()                                                      # a lanes set: downloaded on first use, here or by the host build
+    img, st = ctx.render_plane_single(pmap, sampler.block_seeds(sd.width, sd.height), 2)
+    out = (pmap.read(), pmap.info(), img, {k: st[k] for k in MAP_KEYS}, words, pmap.ms_kernels)
+    pmap.close(); pset.close()
+    return out
+
+
+def _assert_same_map(got, want, what):
+    for name, g, w in zip(("boxes", "links", "planes"), got[0], want[0]):
+        np.testing.assert_array_equal(g.view(np.uint32), w.view(np.uint32), err_msg=f"{what}: {name}")
+    assert got[1] == want[1], what
+    print(what, "pixels that differ:", int(np.count_nonzero((got[2] != want[2]).any(axis=-1))), got[3], want[3])
+    np.testing.assert_array_equal(got[2], want[2], err_msg=str(what))
+    assert got[3] == want[3], (what, got[3], want[3])
+    np.testing.assert_array_equal(got[4], want[4], err_msg=f"{what}: records")
+
+
+@pytest.mark.parametrize("strategy", ["average", "discrete_mis", "cmis"])
+def test_maps_and_images_equal_across_the_forms(built, strategy):
+    sd = scenes.cbox_medium(32, 24, 1.0)
+    ctx = _medium_ctx()
+    want = _map_and_image(ctx, sd, strategy, "serial", "host")
+    assert want[2].any() and want[3]["planes_visible"] > 0 and want[5] is None
+    for form in api.PLANE_FORMS:
+        for build in api.TREE_BUILDS:
+            got = _map_and_image(ctx, sd, strategy, form, build)
+            _assert_same_map(got, want, (strategy, form, build))
+            assert (got[5] is not None and got[5] > 0.0) == (build == "device")
+    with ctx.options(**{KNOB: 8}):                                            # the same map through five global levels
+        _assert_same_map(_map_and_image(ctx, sd, strategy, "lanes", "device"), want, (strategy, "group 8"))
+    # the two options on the old entry points
+    for options in ({"plane_generate_lanes": 1}, {"plane_tree_device": 1}, {"plane_generate_lanes": 1, "plane_tree_device": 1}):
+        _assert_same_map(_map_and_image(ctx, sd, strategy, "serial", "host", options), want, (strategy, options))
+    _assert_same_map(_map_and_image(ctx, sd, strategy, "serial", "host", {"plane_generate_lanes": 0, "plane_tree_device": 0}), want, (strategy, "options at 0"))
+
+
+def test_maps_from_another_context_are_refused(built):
+    sd = scenes.cbox_medium(16, 16, 1.0)
+    ctx, other = _context(sd), _context(sd)
+    s = api.IndependentSampler(0)
+    for form in api.PLANE_FORMS:
+        pset, _ = ctx.plane_generate(s, 16, "average", form=form)
+        for build in api.TREE_BUILDS:
+            with pytest.raises(api.RustlightError) as e:
+                other.plane_map(pset, build=build)                            # a set from another context
+            assert e.value.code == RL_ERR_INVALID_ARGUMENT and "another context" in str(e.value), (form, build)
+        pmap = ctx.plane_map(pset, build="device")
+        with pytest.raises(api.RustlightError) as e:
+            other.render_plane_single(pmap, s.block_seeds(16, 16))            # a device-built map is a map
+        assert e.value.code == RL_ERR_INVALID_ARGUMENT
+    with pytest.raises(api.RustlightError) as e:
+        _context(scenes.cbox(16, 16)).plane_map(pset, build="device")         # no medium
+    assert e.value.code == api.RL_ERR_UNSUPPORTED
+
+
+def test_integrator_compute(built):
+    sd = scenes.cbox_medium(24, 16, 1.0)
+    want = api.IntegratorSinglePlane(nb_primitive=64, strategy="cmis").compute(api.IndependentSampler(9), api.Scene(sd), 2)
+    assert want.any()
+    for generate, tree_build in (("lanes", "host"), ("serial", "device"), ("lanes", "device")):
+        integ = api.IntegratorSinglePlane(nb_primitive=64, strategy="cmis", generate=generate, tree_build=tree_build)
+        np.testing.assert_array_equal(integ.compute(api.IndependentSampler(9), api.Scene(sd), 2), want, err_msg=f"{generate} {tree_build}")
+    for kw in ({"generate": "waves"}, {"tree_build": "gpu"}):
+        with pytest.raises(ValueError):
+            api.IntegratorSinglePlane(**kw)
+
+
+def test_cli_writes_the_same_bytes(built, tmp_path):
+    """`--option plane_generate_lanes=1 --option plane_tree_device=1` goes through the C++ mirror's options (integrator.hpp): the PFM of the same line without
+    them, byte for byte."""
+    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
+    scn = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cbox.pbrt")
+    outs = []
+    for name, extra in (("plain.pfm", []), ("device.pfm", ["--option", "plane_generate_lanes=1", "--option", "plane_tree_device=1"])):
+        out = str(tmp_path / name)
+        r = subprocess.run([exe, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out] + extra + ["plane-single", "-n", "128", "-s", "average"],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        outs.append(open(out, "rb").read())
+    assert len(outs[0]) > 64 and outs[1] == outs[0]
+    assert api.load_pfm(str(tmp_path / "device.pfm")).any()
