@@ -455,6 +455,14 @@ class Context(_ImageCalls):
         result), `None` = back to the default.  The context took the environment's RL_<NAME> values when it was created; renders never read the environment."""
         _check(lib().rl_context_set_option(self.h, name.lower().encode(), None if value is None else str(value).encode()))
 
+    def sample_buf_bytes(self) -> int:
+        """Test hook (rl_debug_sample_buf_bytes): bytes of the per-sample parking buffer this context holds (0 until a render needed one)."""
+        n = C.c_uint64(0)
+        fn = lib().rl_debug_sample_buf_bytes
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        _check(fn(self.h, C.byref(n)))
+        return int(n.value)
+
     def get_option(self, name: str):
         v = lib().rl_context_get_option(self.h, name.lower().encode())
         return None if v is None else v.decode()

@@ -47,6 +47,7 @@
 #define RL_T0 { t0 = __builtin_readcyclecounter(); }
 #define RL_T1(K, COND) { unsigned long long t1 = __builtin_readcyclecounter(); tm[K] += t1 - t0; ln[K] += __popcll(__ballot(COND)); t0 = t1; }
     unsigned long long t0;
+    const unsigned long long wg_t0 = wall_clock64();
 #else
 #define RL_T0
 #define RL_T1(K, COND)
@@ -111,7 +112,13 @@
         ln[4] += 64;
         const bool c0 = PU(U_FLAGS) & ST_REGEN;
 #endif
-        if (PU(U_FLAGS) & ST_REGEN) raygen_slot<true, decltype(ps), SMP>(rc, sc, ps, n_samples, n_draws);   // work items from the global dispenser
+        // (the tail of the static tile order at several lanes per pixel: only the including kernel that says so — fused.hip.h — every other form keeps its code)
+#ifdef RL_FUSED_BODY_TAIL
+        constexpr bool kTail = RL_FUSED_BODY_TAIL;
+#else
+        constexpr bool kTail = false;
+#endif
+        if (PU(U_FLAGS) & ST_REGEN) raygen_slot<true, decltype(ps), SMP, kTail>(rc, sc, ps, n_samples, n_draws);   // work items from the global dispenser
         RL_T1(0, c0)
 #ifdef RL_STAGE_TIMERS
         const bool c1 = PU(U_FLAGS) & ST_RAY;
@@ -145,3 +152,6 @@
         const unsigned vals[5] = {n_samples, n_vertices, n_draws, n_shadow, n_ext};
         block_stats<5>(rc.partials, which, vals);
     }
+#ifdef RL_STAGE_TIMERS
+    if (threadIdx.x == 0u && blockIdx.x < kFusedWgSlots) { g_fused_wgs[2 * blockIdx.x] = wg_t0; g_fused_wgs[2 * blockIdx.x + 1] = wall_clock64(); }      // (after block_stats' barriers: every wave of the workgroup has ended)
+#endif

@@ -5,7 +5,8 @@
 // steps every render kind shares (this shard's blocks, the tables, the image, the statistics rows, the finish) are RenderFrame's (wavefront.hip):
 //   choose_form()      wavefront stage kernels | persistent kernel; reference-order streams in two passes (chain.hip.h) or one
 //   plan_chunks()      two passes: block cursors per chunk so that the recorded sampler states fit their buffer
-//   plan_lanes()       how pixel items / block chains are laid over the lanes (lanes per pixel, pool slots, item spread), buffers
+//   plan_lanes()       how pixel items / block chains are laid over the lanes (lanes per pixel, pool slots, item spread), buffers;
+//                      plan_tail(): the last heavy blocks of the persistent kernel's static tile order at several lanes per pixel
 //   upload()           the shard's tables, the zeroed framebuffer, the counters, RenderConst
 //   run_two_pass()     per chunk: plan_chain_pass() -> chain pass (k_stream_spec | k_stream_chain) with the evaluation pass beside it
 //                      (overlap_loop(): host-driven launches over lists of complete blocks) or after it, then the fold of parked samples
@@ -17,8 +18,11 @@ namespace {
 
 using namespace rl;
 
+std::atomic<int> g_path_renders_in_flight{0};      // rl_render_path calls running in this process (plan_tail's automatic choice)
+
 struct Plan { unsigned split, n_items, P, item_shift; };
 struct Chunk { unsigned c0, c1, n_pix; std::vector<unsigned> base; };
+struct Tail { unsigned begin, pixels, shift; };      // pixel items [begin, begin + pixels) at 2^shift lanes each (pixels = 0: no tail)
 
 class PathRender : RenderFrame {
 public:
@@ -26,6 +30,7 @@ public:
         : RenderFrame(c, seeds, nb, out, out_dev, stream_arg, s, p->shard_index, p->shard_count), params(p) {}
 
     int run() {
+        struct InFlight { InFlight() { g_path_renders_in_flight++; } ~InFlight() { g_path_renders_in_flight--; } } in_flight;
         int r;
         if ((r = choose_form()) != RL_OK) return r;
         plan_chunks();
@@ -51,6 +56,10 @@ private:
     std::vector<Chunk> chunks;
     unsigned max_chunk_pix = 0;
     Plan plan{1u, 0u, 0u, 0u}, plan_chain{1u, 0u, 0u, 0u};
+    Tail tail{0u, 0u, 0u};
+    long long tail_blocks = 0;         // the tail asked for (tail_request): its blocks and log2 lanes per pixel; tail_forced: by the options, not by the frame's size
+    unsigned tail_shift = 0;
+    bool tail_forced = false;
     unsigned split = 1, n_items = 0, item_shift = 0, P = 0, n_item_pixels = 0;
     Pool pool{};
     RenderConst rc{};
@@ -98,7 +107,11 @@ private:
 
     // ---- how a set of work items is laid over the lanes.  per_pixel: pixel items (RL_STREAM_PER_SAMPLE, or the second pass of reference-order
     // streams), else one item per owned block.
-    Plan plan_items(bool per_pixel, unsigned n_pix, unsigned n_chains) const {
+    // static tile order or work items from the dispenser (the persistent kernel)
+    bool dynamic_items() const { return knobs.has(K_FUSED_DYNAMIC) ? knobs.i(K_FUSED_DYNAMIC, 0) != 0 : (medium || !ctx->lds_scene); }
+
+    // tail_lanes: lanes on top of one per pixel item (plan_tail)
+    Plan plan_items(bool per_pixel, unsigned n_pix, unsigned n_chains, unsigned tail_lanes = 0u) const {
         // sample-parallel pixels: `split` lanes per pixel, per-sample radiances parked in HBM ([spp][pixel][3] floats) and folded
         // in order.  Auto: scenes that traverse out of L2 / HBM want ~8 M paths in flight per wavefront launch (measured on the
         // 508 k-triangle living-room scene at 1080p: 1 lane/pixel 935 ms, 4 lanes 787 ms, 8 lanes 836 ms); LDS-staged scenes in the
@@ -120,11 +133,12 @@ private:
             // the evaluation pass beside the chain pass: its last launch — the blocks that completed last — is what is left to do when the chain pass ends, and a launch
             // lasts as long as its slowest pixel: several lanes per pixel cut that tail (1080p x 128 spp, 1 / 4 / 8 lanes: see profiles/NEGATIVES.md round 5)
             if (overlap_wanted && !params->sample_split) want = std::max(want, (unsigned)std::max<long long>(1, knobs.i(K_EVAL_SPLIT, 4)));
+            if (tail_forced) want = 1u;          // options fused_tail_blocks / fused_tail_split: only the tail's pixels get several lanes (a small frame's automatic choice is all of them)
             pl.split = std::max(1u, std::min(want, params->spp));
             if ((size_t)n_pix * params->spp * 3 * sizeof(float) > kSampleBufBudget || one_lane_per_pixel) pl.split = 1;
             while (pl.split > 1 && (size_t)n_pix * pl.split > (size_t)0x7fffff00u) pl.split--;
         }
-        pl.n_items = per_pixel ? n_pix * pl.split : n_chains;
+        pl.n_items = per_pixel ? n_pix * pl.split + tail_lanes : n_chains;
         // a pool never needs more slots than there are work items (and `pool_slots` is caller input: keep the rounding below from wrapping)
         unsigned Pp = params->pool_slots ? std::min(params->pool_slots, std::max(pl.n_items, 1u)) : std::min<unsigned>(pl.n_items, 16u << 20);
         Pp = std::max(256u, (unsigned)(((unsigned long long)Pp + 255ull) / 256ull * 256ull));
@@ -135,8 +149,7 @@ private:
             // no workgroup idles behind its slowest pixel (cbox + medium, 32 spp: 185.5 -> 151.6 ms; 508 k triangles: 148.6 -> 126.9 ms;
             // LDS-staged scenes: plain cbox 63.5 vs 63.6 ms, mixed-BSDF cbox 23.3 vs 25.5 ms, so they keep the static tile order).
             const unsigned resident = (unsigned)cus * (unsigned)(ctx->lds_scene ? RL_FUSED_WAVES : RL_FUSED_WAVES_STREAMING) * 256u;
-            const bool dynamic_items = knobs.has(K_FUSED_DYNAMIC) ? knobs.i(K_FUSED_DYNAMIC, 0) != 0 : (medium || !ctx->lds_scene);
-            Pp = std::max(256u, (std::min(pl.n_items, dynamic_items ? resident : pl.n_items) + 255u) / 256u * 256u);
+            Pp = std::max(256u, (std::min(pl.n_items, dynamic_items() ? resident : pl.n_items) + 255u) / 256u * 256u);
             // sparse item sets (reference-order streams): one item per 2^item_shift lanes, all of them resident from the start
             // (block chains of a scene with a participating medium: their vertices are scattering events, nearly all shading — ~600 wave instructions of exact f64
             // recipes and sampler steps each, whatever the lane count — and four waves of two chains per SIMD saturate its issue slots: four chains per wave on two waves
@@ -193,6 +206,7 @@ private:
         // planned: it asks for several lanes per pixel, i.e. for the per-sample parking buffer.
         overlap_wanted = two_pass && ctx->stream2 && !fast_math && !knobs.has(K_NO_OVERLAP) && knobs.i(K_SPEC_GROUP, 0) != 256;
         int rcode;
+        tail_request();
         for (int attempt = 0; attempt < 2; attempt++) {
             plan = two_pass ? plan_items(true, max_chunk_pix, 0) : plan_items(per_sample, n_pixels, (unsigned)owned.size());   // two-pass: the largest second pass
             // (a SMALLER chunk can ask for MORE lanes per pixel, hence more slots and statistics rows than the largest one: uneven chunks at 1080p — 131 + 125 cursors — lost
@@ -209,6 +223,7 @@ private:
             if (params->sample_split || attempt == 1) return RL_ERR_HIP;
             one_lane_per_pixel = true; overlap_wanted = false;
         }
+        if ((rcode = plan_tail()) != RL_OK) return rcode;
         if ((rcode = alloc_tables()) != RL_OK) return rcode;
         if (per_sample || two_pass) {
             if (per_sample && (rcode = ctx->d_item_seed.ensure(n_item_pixels)) != RL_OK) return rcode;
@@ -232,6 +247,60 @@ private:
         return alloc_output(std::max<size_t>((P + 255) / 256, (size_t)cus * 8u * rl_context::kEvalStreams));
     }
 
+    // ---- The tail of the static tile order.  One launch of the persistent kernel ends as its last heavy workgroups end: a tile lives as long as one pixel's serial
+    // chain of samples, and once the last of them has been dispatched the chip drains from full to empty over one such lifetime.  So the last T blocks of the owned
+    // order that can see the scene (the conservative masks of the speculative chain pass, block-wide) run at S lanes per pixel: S times the workgroups, each 1 / S as
+    // long, their samples parked in sample_buf ([spp][tail pixel][3]) and folded in sample order by k_fold_samples — same image, same counters.  The range is one run of
+    // the owned order (blocks inside it that see nothing come along: they cost nothing), the order itself is kept.  Per-sample streams on an LDS-staged scene without
+    // a medium and with static items only; where the parking buffer cannot be had the frame renders without a tail.  Options fused_tail_blocks / fused_tail_split
+    // (0: off = the plan without it; set, the pixels outside the tail keep one lane each whatever the frame's size); auto: kFusedTailBlocks x kFusedTailSplit for
+    // frames of >= 6000 workgroups, which are the frames whose automatic choice is one lane per pixel (profiles/fused_tail_note.md).
+    static constexpr unsigned kFusedTailBlocks = 512u, kFusedTailSplit = 4u;
+    void tail_request() {
+        tail_blocks = 0; tail_shift = 0; tail_forced = false;
+        if (!per_sample || strat || two_pass || !fused || !ctx->lds_scene || medium || dynamic_items() || params->sample_split || owned.empty()) return;
+        // automatic: large frames of the instantiation it was measured on and whose registers it does not cost — one diffuse BSDF, area lights only, exact build
+        // (profiles/fused_tail_note.md: other forms of the kernel spill up to three times the VGPRs with it and were not timed; the options still put it there) — and
+        // only while this is the process's one path render in flight: beside other frames the drain is filled already and the split only costs (- 1 %, same note)
+        const bool large = (n_pixels + 255u) / 256u >= 6000u && ctx->single_bsdf && ctx->bsdf_type == RL_BSDF_DIFFUSE && ctx->area_lights_only && !fast_math && g_path_renders_in_flight.load() <= 1;
+        const long long T = knobs.has(K_FUSED_TAIL_BLOCKS) ? knobs.i(K_FUSED_TAIL_BLOCKS, 0) : (large ? (long long)kFusedTailBlocks : 0);
+        const long long S = std::min<long long>(std::min<long long>(knobs.has(K_FUSED_TAIL_SPLIT) ? knobs.i(K_FUSED_TAIL_SPLIT, 0) : (long long)kFusedTailSplit, 64), params->spp);
+        unsigned shift = 0;
+        while ((2ll << shift) <= S) shift++;            // the largest power of two <= min(S, spp)
+        if (T <= 0 || shift == 0u) return;
+        tail_blocks = T; tail_shift = shift;
+        tail_forced = knobs.has(K_FUSED_TAIL_BLOCKS) || knobs.has(K_FUSED_TAIL_SPLIT);
+    }
+    int plan_tail() {
+        tail = Tail{0u, 0u, 0u};
+        if (tail_blocks <= 0 || split != 1u) return RL_OK;
+        const long long T = tail_blocks;
+        const unsigned shift = tail_shift;
+        // which owned blocks can see the scene: camera, scene bounds and shard only — once per context and shard
+        const bool expand = !params->has_max_depth || 1u < params->max_depth;
+        const uint64_t key = ((uint64_t)params->shard_index << 33) | ((uint64_t)shard_count << 1) | (expand ? 1u : 0u);
+        if (key != ctx->heavy_key || ctx->heavy_blocks.size() != owned.size()) {
+            std::vector<unsigned> masks;
+            trivial_pixel_masks(trivial_input(ctx), params, owned, nby, false, &masks, true);
+            ctx->heavy_blocks.assign(owned.size(), 0);
+            for (size_t j = 0; j < owned.size(); j++) ctx->heavy_blocks[j] = (masks[j * 8] & 1u) ? 0 : 1;      // (block-wide masks: bit 0 speaks for the block)
+            ctx->heavy_key = key;
+        }
+        size_t j0 = 0, j1 = 0; long long found = 0;
+        for (size_t j = owned.size(); j-- > 0 && found < T;) if (ctx->heavy_blocks[j]) { if (!found) j1 = j; j0 = j; found++; }
+        if (!found) return RL_OK;                       // every block looks past the scene
+        const unsigned p0 = item_base[j0], p1 = j1 + 1 < owned.size() ? item_base[j1 + 1] : n_pixels;
+        const size_t lanes = (size_t)(p1 - p0) << shift;
+        if ((size_t)n_pixels + lanes > (size_t)0x7fffff00u || (size_t)(p1 - p0) * params->spp * 3 * sizeof(float) > kSampleBufBudget) return RL_OK;
+        // no room to park the samples: no tail, and the render that goes on is not left with that failure's message
+        if (knobs.has(K_FUSED_TAIL_NO_BUFFER_TEST) || ctx->d_sample_buf.ensure((size_t)(p1 - p0) * params->spp * 3) != RL_OK) { rl_set_error(""); return RL_OK; }
+        tail = Tail{p0, p1 - p0, shift};
+        plan = plan_items(true, n_pixels, 0, (unsigned)lanes - tail.pixels);
+        n_items = plan.n_items; item_shift = plan.item_shift;
+        P = std::max(plan.P, plan_chain.P);
+        return RL_OK;
+    }
+
     int upload() {
         int rcode;
         if ((rcode = RenderFrame::upload(!two_pass, true)) != RL_OK) return rcode;
@@ -249,6 +318,7 @@ private:
         rc.n_items = n_items;
         rc.item_shift = item_shift;
         rc.split = split; rc.sample_buf = ctx->d_sample_buf.get();
+        rc.tail_begin = tail.begin; rc.tail_pixels = tail.pixels; rc.tail_shift = tail.shift; rc.tail_lanes = tail.pixels << tail.shift;
         rc.sample_states = ctx->d_sample_states.get(); rc.chain_states = ctx->d_chain_states.get();
 
         lds_trav = traversal_lds_bytes(ctx, ctx->lds_scene, 256, true);
@@ -668,6 +738,7 @@ private:
     int finish() {
         // one more raygen pass is never needed: `active` reaches 0 inside k_raygen after the last fold.
         if (split > 1 && !two_pass) { hipLaunchKernelGGL(k_fold_samples, dim3((n_pixels + 255) / 256), dim3(256), 0, st, rc); launches += 1; }
+        else if (tail.pixels) { hipLaunchKernelGGL(k_fold_samples, dim3((tail.pixels + 255) / 256), dim3(256), 0, st, rc); launches += 1; }      // (the tail's pixels only)
         const int rcode = download();
         if (rcode != RL_OK) return rcode;
         if (stats) {

@@ -141,6 +141,10 @@ struct RenderConst {
     const unsigned* q_list;             // QUEUE form: owned-block indices this launch renders, q_n of them; q_ctr: its item-claim counter
     unsigned q_n;
     unsigned* q_ctr;
+    // the tail of the persistent kernel's static tile order (per-sample streams, one item per lane): the pixel items [tail_begin, tail_begin + tail_pixels) run at
+    // 2^tail_shift adjacent lanes per pixel — lane items [tail_begin, tail_begin + tail_lanes) — and park their samples in sample_buf ([spp][tail pixel][3]); the
+    // pixel items before and after them keep one lane each.  tail_lanes = 0: no tail (every other kernel and form).
+    unsigned tail_begin, tail_lanes, tail_shift, tail_pixels;
 };
 // called by thread 0 of every workgroup of a chain kernel
 RL_DEV void queue_workgroup_started(const RenderConst& rc) {

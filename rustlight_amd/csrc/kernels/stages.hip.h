@@ -86,7 +86,9 @@ RL_DEV void raygen_chain_slot(const RenderConst& rc, const DeviceScene& sc, PS& 
 // Camera::generate for one slot that asked for regeneration.  DYNAMIC: work items come from the global
 // dispenser (wavefront pool); otherwise the slot owns exactly one item (persistent fused kernel).
 // SMP: the sampler the sample's draws go through (sampler.hip.h) — Rng, or StratSampler (RL_STREAM_STRATIFIED: per-pixel items only).
-template <bool DYNAMIC, class PS, class SMP = Rng>
+// TAIL (k_path_fused<.., NUM + 2, ..>, launched only for a render that has a tail: rc.split is 1, the work items are static): the lanes per pixel are a function of
+// the lane's item — RenderConst::tail_* — recomputed from U_ITEM here, so that nothing of it stays live across the kernel's loop.
+template <bool DYNAMIC, class PS, class SMP = Rng, bool TAIL = false>
 RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, unsigned& n_samples, unsigned& n_draws) {
     unsigned flags = PU(U_FLAGS);
     if (!(flags & ST_REGEN)) return;
@@ -99,13 +101,27 @@ RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, un
     constexpr bool STRAT = !std::is_same<SMP, Rng>::value;
     const bool per_pixel = STRAT || rc.stream_mode != RL_STREAM_REFERENCE_ORDER;    // per-pixel work items: RL_STREAM_PER_SAMPLE / _STRATIFIED, or the second pass of reference-order streams
     const bool given = !STRAT && rc.stream_mode == kStreamGivenStates;
-    const unsigned split = per_pixel ? rc.split : 1u;
-    const unsigned pitem = split > 1u ? item / split : item;         // pixel item of this lane
+    unsigned split = per_pixel ? rc.split : 1u;
+    unsigned pitem = split > 1u ? item / split : item;               // pixel item of this lane
+    // TAIL: the tail's constants are read from the kernarg segment here and now (k_path_fused's first argument is the RenderConst; see fused_body.inc.h on what
+    // scalars kept live across the loop cost); the lanes with split > 1 are the tail's.
+    unsigned tail_begin = 0u, tail_lanes = 0u, tail_shift = 0u;
+    constexpr bool tail = TAIL;
+    if constexpr (TAIL) {
+        const char __attribute__((address_space(4)))* kt = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kt));
+        const RenderConst& rt = *(const RenderConst*)kt;
+        tail_begin = rt.tail_begin; tail_lanes = rt.tail_lanes; tail_shift = rt.tail_shift;
+        const unsigned rel = item - tail_begin;
+        const bool in_tail = rel < tail_lanes;
+        split = in_tail ? 1u << tail_shift : 1u;
+        pitem = in_tail ? tail_begin + (rel >> tail_shift) : (item < tail_begin ? item : item - (tail_lanes - (tail_lanes >> tail_shift)));
+    }
     if (!fresh && split > 1u) {
         // sample-parallel pixels: this lane owns samples s, s + split, ...; each sample's radiance is parked in
         // sample_buf[s][pixel item] and k_fold_samples adds them up in sample order, as mod.rs:431 does
         const Col L = loadc(ps, F_LR);
-        float* dst = rc.sample_buf + 3 * ((size_t)s * (rc.n_items / split) + pitem);
+        float* dst = tail ? rc.sample_buf + 3 * ((size_t)s * (tail_lanes >> tail_shift) + (pitem - tail_begin)) : rc.sample_buf + 3 * ((size_t)s * (rc.n_items / split) + pitem);
         dst[0] = L.r; dst[1] = L.g; dst[2] = L.b;
         s += split;
         if (s >= rc.spp) need_item = true;
@@ -114,7 +130,7 @@ RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, un
         acc = acc + loadc(ps, F_LR);
         s++;
         if (s == rc.spp) {
-            unsigned pix = per_pixel ? rc.item_pixel[item] : (by + cursor / bw) * rc.W + (bx + cursor % bw);
+            unsigned pix = per_pixel ? rc.item_pixel[TAIL ? pitem : item] : (by + cursor / bw) * rc.W + (bx + cursor % bw);
             Col px = scale_unguarded(acc, rc.inv_spp);            // im_block.scale(1 / spp) (mod.rs:436)
             rc.out[3 * (size_t)pix] = px.r; rc.out[3 * (size_t)pix + 1] = px.g; rc.out[3 * (size_t)pix + 2] = px.b;
             acc = czero();
@@ -137,9 +153,9 @@ RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, un
             if (split > 1u) s = item % split;
             rng = load_sample_state(rc, s, pi);                             // the block sampler as compute_mc would hold it here (k_stream_chain)
         } else if (per_pixel) {
-            const unsigned pi = split > 1u ? item / split : item;
+            const unsigned pi = TAIL ? pitem : (split > 1u ? item / split : item);
             Rng item_rng = rng_seed(rc.item_seed[pi], rc.seed_variant);     // pixel sampler = block_sampler.clone_box()
-            if (split > 1u) { s = item % split; for (unsigned k = 0; k < s; k++) rng_next_u64(item_rng); }   // forks of the samples before ours
+            if (split > 1u) { s = tail ? (item - tail_begin) & (split - 1u) : item % split; for (unsigned k = 0; k < s; k++) rng_next_u64(item_rng); }   // forks of the samples before ours
             rng = rng_seed(rng_next_u64(item_rng), rc.seed_variant);        // sample sampler = pixel_sampler.clone_box()
             store_rng(ps, Q_I0, item_rng);
         } else {
@@ -159,9 +175,9 @@ RL_DEV void raygen_slot(const RenderConst& rc, const DeviceScene& sc, PS& ps, un
         rng = load_rng(ps, Q_R0);
     }
     unsigned px, py;
-    if (per_pixel) { unsigned pix = rc.item_pixel[split > 1u ? item / split : item]; px = pix % rc.W; py = pix / rc.W; }
+    if (per_pixel) { unsigned pix = rc.item_pixel[TAIL ? pitem : (split > 1u ? item / split : item)]; px = pix % rc.W; py = pix / rc.W; }
     else { px = bx + cursor % bw; py = by + cursor / bw; }
-    SMP smp = SmpState<SMP>::begin(rc, rng, split > 1u ? item / split : item, s);
+    SMP smp = SmpState<SMP>::begin(rc, rng, TAIL ? pitem : (split > 1u ? item / split : item), s);
     // Path::from_sensor: uv = (ix + next(), iy + next())
     float u = (float)px + smp_next(smp);
     float v = (float)py + smp_next(smp);

@@ -35,6 +35,8 @@ int rl_debug_rng_advance(int device, size_t n, const uint64_t* states_in, const 
 int rl_debug_stratified_draws(int device, size_t n_pixels, const uint64_t* pixel_seeds, uint32_t spp, int seed_variant, size_t n_calls, const int32_t* pattern, float* out);
 // host only: out[y * W + x] = 1 where every camera sample of the pixel takes exactly two draws (its rays cannot reach the scene's bounding box; k_stream_spec's shortcut)
 int rl_debug_trivial_pixels(const rl_scene* scene, int has_max_depth, uint32_t max_depth, uint8_t* out);
+// bytes of the per-sample parking buffer the context holds (sample-parallel pixels, the tail of the persistent kernel): 0 until a render needed it
+int rl_debug_sample_buf_bytes(const rl_context* ctx, uint64_t* bytes);
 int rl_debug_bvh_sizes(const rl_context* ctx, uint64_t* n_ref_nodes, uint64_t* n_prims, uint32_t* stack_depth, int* lds_scene);
 // host-only: builds the BVH of `scene` and returns it in the reference's node shape (no GPU needed)
 int rl_debug_bvh(const rl_scene* scene, uint64_t* n_nodes, uint64_t* n_prims, float* boxes, uint64_t* info, uint64_t* count,

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -108,7 +109,8 @@ __global__ void __launch_bounds__(256) k_raygen(RenderConst rc, DeviceScene sc, 
 // k_fold_samples — sample-parallel pixels (split > 1): add the parked per-sample radiances of each pixel in sample
 // order and scale by 1 / spp, i.e. exactly the accumulate / scale sequence of compute_mc (mod.rs:431-436).
 __global__ void __launch_bounds__(256) k_fold_samples(RenderConst rc) {
-    const unsigned n_pix = rc.n_items / rc.split;
+    const bool tail = rc.tail_lanes != 0u;       // only the tail's pixels were parked (RenderConst::tail_*): [spp][tail pixel][3]
+    const unsigned n_pix = tail ? rc.tail_pixels : rc.n_items / rc.split;
     const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n_pix) return;
     Col acc = czero();
@@ -117,7 +119,7 @@ __global__ void __launch_bounds__(256) k_fold_samples(RenderConst rc) {
         acc = acc + mkc(src[0], src[1], src[2]);
     }
     const Col px = scale_unguarded(acc, rc.inv_spp);
-    const size_t pix = rc.item_pixel[p];
+    const size_t pix = rc.item_pixel[tail ? rc.tail_begin + p : p];
     rc.out[3 * pix] = px.r; rc.out[3 * pix + 1] = px.g; rc.out[3 * pix + 2] = px.b;
 }
 
@@ -312,6 +314,8 @@ struct rl_context {
     HipBuffer<ulonglong2> d_trk_st;
     HipBuffer<unsigned> d_trivial;
     uint64_t trivial_key = ~0ull;         // (shard index, shard count, sensor expanded?) the masks on the device were computed for
+    std::vector<unsigned char> heavy_blocks;      // per owned block: it can see the scene (PathRender::plan_tail), for the shard and sensor of heavy_key
+    uint64_t heavy_key = ~0ull;
     HipBuffer<unsigned long long> d_spec_stats;
     std::vector<hipEvent_t> events;
     // the evaluation pass overlapped with the chain pass (reference-order streams): its own low-priority stream, the completion queue, ordering events
@@ -568,7 +572,8 @@ static TrivialInput trivial_input(const rl_context* ctx) {
     in.camera = ctx->ds.camera;
     return in;
 }
-static void trivial_pixel_masks(const TrivialInput& ti, const rl_path_params* params, const std::vector<unsigned>& owned, size_t nby, bool no_shortcut, std::vector<unsigned>* out) {
+// blocks_only: only the block-wide test (a block's bits are then all set or all clear)
+static void trivial_pixel_masks(const TrivialInput& ti, const rl_path_params* params, const std::vector<unsigned>& owned, size_t nby, bool no_shortcut, std::vector<unsigned>* out, bool blocks_only = false) {
     const uint32_t W = ti.W, H = ti.H;
     out->assign(owned.size() * 8, 0u);
     const bool expand = !params->has_max_depth || 1u < params->max_depth;
@@ -631,6 +636,7 @@ static void trivial_pixel_masks(const TrivialInput& ti, const rl_path_params* pa
         const BlockRect r = block_rect(owned[j], nby, W, H);
         const unsigned bx = r.x, by = r.y, bw = r.w, bh = r.h;
         if (misses(bx - 0.25, by - 0.25, bx + bw + 0.25, by + bh + 0.25)) { all_of_block(j, bw * bh); continue; }
+        if (blocks_only) continue;
         for (unsigned c = 0; c < bw * bh; c++) {
             const double x = bx + c % bw, y = by + c / bw;
             if (misses(x - 0.25, y - 0.25, x + 1.25, y + 1.25)) (*out)[j * 8 + (c >> 5)] |= 1u << (c & 31u);
@@ -1414,6 +1420,11 @@ extern "C" int rl_debug_trace_batch_two_level(rl_context* ctx, size_t n, const f
     return RL_OK;
 }
 
+extern "C" int rl_debug_sample_buf_bytes(const rl_context* ctx, uint64_t* bytes) {
+    if (!ctx || !bytes) return RL_ERR_INVALID_ARGUMENT;
+    *bytes = (uint64_t)ctx->d_sample_buf.capacity() * sizeof(float);
+    return RL_OK;
+}
 extern "C" int rl_debug_bvh_sizes(const rl_context* ctx, uint64_t* n_ref_nodes, uint64_t* n_prims, uint32_t* stack_depth, int* lds_scene) {
     if (!ctx) return RL_ERR_INVALID_ARGUMENT;
     *n_ref_nodes = ctx->bvh_dump.ref_info.size(); *n_prims = ctx->bvh_dump.ref_prim_mesh.size();
