@@ -503,7 +503,25 @@ int rl_photon_map_read(const rl_photon_map* map, size_t node_capacity, float* no
  * writes the planes in leaf order.  A set made by rl_plane_generate is uploaded once.  ms_kernels as for rl_photon_map_build_device.  Ranges of at most
  * RL_PLANE_TREE_GROUP_PLANES planes are finished by one workgroup in LDS; the option plane_tree_group_planes = n forces a smaller group (tests).
  * rl_plane_tree_build_device: rl_plane_tree_build's contract (codes, size-only call, refusals) computed by the same kernels, with
- * rl_photon_tree_build_device's calling convention. */
+ * rl_photon_tree_build_device's calling convention.
+ * ---- IntegratorSinglePlaneUncorrelated { nb_primitive, strategy } (src/integrators/explicit/uncorrelated_plane_single.rs; the reference's CLI word is
+ * `uncorrelated-plane-single`, here `plane-single --uncorrelated`): the same estimate with no plane set — every camera sample makes nb_primitive planes of
+ * its own.  rl_render_plane_uncorrelated is the whole integrator behind the block seeds (:83: they come straight from the main sampler, as for `path`): no
+ * light pass, no tree, one kernel (kernels/uplane.hip.h).  Per camera sample, in the block's loop order ix, iy, sample (:95-97), the block's stream gives 2
+ * draws for the jitter (:99-102) — the camera ray takes tfar = its closest hit's distance, f32::MAX on a miss (:103-110) — and per plane j < nb_primitive:
+ * 1 for id_emitter (:115; clamped to the last light, the deviation rl_plane_generate has), 1 more under AVERAGE / DISCRETE_MIS for the plane type (< 1/3 UV,
+ * < 2/3 VT, else UT, :142-167), 2 for the direction (drawn again while its z is 0, :51-55), 1 for the distance (:65), 2 for `sample` (:68), 1 for alpha (:74).
+ * The plane is then treated as rl_render_plane_single treats one (:179-292): c += w * rho * transmittance * sigma_s * flux * n_lights * (1 / nb_primitive).
+ * A sample so takes D = 2 + nb_primitive * (7 or 8) draws plus 2 per redraw; the 256 lanes of a block enter its stream D * spp draws apart by jump-ahead and a
+ * block in which a direction is drawn again resolves the moved starts inside the kernel, so the image is the serial walk's bit for bit.
+ * Two behaviours of the reference are kept: (1) a plane with a non-finite corner is not refused — there is no tree to refuse it — and goes through the
+ * intersection's comparisons as it does there; (2) AVERAGE and DISCRETE_MIS pick ONE of the three plane types with probability 1/3 and still weight it by 1/3
+ * (or by a balance weight that sums to 1 over the types) while dividing by nb_primitive: they return a third of the radiance of the other strategies.
+ * Refused before any kernel: what rl_plane_generate refuses about the scene, with its codes; nb_primitive outside 1 .. RL_VPL_MAX, an unknown strategy, spp = 0,
+ * a bad shard (RL_ERR_INVALID_ARGUMENT); 256 * spp * D > 2^32 - 1, the jump-ahead's reach (RL_ERR_UNSUPPORTED).  Reference-order streams, exact numerics, one
+ * device, host output; shards as rl_render_bre.  Counters: camera_samples, extension_rays = camera_samples, shadow_rays = planes intersected, rng_draws =
+ * camera_samples * D + 2 * redraws, kernel_launches, ms_other = the kernel; reserved[0] = direction redraws, reserved[1] = planes intersected, reserved[2] = of
+ * those, visible. */
 typedef enum rl_plane_type { RL_PLANE_UV = 0, RL_PLANE_VT = 1, RL_PLANE_UT = 2, RL_PLANE_UALPHAT = 3 } rl_plane_type;
 typedef enum rl_plane_strategy { RL_PLANE_STRATEGY_UV = 0, RL_PLANE_STRATEGY_VT = 1, RL_PLANE_STRATEGY_UT = 2, RL_PLANE_STRATEGY_AVERAGE = 3,
                                  RL_PLANE_STRATEGY_DISCRETE_MIS = 4, RL_PLANE_STRATEGY_UALPHA = 5, RL_PLANE_STRATEGY_CMIS = 6 } rl_plane_strategy;
@@ -525,6 +543,8 @@ int rl_plane_tree_build_device(rl_context* ctx, const uint32_t* words, size_t n_
                                uint32_t* node_links, uint32_t* order);
 int rl_render_plane_single(rl_context* ctx, const rl_plane_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
                            const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
+int rl_render_plane_uncorrelated(rl_context* ctx, uint32_t nb_primitive, int strategy, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
+                                 const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
 
 /* Frames in flight behind one call (the progressive wrappers' passes, avg.rs:5-131 / equal_time.rs:4-66: N independent renders of one scene): frame f — block
  * seeds `block_seeds[f]`, host image `out_rgb[f]` (W*H*3 f32) — renders on `ctxs[f % k]` from host thread f % k, k = min(n_ctx, n_frames); `ctxs` are distinct

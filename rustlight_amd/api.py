@@ -48,7 +48,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -149,6 +149,7 @@ def lib():
     L.rl_plane_map_destroy.argtypes = [vp]
     L.rl_plane_map_destroy.restype = None
     L.rl_render_plane_single.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
+    L.rl_render_plane_uncorrelated.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
     for fn in (L.rl_render_ao, L.rl_render_direct):
         fn.argtypes = [vp, C.POINTER(abi.McParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_multi_create.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -625,6 +626,16 @@ class Context(_ImageCalls):
         return self._render_gather(lib().rl_render_plane_single, planes.h, seeds, spp, seed_variant, shard_index, shard_count,
                                    ("nodes_entered", "planes_intersected", "planes_visible"))
 
+    def render_plane_uncorrelated(self, seeds, nb_primitive=128, strategy="average", spp=1, seed_variant=0, shard_index=0, shard_count=1):
+        """IntegratorSinglePlaneUncorrelated behind its block seeds (uncorrelated_plane_single.rs:86-316) through rl_render_plane_uncorrelated: (image HxWx3 f32,
+        stats dict).  stats: redraws / planes_intersected / planes_visible = reserved[0..2], shadow_rays = planes_intersected, rng_draws = camera_samples * D +
+        2 * redraws, ms_other = the kernel."""
+        img, st = self._image_call(seeds, lambda sp, n, out, st: lib().rl_render_plane_uncorrelated(self.h, nb_primitive, plane_strategy(strategy), spp, seed_variant,
+                                                                                                    shard_index, shard_count, sp, n, out, st))
+        d = st.as_dict()
+        d.update((name, int(st.reserved[k])) for k, name in enumerate(("redraws", "planes_intersected", "planes_visible")))
+        return img, d
+
     def trace(self, origins, directions):
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
@@ -1038,6 +1049,22 @@ class IntegratorSinglePlane(_Integrator):
             if pmap is not None:
                 pmap.close()
             planes.close()
+        return img
+
+
+class IntegratorSinglePlaneUncorrelated(_Integrator):
+    """struct IntegratorSinglePlaneUncorrelated { nb_primitive, strategy } (src/integrators/explicit/uncorrelated_plane_single.rs:8-11) + Integrator::compute, seed
+    for seed the reference: the block seeds straight from the main sampler (:83), then every camera sample makes and gathers its own planes."""
+
+    def __init__(self, nb_primitive=128, strategy="average", device=0, options=None):
+        super().__init__(device, options)
+        self.nb_primitive, self.strategy = nb_primitive, PLANE_STRATEGIES[plane_strategy(strategy)]
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        ctx = self._context(scene)
+        w, h = scene.size
+        seeds = sampler.block_seeds(w, h)
+        img, self.last_stats = ctx.render_plane_uncorrelated(seeds, self.nb_primitive, self.strategy, nb_samples, sampler.variant)
         return img
 
 

@@ -18,6 +18,8 @@
 //                 kernels with no record leaving the GPU (rl_photon_map_build_device)
 //               | plane-single [-n|--nb-primitive N] [-s|--strategy uv|ut|vt|average|discrete_mis|ualpha|cmis]   (examples/cli.rs:197-202, 664-691; needs -m;
 //                 the limits of vol-primitivies: independent sampler, reference-order streams, exact numerics, one device, one pass)
+//                 --uncorrelated: IntegratorSinglePlaneUncorrelated (uncorrelated_plane_single.rs; the reference's subcommand `uncorrelated-plane-single`, cli.rs): every
+//                 camera sample makes its own N planes; the same options, limits and refusals
 // Note `-n` / `-m` / `-r` / `-s` mean spp / medium / sampler / scale before the subcommand and
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 #include <chrono>
@@ -84,6 +86,7 @@ int main(int argc, char** argv) {
     std::string light_streams = "reference";            // vpl, vol-primitivies: `--light-streams per-path` shoots the light paths in parallel, each on its own stream
     std::string tree_build = "host";                    // vol-primitivies: `--tree-build device` builds the photon tree on the GPU
     std::string plane_nb = "128", plane_strategy = "average";     // plane-single (cli.rs:197-202)
+    bool plane_uncorrelated = false;                              // plane-single --uncorrelated
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -158,6 +161,7 @@ int main(int argc, char** argv) {
         } else if (cmd == "plane-single") {
             if (a == "-n" || a == "--nb-primitive") plane_nb = val();
             else if (a == "-s" || a == "--strategy") plane_strategy = val();
+            else if (a == "--uncorrelated") plane_uncorrelated = true;
             else { std::fprintf(stderr, "unknown plane-single option %s\n", a.c_str()); return 2; }
         } else if (cmd == "light-tracing") {
             if (a == "-m" || a == "--max-depth") max_depth = val();
@@ -260,6 +264,8 @@ int main(int argc, char** argv) {
         plane.device = device;
         plane.options = options;
     }
+    IntegratorSinglePlaneUncorrelated uplane;
+    uplane.nb_primitive = plane.nb_primitive; uplane.strategy = plane.strategy; uplane.device = device; uplane.options = options;
     // the sampler (cli.rs:876-896): the master sampler that draws the block seeds is IndependentSampler(SEED) for both kinds — OS entropy without a seed, as
     // IndependentSampler::default() / StratifiedSampler's random() are; `stratified:SEED` is this drop-in's reproducible form.  stratified =
     // RL_STREAM_STRATIFIED: StratifiedSampler::create(spp, 4) on every pixel (include/rustlight_amd.h)
@@ -345,7 +351,8 @@ int main(int argc, char** argv) {
         } else if (cmd == "vol-primitivies") {
             img = volp.compute(sampler, *scene); elapsed_ms = volp.last_stats.render_ms;
         } else if (cmd == "plane-single") {
-            img = plane.compute(sampler, *scene); elapsed_ms = plane.last_stats.render_ms;
+            if (plane_uncorrelated) { img = uplane.compute(sampler, *scene); elapsed_ms = uplane.last_stats.render_ms; }
+            else { img = plane.compute(sampler, *scene); elapsed_ms = plane.last_stats.render_ms; }
         } else if (cmd == "light-tracing") {
             if (!equal_time.empty()) {
                 IntegratorEqualTime<IntegratorLightTracing> eq{light, std::strtod(equal_time.c_str(), nullptr) * 1000.0};

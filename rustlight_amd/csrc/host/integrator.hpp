@@ -402,6 +402,23 @@ struct IntegratorSinglePlane {
     }
 };
 
+// struct IntegratorSinglePlaneUncorrelated { nb_primitive, strategy } (src/integrators/explicit/uncorrelated_plane_single.rs:8-11) + Integrator::compute, seed for
+// seed the reference: the block seeds straight from the main sampler (:83), then every camera sample makes and gathers its own planes (rl_render_plane_uncorrelated).
+struct IntegratorSinglePlaneUncorrelated {
+    uint32_t nb_primitive = 128;
+    rl_plane_strategy strategy = RL_PLANE_STRATEGY_AVERAGE;
+    int device = 0;
+    Options options;
+    rl_render_stats last_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        RenderContext ctx(scene, device, options);
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        check(rl_render_plane_uncorrelated(ctx, nb_primitive, strategy, (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats),
+              "plane-single --uncorrelated");
+        return std::move(ctx.img);
+    }
+};
+
 // IntegratorAverage (src/integrators/avg.rs:5-131) and IntegratorEqualTime (src/integrators/equal_time.rs:4-66):
 // host loops around any inner integrator with `compute(IndependentSampler&, Scene&)`.
 template <class T, class = void> struct has_frames_in_flight : std::false_type {};

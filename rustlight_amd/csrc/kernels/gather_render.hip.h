@@ -1,7 +1,8 @@
 // gather_render.hip.h — the host side of the two integrators that gather along camera beams (included by wavefront.hip after rl_context, RenderFrame and the
 // launch helpers; host code only): the beam radiance estimate (rl_photon_map_*, rl_photon_tree_build_device, rl_render_bre) and the single-scattering photon
 // planes (rl_plane_*, rl_plane_map_*, rl_render_plane_single).  Both upload an element tree (host/photontree.h) in the gather's node format and render through
-// render_gather: one launch of beam_gather (gather.hip.h) over this shard's blocks.
+// render_gather: one launch of beam_gather (gather.hip.h) over this shard's blocks.  The uncorrelated photon planes (rl_render_plane_uncorrelated) have no tree
+// and a kernel of their own (uplane.hip.h), and go through render_gather for everything else.
 
 // an element tree -> its nodes in the gather's format (launch.h: BreConst::nodes)
 static std::vector<float4> pack_tree_nodes(const ElementTree& tree) {
@@ -35,6 +36,7 @@ struct GatherKind {
     int (*check_scene)(const rl_context*);
     int n_counters;                             // the leaf's walk counters (gather.hip.h) ...
     int lo[2], hi[2];                           // ... and the statistics rows of their low and high parts
+    uint64_t draws = 2;                         // draws per camera sample: the 256 lanes of a block enter its stream with 32-bit jumps
 };
 // rl_render_bre / rl_render_plane_single: the argument checks, the frame, one launch — launch(lds_scene, grid, lds_bytes, stream, rc, stc) — between two events,
 // the finish.  stats: reserved[0] = nodes entered, reserved[1 + k] = the leaf's counter k; extension rays and draws follow from the samples (one ray, 2 draws each)
@@ -47,6 +49,7 @@ static int render_gather(rl_context* ctx, const GatherKind& kind, const rl_conte
     if (map_ctx != ctx) { rl_set_error(std::string("the ") + kind.map + " belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
     if (shard_index >= (shard_count ? shard_count : 1)) return RL_ERR_INVALID_ARGUMENT;
     if (spp > (uint32_t)RL_VPL_MAX_SPP) { rl_set_error(std::string(kind.who) + " takes at most RL_VPL_MAX_SPP spp (a block's stream is entered with 32-bit jumps, 2 draws per sample)"); return RL_ERR_UNSUPPORTED; }
+    if (256ull * spp * kind.draws > 0xffffffffull) { rl_set_error(std::string(kind.who) + ": 256 * spp * (draws per sample) exceeds 2^32 - 1, the reach of the jumps a block's stream is entered with"); return RL_ERR_UNSUPPORTED; }
     HIP_OK(hipSetDevice(ctx->device));
     RenderFrame fr(ctx, block_seeds, n_blocks, out_rgb, 0, nullptr, stats, shard_index, shard_count);
     const unsigned n_owned = (unsigned)fr.owned.size();
@@ -528,5 +531,42 @@ extern "C" int rl_render_plane_single(rl_context* ctx, const rl_plane_map* map, 
         (lds_scene ? launch_plane_lds : launch_plane_stream)(mode, grid, dim3(256), lds, st, rc, ctx->ds, stc, pc);
     });
     if (rcode == RL_OK && stats) stats->shadow_rays = stats->reserved[1];      // reserved[1] = planes intersected, each of which takes a visibility ray; [2] = of those visible
+    return rcode;
+}
+
+// ---- IntegratorSinglePlaneUncorrelated (uncorrelated_plane_single.rs): no plane pass and no map — every camera sample makes its nb_primitive planes itself
+// (k_uplane, uplane.hip.h); the call uploads the rectangular lights and launches once.  reserved[0], the gather's nodes entered, carries the direction redraws.
+extern "C" int rl_render_plane_uncorrelated(rl_context* ctx, uint32_t nb_primitive, int strategy, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
+                                            const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats) {
+    if (!ctx) return RL_ERR_INVALID_ARGUMENT;
+    if (strategy < RL_PLANE_STRATEGY_UV || strategy > RL_PLANE_STRATEGY_CMIS) { rl_set_error("strategy must be one of RL_PLANE_STRATEGY_*"); return RL_ERR_INVALID_ARGUMENT; }
+    if (nb_primitive == 0 || nb_primitive > (uint32_t)RL_VPL_MAX) { rl_set_error("nb_primitive must be 1 .. RL_VPL_MAX"); return RL_ERR_INVALID_ARGUMENT; }
+    const bool pick = strategy == RL_PLANE_STRATEGY_AVERAGE || strategy == RL_PLANE_STRATEGY_DISCRETE_MIS;
+    const uint64_t draws = 2ull + (uint64_t)nb_primitive * (pick ? 8u : 7u);      // the jitter; per plane id_emitter, the type (Average / DiscreteMIS), plane_sample's 6
+    const GatherKind kind{"plane-single --uncorrelated", "context", check_plane_scene, 2, {STAT_PLANE_ISECT, STAT_PLANE_VISIBLE}, {STAT_PLANE_ISECT_HI, STAT_PLANE_VISIBLE_HI}, draws};
+    int rcode;
+    if ((rcode = check_frame(ctx, spp, block_seeds, n_blocks, out_rgb)) != RL_OK || (rcode = check_plane_scene(ctx)) != RL_OK) return rcode;
+    HIP_OK(hipSetDevice(ctx->device));
+    const std::vector<PlaneLight> lights = plane_lights(ctx);
+    HipBuffer<PlaneLight> d_lights;               // freed once render_gather has synchronised
+    if ((rcode = d_lights.ensure(lights.size())) != RL_OK) return rcode;
+    HIP_OK(hipMemcpy(d_lights.get(), lights.data(), lights.size() * sizeof(PlaneLight), hipMemcpyHostToDevice));
+    rcode = render_gather(ctx, kind, ctx, spp, seed_variant, shard_index, shard_count, block_seeds, n_blocks, out_rgb, stats,
+                          [&](bool lds_scene, dim3 grid, size_t lds, hipStream_t st, const RenderConst& rc, const StackConf& stc) {
+        UPlaneConst uc{};
+        uc.lights = d_lights.get(); uc.n_lights = (unsigned)lights.size();
+        uc.nb_primitive = nb_primitive; uc.draws = (unsigned)draws;
+        uc.pick_type = pick ? 1 : 0;
+        uc.type = strategy == RL_PLANE_STRATEGY_UV ? RL_PLANE_UV : strategy == RL_PLANE_STRATEGY_VT ? RL_PLANE_VT : strategy == RL_PLANE_STRATEGY_UT ? RL_PLANE_UT : RL_PLANE_UALPHAT;
+        uc.w = strategy == RL_PLANE_STRATEGY_AVERAGE ? 1.0f / 3.0f : 1.0f;
+        uc.n_lights_f = (float)lights.size();                                   // rect_lights.len() as f32
+        uc.inv_nb = 1.0f / (float)nb_primitive;                                 // 1.0 / self.nb_primitive as f32
+        const int mode = strategy == RL_PLANE_STRATEGY_DISCRETE_MIS ? PLANE_MODE_DISCRETE_MIS : strategy == RL_PLANE_STRATEGY_CMIS ? PLANE_MODE_CMIS : PLANE_MODE_PLAIN;
+        (lds_scene ? launch_uplane_lds : launch_uplane_stream)(mode, grid, dim3(256), lds, st, rc, ctx->ds, stc, uc);
+    });
+    if (rcode == RL_OK && stats) {
+        stats->shadow_rays = stats->reserved[1];                                // each plane the ray meets takes one visibility ray
+        stats->rng_draws = stats->camera_samples * draws + 2 * stats->reserved[0];
+    }
     return rcode;
 }

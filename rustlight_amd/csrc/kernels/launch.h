@@ -1,5 +1,5 @@
 // launch.h — host-side launchers of the kernel families that live in their own translation units (fused_*.hip, fusedq_*.hip, fused_strat_*.hip,
-// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, plane_*.hip), so that the families compile in parallel, and
+// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, plane_*.hip, uplane_*.hip), so that the families compile in parallel, and
 // the dispatcher every one of them maps its run-time arguments to template arguments with (with_bsdf, with_flag).  Launch errors are picked up by
 // the caller's hipGetLastError().
 #pragma once
@@ -125,6 +125,28 @@ struct PlaneConst {
     float inv_gen;                      // 1.0 / number_plane_gen as f32
 };
 
+// with_plane_mode(mode, f): f(std::integral_constant<int, MODE>{}) for MODE = PLANE_MODE_*
+template <class F>
+static void with_plane_mode(int mode, F&& f) {
+    if (mode == PLANE_MODE_DISCRETE_MIS) f(std::integral_constant<int, PLANE_MODE_DISCRETE_MIS>{});
+    else if (mode == PLANE_MODE_CMIS) f(std::integral_constant<int, PLANE_MODE_CMIS>{});
+    else f(std::integral_constant<int, PLANE_MODE_PLAIN>{});
+}
+// IntegratorSinglePlaneUncorrelated (uplane.hip.h): every camera sample makes its own nb_primitive planes.  Its statistics rows are the plane gather's, and the
+// direction redraws take the row of the nodes entered, which it has none of
+enum { STAT_UPLANE_REDRAWS = STAT_GATHER_NODES };
+struct UPlaneConst {
+    const PlaneLight* lights;
+    unsigned n_lights;
+    unsigned nb_primitive;
+    unsigned draws;                     // D: draws per camera sample without a redraw, 2 + nb_primitive * (7, or 8 when the plane type is drawn)
+    int pick_type;                      // Average / DiscreteMIS: one more draw per plane picks UV / VT / UT
+    unsigned type;                      // rl_plane_type of every plane otherwise
+    float w;                            // the strategy's constant weight: 1, or 1 / 3 for Average (DiscreteMIS computes its own)
+    float n_lights_f;                   // rect_lights.len() as f32
+    float inv_nb;                       // 1.0 / nb_primitive as f32
+};
+
 // mat: the scene's one BSDF type, or -1 = run-time switch per vertex.  area_only: every emitter is a mesh area light and there is no light
 // tree (the NEE code of the other emitter kinds is compiled out: same results, 84 -> 21 spilled VGPRs on the diffuse Cornell box)
 void launch_fused_lds(int mat, bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc);
@@ -175,6 +197,9 @@ void launch_plane_generate(hipStream_t st, const PlaneGenConst& gc);
 void launch_plane_generate_lanes(hipStream_t st, const PlaneGenConst& gc, unsigned n_gen);      // k_plane_generate_lanes: one lane per iteration, n_gen of them
 void launch_plane_lds(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PlaneConst& pc);
 void launch_plane_stream(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PlaneConst& pc);
+// IntegratorSinglePlaneUncorrelated (uplane.hip.h): k_uplane over the owned blocks, mode = PLANE_MODE_*
+void launch_uplane_lds(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const UPlaneConst& uc);
+void launch_uplane_stream(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const UPlaneConst& uc);
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)
 void dump_stage_timers_stream();
 void dump_chain_timers_lds();      // dev-only (-DRL_STAGE_TIMERS): cycle shares of k_stream_chain's stages

@@ -1,7 +1,8 @@
 // plane.hip.h — IntegratorSinglePlane (src/integrators/explicit/plane_single.rs): single scattering from rectangular area lights estimated with photon
 // planes.  The device pieces every plane integrator shares come first — SinglePhotonPlane::new, intersection, light_position, contrib and the weights of the
 // seven strategies —, then the gather kernel, instantiated by plane_lds.hip (scene staged in LDS) and plane_stream.hip (BVH streamed from L2 / HBM).  The
-// generation kernel (k_plane_generate, plane_generate.hip) is built from the same pieces.
+// generation kernels (k_plane_generate, k_plane_generate_lanes, plane_generate.hip) and the uncorrelated integrator (k_uplane, uplane.hip.h) are built from the same
+// pieces.
 //
 // The gather is beam_gather (gather.hip.h) over the leaf below, through the plane tree (host/planetree.cpp).  Plane: 4 float4 = o, length0 | d0, length1 |
 // d1, type + 4 * id_emitter | weight, 0; the weight is loaded for visible planes only.
@@ -57,6 +58,25 @@ RL_DEV Plane plane_new(unsigned type, const PlaneLight& l, V3 d, V2 sample, floa
     return p;
 }
 
+// generate_plane (plane_single.rs:326-361, uncorrelated_plane_single.rs:44-79) for a plane of type `type` on `light`: cosine_sample_hemisphere(next2d()), next() for the
+// medium's distance (HomogenousVolume::sample on Ray::new(light.o, d), volume.rs:95-135: continued_t, the distance sampled whatever the ray's tfar is), next2d() for
+// `sample`, next() for alpha, SinglePhotonPlane::new.  false, after the direction's 2 draws alone, when its z is 0: the reference draws the direction again, and so
+// does the caller — by calling again (the serial walks) or by giving the stream up (k_plane_generate_lanes).
+RL_DEV bool plane_sample(Rng& rng, unsigned type, const PlaneLight& light, Col sigma_t, Col sigma_s, Plane* p, V2* sample) {
+    const V3 d_out = cosine_sample_hemisphere(smp_next2d(rng));
+    if (d_out.z == 0.0f) return false;
+    const V3 d = to_world(make_frame(pl3(light.n)), d_out);
+    float xi = rng_next_f32(rng);
+    const float u3 = xi * 3.0f;
+    const int component = u3 != u3 ? 0 : (u3 <= 0.0f ? 0 : (u3 >= 255.0f ? 255 : (int)u3));   // `as u8`
+    xi = xi * 3.0f - (float)component;
+    const float t_sampled = div_rn(-m_logf(1.0f - xi), cget(sigma_t, component));
+    *sample = smp_next2d(rng);
+    const float alpha = rng_next_f32(rng);
+    *p = plane_new(type, light, d, *sample, alpha, t_sampled, sigma_s);
+    return true;
+}
+
 // BVHElement::intersection (plane_single.rs:121-160): the triangle test without its u + v <= 1.  The comparisons are the reference's, so a NaN passes where it
 // passes there.
 RL_DEV bool plane_intersect(V3 po, V3 d0, V3 d1, float l0, float l1, V3 ro, V3 rd, float tnear, float tfar, PlaneIts* its) {
@@ -107,6 +127,27 @@ RL_DEV float plane_w_cmis(const PlaneLight& l, V3 d1, V3 rd) {
 }
 
 // MODE: PLAIN = a run-time w (1 for UV / VT / UT / UAlpha, 1 / 3 for Average: 1.0 * rho is exact), DISCRETE_MIS, CMIS
+// What a plane the camera ray meets adds (plane_single.rs:463-596, uncorrelated_plane_single.rs:185-292): the point on the light, one visibility ray — false when it
+// is blocked —, then cs += w * rho * transmittance * sigma_s * flux * n_lights * inv_gen.  weight() is asked for visible planes only.
+template <int MODE, class STACK, class WEIGHT>
+RL_DEV bool plane_contribution(unsigned type, V3 po, V3 d0, V3 d1, const PlaneLight& light, const PlaneIts& its, V3 cam, V3 rd, const DeviceScene& sc, const SceneRecs& recs,
+                               const STACK& stack, float w, float n_lights_f, float inv_gen, WEIGHT&& weight_of, Col& cs) {
+    const V3 p_hit = cam + rd * its.t_cam;
+    const V3 p_light = plane_light_position(type, po, d0, light, its);
+    if (!shadow_visible(sc, recs, stack, p_hit, p_light)) return false;
+    const Col weight = weight_of();
+    const Col trans = medium_transmittance(sc.medium, its.t_cam);
+    const Col sigma_s = mkc(sc.medium.sigma_s[0], sc.medium.sigma_s[1], sc.medium.sigma_s[2]);
+    const Col rho = cval(div_rn(1.0f, kPi * 4.0f));                 // PhaseFunction::Isotropic(), whatever the medium's phase function is (plane_single.rs:440)
+    if (MODE == PLANE_MODE_DISCRETE_MIS) w = plane_discrete_mis(type, light, sigma_s, p_hit, p_light, rd);
+    Col flux;
+    if (MODE == PLANE_MODE_CMIS) flux = plane_w_cmis(light, d1, rd) * weight;
+    else flux = plane_contrib(weight, d0, d1, rd);
+    // c += w * rho * transmittance * sigma_s * flux * (emitters.len() as f32) * (1.0 / number_plane_gen as f32)
+    cs = cs + (((((w * rho) * trans) * sigma_s) * flux) * n_lights_f) * inv_gen;
+    return true;
+}
+
 template <int MODE>
 struct PlaneLeaf {
     PlaneConst c;
@@ -121,23 +162,8 @@ struct PlaneLeaf {
         if (!plane_intersect(po, d0, d1, q0.w, q1.w, cam, rd, kEps, tfar, &its)) return;
         n[0]++;
         const unsigned tb = __float_as_uint(q2.w), type = tb & 3u;
-        const PlaneLight& light = c.lights[tb >> 2];
-        const V3 p_hit = cam + rd * its.t_cam;
-        const V3 p_light = plane_light_position(type, po, d0, light, its);
-        if (!shadow_visible(sc, recs, stack, p_hit, p_light)) return;
-        n[1]++;
-        const float4 q3 = pl[3];
-        const Col weight = mkc(q3.x, q3.y, q3.z);
-        const Col trans = medium_transmittance(sc.medium, its.t_cam);
-        const Col sigma_s = mkc(sc.medium.sigma_s[0], sc.medium.sigma_s[1], sc.medium.sigma_s[2]);
-        const Col rho = cval(div_rn(1.0f, kPi * 4.0f));                 // PhaseFunction::Isotropic(), whatever the medium's phase function is (plane_single.rs:440)
-        float w = c.w;
-        if (MODE == PLANE_MODE_DISCRETE_MIS) w = plane_discrete_mis(type, light, sigma_s, p_hit, p_light, rd);
-        Col flux;
-        if (MODE == PLANE_MODE_CMIS) flux = plane_w_cmis(light, d1, rd) * weight;
-        else flux = plane_contrib(weight, d0, d1, rd);
-        // c += w * rho * transmittance * sigma_s * flux * (emitters.len() as f32) * (1.0 / number_plane_gen as f32)
-        cs = cs + (((((w * rho) * trans) * sigma_s) * flux) * c.n_lights_f) * c.inv_gen;
+        if (plane_contribution<MODE>(type, po, d0, d1, c.lights[tb >> 2], its, cam, rd, sc, recs, stack, c.w, c.n_lights_f, c.inv_gen,
+                                     [&]() { const float4 q3 = pl[3]; return mkc(q3.x, q3.y, q3.z); }, cs)) n[1]++;
     }
 };
 

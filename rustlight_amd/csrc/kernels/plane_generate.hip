@@ -30,21 +30,10 @@ __global__ void __launch_bounds__(64) k_plane_generate(PlaneGenConst gc) {
         const PlaneLight& light = gc.lights[id];
         for (unsigned k = 0; k < (three ? 3u : 1u); k++) {
             const unsigned type = three ? (k == 0 ? RL_PLANE_UV : k == 1 ? RL_PLANE_VT : RL_PLANE_UT) : single;
-            // generate_plane (326-361)
-            V3 d_out = cosine_sample_hemisphere(smp_next2d(rng));
-            n_draws += 2;
-            while (d_out.z == 0.0f) { d_out = cosine_sample_hemisphere(smp_next2d(rng)); n_draws += 2; }
-            const V3 d = to_world(make_frame(pl3(light.n)), d_out);
-            // HomogenousVolume::sample on Ray::new(light.o, d) (volume.rs:95-135): continued_t, the distance sampled whatever the ray's tfar is
-            float xi = rng_next_f32(rng);
-            const float u3 = xi * 3.0f;
-            const int component = u3 != u3 ? 0 : (u3 <= 0.0f ? 0 : (u3 >= 255.0f ? 255 : (int)u3));   // `as u8`
-            xi = xi * 3.0f - (float)component;
-            const float t_sampled = div_rn(-m_logf(1.0f - xi), cget(sigma_t, component));
-            const V2 sample = smp_next2d(rng);
-            const float alpha = rng_next_f32(rng);
-            n_draws += 4;
-            const Plane p = plane_new(type, light, d, sample, alpha, t_sampled, sigma_s);
+            // generate_plane (326-361): the direction is drawn again while its z is 0
+            Plane p; V2 sample;
+            while (!plane_sample(rng, type, light, sigma_t, sigma_s, &p, &sample)) n_draws += 2;
+            n_draws += 6;
             if (n_planes < gc.cap) {
                 unsigned* w = gc.words + (size_t)n_planes * RL_PLANE_WORDS;
                 w[0] = __float_as_uint(p.o.x); w[1] = __float_as_uint(p.o.y); w[2] = __float_as_uint(p.o.z);
@@ -63,22 +52,12 @@ __global__ void __launch_bounds__(64) k_plane_generate(PlaneGenConst gc) {
     gc.gen_out[PLANE_GEN_PLANES] = n_planes; gc.gen_out[PLANE_GEN_ITERATIONS] = n_gen; gc.gen_out[PLANE_GEN_DRAWS] = n_draws;
 }
 
-// One plane of the lane-parallel form, the text of k_plane_generate's inner loop without its redraw: generate_plane (326-361) for a plane of type `type` from
-// light `id`, stored at `index`.  false, and nothing stored, when the direction's z is 0 (the serial walk draws it again).
+// One plane of the lane-parallel form: plane_sample for a plane of type `type` from light `id`, stored at `index`.  false, and nothing stored, when the
+// direction's z is 0 (the serial walk draws it again).
 RL_DEV bool plane_lane_one(const PlaneGenConst& gc, Rng& rng, unsigned type, unsigned id, unsigned index, Plane* made) {
-    const PlaneLight& light = gc.lights[id];
     const Col sigma_t = mkc(gc.sigma_t[0], gc.sigma_t[1], gc.sigma_t[2]), sigma_s = mkc(gc.sigma_s[0], gc.sigma_s[1], gc.sigma_s[2]);
-    const V3 d_out = cosine_sample_hemisphere(smp_next2d(rng));
-    if (d_out.z == 0.0f) return false;
-    const V3 d = to_world(make_frame(pl3(light.n)), d_out);
-    float xi = rng_next_f32(rng);
-    const float u3 = xi * 3.0f;
-    const int component = u3 != u3 ? 0 : (u3 <= 0.0f ? 0 : (u3 >= 255.0f ? 255 : (int)u3));   // `as u8`
-    xi = xi * 3.0f - (float)component;
-    const float t_sampled = div_rn(-m_logf(1.0f - xi), cget(sigma_t, component));
-    const V2 sample = smp_next2d(rng);
-    const float alpha = rng_next_f32(rng);
-    const Plane p = plane_new(type, light, d, sample, alpha, t_sampled, sigma_s);
+    Plane p; V2 sample;
+    if (!plane_sample(rng, type, gc.lights[id], sigma_t, sigma_s, &p, &sample)) return false;
     unsigned* w = gc.words + (size_t)index * RL_PLANE_WORDS;
     w[0] = __float_as_uint(p.o.x); w[1] = __float_as_uint(p.o.y); w[2] = __float_as_uint(p.o.z);
     w[3] = __float_as_uint(p.d0.x); w[4] = __float_as_uint(p.d0.y); w[5] = __float_as_uint(p.d0.z);
