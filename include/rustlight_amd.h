@@ -419,7 +419,7 @@ int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_path_params* 
                   float* out_rgb, int out_is_device, void* stream, rl_render_stats* stats);
 
 /* ---- IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: BRE } (src/integrators/explicit/vol_primitives.rs; CLI `vol-primitivies -p bre`,
- * examples/cli.rs:189-196, 692-716): the beam radiance estimate.  Beams, planes and VRL are not built.
+ * examples/cli.rs:189-196, 692-716): the beam radiance estimate.  Planes and VRL are not built; beams have entry points of their own (rl_beam_*, below).
  * The photons are the records of a set generated by rl_vpl_generate with option_vpl = RL_VPL_VOLUME and nb_vpl = nb_primitive: convert_photons
  * (vol_primitives.rs:525-565) stores at every Vertex::Volume what convert_vpl stores under `-v volume`, from the same light paths, and the shooting stops on the
  * same count — words 4..6 = pos, 7..9 = radiance, 10..12 = d_in; the set's path count is nb_path_shot.
@@ -462,6 +462,54 @@ int rl_photon_map_build_device(rl_context* ctx, const rl_vpl_set* set, float rad
 int rl_photon_tree_build_device(rl_context* ctx, const uint32_t* words, size_t n_photons, float radius, size_t node_capacity, size_t* n_nodes, float* node_boxes,
                                 uint32_t* node_links, uint32_t* order);
 int rl_photon_map_read(const rl_photon_map* map, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t photon_capacity, float* photons);
+
+/* ---- Photon beams: IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: Beams } (src/integrators/explicit/vol_primitives.rs), behind entry
+ * points and a CLI word (`photon-beams`) of their own: `vol-primitivies -p beam` stays refused with the other unbuilt primitives.
+ * rl_beam_generate (vol_primitives.rs:437-523, 608-630): the light paths of rl_vpl_generate — Path::from_light, `generate` with max_depth / rr_depth and
+ * DirectionalSamplingStrategy { Radiance }, the same draws in the same order on the main sampler, seed for seed — stored by convert_beams(false, ..) while
+ * fewer than nb_primitive beams are stored (every beam of the last path is kept).  A beam is a traced edge that ends in a vertex; with a medium every traced
+ * edge does (src/paths/edge.rs:90-126), so a path stores one beam per extension ray.  nb_primitive is 1 .. RL_BEAM_MAX (the split below makes at most about 6
+ * sub-beams per beam, and the tree takes RL_VPL_MAX + 4096 elements).  Refused with rl_vpl_generate(RL_VPL_VOLUME)'s codes: a scene without a medium, with an
+ * environment emitter or a directional light (RL_ERR_UNSUPPORTED), without an emitter (RL_ERR_NO_EMITTER), max_depth <= 1, nb_primitive out of range
+ * (RL_ERR_INVALID_ARGUMENT); RL_ERR_UNSUPPORTED when RL_VPL_MAX_PATHS paths store fewer beams than asked.  Counters and the sampler on return: rl_vpl_generate's.
+ * rl_beam_generate_paths: the same pass with one light path per device lane under rl_vpl_generate_paths' stream contract (path k on the k-th clone_box; a
+ * count pass, then a write pass; records in path order and in vertex order within a path; `sampler` advanced by K next_u64()); its counters.
+ * rl_beam_read: RL_BEAM_WORDS u32 per beam in storing order (f32 fields as their bits): [0..2] o, the position of the vertex the edge leaves, [3] length =
+ * edge.dist (the sampled medium distance where the path scattered, the hit distance otherwise), [4..6] d, the edge's direction, [7] bit 0 = from_surface (o is
+ * the light vertex or a surface vertex), [8..10] radiance, the flux that reached o (before this edge's weight * rr_weight, :453-520), [11] the path's index
+ * within the generation.  n_words must be n_beams * RL_BEAM_WORDS.  A beam's phase function is Isotropic whatever the medium's is (:457, 483, 500): kept.
+ * rl_beam_split (vol_primitives.rs:647-684), the host part alone, no GPU: SPLIT = 5, avg_split = (the lengths summed in f32 in record order) / (n * 5) as f32,
+ * a beam yields ceil(length / avg_split) as u32 sub-beams of new_length = length / that count, sub-beam i starting at o + d * (i as f32) * new_length; a beam of
+ * length 0 yields none.  Sub-beams are records of the same layout in beam order.  With sub_words NULL only *n_sub is written; `capacity` is in records.
+ * RL_ERR_INVALID_ARGUMENT for a non-finite o, d or length and for an avg_split that is zero or not finite, RL_ERR_UNSUPPORTED when the split makes more than
+ * RL_VPL_MAX + 4096 sub-beams.
+ * rl_beam_tree_build (vol_primitives.rs:123-136, 686-699), no GPU, rl_photon_tree_build's calling convention over sub-beam records: box = the union of
+ * o - r, o + r, (o + d * length) - r, (o + d * length) + r, sort key = o + d * length * 0.5, otherwise rl_photon_map_build's tree with its two deliberate
+ * differences (a stable sort; a non-finite record or box is RL_ERR_INVALID_ARGUMENT).
+ * rl_beam_map_build: split, tree, upload (the tree and the sub-beams in leaf order as 48-byte records o, length | d, 0 | radiance, 0).  `radius` as for
+ * rl_photon_map_build; the set must come from the same context.  rl_beam_map_build_words: the same from caller-supplied beam records; n_paths >= 1 stands for
+ * nb_path_shot.  rl_beam_map_read: node_boxes / node_links as rl_photon_map_read writes them, beams [n_sub][12] f32 in leaf order.
+ * rl_render_beams (vol_primitives.rs:140-199, 705-790): rl_render_bre's camera loop, streams, shards, refusals and counters over the beam tree; per sub-beam
+ * PhotonBeam::intersection statement by statement (tnear = 1e-4) and c += radiance * transmittance(w) * (sigma_s * 1 / (4 PI)) * ((1 / sin_theta) * (0.5 /
+ * radius)) * (1 / nb_path_shot) in gather order.  reserved[0] = beam-tree nodes entered, reserved[1] = beams accepted. */
+enum { RL_BEAM_WORDS = 12, RL_BEAM_MAX = 1 << 17 };
+typedef struct rl_beam_set rl_beam_set;         /* opaque: the beams of one generation, on the context's device */
+typedef struct rl_beam_map rl_beam_map;         /* opaque: beam tree and sub-beams, on the context's device */
+int rl_beam_generate(rl_context* ctx, const rl_path_params* params, uint32_t nb_primitive, rl_sampler* sampler, rl_beam_set** out, rl_render_stats* stats);
+int rl_beam_generate_paths(rl_context* ctx, const rl_path_params* params, uint32_t nb_primitive, rl_sampler* sampler, rl_beam_set** out, rl_render_stats* stats);
+int rl_beam_info(const rl_beam_set* set, uint64_t* n_beams, uint64_t* n_paths);
+int rl_beam_read(const rl_beam_set* set, uint32_t* words, size_t n_words);
+void rl_beam_destroy(rl_beam_set* set);
+int rl_beam_split(const uint32_t* words, size_t n_beams, size_t capacity, size_t* n_sub, uint32_t* sub_words);
+int rl_beam_tree_build(const uint32_t* sub_words, size_t n_sub, float radius, size_t node_capacity, size_t* n_nodes, float* node_boxes, uint32_t* node_links,
+                       uint32_t* order);
+int rl_beam_map_build(rl_context* ctx, const rl_beam_set* set, float radius, rl_beam_map** out);
+int rl_beam_map_build_words(rl_context* ctx, const uint32_t* words, size_t n_beams, uint64_t n_paths, float radius, rl_beam_map** out);
+int rl_beam_map_info(const rl_beam_map* map, uint64_t* n_beams, uint64_t* n_sub, uint64_t* n_nodes, uint64_t* n_paths, float* radius);
+int rl_beam_map_read(const rl_beam_map* map, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t beam_capacity, float* beams);
+void rl_beam_map_destroy(rl_beam_map* map);
+int rl_render_beams(rl_context* ctx, const rl_beam_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
+                    const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
 
 /* ---- IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs; CLI `plane-single`, examples/cli.rs:197-202, 664-691): single
  * scattering from rectangular area lights, estimated with photon planes under one of seven sampling strategies.

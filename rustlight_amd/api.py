@@ -34,6 +34,8 @@ VPL_WORDS = 24                                            # RL_VPL_WORDS: u32 pe
 TREE_BUILDS = ("host", "device")                          # where the photon tree of vol-primitivies is built: rl_photon_map_build | rl_photon_map_build_device
 PHOTON_TREE_GROUP_PHOTONS = 2048                          # RL_PHOTON_TREE_GROUP_PHOTONS: photons one workgroup of the device build finishes in LDS
 PHOTON_RADIUS_DEFAULT = 0.001                             # RL_PHOTON_RADIUS_DEFAULT: the radius the reference hard-codes (vol_primitives.rs:618)
+BEAM_WORDS = 12                                           # RL_BEAM_WORDS: u32 per beam record (rl_beam_read)
+BEAM_MAX = 1 << 17                                        # RL_BEAM_MAX: the most beams a beam pass is asked for
 PLANE_FORMS = ("serial", "lanes")                         # how the plane pass of plane-single runs: rl_plane_generate | rl_plane_generate_lanes
 PLANE_TREE_GROUP_PLANES = 1024                            # RL_PLANE_TREE_GROUP_PLANES: planes one workgroup of the device build finishes in LDS
 PLANE_WORDS = 18                                          # RL_PLANE_WORDS: u32 per plane record (rl_plane_read)
@@ -48,7 +50,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -134,6 +136,21 @@ def lib():
     L.rl_photon_map_build_device.argtypes = [vp, vp, C.c_float, C.POINTER(vp), f32p]
     L.rl_photon_tree_build_device.argtypes = [vp, u32p, C.c_size_t, C.c_float, C.c_size_t, C.POINTER(C.c_size_t), f32p, u32p, u32p]
     L.rl_photon_map_read.argtypes = [vp, C.c_size_t, f32p, u32p, C.c_size_t, f32p]
+    L.rl_beam_generate.argtypes = [vp, C.POINTER(abi.PathParams), C.c_uint32, C.POINTER(abi.Sampler), C.POINTER(vp), C.POINTER(abi.RenderStats)]
+    L.rl_beam_generate_paths.argtypes = L.rl_beam_generate.argtypes
+    L.rl_beam_info.argtypes = [vp, u64p, u64p]
+    L.rl_beam_read.argtypes = [vp, u32p, C.c_size_t]
+    L.rl_beam_destroy.argtypes = [vp]
+    L.rl_beam_destroy.restype = None
+    L.rl_beam_split.argtypes = [u32p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), u32p]
+    L.rl_beam_tree_build.argtypes = [u32p, C.c_size_t, C.c_float, C.c_size_t, C.POINTER(C.c_size_t), f32p, u32p, u32p]
+    L.rl_beam_map_build.argtypes = [vp, vp, C.c_float, C.POINTER(vp)]
+    L.rl_beam_map_build_words.argtypes = [vp, u32p, C.c_size_t, C.c_uint64, C.c_float, C.POINTER(vp)]
+    L.rl_beam_map_info.argtypes = [vp, u64p, u64p, u64p, u64p, f32p]
+    L.rl_beam_map_read.argtypes = [vp, C.c_size_t, f32p, u32p, C.c_size_t, f32p]
+    L.rl_beam_map_destroy.argtypes = [vp]
+    L.rl_beam_map_destroy.restype = None
+    L.rl_render_beams.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
     L.rl_plane_generate.argtypes = [vp, C.c_uint32, C.c_int, C.POINTER(abi.Sampler), C.POINTER(vp), C.POINTER(abi.RenderStats)]
     L.rl_plane_info.argtypes = [vp, u64p, u64p, C.POINTER(C.c_int)]
     L.rl_plane_read.argtypes = [vp, u32p, C.c_size_t]
@@ -586,6 +603,41 @@ class Context(_ImageCalls):
         photons_gathered = reserved[0] / reserved[1], ms_other = the gather kernel."""
         return self._render_gather(lib().rl_render_bre, photons.h, seeds, spp, seed_variant, shard_index, shard_count, ("nodes_entered", "photons_gathered"))
 
+    def beam_generate(self, sampler: "IndependentSampler", nb_primitive=128, max_depth=None, rr_depth=0, streams="reference"):
+        """The photon beams' beam pass (vol_primitives.rs:437-523, 608-630): (BeamSet, stats dict).  streams="reference": rl_beam_generate, one lane on the main
+        sampler's serial stream, seed for seed the reference; streams="per_path": rl_beam_generate_paths under rl_vpl_generate_paths' stream contract.  `sampler`
+        and the stats follow Context.vpl_generate's rules."""
+        if streams not in LIGHT_STREAMS:
+            raise ValueError(f"streams must be one of {LIGHT_STREAMS}, not {streams!r}")
+        p = path_params(1, 0, max_depth, rr_depth, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=sampler.variant)
+        st = abi.RenderStats()
+        h = C.c_void_p()
+        fn = lib().rl_beam_generate if streams == "reference" else lib().rl_beam_generate_paths
+        _check(fn(self.h, C.byref(p), nb_primitive, C.byref(sampler.s), C.byref(h), C.byref(st)))
+        d = st.as_dict()
+        if streams == "per_path":
+            d["paths_walked"] = int(st.reserved[0])
+        return BeamSet(h, self), d
+
+    def beam_map(self, beams: "BeamSet", radius=PHOTON_RADIUS_DEFAULT):
+        """rl_beam_map_build: the beams of a set split into sub-beams and sorted into the beam tree on the host, uploaded.  radius: the reference hard-codes
+        PHOTON_RADIUS_DEFAULT."""
+        h = C.c_void_p()
+        _check(lib().rl_beam_map_build(self.h, beams.h, radius, C.byref(h)))
+        return BeamMap(h, self)
+
+    def beam_map_from_words(self, words, n_paths, radius=PHOTON_RADIUS_DEFAULT):
+        """rl_beam_map_build_words: Context.beam_map over caller-supplied beam records ([n, BEAM_WORDS] u32) of n_paths light paths."""
+        w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, BEAM_WORDS)
+        h = C.c_void_p()
+        _check(lib().rl_beam_map_build_words(self.h, abi.u32ptr(w), w.shape[0], n_paths, radius, C.byref(h)))
+        return BeamMap(h, self)
+
+    def render_beams(self, beams: "BeamMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
+        """The photon beams' gather (vol_primitives.rs:140-199, 705-790) through rl_render_beams: (image HxWx3 f32, stats dict).  stats: nodes_entered /
+        beams_accepted = reserved[0] / reserved[1], ms_other = the gather kernel."""
+        return self._render_gather(lib().rl_render_beams, beams.h, seeds, spp, seed_variant, shard_index, shard_count, ("nodes_entered", "beams_accepted"))
+
     def plane_generate(self, sampler: "IndependentSampler", nb_primitive=128, strategy="average", form="serial"):
         """IntegratorSinglePlane's plane pass (plane_single.rs:363-427) through rl_plane_generate: (PlaneSet, stats dict).  `sampler` is advanced as the
         reference's main sampler is.  stats: camera_samples = iterations (number_plane_gen), vertices = planes, rng_draws, ms_prepass = the kernel.
@@ -959,6 +1011,97 @@ class IntegratorVolPrimitives(_Integrator):
             if photons is not None:
                 photons.close()
             vpls.close()
+        return img
+
+
+class BeamSet(_DeviceHandle):
+    """rl_beam_set: the beams of one beam pass, on the device of the context that made them (kept alive with it)."""
+    _destroy = "rl_beam_destroy"
+
+    def info(self):
+        """(beams stored, light paths shot)."""
+        n, p = C.c_uint64(), C.c_uint64()
+        _check(lib().rl_beam_info(self.h, C.byref(n), C.byref(p)))
+        return int(n.value), int(p.value)
+
+    def __len__(self):
+        return self.info()[0]
+
+    def words(self) -> np.ndarray:
+        """The raw records, [n_beams, BEAM_WORDS] u32 (layout: include/rustlight_amd.h, rl_beam_read)."""
+        w = np.zeros((self.info()[0], BEAM_WORDS), np.uint32)
+        _check(lib().rl_beam_read(self.h, abi.u32ptr(w), w.size))
+        return w
+
+    def records(self) -> np.ndarray:
+        """The records as a numpy structured array: o, length, d, flags (bit 0 = from_surface), radiance, path."""
+        return self.words().view(BEAM_RECORD_DTYPE).reshape(-1)
+
+
+BEAM_RECORD_DTYPE = np.dtype([("o", "<f4", 3), ("length", "<f4"), ("d", "<f4", 3), ("flags", "<u4"), ("radiance", "<f4", 3), ("path", "<u4")])
+assert BEAM_RECORD_DTYPE.itemsize == 4 * BEAM_WORDS
+
+
+class BeamMap(_DeviceHandle):
+    """rl_beam_map: beam tree and sub-beams of one beam pass, on the device of the context that made them (kept alive with it)."""
+    _destroy = "rl_beam_map_destroy"
+
+    def info(self):
+        """(beams, sub-beams, tree nodes, light paths shot, radius)."""
+        n, s_, m, p, r = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _check(lib().rl_beam_map_info(self.h, C.byref(n), C.byref(s_), C.byref(m), C.byref(p), C.byref(r)))
+        return int(n.value), int(s_.value), int(m.value), int(p.value), float(r.value)
+
+    def read(self):
+        """rl_beam_map_read: (boxes [n, 6] f32, links [n, 3] u32 = skip, first, count, beams [n_sub, 12] f32 = o, length | d, 0 | radiance, 0 in leaf order)."""
+        _, n_sub, n_nodes, _, _ = self.info()
+        boxes, links, beams = np.zeros((n_nodes, 6), np.float32), np.zeros((n_nodes, 3), np.uint32), np.zeros((n_sub, 12), np.float32)
+        _check(lib().rl_beam_map_read(self.h, n_nodes, abi.fptr(boxes), abi.u32ptr(links), n_sub, abi.fptr(beams)))
+        return boxes, links, beams
+
+
+def beam_split(words):
+    """rl_beam_split, host only: the sub-beams ([n_sub, BEAM_WORDS] u32, in beam order) of beam records `words` ([n, BEAM_WORDS] u32)."""
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, BEAM_WORDS)
+    n = C.c_size_t()
+    _check(lib().rl_beam_split(abi.u32ptr(w), w.shape[0], 0, C.byref(n), None))
+    sub = np.zeros((n.value, BEAM_WORDS), np.uint32)
+    _check(lib().rl_beam_split(abi.u32ptr(w), w.shape[0], n.value, C.byref(n), abi.u32ptr(sub)))
+    return sub
+
+
+def beam_tree_build(sub_words, radius):
+    """rl_beam_tree_build, host only: photon_tree_build's arrays for the beam tree over sub-beam records ([n_sub, BEAM_WORDS] u32)."""
+    w = np.ascontiguousarray(sub_words, dtype=np.uint32).reshape(-1, BEAM_WORDS)
+    return _tree_arrays(lambda *out: lib().rl_beam_tree_build(abi.u32ptr(w), w.shape[0], radius, *out), w.shape[0])
+
+
+class IntegratorPhotonBeams(_Integrator):
+    """IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: Beams } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute, seed
+    for seed the reference: the beams from the main sampler, the split, the beam tree, the block seeds from the sampler the beam pass leaves, the gather on
+    reference-order streams.  A class of its own: IntegratorVolPrimitives keeps refusing every primitive but bre.  radius: the reference's constant unless
+    given.  light_streams="per_path": the beams from rl_beam_generate_paths: statistically, not seed-for-seed, the same image."""
+
+    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, radius=PHOTON_RADIUS_DEFAULT, light_streams="reference", device=0, options=None):
+        if light_streams not in LIGHT_STREAMS:
+            raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
+        super().__init__(device, options)
+        self.nb_primitive, self.max_depth, self.rr_depth, self.radius, self.light_streams = nb_primitive, max_depth, rr_depth, radius, light_streams
+        self.last_generation_stats = None
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        ctx = self._context(scene)
+        beams, self.last_generation_stats = ctx.beam_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, self.light_streams)
+        bmap = None
+        try:
+            bmap = ctx.beam_map(beams, self.radius)
+            w, h = scene.size
+            seeds = sampler.block_seeds(w, h)
+            img, self.last_stats = ctx.render_beams(bmap, seeds, nb_samples, sampler.variant)
+        finally:
+            if bmap is not None:
+                bmap.close()
+            beams.close()
         return img
 
 

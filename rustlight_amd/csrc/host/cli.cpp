@@ -16,6 +16,9 @@
 //                 per-path = one light path per GPU lane, each on its own stream (rl_vpl_generate_paths): statistically, not seed-for-seed, the same image
 //                 --tree-build (vol-primitivies): host = the photon tree built on the host (default); device = the same tree, byte for byte, built by device
 //                 kernels with no record leaving the GPU (rl_photon_map_build_device)
+//               | photon-beams [-m MAX|inf] [-n MIN] [-r RR|inf] [--nb-primitive N] [--radius R] [--light-streams reference|per-path]   (IntegratorVolPrimitives with
+//                 primitives = Beams, vol_primitives.rs; a subcommand of its own: `vol-primitivies -p beam` stays refused with the other unbuilt primitives.  The
+//                 options and limits of vol-primitivies; N is 1 .. RL_BEAM_MAX; no --tree-build: the split and the beam tree are built on the host)
 //               | plane-single [-n|--nb-primitive N] [-s|--strategy uv|ut|vt|average|discrete_mis|ualpha|cmis]   (examples/cli.rs:197-202, 664-691; needs -m;
 //                 the limits of vol-primitivies: independent sampler, reference-order streams, exact numerics, one device, one pass)
 //                 --uncorrelated: IntegratorSinglePlaneUncorrelated (uncorrelated_plane_single.rs; the reference's subcommand `uncorrelated-plane-single`, cli.rs): every
@@ -93,7 +96,7 @@ int main(int argc, char** argv) {
         if (!have_cmd) {
             if (a == "path" || a == "ao" || a == "direct" || a == "light-tracing" || a == "vpl") { have_cmd = true; cmd = a; }
             else if (a == "vol-primitivies" || a == "vol-primitives") { have_cmd = true; cmd = "vol-primitivies"; }
-            else if (a == "plane-single") { have_cmd = true; cmd = a; }
+            else if (a == "plane-single" || a == "photon-beams") { have_cmd = true; cmd = a; }
             else if (a == "-n" || a == "--nbsamples") nbsamples = std::strtoull(val().c_str(), nullptr, 10);
             else if (a == "-o" || a == "--output") output = val();
             else if (a == "-r" || a == "--random-number-generator") rng = val();
@@ -121,13 +124,13 @@ int main(int argc, char** argv) {
                 else { std::fprintf(stderr, "extra option %s is not supported by this drop-in (ats, no-shading, hvs-light, texture-light)\n", o.c_str()); return 2; }
             }
             else if (a == "-l" || a == "--log") (void)val();   // log file: nothing is logged on this path
-            else if (a == "--light-streams") { std::fprintf(stderr, "--light-streams is an option of the vpl and vol-primitivies subcommands: give it after the subcommand\n"); return 2; }
+            else if (a == "--light-streams") { std::fprintf(stderr, "--light-streams is an option of the vpl, vol-primitivies and photon-beams subcommands: give it after the subcommand\n"); return 2; }
             else if (a == "--tree-build") { std::fprintf(stderr, "--tree-build is an option of the vol-primitivies subcommand: give it after the subcommand\n"); return 2; }
             else if (a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
             else if (scene_path.empty()) scene_path = a;
-            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl`, `vol-primitivies` and `plane-single` subcommands are provided (got %s)\n", a.c_str()); return 2; }
-        } else if (a == "--light-streams" && cmd != "vpl" && cmd != "vol-primitivies") {
-            std::fprintf(stderr, "%s: --light-streams is not supported (vpl and vol-primitivies only)\n", cmd.c_str()); return 2;
+            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl`, `vol-primitivies`, `photon-beams` and `plane-single` subcommands are provided (got %s)\n", a.c_str()); return 2; }
+        } else if (a == "--light-streams" && cmd != "vpl" && cmd != "vol-primitivies" && cmd != "photon-beams") {
+            std::fprintf(stderr, "%s: --light-streams is not supported (photon-beams, vpl and vol-primitivies only)\n", cmd.c_str()); return 2;
         } else if (a == "--tree-build" && cmd != "vol-primitivies") {
             std::fprintf(stderr, "%s: --tree-build is not supported (vol-primitivies only)\n", cmd.c_str()); return 2;
         } else if (cmd == "ao") {
@@ -158,6 +161,14 @@ int main(int argc, char** argv) {
             else if (a == "--light-streams") light_streams = val();
             else if (a == "--tree-build") tree_build = val();
             else { std::fprintf(stderr, "unknown vol-primitivies option %s\n", a.c_str()); return 2; }
+        } else if (cmd == "photon-beams") {
+            if (a == "-m" || a == "--max-depth") max_depth = val();
+            else if (a == "-n" || a == "--min-depth") (void)val();          // `_min_depth` (cli.rs:697): never read
+            else if (a == "-r" || a == "--rr-depth") rr_depth = val();
+            else if (a == "--nb-primitive") nb_primitive = val();
+            else if (a == "--radius") radius = val();
+            else if (a == "--light-streams") light_streams = val();
+            else { std::fprintf(stderr, "unknown photon-beams option %s\n", a.c_str()); return 2; }
         } else if (cmd == "plane-single") {
             if (a == "-n" || a == "--nb-primitive") plane_nb = val();
             else if (a == "-s" || a == "--strategy") plane_strategy = val();
@@ -208,9 +219,9 @@ int main(int argc, char** argv) {
         light.device = device;
         light.options = options;
     }
-    // vpl, vol-primitivies: how the light paths draw (the gather stays in reference order either way)
+    // vpl, vol-primitivies, photon-beams: how the light paths draw (the gather stays in reference order either way)
     LightStreams light_streams_mode = LightStreams::Reference;
-    if (cmd == "vpl" || cmd == "vol-primitivies") {
+    if (cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams") {
         if (light_streams == "per-path") light_streams_mode = LightStreams::PerPath;
         else if (light_streams != "reference") { std::fprintf(stderr, "invalid --light-streams: %s (reference or per-path)\n", light_streams.c_str()); return 2; }
     }
@@ -231,15 +242,19 @@ int main(int argc, char** argv) {
         vpl.options = options;
     }
     // vol-primitivies: the primitives that are not built are refused here
+    auto parse_radius = [&](float* out) -> bool {
+        char* end = nullptr;
+        *out = std::strtof(radius.c_str(), &end);
+        if (radius.empty() || *end != '\0' || !(*out > 0.0f) || *out > 3.0e38f) { std::fprintf(stderr, "invalid --radius: %s (a finite number > 0)\n", radius.c_str()); return false; }
+        return true;
+    };
     IntegratorVolPrimitives volp;
     if (cmd == "vol-primitivies") {
         if (primitives == "beam" || primitives == "plane" || primitives == "vrl") { std::fprintf(stderr, "vol-primitivies: -p %s is not built (bre only)\n", primitives.c_str()); return 2; }
         if (primitives != "bre") { std::fprintf(stderr, "%s is not a correct primitive (bre, beam, plane, vrl)\n", primitives.c_str()); return 2; }
         if (refused("vol-primitivies", RL_STREAM_REFERENCE_ORDER, true)) return 2;
         if (!parse_count("--nb-primitive", nb_primitive, &volp.nb_primitive)) return 2;
-        char* end = nullptr;
-        volp.radius = std::strtof(radius.c_str(), &end);
-        if (radius.empty() || *end != '\0' || !(volp.radius > 0.0f) || volp.radius > 3.0e38f) { std::fprintf(stderr, "invalid --radius: %s (a finite number > 0)\n", radius.c_str()); return 2; }
+        if (!parse_radius(&volp.radius)) return 2;
         volp.max_depth = match_infinity(max_depth);
         volp.rr_depth = match_infinity(rr_depth);
         volp.light_streams = light_streams_mode;
@@ -247,6 +262,21 @@ int main(int argc, char** argv) {
         else if (tree_build != "host") { std::fprintf(stderr, "invalid --tree-build: %s (host or device)\n", tree_build.c_str()); return 2; }
         volp.device = device;
         volp.options = options;
+    }
+    // photon-beams: the limits of vol-primitivies, and the medium the reference panics without
+    IntegratorPhotonBeams pbeams;
+    if (cmd == "photon-beams") {
+        if (refused("photon-beams", RL_STREAM_REFERENCE_ORDER, true)) return 2;
+        if (!parse_count("--nb-primitive", nb_primitive, &pbeams.nb_primitive)) return 2;
+        if (pbeams.nb_primitive > (uint32_t)RL_BEAM_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", nb_primitive.c_str(), (int)RL_BEAM_MAX); return 2; }
+        if (!parse_radius(&pbeams.radius)) return 2;
+        const Medium m = parse_medium(medium);
+        if (m.sigma_a + m.sigma_s == 0.0f) { std::fprintf(stderr, "photon-beams: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n"); return 2; }
+        pbeams.max_depth = match_infinity(max_depth);
+        pbeams.rr_depth = match_infinity(rr_depth);
+        pbeams.light_streams = light_streams_mode;
+        pbeams.device = device;
+        pbeams.options = options;
     }
     // plane-single needs the medium
     IntegratorSinglePlane plane;
@@ -319,7 +349,7 @@ int main(int argc, char** argv) {
         }
         scene->build_emitters(use_ats);      // scene.build_emitters(use_ats) (cli.rs:432)
         IntegratorPathTracing integrator;
-        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies" || cmd == "plane-single") strategy = "all";       // (the path integrator below is not used)
+        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams" || cmd == "plane-single") strategy = "all";       // (the path integrator below is not used)
         integrator.min_depth = match_infinity(min_depth);
         integrator.max_depth = match_infinity(max_depth);
         integrator.rr_depth = match_infinity(rr_depth);
@@ -350,6 +380,8 @@ int main(int argc, char** argv) {
             img = vpl.compute(sampler, *scene); elapsed_ms = vpl.last_stats.render_ms;
         } else if (cmd == "vol-primitivies") {
             img = volp.compute(sampler, *scene); elapsed_ms = volp.last_stats.render_ms;
+        } else if (cmd == "photon-beams") {
+            img = pbeams.compute(sampler, *scene); elapsed_ms = pbeams.last_stats.render_ms;
         } else if (cmd == "plane-single") {
             if (plane_uncorrelated) { img = uplane.compute(sampler, *scene); elapsed_ms = uplane.last_stats.render_ms; }
             else { img = plane.compute(sampler, *scene); elapsed_ms = plane.last_stats.render_ms; }

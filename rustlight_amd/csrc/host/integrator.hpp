@@ -372,6 +372,40 @@ struct IntegratorVolPrimitives {
     }
 };
 
+// IntegratorVolPrimitives with primitives = Beams (vol_primitives.rs:437-523, 608-790) as a struct of its own — IntegratorVolPrimitives above keeps refusing every
+// primitive but BRE, and nothing above refers to this one — + Integrator::compute, seed for seed the reference: the beams from the main sampler
+// (rl_beam_generate: the light paths of rl_vpl_generate stored by convert_beams(false, ..)), the split and the beam tree (rl_beam_map_build), the block seeds
+// from the sampler the generation leaves, the gather on reference-order streams (rl_render_beams).  light_streams = PerPath: rl_beam_generate_paths.
+using BeamSetHandle = Handle<rl_beam_set, rl_beam_destroy>;
+using BeamMapHandle = Handle<rl_beam_map, rl_beam_map_destroy>;
+struct IntegratorPhotonBeams {
+    uint32_t nb_primitive = 128;
+    std::optional<uint32_t> max_depth, rr_depth = 0u;
+    float radius = RL_PHOTON_RADIUS_DEFAULT;
+    LightStreams light_streams{LightStreams::Reference};
+    int device = 0;
+    Options options;
+    rl_render_stats last_stats{}, last_generation_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        RenderContext ctx(scene, device, options);
+        rl_path_params p;
+        rl_path_params_default(&p);
+        p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
+        p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
+        p.stream_mode = RL_STREAM_REFERENCE_ORDER;
+        p.seed_variant = sampler.variant;
+        rl_beam_set* generated = nullptr;
+        check((light_streams == LightStreams::PerPath ? rl_beam_generate_paths : rl_beam_generate)(ctx, &p, nb_primitive, &sampler.rnd, &generated, &last_generation_stats), "photon-beams");
+        const BeamSetHandle beams(generated);
+        rl_beam_map* built = nullptr;
+        check(rl_beam_map_build(ctx, beams.get(), radius, &built), "photon-beams");
+        const BeamMapHandle map(built);
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        check(rl_render_beams(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "photon-beams");
+        return std::move(ctx.img);
+    }
+};
+
 // struct IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs:280-294) + Integrator::compute, seed for seed the reference:
 // the planes from the main sampler (rl_plane_generate), the plane tree (rl_plane_map_build), the block seeds from the sampler the generation leaves, the
 // gather on reference-order streams (rl_render_plane_single).  generate = Lanes and tree_build = Device set the context options plane_generate_lanes and

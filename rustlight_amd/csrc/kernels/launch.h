@@ -1,5 +1,5 @@
 // launch.h — host-side launchers of the kernel families that live in their own translation units (fused_*.hip, fusedq_*.hip, fused_strat_*.hip,
-// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, plane_*.hip, uplane_*.hip), so that the families compile in parallel, and
+// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, beamgen_*.hip, beam_*.hip, plane_*.hip, uplane_*.hip), so that the families compile in parallel, and
 // the dispatcher every one of them maps its run-time arguments to template arguments with (with_bsdf, with_flag).  Launch errors are picked up by
 // the caller's hipGetLastError().
 #pragma once
@@ -99,6 +99,17 @@ struct BreConst {
     float norm_photon;                  // 1 / paths shot
 };
 
+// The photon beams (beam.hip.h): the beam tree in visiting order and the sub-beams in leaf order (host/beamtree.cpp), the kernel's constants
+enum { STAT_BEAM_ACCEPTED = 6, STAT_BEAM_ACCEPTED_HI = 3 };    // its leaf's statistics rows: beams accepted
+struct BeamConst {
+    const float4* nodes;                // [n_nodes][2]: p_min.xyz, p_max.x | p_max.yz, skip, first << 3 | count
+    const float4* beams;                // [n_sub][3]: o, length | d, 0 | radiance, 0
+    unsigned n_nodes;
+    float radius2;                      // self.radius * self.radius
+    float half_inv_radius;              // 0.5 / self.radius
+    float norm_photon;                  // 1 / paths shot
+};
+
 // IntegratorSinglePlane (plane.hip.h): the rectangular lights, the generation's constants, and for the gather the plane tree in visiting order with the
 // planes in leaf order (host/planetree.cpp)
 struct PlaneLight { float o[3], u_l, u[3], v_l, v[3], pad0, n[3], pad1, emission[3], pad2; };      // RectangularLightSource, 5 float4
@@ -192,6 +203,14 @@ void launch_vpl_paths_stream(bool write, int mat, bool medium, dim3 grid, dim3 b
 // IntegratorVolPrimitives' beam radiance estimate (bre.hip.h): k_bre_gather over the owned blocks; hg: the medium's phase function is Henyey-Greenstein
 void launch_bre_lds(bool hg, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BreConst& bc);
 void launch_bre_stream(bool hg, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BreConst& bc);
+// The photon beams: the beam pass (beamgen.hip.h; which = 0 k_beam_generate reading vc as k_vpl_generate does, 1 / 2 k_beam_shoot's count / write pass reading pc as
+// k_vpl_shoot does, mat as for launch_vpl_*; the scene has a medium) and k_beam_gather over the owned blocks (beam.hip.h)
+void launch_beamgen_lds(int which, int mat, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc,
+                        const VplConst& vc, const VplPathsConst& pc);
+void launch_beamgen_stream(int which, int mat, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc,
+                           const VplConst& vc, const VplPathsConst& pc);
+void launch_beam_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BeamConst& bc);
+void launch_beam_stream(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BeamConst& bc);
 // IntegratorSinglePlane (plane.hip.h): k_plane_generate on one lane, k_plane_generate_lanes on one lane per iteration (plane_generate.hip); k_plane_gather over the owned blocks, mode = PLANE_MODE_*
 void launch_plane_generate(hipStream_t st, const PlaneGenConst& gc);
 void launch_plane_generate_lanes(hipStream_t st, const PlaneGenConst& gc, unsigned n_gen);      // k_plane_generate_lanes: one lane per iteration, n_gen of them

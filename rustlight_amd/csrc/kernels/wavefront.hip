@@ -45,6 +45,7 @@
 #include "rngjump.h"
 #include "../host/hip_buffer.h"
 #include "../host/photontree.h"
+#include "../host/beamtree.h"
 #include "phototree.h"
 #include "../host/scene.h"
 #include "wavefront.h"
@@ -1045,6 +1046,48 @@ static int check_vpl_generate(const rl_context* ctx, const rl_path_params* param
     }
     return RL_OK;
 }
+// The light passes that store records along light paths — the VPLs (and the photons they double as) and the photon beams (beam_render.hip.h) — share their two
+// host sequences; a pass names its record size and its refusal, and launches its own kernels.
+struct LightPassKind {
+    unsigned rec_words;               // u32 per record
+    const char* too_few;              // rl_last_error when RL_VPL_MAX_PATHS paths store fewer than nb records
+};
+static const LightPassKind kVplPass{RL_VPL_WORDS, "vpl: fewer than nb_vpl VPLs stored within RL_VPL_MAX_PATHS light paths"};
+// The serial pass (k_vpl_generate, k_beam_generate): one lane on the main sampler's stream.  launch(lds_bytes, rc, stc, vc); on RL_OK *words holds *n_records
+// records of *n_paths paths and `sampler` is the one the lane left
+template <class Launch>
+static int light_pass_serial(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, const LightPassKind& kind, rl_sampler* sampler,
+                             HipBuffer<unsigned>* words, uint64_t* n_records, uint64_t* n_paths, rl_render_stats* stats, Launch&& launch) {
+    int rcode;
+    const unsigned cap = nb_vpl + kDepthCap + 1u;        // the last path adds at most one record per vertex
+    if ((rcode = words->ensure((size_t)cap * kind.rec_words)) != RL_OK) return rcode;
+    RenderConst rc{};
+    rc.has_max = params->has_max_depth; rc.max_depth = params->max_depth;
+    rc.has_rr = params->has_rr_depth; rc.rr_depth = params->rr_depth;
+    VplConst vc{};
+    vc.nb_vpl = nb_vpl; vc.cap = cap; vc.max_paths = RL_VPL_MAX_PATHS;
+    vc.option_vpl = option_vpl;
+    vc.vpl_words = words->get();
+    StackConf stc;
+    if ((rcode = stack_conf(ctx, 256, &stc)) != RL_OK) return rcode;
+    const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
+    LaneRun run;
+    if ((rcode = run_one_lane(ctx->stream, stats != nullptr && !ctx->knobs.has(K_NO_EVENTS), sampler, VPL_GEN_WORDS, &run, [&](unsigned long long* d_gen) {
+            vc.gen_state = d_gen; vc.gen_out = d_gen + 4;
+            launch(lds, rc, stc, vc);
+        })) != RL_OK) return rcode;
+    const unsigned long long* g = run.words.data() + 4;
+    if (g[VPL_GEN_VPLS] < nb_vpl) { rl_set_error(kind.too_few); return RL_ERR_UNSUPPORTED; }
+    for (int i = 0; i < 4; i++) sampler->s[i] = run.words[i];
+    *n_records = g[VPL_GEN_VPLS]; *n_paths = g[VPL_GEN_PATHS];
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->camera_samples = g[VPL_GEN_PATHS]; stats->vertices = g[VPL_GEN_VERTICES]; stats->extension_rays = g[VPL_GEN_EXT]; stats->rng_draws = g[VPL_GEN_DRAWS];
+        stats->iterations = 1; stats->kernel_launches = 1; stats->ms_prepass = run.ev.ms;
+        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - run.t0).count();
+    }
+    return RL_OK;
+}
 extern "C" int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, rl_sampler* sampler, rl_vpl_set** out,
                                rl_render_stats* stats) {
     int rcode;
@@ -1052,33 +1095,10 @@ extern "C" int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, ui
     HIP_OK(hipSetDevice(ctx->device));
     auto set = std::make_unique<rl_vpl_set>();
     set->ctx = ctx; set->device = ctx->device;
-    const unsigned cap = nb_vpl + kDepthCap + 1u;        // the last path adds at most one VPL per vertex
-    if ((rcode = set->words.ensure((size_t)cap * RL_VPL_WORDS)) != RL_OK) return rcode;
-    RenderConst rc{};
-    rc.has_max = params->has_max_depth; rc.max_depth = params->max_depth;
-    rc.has_rr = params->has_rr_depth; rc.rr_depth = params->rr_depth;
-    VplConst vc{};
-    vc.nb_vpl = nb_vpl; vc.cap = cap; vc.max_paths = RL_VPL_MAX_PATHS;
-    vc.option_vpl = option_vpl;
-    vc.vpl_words = set->words.get();
-    StackConf stc;
-    if ((rcode = stack_conf(ctx, 256, &stc)) != RL_OK) return rcode;
-    const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
-    LaneRun run;
-    if ((rcode = run_one_lane(ctx->stream, stats != nullptr && !ctx->knobs.has(K_NO_EVENTS), sampler, VPL_GEN_WORDS, &run, [&](unsigned long long* d_gen) {
-            vc.gen_state = d_gen; vc.gen_out = d_gen + 4;
+    if ((rcode = light_pass_serial(ctx, params, nb_vpl, option_vpl, kVplPass, sampler, &set->words, &set->n_vpl, &set->n_paths, stats,
+                                   [&](size_t lds, const RenderConst& rc, const StackConf& stc, const VplConst& vc) {
             (ctx->lds_scene ? launch_vpl_lds : launch_vpl_stream)(0, ctx->single_bsdf ? ctx->bsdf_type : -1, ctx->ds.medium.enabled != 0, dim3(1), dim3(256), lds, ctx->stream, rc, ctx->ds, stc, vc);
         })) != RL_OK) return rcode;
-    const unsigned long long* g = run.words.data() + 4;
-    if (g[VPL_GEN_VPLS] < nb_vpl) { rl_set_error("vpl: fewer than nb_vpl VPLs stored within RL_VPL_MAX_PATHS light paths"); return RL_ERR_UNSUPPORTED; }
-    for (int i = 0; i < 4; i++) sampler->s[i] = run.words[i];
-    set->n_vpl = g[VPL_GEN_VPLS]; set->n_paths = g[VPL_GEN_PATHS];
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->camera_samples = g[VPL_GEN_PATHS]; stats->vertices = g[VPL_GEN_VERTICES]; stats->extension_rays = g[VPL_GEN_EXT]; stats->rng_draws = g[VPL_GEN_DRAWS];
-        stats->iterations = 1; stats->kernel_launches = 1; stats->ms_prepass = run.ev.ms;
-        stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - run.t0).count();
-    }
     *out = set.release();
     return RL_OK;
 }
@@ -1086,14 +1106,11 @@ extern "C" int rl_vpl_generate(rl_context* ctx, const rl_path_params* params, ui
 // over a batch of path indices, the counts brought to the host, which takes their prefix sum and looks for K (the smallest path count that stores nb_vpl
 // records); when the batch did not reach it, the next one is sized from the records per path measured so far.  Then one write pass over paths 0 .. K-1.
 static constexpr unsigned kVplFirstBatch = 4096, kVplShootGroupsPerCu = 2;
-extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, rl_sampler* sampler, rl_vpl_set** out,
-                                     rl_render_stats* stats) {
+// launch(write, groups, lds_bytes, rc, stc, pc) on ctx->stream (k_vpl_shoot, k_beam_shoot); the results as light_pass_serial leaves them
+template <class Launch>
+static int light_pass_paths(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, const LightPassKind& kind, rl_sampler* sampler,
+                            HipBuffer<unsigned>* words, uint64_t* n_records, uint64_t* n_paths, rl_render_stats* stats, Launch&& launch) {
     int rcode;
-    if ((rcode = check_vpl_generate(ctx, params, nb_vpl, option_vpl, sampler, out)) != RL_OK) return rcode;
-    const bool medium = ctx->ds.medium.enabled != 0;
-    HIP_OK(hipSetDevice(ctx->device));
-    auto set = std::make_unique<rl_vpl_set>();
-    set->ctx = ctx; set->device = ctx->device;
     const hipStream_t st = ctx->stream;
     const long long forced = ctx->knobs.has(K_VPL_BATCH_PATHS) ? std::max<long long>(1, ctx->knobs.i(K_VPL_BATCH_PATHS, 0)) : 0;
     int cus = 256;
@@ -1107,8 +1124,6 @@ extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* para
     for (int i = 0; i < 4; i++) pc.main[i] = sampler->s[i];
     pc.option_vpl = option_vpl;
     const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
-    const int mat = ctx->single_bsdf ? ctx->bsdf_type : -1;
-    const auto launch = ctx->lds_scene ? launch_vpl_paths_lds : launch_vpl_paths_stream;
     EventPair ev;
     if ((rcode = ev.open(stats != nullptr && !ctx->knobs.has(K_NO_EVENTS))) != RL_OK) return rcode;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1121,7 +1136,7 @@ extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* para
         if (r != RL_OK) return r;
         pc.first = first; pc.count = count;
         ev.begin(st);
-        launch(write, mat, medium, dim3(groups), dim3(256), lds, st, rc, ctx->ds, stc, pc);
+        launch(write, groups, lds, rc, stc, pc);
         ev.end(st);
         launches++;
         return RL_OK;
@@ -1158,18 +1173,18 @@ extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* para
         }
         walked += batch;
     }
-    if (K == 0) { rl_set_error("vpl: fewer than nb_vpl VPLs stored within RL_VPL_MAX_PATHS light paths"); return RL_ERR_UNSUPPORTED; }
+    if (K == 0) { rl_set_error(kind.too_few); return RL_ERR_UNSUPPORTED; }
     // ---- write pass: paths 0 .. K-1 again, each to its own offset
     HipBuffer<unsigned> d_offsets;
-    if ((rcode = set->words.ensure((size_t)stored * RL_VPL_WORDS)) != RL_OK || (rcode = d_offsets.ensure(K)) != RL_OK) return rcode;
+    if ((rcode = words->ensure((size_t)stored * kind.rec_words)) != RL_OK || (rcode = d_offsets.ensure(K)) != RL_OK) return rcode;
     HIP_OK(hipMemcpyAsync(d_offsets.get(), offsets.data(), (size_t)K * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    pc.cap = (unsigned)stored; pc.vpl_words = set->words.get(); pc.offsets = d_offsets.get(); pc.counts = nullptr;
+    pc.cap = (unsigned)stored; pc.vpl_words = words->get(); pc.offsets = d_offsets.get(); pc.counts = nullptr;
     if ((rcode = shoot(true, 0u, K)) != RL_OK) return rcode;
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
     ev.add();
     for (unsigned k = 0; k < K; k++) (void)rl_sampler_next_u64(sampler);           // the K clone_box calls
-    set->n_vpl = stored; set->n_paths = K;
+    *n_records = stored; *n_paths = K;
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->camera_samples = K;
@@ -1181,6 +1196,20 @@ extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* para
         stats->reserved[0] = walked;
         stats->render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
+    return RL_OK;
+}
+extern "C" int rl_vpl_generate_paths(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, rl_sampler* sampler, rl_vpl_set** out,
+                                     rl_render_stats* stats) {
+    int rcode;
+    if ((rcode = check_vpl_generate(ctx, params, nb_vpl, option_vpl, sampler, out)) != RL_OK) return rcode;
+    HIP_OK(hipSetDevice(ctx->device));
+    auto set = std::make_unique<rl_vpl_set>();
+    set->ctx = ctx; set->device = ctx->device;
+    if ((rcode = light_pass_paths(ctx, params, nb_vpl, option_vpl, kVplPass, sampler, &set->words, &set->n_vpl, &set->n_paths, stats,
+                                  [&](bool write, unsigned groups, size_t lds, const RenderConst& rc, const StackConf& stc, const VplPathsConst& pc) {
+            (ctx->lds_scene ? launch_vpl_paths_lds : launch_vpl_paths_stream)(write, ctx->single_bsdf ? ctx->bsdf_type : -1, ctx->ds.medium.enabled != 0, dim3(groups), dim3(256), lds,
+                                                                              ctx->stream, rc, ctx->ds, stc, pc);
+        })) != RL_OK) return rcode;
     *out = set.release();
     return RL_OK;
 }
@@ -1276,6 +1305,7 @@ extern "C" int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_pa
 }
 
 #include "gather_render.hip.h"
+#include "beam_render.hip.h"
 
 // ---- batched Acceleration::{trace, visible}
 namespace {
