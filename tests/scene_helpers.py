@@ -55,6 +55,25 @@ def single_bsdf(w, h, bsdf):
     return sd
 
 
+def open_floor(w, h, bsdf=None, environment=None, light=True, light_in_view=False):
+    """An open receiver: a camera 3 above an 8 x 8 floor looks straight down (40 degrees across), a 0.6 x 0.5 light 2 above the floor and a black occluding
+    quad 1 above it both stand beside the frustum, and the occluder's shadow falls into the frame.  Nothing in view has a silhouette.
+    light_in_view: the light hangs 1.5 above the floor inside the frustum instead, so that the camera sees its back (the one surface kind that is not
+    turned towards the viewer), and a black canopy beside the frustum, 0.7 above the light, hides part of the sky over that back."""
+    black = scenes.matte((0.0, 0.0, 0.0))
+    meshes = [scenes._quad_mesh("Floor", [-4, 0, -4, -4, 0, 4, 4, 0, 4, 4, 0, -4], [0, 1, 0], bsdf or scenes.matte((0.7, 0.5, 0.3))),
+              scenes._quad_mesh("Occluder", [0.9, 1, 0.0, 1.4, 1, 0.0, 1.4, 1, 0.6, 0.9, 1, 0.6], [0, 1, 0], black)]
+    if light_in_view:
+        meshes.append(scenes._quad_mesh("Light", [-0.1, 1.5, -0.15, 0.5, 1.5, -0.15, 0.5, 1.5, 0.35, -0.1, 1.5, 0.35], [0, -1, 0], black, emission=(9.0, 7.0, 5.0)))
+        meshes.append(scenes._quad_mesh("Canopy", [0.4, 2.2, -0.4, 1.2, 2.2, -0.4, 1.2, 2.2, 0.6, 0.4, 2.2, 0.6], [0, -1, 0], black))
+    elif light:
+        meshes.append(scenes._quad_mesh("Light", [1.7, 2, 0.25, 2.3, 2, 0.25, 2.3, 2, 0.75, 1.7, 2, 0.75], [0, -1, 0], black, emission=(9.0, 7.0, 5.0)))
+    to_world = np.asarray([1, 0, 0, 0, 0, 0, -1, 0, 0, -1, 0, 0, 0, 3, 0, 1], dtype=np.float32)
+    sd = scenes.SceneData(w, h, 40.0, 0, to_world, False, meshes)
+    sd.environment = environment
+    return sd
+
+
 def glass_and_mirror(w, h):
     # several BSDF types in one scene (the run-time switch); glass transmission carries eta^2 into the russian roulette
     sd = scenes.cbox(w, h)
