@@ -419,7 +419,7 @@ int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_path_params* 
                   float* out_rgb, int out_is_device, void* stream, rl_render_stats* stats);
 
 /* ---- IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: BRE } (src/integrators/explicit/vol_primitives.rs; CLI `vol-primitivies -p bre`,
- * examples/cli.rs:189-196, 692-716): the beam radiance estimate.  Planes and VRL are not built; beams have entry points of their own (rl_beam_*, below).
+ * examples/cli.rs:189-196, 692-716): the beam radiance estimate.  VRL is not built; beams and planes have entry points of their own (rl_beam_*, rl_pplane_*, below).
  * The photons are the records of a set generated by rl_vpl_generate with option_vpl = RL_VPL_VOLUME and nb_vpl = nb_primitive: convert_photons
  * (vol_primitives.rs:525-565) stores at every Vertex::Volume what convert_vpl stores under `-v volume`, from the same light paths, and the shooting stops on the
  * same count — words 4..6 = pos, 7..9 = radiance, 10..12 = d_in; the set's path count is nb_path_shot.
@@ -510,6 +510,53 @@ int rl_beam_map_read(const rl_beam_map* map, size_t node_capacity, float* node_b
 void rl_beam_map_destroy(rl_beam_map* map);
 int rl_render_beams(rl_context* ctx, const rl_beam_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
                     const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
+
+/* ---- Photon planes: IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: Planes } (src/integrators/explicit/vol_primitives.rs), behind entry
+ * points and a CLI word (`photon-planes`) of their own: `vol-primitivies -p plane` stays refused with the other unbuilt primitives.
+ * rl_pplane_generate (vol_primitives.rs:376-523, 608-630): the light paths of rl_beam_generate — the same draws in the same order on the main sampler, seed for
+ * seed — stored by convert_beams(true, ..) and convert_planes(..) while fewer than nb_primitive planes are stored (every record of the last path is kept).  An
+ * edge that leaves the light vertex or a surface vertex is a beam.  An edge e that leaves a volume vertex V1 is a plane when it ends in a volume vertex V2 that
+ * was expanded with an edge e2, and a beam otherwise (V2 on a surface, or not expanded: depth limit, Russian roulette, zero throughput).  nb_primitive is 1 ..
+ * RL_BEAM_MAX.  Refused with rl_beam_generate's codes for what it refuses; max_depth <= 3 is RL_ERR_INVALID_ARGUMENT (V2 is expanded only when 3 < max_depth: no
+ * plane exists below that and the reference never stops shooting); RL_ERR_UNSUPPORTED when RL_VPL_MAX_PATHS paths store fewer planes than asked, or when more
+ * than RL_BEAM_MAX + 2048 beams arise before nb_primitive planes are stored (the beams are not bounded by the plane count; the message names the medium).
+ * Counters and the sampler on return: rl_vpl_generate's, camera_samples = paths shot.
+ * rl_pplane_generate_paths: the same pass with one light path per device lane under rl_vpl_generate_paths' stream contract (a count pass, then a write pass;
+ * both kinds of record in path order; `sampler` advanced by K next_u64()); its counters.
+ * rl_pplane_read: the planes, RL_PLANE_WORDS u32 each in rl_plane_read's geometry layout (:404-412) — [0..2] o = V1, [3..5] d0 = e.d, [6..8] d1 = e2.d, [9]
+ * length0 = continued_t(e) = e.dist, [10] length1 = continued_t(e2), the distance e2's medium sample drew before it was cut at the hit distance (volume.rs:102-130;
+ * it exceeds the hit distance when e2 ends on a surface), [11..13] radiance, the flux that reached V1, [14] the path's index within the generation, [15] the
+ * index of e within the path, [16..17] 0 — and the beams, RL_BEAM_WORDS u32 each in rl_beam_read's layout; both in storing order.  The word counts must be
+ * n_planes * RL_PLANE_WORDS and n_beams * RL_BEAM_WORDS.  A plane's phase function is Isotropic whatever the medium's is (:410): kept.
+ * rl_pplane_map_build (vol_primitives.rs:647-699): the beams through rl_beam_map_build's split and beam tree (`radius` as there; the reference hard-codes
+ * 0.001), the planes through rl_plane_tree_build's tree (aabb = the four corners, position = the middle, :275-291), both uploaded: sub-beams as 48-byte records,
+ * planes as 4 x float4 in leaf order, o, length0 | d0, length1 | d1, 0 | radiance, 0.  The context option pplane_tree_device = 1 builds the plane tree with the
+ * kernels of rl_plane_map_build_device: the same bytes.  rl_pplane_map_build_words: the same from caller-supplied records; n_paths >= 1 stands for nb_path_shot.
+ * Refused: what rl_beam_map_build_words and rl_plane_tree_build refuse (a radius that is not finite and > 0, non-finite o, d, length or corner, a zero or
+ * non-finite avg_split, n_paths = 0, a split beyond the tree's capacity), a caller's plane record whose words 16 or 17 are not 0, a set of another context.
+ * rl_pplane_map_read: which = 0 the beam tree with the sub-beams [n_sub][12] f32, which = 1 the plane tree with the planes [n_planes][16] f32; node_boxes /
+ * node_links as rl_photon_map_read writes them.
+ * rl_render_photon_planes (vol_primitives.rs:295-373, 705-790): rl_render_beams' camera loop, streams, shards and refusals; per camera sample first the beam
+ * tree with rl_render_beams' test and contribution, then the plane tree, both added into one c, which is then accumulated (in f32 the order matters, so one
+ * kernel walks both).  Per plane PhotonPlane::intersection statement by statement (tnear = 1e-4), one visibility ray visible(o + d0 * t0, ray.o + ray.d * t_cam),
+ * c += radiance * 1 / (4 PI) * sigma_s * sigma_s * transmittance(t_cam) * (1 / |d0 . (d1 x -ray.d)|) * (1 / nb_path_shot).  reserved[0] = nodes entered in both
+ * trees, reserved[1] = beams accepted, reserved[2] = planes intersected (= shadow_rays), reserved[3] = of those, visible. */
+typedef struct rl_pplane_set rl_pplane_set;     /* opaque: the planes and surface beams of one generation, on the context's device */
+typedef struct rl_pplane_map rl_pplane_map;     /* opaque: beam tree, sub-beams, plane tree and planes, on the context's device */
+int rl_pplane_generate(rl_context* ctx, const rl_path_params* params, uint32_t nb_primitive, rl_sampler* sampler, rl_pplane_set** out, rl_render_stats* stats);
+int rl_pplane_generate_paths(rl_context* ctx, const rl_path_params* params, uint32_t nb_primitive, rl_sampler* sampler, rl_pplane_set** out, rl_render_stats* stats);
+int rl_pplane_info(const rl_pplane_set* set, uint64_t* n_planes, uint64_t* n_beams, uint64_t* n_paths);
+int rl_pplane_read(const rl_pplane_set* set, uint32_t* plane_words, size_t n_plane_words, uint32_t* beam_words, size_t n_beam_words);
+void rl_pplane_destroy(rl_pplane_set* set);
+int rl_pplane_map_build(rl_context* ctx, const rl_pplane_set* set, float radius, rl_pplane_map** out);
+int rl_pplane_map_build_words(rl_context* ctx, const uint32_t* beam_words, size_t n_beams, const uint32_t* plane_words, size_t n_planes, uint64_t n_paths,
+                              float radius, rl_pplane_map** out);
+int rl_pplane_map_info(const rl_pplane_map* map, uint64_t* n_beams, uint64_t* n_sub, uint64_t* n_beam_nodes, uint64_t* n_planes, uint64_t* n_plane_nodes,
+                       uint64_t* n_paths, float* radius);
+int rl_pplane_map_read(const rl_pplane_map* map, int which, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t element_capacity, float* elements);
+void rl_pplane_map_destroy(rl_pplane_map* map);
+int rl_render_photon_planes(rl_context* ctx, const rl_pplane_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
+                            const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
 
 /* ---- IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs; CLI `plane-single`, examples/cli.rs:197-202, 664-691): single
  * scattering from rectangular area lights, estimated with photon planes under one of seven sampling strategies.

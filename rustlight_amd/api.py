@@ -50,7 +50,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_pplane_generate", "rl_pplane_generate_paths", "rl_pplane_info", "rl_pplane_read", "rl_pplane_destroy", "rl_pplane_map_build", "rl_pplane_map_build_words", "rl_pplane_map_info", "rl_pplane_map_read", "rl_pplane_map_destroy", "rl_render_photon_planes", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -151,6 +151,19 @@ def lib():
     L.rl_beam_map_destroy.argtypes = [vp]
     L.rl_beam_map_destroy.restype = None
     L.rl_render_beams.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
+    L.rl_pplane_generate.argtypes = [vp, C.POINTER(abi.PathParams), C.c_uint32, C.POINTER(abi.Sampler), C.POINTER(vp), C.POINTER(abi.RenderStats)]
+    L.rl_pplane_generate_paths.argtypes = L.rl_pplane_generate.argtypes
+    L.rl_pplane_info.argtypes = [vp, u64p, u64p, u64p]
+    L.rl_pplane_read.argtypes = [vp, u32p, C.c_size_t, u32p, C.c_size_t]
+    L.rl_pplane_destroy.argtypes = [vp]
+    L.rl_pplane_destroy.restype = None
+    L.rl_pplane_map_build.argtypes = [vp, vp, C.c_float, C.POINTER(vp)]
+    L.rl_pplane_map_build_words.argtypes = [vp, u32p, C.c_size_t, u32p, C.c_size_t, C.c_uint64, C.c_float, C.POINTER(vp)]
+    L.rl_pplane_map_info.argtypes = [vp, u64p, u64p, u64p, u64p, u64p, u64p, f32p]
+    L.rl_pplane_map_read.argtypes = [vp, C.c_int, C.c_size_t, f32p, u32p, C.c_size_t, f32p]
+    L.rl_pplane_map_destroy.argtypes = [vp]
+    L.rl_pplane_map_destroy.restype = None
+    L.rl_render_photon_planes.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
     L.rl_plane_generate.argtypes = [vp, C.c_uint32, C.c_int, C.POINTER(abi.Sampler), C.POINTER(vp), C.POINTER(abi.RenderStats)]
     L.rl_plane_info.argtypes = [vp, u64p, u64p, C.POINTER(C.c_int)]
     L.rl_plane_read.argtypes = [vp, u32p, C.c_size_t]
@@ -638,6 +651,43 @@ class Context(_ImageCalls):
         beams_accepted = reserved[0] / reserved[1], ms_other = the gather kernel."""
         return self._render_gather(lib().rl_render_beams, beams.h, seeds, spp, seed_variant, shard_index, shard_count, ("nodes_entered", "beams_accepted"))
 
+    def pplane_generate(self, sampler: "IndependentSampler", nb_primitive=128, max_depth=None, rr_depth=0, streams="reference"):
+        """The photon planes' plane pass (vol_primitives.rs:376-523, 608-630): (PPlaneSet, stats dict).  The light paths of Context.beam_generate, stored as
+        surface beams and planes while fewer than nb_primitive planes are stored.  streams, `sampler` and the stats follow Context.beam_generate's rules."""
+        if streams not in LIGHT_STREAMS:
+            raise ValueError(f"streams must be one of {LIGHT_STREAMS}, not {streams!r}")
+        p = path_params(1, 0, max_depth, rr_depth, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=sampler.variant)
+        st = abi.RenderStats()
+        h = C.c_void_p()
+        fn = lib().rl_pplane_generate if streams == "reference" else lib().rl_pplane_generate_paths
+        _check(fn(self.h, C.byref(p), nb_primitive, C.byref(sampler.s), C.byref(h), C.byref(st)))
+        d = st.as_dict()
+        if streams == "per_path":
+            d["paths_walked"] = int(st.reserved[0])
+        return PPlaneSet(h, self), d
+
+    def pplane_map(self, records: "PPlaneSet", radius=PHOTON_RADIUS_DEFAULT):
+        """rl_pplane_map_build: the surface beams of a set split and sorted into the beam tree, its planes sorted into the plane tree, both uploaded.  The plane
+        tree is built on the host, or by the device kernels under the context option pplane_tree_device = 1 (the same bytes)."""
+        h = C.c_void_p()
+        _check(lib().rl_pplane_map_build(self.h, records.h, radius, C.byref(h)))
+        return PPlaneMap(h, self)
+
+    def pplane_map_from_words(self, beam_words, plane_words, n_paths, radius=PHOTON_RADIUS_DEFAULT):
+        """rl_pplane_map_build_words: Context.pplane_map over caller-supplied beam ([n, BEAM_WORDS] u32) and plane ([m, PLANE_WORDS] u32) records of n_paths
+        light paths."""
+        b = np.ascontiguousarray(beam_words, dtype=np.uint32).reshape(-1, BEAM_WORDS)
+        w = np.ascontiguousarray(plane_words, dtype=np.uint32).reshape(-1, PLANE_WORDS)
+        h = C.c_void_p()
+        _check(lib().rl_pplane_map_build_words(self.h, abi.u32ptr(b), b.shape[0], abi.u32ptr(w), w.shape[0], n_paths, radius, C.byref(h)))
+        return PPlaneMap(h, self)
+
+    def render_photon_planes(self, pmap: "PPlaneMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
+        """The photon planes' gather (vol_primitives.rs:295-373, 705-790) through rl_render_photon_planes: (image HxWx3 f32, stats dict).  stats: nodes_entered
+        (both trees) / beams_accepted / planes_intersected / planes_visible = reserved[0 .. 3], ms_other = the gather kernel."""
+        return self._render_gather(lib().rl_render_photon_planes, pmap.h, seeds, spp, seed_variant, shard_index, shard_count,
+                                   ("nodes_entered", "beams_accepted", "planes_intersected", "planes_visible"))
+
     def plane_generate(self, sampler: "IndependentSampler", nb_primitive=128, strategy="average", form="serial"):
         """IntegratorSinglePlane's plane pass (plane_single.rs:363-427) through rl_plane_generate: (PlaneSet, stats dict).  `sampler` is advanced as the
         reference's main sampler is.  stats: camera_samples = iterations (number_plane_gen), vertices = planes, rng_draws, ms_prepass = the kernel.
@@ -1102,6 +1152,89 @@ class IntegratorPhotonBeams(_Integrator):
             if bmap is not None:
                 bmap.close()
             beams.close()
+        return img
+
+
+class PPlaneSet(_DeviceHandle):
+    """rl_pplane_set: the planes and surface beams of one plane pass, on the device of the context that made them (kept alive with it)."""
+    _destroy = "rl_pplane_destroy"
+
+    def info(self):
+        """(planes stored, beams stored, light paths shot)."""
+        n, b, p = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().rl_pplane_info(self.h, C.byref(n), C.byref(b), C.byref(p)))
+        return int(n.value), int(b.value), int(p.value)
+
+    def __len__(self):
+        return self.info()[0]
+
+    def words(self):
+        """The raw records: (planes [n_planes, PLANE_WORDS] u32, beams [n_beams, BEAM_WORDS] u32) (layouts: include/rustlight_amd.h, rl_pplane_read)."""
+        n, b, _ = self.info()
+        pw, bw = np.zeros((n, PLANE_WORDS), np.uint32), np.zeros((b, BEAM_WORDS), np.uint32)
+        _check(lib().rl_pplane_read(self.h, abi.u32ptr(pw), pw.size, abi.u32ptr(bw), bw.size))
+        return pw, bw
+
+    def records(self):
+        """The records as numpy structured arrays: (planes: o, d0, d1, length0, length1, radiance, path, edge; beams: BEAM_RECORD_DTYPE)."""
+        pw, bw = self.words()
+        return pw.view(PPLANE_RECORD_DTYPE).reshape(-1), bw.view(BEAM_RECORD_DTYPE).reshape(-1)
+
+
+PPLANE_RECORD_DTYPE = np.dtype([("o", "<f4", 3), ("d0", "<f4", 3), ("d1", "<f4", 3), ("length0", "<f4"), ("length1", "<f4"), ("radiance", "<f4", 3), ("path", "<u4"),
+                                ("edge", "<u4"), ("zero", "<u4", 2)])
+assert PPLANE_RECORD_DTYPE.itemsize == 4 * PLANE_WORDS
+
+
+class PPlaneMap(_DeviceHandle):
+    """rl_pplane_map: beam tree, sub-beams, plane tree and planes of one plane pass, on the device of the context that made them (kept alive with it)."""
+    _destroy = "rl_pplane_map_destroy"
+
+    def info(self):
+        """(beams, sub-beams, beam-tree nodes, planes, plane-tree nodes, light paths shot, radius)."""
+        v = [C.c_uint64() for _ in range(6)]
+        r = C.c_float()
+        _check(lib().rl_pplane_map_info(self.h, *[C.byref(x) for x in v], C.byref(r)))
+        return tuple(int(x.value) for x in v) + (float(r.value),)
+
+    def read(self, which):
+        """rl_pplane_map_read: (boxes [n, 6] f32, links [n, 3] u32 = skip, first, count, elements in leaf order) of which = "beams" ([n_sub, 12] f32 = o, length
+        | d, 0 | radiance, 0) or "planes" ([n_planes, 16] f32 = o, length0 | d0, length1 | d1, 0 | radiance, 0)."""
+        if which not in ("beams", "planes"):
+            raise ValueError(f"which must be 'beams' or 'planes', not {which!r}")
+        _, n_sub, n_bn, n_planes, n_pn, _, _ = self.info()
+        n_nodes, n_el, width = (n_bn, n_sub, 12) if which == "beams" else (n_pn, n_planes, 16)
+        boxes, links, el = np.zeros((n_nodes, 6), np.float32), np.zeros((n_nodes, 3), np.uint32), np.zeros((n_el, width), np.float32)
+        _check(lib().rl_pplane_map_read(self.h, 0 if which == "beams" else 1, n_nodes, abi.fptr(boxes), abi.u32ptr(links), n_el, abi.fptr(el)))
+        return boxes, links, el
+
+
+class IntegratorPhotonPlanes(_Integrator):
+    """IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: Planes } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute, seed
+    for seed the reference: surface beams and planes from the main sampler, the split, the two trees, the block seeds from the sampler the plane pass leaves,
+    the gather on reference-order streams.  A class of its own: IntegratorVolPrimitives keeps refusing every primitive but bre.  radius: the reference's
+    constant unless given.  light_streams="per_path": the records from rl_pplane_generate_paths: statistically, not seed-for-seed, the same image."""
+
+    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, radius=PHOTON_RADIUS_DEFAULT, light_streams="reference", device=0, options=None):
+        if light_streams not in LIGHT_STREAMS:
+            raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
+        super().__init__(device, options)
+        self.nb_primitive, self.max_depth, self.rr_depth, self.radius, self.light_streams = nb_primitive, max_depth, rr_depth, radius, light_streams
+        self.last_generation_stats = None
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        ctx = self._context(scene)
+        records, self.last_generation_stats = ctx.pplane_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, self.light_streams)
+        pmap = None
+        try:
+            pmap = ctx.pplane_map(records, self.radius)
+            w, h = scene.size
+            seeds = sampler.block_seeds(w, h)
+            img, self.last_stats = ctx.render_photon_planes(pmap, seeds, nb_samples, sampler.variant)
+        finally:
+            if pmap is not None:
+                pmap.close()
+            records.close()
         return img
 
 

@@ -19,6 +19,9 @@
 //               | photon-beams [-m MAX|inf] [-n MIN] [-r RR|inf] [--nb-primitive N] [--radius R] [--light-streams reference|per-path]   (IntegratorVolPrimitives with
 //                 primitives = Beams, vol_primitives.rs; a subcommand of its own: `vol-primitivies -p beam` stays refused with the other unbuilt primitives.  The
 //                 options and limits of vol-primitivies; N is 1 .. RL_BEAM_MAX; no --tree-build: the split and the beam tree are built on the host)
+//               | photon-planes [-m MAX|inf] [-n MIN] [-r RR|inf] [--nb-primitive N] [--radius R] [--light-streams reference|per-path]   (IntegratorVolPrimitives with
+//                 primitives = Planes; a subcommand of its own as photon-beams is: `vol-primitivies -p plane` stays refused.  photon-beams' options and limits;
+//                 MAX >= 4: no light path holds a plane below that; no --tree-build and no -p / -s)
 //               | plane-single [-n|--nb-primitive N] [-s|--strategy uv|ut|vt|average|discrete_mis|ualpha|cmis]   (examples/cli.rs:197-202, 664-691; needs -m;
 //                 the limits of vol-primitivies: independent sampler, reference-order streams, exact numerics, one device, one pass)
 //                 --uncorrelated: IntegratorSinglePlaneUncorrelated (uncorrelated_plane_single.rs; the reference's subcommand `uncorrelated-plane-single`, cli.rs): every
@@ -96,7 +99,7 @@ int main(int argc, char** argv) {
         if (!have_cmd) {
             if (a == "path" || a == "ao" || a == "direct" || a == "light-tracing" || a == "vpl") { have_cmd = true; cmd = a; }
             else if (a == "vol-primitivies" || a == "vol-primitives") { have_cmd = true; cmd = "vol-primitivies"; }
-            else if (a == "plane-single" || a == "photon-beams") { have_cmd = true; cmd = a; }
+            else if (a == "plane-single" || a == "photon-beams" || a == "photon-planes") { have_cmd = true; cmd = a; }
             else if (a == "-n" || a == "--nbsamples") nbsamples = std::strtoull(val().c_str(), nullptr, 10);
             else if (a == "-o" || a == "--output") output = val();
             else if (a == "-r" || a == "--random-number-generator") rng = val();
@@ -124,13 +127,13 @@ int main(int argc, char** argv) {
                 else { std::fprintf(stderr, "extra option %s is not supported by this drop-in (ats, no-shading, hvs-light, texture-light)\n", o.c_str()); return 2; }
             }
             else if (a == "-l" || a == "--log") (void)val();   // log file: nothing is logged on this path
-            else if (a == "--light-streams") { std::fprintf(stderr, "--light-streams is an option of the vpl, vol-primitivies and photon-beams subcommands: give it after the subcommand\n"); return 2; }
+            else if (a == "--light-streams") { std::fprintf(stderr, "--light-streams is an option of the vpl, vol-primitivies, photon-beams and photon-planes subcommands: give it after the subcommand\n"); return 2; }
             else if (a == "--tree-build") { std::fprintf(stderr, "--tree-build is an option of the vol-primitivies subcommand: give it after the subcommand\n"); return 2; }
             else if (a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
             else if (scene_path.empty()) scene_path = a;
-            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl`, `vol-primitivies`, `photon-beams` and `plane-single` subcommands are provided (got %s)\n", a.c_str()); return 2; }
-        } else if (a == "--light-streams" && cmd != "vpl" && cmd != "vol-primitivies" && cmd != "photon-beams") {
-            std::fprintf(stderr, "%s: --light-streams is not supported (photon-beams, vpl and vol-primitivies only)\n", cmd.c_str()); return 2;
+            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl`, `vol-primitivies`, `photon-beams`, `photon-planes` and `plane-single` subcommands are provided (got %s)\n", a.c_str()); return 2; }
+        } else if (a == "--light-streams" && cmd != "vpl" && cmd != "vol-primitivies" && cmd != "photon-beams" && cmd != "photon-planes") {
+            std::fprintf(stderr, "%s: --light-streams is not supported (photon-beams, photon-planes, vpl and vol-primitivies only)\n", cmd.c_str()); return 2;
         } else if (a == "--tree-build" && cmd != "vol-primitivies") {
             std::fprintf(stderr, "%s: --tree-build is not supported (vol-primitivies only)\n", cmd.c_str()); return 2;
         } else if (cmd == "ao") {
@@ -161,14 +164,14 @@ int main(int argc, char** argv) {
             else if (a == "--light-streams") light_streams = val();
             else if (a == "--tree-build") tree_build = val();
             else { std::fprintf(stderr, "unknown vol-primitivies option %s\n", a.c_str()); return 2; }
-        } else if (cmd == "photon-beams") {
+        } else if (cmd == "photon-beams" || cmd == "photon-planes") {
             if (a == "-m" || a == "--max-depth") max_depth = val();
             else if (a == "-n" || a == "--min-depth") (void)val();          // `_min_depth` (cli.rs:697): never read
             else if (a == "-r" || a == "--rr-depth") rr_depth = val();
             else if (a == "--nb-primitive") nb_primitive = val();
             else if (a == "--radius") radius = val();
             else if (a == "--light-streams") light_streams = val();
-            else { std::fprintf(stderr, "unknown photon-beams option %s\n", a.c_str()); return 2; }
+            else { std::fprintf(stderr, "unknown %s option %s\n", cmd.c_str(), a.c_str()); return 2; }
         } else if (cmd == "plane-single") {
             if (a == "-n" || a == "--nb-primitive") plane_nb = val();
             else if (a == "-s" || a == "--strategy") plane_strategy = val();
@@ -219,9 +222,9 @@ int main(int argc, char** argv) {
         light.device = device;
         light.options = options;
     }
-    // vpl, vol-primitivies, photon-beams: how the light paths draw (the gather stays in reference order either way)
+    // vpl, vol-primitivies, photon-beams, photon-planes: how the light paths draw (the gather stays in reference order either way)
     LightStreams light_streams_mode = LightStreams::Reference;
-    if (cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams") {
+    if (cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams" || cmd == "photon-planes") {
         if (light_streams == "per-path") light_streams_mode = LightStreams::PerPath;
         else if (light_streams != "reference") { std::fprintf(stderr, "invalid --light-streams: %s (reference or per-path)\n", light_streams.c_str()); return 2; }
     }
@@ -277,6 +280,22 @@ int main(int argc, char** argv) {
         pbeams.light_streams = light_streams_mode;
         pbeams.device = device;
         pbeams.options = options;
+    }
+    // photon-planes: photon-beams' limits, and the depth below which no plane exists
+    IntegratorPhotonPlanes pplanes;
+    if (cmd == "photon-planes") {
+        if (refused("photon-planes", RL_STREAM_REFERENCE_ORDER, true)) return 2;
+        if (!parse_count("--nb-primitive", nb_primitive, &pplanes.nb_primitive)) return 2;
+        if (pplanes.nb_primitive > (uint32_t)RL_BEAM_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", nb_primitive.c_str(), (int)RL_BEAM_MAX); return 2; }
+        if (!parse_radius(&pplanes.radius)) return 2;
+        const Medium m = parse_medium(medium);
+        if (m.sigma_a + m.sigma_s == 0.0f) { std::fprintf(stderr, "photon-planes: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n"); return 2; }
+        pplanes.max_depth = match_infinity(max_depth);
+        if (pplanes.max_depth.has_value() && *pplanes.max_depth <= 3u) { std::fprintf(stderr, "photon-planes: -m %s is too small (no light path holds a plane below a max depth of 4)\n", max_depth.c_str()); return 2; }
+        pplanes.rr_depth = match_infinity(rr_depth);
+        pplanes.light_streams = light_streams_mode;
+        pplanes.device = device;
+        pplanes.options = options;
     }
     // plane-single needs the medium
     IntegratorSinglePlane plane;
@@ -349,7 +368,7 @@ int main(int argc, char** argv) {
         }
         scene->build_emitters(use_ats);      // scene.build_emitters(use_ats) (cli.rs:432)
         IntegratorPathTracing integrator;
-        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams" || cmd == "plane-single") strategy = "all";       // (the path integrator below is not used)
+        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams" || cmd == "photon-planes" || cmd == "plane-single") strategy = "all";       // (the path integrator below is not used)
         integrator.min_depth = match_infinity(min_depth);
         integrator.max_depth = match_infinity(max_depth);
         integrator.rr_depth = match_infinity(rr_depth);
@@ -382,6 +401,8 @@ int main(int argc, char** argv) {
             img = volp.compute(sampler, *scene); elapsed_ms = volp.last_stats.render_ms;
         } else if (cmd == "photon-beams") {
             img = pbeams.compute(sampler, *scene); elapsed_ms = pbeams.last_stats.render_ms;
+        } else if (cmd == "photon-planes") {
+            img = pplanes.compute(sampler, *scene); elapsed_ms = pplanes.last_stats.render_ms;
         } else if (cmd == "plane-single") {
             if (plane_uncorrelated) { img = uplane.compute(sampler, *scene); elapsed_ms = uplane.last_stats.render_ms; }
             else { img = plane.compute(sampler, *scene); elapsed_ms = plane.last_stats.render_ms; }

@@ -406,6 +406,41 @@ struct IntegratorPhotonBeams {
     }
 };
 
+// IntegratorVolPrimitives with primitives = Planes (vol_primitives.rs:256-435, 608-790) as a struct of its own, for the reason IntegratorPhotonBeams is one, +
+// Integrator::compute, seed for seed the reference, with IntegratorPhotonBeams' host sequence: the surface beams and the planes from the main sampler
+// (rl_pplane_generate: the light paths of rl_beam_generate stored by convert_beams(true, ..) and convert_planes), the split and the two trees
+// (rl_pplane_map_build), the block seeds from the sampler the generation leaves, the gather on reference-order streams (rl_render_photon_planes).
+// light_streams = PerPath: rl_pplane_generate_paths.
+using PPlaneSetHandle = Handle<rl_pplane_set, rl_pplane_destroy>;
+using PPlaneMapHandle = Handle<rl_pplane_map, rl_pplane_map_destroy>;
+struct IntegratorPhotonPlanes {
+    uint32_t nb_primitive = 128;
+    std::optional<uint32_t> max_depth, rr_depth = 0u;
+    float radius = RL_PHOTON_RADIUS_DEFAULT;
+    LightStreams light_streams{LightStreams::Reference};
+    int device = 0;
+    Options options;
+    rl_render_stats last_stats{}, last_generation_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        RenderContext ctx(scene, device, options);
+        rl_path_params p;
+        rl_path_params_default(&p);
+        p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
+        p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
+        p.stream_mode = RL_STREAM_REFERENCE_ORDER;
+        p.seed_variant = sampler.variant;
+        rl_pplane_set* generated = nullptr;
+        check((light_streams == LightStreams::PerPath ? rl_pplane_generate_paths : rl_pplane_generate)(ctx, &p, nb_primitive, &sampler.rnd, &generated, &last_generation_stats), "photon-planes");
+        const PPlaneSetHandle records(generated);
+        rl_pplane_map* built = nullptr;
+        check(rl_pplane_map_build(ctx, records.get(), radius, &built), "photon-planes");
+        const PPlaneMapHandle map(built);
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        check(rl_render_photon_planes(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "photon-planes");
+        return std::move(ctx.img);
+    }
+};
+
 // struct IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs:280-294) + Integrator::compute, seed for seed the reference:
 // the planes from the main sampler (rl_plane_generate), the plane tree (rl_plane_map_build), the block seeds from the sampler the generation leaves, the
 // gather on reference-order streams (rl_render_plane_single).  generate = Lanes and tree_build = Device set the context options plane_generate_lanes and

@@ -35,8 +35,9 @@ struct GatherKind {
     const char* map;                            // and its map's
     int (*check_scene)(const rl_context*);
     int n_counters;                             // the leaf's walk counters (gather.hip.h) ...
-    int lo[2], hi[2];                           // ... and the statistics rows of their low and high parts
+    int lo[3], hi[3];                           // ... and the statistics rows of their low and high parts
     uint64_t draws = 2;                         // draws per camera sample: the 256 lanes of a block enter its stream with 32-bit jumps
+    bool derive_samples = false;                // the kernel's counters take every statistics row: camera_samples = owned pixels * spp, which is what the lanes count
 };
 // rl_render_bre / rl_render_plane_single: the argument checks, the frame, one launch — launch(lds_scene, grid, lds_bytes, stream, rc, stc) — between two events,
 // the finish.  stats: reserved[0] = nodes entered, reserved[1 + k] = the leaf's counter k; extension rays and draws follow from the samples (one ray, 2 draws each)
@@ -68,6 +69,7 @@ static int render_gather(rl_context* ctx, const GatherKind& kind, const rl_conte
     if ((rcode = fr.download()) != RL_OK) return rcode;
     if (stats) {
         // (the rows of vertices / extension_rays / shadow_rays carried the high parts of the walk counters)
+        if (kind.derive_samples) stats->camera_samples = (uint64_t)fr.n_pixels * spp;
         stats->reserved[0] = gather_merge24(fr.totals, STAT_GATHER_NODES, STAT_GATHER_NODES_HI);
         for (int k = 0; k < kind.n_counters; k++) stats->reserved[1 + k] = gather_merge24(fr.totals, kind.lo[k], kind.hi[k]);
         stats->vertices = 0; stats->extension_rays = stats->camera_samples; stats->shadow_rays = 0; stats->rng_draws = 2 * stats->camera_samples;

@@ -40,6 +40,7 @@ enum KnobId {
     K_PLANE_GENERATE_LANES, // rl_plane_generate forwards to rl_plane_generate_lanes (one lane per iteration; the same set, sampler and counters)
     K_PLANE_TREE_DEVICE,    // rl_plane_map_build forwards to rl_plane_map_build_device (the same map from device kernels)
     K_PLANE_TREE_GROUP_PLANES, // rl_plane_map_build_device: a workgroup finishes ranges of at most this many planes (tests, as photon_tree_group_photons)
+    K_PPLANE_TREE_DEVICE,   // rl_pplane_map_build builds its plane tree with the device kernels of rl_plane_map_build_device (the same map)
     // read when the context is created only
     K_FORCE_STREAMING,      // keep small scenes out of LDS (the kernels that stream the BVH, on scenes the oracle finishes in seconds)
     K_GENERIC_LIGHTS,       // do not specialise the NEE code for area-light-only scenes
@@ -56,7 +57,7 @@ struct Knobs {
             "fused_dynamic", "fused_tail_blocks", "fused_tail_split", "fused_tail_no_buffer_test", "eval_split", "eval_min", "eval_div", "no_events", "queue_debug",
             "spec_group", "spec_sub", "spec_cap", "spec_probe", "spec_lead", "spec_lead_max", "spec_lead_var", "spec_extra", "spec_dense", "spec_dense_frac",
             "spec_probe_every", "spec_ks", "spec_ke", "spec_serial_ratio", "spec_no_trivial", "spec_lds_limit_test", "spec_stats", "spec_wave_times", "spec_lds_levels", "vpl_batch_paths", "photon_tree_group_photons",
-            "plane_generate_lanes", "plane_tree_device", "plane_tree_group_planes",
+            "plane_generate_lanes", "plane_tree_device", "plane_tree_group_planes", "pplane_tree_device",
             "force_streaming", "generic_lights"};
         return names[k];
     }

@@ -1,5 +1,5 @@
 // launch.h — host-side launchers of the kernel families that live in their own translation units (fused_*.hip, fusedq_*.hip, fused_strat_*.hip,
-// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, beamgen_*.hip, beam_*.hip, plane_*.hip, uplane_*.hip), so that the families compile in parallel, and
+// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, beamgen_*.hip, beam_*.hip, pplanegen_*.hip, pplane_*.hip, plane_*.hip, uplane_*.hip), so that the families compile in parallel, and
 // the dispatcher every one of them maps its run-time arguments to template arguments with (with_bsdf, with_flag).  Launch errors are picked up by
 // the caller's hipGetLastError().
 #pragma once
@@ -110,6 +110,25 @@ struct BeamConst {
     float norm_photon;                  // 1 / paths shot
 };
 
+// The photon planes (pplanegen.hip.h, pplane.hip.h).  The plane pass stores two kinds of record: the planes go where VplConst / VplPathsConst say, the surface
+// beams where PPlaneGenConst says.  The gather walks two trees: the beam tree with BeamLeaf's constants, then the plane tree.
+// where the two generation kernels put the beam count: behind the counters they share with the beam pass
+enum { PPLANE_GEN_BEAMS = VPL_GEN_WORDS, PPLANE_GEN_WORDS = VPL_GEN_WORDS + 1, PPLANE_PATH_BEAMS = VPL_PATH_WORDS, PPLANE_PATH_WORDS = VPL_PATH_WORDS + 1 };
+struct PPlaneGenConst {
+    unsigned* beam_words;               // [beam_cap][kBeamWords] (records beyond beam_cap are not written)
+    unsigned beam_cap;
+    unsigned beam_max;                  // k_pplane_generate: the loop ends once more beams than this are stored
+    const unsigned* beam_offsets;       // k_pplane_shoot's write pass: [path] the record index the path's first beam gets
+};
+// the gather's statistics rows: all STAT_COUNT = 8, the samples being derived on the host (pplane.hip.h)
+enum { STAT_PPLANE_BEAMS = 6, STAT_PPLANE_BEAMS_HI = 3, STAT_PPLANE_ISECT = 7, STAT_PPLANE_ISECT_HI = 2, STAT_PPLANE_VISIBLE = 0, STAT_PPLANE_VISIBLE_HI = 4 };
+struct PPlaneConst {
+    BeamConst beam;                     // the beam tree, the sub-beams and PhotonBeam's constants; beam.norm_photon serves the planes too
+    const float4* nodes;                // the plane tree, [n_nodes][2]: p_min.xyz, p_max.x | p_max.yz, skip, first << 3 | count
+    const float4* planes;               // [n_planes][4]: o, length0 | d0, length1 | d1, 0 | radiance, 0
+    unsigned n_nodes;
+};
+
 // IntegratorSinglePlane (plane.hip.h): the rectangular lights, the generation's constants, and for the gather the plane tree in visiting order with the
 // planes in leaf order (host/planetree.cpp)
 struct PlaneLight { float o[3], u_l, u[3], v_l, v[3], pad0, n[3], pad1, emission[3], pad2; };      // RectangularLightSource, 5 float4
@@ -211,6 +230,13 @@ void launch_beamgen_stream(int which, int mat, dim3 grid, dim3 block, size_t lds
                            const VplConst& vc, const VplPathsConst& pc);
 void launch_beam_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BeamConst& bc);
 void launch_beam_stream(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const BeamConst& bc);
+// The photon planes: the plane pass (pplanegen.hip.h; which and mat as for launch_beamgen_*, xc: where the surface beams go) and k_pplane_gather over the owned blocks (pplane.hip.h)
+void launch_pplanegen_lds(int which, int mat, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc,
+                          const VplConst& vc, const VplPathsConst& pc, const PPlaneGenConst& xc);
+void launch_pplanegen_stream(int which, int mat, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc,
+                             const VplConst& vc, const VplPathsConst& pc, const PPlaneGenConst& xc);
+void launch_pplane_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PPlaneConst& pc);
+void launch_pplane_stream(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PPlaneConst& pc);
 // IntegratorSinglePlane (plane.hip.h): k_plane_generate on one lane, k_plane_generate_lanes on one lane per iteration (plane_generate.hip); k_plane_gather over the owned blocks, mode = PLANE_MODE_*
 void launch_plane_generate(hipStream_t st, const PlaneGenConst& gc);
 void launch_plane_generate_lanes(hipStream_t st, const PlaneGenConst& gc, unsigned n_gen);      // k_plane_generate_lanes: one lane per iteration, n_gen of them

@@ -1053,14 +1053,32 @@ struct LightPassKind {
     const char* too_few;              // rl_last_error when RL_VPL_MAX_PATHS paths store fewer than nb records
 };
 static const LightPassKind kVplPass{RL_VPL_WORDS, "vpl: fewer than nb_vpl VPLs stored within RL_VPL_MAX_PATHS light paths"};
+// A pass that stores a second kind of record along the same paths (the photon planes' surface beams, pplane_render.hip.h) hands both sequences one of these.
+// The first kind is the one the shooting stops on; the second is not bounded by it, so the pass is refused once more than max_records of it arise before the
+// first kind's count is reached.  A path stores at most kDepthCap of them.  The sequences fill the last three members for the pass's launch to read.
+struct LightPassSecond {
+    unsigned rec_words;               // u32 per record
+    unsigned max_records;
+    const char* too_many;             // rl_last_error of that refusal (RL_ERR_UNSUPPORTED)
+    HipBuffer<unsigned>* words;       // on RL_OK [*n_records][rec_words]
+    uint64_t* n_records;
+    unsigned cap = 0;                 // records *words has room for
+    unsigned* d_words = nullptr;
+    const unsigned* d_offsets = nullptr;      // the per-path write pass: [path] the index of the path's first record
+};
 // The serial pass (k_vpl_generate, k_beam_generate): one lane on the main sampler's stream.  launch(lds_bytes, rc, stc, vc); on RL_OK *words holds *n_records
 // records of *n_paths paths and `sampler` is the one the lane left
 template <class Launch>
 static int light_pass_serial(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, const LightPassKind& kind, rl_sampler* sampler,
-                             HipBuffer<unsigned>* words, uint64_t* n_records, uint64_t* n_paths, rl_render_stats* stats, Launch&& launch) {
+                             HipBuffer<unsigned>* words, uint64_t* n_records, uint64_t* n_paths, rl_render_stats* stats, Launch&& launch, LightPassSecond* second = nullptr) {
     int rcode;
     const unsigned cap = nb_vpl + kDepthCap + 1u;        // the last path adds at most one record per vertex
     if ((rcode = words->ensure((size_t)cap * kind.rec_words)) != RL_OK) return rcode;
+    if (second) {                                        // the lane stops once more than max_records are stored: one path beyond that at most
+        second->cap = second->max_records + kDepthCap + 1u;
+        if ((rcode = second->words->ensure((size_t)second->cap * second->rec_words)) != RL_OK) return rcode;
+        second->d_words = second->words->get();
+    }
     RenderConst rc{};
     rc.has_max = params->has_max_depth; rc.max_depth = params->max_depth;
     rc.has_rr = params->has_rr_depth; rc.rr_depth = params->rr_depth;
@@ -1072,12 +1090,14 @@ static int light_pass_serial(rl_context* ctx, const rl_path_params* params, uint
     if ((rcode = stack_conf(ctx, 256, &stc)) != RL_OK) return rcode;
     const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);
     LaneRun run;
-    if ((rcode = run_one_lane(ctx->stream, stats != nullptr && !ctx->knobs.has(K_NO_EVENTS), sampler, VPL_GEN_WORDS, &run, [&](unsigned long long* d_gen) {
+    if ((rcode = run_one_lane(ctx->stream, stats != nullptr && !ctx->knobs.has(K_NO_EVENTS), sampler, VPL_GEN_WORDS + (second ? 1 : 0), &run, [&](unsigned long long* d_gen) {
             vc.gen_state = d_gen; vc.gen_out = d_gen + 4;
             launch(lds, rc, stc, vc);
         })) != RL_OK) return rcode;
     const unsigned long long* g = run.words.data() + 4;
+    if (g[VPL_GEN_VPLS] < nb_vpl && second && g[VPL_GEN_WORDS] > second->max_records) { rl_set_error(second->too_many); return RL_ERR_UNSUPPORTED; }
     if (g[VPL_GEN_VPLS] < nb_vpl) { rl_set_error(kind.too_few); return RL_ERR_UNSUPPORTED; }
+    if (second) *second->n_records = g[VPL_GEN_WORDS];          // the lane's counter beyond the shared five
     for (int i = 0; i < 4; i++) sampler->s[i] = run.words[i];
     *n_records = g[VPL_GEN_VPLS]; *n_paths = g[VPL_GEN_PATHS];
     if (stats) {
@@ -1109,9 +1129,10 @@ static constexpr unsigned kVplFirstBatch = 4096, kVplShootGroupsPerCu = 2;
 // launch(write, groups, lds_bytes, rc, stc, pc) on ctx->stream (k_vpl_shoot, k_beam_shoot); the results as light_pass_serial leaves them
 template <class Launch>
 static int light_pass_paths(rl_context* ctx, const rl_path_params* params, uint32_t nb_vpl, int option_vpl, const LightPassKind& kind, rl_sampler* sampler,
-                            HipBuffer<unsigned>* words, uint64_t* n_records, uint64_t* n_paths, rl_render_stats* stats, Launch&& launch) {
+                            HipBuffer<unsigned>* words, uint64_t* n_records, uint64_t* n_paths, rl_render_stats* stats, Launch&& launch, LightPassSecond* second = nullptr) {
     int rcode;
     const hipStream_t st = ctx->stream;
+    const size_t cw = VPL_PATH_WORDS + (second ? 1 : 0);     // count words per path: a second kind of record adds its count behind the shared four
     const long long forced = ctx->knobs.has(K_VPL_BATCH_PATHS) ? std::max<long long>(1, ctx->knobs.i(K_VPL_BATCH_PATHS, 0)) : 0;
     int cus = 256;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) { (void)hipGetLastError(); cus = 256; }
@@ -1143,9 +1164,9 @@ static int light_pass_paths(rl_context* ctx, const rl_path_params* params, uint3
     };
     // ---- count rounds
     HipBuffer<unsigned> d_counts;
-    std::vector<unsigned> counts;                    // [path][VPL_PATH_WORDS], every path walked so far
-    std::vector<unsigned> offsets;                   // [path] exclusive prefix sum of the record counts, paths 0 .. K-1 once K is known
-    unsigned long long stored = 0;
+    std::vector<unsigned> counts;                    // [path][cw], every path walked so far
+    std::vector<unsigned> offsets, offsets2;         // [path] exclusive prefix sum of the record counts (of the second kind's), paths 0 .. K-1 once K is known
+    unsigned long long stored = 0, stored2 = 0;
     unsigned walked = 0, K = 0;
     while (K == 0 && walked < (unsigned)RL_VPL_MAX_PATHS) {
         unsigned batch;
@@ -1157,27 +1178,35 @@ static int light_pass_paths(rl_context* ctx, const rl_path_params* params, uint3
             batch = stored ? (unsigned)std::min<double>((double)RL_VPL_MAX_PATHS, (double)(nb_vpl - stored) / per_path * 1.125 + 64.0) : 2u * walked;
         }
         batch = std::min(batch, (unsigned)RL_VPL_MAX_PATHS - walked);
-        if ((rcode = d_counts.ensure((size_t)batch * VPL_PATH_WORDS)) != RL_OK) return rcode;
+        if ((rcode = d_counts.ensure((size_t)batch * cw)) != RL_OK) return rcode;
         pc.counts = d_counts.get();
         if ((rcode = shoot(false, walked, batch)) != RL_OK) return rcode;
-        counts.resize((size_t)(walked + batch) * VPL_PATH_WORDS);
-        HIP_OK(hipMemcpyAsync(counts.data() + (size_t)walked * VPL_PATH_WORDS, d_counts.get(), (size_t)batch * VPL_PATH_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        counts.resize((size_t)(walked + batch) * cw);
+        HIP_OK(hipMemcpyAsync(counts.data() + (size_t)walked * cw, d_counts.get(), (size_t)batch * cw * sizeof(unsigned), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         HIP_OK(hipGetLastError());
         ev.add();
         rounds++;
         for (unsigned k = walked; k < walked + batch && K == 0; k++) {            // the cut: `while stored < nb` on this path sequence
             offsets.push_back((unsigned)stored);
-            stored += counts[(size_t)k * VPL_PATH_WORDS + VPL_PATH_RECORDS];
+            stored += counts[(size_t)k * cw + VPL_PATH_RECORDS];
+            if (second) { offsets2.push_back((unsigned)stored2); stored2 += counts[(size_t)k * cw + VPL_PATH_WORDS]; }
             if (stored >= nb_vpl) K = k + 1u;
+            else if (second && stored2 > second->max_records) { rl_set_error(second->too_many); return RL_ERR_UNSUPPORTED; }      // where the serial lane stops
         }
         walked += batch;
     }
     if (K == 0) { rl_set_error(kind.too_few); return RL_ERR_UNSUPPORTED; }
     // ---- write pass: paths 0 .. K-1 again, each to its own offset
-    HipBuffer<unsigned> d_offsets;
+    HipBuffer<unsigned> d_offsets, d_offsets2;
     if ((rcode = words->ensure((size_t)stored * kind.rec_words)) != RL_OK || (rcode = d_offsets.ensure(K)) != RL_OK) return rcode;
     HIP_OK(hipMemcpyAsync(d_offsets.get(), offsets.data(), (size_t)K * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    if (second) {
+        if ((rcode = second->words->ensure((size_t)stored2 * second->rec_words)) != RL_OK || (rcode = d_offsets2.ensure(K)) != RL_OK) return rcode;
+        HIP_OK(hipMemcpyAsync(d_offsets2.get(), offsets2.data(), (size_t)K * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        second->cap = (unsigned)stored2; second->d_words = second->words->get(); second->d_offsets = d_offsets2.get();
+        *second->n_records = stored2;
+    }
     pc.cap = (unsigned)stored; pc.vpl_words = words->get(); pc.offsets = d_offsets.get(); pc.counts = nullptr;
     if ((rcode = shoot(true, 0u, K)) != RL_OK) return rcode;
     HIP_OK(hipStreamSynchronize(st));
@@ -1189,7 +1218,7 @@ static int light_pass_paths(rl_context* ctx, const rl_path_params* params, uint3
         std::memset(stats, 0, sizeof(*stats));
         stats->camera_samples = K;
         for (unsigned k = 0; k < K; k++) {
-            const unsigned* c = &counts[(size_t)k * VPL_PATH_WORDS];
+            const unsigned* c = &counts[k * cw];
             stats->vertices += c[VPL_PATH_VERTICES]; stats->extension_rays += c[VPL_PATH_EXT]; stats->rng_draws += c[VPL_PATH_DRAWS];
         }
         stats->iterations = rounds; stats->kernel_launches = launches; stats->ms_prepass = ev.ms;
@@ -1306,6 +1335,7 @@ extern "C" int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_pa
 
 #include "gather_render.hip.h"
 #include "beam_render.hip.h"
+#include "pplane_render.hip.h"
 
 // ---- batched Acceleration::{trace, visible}
 namespace {
