@@ -419,7 +419,7 @@ int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_path_params* 
                   float* out_rgb, int out_is_device, void* stream, rl_render_stats* stats);
 
 /* ---- IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: BRE } (src/integrators/explicit/vol_primitives.rs; CLI `vol-primitivies -p bre`,
- * examples/cli.rs:189-196, 692-716): the beam radiance estimate.  VRL is not built; beams and planes have entry points of their own (rl_beam_*, rl_pplane_*, below).
+ * examples/cli.rs:189-196, 692-716): the beam radiance estimate.  Beams, planes and VRL have entry points of their own (rl_beam_*, rl_pplane_*, rl_vrl_*, below).
  * The photons are the records of a set generated by rl_vpl_generate with option_vpl = RL_VPL_VOLUME and nb_vpl = nb_primitive: convert_photons
  * (vol_primitives.rs:525-565) stores at every Vertex::Volume what convert_vpl stores under `-v volume`, from the same light paths, and the shooting stops on the
  * same count — words 4..6 = pos, 7..9 = radiance, 10..12 = d_in; the set's path count is nb_path_shot.
@@ -557,6 +557,33 @@ int rl_pplane_map_read(const rl_pplane_map* map, int which, size_t node_capacity
 void rl_pplane_map_destroy(rl_pplane_map* map);
 int rl_render_photon_planes(rl_context* ctx, const rl_pplane_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
                             const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
+
+/* ---- Virtual ray lights: IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: VRL } (src/integrators/explicit/vol_primitives.rs:201-253,
+ * 608-699, 741-764), behind entry points and a CLI word (`virtual-ray-lights`) of their own: `vol-primitivies -p vrl` stays refused.
+ * The beams are rl_beam_generate's / rl_beam_generate_paths': the VRL arm shoots with convert_beams(false, ..) and stops on the same count.
+ * rl_vrl_map_build (vol_primitives.rs:632-699): the beams whose word 7 bit 0 (from_surface) is clear are the VRLs, in storing order and unsplit; avg = (their
+ * channel_max(radiance) summed in f32 in that order) / n_vrl as f32, rr = ((channel_max(radiance) / avg) * 0.01).min(1.0) (f32::min returns the operand that
+ * is no NaN: avg = 0 gives rr = 1).  The surface beams go through rl_beam_map_build's split and tree; avg_split is taken over them alone.  rl_vrl_map_build_words:
+ * the same from caller-supplied beam records.  Refused: what rl_beam_map_build_words refuses, with its codes; no surface beam among the records, or a VRL record
+ * with a non-finite o, d, length or radiance (RL_ERR_INVALID_ARGUMENT).  No VRL at all is valid (max_depth = 2).
+ * rl_vrl_map_info: surface beams, their sub-beams, tree nodes, VRLs, light paths, radius, avg (0 when there is no VRL).  rl_vrl_map_read: node_boxes / node_links
+ * and beams as rl_beam_map_read writes them, then vrls [n_vrl][12] f32 = o, length | d, rr | radiance, 0 in storing order (vrls may be NULL when there is none).
+ * rl_render_vrl (vol_primitives.rs:741-764): rl_render_beams' camera loop, streams, shards and refusals; per camera sample c = the surface beams' contributions
+ * in gather order, then for each VRL in order `if rr >= next()`: t_cam = (tfar - 1e-4) * next() + 1e-4, t_vrl = length * next(), one visibility ray
+ * visible(ray.o + ray.d * t_cam, o + d * t_vrl), c += ((radiance * (sigma_s / 4 PI) * (sigma_s / 4 PI) * transmittance(t_cam) * transmittance(dist) * (length *
+ * (tfar - 1e-4)) / (dist * dist)) / rr) * (1 / nb_path_shot), left to right with Color's guards.  A sample takes 2 + n_vrl + 2 A draws (A = the VRLs that passed
+ * its roulette), so a first kernel walks every block's stream for the draw at which each pixel starts.  RL_ERR_UNSUPPORTED when 256 * spp * (2 + 3 * n_vrl)
+ * reaches 2^32.  rng_draws = the draws walked; reserved[0] = beam-tree nodes entered, reserved[1] = beams accepted, reserved[2] = VRLs that passed the roulette
+ * (= shadow_rays), reserved[3] = of those, visible; ms_prepass = the first kernel, ms_other = both. */
+typedef struct rl_vrl_map rl_vrl_map;           /* opaque: beam tree and sub-beams of the surface beams, and the VRLs, on the context's device */
+int rl_vrl_map_build(rl_context* ctx, const rl_beam_set* set, float radius, rl_vrl_map** out);
+int rl_vrl_map_build_words(rl_context* ctx, const uint32_t* words, size_t n_beams, uint64_t n_paths, float radius, rl_vrl_map** out);
+int rl_vrl_map_info(const rl_vrl_map* map, uint64_t* n_surface, uint64_t* n_sub, uint64_t* n_nodes, uint64_t* n_vrl, uint64_t* n_paths, float* radius, float* avg);
+int rl_vrl_map_read(const rl_vrl_map* map, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t beam_capacity, float* beams, size_t vrl_capacity,
+                    float* vrls);
+void rl_vrl_map_destroy(rl_vrl_map* map);
+int rl_render_vrl(rl_context* ctx, const rl_vrl_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
+                  const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
 
 /* ---- IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs; CLI `plane-single`, examples/cli.rs:197-202, 664-691): single
  * scattering from rectangular area lights, estimated with photon planes under one of seven sampling strategies.

@@ -50,7 +50,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_pplane_generate", "rl_pplane_generate_paths", "rl_pplane_info", "rl_pplane_read", "rl_pplane_destroy", "rl_pplane_map_build", "rl_pplane_map_build_words", "rl_pplane_map_info", "rl_pplane_map_read", "rl_pplane_map_destroy", "rl_render_photon_planes", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_pplane_generate", "rl_pplane_generate_paths", "rl_pplane_info", "rl_pplane_read", "rl_pplane_destroy", "rl_pplane_map_build", "rl_pplane_map_build_words", "rl_pplane_map_info", "rl_pplane_map_read", "rl_pplane_map_destroy", "rl_render_photon_planes", "rl_vrl_map_build", "rl_vrl_map_build_words", "rl_vrl_map_info", "rl_vrl_map_read", "rl_vrl_map_destroy", "rl_render_vrl", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -151,6 +151,13 @@ def lib():
     L.rl_beam_map_destroy.argtypes = [vp]
     L.rl_beam_map_destroy.restype = None
     L.rl_render_beams.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
+    L.rl_vrl_map_build.argtypes = [vp, vp, C.c_float, C.POINTER(vp)]
+    L.rl_vrl_map_build_words.argtypes = [vp, u32p, C.c_size_t, C.c_uint64, C.c_float, C.POINTER(vp)]
+    L.rl_vrl_map_info.argtypes = [vp, u64p, u64p, u64p, u64p, u64p, f32p, f32p]
+    L.rl_vrl_map_read.argtypes = [vp, C.c_size_t, f32p, u32p, C.c_size_t, f32p, C.c_size_t, f32p]
+    L.rl_vrl_map_destroy.argtypes = [vp]
+    L.rl_vrl_map_destroy.restype = None
+    L.rl_render_vrl.argtypes = L.rl_render_beams.argtypes
     L.rl_pplane_generate.argtypes = [vp, C.POINTER(abi.PathParams), C.c_uint32, C.POINTER(abi.Sampler), C.POINTER(vp), C.POINTER(abi.RenderStats)]
     L.rl_pplane_generate_paths.argtypes = L.rl_pplane_generate.argtypes
     L.rl_pplane_info.argtypes = [vp, u64p, u64p, u64p]
@@ -650,6 +657,26 @@ class Context(_ImageCalls):
         """The photon beams' gather (vol_primitives.rs:140-199, 705-790) through rl_render_beams: (image HxWx3 f32, stats dict).  stats: nodes_entered /
         beams_accepted = reserved[0] / reserved[1], ms_other = the gather kernel."""
         return self._render_gather(lib().rl_render_beams, beams.h, seeds, spp, seed_variant, shard_index, shard_count, ("nodes_entered", "beams_accepted"))
+
+    def vrl_map(self, beams: "BeamSet", radius=PHOTON_RADIUS_DEFAULT):
+        """rl_vrl_map_build: the beams of a beam pass partitioned by from_surface — the surface beams split and sorted into the beam tree, the others kept in
+        storing order as VRLs with their roulette probabilities — and uploaded."""
+        h = C.c_void_p()
+        _check(lib().rl_vrl_map_build(self.h, beams.h, radius, C.byref(h)))
+        return VrlMap(h, self)
+
+    def vrl_map_from_words(self, words, n_paths, radius=PHOTON_RADIUS_DEFAULT):
+        """rl_vrl_map_build_words: Context.vrl_map over caller-supplied beam records ([n, BEAM_WORDS] u32) of n_paths light paths."""
+        w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, BEAM_WORDS)
+        h = C.c_void_p()
+        _check(lib().rl_vrl_map_build_words(self.h, abi.u32ptr(w), w.shape[0], n_paths, radius, C.byref(h)))
+        return VrlMap(h, self)
+
+    def render_vrl(self, vmap: "VrlMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
+        """The virtual ray lights' gather (vol_primitives.rs:201-253, 741-764) through rl_render_vrl: (image HxWx3 f32, stats dict).  stats: nodes_entered /
+        beams_accepted / vrl_accepted / vrl_visible = reserved[0 .. 3], ms_prepass = the chain pass, ms_other = both kernels."""
+        return self._render_gather(lib().rl_render_vrl, vmap.h, seeds, spp, seed_variant, shard_index, shard_count,
+                                   ("nodes_entered", "beams_accepted", "vrl_accepted", "vrl_visible"))
 
     def pplane_generate(self, sampler: "IndependentSampler", nb_primitive=128, max_depth=None, rr_depth=0, streams="reference"):
         """The photon planes' plane pass (vol_primitives.rs:376-523, 608-630): (PPlaneSet, stats dict).  The light paths of Context.beam_generate, stored as
@@ -1151,6 +1178,56 @@ class IntegratorPhotonBeams(_Integrator):
         finally:
             if bmap is not None:
                 bmap.close()
+            beams.close()
+        return img
+
+
+class VrlMap(_DeviceHandle):
+    """rl_vrl_map: beam tree and sub-beams of the surface beams, and the VRLs, of one beam pass, on the device of the context that made them (kept alive with it)."""
+    _destroy = "rl_vrl_map_destroy"
+
+    def info(self):
+        """(surface beams, sub-beams, tree nodes, VRLs, light paths shot, radius, avg)."""
+        v = [C.c_uint64() for _ in range(5)]
+        r, a = C.c_float(), C.c_float()
+        _check(lib().rl_vrl_map_info(self.h, *[C.byref(x) for x in v], C.byref(r), C.byref(a)))
+        return tuple(int(x.value) for x in v) + (float(r.value), float(a.value))
+
+    def read(self):
+        """rl_vrl_map_read: (boxes [n, 6] f32, links [n, 3] u32 = skip, first, count, beams [n_sub, 12] f32 in leaf order, vrls [n_vrl, 12] f32 = o, length | d, rr
+        | radiance, 0 in storing order)."""
+        _, n_sub, n_nodes, n_vrl, _, _, _ = self.info()
+        boxes, links = np.zeros((n_nodes, 6), np.float32), np.zeros((n_nodes, 3), np.uint32)
+        beams, vrls = np.zeros((n_sub, 12), np.float32), np.zeros((n_vrl, 12), np.float32)
+        _check(lib().rl_vrl_map_read(self.h, n_nodes, abi.fptr(boxes), abi.u32ptr(links), n_sub, abi.fptr(beams), n_vrl, abi.fptr(vrls)))
+        return boxes, links, beams, vrls
+
+
+class IntegratorVirtualRayLights(_Integrator):
+    """IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: VRL } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute, seed for
+    seed the reference: the beams from the main sampler, the partition, the split and tree of the surface beams, the block seeds from the sampler the beam pass
+    leaves, the gather on reference-order streams.  A class of its own: IntegratorVolPrimitives keeps refusing every primitive but bre.  radius: the reference's
+    constant unless given.  light_streams="per_path": the beams from rl_beam_generate_paths: statistically, not seed-for-seed, the same image."""
+
+    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, radius=PHOTON_RADIUS_DEFAULT, light_streams="reference", device=0, options=None):
+        if light_streams not in LIGHT_STREAMS:
+            raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
+        super().__init__(device, options)
+        self.nb_primitive, self.max_depth, self.rr_depth, self.radius, self.light_streams = nb_primitive, max_depth, rr_depth, radius, light_streams
+        self.last_generation_stats = None
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        ctx = self._context(scene)
+        beams, self.last_generation_stats = ctx.beam_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, self.light_streams)
+        vmap = None
+        try:
+            vmap = ctx.vrl_map(beams, self.radius)
+            w, h = scene.size
+            seeds = sampler.block_seeds(w, h)
+            img, self.last_stats = ctx.render_vrl(vmap, seeds, nb_samples, sampler.variant)
+        finally:
+            if vmap is not None:
+                vmap.close()
             beams.close()
         return img
 

@@ -22,6 +22,9 @@
 //               | photon-planes [-m MAX|inf] [-n MIN] [-r RR|inf] [--nb-primitive N] [--radius R] [--light-streams reference|per-path]   (IntegratorVolPrimitives with
 //                 primitives = Planes; a subcommand of its own as photon-beams is: `vol-primitivies -p plane` stays refused.  photon-beams' options and limits;
 //                 MAX >= 4: no light path holds a plane below that; no --tree-build and no -p / -s)
+//               | virtual-ray-lights [-m MAX|inf] [-n MIN] [-r RR|inf] [--nb-primitive N] [--radius R] [--light-streams reference|per-path]   (IntegratorVolPrimitives
+//                 with primitives = VRL; a subcommand of its own as photon-beams is: `vol-primitivies -p vrl` stays refused.  photon-beams' options and limits: the
+//                 beams are its beam pass's, the ones that leave a volume vertex are the VRLs)
 //               | plane-single [-n|--nb-primitive N] [-s|--strategy uv|ut|vt|average|discrete_mis|ualpha|cmis]   (examples/cli.rs:197-202, 664-691; needs -m;
 //                 the limits of vol-primitivies: independent sampler, reference-order streams, exact numerics, one device, one pass)
 //                 --uncorrelated: IntegratorSinglePlaneUncorrelated (uncorrelated_plane_single.rs; the reference's subcommand `uncorrelated-plane-single`, cli.rs): every
@@ -99,7 +102,7 @@ int main(int argc, char** argv) {
         if (!have_cmd) {
             if (a == "path" || a == "ao" || a == "direct" || a == "light-tracing" || a == "vpl") { have_cmd = true; cmd = a; }
             else if (a == "vol-primitivies" || a == "vol-primitives") { have_cmd = true; cmd = "vol-primitivies"; }
-            else if (a == "plane-single" || a == "photon-beams" || a == "photon-planes") { have_cmd = true; cmd = a; }
+            else if (a == "plane-single" || a == "photon-beams" || a == "photon-planes" || a == "virtual-ray-lights") { have_cmd = true; cmd = a; }
             else if (a == "-n" || a == "--nbsamples") nbsamples = std::strtoull(val().c_str(), nullptr, 10);
             else if (a == "-o" || a == "--output") output = val();
             else if (a == "-r" || a == "--random-number-generator") rng = val();
@@ -127,13 +130,13 @@ int main(int argc, char** argv) {
                 else { std::fprintf(stderr, "extra option %s is not supported by this drop-in (ats, no-shading, hvs-light, texture-light)\n", o.c_str()); return 2; }
             }
             else if (a == "-l" || a == "--log") (void)val();   // log file: nothing is logged on this path
-            else if (a == "--light-streams") { std::fprintf(stderr, "--light-streams is an option of the vpl, vol-primitivies, photon-beams and photon-planes subcommands: give it after the subcommand\n"); return 2; }
+            else if (a == "--light-streams") { std::fprintf(stderr, "--light-streams is an option of the vpl, vol-primitivies, photon-beams, photon-planes and virtual-ray-lights subcommands: give it after the subcommand\n"); return 2; }
             else if (a == "--tree-build") { std::fprintf(stderr, "--tree-build is an option of the vol-primitivies subcommand: give it after the subcommand\n"); return 2; }
             else if (a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
             else if (scene_path.empty()) scene_path = a;
-            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl`, `vol-primitivies`, `photon-beams`, `photon-planes` and `plane-single` subcommands are provided (got %s)\n", a.c_str()); return 2; }
-        } else if (a == "--light-streams" && cmd != "vpl" && cmd != "vol-primitivies" && cmd != "photon-beams" && cmd != "photon-planes") {
-            std::fprintf(stderr, "%s: --light-streams is not supported (photon-beams, photon-planes, vpl and vol-primitivies only)\n", cmd.c_str()); return 2;
+            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl`, `vol-primitivies`, `photon-beams`, `photon-planes`, `virtual-ray-lights` and `plane-single` subcommands are provided (got %s)\n", a.c_str()); return 2; }
+        } else if (a == "--light-streams" && cmd != "vpl" && cmd != "vol-primitivies" && cmd != "photon-beams" && cmd != "photon-planes" && cmd != "virtual-ray-lights") {
+            std::fprintf(stderr, "%s: --light-streams is not supported (photon-beams, photon-planes, virtual-ray-lights, vpl and vol-primitivies only)\n", cmd.c_str()); return 2;
         } else if (a == "--tree-build" && cmd != "vol-primitivies") {
             std::fprintf(stderr, "%s: --tree-build is not supported (vol-primitivies only)\n", cmd.c_str()); return 2;
         } else if (cmd == "ao") {
@@ -164,7 +167,7 @@ int main(int argc, char** argv) {
             else if (a == "--light-streams") light_streams = val();
             else if (a == "--tree-build") tree_build = val();
             else { std::fprintf(stderr, "unknown vol-primitivies option %s\n", a.c_str()); return 2; }
-        } else if (cmd == "photon-beams" || cmd == "photon-planes") {
+        } else if (cmd == "photon-beams" || cmd == "photon-planes" || cmd == "virtual-ray-lights") {
             if (a == "-m" || a == "--max-depth") max_depth = val();
             else if (a == "-n" || a == "--min-depth") (void)val();          // `_min_depth` (cli.rs:697): never read
             else if (a == "-r" || a == "--rr-depth") rr_depth = val();
@@ -222,9 +225,9 @@ int main(int argc, char** argv) {
         light.device = device;
         light.options = options;
     }
-    // vpl, vol-primitivies, photon-beams, photon-planes: how the light paths draw (the gather stays in reference order either way)
+    // vpl, vol-primitivies, photon-beams, photon-planes, virtual-ray-lights: how the light paths draw (the gather stays in reference order either way)
     LightStreams light_streams_mode = LightStreams::Reference;
-    if (cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams" || cmd == "photon-planes") {
+    if (cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams" || cmd == "photon-planes" || cmd == "virtual-ray-lights") {
         if (light_streams == "per-path") light_streams_mode = LightStreams::PerPath;
         else if (light_streams != "reference") { std::fprintf(stderr, "invalid --light-streams: %s (reference or per-path)\n", light_streams.c_str()); return 2; }
     }
@@ -280,6 +283,21 @@ int main(int argc, char** argv) {
         pbeams.light_streams = light_streams_mode;
         pbeams.device = device;
         pbeams.options = options;
+    }
+    // virtual-ray-lights: photon-beams' limits
+    IntegratorVirtualRayLights vrls;
+    if (cmd == "virtual-ray-lights") {
+        if (refused("virtual-ray-lights", RL_STREAM_REFERENCE_ORDER, true)) return 2;
+        if (!parse_count("--nb-primitive", nb_primitive, &vrls.nb_primitive)) return 2;
+        if (vrls.nb_primitive > (uint32_t)RL_BEAM_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", nb_primitive.c_str(), (int)RL_BEAM_MAX); return 2; }
+        if (!parse_radius(&vrls.radius)) return 2;
+        const Medium m = parse_medium(medium);
+        if (m.sigma_a + m.sigma_s == 0.0f) { std::fprintf(stderr, "virtual-ray-lights: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n"); return 2; }
+        vrls.max_depth = match_infinity(max_depth);
+        vrls.rr_depth = match_infinity(rr_depth);
+        vrls.light_streams = light_streams_mode;
+        vrls.device = device;
+        vrls.options = options;
     }
     // photon-planes: photon-beams' limits, and the depth below which no plane exists
     IntegratorPhotonPlanes pplanes;
@@ -368,7 +386,7 @@ int main(int argc, char** argv) {
         }
         scene->build_emitters(use_ats);      // scene.build_emitters(use_ats) (cli.rs:432)
         IntegratorPathTracing integrator;
-        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams" || cmd == "photon-planes" || cmd == "plane-single") strategy = "all";       // (the path integrator below is not used)
+        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams" || cmd == "photon-planes" || cmd == "virtual-ray-lights" || cmd == "plane-single") strategy = "all";       // (the path integrator below is not used)
         integrator.min_depth = match_infinity(min_depth);
         integrator.max_depth = match_infinity(max_depth);
         integrator.rr_depth = match_infinity(rr_depth);
@@ -403,6 +421,8 @@ int main(int argc, char** argv) {
             img = pbeams.compute(sampler, *scene); elapsed_ms = pbeams.last_stats.render_ms;
         } else if (cmd == "photon-planes") {
             img = pplanes.compute(sampler, *scene); elapsed_ms = pplanes.last_stats.render_ms;
+        } else if (cmd == "virtual-ray-lights") {
+            img = vrls.compute(sampler, *scene); elapsed_ms = vrls.last_stats.render_ms;
         } else if (cmd == "plane-single") {
             if (plane_uncorrelated) { img = uplane.compute(sampler, *scene); elapsed_ms = uplane.last_stats.render_ms; }
             else { img = plane.compute(sampler, *scene); elapsed_ms = plane.last_stats.render_ms; }

@@ -339,7 +339,7 @@ struct IntegratorVPL {
 // struct IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives } (src/integrators/explicit/vol_primitives.rs:12-24) + Integrator::compute
 // for the beam radiance estimate, seed for seed the reference: the photons from the main sampler (rl_vpl_generate with RL_VPL_VOLUME: the records convert_photons
 // stores), the photon tree (rl_photon_map_build), the block seeds from the sampler the generation leaves, the gather on reference-order streams (rl_render_bre).
-// Beams, Planes and VRL are not built.  radius: the reference hard-codes 0.001 (vol_primitives.rs:618).  tree_build: Host = rl_photon_map_build (the records
+// Beams, Planes and VRL are not built here (they are structs of their own, below).  radius: the reference hard-codes 0.001 (vol_primitives.rs:618).  tree_build: Host = rl_photon_map_build (the records
 // go to the host and the tree comes back), Device = rl_photon_map_build_device (the same tree, byte for byte, from device kernels; `--tree-build device`).
 enum class VolPrimitivies { BRE, Beams, Planes, VRL };
 enum class TreeBuild { Host, Device };
@@ -437,6 +437,39 @@ struct IntegratorPhotonPlanes {
         const PPlaneMapHandle map(built);
         const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
         check(rl_render_photon_planes(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "photon-planes");
+        return std::move(ctx.img);
+    }
+};
+
+// IntegratorVolPrimitives with primitives = VRL (vol_primitives.rs:201-253, 608-699, 741-764) as a struct of its own, for the reason IntegratorPhotonBeams is one,
+// + Integrator::compute, seed for seed the reference, with IntegratorPhotonBeams' host sequence: the beams from the main sampler (rl_beam_generate: the VRL arm
+// shoots what the Beams arm shoots), the partition by from_surface with the surface beams' split and tree (rl_vrl_map_build), the block seeds from the sampler
+// the generation leaves, the chain pass and the gather on reference-order streams (rl_render_vrl).  light_streams = PerPath: rl_beam_generate_paths.
+using VrlMapHandle = Handle<rl_vrl_map, rl_vrl_map_destroy>;
+struct IntegratorVirtualRayLights {
+    uint32_t nb_primitive = 128;
+    std::optional<uint32_t> max_depth, rr_depth = 0u;
+    float radius = RL_PHOTON_RADIUS_DEFAULT;
+    LightStreams light_streams{LightStreams::Reference};
+    int device = 0;
+    Options options;
+    rl_render_stats last_stats{}, last_generation_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        RenderContext ctx(scene, device, options);
+        rl_path_params p;
+        rl_path_params_default(&p);
+        p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
+        p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
+        p.stream_mode = RL_STREAM_REFERENCE_ORDER;
+        p.seed_variant = sampler.variant;
+        rl_beam_set* generated = nullptr;
+        check((light_streams == LightStreams::PerPath ? rl_beam_generate_paths : rl_beam_generate)(ctx, &p, nb_primitive, &sampler.rnd, &generated, &last_generation_stats), "virtual-ray-lights");
+        const BeamSetHandle beams(generated);
+        rl_vrl_map* built = nullptr;
+        check(rl_vrl_map_build(ctx, beams.get(), radius, &built), "virtual-ray-lights");
+        const VrlMapHandle map(built);
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        check(rl_render_vrl(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "virtual-ray-lights");
         return std::move(ctx.img);
     }
 };

@@ -1,5 +1,5 @@
 // launch.h — host-side launchers of the kernel families that live in their own translation units (fused_*.hip, fusedq_*.hip, fused_strat_*.hip,
-// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, beamgen_*.hip, beam_*.hip, pplanegen_*.hip, pplane_*.hip, plane_*.hip, uplane_*.hip), so that the families compile in parallel, and
+// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, beamgen_*.hip, beam_*.hip, pplanegen_*.hip, pplane_*.hip, vrl_*.hip, plane_*.hip, uplane_*.hip), so that the families compile in parallel, and
 // the dispatcher every one of them maps its run-time arguments to template arguments with (with_bsdf, with_flag).  Launch errors are picked up by
 // the caller's hipGetLastError().
 #pragma once
@@ -129,6 +129,16 @@ struct PPlaneConst {
     unsigned n_nodes;
 };
 
+// The virtual ray lights (vrl.hip.h): the surface beams' tree with BeamLeaf's constants, the VRLs in storing order, and what the chain pass hands the gather.
+// The gather's statistics rows are the photon planes' eight: STAT_PPLANE_ISECT = VRLs that passed the roulette, STAT_PPLANE_VISIBLE = of those, visible
+struct VrlConst {
+    BeamConst beam;                     // the beam tree over the surface beams' sub-beams; beam.norm_photon serves the VRLs too
+    const float4* vrls;                 // [n_vrl][3]: o, length | d, rr | radiance, 0
+    unsigned n_vrl;
+    unsigned* starts;                   // [owned block][256] the draw of the block's stream at which pixel c = ix * bh + iy starts: k_vrl_chain writes, k_vrl_gather reads
+    unsigned* totals;                   // [owned block] the draws the block takes
+};
+
 // IntegratorSinglePlane (plane.hip.h): the rectangular lights, the generation's constants, and for the gather the plane tree in visiting order with the
 // planes in leaf order (host/planetree.cpp)
 struct PlaneLight { float o[3], u_l, u[3], v_l, v[3], pad0, n[3], pad1, emission[3], pad2; };      // RectangularLightSource, 5 float4
@@ -237,6 +247,10 @@ void launch_pplanegen_stream(int which, int mat, dim3 grid, dim3 block, size_t l
                              const VplConst& vc, const VplPathsConst& pc, const PPlaneGenConst& xc);
 void launch_pplane_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PPlaneConst& pc);
 void launch_pplane_stream(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PPlaneConst& pc);
+// The virtual ray lights (vrl.hip.h): k_vrl_chain, one lane per owned block (rc.n_owned of them), then k_vrl_gather over the owned blocks
+void launch_vrl_chain(hipStream_t st, const RenderConst& rc, const VrlConst& vc);
+void launch_vrl_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VrlConst& vc);
+void launch_vrl_stream(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const VrlConst& vc);
 // IntegratorSinglePlane (plane.hip.h): k_plane_generate on one lane, k_plane_generate_lanes on one lane per iteration (plane_generate.hip); k_plane_gather over the owned blocks, mode = PLANE_MODE_*
 void launch_plane_generate(hipStream_t st, const PlaneGenConst& gc);
 void launch_plane_generate_lanes(hipStream_t st, const PlaneGenConst& gc, unsigned n_gen);      // k_plane_generate_lanes: one lane per iteration, n_gen of them

@@ -1335,6 +1335,7 @@ extern "C" int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_pa
 
 #include "gather_render.hip.h"
 #include "beam_render.hip.h"
+#include "vrl_render.hip.h"
 #include "pplane_render.hip.h"
 
 // ---- batched Acceleration::{trace, visible}
