@@ -74,6 +74,107 @@ def open_floor(w, h, bsdf=None, environment=None, light=True, light_in_view=Fals
     return sd
 
 
+DELTA_SKY = (0.3, 0.4, 0.6)
+MIRROR_TILT = 55.0
+PANE_HALF = 4.0
+MIRROR_CENTRE, MIRROR_HALF = (0.3, 1.3, 0.4), 0.5
+
+
+def flat_quad(name, x0, x1, y, z0, z1, up, bsdf):
+    """A quad in the plane of height y whose mesh normal, in the normals array and by its winding alike, points up or down."""
+    corners = [x0, y, z0, x0, y, z1, x1, y, z1, x1, y, z0]
+    if not up:
+        corners = [x0, y, z0, x1, y, z0, x1, y, z1, x0, y, z1]
+    return scenes._quad_mesh(name, corners, [0, 1 if up else -1, 0], bsdf)
+
+
+def pane(w, h, camera_inside=False, tilt=0.0):
+    """open_floor under a sky with an 8 x 8 pane of glass 2.5 above the floor, between the camera (3 above) and everything else: a single crossing, the one
+    place where the eta^2 of radiance does not cancel.  camera_inside: the pane's normal points down, so that the camera looks out of the denser side.
+    tilt: the camera turned by that many degrees towards +x about its own vertical axis; with camera_inside and 41.6 degrees the frame's 40 degrees
+    straddle the critical angle asin(1 / eta)."""
+    sd = open_floor(w, h, environment=DELTA_SKY)
+    sd.meshes.append(flat_quad("Pane", -PANE_HALF, PANE_HALF, 2.5, -PANE_HALF, PANE_HALF, not camera_inside, scenes.Bsdf(type=scenes.GLASS)))
+    c, s = np.cos(np.radians(tilt)), np.sin(np.radians(tilt))
+    sd.to_world = np.asarray([c, s, 0, 0, 0, 0, -1, 0, s, -c, 0, 0, 0, 3, 0, 1], dtype=np.float32)
+    if tilt:
+        # what the pane reflects past the critical angle ends on a black canopy 0.9 above it, what it reflects short of that angle passes the canopy's edge
+        # into the sky: under a sky alone a ray sent on along the pane instead of back up would find the same radiance
+        sd.meshes.append(flat_quad("Canopy", 1.3, 4, 3.4, -2, 2, False, scenes.matte((0.0, 0.0, 0.0))))
+    return sd
+
+
+def slab(w, h):
+    """open_floor under a sky with a slab of glass between the camera and everything else: two 8 x 8 quads 2.5 and 2.2 above the floor, normals outward."""
+    sd = open_floor(w, h, environment=DELTA_SKY)
+    sd.meshes.append(flat_quad("SlabTop", -PANE_HALF, PANE_HALF, 2.5, -PANE_HALF, PANE_HALF, True, scenes.Bsdf(type=scenes.GLASS)))
+    sd.meshes.append(flat_quad("SlabBottom", -PANE_HALF, PANE_HALF, 2.2, -PANE_HALF, PANE_HALF, False, scenes.Bsdf(type=scenes.GLASS)))
+    return sd
+
+
+def mirror(w, h, shows_light=False):
+    """open_floor (no sky: by way of a mirror a sky lights the floor from a whole hemisphere of images, which no image source sums up) with a smooth-metal
+    quad (the default eta and k: three different Fresnel curves) 1.6 x 1.2, tilted in view about the z axis: it covers the left of the frame and reflects
+    the lit floor.  shows_light: a quad of side 2 MIRROR_HALF about MIRROR_CENTRE instead, turned so that the camera sees the light's centre in its own."""
+    sd = open_floor(w, h)
+    metal = scenes.Bsdf(type=scenes.METAL, distribution=scenes.MF_NONE)
+    if shows_light:
+        # the mirror's plane passes through MIRROR_CENTRE with normal n = unit(d_light - d_camera) for the light's centre (2, 2, 0.5): the camera sees it there
+        centre, to_camera, to_light = np.asarray(MIRROR_CENTRE), np.asarray([0.0, 3.0, 0.0]), np.asarray([2.0, 2.0, 0.5])
+        a, b = to_camera - centre, to_light - centre
+        n = a / np.linalg.norm(a) + b / np.linalg.norm(b)
+        n /= np.linalg.norm(n)
+        s = np.cross([0.0, 0.0, 1.0], n)
+        s /= np.linalg.norm(s)
+        t = np.cross(n, s)
+        corners = [centre + MIRROR_HALF * (i * s + j * t) for i, j in ((-1, -1), (1, -1), (1, 1), (-1, 1))]
+    else:
+        c, s = np.cos(np.radians(MIRROR_TILT)), np.sin(np.radians(MIRROR_TILT))
+        n = np.asarray([s, c, 0.0])
+        corners = [np.asarray([-0.5 + i * 0.8 * c, 0.8 - i * 0.8 * s, 0.6 * j]) for i, j in ((-1, -1), (-1, 1), (1, 1), (1, -1))]
+    sd.meshes.append(scenes._quad_mesh("Mirror", np.concatenate(corners).tolist(), [float(x) for x in n], metal))
+    return sd
+
+
+def coat(w, h):
+    """open_floor under a sky, its floor a smooth substrate: a diffuse term under a mirror coat of Schlick's F."""
+    return open_floor(w, h, environment=DELTA_SKY,
+                      bsdf=scenes.Bsdf(type=scenes.SUBSTRATE, diffuse=scenes.const_color((0.5, 0.3, 0.2)), specular=scenes.const_color((0.05, 0.05, 0.05)),
+                                       distribution=scenes.MF_NONE))
+
+
+def caustic(w, h):
+    """open_floor with an upright smooth-metal quad in the plane x = -1.3, beside the frustum and facing the light: it throws the light's image onto the
+    floor in view, the occluder's shadow included, where nothing else lights the floor."""
+    sd = open_floor(w, h)
+    sd.meshes.append(scenes._quad_mesh("Mirror", [-1.3, 0.02, -1.5, -1.3, 2.5, -1.5, -1.3, 2.5, 2.5, -1.3, 0.02, 2.5], [1, 0, 0],
+                                       scenes.Bsdf(type=scenes.METAL, distribution=scenes.MF_NONE)))
+    return sd
+
+
+def lit_through_a_pane(w, h):
+    """open_floor with a pane of glass 1.5 above the floor under the light, x 0.7 .. 3.3, z -0.8 .. 1.8, normal up, beside the frustum: every segment from the
+    floor in view to the light crosses it, so a light sample finds nothing and the floor is lit through one crossing alone, which `path` and the light
+    tracer can both render."""
+    sd = open_floor(w, h)
+    sd.meshes.append(flat_quad("Pane", 0.7, 3.3, 1.5, -0.8, 1.8, True, scenes.Bsdf(type=scenes.GLASS)))
+    return sd
+
+
+# name: (builder(w, h), the delta tree's max_edges, rays per pixel n of the reference: n x n against 2n x 2n; a mirror's outline in view needs more).  `path` renders exactly the tree's paths at max_depth = max_edges + 1: one more and the first path with
+# two vertices that are no delta vertices comes in (floor -> pane -> sky, floor -> mirror -> floor, a coat's second bounce).
+DELTA_SCENES = {
+    "pane": (lambda w, h: pane(w, h), 3, 2),                                                  # camera -> pane -> floor -> light
+    "pane_inside": (lambda w, h: pane(w, h, camera_inside=True), 3, 2),
+    "pane_critical": (lambda w, h: pane(w, h, camera_inside=True, tilt=41.6), 3, 4),
+    "slab": (lambda w, h: slab(w, h), 4, 2),                                                  # camera -> top -> bottom -> floor -> light
+    "mirror": (lambda w, h: mirror(w, h), 3, 4),                                              # camera -> mirror -> floor -> light
+    "mirror_light": (lambda w, h: mirror(w, h, shows_light=True), 3, 4),
+    "caustic": (lambda w, h: caustic(w, h), 3, 2),                                         # camera -> floor -> mirror -> light: the image source
+    "coat": (lambda w, h: coat(w, h), 2, 2),                                                  # camera -> coat -> light or sky
+}
+
+
 def glass_and_mirror(w, h):
     # several BSDF types in one scene (the run-time switch); glass transmission carries eta^2 into the russian roulette
     sd = scenes.cbox(w, h)

@@ -20,7 +20,10 @@ the viewer) and the normal n, and returns f cos_x:
                             to the complex Fresnel coefficients)
     Ashikhmin-Shirley       28 Rd / (23 pi) (1 - Rs) (1 - (1 - cos_l / 2)^5) (1 - (1 - cos_v / 2)^5) + D F_schlick(v.h) / (4 (v.h) max(cos_l, cos_v))  (2000, eq. 4-5,
                             with the microfacet D in place of their anisotropic lobe, as pbrt's FresnelBlend does)
-Delta BSDFs have no integral to hold and are refused.
+A delta lobe has no integral and bsdf_cos refuses it; what is held of glass, the smooth metal and the smooth substrate is the tree of delta_radiance: a camera
+ray that meets such a surface becomes a few rays of known weight (the dielectric Fresnel term F and Snell's law, F_conductor, Schlick's F; written from the
+published formulas), and where a branch ends on any other surface radiance() does the rest.  image_source adds the caustic of a plane mirror and
+refracted_source the light that reaches a surface through one pane of glass.
 
 Where the reference renderer's text departs from the published model, the departure is a named switch (the `departures` argument; REFERENCE is what the
 renderer computes, PUBLISHED the models as published):
@@ -42,6 +45,29 @@ renderer computes, PUBLISHED the models as published):
     substrate_denominator   "max": 4 (v.h) max(cos_l, cos_v) (src/bsdfs/substrate.rs:186-189).  This is the Ashikhmin-Shirley paper's own denominator, so
                             REFERENCE and PUBLISHED agree on it; "product" is the Cook-Torrance reading 4 cos_l cos_v, kept as a switch so that the
                             difference can be measured.
+    glass_radiance_scale    "none": what crosses a pane is scaled by (1 - F) transmittance alone.  src/bsdfs/glass.rs:99-107 multiplies by (n_i / n_t)^2 under
+                            Transport::Radiance only, and `path` walks camera paths under Transport::Importance (src/integrators/explicit/path.rs).  "eta2" is
+                            the published radiance scaling: 1 / eta^2 entering the denser side, eta^2 leaving it.  Over a slab the two cancel; on a single
+                            crossing `path` reads 2.26 times or 0.44 of the published radiance.  The light tracer walks light paths under Importance too
+                            (light.rs), and for a light path no eta^2 is the published model: its image is the "eta2" one, so the two integrators differ
+                            by eta^2 on a floor lit through one pane (test_both_transports_on_the_single_crossing pins both).
+    emitter_after_delta     False: under strategy = emitter the emission, or the sky, at the end of an edge that no light sample made counts for nothing
+                            (path.rs:60-66), so a light seen in a mirror and the sky in a pane are black; the camera's own edge always counts
+                            (path.rs:152-166).  True: such an edge counts, as it must where no light sample can make it.
+    smooth_substrate_nee    False: no light sample is made at a smooth substrate, because BSDFType::is_smooth (src/bsdfs/mod.rs:157-161) is true of
+                            DELTA | DIFFUSE (src/paths/strategies/emitters.rs:110; src/integrators/direct.rs:76).  Under strategy = emitter its diffuse term
+                            is black, under the others sampled directions alone light it.  `direct` still weights those directions by the power heuristic
+                            against the light samples it skipped (direct.rs:148-169): with nb_light_samples > 0 it loses a third of the diffuse term, which
+                            no switch models; the tests assert the miss.
+    sky_shadow_ray          "antipodal": a light sample of the sky ends its shadow ray where the scene's sphere lies along -d, not along d
+                            (BoundingSphere::intersect, src/structure.rs:899-902, takes `center - o` where the quadratic wants `o - center`).  Seen from
+                            off the sphere's centre that end can lie short of an occluder: from the floor under a pane the sky lights the floor through
+                            the pane's rim.  radiance(sky=...) gathers the sky as the strategy does: "bsdf" by V along the direction, "emitter" by V to that
+                            end, "all" by the two under the balance heuristic of path.rs (Lambert's cos / pi against the light sample's density).  Found
+                            by the pane's first run: its emitter frame read 3 % above its other two.
+
+What `direct` does at a delta hit (src/integrators/direct.rs): it samples one direction there and adds the light or the sky that direction ends on, with weight 1
+for a discrete direction, and nothing beyond.  That is delta_radiance at max_edges = 2 under "all".
 
 The rule.  Each rectangular light carries panels x panels squares of a tensor Gauss-Legendre grid; `res` multiplies the panel count and the nodes per panel
 (L_PANELS, L_NODES at res = 1).  Panels are what a glossy lobe narrower than the light and a shadow edge across it need.  The error estimate is the difference
@@ -62,8 +88,10 @@ CHUNK_POINTS = 1 << 17                        # (ray, light point) pairs evaluat
 WORKERS = 8                                   # threads that share the chunks
 FAR = 1.0e3                                   # where a directional light's shadow ray ends: beyond everything
 
-REFERENCE = {"phong_lobe_cosine": False, "smith_beckmann": "rational", "substrate_denominator": "max", "conductor_fresnel": "cos2"}
-PUBLISHED = {"phong_lobe_cosine": True, "smith_beckmann": "exact", "substrate_denominator": "max", "conductor_fresnel": "exact"}
+REFERENCE = {"phong_lobe_cosine": False, "smith_beckmann": "rational", "substrate_denominator": "max", "conductor_fresnel": "cos2",
+             "glass_radiance_scale": "none", "emitter_after_delta": False, "smooth_substrate_nee": False, "sky_shadow_ray": "antipodal"}
+PUBLISHED = {"phong_lobe_cosine": True, "smith_beckmann": "exact", "substrate_denominator": "max", "conductor_fresnel": "exact",
+             "glass_radiance_scale": "eta2", "emitter_after_delta": True, "smooth_substrate_nee": True, "sky_shadow_ray": "exact"}
 
 _GLOSSY = dict(diffuse=scenes.const_color((0.4, 0.3, 0.2)), specular=scenes.const_color((0.2, 0.3, 0.5)), weight_specular=0.5)
 TEST_BSDFS = {                                # what both test files put on every mesh of the box (Lambert is the box's own three albedos)
@@ -149,6 +177,43 @@ def fresnel_conductor(cos, eta, k, form="exact"):
     return 0.5 * (rs + rp)
 
 
+def coat_diffuse(bsdf, cl, cv):
+    """The diffuse term of Ashikhmin & Shirley (2000, eq. 5), without cos_x: [..., 3]."""
+    rs, rd = _colour(bsdf.specular), _colour(bsdf.diffuse)
+    return rd * (1.0 - rs) * 28.0 / (23.0 * np.pi) * ((1.0 - (1.0 - 0.5 * cl) ** 5) * (1.0 - (1.0 - 0.5 * cv) ** 5))[..., None]
+
+
+class CoatDiffuse:
+    """That diffuse term alone as a BSDF of bsdf_cos: the part of a smooth substrate that is no delta lobe."""
+    type = "coat-diffuse"
+
+    def __init__(self, bsdf):
+        self.diffuse, self.specular = bsdf.diffuse, bsdf.specular
+
+
+def fresnel_dielectric(cos_i, eta):
+    """(F, cos_t): the reflectance of unpolarised light that meets, at cosine cos_i >= 0, the boundary from index n_i to n_t, eta = n_t / n_i, and the cosine
+    of the refracted direction by Snell's law (n_i sin_i = n_t sin_t).  r_s = (cos_i - eta cos_t) / (cos_i + eta cos_t), r_p = (eta cos_i - cos_t) /
+    (eta cos_i + cos_t), F = (r_s^2 + r_p^2) / 2 (Born & Wolf 1.5.2); at and past the critical angle F = 1 and cos_t = 0."""
+    c = np.clip(np.asarray(cos_i, np.float64), 0.0, 1.0)
+    eta = np.asarray(eta, np.float64)
+    sin2_t = (1.0 - c * c) / (eta * eta)
+    total = sin2_t >= 1.0
+    ct = np.sqrt(np.where(total, 0.0, 1.0 - sin2_t))
+    rs = (c - eta * ct) / np.where(total, 1.0, c + eta * ct)
+    rp = (eta * c - ct) / np.where(total, 1.0, eta * c + ct)
+    return np.where(total, 1.0, 0.5 * (rs * rs + rp * rp)), ct
+
+
+def refract(d, n, eta):
+    """The unit direction d, arriving against the unit normal n (d . n < 0), past a boundary of relative index eta = n_t / n_i:
+    d / eta + (cos_i / eta - cos_t) n, cos_t from fresnel_dielectric; meaningless past the critical angle (cos_t = 0 there)."""
+    ci = -_dot(d, n)
+    _, ct = fresnel_dielectric(ci, eta)
+    eta = np.asarray(eta, np.float64)
+    return d / eta[..., None] + ((ci / eta - ct)[..., None]) * n
+
+
 def bsdf_cos(bsdf, n, l, v, departures=REFERENCE):
     """f(l, v) cos_x [..., 3] for unit vectors n, l, v that broadcast against each other; 0 unless l and v are both on n's side."""
     cl, cv = _dot(n, l), _dot(n, v)
@@ -156,6 +221,8 @@ def bsdf_cos(bsdf, n, l, v, departures=REFERENCE):
     cl, cv = np.where(ok, cl, 1.0), np.where(ok, cv, 1.0)
     if bsdf.type == scenes.DIFFUSE:
         out = _colour(bsdf.diffuse) / np.pi * cl[..., None]
+    elif bsdf.type == CoatDiffuse.type:
+        out = coat_diffuse(bsdf, cl, cv) * cl[..., None]
     elif bsdf.type == scenes.PHONG:
         mirror = 2.0 * cv[..., None] * n - v
         lobe = (bsdf.exponent + 2.0) / (2.0 * np.pi) * np.maximum(_dot(mirror, l), 0.0) ** bsdf.exponent
@@ -176,8 +243,7 @@ def bsdf_cos(bsdf, n, l, v, departures=REFERENCE):
                                                                                                         departures["smith_beckmann"])
             out = _colour(bsdf.specular) * fresnel_conductor(vh, _colour(bsdf.eta), _colour(bsdf.k), departures["conductor_fresnel"]) * (d * g / (4.0 * cv))[..., None]
         else:
-            rs, rd = _colour(bsdf.specular), _colour(bsdf.diffuse)
-            diffuse = rd * (1.0 - rs) * 28.0 / (23.0 * np.pi) * ((1.0 - (1.0 - 0.5 * cl) ** 5) * (1.0 - (1.0 - 0.5 * cv) ** 5))[..., None]
+            rs, diffuse = _colour(bsdf.specular), coat_diffuse(bsdf, cl, cv)
             schlick = rs + (1.0 - rs) * ((1.0 - vh) ** 5)[..., None]
             assert departures["substrate_denominator"] in ("max", "product")
             below = 4.0 * vh * np.maximum(cl, cv) if departures["substrate_denominator"] == "max" else 4.0 * cl * cv
@@ -190,7 +256,8 @@ def bsdf_cos(bsdf, n, l, v, departures=REFERENCE):
 # ---- the first hit
 class Hits:
     """The first hits of rays (o, d): hit [n] bool, mesh [n], p [n, 3] float64, n [n, 3] the shading normal as the viewer sees it, v [n, 3] = -d,
-    front [n] (v on n's side: always for a mesh that emits nothing, the emitting side alone for a light), p32 [n, 3] the float32 point V is asked about."""
+    front [n] (v on n's side: always for a mesh that emits nothing, the emitting side alone for a light), p32 [n, 3] the float32 point V is asked about,
+    n_mesh [n, 3] the same normal as the mesh arrays give it, not turned: the side of a pane of glass that is outside."""
 
     def __init__(self, sc, sd, o, d):
         o32, d32 = np.ascontiguousarray(o, np.float32).reshape(-1, 3), np.ascontiguousarray(d, np.float32).reshape(-1, 3)
@@ -200,7 +267,7 @@ class Hits:
         self.hit, self.mesh, self.v = mesh >= 0, mesh, -dn
         self.p = o64 + np.where(self.hit, t.astype(np.float64), 0.0)[:, None] * d64
         self.p32 = (o32 + np.where(self.hit, t, np.float32(0.0))[:, None] * d32).astype(np.float32)
-        self.n = np.zeros_like(self.p)
+        self.n, self.n_mesh = np.zeros_like(self.p), np.zeros_like(self.p)
         for m, md in enumerate(sd.meshes):
             at = np.nonzero(mesh == m)[0]
             if at.size == 0:
@@ -216,6 +283,7 @@ class Hits:
                 ns = _unit(np.sum(w[:, :, None] * np.stack([nv[idx[:, 0]], nv[idx[:, 1]], nv[idx[:, 2]]], axis=1), axis=1))
             else:
                 ns = _unit(np.cross(b - a, c - a))
+            self.n_mesh[at] = ns
             if md.emission is None:
                 ns = np.where((_dot(dn[at], ns) > 0.0)[:, None], -ns, ns)
             self.n[at] = ns
@@ -269,11 +337,34 @@ def _hemisphere(sc, hits, at, res):
     return world, w, np.where(mesh >= 0, dist.astype(np.float64), np.inf).reshape(world.shape[:2])
 
 
-def radiance(sc, sd, o, d, res=1, bsdfs=None, departures=REFERENCE, rule=None, emission=True):
+def sky_sphere(sd):
+    """(centre [3], radius, p): the sphere the renderer hangs its environment on, 1.1 times the sphere about the box of every vertex and the camera
+    (src/scene.rs:53-123 with Emitter::preprocess), and the density per solid angle with which a light sample picks a direction of the sky: 1 / (4 pi) times
+    the sky's share of the power, pi radius^2 max(c) beside every light's pi area max(Le) (src/emitter.rs:519-531, 591-599)."""
+    points = np.concatenate([np.asarray(m.vertices, np.float64).reshape(-1, 3) for m in sd.meshes] + [np.asarray(sd.to_world, np.float64)[None, 12:15]])
+    low, high = points.min(axis=0), points.max(axis=0)
+    radius = 1.1 * np.linalg.norm(0.5 * (high - low))
+    power = np.pi * radius ** 2 * max(sd.environment)
+    others = sum(np.pi * light.area * light.emission.max() for light in lights_of(sd))
+    assert not sd.lights, "area lights and a sky only"
+    return 0.5 * (low + high), radius, power / (power + others) / (4.0 * np.pi)
+
+
+def sky_shadow_end(p, d, centre, radius):
+    """Where a light sample of the sky along the unit vector d ends its shadow ray from p (inside the sphere) under sky_shadow_ray = "antipodal": p + d t, t the
+    distance from p to the sphere along -d, (p - c) . d + sqrt(((p - c) . d)^2 - |p - c|^2 + radius^2)."""
+    oc = p - centre
+    along = _dot(oc, d)
+    return p + (along + np.sqrt(along * along - _dot(oc, oc) + radius * radius))[..., None] * d
+
+
+def radiance(sc, sd, o, d, res=1, bsdfs=None, departures=REFERENCE, rule=None, emission=True, direct=True, sky="bsdf"):
     """L [n_rays, 3] float64 at resolution `res` with every mesh's own BSDF, or, with `bsdfs` (a list of scenes.Bsdf), L [n_bsdfs, n_rays, 3] with each of them
     in turn on every mesh (tests.scene_helpers.single_bsdf); the geometry and V are worked out once for all of them.  rule: (panels, nodes per panel) on a
     light's side at res = 1 instead of (L_PANELS, L_NODES).  sc: the orc.Scene of sd.  Chunks of rays are worked on by WORKERS threads (numpy and the
-    oracle's V and trace release the interpreter); a chunk adds to its own rays' rows alone."""
+    oracle's V and trace release the interpreter); a chunk adds to its own rays' rows alone.
+    emission: what the first hit emits itself, and the sky behind a ray that hits nothing; direct: the lighting integrals; sky: the strategy that gathers
+    the sky ("bsdf", "emitter", "all"), which matters under sky_shadow_ray = "antipodal" alone."""
     hits = Hits(sc, sd, o, d)
     variants = [None] if bsdfs is None else list(bsdfs)
     out = np.zeros((len(variants), hits.hit.shape[0], 3))
@@ -308,7 +399,7 @@ def radiance(sc, sd, o, d, res=1, bsdfs=None, departures=REFERENCE, rule=None, e
                 assert md.emission_kind is None
                 out[:, lit[hits.mesh[lit] == m]] += np.asarray(md.emission, np.float64)
     panels, nodes = (L_PANELS, L_NODES) if rule is None else rule
-    for light in lights_of(sd):
+    for light in lights_of(sd) if direct else ():
         y, wy = _panel_grid(light, panels * res, nodes * res)
 
         def of_light(at):
@@ -325,7 +416,7 @@ def radiance(sc, sd, o, d, res=1, bsdfs=None, departures=REFERENCE, rule=None, e
             shade(at, rows, r[rows, cols] / dist[:, None], (cos_l[rows, cols] / dist ** 3 * wy[cols])[:, None] * light.emission)
 
         in_parallel(of_light, chunks(y.shape[0]))
-    for lt in sd.lights:
+    for lt in sd.lights if direct else ():
         a, intensity = np.asarray(lt["a"], np.float64), np.asarray(lt["intensity"], np.float64)
         if lt["type"] == "point":
             r = a[None, :] - hits.p[lit]
@@ -336,16 +427,317 @@ def radiance(sc, sd, o, d, res=1, bsdfs=None, departures=REFERENCE, rule=None, e
             end, scale = (hits.p[lit] + FAR * l).astype(np.float32), np.ones(lit.size)
         vis = sc.visible(hits.p32[lit], end).astype(np.float64) if lit.size else np.zeros(0)
         shade(lit, np.arange(lit.size), l, (scale * vis)[:, None] * intensity)
-    if sd.environment is not None:
+    if sd.environment is not None and direct:
+        assert sky in ("bsdf", "emitter", "all") and departures["sky_shadow_ray"] in ("exact", "antipodal")
+        centre, radius, p_light = sky_sphere(sd)
+        cos_local = hemisphere_rule(res)[0][:, 2]
+
         def of_sky(at):
             world, w, dist = _hemisphere(sc, hits, at, res)
-            rows, cols = np.nonzero(np.isinf(dist))
-            shade(at, rows, world[rows, cols], w[cols][:, None] * np.asarray(sd.environment, np.float64))
+            share = np.isinf(dist).astype(np.float64)                                                # V as a sampled direction finds it
+            if sky != "bsdf" and departures["sky_shadow_ray"] == "antipodal":
+                end = sky_shadow_end(hits.p[at][:, None, :], world, centre, radius)
+                start = np.broadcast_to(hits.p32[at][:, None, :], world.shape).reshape(-1, 3)
+                sampled = (sc.visible(start, end.reshape(-1, 3).astype(np.float32)) != 0).reshape(share.shape).astype(np.float64)
+                if sky == "all" and np.any(sampled != share):
+                    assert bsdfs is None and all(sd.meshes[m].bsdf.type == scenes.DIFFUSE for m in np.unique(hits.mesh[at])), "the MIS of Lambert alone"
+                    p_bsdf = cos_local[None, :] / np.pi
+                    sampled = (p_bsdf * share + p_light * sampled) / (p_bsdf + p_light)
+                share = sampled
+            rows, cols = np.nonzero(share)
+            shade(at, rows, world[rows, cols], (w[cols] * share[rows, cols])[:, None] * np.asarray(sd.environment, np.float64))
 
         in_parallel(of_sky, chunks(hemisphere_rule(res)[0].shape[0]))
+    if sd.environment is not None and emission:
         out[:, ~hits.hit] += np.asarray(sd.environment, np.float64)                                  # a ray that leaves the scene sees the sky
     assert sd.environment_map is None, "constant environments only"
     return out[0] if bsdfs is None else out
+
+
+# ---- the delta tree
+def is_delta(bsdf):
+    """Glass, and a metal or a substrate without a microfacet distribution: a surface that scatters into single directions."""
+    return bsdf.type == scenes.GLASS or (bsdf.type in (scenes.METAL, scenes.SUBSTRATE) and bsdf.distribution == scenes.MF_NONE)
+
+
+def delta_tree(sc, sd, o, d, max_edges, departures=REFERENCE):
+    """The deterministic tree a camera ray becomes at delta surfaces.  Yields, for edge = 1 .. max_edges, (edge, ray [m], o [m, 3], d [m, 3], weight [m, 3],
+    hits): every branch whose edge-th edge starts at o along d, the camera ray `ray` it descends from, the product of the branch weights so far, and the
+    Hits at the edge's end.  A branch ends where it hits no delta surface; a hit on one spawns, from the float32 hit point,
+        smooth metal       the mirror direction, weight specular F_conductor(cos) (conductor_fresnel)
+        smooth substrate   the mirror direction, weight Schlick's F(cos) = Rs + (1 - Rs) (1 - cos)^5
+        glass              the mirror direction, weight F specular_reflectance, and, short of the critical angle, Snell's direction, weight
+                           (1 - F) specular_transmittance scale; scale is 1 (glass_radiance_scale = "none") or (n_i / n_t)^2 ("eta2": radiance over n^2 is
+                           what a boundary conserves, Veach 1997 ch. 5.2), n_i on the side the camera ray arrives from.  The outside of the pane is where
+                           the mesh arrays' normal points."""
+    assert departures["glass_radiance_scale"] in ("none", "eta2")
+    o, d = np.asarray(o, np.float64).reshape(-1, 3), _unit(np.asarray(d, np.float64).reshape(-1, 3))
+    ray, weight = np.arange(o.shape[0]), np.ones((o.shape[0], 3))
+    for edge in range(1, max_edges + 1):
+        if ray.size == 0:
+            return
+        hits = Hits(sc, sd, o, d)
+        yield edge, ray, o, d, weight, hits
+        spawned = []
+        for m, md in enumerate(sd.meshes):
+            at = np.nonzero(hits.mesh == m)[0]
+            if at.size == 0 or not is_delta(md.bsdf):
+                continue
+            b, v, start = md.bsdf, hits.v[at], hits.p32[at].astype(np.float64)
+            if b.type == scenes.GLASS:
+                cos = _dot(v, hits.n_mesh[at])
+                outside = cos > 0.0
+                n = np.where(outside[:, None], hits.n_mesh[at], -hits.n_mesh[at])
+                eta = np.where(outside, b.glass_eta, 1.0 / b.glass_eta)
+                f, _ = fresnel_dielectric(np.abs(cos), eta)
+                spawned.append((ray[at], start, 2.0 * np.abs(cos)[:, None] * n - v, weight[at] * f[:, None] * _colour(b.specular)))
+                through = np.nonzero(f < 1.0)[0]
+                scale = 1.0 / eta[through] ** 2 if departures["glass_radiance_scale"] == "eta2" else np.ones(through.size)
+                spawned.append((ray[at][through], start[through], refract(-v[through], n[through], eta[through]),
+                                weight[at][through] * ((1.0 - f[through]) * scale)[:, None] * _colour(b.transmittance)))
+            else:
+                n = hits.n[at]
+                cos = _dot(v, n)
+                if b.type == scenes.METAL:
+                    f = _colour(b.specular) * fresnel_conductor(cos, _colour(b.eta), _colour(b.k), departures["conductor_fresnel"])
+                else:
+                    f = _colour(b.specular) + (1.0 - _colour(b.specular)) * ((1.0 - cos) ** 5)[:, None]
+                spawned.append((ray[at], start, 2.0 * cos[:, None] * n - v, weight[at] * f))
+        if not spawned:
+            return
+        ray, o, d, weight = (np.concatenate(part) for part in zip(*spawned))
+        d = _unit(d)
+
+
+MIRROR_LIFT = 1.0e-4                          # the shadow ray from a mirror point to the light starts this far off the mirror's plane, on the side it left from
+
+
+def image_source(sc, sd, o, d, res=1, departures=REFERENCE, rule=None):
+    """L [n_rays, 3]: what the first hit x of (o, d) sends back of the light that reaches it by one reflection in a planar smooth-metal quad (a parallelogram of
+    four vertices), the caustic of a plane mirror.  It is the direct lighting from the light's mirror image y' = y - 2 ((y - q) . n) n: the same panelled grid
+    on the mirrored quad with the area form f(l, v) cos_x Le cos_l / |x - y'|^2, times specular F_conductor at the angle of incidence on the mirror, times V:
+    the segment x -> y' crosses the mirror's plane inside the quad at m, and x -> m and m -> y are both visible.  One reflection, one mirror at a time."""
+    hits = Hits(sc, sd, o, d)
+    out = np.zeros((hits.hit.shape[0], 3))
+    panels, nodes = (L_PANELS, L_NODES) if rule is None else rule
+    lit = np.nonzero(hits.front & ~np.asarray([is_delta(m.bsdf) for m in sd.meshes] + [False])[hits.mesh])[0]
+    for md in sd.meshes:
+        if not (md.bsdf.type == scenes.METAL and is_delta(md.bsdf)):
+            continue
+        quad = np.asarray(md.vertices, np.float64).reshape(-1, 3)
+        assert quad.shape[0] == 4 and np.allclose(quad[2], quad[1] + quad[3] - quad[0], atol=1e-6), "planar mirrors of four vertices only"
+        q0, e0, e1 = quad[0], quad[1] - quad[0], quad[3] - quad[0]
+        nm = _unit(np.cross(e0, e1))
+        metric = np.linalg.inv(np.asarray([[e0 @ e0, e0 @ e1], [e0 @ e1, e1 @ e1]]))
+        for light in lights_of(sd):
+            y, wy = _panel_grid(light, panels * res, nodes * res)
+            yi = y - 2.0 * ((y - q0) @ nm)[:, None] * nm[None, :]
+            ni = light.n - 2.0 * (light.n @ nm) * nm
+            side_y = (yi - q0) @ nm
+            for first in range(0, lit.size, 2048):
+                at = lit[first:first + 2048]
+                p = hits.p[at]
+                r = yi[None, :, :] - p[:, None, :]
+                side_x = (p - q0) @ nm
+                s = side_x[:, None] / np.where(side_x[:, None] == side_y[None, :], 1.0, side_x[:, None] - side_y[None, :])
+                m = p[:, None, :] + s[..., None] * r
+                ab = np.stack([_dot(m - q0, e0), _dot(m - q0, e1)], axis=-1) @ metric
+                ok = (side_x[:, None] * side_y[None, :] < 0.0) & np.all((ab >= 0.0) & (ab <= 1.0), axis=-1)
+                cos_l, cos_x = -_dot(r, ni), _dot(r, hits.n[at][:, None, :])
+                rows, cols = np.nonzero(ok & (cos_l > 0.0) & (cos_x > 0.0))
+                if rows.size == 0:
+                    continue
+                on = m[rows, cols]
+                lifted = (on + MIRROR_LIFT * np.sign(side_x[rows])[:, None] * nm[None, :]).astype(np.float32)
+                vis = (sc.visible(hits.p32[at][rows], on.astype(np.float32)) != 0) & (sc.visible(lifted, y[cols].astype(np.float32)) != 0)
+                rows, cols = rows[vis], cols[vis]
+                dist = np.linalg.norm(r[rows, cols], axis=-1)
+                l = r[rows, cols] / dist[:, None]
+                f = _colour(md.bsdf.specular) * fresnel_conductor(np.abs(l @ nm), _colour(md.bsdf.eta), _colour(md.bsdf.k), departures["conductor_fresnel"])
+                value = f * (cos_l[rows, cols] / dist ** 3 * wy[cols])[:, None] * light.emission
+                ray = at[rows]
+                for mesh in np.unique(hits.mesh[ray]):
+                    g = hits.mesh[ray] == mesh
+                    contrib = bsdf_cos(sd.meshes[mesh].bsdf, hits.n[ray[g]], l[g], hits.v[ray[g]], departures) * value[g]
+                    for c in range(3):
+                        out[:, c] += np.bincount(ray[g], weights=contrib[:, c], minlength=out.shape[0])
+    return out
+
+
+def refracted_source(sc, sd, o, d, res=1, departures=REFERENCE, rule=None):
+    """L [n_rays, 3]: what the first hit x of (o, d) sends back of a horizontal light that reaches it through one horizontal rectangle of glass between them.
+    Per light point y the ray x -> c -> y that obeys Snell's law at the pane's plane is found by bisection: with a, b the heights of x and y off the plane,
+    D their horizontal distance and s that of c from x, n_i s / sqrt(s^2 + a^2) = n_t (D - s) / sqrt((D - s)^2 + b^2).  About the vertical through x the
+    light's plane has the area element D dD dphi and the directions at x the solid angle sin(theta_1) dtheta_1 dphi, with D = a tan(theta_1) +
+    b tan(theta_2), so d(omega) / dA = sin(theta_1) / (D dD / dtheta_1), dD / dtheta_1 = a / cos^2(theta_1) + b / cos^2(theta_2) n_i cos(theta_1) /
+    (n_t cos(theta_2)); for n_i = n_t that is cos_l / r^2.  The term is f(l, v) cos_x (1 - F) transmittance scale Le d(omega) / dA V: c lies in the
+    rectangle, and x -> c and c -> y are both visible; scale as in delta_tree, n_i on x's side."""
+    hits = Hits(sc, sd, o, d)
+    out = np.zeros((hits.hit.shape[0], 3))
+    panels, nodes = (L_PANELS, L_NODES) if rule is None else rule
+    lit = np.nonzero(hits.front & ~np.asarray([is_delta(m.bsdf) for m in sd.meshes] + [False])[hits.mesh])[0]
+    up = np.asarray([0.0, 1.0, 0.0])
+    for md in sd.meshes:
+        if md.bsdf.type != scenes.GLASS:
+            continue
+        quad = np.asarray(md.vertices, np.float64).reshape(-1, 3)
+        normal = np.asarray(md.normals, np.float64).reshape(-1, 3)[0]
+        if quad.shape[0] != 4 or np.ptp(quad[:, 1]) > 0.0 or abs(normal[1]) != 1.0:
+            continue                                                                                 # horizontal rectangles only
+        h, low, high = quad[0, 1], quad.min(axis=0), quad.max(axis=0)
+        for light in lights_of(sd):
+            if abs(light.n[1]) != 1.0 or (h - light.v0[1]) * light.n[1] <= 0.0:
+                continue                                                                             # a horizontal light that faces the pane
+            y, wy = _panel_grid(light, panels * res, nodes * res)
+            at = lit[(hits.p[lit, 1] - h) * (light.v0[1] - h) < 0.0]
+            if at.size == 0:
+                continue
+            p = hits.p[at]
+            side = np.sign(h - p[:, 1])                                                              # +1: x below the pane
+            n_i = np.where(side * normal[1] > 0.0, md.bsdf.glass_eta, 1.0)[:, None]                  # x on the side the normal points away from: inside
+            n_t = np.where(side * normal[1] > 0.0, 1.0, md.bsdf.glass_eta)[:, None]
+            a, b = np.abs(h - p[:, 1])[:, None], abs(light.v0[1] - h)
+            flat = y[None, :, :] - p[:, None, :]
+            flat[..., 1] = 0.0
+            dist = np.linalg.norm(flat, axis=-1)
+            along = flat / np.maximum(dist, 1e-30)[..., None]
+            s_low, s_high = np.zeros_like(dist), dist.copy()
+            for _ in range(60):
+                s = 0.5 * (s_low + s_high)
+                over = n_i * s / np.sqrt(s * s + a * a) > n_t * (dist - s) / np.sqrt((dist - s) ** 2 + b * b)
+                s_low, s_high = np.where(over, s_low, s), np.where(over, s, s_high)
+            s = 0.5 * (s_low + s_high)
+            sin1, cos1 = s / np.sqrt(s * s + a * a), a / np.sqrt(s * s + a * a)
+            cos2 = b / np.sqrt((dist - s) ** 2 + b * b)
+            spread = a / cos1 ** 2 + b / cos2 ** 2 * n_i * cos1 / (n_t * cos2)
+            density = np.where(dist > 1e-6, sin1 / (np.maximum(dist, 1e-6) * spread), 1.0 / (a + b * n_i / n_t) ** 2)
+            f, _ = fresnel_dielectric(cos1, n_t / n_i)
+            scale = (n_i / n_t) ** 2 if departures["glass_radiance_scale"] == "eta2" else 1.0
+            cross = p[:, None, :] + s[..., None] * along + (side[:, None] * a)[..., None] * up
+            l = sin1[..., None] * along + (side[:, None] * cos1)[..., None] * up
+            inside = np.all((cross[..., [0, 2]] >= low[[0, 2]]) & (cross[..., [0, 2]] <= high[[0, 2]]), axis=-1)
+            rows, cols = np.nonzero(inside & (_dot(l, hits.n[at][:, None, :]) > 0.0))
+            if rows.size == 0:
+                continue
+            on = cross[rows, cols]
+            lifted = (on + MIRROR_LIFT * side[rows][:, None] * up).astype(np.float32)
+            vis = (sc.visible(hits.p32[at][rows], on.astype(np.float32)) != 0) & (sc.visible(lifted, y[cols].astype(np.float32)) != 0)
+            rows, cols = rows[vis], cols[vis]
+            value = ((1.0 - f) * scale * density)[rows, cols][:, None] * wy[cols][:, None] * _colour(md.bsdf.transmittance) * light.emission
+            ray = at[rows]
+            for mesh in np.unique(hits.mesh[ray]):
+                g = hits.mesh[ray] == mesh
+                contrib = bsdf_cos(sd.meshes[mesh].bsdf, hits.n[ray[g]], l[rows, cols][g], hits.v[ray[g]], departures) * value[g]
+                for c in range(3):
+                    out[:, c] += np.bincount(ray[g], weights=contrib[:, c], minlength=out.shape[0])
+    return out
+
+
+def delta_radiance(sc, sd, o, d, max_edges, res=1, departures=REFERENCE, strategy="all", rule=None):
+    """L [n_rays, 3] float64 (or [n_strategies, n_rays, 3] for a tuple of strategies, from one tree): the sum over all light paths of at most max_edges
+    edges, the camera's edge counted, whose only scattering vertex that is no delta vertex is the last one before the light.  For `path` that is
+    max_depth = max_edges + 1.  Along delta_tree's branches:
+        where a branch ends on a surface that is no delta surface, radiance(): what it emits, and, while edge + 1 <= max_edges, its direct lighting;
+        where it leaves the scene, the sky;
+        at a smooth substrate, while edge + 1 <= max_edges, the direct lighting of its diffuse term (coat_diffuse), beside the mirror branch;
+        where a branch ends as in the first line, while edge + 2 <= max_edges, image_source() and refracted_source(): the light by way of a plane mirror
+        and through a pane of glass.  A light sample cannot make those paths, so "emitter" never has them.
+    strategy is the path integrator's: "all" and "bsdf" take everything; under "emitter"
+        emitter_after_delta = False    what a branch finds at its end (emission, the sky) counts on the camera's own edge alone (src/integrators/explicit/
+                                       path.rs:60-66 drops the contribution of an edge that no light sample made; :152-166 takes the camera's edge always)
+        smooth_substrate_nee = False   a smooth substrate's diffuse term is black: BSDFType::is_smooth (src/bsdfs/mod.rs:157-161) is true of
+                                       DELTA | DIFFUSE, and no light sample is made at such a vertex (src/paths/strategies/emitters.rs:110)
+    `direct` (src/integrators/direct.rs) is this tree at max_edges = 2 under "all": it samples one direction at the first hit and looks for a light or the sky
+    at its end, nothing further (direct.rs:76 skips the light samples at a smooth vertex as emitters.rs:110 does).
+    Truncated: whatever needs more than max_edges edges, so of a slab's series of internal reflections the terms beyond the budget; and every path with a
+    second vertex that is no delta vertex.  First hits and V are the oracle's.  bsdf_cos is never asked about a delta lobe."""
+    strategies = (strategy,) if isinstance(strategy, str) else tuple(strategy)
+    assert all(s in ("all", "bsdf", "emitter") for s in strategies)
+    n_rays = np.asarray(o).reshape(-1, 3).shape[0]
+    parts = {name: np.zeros((n_rays, 3)) for name in ("first", "found", "image", "coat") + tuple("direct:" + s for s in strategies)}
+    delta_mesh = np.asarray([is_delta(m.bsdf) for m in sd.meshes] + [False])
+
+    def add(name, ray, value):
+        for c in range(3):
+            parts[name][:, c] += np.bincount(ray, weights=value[:, c], minlength=n_rays)
+
+    for edge, ray, eo, ed, weight, hits in delta_tree(sc, sd, o, d, max_edges, departures):
+        leaf = ~delta_mesh[hits.mesh]
+        common = dict(res=res, departures=departures, rule=rule)
+        if leaf.any():
+            add("first" if edge == 1 else "found", ray[leaf], weight[leaf] * radiance(sc, sd, eo[leaf], ed[leaf], emission=True, direct=False, **common))
+            if edge + 1 <= max_edges:
+                lit = None
+                for s in strategies:
+                    if lit is None or sd.environment is not None:                                    # without a sky every strategy gathers the same
+                        lit = weight[leaf] * radiance(sc, sd, eo[leaf], ed[leaf], emission=False, direct=True, sky=s, **common)
+                    add("direct:" + s, ray[leaf], lit)
+            if edge + 2 <= max_edges:
+                add("image", ray[leaf], weight[leaf] * image_source(sc, sd, eo[leaf], ed[leaf], **common))
+                add("image", ray[leaf], weight[leaf] * refracted_source(sc, sd, eo[leaf], ed[leaf], **common))
+        for m, md in enumerate(sd.meshes):
+            at = np.nonzero(hits.mesh == m)[0]
+            if at.size and md.bsdf.type == scenes.SUBSTRATE and is_delta(md.bsdf) and edge + 1 <= max_edges:
+                add("coat", ray[at], weight[at] * radiance(sc, sd, eo[at], ed[at], bsdfs=[CoatDiffuse(md.bsdf)], emission=False, direct=True, **common)[0])
+    out = []
+    for s in strategies:
+        total = parts["first"] + parts["direct:" + s]
+        if s != "emitter" or departures["emitter_after_delta"]:
+            total = total + parts["found"]
+        if s != "emitter":
+            total = total + parts["image"]
+        if s != "emitter" or departures["smooth_substrate_nee"]:
+            total = total + parts["coat"]
+        out.append(total)
+    return out[0] if isinstance(strategy, str) else np.stack(out)
+
+
+DELTA_RAYS = 2                                # rays per pixel of a delta scene's Footprint: 2 x 2 against 4 x 4 where nothing in view has an outline
+
+
+def delta_reference(sc, sd, max_edges, strategies=("all", "emitter"), departures=REFERENCE, n=DELTA_RAYS):
+    """(Footprint, names): delta_radiance at max_edges over every pixel's footprint, one variant per strategy, named by it."""
+    fn = lambda o, d, res: delta_radiance(sc, sd, o, d, max_edges, res, departures, tuple(strategies), rule=FOOTPRINT_RULE)
+    return Footprint(sc, sd, n, fn), list(strategies)
+
+
+LIGHT_CAUSTIC_SPP = 256                       # light-tracing on the caustic: SE(r) 0.8 %, so that 4 SE + the quadrature's 2.5 % stay below the caustic's 9 %
+CROSSING_SPP = 512                            # `path` on lit_through_a_pane: sampled directions alone find the light, SE(r) 3 %
+DELTA_SPP = 64                                # samples per pixel of `path` on the delta scenes, both test files: the oracle's SE(r) is 0.1 .. 1.2 % there
+
+
+def mirror_pixel_bound(value, spread, spp):
+    """How far a pixel of light_in_a_mirror may lie from `value` when each of its spp samples is specular F Le in float32: 1.5 spread + (spp + 32) 2^-24 value.
+    Every sample lies between the smallest and the largest specular F Le over the pixel, and so does their mean; the 4 x 4 rays stand at the centres of
+    their cells and span 3 / 4 of the pixel each way, and F is monotone and close to linear over one pixel, so the whole pixel spans 4 / 3 of `spread`: 1.5 to
+    be safe, on either side of a value that lies inside.  A float32 sum of spp equal terms and its division are off by at most spp 2^-24 of the sum, and the
+    term itself, the real form of F in some thirty float32 operations without cancellation (the denominators are sums; the numerators lose less than a
+    bit at these angles), by at most 32 2^-24."""
+    return 1.5 * spread + (spp + 32) * 2.0 ** -24 * value
+
+
+def light_in_a_mirror(sc, sd, n=DELTA_RAYS, departures=REFERENCE):
+    """(inside [H, W] bool, value [H, W, 3], spread [H, W, 3]): the pixels every footprint ray of which (n x n and 2n x 2n) ends, by way of one smooth metal, on
+    the front of a light; over each such pixel the mean of specular F_conductor Le on the 2n x 2n rays, and the largest less the smallest of them."""
+    inside = np.ones((sd.height, sd.width), bool)
+    for rays in (n, 2 * n):
+        px, py, w, o, d, _ = pixel_rays(sc, sd, rays)
+        ends = np.zeros(o.shape[0], bool)
+        seen = np.zeros((o.shape[0], 3))
+        for edge, ray, _, _, weight, hits in delta_tree(sc, sd, o, d, 2, departures):
+            if edge == 1:                                                                            # here ray is 0 .. n - 1 in order
+                by_metal = np.asarray([m.bsdf.type == scenes.METAL and is_delta(m.bsdf) for m in sd.meshes] + [False])[hits.mesh]
+            else:
+                on = hits.front & np.asarray([m.emission is not None for m in sd.meshes] + [False])[hits.mesh] & by_metal[ray]
+                ends[ray[on]] = True
+                emitted = np.asarray([m.emission if m.emission is not None else (0.0, 0.0, 0.0) for m in sd.meshes] + [(0.0, 0.0, 0.0)])[hits.mesh]
+                seen[ray] = weight * emitted
+        np.logical_and.at(inside, (py, px), ends)
+    value, low, high = np.zeros((sd.height, sd.width, 3)), np.full((sd.height, sd.width, 3), np.inf), np.zeros((sd.height, sd.width, 3))
+    np.add.at(value, (py, px), seen * w[:, None])
+    np.minimum.at(low, (py, px), seen)
+    np.maximum.at(high, (py, px), seen)
+    return inside, value, np.where(inside[..., None], high - low, 0.0)
 
 
 def ambient_occlusion(sc, sd, o, d, res=1, max_distance=1.0, normal_correction=False):

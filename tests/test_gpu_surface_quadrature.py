@@ -23,15 +23,23 @@ without its cosine, Beckmann's rational G1, the conductor Fresnel term with 2 a 
 metal the MIS weights of direct do not sum to one (BSDFMetal::sample reports the microfacet normal's density, pdf the outgoing direction's): the pure
 strategies are asserted to hold and the combinations to miss, as the CPU run shows.
 
+Delta BSDFs (glass, the smooth metal, the smooth substrate) are held through surface_quadrature.delta_radiance, the deterministic tree a camera ray becomes
+at delta vertices, on tests.scene_helpers.DELTA_SCENES (a pane of glass from either side and across the critical angle, a slab, two mirrors, the caustic of a third, a coated floor;
+all on open_floor's layout).  Gates: path max_depth = max_edges + 1 renders exactly the tree's paths (one below is darker or black, asserted; one more and
+the first path with two vertices that are no delta vertices comes in).  What the reference does there and the published models do not is again a switch of
+the quadrature: no eta^2 on what crosses glass, the `emitter` strategy dropping whatever a delta edge finds, no light sample at a smooth substrate, and the
+shadow ray of a sky sample ending short of the scene's sphere.  The light tracer is held on the caustic and, beside `path`, on a floor lit through one pane, where
+the two compute different radiance scalings; vpl is not held (profiles/delta_quadrature_note.md says why).
+
 The counts are constants chosen on the CPU from the oracle's spread (bit-identical to the device's); what each case reaches is in
-profiles/surface_quadrature_note.md."""
+profiles/surface_quadrature_note.md and profiles/delta_quadrature_note.md."""
 import numpy as np
 import pytest
 
 from oracle import orc
 from rustlight_amd import api, scenes
 from tests import surface_quadrature as Q
-from tests.scene_helpers import add_second_light, context as _context, open_floor, single_bsdf, with_back_triangle
+from tests.scene_helpers import DELTA_SCENES, add_second_light, context as _context, lit_through_a_pane, open_floor, single_bsdf, with_back_triangle
 
 pytestmark = pytest.mark.gpu
 
@@ -243,3 +251,151 @@ def test_ao_on_the_open_floor(reference, limit):
     ctx = _context(open_floor(W, H))
     images = [ctx.render_ao(_seeds(k), spp=64, max_distance=limit)[0] for k in range(K)]
     Q.check_ratios(f"ao floor max_distance {limit}", [img.mean(axis=(0, 1)) / value for img in images], error / value)
+
+
+# ---- path, direct through delta surfaces: glass, the smooth metal, the smooth substrate
+STRATEGY = {"all": api.STRATEGY_ALL, "bsdf": api.STRATEGY_BSDF, "emitter": api.STRATEGY_EMITTER}
+FUSED, WAVEFRONT = (api.PIPELINE_FUSED, api.STREAM_PER_SAMPLE), (api.PIPELINE_WAVEFRONT, api.STREAM_PER_SAMPLE)
+
+
+class _DeltaScenes:
+    """Per scene of DELTA_SCENES the scene, its context (one streamed, where asked) and Q.delta_reference at the gate and at max_edges = 2, each made once."""
+
+    def __init__(self):
+        self._made = {}
+
+    def _once(self, key, make):
+        if key not in self._made:
+            self._made[key] = make()
+        return self._made[key]
+
+    def sd(self, scene):
+        return self._once(("sd", scene), lambda: DELTA_SCENES[scene][0](W, H))
+
+    def context(self, scene, streaming=False):
+        return self._once(("context", scene, streaming), lambda: _context(self.sd(scene), streaming=streaming))
+
+    def reference(self, scene, max_edges=None):
+        def make():
+            sd = self.sd(scene)
+            strategies = ("all", "bsdf", "emitter") if scene == "pane" else ("all", "emitter")
+            made = Q.delta_reference(orc.Scene(sd), sd, max_edges or DELTA_SCENES[scene][1], strategies, n=DELTA_SCENES[scene][2])
+            assert made[0].keep.mean() >= 0.9, "more than 10 % of the pixels masked"
+            print(f"reference {scene} to {max_edges or DELTA_SCENES[scene][1]} edges: {int((~made[0].keep).sum())} of {W * H} pixels masked")
+            return made
+        return self._once(("reference", scene, max_edges or DELTA_SCENES[scene][1]), make)
+
+    def path(self, scene, strategy, pipeline, stream_mode, streaming=False, below=0, **kw):
+        params = dict(max_depth=DELTA_SCENES[scene][1] + 1 - below, strategy=STRATEGY[strategy], pipeline=pipeline, stream_mode=stream_mode, **kw)
+        ctx = self.context(scene, streaming)
+        return [ctx.render(_seeds(k), api.path_params(Q.DELTA_SPP, **params))[0] for k in range(K)]
+
+
+@pytest.fixture(scope="module")
+def delta(built):
+    return _DeltaScenes()
+
+
+@pytest.mark.parametrize("pipeline,stream_mode", [FUSED, WAVEFRONT])
+@pytest.mark.parametrize("strategy", ["all", "emitter"])
+@pytest.mark.parametrize("scene", [s for s in DELTA_SCENES if s != "coat"])
+def test_path_through_delta_surfaces(delta, scene, strategy, pipeline, stream_mode):
+    """path at the scene's gate, max_depth = max_edges + 1 (confirmed on the CPU oracle, tests/test_surface_quadrature.py), against Q.delta_radiance: the
+    dielectric Fresnel term and Snell's direction on both sides of a pane and of the critical angle, the choice between the two branches and its weight, the
+    smooth metal's Fresnel factor, the MIS weight of a discrete edge, and under "emitter" the edge that left a delta vertex counting for nothing."""
+    images = delta.path(scene, strategy, pipeline, stream_mode)
+    if strategy == "all" and scene != "mirror_light":
+        fp, _ = delta.reference(scene)
+        below = delta.path(scene, strategy, pipeline, stream_mode, below=1)
+        assert np.all(np.mean([img[fp.keep].mean(axis=0) for img in below], axis=0) < np.mean([img[fp.keep].mean(axis=0) for img in images], axis=0))
+    Q.check_footprint(f"path {scene} {strategy} pipeline {pipeline}", images, delta.reference(scene), strategy)
+
+
+@pytest.mark.parametrize("pipeline,stream_mode", [FUSED, WAVEFRONT])
+def test_path_on_the_coat(delta, pipeline, stream_mode):
+    """The smooth substrate: Schlick's F along the mirror direction beside the diffuse term, each sampled half the time.  One below the gate the frame is
+    black, and under "emitter" it is black at the gate too: no light sample is made at a smooth vertex (surface_quadrature's smooth_substrate_nee)."""
+    fp, _ = delta.reference("coat")
+    assert not any(img[fp.keep].any() for img in delta.path("coat", "all", pipeline, stream_mode, below=1))
+    assert not any(img.any() for img in delta.path("coat", "emitter", pipeline, stream_mode))
+    Q.check_footprint(f"path coat all pipeline {pipeline}", delta.path("coat", "all", pipeline, stream_mode), delta.reference("coat"), "all")
+
+
+@pytest.mark.parametrize("how", ["bsdf", "reference_order", "stratified", "streaming"])
+def test_path_through_the_pane_the_other_ways(delta, how):
+    """The pane from outside under the "bsdf" strategy, the reference-order streams, `-r stratified` and the streamed scene, once each."""
+    kw = {"bsdf": dict(stream_mode=api.STREAM_PER_SAMPLE), "reference_order": dict(stream_mode=api.STREAM_REFERENCE_ORDER),
+          "stratified": dict(stream_mode=api.STREAM_STRATIFIED), "streaming": dict(stream_mode=api.STREAM_PER_SAMPLE, streaming=True)}[how]
+    strategy = "bsdf" if how == "bsdf" else "all"
+    Q.check_footprint(f"path pane {strategy} {how}", delta.path("pane", strategy, api.PIPELINE_AUTO, **kw), delta.reference("pane"), strategy)
+
+
+@pytest.mark.parametrize("scene,nb,miss", [("mirror", (1, 1), False), ("mirror_light", (1, 1), False), ("coat", (1, 0), False), ("coat", (1, 1), True)])
+def test_direct_at_a_delta_hit(delta, scene, nb, miss):
+    """direct samples one direction at the first hit and looks for a light or the sky at its end: the delta tree at max_edges = 2.  At a smooth vertex it
+    makes no light sample (direct.rs:76) and still weights a sampled direction of the substrate's diffuse half against one (direct.rs:148-169): with
+    nb_light_samples > 0 the coat reads 0.64, 0.68, 0.73 on the CPU, the reference's own text, asserted to miss."""
+    images = _direct(delta.context(scene), nb, 128)
+    Q.check_footprint(f"direct {scene} {nb}", images, delta.reference(scene, 2), "all", expect_miss=miss)
+
+
+def test_zero_variance_in_the_mirror(delta):
+    """The pixels every footprint ray of which ends on the light by way of the mirror, without russian roulette: every seed's pixel is the footprint mean of
+    specular F Le under "all" and "bsdf" (a discrete edge has MIS weight 1), within Q.mirror_pixel_bound, and exactly 0 under "emitter"."""
+    sd = delta.sd("mirror_light")
+    inside, value, spread = Q.light_in_a_mirror(orc.Scene(sd), sd)
+    assert inside.sum() >= 2, "the light's image fills too few pixels"
+    bound = Q.mirror_pixel_bound(value, spread, Q.DELTA_SPP)[inside]
+    for pipeline, stream_mode in (FUSED, WAVEFRONT):
+        for strategy in ("all", "bsdf"):
+            for img in delta.path("mirror_light", strategy, pipeline, stream_mode, rr_depth=10):
+                assert np.all(np.abs(img[inside] - value[inside]) <= bound), (strategy, pipeline, img[inside], value[inside], bound)
+        assert not any(img[inside].any() for img in delta.path("mirror_light", "emitter", pipeline, stream_mode, rr_depth=10))
+
+
+def test_path_finds_the_caustic_by_sampled_directions(delta):
+    """The caustic under "bsdf": the one pure BSDF-sampling case that needs 512 spp to stay under SE 5 % (a sampled direction finds the light's image once in
+    a thousand)."""
+    ctx = delta.context("caustic")
+    params = dict(max_depth=4, strategy=api.STRATEGY_BSDF, pipeline=api.PIPELINE_AUTO, stream_mode=api.STREAM_PER_SAMPLE)
+    images = [ctx.render(_seeds(k), api.path_params(512, **params))[0] for k in range(K)]
+    Q.check_footprint("path caustic bsdf", images, delta.reference("caustic"), "all")
+
+
+def test_light_tracing_on_the_caustic(delta):
+    """light -> mirror -> floor -> camera, the light kernel through a discrete vertex: max_depth = 3 holds direct lighting plus the image source, one below holds
+    direct lighting alone (the tree's "emitter" frame), and against that frame the depth-3 image is asserted to miss."""
+    ctx = delta.context("caustic")
+    lit = np.zeros((H, W), bool)
+    lit[:, :W - (W - H) // 2] = True
+    for max_depth, name in ((2, "emitter"), (3, "all")):
+        images = []
+        for k in range(K):
+            img, st = ctx.render_light(_seeds(k), spp=Q.LIGHT_CAUSTIC_SPP, max_depth=max_depth)
+            assert st["splats_invalid"] == 0 and st["splats_saturated"] == 0 and not img[~lit].any()
+            images.append(img)
+        Q.check_footprint(f"light-tracing caustic max_depth {max_depth}", images, delta.reference("caustic"), name, also=lit)
+    Q.check_footprint("light-tracing caustic max_depth 3, no image source", images, delta.reference("caustic"), "emitter", also=lit, expect_miss=True)
+
+
+def test_both_transports_on_the_single_crossing(delta):
+    """tests.scene_helpers.lit_through_a_pane, a floor lit through one pane of glass: `path` at max_depth = 4 holds glass_radiance_scale = "none" and misses
+    "eta2", light-tracing at max_depth = 3 holds "eta2" and misses "none" (the reference's text: both walk under Transport::Importance, which is the
+    published model for a light path and lacks eta^2 for a camera path).  One below either gate, and under "emitter", the frame is black."""
+    sd = lit_through_a_pane(W, H)
+    sc, ctx = orc.Scene(sd), _context(sd)
+    none, eta2 = (Q.delta_reference(sc, sd, 3, ("all",), dict(Q.REFERENCE, glass_radiance_scale=scale)) for scale in ("none", "eta2"))
+    assert none[0].keep.mean() >= 0.9, "more than 10 % of the pixels masked"
+    params = dict(pipeline=api.PIPELINE_AUTO, stream_mode=api.STREAM_PER_SAMPLE)
+    assert not ctx.render(_seeds(0), api.path_params(16, max_depth=4, strategy=api.STRATEGY_EMITTER, **params))[0].any()
+    assert not ctx.render(_seeds(0), api.path_params(16, max_depth=3, strategy=api.STRATEGY_ALL, **params))[0].any()
+    for strategy in ("all", "bsdf"):
+        images = [ctx.render(_seeds(k), api.path_params(Q.CROSSING_SPP, max_depth=4, strategy=STRATEGY[strategy], **params))[0] for k in range(K)]
+        Q.check_footprint(f"path through one pane {strategy}", images, none, "all")
+        Q.check_footprint(f"path through one pane {strategy}, published scaling", images, eta2, "all", expect_miss=True)
+    lit = np.zeros((H, W), bool)
+    lit[:, :W - (W - H) // 2] = True
+    assert not ctx.render_light(_seeds(0), spp=16, max_depth=2)[0].any()
+    images = [ctx.render_light(_seeds(k), spp=Q.LIGHT_CAUSTIC_SPP, max_depth=3)[0] for k in range(K)]
+    Q.check_footprint("light-tracing through one pane", images, eta2, "all", also=lit)
+    Q.check_footprint("light-tracing through one pane, path's scaling", images, none, "all", also=lit, expect_miss=True)
