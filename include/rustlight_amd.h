@@ -668,6 +668,43 @@ int rl_render_plane_single(rl_context* ctx, const rl_plane_map* map, uint32_t sp
 int rl_render_plane_uncorrelated(rl_context* ctx, uint32_t nb_primitive, int strategy, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
                                  const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats);
 
+/* ---- IntegratorPointNormal { strategy, use_mis, warps, warps_strategy, splitting, use_aa } (src/integrators/explicit/point_normal.rs:1172-1179; CLI
+ * `point-normal`, examples/cli.rs:209-224, 436-521): single scattering from the lights along the camera ray.  A plain compute_mc integrator like `ao` and
+ * `direct`: no light pass, no tree.  Built: the seven plain strategies — compute_pixel (:2585-2633) with use_mis = false and splitting = None,
+ * compute_single_tr (:2209-2284), compute_single_tr_phase (:2287-2334), compute_single_strategy (:2336-2453), create_distance_sampling's three arms without a
+ * flavour bit (:1393, :1547, :1550), EquiAngularSampling::{new, new_clamping, sample} (:26-166), PointNormalSampling::{new, sample} (:660-739),
+ * TransmittanceSampling::sample (:1087-1116), fix_random_sample_emitter's non-ATS arm (:1201-1216).  Left out: the Taylor / warp / "best" flavours, MIS,
+ * splitting, ATS, the stratified sampler, several devices.
+ * Draws per camera sample, after the 2 of the pixel jitter (none with use_aa = 0: the pixel centre): tr_ex 1 distance + 4 emitter (next, next, next2d);
+ * tr_phase 1 + 2 phase; eq_ex 4 + 1; eq_phase 4 + 1 + 2; eq_clamped_ex and pn_ex 4, then 1 only when a distance sampler exists; eq_clamped_phase 4, then 3
+ * only then (new_clamping / PointNormalSampling::new return None, :2364-2367; the point light's zero normal always does).  Every other early return comes
+ * after all draws of its sample.  Defined where the reference panics: a sample whose equi-angular range is empty (assert!(theta_a < theta_b), :42) and a
+ * transmittance sample that `exited` on an unbounded ray (:1093-1096) take their usual draws and add zero.  atan(x) = atan2f_det(x, 1), tan(x) =
+ * sinf_det(x) / cosf_det(x) — it departs from libm's tan by this construction.
+ * stream_mode: RL_STREAM_PER_SAMPLE (the per-pixel, per-sample fork of rl_render_ao) or RL_STREAM_REFERENCE_ORDER, the reference's image seed for seed: a
+ * constant-count strategy enters the block's stream by jump-ahead, a data-dependent one takes a chain pass first (stats->ms_prepass) that records where every
+ * pixel starts; the context option ref_single_pass walks every block on one lane instead (same bytes, same counters).
+ * Refused before any kernel: no medium (the reference unwraps scene.volume), a scene built with the light tree (`-x ats`), a directional light (its
+ * correct_flux is todo!()), an environment emitter, RL_STREAM_STRATIFIED: RL_ERR_UNSUPPORTED; no emitter: RL_ERR_NO_EMITTER; an unknown strategy or stream
+ * mode, spp = 0, a bad shard: RL_ERR_INVALID_ARGUMENT; a jump-ahead frame with 256 * spp * D > 2^32 - 1: RL_ERR_UNSUPPORTED.  Exact numerics, one device, host
+ * output; shards as rl_render_ao.  Counters: camera_samples; rng_draws, the exact count; extension_rays = camera rays + phase rays (the chain pass's rays are
+ * not counted); shadow_rays = visible() calls; vertices = samples for which a distance sampler existed; kernel_launches, ms_other = k_pn_pixel.
+ * The struct is declared in two statements: tests/test_abi_layout.py holds the ten structs above to their mirrors, tests/test_pn_abi.py holds this one. */
+typedef enum rl_pn_strategy { RL_PN_TR_EX = 0, RL_PN_TR_PHASE = 1, RL_PN_EQ_EX = 2, RL_PN_EQ_PHASE = 3, RL_PN_EQ_CLAMPED_EX = 4, RL_PN_EQ_CLAMPED_PHASE = 5,
+                              RL_PN_PN_EX = 6 } rl_pn_strategy;
+struct rl_point_normal_params {
+    uint32_t spp;               /* scene.nb_samples */
+    int32_t strategy;           /* rl_pn_strategy: the names of cli.rs:455-492 without a flavour */
+    int32_t use_aa;             /* !disable_aa (cli.rs:213, 516) */
+    int32_t stream_mode;        /* rl_stream_mode: reference order or per sample */
+    int32_t seed_variant;
+    uint32_t shard_index, shard_count;
+};
+typedef struct rl_point_normal_params rl_point_normal_params;
+void rl_point_normal_params_default(rl_point_normal_params* params);   /* cli.rs:209-224: strategy tr_ex, AA on; spp 1, reference order, one shard */
+int rl_render_point_normal(rl_context* ctx, const rl_point_normal_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
+                           rl_render_stats* stats);
+
 /* Frames in flight behind one call (the progressive wrappers' passes, avg.rs:5-131 / equal_time.rs:4-66: N independent renders of one scene): frame f — block
  * seeds `block_seeds[f]`, host image `out_rgb[f]` (W*H*3 f32) — renders on `ctxs[f % k]` from host thread f % k, k = min(n_ctx, n_frames); `ctxs` are distinct
  * contexts of the same scene.  Returns when every frame is done; the images (and `stats[f]`, if not NULL) are those of `n_frames` rl_render_path calls one after

@@ -521,6 +521,27 @@ struct IntegratorSinglePlaneUncorrelated {
     }
 };
 
+// struct IntegratorPointNormal { strategy, use_mis, warps, warps_strategy, splitting, use_aa } (src/integrators/explicit/point_normal.rs:1172-1179) +
+// Integrator::compute -> compute_mc (:1181-1199), seed for seed the reference: the block seeds straight from the main sampler, then rl_render_point_normal.
+// The seven plain strategies; the CLI refuses the flavoured ones, MIS, splitting and the warps before it gets here.
+struct IntegratorPointNormal {
+    rl_pn_strategy strategy = RL_PN_TR_EX;
+    bool use_aa = true;
+    rl_stream_mode stream_mode = RL_STREAM_REFERENCE_ORDER;
+    int device = 0;
+    Options options;
+    rl_render_stats last_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        RenderContext ctx(scene, device, options);
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        rl_point_normal_params p;
+        rl_point_normal_params_default(&p);
+        p.spp = (uint32_t)scene.nb_samples; p.strategy = strategy; p.use_aa = use_aa ? 1 : 0; p.stream_mode = stream_mode; p.seed_variant = sampler.variant;
+        check(rl_render_point_normal(ctx, &p, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "point-normal");
+        return std::move(ctx.img);
+    }
+};
+
 // IntegratorAverage (src/integrators/avg.rs:5-131) and IntegratorEqualTime (src/integrators/equal_time.rs:4-66):
 // host loops around any inner integrator with `compute(IndependentSampler&, Scene&)`.
 template <class T, class = void> struct has_frames_in_flight : std::false_type {};

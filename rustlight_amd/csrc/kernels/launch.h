@@ -1,5 +1,5 @@
 // launch.h — host-side launchers of the kernel families that live in their own translation units (fused_*.hip, fusedq_*.hip, fused_strat_*.hip,
-// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, beamgen_*.hip, beam_*.hip, pplanegen_*.hip, pplane_*.hip, vrl_*.hip, plane_*.hip, uplane_*.hip), so that the families compile in parallel, and
+// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, beamgen_*.hip, beam_*.hip, pplanegen_*.hip, pplane_*.hip, vrl_*.hip, plane_*.hip, uplane_*.hip, pn_*.hip), so that the families compile in parallel, and
 // the dispatcher every one of them maps its run-time arguments to template arguments with (with_bsdf, with_flag).  Launch errors are picked up by
 // the caller's hipGetLastError().
 #pragma once
@@ -187,6 +187,17 @@ struct UPlaneConst {
     float inv_nb;                       // 1.0 / nb_primitive as f32
 };
 
+// IntegratorPointNormal (pn.hip.h).  How a lane of k_pn_pixel comes by its sampler: forked per sample from the pixel's seed (per-sample streams); the block's
+// stream entered by jump-ahead (reference order, a constant number of draws per sample); the state k_pn_chain recorded for the pixel (reference order, a
+// data-dependent number); or one lane per block walking the block's stream (reference order in a single pass)
+enum { PN_MODE_PER_SAMPLE = 0, PN_MODE_ADVANCE = 1, PN_MODE_GIVEN = 2, PN_MODE_BLOCK = 3 };
+struct PnConst {
+    int use_aa;                         // 0: the pixel centre instead of the two jitter draws (-z)
+    int mode;                           // PN_MODE_*
+    unsigned draws;                     // PN_MODE_ADVANCE: D, the draws of one camera sample
+    unsigned long long* pixel_states;   // [pixel item][4] the block sampler's state at the pixel's first sample: k_pn_chain writes, k_pn_pixel reads (PN_MODE_GIVEN)
+};
+
 // mat: the scene's one BSDF type, or -1 = run-time switch per vertex.  area_only: every emitter is a mesh area light and there is no light
 // tree (the NEE code of the other emitter kinds is compiled out: same results, 84 -> 21 spilled VGPRs on the diffuse Cornell box)
 void launch_fused_lds(int mat, bool medium, bool area_only, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc);
@@ -259,6 +270,10 @@ void launch_plane_stream(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipS
 // IntegratorSinglePlaneUncorrelated (uplane.hip.h): k_uplane over the owned blocks, mode = PLANE_MODE_*
 void launch_uplane_lds(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const UPlaneConst& uc);
 void launch_uplane_stream(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const UPlaneConst& uc);
+// IntegratorPointNormal (pn.hip.h): chain = false k_pn_pixel over the pixel items (or, PN_MODE_BLOCK, the owned blocks), true k_pn_chain over the owned blocks;
+// strategy = rl_pn_strategy
+void launch_pn_lds(bool chain, int strategy, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
+void launch_pn_stream(bool chain, int strategy, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)
 void dump_stage_timers_stream();
 void dump_chain_timers_lds();      // dev-only (-DRL_STAGE_TIMERS): cycle shares of k_stream_chain's stages
