@@ -705,6 +705,39 @@ void rl_point_normal_params_default(rl_point_normal_params* params);   /* cli.rs
 int rl_render_point_normal(rl_context* ctx, const rl_point_normal_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
                            rl_render_stats* stats);
 
+/* ---- IntegratorPointNormal with use_mis = true (point_normal.rs:2605-2612; CLI `point-normal -x`, here `point-normal-mis`: `point-normal -x` stays refused):
+ * phase sampling and explicit light sampling combined with two or three distance samplers under the power heuristic.  Only the distance family of `strategy`
+ * selects the function, the EX / PHASE bit is ignored: tr_* compute_multiple_tr (:2095-2206), eq_ex | eq_phase compute_multiple_equiangular (:1849-2091),
+ * eq_clamped_* and pn_ex compute_multiple_strategy (:1560-1847); the two names of a family render the same bytes.  New beside rl_render_point_normal:
+ * EquiAngularSampling::{inside_bound, pdf} (:135-175), PointNormalSampling::pdf (:741-754), TransmittanceSampling::pdf (:1118-1130), the non-ATS arm of
+ * EmitterSampler::direct_pdf_ray / direct_pdf (emitter.rs:1537, 1574) and the four-pdf power heuristic, pdf_current^2 / sum of squares in the order of the
+ * vec!, plain IEEE arithmetic: a 0 / 0 or inf / inf weight is NaN and reaches the colour as the reference's would.  Only the non-ATS arms are built.
+ * Draws per camera sample after the 2 of the jitter, in order: tr 1 distance, 4 emitter, 2 phase = 7; eq 1 transmittance, 4 emitter, 1 equi-angular, 2 phase =
+ * 8; clamped and pn 4 emitter, 2 phase, 1 transmittance, 1 equi-angular, and 1 more only when create_distance_sampling gave Some = 8 | 9.  Second rays: tr 1
+ * visibility + 1 phase, the others 2 + 2.
+ * Kept as the reference has them: compute_multiple_strategy and compute_multiple_equiangular scale the flux by FRAC_1_PI whatever the emitter is
+ * (compute_multiple_tr uses correct_flux()); a point light adds nothing (its zero normal makes n . (-d) <= 0 in every explicit technique and no phase ray hits
+ * it).  Defined where the reference panics: (1) an EquiAngularSampling::new whose assert!(theta_a < theta_b) (:42) would fire — built on the sampled light
+ * position: the sample takes its usual draws, traces no second ray and adds zero; built to evaluate a pdf at a phase ray's hit: that contribution is zero;
+ * (2) a transmittance sample that `exited` on an unbounded ray (:1093-1096): the usual draws, no second ray, zero.
+ * Stream modes, shards, refusals and their codes are rl_render_point_normal's (a jump-ahead frame with 256 * spp * D > 2^32 - 1, D = 7 or 8 plus the jitter's
+ * 2: RL_ERR_UNSUPPORTED; clamped and pn take the chain pass, stats->ms_prepass).  Counters: camera_samples; rng_draws, the exact count; extension_rays =
+ * camera rays + phase rays traced; shadow_rays = visible() calls (none when n . (-d) <= 0 or t_light is zero or not finite); vertices = for tr and eq the
+ * samples no defined panic ended, for clamped and pn the samples whose third sampler was Some; kernel_launches; ms_other = k_pnmis_pixel.
+ * The struct has rl_point_normal_params' fields and is declared in two statements like it; tests/test_pnmis_abi.py holds it to its mirrors. */
+struct rl_point_normal_mis_params {
+    uint32_t spp;               /* scene.nb_samples */
+    int32_t strategy;           /* rl_pn_strategy: only its distance family matters */
+    int32_t use_aa;             /* !disable_aa */
+    int32_t stream_mode;        /* rl_stream_mode: reference order or per sample */
+    int32_t seed_variant;
+    uint32_t shard_index, shard_count;
+};
+typedef struct rl_point_normal_mis_params rl_point_normal_mis_params;
+void rl_point_normal_mis_params_default(rl_point_normal_mis_params* params);   /* strategy tr_ex, AA on; spp 1, reference order, one shard */
+int rl_render_point_normal_mis(rl_context* ctx, const rl_point_normal_mis_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
+                               rl_render_stats* stats);
+
 /* Frames in flight behind one call (the progressive wrappers' passes, avg.rs:5-131 / equal_time.rs:4-66: N independent renders of one scene): frame f — block
  * seeds `block_seeds[f]`, host image `out_rgb[f]` (W*H*3 f32) — renders on `ctxs[f % k]` from host thread f % k, k = min(n_ctx, n_frames); `ctxs` are distinct
  * contexts of the same scene.  Returns when every frame is done; the images (and `stats[f]`, if not NULL) are those of `n_frames` rl_render_path calls one after

@@ -51,12 +51,18 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_pplane_generate", "rl_pplane_generate_paths", "rl_pplane_info", "rl_pplane_read", "rl_pplane_destroy", "rl_pplane_map_build", "rl_pplane_map_build_words", "rl_pplane_map_info", "rl_pplane_map_read", "rl_pplane_map_destroy", "rl_render_photon_planes", "rl_vrl_map_build", "rl_vrl_map_build_words", "rl_vrl_map_info", "rl_vrl_map_read", "rl_vrl_map_destroy", "rl_render_vrl", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_point_normal_params_default", "rl_render_point_normal", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_pplane_generate", "rl_pplane_generate_paths", "rl_pplane_info", "rl_pplane_read", "rl_pplane_destroy", "rl_pplane_map_build", "rl_pplane_map_build_words", "rl_pplane_map_info", "rl_pplane_map_read", "rl_pplane_map_destroy", "rl_render_photon_planes", "rl_vrl_map_build", "rl_vrl_map_build_words", "rl_vrl_map_info", "rl_vrl_map_read", "rl_vrl_map_destroy", "rl_render_vrl", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_point_normal_params_default", "rl_render_point_normal", "rl_point_normal_mis_params_default", "rl_render_point_normal_mis", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
 class PointNormalParams(C.Structure):
     """rl_point_normal_params (include/rustlight_amd.h): IntegratorPointNormal's fields that are built, and how the call runs."""
+    _fields_ = [("spp", C.c_uint32), ("strategy", C.c_int32), ("use_aa", C.c_int32), ("stream_mode", C.c_int32), ("seed_variant", C.c_int32),
+                ("shard_index", C.c_uint32), ("shard_count", C.c_uint32)]
+
+
+class PointNormalMisParams(C.Structure):
+    """rl_point_normal_mis_params (include/rustlight_amd.h): rl_point_normal_params' fields for IntegratorPointNormal with use_mis."""
     _fields_ = [("spp", C.c_uint32), ("strategy", C.c_int32), ("use_aa", C.c_int32), ("stream_mode", C.c_int32), ("seed_variant", C.c_int32),
                 ("shard_index", C.c_uint32), ("shard_count", C.c_uint32)]
 
@@ -197,6 +203,9 @@ def lib():
     L.rl_point_normal_params_default.argtypes = [C.POINTER(PointNormalParams)]
     L.rl_point_normal_params_default.restype = None
     L.rl_render_point_normal.argtypes = [vp, C.POINTER(PointNormalParams), u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
+    L.rl_point_normal_mis_params_default.argtypes = [C.POINTER(PointNormalMisParams)]
+    L.rl_point_normal_mis_params_default.restype = None
+    L.rl_render_point_normal_mis.argtypes = [vp, C.POINTER(PointNormalMisParams), u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
     for fn in (L.rl_render_ao, L.rl_render_direct):
         fn.argtypes = [vp, C.POINTER(abi.McParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_multi_create.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -784,6 +793,18 @@ class Context(_ImageCalls):
         p.spp, p.strategy, p.use_aa, p.stream_mode, p.seed_variant = spp, pn_strategy(strategy), int(bool(use_aa)), stream_mode, seed_variant
         p.shard_index, p.shard_count = shard_index, shard_count
         img, st = self._image_call(seeds, lambda sp, n, out, st: lib().rl_render_point_normal(self.h, C.byref(p), sp, n, out, st))
+        return img, st.as_dict()
+
+    def render_point_normal_mis(self, seeds, strategy="tr_ex", spp=1, use_aa=True, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
+        """IntegratorPointNormal with use_mis behind its block seeds (point_normal.rs:2605-2612) through rl_render_point_normal_mis: (image HxWx3 f32, stats
+        dict).  Only the distance family of `strategy` matters.  stats: camera_samples, rng_draws, extension_rays = camera rays + phase rays, shadow_rays =
+        visibility rays, vertices = samples no defined panic ended (tr, eq) or whose third sampler was Some (clamped, pn); ms_prepass = the chain pass of clamped
+        and pn in reference order, ms_other = k_pnmis_pixel."""
+        p = PointNormalMisParams()
+        lib().rl_point_normal_mis_params_default(C.byref(p))
+        p.spp, p.strategy, p.use_aa, p.stream_mode, p.seed_variant = spp, pn_strategy(strategy), int(bool(use_aa)), stream_mode, seed_variant
+        p.shard_index, p.shard_count = shard_index, shard_count
+        img, st = self._image_call(seeds, lambda sp, n, out, st: lib().rl_render_point_normal_mis(self.h, C.byref(p), sp, n, out, st))
         return img, st.as_dict()
 
     def trace(self, origins, directions):
@@ -1465,6 +1486,23 @@ class IntegratorPointNormal(_Integrator):
         w, h = scene.size
         seeds = sampler.block_seeds(w, h)
         img, self.last_stats = ctx.render_point_normal(seeds, self.strategy, nb_samples, self.use_aa, self.stream_mode, sampler.variant)
+        return img
+
+
+class IntegratorPointNormalMis(_Integrator):
+    """IntegratorPointNormal with use_mis = true (src/integrators/explicit/point_normal.rs:1172-1179, 2605-2612) + Integrator::compute -> compute_mc, seed for
+    seed the reference: the block seeds straight from the main sampler, then rl_render_point_normal_mis.  Only the distance family of the strategy selects the
+    estimator (tr, eq, clamped, pn); the two names of a family render the same bytes."""
+
+    def __init__(self, strategy="tr_ex", use_aa=True, stream_mode=STREAM_REFERENCE_ORDER, device=0, options=None):
+        super().__init__(device, options)
+        self.strategy, self.use_aa, self.stream_mode = PN_STRATEGIES[pn_strategy(strategy)], use_aa, stream_mode
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        ctx = self._context(scene)
+        w, h = scene.size
+        seeds = sampler.block_seeds(w, h)
+        img, self.last_stats = ctx.render_point_normal_mis(seeds, self.strategy, nb_samples, self.use_aa, self.stream_mode, sampler.variant)
         return img
 
 

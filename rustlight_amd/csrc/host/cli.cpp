@@ -32,6 +32,9 @@
 //               | point-normal [-s|--strategy tr_ex|tr_phase|eq_ex|eq_phase|eq_clamped_ex|eq_clamped_phase|pn_ex] [-z|--disable-aa]   (examples/cli.rs:209-224,
 //                 436-521; needs -m; both stream modes; independent sampler, exact numerics, one device, one pass, no light tree.  The flavoured strategies
 //                 (Taylor, warp, best), -x / --use-mis, -k / --splitting, -w / --warps and --warps-strategy are not built and are refused by name)
+//               | point-normal-mis [-s|--strategy NAME] [-z|--disable-aa]   (the reference's `point-normal -x`: IntegratorPointNormal with use_mis; NAME is one
+//                 of point-normal's seven, of which only the distance family matters; the limits and refusals of point-normal; -x, -k, -w, --warps-strategy
+//                 and the flavoured strategies are refused by name)
 // Note `-n` / `-m` / `-r` / `-s` mean spp / medium / sampler / scale before the subcommand and
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 #include <chrono>
@@ -107,7 +110,7 @@ int main(int argc, char** argv) {
         if (!have_cmd) {
             if (a == "path" || a == "ao" || a == "direct" || a == "light-tracing" || a == "vpl") { have_cmd = true; cmd = a; }
             else if (a == "vol-primitivies" || a == "vol-primitives") { have_cmd = true; cmd = "vol-primitivies"; }
-            else if (a == "plane-single" || a == "photon-beams" || a == "photon-planes" || a == "virtual-ray-lights" || a == "point-normal") { have_cmd = true; cmd = a; }
+            else if (a == "plane-single" || a == "photon-beams" || a == "photon-planes" || a == "virtual-ray-lights" || a == "point-normal" || a == "point-normal-mis") { have_cmd = true; cmd = a; }
             else if (a == "-n" || a == "--nbsamples") nbsamples = std::strtoull(val().c_str(), nullptr, 10);
             else if (a == "-o" || a == "--output") output = val();
             else if (a == "-r" || a == "--random-number-generator") rng = val();
@@ -139,7 +142,7 @@ int main(int argc, char** argv) {
             else if (a == "--tree-build") { std::fprintf(stderr, "--tree-build is an option of the vol-primitivies subcommand: give it after the subcommand\n"); return 2; }
             else if (a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
             else if (scene_path.empty()) scene_path = a;
-            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl`, `vol-primitivies`, `photon-beams`, `photon-planes`, `virtual-ray-lights`, `plane-single` and `point-normal` subcommands are provided (got %s)\n", a.c_str()); return 2; }
+            else { std::fprintf(stderr, "only the `path`, `ao`, `direct`, `light-tracing`, `vpl`, `vol-primitivies`, `photon-beams`, `photon-planes`, `virtual-ray-lights`, `plane-single`, `point-normal` and `point-normal-mis` subcommands are provided (got %s)\n", a.c_str()); return 2; }
         } else if (a == "--light-streams" && cmd != "vpl" && cmd != "vol-primitivies" && cmd != "photon-beams" && cmd != "photon-planes" && cmd != "virtual-ray-lights") {
             std::fprintf(stderr, "%s: --light-streams is not supported (photon-beams, photon-planes, virtual-ray-lights, vpl and vol-primitivies only)\n", cmd.c_str()); return 2;
         } else if (a == "--tree-build" && cmd != "vol-primitivies") {
@@ -185,6 +188,12 @@ int main(int argc, char** argv) {
             else if (a == "-s" || a == "--strategy") plane_strategy = val();
             else if (a == "--uncorrelated") plane_uncorrelated = true;
             else { std::fprintf(stderr, "unknown plane-single option %s\n", a.c_str()); return 2; }
+        } else if (cmd == "point-normal-mis") {
+            if (a == "-s" || a == "--strategy") pn_strategy = val();
+            else if (a == "-z" || a == "--disable-aa") pn_disable_aa = true;
+            else if (a == "-x" || a == "--use-mis") { if (pn_unbuilt.empty()) pn_unbuilt = a; }
+            else if (a == "-k" || a == "--splitting" || a == "-w" || a == "--warps" || a == "--warps-strategy") { (void)val(); if (pn_unbuilt.empty()) pn_unbuilt = a; }
+            else { std::fprintf(stderr, "unknown point-normal-mis option %s\n", a.c_str()); return 2; }
         } else if (cmd == "point-normal") {
             if (a == "-s" || a == "--strategy") pn_strategy = val();
             else if (a == "-z" || a == "--disable-aa") pn_disable_aa = true;
@@ -342,28 +351,33 @@ int main(int argc, char** argv) {
         plane.device = device;
         plane.options = options;
     }
-    // point-normal: the seven plain strategies on either kind of streams; everything else of the reference's subcommand is refused by name
+    // point-normal: the seven plain strategies on either kind of streams; everything else of the reference's subcommand is refused by name.
+    // point-normal-mis: the same names and refusals, the MIS estimator of the name's distance family
     IntegratorPointNormal pn;
-    if (cmd == "point-normal") {
+    IntegratorPointNormalMis pnmis;
+    if (cmd == "point-normal" || cmd == "point-normal-mis") {
+        const char* const word = cmd.c_str();
         static const char* const names[] = {"tr_ex", "tr_phase", "eq_ex", "eq_phase", "eq_clamped_ex", "eq_clamped_phase", "pn_ex"};      // rl_pn_strategy, by value
         static const char* const flavoured[] = {"eq_best_ex", "eq_warp_ex", "eq_phase_taylor_ex", "eq_tr_taylor_ex", "eq_clamped_best_ex", "eq_clamped_warp_ex",
                                                 "eq_clamped_phase_taylor_ex", "eq_clamped_tr_taylor_ex", "pn_tr_taylor_ex", "pn_phase_taylor_ex", "pn_warp_ex", "pn_best_ex"};
         const char* list = "tr_ex, tr_phase, eq_ex, eq_phase, eq_clamped_ex, eq_clamped_phase, pn_ex";
         for (const char* f : flavoured)
-            if (pn_strategy == f) { std::fprintf(stderr, "point-normal: -s %s is not built (%s)\n", f, list); return 2; }
+            if (pn_strategy == f) { std::fprintf(stderr, "%s: -s %s is not built (%s)\n", word, f, list); return 2; }
         int which = -1;
         for (int k = 0; k < 7; k++) if (pn_strategy == names[k]) which = k;
         if (which < 0) { std::fprintf(stderr, "invalid strategy: %s (%s)\n", pn_strategy.c_str(), list); return 2; }
-        if (!pn_unbuilt.empty()) { std::fprintf(stderr, "point-normal: %s is not built (MIS, splitting and the warps are left out)\n", pn_unbuilt.c_str()); return 2; }
-        if (use_ats) { std::fprintf(stderr, "point-normal: -x ats is not built (the light tree's emitter sampling is left out)\n"); return 2; }
-        if (refused("point-normal", mode, true)) return 2;
+        if (!pn_unbuilt.empty() && cmd == "point-normal") { std::fprintf(stderr, "point-normal: %s is not built (MIS, splitting and the warps are left out)\n", pn_unbuilt.c_str()); return 2; }
+        if (!pn_unbuilt.empty()) { std::fprintf(stderr, "point-normal-mis: %s is not built (the subcommand is `point-normal -x` itself; splitting and the warps are left out)\n", pn_unbuilt.c_str()); return 2; }
+        if (use_ats) { std::fprintf(stderr, "%s: -x ats is not built (the light tree's emitter sampling is left out)\n", word); return 2; }
+        if (refused(word, mode, true)) return 2;
         const Medium m = parse_medium(medium);
-        if (m.sigma_a + m.sigma_s == 0.0f) { std::fprintf(stderr, "point-normal: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n"); return 2; }
+        if (m.sigma_a + m.sigma_s == 0.0f) { std::fprintf(stderr, "%s: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n", word); return 2; }
         pn.strategy = (rl_pn_strategy)which;
         pn.use_aa = !pn_disable_aa;
         pn.stream_mode = mode;
         pn.device = device;
         pn.options = options;
+        pnmis.strategy = pn.strategy; pnmis.use_aa = pn.use_aa; pnmis.stream_mode = mode; pnmis.device = device; pnmis.options = options;
     }
     IntegratorSinglePlaneUncorrelated uplane;
     uplane.nb_primitive = plane.nb_primitive; uplane.strategy = plane.strategy; uplane.device = device; uplane.options = options;
@@ -420,7 +434,7 @@ int main(int argc, char** argv) {
         }
         scene->build_emitters(use_ats);      // scene.build_emitters(use_ats) (cli.rs:432)
         IntegratorPathTracing integrator;
-        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams" || cmd == "photon-planes" || cmd == "virtual-ray-lights" || cmd == "plane-single" || cmd == "point-normal") strategy = "all";       // (the path integrator below is not used)
+        if (cmd == "light-tracing" || cmd == "vpl" || cmd == "vol-primitivies" || cmd == "photon-beams" || cmd == "photon-planes" || cmd == "virtual-ray-lights" || cmd == "plane-single" || cmd == "point-normal" || cmd == "point-normal-mis") strategy = "all";       // (the path integrator below is not used)
         integrator.min_depth = match_infinity(min_depth);
         integrator.max_depth = match_infinity(max_depth);
         integrator.rr_depth = match_infinity(rr_depth);
@@ -462,6 +476,8 @@ int main(int argc, char** argv) {
             else { img = plane.compute(sampler, *scene); elapsed_ms = plane.last_stats.render_ms; }
         } else if (cmd == "point-normal") {
             img = pn.compute(sampler, *scene); elapsed_ms = pn.last_stats.render_ms;
+        } else if (cmd == "point-normal-mis") {
+            img = pnmis.compute(sampler, *scene); elapsed_ms = pnmis.last_stats.render_ms;
         } else if (cmd == "light-tracing") {
             if (!equal_time.empty()) {
                 IntegratorEqualTime<IntegratorLightTracing> eq{light, std::strtod(equal_time.c_str(), nullptr) * 1000.0};

@@ -542,6 +542,26 @@ struct IntegratorPointNormal {
     }
 };
 
+// IntegratorPointNormal with use_mis = true (point_normal.rs:2605-2612): compute_multiple_tr, compute_multiple_equiangular or compute_multiple_strategy by the
+// strategy's distance family, through rl_render_point_normal_mis.  A struct of its own: IntegratorPointNormal above stays the seven plain estimators.
+struct IntegratorPointNormalMis {
+    rl_pn_strategy strategy = RL_PN_TR_EX;
+    bool use_aa = true;
+    rl_stream_mode stream_mode = RL_STREAM_REFERENCE_ORDER;
+    int device = 0;
+    Options options;
+    rl_render_stats last_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        RenderContext ctx(scene, device, options);
+        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+        rl_point_normal_mis_params p;
+        rl_point_normal_mis_params_default(&p);
+        p.spp = (uint32_t)scene.nb_samples; p.strategy = strategy; p.use_aa = use_aa ? 1 : 0; p.stream_mode = stream_mode; p.seed_variant = sampler.variant;
+        check(rl_render_point_normal_mis(ctx, &p, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "point-normal-mis");
+        return std::move(ctx.img);
+    }
+};
+
 // IntegratorAverage (src/integrators/avg.rs:5-131) and IntegratorEqualTime (src/integrators/equal_time.rs:4-66):
 // host loops around any inner integrator with `compute(IndependentSampler&, Scene&)`.
 template <class T, class = void> struct has_frames_in_flight : std::false_type {};

@@ -1338,6 +1338,7 @@ extern "C" int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_pa
 #include "vrl_render.hip.h"
 #include "pplane_render.hip.h"
 #include "pn_render.hip.h"
+#include "pnmis_render.hip.h"
 
 // ---- batched Acceleration::{trace, visible}
 namespace {

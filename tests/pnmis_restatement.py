@@ -1,0 +1,534 @@
+"""IntegratorPointNormal with use_mis restated in float32 numpy from the reference's text (src/integrators/explicit/point_normal.rs), the yardstick of
+tests/test_pnmis_restatement.py, tests/test_gpu_pnmis_exact.py, tests/test_gpu_pnmis_fuzz.py and tests/test_gpu_pnmis_quadrature.py (a plain module: `from
+tests import pnmis_restatement`).  The emitters, the medium, the three distance samplers, the deterministic math, the scenes and the block drivers' pieces are
+tests/pn_restatement.py's, imported and left as they are.
+
+compute_pixel (:2585-2633) with use_mis: only the distance family of the strategy selects the function —
+  tr       tr_ex, tr_phase                    compute_multiple_tr (:2095-2206)            draws 1 distance, 4 emitter, 2 phase                        = 7
+  eq       eq_ex, eq_phase                    compute_multiple_equiangular (:1849-2091)   1 transmittance, 4 emitter, 1 equi-angular, 2 phase         = 8
+  clamped  eq_clamped_ex, eq_clamped_phase    compute_multiple_strategy (:1560-1847)      4 emitter, 2 phase, 1 transmittance, 1 equi-angular, 1 more
+  pn       pn_ex                              the same with PointNormalSampling                only when create_distance_sampling gave Some        = 8 | 9
+(after the 2 of the jitter), with EquiAngularSampling::{inside_bound, pdf} (:135-175), PointNormalSampling::pdf (:741-754), TransmittanceSampling::pdf
+(:1118-1130, the None arm is HomogenousVolume::pdf(ray, false), volume.rs:143-150), EmitterSampler::direct_pdf_ray / direct_pdf's non-ATS arm
+(emitter.rs:1537, 1574: Mesh::direct_pdf :571-579 times emitters_cdf.pdf) and the power heuristic pdf_current^2 / (((0 + v0^2) + v1^2) + v2^2) + v3^2) in the
+order of the vec!, plain IEEE: a 0 / 0 or inf / inf weight is NaN and flows into the colour through f32 * Color, which has no guard.
+
+Kept as the reference has them: compute_multiple_strategy and compute_multiple_equiangular scale the flux by FRAC_1_PI whatever the emitter is, and
+compute_multiple_tr uses correct_flux(); a point light's zero normal makes n . (-d) = 0 <= 0 in every explicit technique and no phase ray hits a point light,
+so a point light adds nothing.
+
+Defined where the reference panics, as the kernel defines it: (1) an EquiAngularSampling::new whose assert!(theta_a < theta_b) (:42) would fire — when it is
+the sampler built on the sampled light position, the sample takes its usual draws, traces no second ray and adds zero; when it is one built only to evaluate a
+pdf at a phase ray's hit, the contribution in which it is built is zero; (2) a transmittance sample that `exited` on an unbounded ray (:1093-1096): the
+sample takes its usual draws, traces no second ray and adds zero.
+
+Counters: camera_samples; rng_draws; extension_rays = camera rays + phase rays traced; shadow_rays = visible() calls (the reference's || short-circuits: none
+when n . (-d) <= 0, none when t_light is zero or not finite); vertices = for tr and eq the samples no defined panic ended, for clamped and pn the samples whose
+third sampler was Some.
+
+As in pn_restatement, evaluate() is one set of elementwise float32 statements over arrays of camera samples; render_walk calls it sample by sample (arrays of
+one element) on one orc.Rng per block, every draw taken where the reference takes it, and render calls it once per block with the draws read from the
+block's stream at each sample's offset (chain_offsets walks the None test alone for clamped and pn, which is what the device's chain pass does).
+
+MUTATION (None in every test of the product) breaks one statement on purpose, for the quadrature test's proof that its assertion has teeth."""
+
+import numpy as np
+
+from oracle import orc
+from rustlight_amd import api
+from tests import plane_single_restatement as R
+from tests import pn_restatement as P
+from tests import uplane_restatement as U
+from tests.pn_restatement import F32, FRAC_1_PI, ONE, PI, ZERO, Refused, _col, _mul_guarded  # noqa: F401
+
+STRATEGIES = P.STRATEGIES
+FAMILIES = ("tr", "eq", "clamped", "pn")
+COUNTERS = P.COUNTERS
+MUTATION = None          # "no_sigma_s" | "no_inv_pdf" | "weight_one": see evaluate
+
+
+def family(strategy):
+    return {"tr_ex": "tr", "tr_phase": "tr", "eq_ex": "eq", "eq_phase": "eq", "eq_clamped_ex": "clamped", "eq_clamped_phase": "clamped", "pn_ex": "pn"}[strategy]
+
+
+def third(fam):
+    """The strategy whose create_distance_sampling arm is the family's third sampler."""
+    return "pn_ex" if fam == "pn" else "eq_clamped_ex"
+
+
+def draws_per_sample(strategy, use_aa=True):
+    """The constant count D of a family, None when it depends on the data."""
+    base = {"tr": 7, "eq": 8}.get(family(strategy))
+    return None if base is None else base + (2 if use_aa else 0)
+
+
+def max_draws(strategy, use_aa=True):
+    return (2 if use_aa else 0) + {"tr": 7, "eq": 8, "clamped": 9, "pn": 9}[family(strategy)]
+
+
+# ---- the pdf side of the distance samplers
+def pdf_equiangular(s, dist):
+    """EquiAngularSampling::pdf of a sampler made by new (clamped = false)."""
+    with np.errstate(all="ignore"):
+        t = (dist - s["delta"]).astype(np.float32)
+        return (s["d_l"] / ((s["theta_b"] - s["theta_a"]) * (s["d_l"] * s["d_l"] + t * t))).astype(np.float32)
+
+
+def inside_bound(s, dist):
+    with np.errstate(all="ignore"):
+        theta = P._atan(((dist - s["delta"]) / s["d_l"]).astype(np.float32))
+        return (theta >= s["theta_a"]) & (theta <= s["theta_b"])
+
+
+def pdf_third(fam, s, dist):
+    """The pdf of create_distance_sampling's sampler: EquiAngularSampling::pdf with clamped = true, or PointNormalSampling::pdf."""
+    with np.errstate(all="ignore"):
+        if fam == "clamped":
+            val = pdf_equiangular(s, dist)
+        else:
+            t = (dist - s["delta"]).astype(np.float32)
+            theta = P._atan((t / s["d_l"]).astype(np.float32))
+            pdf_angular = (s["a"] * P._cos(theta) + s["b"] * P._sin(theta)).astype(np.float32)
+            jacobian = (s["d_l"] / (s["d_l"] * s["d_l"] + t * t)).astype(np.float32)
+            val = np.abs(pdf_angular * jacobian).astype(np.float32)
+        return np.where(inside_bound(s, dist), val, ZERO).astype(np.float32)
+
+
+def pdf_transmittance(med, has_max, max_dist, dist):
+    sigma_t = med.sigma_t[None, :]
+    with np.errstate(all="ignore"):
+        pdf0 = R._avg((sigma_t * P._expf(-_mul_guarded(sigma_t, dist))).astype(np.float32))
+        norm_c = (ONE - P._expf(_mul_guarded(-sigma_t, max_dist))).astype(np.float32)
+        pdf1 = R._avg(((sigma_t / norm_c) * P._expf(_mul_guarded(-sigma_t, dist))).astype(np.float32))
+    return np.where(has_max, pdf1, pdf0).astype(np.float32)
+
+
+def power4(v0, v1, v2, v3):
+    with np.errstate(all="ignore"):
+        total = ((((ZERO + v0 * v0) + v1 * v1) + v2 * v2) + v3 * v3).astype(np.float32)
+        return ((v0 * v0) / total).astype(np.float32)
+
+
+def pdf_other_clamped(fam, has_max, max_dist, o, d, pos, nrm, dist):
+    """compute_pdf_other_clamped (:1574-1578)."""
+    s, ok = P.make_sampler(third(fam), has_max, max_dist, o, d, pos, nrm)
+    return np.where(ok, pdf_third(fam, s, dist), ZERO).astype(np.float32)
+
+
+def sample_emitter(em, r_sel, r_pos, ux, uy):
+    """random_sample_emitter_position without a correct_flux: (p, n, flux = w / pdf_sel, pdf = sampled_pos.pdf * pdf_sel, is_surface, correct_flux)."""
+    p, nrm, _, surface = em.sample(r_sel, r_pos, ux, uy)
+    n = r_sel.shape[0]
+    ids = P.sample_discrete(em.cdf, r_sel)
+    pdf_sel = (em.cdf[ids + 1] - em.cdf[ids]).astype(np.float32)
+    flux, pdf, correct = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    with np.errstate(all="ignore"):
+        for e in range(em.n):
+            m = ids == e
+            if em.kind[e] == "point":
+                flux[m] = ((em.intensity[e] * F32(4.0)) * PI).astype(np.float32)
+                pdf[m] = ONE
+                correct[m] = ONE / (F32(4.0) * PI)
+            else:
+                me = em.mesh[e]
+                flux[m] = ((me["emission"] * PI) / (ONE / me["total"])).astype(np.float32)
+                pdf[m] = ONE / me["total"]
+                correct[m] = ONE / PI
+        flux = (flux / _col(pdf_sel)).astype(np.float32)
+        pdf = (pdf * pdf_sel).astype(np.float32)
+    return p, nrm, flux, pdf, surface, correct
+
+
+class Frame(P.Frame):
+    """pn_restatement's frame, and for a phase ray's hit Mesh::pdf() and emitters_cdf.pdf of every emissive mesh."""
+
+    def __init__(self, sd, sc=None):
+        super().__init__(sd, sc)
+        self.light_pdf = {}
+        e = 0
+        for i, m in enumerate(sd.meshes):
+            if m.emission is None:
+                continue
+            self.light_pdf[i] = (F32(ONE / self.emitters.mesh[e]["total"]), F32(self.emitters.cdf[e + 1] - self.emitters.cdf[e]))
+            e += 1
+
+
+def _explicit(fr, d, pos, nrm, flux, pdf_area, p, trans, weight, active, mutate=False):
+    """An explicit contribution of compute_multiple_equiangular / compute_multiple_strategy: (radiance [n, 3], visible() calls [n])."""
+    med, n = fr.medium, d.shape[0]
+    out = np.zeros((n, 3), np.float32)
+    with np.errstate(all="ignore"):
+        d_light = (pos - p).astype(np.float32)
+        t_light = R._mag(d_light)
+        go = active & ~((t_light == ZERO) | ~np.isfinite(t_light))
+        d_light = (d_light / _col(t_light)).astype(np.float32)
+        cos_l = R._dot(nrm, -d_light).astype(np.float32)
+        t2 = (t_light * t_light).astype(np.float32)
+        pdf_ex = ((pdf_area * t2) / cos_l).astype(np.float32)
+        fl = R._div_guarded(_mul_guarded(_mul_guarded(flux, np.full(n, FRAC_1_PI, np.float32)), cos_l), t2)
+        go &= ~(cos_l <= ZERO)
+        idx = np.flatnonzero(go)
+        if idx.size:
+            vis = fr.sc.visible(p[idx], pos[idx]).astype(bool)
+            w_i = (-d).astype(np.float32)
+            ph = med.phase_eval(w_i, d_light)
+            w = weight(pdf_ex, R._avg(ph))
+            if mutate and MUTATION == "weight_one":
+                w = np.ones_like(w)
+            v = (fl * med.sigma_s[None, :]).astype(np.float32) if not (mutate and MUTATION == "no_sigma_s") else fl
+            v = (v * ph).astype(np.float32)
+            value = (((v * _col(w)) * trans) * med.transmittance(t_light)).astype(np.float32)
+            k = idx[vis]
+            out[k] = value[k]
+    return out, go.astype(np.int64)
+
+
+def _phase(fr, p, nd, trans, weight, active):
+    """A phase contribution: (radiance [n, 3], rays traced [n]).  weight(k, pdf_ex, its_p, its_n) -> (ok, w) for the sample indices k."""
+    med, n = fr.medium, p.shape[0]
+    out = np.zeros((n, 3), np.float32)
+    idx = np.flatnonzero(active)
+    if not idx.size:
+        return out, active.astype(np.int64)
+    _, _, _, mesh2, _ = fr.sc.trace(p[idx], nd[idx])
+    ks, ips, ins, ms = [], [], [], []
+    for j, k in enumerate(idx):
+        if int(mesh2[j]) not in fr.light_mesh:
+            continue
+        its = fr.sc.trace_full(p[k], nd[k])
+        if its is None:
+            continue
+        ks.append(k); ips.append(R._v(its["p"])); ins.append(R._v(its["n_g"])); ms.append(int(mesh2[j]))
+    if not ks:
+        return out, active.astype(np.int64)
+    k = np.asarray(ks)
+    ip, inn = np.asarray(ips, np.float32).reshape(-1, 3), np.asarray(ins, np.float32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        facing = ~(R._dot(inn, -nd[k]) < ZERO)
+        to = (ip - p[k]).astype(np.float32)
+        light_trans = med.transmittance(R._mag(to))
+        cos_light = np.fmax(R._dot(inn, -nd[k]), ZERO).astype(np.float32)                    # Mesh::direct_pdf (emitter.rs:571-579)
+        geom = (cos_light / R._dot(to, to)).astype(np.float32)
+        inv_area = np.asarray([fr.light_pdf[m][0] for m in ms], np.float32)
+        e_pdf = np.asarray([fr.light_pdf[m][1] for m in ms], np.float32)
+        pdf_ex = np.where(cos_light == ZERO, ZERO * e_pdf, (inv_area / geom) * e_pdf).astype(np.float32)
+        ok, w = weight(k, pdf_ex, ip, inn)
+        emit = np.asarray([fr.light_mesh[m] for m in ms], np.float32).reshape(-1, 3)
+        v = ((emit * med.sigma_s[None, :]) * ONE).astype(np.float32)
+        value = (((v * _col(w)) * trans[k]) * light_trans).astype(np.float32)
+        keep = facing & ok
+        out[k[keep]] = value[keep]
+    return out, active.astype(np.int64)
+
+
+def evaluate(fr, strategy, use_aa, px, py, draw):
+    """compute_pixel with use_mis for the camera samples of pixels (px, py) [n]: draw() gives the next draw of every sample, [n] f32, and is called exactly
+    where the reference draws.  Returns (radiance [n, 3], counts dict of [n] arrays)."""
+    fam = family(strategy)
+    n = px.shape[0]
+    sc, med = fr.sc, fr.medium
+    if use_aa:
+        u, v = (px.astype(np.float32) + draw()).astype(np.float32), (py.astype(np.float32) + draw()).astype(np.float32)
+    else:
+        u, v = (px.astype(np.float32) + F32(0.5)).astype(np.float32), (py.astype(np.float32) + F32(0.5)).astype(np.float32)
+    rays = [sc.camera_generate(float(a), float(b)) for a, b in zip(u, v)]
+    o = np.asarray([r[0] for r in rays], np.float32).reshape(-1, 3)
+    d = np.asarray([r[1] for r in rays], np.float32).reshape(-1, 3)
+    t, _, _, mesh, _ = sc.trace(o, d)
+    has_max, max_dist = mesh >= 0, t.astype(np.float32)
+    w_i = (-d).astype(np.float32)
+    cnt = {"draws": np.full(n, 2 if use_aa else 0, np.int64), "ext": np.ones(n, np.int64), "shadow": np.zeros(n, np.int64), "vertices": np.zeros(n, np.int64),
+           "some": np.ones(n, bool), "panic": np.zeros(n, bool), "o": o, "d": d, "has_max": has_max, "max_dist": max_dist}
+
+    def phase_dir(ux, uy):
+        nd = med.phase_sample(w_i, ux, uy)
+        pdf = R._avg(med.phase_eval(w_i, nd)) if med.hg else np.full(n, ONE / (PI * F32(4.0)), np.float32)
+        return nd, pdf
+
+    with np.errstate(all="ignore"):
+        if fam == "tr":
+            t_cam, t_pdf, ok = P.sample_transmittance(med, has_max, max_dist, draw())
+            r_sel, r_pos, ux, uy = draw(), draw(), draw(), draw()
+            sx, sy = draw(), draw()
+            cnt["draws"] += 7
+            cnt["panic"] = ~ok
+            cnt["vertices"] = ok.astype(np.int64)
+            pos, nrm, flux, pdf_area, _, correct = sample_emitter(fr.emitters, r_sel, r_pos, ux, uy)
+            p = (o + d * _col(t_cam)).astype(np.float32)
+            cam_trans = R._div_guarded(med.transmittance(t_cam), t_pdf) if MUTATION != "no_inv_pdf" else med.transmittance(t_cam)
+            # contrib_ex (:2138-2168)
+            ex = np.zeros((n, 3), np.float32)
+            flux0 = _mul_guarded(flux, correct)
+            d_light = (pos - p).astype(np.float32)
+            t_light = R._mag(d_light)
+            go = ok & ~((t_light == ZERO) | ~np.isfinite(t_light))
+            d_light = (d_light / _col(t_light)).astype(np.float32)
+            cos_l = R._dot(nrm, -d_light).astype(np.float32)
+            geom = (cos_l / (t_light * t_light)).astype(np.float32)
+            fl = _mul_guarded(flux0, geom)
+            go &= ~(cos_l <= ZERO)
+            cnt["shadow"] = go.astype(np.int64)
+            idx = np.flatnonzero(go)
+            if idx.size:
+                vis = sc.visible(p[idx], pos[idx]).astype(bool)
+                ph = med.phase_eval(w_i, d_light)
+                contrib = (fl * med.sigma_s[None, :]).astype(np.float32) if MUTATION != "no_sigma_s" else fl
+                contrib = (contrib * ph).astype(np.float32)
+                pdf_ph = R._avg(ph)
+                pdf_ex = (pdf_area / geom).astype(np.float32)
+                w = ((pdf_ex * pdf_ex) / (pdf_ph * pdf_ph + pdf_ex * pdf_ex)).astype(np.float32)
+                if MUTATION == "weight_one":
+                    w = np.ones_like(w)
+                value = (((contrib * _col(w)) * cam_trans) * med.transmittance(t_light)).astype(np.float32)
+                k = idx[vis]
+                ex[k] = value[k]
+            # contrib_phase (:2172-2203)
+            nd, pdf_phase = phase_dir(sx, sy)
+
+            def w_tr(k, pdf_ex, ip, inn):
+                pp = pdf_phase[k]
+                return np.ones(k.shape[0], bool), ((pp * pp) / (pp * pp + pdf_ex * pdf_ex)).astype(np.float32)
+
+            ph_c, rays2 = _phase(fr, p, nd, cam_trans, w_tr, ok)
+            cnt["ext"] = cnt["ext"] + rays2
+            return (ex + ph_c).astype(np.float32), cnt
+
+        if fam == "eq":
+            t_tr, pdf_tr, ok_tr = P.sample_transmittance(med, has_max, max_dist, draw())
+            r_sel, r_pos, ux, uy = draw(), draw(), draw(), draw()
+            xi_eq = draw()
+            sx, sy = draw(), draw()
+            cnt["draws"] += 8
+            pos, nrm, flux, pdf_area, _, _ = sample_emitter(fr.emitters, r_sel, r_pos, ux, uy)
+            se, ok_eq = P.make_sampler("eq_ex", has_max, max_dist, o, d, pos, nrm)
+            ok = ok_tr & ok_eq
+            cnt["panic"] = ~ok
+            cnt["vertices"] = ok.astype(np.int64)
+            some = np.zeros(n, bool)
+            t_cl = pdf_cl = None
+        else:
+            r_sel, r_pos, ux, uy = draw(), draw(), draw(), draw()
+            pos, nrm, flux, pdf_area, _, _ = sample_emitter(fr.emitters, r_sel, r_pos, ux, uy)
+            sc3, some = P.make_sampler(third(fam), has_max, max_dist, o, d, pos, nrm)
+            se, ok_eq = P.make_sampler("eq_ex", has_max, max_dist, o, d, pos, nrm)
+            sx, sy = draw(), draw()
+            xi_tr, xi_eq = draw(), draw()
+            xi_cl = draw() if some.any() else np.zeros(n, np.float32)
+            cnt["draws"] += 8 + some.astype(np.int64)
+            cnt["some"] = some.copy()
+            cnt["vertices"] = some.astype(np.int64)
+            t_tr, pdf_tr, ok_tr = P.sample_transmittance(med, has_max, max_dist, xi_tr)
+            ok = ok_tr & ok_eq
+            cnt["panic"] = ~ok
+            t_cl, pdf_cl = P.sample_point_normal(sc3, xi_cl) if fam == "pn" else P.sample_equiangular(sc3, has_max, max_dist, xi_cl)
+        t_eq, pdf_eq = P.sample_equiangular(se, has_max, max_dist, xi_eq)
+        p_tr, p_eq = (o + d * _col(t_tr)).astype(np.float32), (o + d * _col(t_eq)).astype(np.float32)
+        trans_tr = R._div_guarded(med.transmittance(t_tr), pdf_tr) if MUTATION != "no_inv_pdf" else med.transmittance(t_tr)
+        trans_eq = R._div_guarded(med.transmittance(t_eq), pdf_eq)
+        nd, pdf_phase = phase_dir(sx, sy)
+        if fam == "eq":
+            pdf_eq_prime = pdf_equiangular(se, t_tr)
+            pdf_tr_prime = pdf_transmittance(med, has_max, max_dist, t_eq)
+            ex_tr, s1 = _explicit(fr, d, pos, nrm, flux, pdf_area, p_tr, trans_tr,
+                                  lambda pe, pp: power4(pe * pdf_tr, pp * pdf_tr, pp * pdf_eq_prime, pe * pdf_eq_prime), ok, mutate=True)
+            ex_ot, s2 = _explicit(fr, d, pos, nrm, flux, pdf_area, p_eq, trans_eq,
+                                  lambda pe, pp: power4(pe * pdf_eq, pp * pdf_eq, pp * pdf_tr_prime, pe * pdf_tr_prime), ok)
+
+            def w1(k, pe, ip, inn):
+                pp = pdf_phase[k]
+                return np.ones(k.shape[0], bool), power4(pp * pdf_tr[k], pe * pdf_tr[k], pp * pdf_eq_prime[k], pe * pdf_eq_prime[k])
+
+            def w2(k, pe, ip, inn):
+                pp = pdf_phase[k]
+                return np.ones(k.shape[0], bool), power4(pp * pdf_eq[k], pe * pdf_eq[k], pp * pdf_tr_prime[k], pe * pdf_tr_prime[k])
+        else:
+            pdf_other_tr = pdf_equiangular(se, t_tr)
+            pdf_third_tr = np.where(some, pdf_third(fam, sc3, t_tr), ZERO).astype(np.float32)
+            ex_tr, s1 = _explicit(fr, d, pos, nrm, flux, pdf_area, p_tr, trans_tr,
+                                  lambda pe, pp: power4(pe * pdf_tr, pp * pdf_tr, pp * pdf_other_tr, pe * pdf_third_tr), ok, mutate=True)
+            has_cl = ok & some & (pdf_cl != ZERO)                                             # res_other_clamped (:1638-1653)
+            p_cl = (o + d * _col(t_cl)).astype(np.float32)
+            trans_cl = R._div_guarded(med.transmittance(t_cl), pdf_cl)
+            pdf_other_cl = pdf_equiangular(se, t_cl)
+            pdf_t_cl = pdf_transmittance(med, has_max, max_dist, t_cl)
+            ex_ot, s2 = _explicit(fr, d, pos, nrm, flux, pdf_area, p_cl, trans_cl,
+                                  lambda pe, pp: power4(pe * pdf_cl, pp * pdf_other_cl, pp * pdf_t_cl, pe * pdf_t_cl), has_cl)
+            pdf_t_eq = pdf_transmittance(med, has_max, max_dist, t_eq)
+
+            def at_hit(k, ip, inn, dist):
+                sh, okh = P.make_sampler("eq_ex", has_max[k], max_dist[k], o[k], d[k], ip, inn)      # defined panic (1) at the hit
+                return okh, pdf_equiangular(sh, dist), pdf_other_clamped(fam, has_max[k], max_dist[k], o[k], d[k], ip, inn, dist)
+
+            def w1(k, pe, ip, inn):
+                okh, p_other, p_third = at_hit(k, ip, inn, t_tr[k])
+                pp = pdf_phase[k]
+                return okh, power4(pp * pdf_tr[k], pe * pdf_tr[k], pp * p_other, pe * p_third)
+
+            def w2(k, pe, ip, inn):
+                okh, p_other, p_third = at_hit(k, ip, inn, t_eq[k])
+                pp = pdf_phase[k]
+                return okh, power4(pp * p_other, pe * p_third, pp * pdf_t_eq[k], pe * pdf_t_eq[k])
+        ph_tr, r1 = _phase(fr, p_tr, nd, trans_tr, w1, ok)
+        ph_eq, r2 = _phase(fr, p_eq, nd, trans_eq, w2, ok)
+        cnt["shadow"] = s1 + s2
+        cnt["ext"] = cnt["ext"] + r1 + r2
+        return (((ph_tr + ph_eq) + ex_tr) + ex_ot).astype(np.float32), cnt
+
+
+# ---- drivers (pn_restatement's, around evaluate above)
+block_pixels, _finish, check_scene = P.block_pixels, P._finish, P.check_scene
+
+
+def check_params(strategy, spp, stream_mode, shard_index, shard_count, use_aa=True, single_pass=False):
+    P.check_params(strategy, 1 if spp else 0, stream_mode, shard_index, shard_count, use_aa, True)
+    dcount = draws_per_sample(strategy, use_aa)
+    if stream_mode == api.STREAM_REFERENCE_ORDER and not single_pass and dcount is not None and 256 * spp * dcount > 0xffffffff:
+        raise Refused(P.RL_ERR_UNSUPPORTED, "jump-ahead reach")
+
+
+def walk_block(fr, b, seed, strategy, spp, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0):
+    """The reference's loop over one block, camera sample after camera sample, draw after draw on orc.Rng."""
+    px, py = block_pixels(fr.sd, b)
+    block_rng = orc.Rng(int(seed), seed_variant)
+    taken = [0]
+    rads, cnts, starts = [], [], []
+    for c in range(px.shape[0]):
+        starts.append(taken[0])
+        pixel_rng = orc.Rng(block_rng.next_u64(), seed_variant) if stream_mode == api.STREAM_PER_SAMPLE else None
+        for s in range(spp):
+            rng = orc.Rng(pixel_rng.next_u64(), seed_variant) if pixel_rng is not None else block_rng
+
+            def draw():
+                taken[0] += 1
+                return np.asarray([rng.next_f32()], np.float32)
+
+            before = taken[0]
+            rad, cnt = evaluate(fr, strategy, use_aa, px[c:c + 1], py[c:c + 1], draw)
+            assert taken[0] - before == int(cnt["draws"][0]), (strategy, taken[0] - before, cnt["draws"])
+            rads.append(rad[0]); cnts.append(cnt)
+    counts = {k: np.concatenate([c[k] for c in cnts]) for k in ("draws", "ext", "shadow", "vertices", "some", "panic")}
+    return px, py, np.asarray(rads, np.float32), counts, np.asarray(starts, np.int64)
+
+
+def chain_offsets(fr, b, seed, strategy, spp, use_aa, seed_variant, s_stream):
+    """Where every camera sample of block b starts in the block's stream for clamped and pn: the walk of the None test alone."""
+    px, py = block_pixels(fr.sd, b)
+    px, py = np.repeat(px, spp), np.repeat(py, spp)
+    aa = 2 if use_aa else 0
+    offs, at = np.zeros(px.shape[0], np.int64), 0
+    sc = fr.sc
+    for i in range(px.shape[0]):
+        offs[i] = at
+        if use_aa:
+            u, v = F32(px[i]) + s_stream[at], F32(py[i]) + s_stream[at + 1]
+        else:
+            u, v = F32(px[i]) + F32(0.5), F32(py[i]) + F32(0.5)
+        o, d = sc.camera_generate(float(u), float(v))
+        o, d = o.reshape(1, 3), d.reshape(1, 3)
+        t, _, _, mesh, _ = sc.trace(o, d)
+        q = s_stream[at + aa:at + aa + 4]
+        pos, nrm, _, _ = fr.emitters.sample(q[0:1], q[1:2], q[2:3], q[3:4])
+        _, ok = P.make_sampler(third(family(strategy)), mesh >= 0, t.astype(np.float32), o, d, pos, nrm)
+        at += aa + 8 + (1 if ok[0] else 0)
+    return offs, at
+
+
+def _new_detail():
+    return {"starts": {}, "some": 0, "none": 0, "panic": 0}
+
+
+def _add_detail(detail, cnt):
+    detail["some"] += int(cnt["some"].sum()); detail["none"] += int((~cnt["some"]).sum()); detail["panic"] += int(cnt["panic"].sum())
+
+
+def render(fr, seeds, strategy, spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
+    """(image HxWx3 f32, the five counters, detail) with every camera sample of a block as one array element.  detail: "starts" {block: [pixels] the draws the
+    block's stream has given when each pixel starts} (reference order), "some" / "none": how many samples had / lacked a third sampler (clamped, pn),
+    "panic": how many a defined panic ended."""
+    check_params(strategy, spp, stream_mode, shard_index, shard_count, use_aa)
+    sd = fr.sd
+    img = np.zeros((sd.height, sd.width, 3), np.float32)
+    st = {k: 0 for k in COUNTERS}
+    detail = _new_detail()
+    kmax = max_draws(strategy, use_aa)
+    for b, seed in enumerate(np.asarray(seeds, np.uint64)):
+        if b % max(shard_count, 1) != shard_index:
+            continue
+        px, py = block_pixels(sd, b)
+        n_pix = px.shape[0]
+        spx, spy = np.repeat(px, spp), np.repeat(py, spp)
+        n = n_pix * spp
+        if stream_mode == api.STREAM_PER_SAMPLE:
+            block_rng = orc.Rng(int(seed), seed_variant)
+            table = np.zeros((n, kmax), np.float32)
+            for c in range(n_pix):
+                pixel_rng = orc.Rng(block_rng.next_u64(), seed_variant)
+                for s in range(spp):
+                    rng = orc.Rng(pixel_rng.next_u64(), seed_variant)
+                    table[c * spp + s] = [rng.next_f32() for _ in range(kmax)]
+        else:
+            s_stream = U.stream(int(seed), seed_variant, n * kmax + kmax)
+            dconst = draws_per_sample(strategy, use_aa)
+            if dconst is not None:
+                offs = np.arange(n, dtype=np.int64) * dconst
+            else:
+                offs, _ = chain_offsets(fr, b, int(seed), strategy, spp, use_aa, seed_variant, s_stream)
+            table = s_stream[offs[:, None] + np.arange(kmax)[None, :]]
+            detail["starts"][b] = offs[::spp].copy()
+        col = [0]
+
+        def draw():
+            col[0] += 1
+            return table[:, col[0] - 1].copy()
+
+        rad, cnt = evaluate(fr, strategy, use_aa, spx, spy, draw)
+        _finish(sd, spp, px, py, rad, cnt, img, st)
+        _add_detail(detail, cnt)
+    return img, st, detail
+
+
+def render_walk(fr, seeds, strategy, spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
+    """render through walk_block: (image, counters, detail)."""
+    check_params(strategy, spp, stream_mode, shard_index, shard_count, use_aa)
+    sd = fr.sd
+    img = np.zeros((sd.height, sd.width, 3), np.float32)
+    st = {k: 0 for k in COUNTERS}
+    detail = _new_detail()
+    for b, seed in enumerate(np.asarray(seeds, np.uint64)):
+        if b % max(shard_count, 1) != shard_index:
+            continue
+        px, py, rad, cnt, starts = walk_block(fr, b, int(seed), strategy, spp, use_aa, stream_mode, seed_variant)
+        _finish(sd, spp, px, py, rad, cnt, img, st)
+        if stream_mode == api.STREAM_REFERENCE_ORDER:
+            detail["starts"][b] = starts
+        _add_detail(detail, cnt)
+    return img, st, detail
+
+
+def compute(sd, seed=0, strategy="tr_ex", spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0):
+    """IntegratorPointNormal::compute with use_mis, seed for seed: the block seeds straight from the main sampler seeded as `-r independent:SEED`."""
+    fr = Frame(sd)
+    seeds = orc.block_seeds(seed, sd.width, sd.height, seed_variant)
+    img, st, detail = render(fr, seeds, strategy, spp, use_aa, stream_mode, seed_variant)
+    return {"seeds": seeds, "image": img, "stats": st, "detail": detail, "frame": fr}
+
+
+# ---- the scenes and fixtures the CPU and the GPU tests share, each computed once and left unchanged
+scene = P.scene
+_CACHE = {}
+
+
+def frame(name, w=24, h=18):
+    if (name, w, h) not in _CACHE:
+        _CACHE[(name, w, h)] = Frame(scene(name, w, h))
+    return _CACHE[(name, w, h)]
+
+
+def fixture(name, strategy, spp=3, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, w=24, h=18, seed=7, shard_index=0, shard_count=1):
+    """(frame, seeds, image, counters, detail) of one render of scene(name), computed once.  The two names of a family share one render."""
+    key = ("render", name, family(strategy), spp, use_aa, stream_mode, w, h, seed, shard_index, shard_count)
+    if key not in _CACHE:
+        fr = frame(name, w, h)
+        seeds = orc.block_seeds(seed, w, h)
+        _CACHE[key] = (fr, seeds) + render(fr, seeds, strategy, spp, use_aa, stream_mode, 0, shard_index, shard_count)
+    return _CACHE[key]
