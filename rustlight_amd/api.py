@@ -788,23 +788,23 @@ class Context(_ImageCalls):
         """IntegratorPointNormal behind its block seeds (point_normal.rs:2584-2633) through rl_render_point_normal: (image HxWx3 f32, stats dict).  stats:
         camera_samples, rng_draws, extension_rays = camera rays + phase rays, shadow_rays = visibility rays, vertices = samples that had a distance sampler;
         ms_prepass = the chain pass of a data-dependent strategy in reference order, ms_other = k_pn_pixel."""
-        p = PointNormalParams()
-        lib().rl_point_normal_params_default(C.byref(p))
-        p.spp, p.strategy, p.use_aa, p.stream_mode, p.seed_variant = spp, pn_strategy(strategy), int(bool(use_aa)), stream_mode, seed_variant
-        p.shard_index, p.shard_count = shard_index, shard_count
-        img, st = self._image_call(seeds, lambda sp, n, out, st: lib().rl_render_point_normal(self.h, C.byref(p), sp, n, out, st))
-        return img, st.as_dict()
+        return self._render_pn(PointNormalParams(), lib().rl_point_normal_params_default, lib().rl_render_point_normal, seeds, strategy, spp, use_aa, stream_mode,
+                               seed_variant, shard_index, shard_count)
 
     def render_point_normal_mis(self, seeds, strategy="tr_ex", spp=1, use_aa=True, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
         """IntegratorPointNormal with use_mis behind its block seeds (point_normal.rs:2605-2612) through rl_render_point_normal_mis: (image HxWx3 f32, stats
         dict).  Only the distance family of `strategy` matters.  stats: camera_samples, rng_draws, extension_rays = camera rays + phase rays, shadow_rays =
         visibility rays, vertices = samples no defined panic ended (tr, eq) or whose third sampler was Some (clamped, pn); ms_prepass = the chain pass of clamped
-        and pn in reference order, ms_other = k_pnmis_pixel."""
-        p = PointNormalMisParams()
-        lib().rl_point_normal_mis_params_default(C.byref(p))
+        and pn in reference order, ms_other = k_pn_pixel."""
+        return self._render_pn(PointNormalMisParams(), lib().rl_point_normal_mis_params_default, lib().rl_render_point_normal_mis, seeds, strategy, spp, use_aa,
+                               stream_mode, seed_variant, shard_index, shard_count)
+
+    def _render_pn(self, p, defaults, render, seeds, strategy, spp, use_aa, stream_mode, seed_variant, shard_index, shard_count):
+        """render_point_normal and render_point_normal_mis: the params struct `p` filled by `defaults` and the arguments, one call of `render`."""
+        defaults(C.byref(p))
         p.spp, p.strategy, p.use_aa, p.stream_mode, p.seed_variant = spp, pn_strategy(strategy), int(bool(use_aa)), stream_mode, seed_variant
         p.shard_index, p.shard_count = shard_index, shard_count
-        img, st = self._image_call(seeds, lambda sp, n, out, st: lib().rl_render_point_normal_mis(self.h, C.byref(p), sp, n, out, st))
+        img, st = self._image_call(seeds, lambda sp, n, out, st: render(self.h, C.byref(p), sp, n, out, st))
         return img, st.as_dict()
 
     def trace(self, origins, directions):

@@ -521,6 +521,19 @@ struct IntegratorSinglePlaneUncorrelated {
     }
 };
 
+// compute of the two point-normal structs below: the block seeds straight from the main sampler, `self`'s fields into the params `defaults` fills, `render`
+template <class Self, class Params>
+BufferCollection compute_point_normal(Self& self, IndependentSampler& sampler, Scene& scene, void (*defaults)(Params*),
+                                      int (*render)(rl_context*, const Params*, const uint64_t*, size_t, float*, rl_render_stats*), const char* what) {
+    RenderContext ctx(scene, self.device, self.options);
+    const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+    Params p;
+    defaults(&p);
+    p.spp = (uint32_t)scene.nb_samples; p.strategy = self.strategy; p.use_aa = self.use_aa ? 1 : 0; p.stream_mode = self.stream_mode; p.seed_variant = sampler.variant;
+    check(render(ctx, &p, seeds.data(), seeds.size(), ctx.img.primal.data(), &self.last_stats), what);
+    return std::move(ctx.img);
+}
+
 // struct IntegratorPointNormal { strategy, use_mis, warps, warps_strategy, splitting, use_aa } (src/integrators/explicit/point_normal.rs:1172-1179) +
 // Integrator::compute -> compute_mc (:1181-1199), seed for seed the reference: the block seeds straight from the main sampler, then rl_render_point_normal.
 // The seven plain strategies; the CLI refuses the flavoured ones, MIS, splitting and the warps before it gets here.
@@ -532,13 +545,7 @@ struct IntegratorPointNormal {
     Options options;
     rl_render_stats last_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
-        RenderContext ctx(scene, device, options);
-        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
-        rl_point_normal_params p;
-        rl_point_normal_params_default(&p);
-        p.spp = (uint32_t)scene.nb_samples; p.strategy = strategy; p.use_aa = use_aa ? 1 : 0; p.stream_mode = stream_mode; p.seed_variant = sampler.variant;
-        check(rl_render_point_normal(ctx, &p, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "point-normal");
-        return std::move(ctx.img);
+        return compute_point_normal(*this, sampler, scene, rl_point_normal_params_default, rl_render_point_normal, "point-normal");
     }
 };
 
@@ -552,13 +559,7 @@ struct IntegratorPointNormalMis {
     Options options;
     rl_render_stats last_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
-        RenderContext ctx(scene, device, options);
-        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
-        rl_point_normal_mis_params p;
-        rl_point_normal_mis_params_default(&p);
-        p.spp = (uint32_t)scene.nb_samples; p.strategy = strategy; p.use_aa = use_aa ? 1 : 0; p.stream_mode = stream_mode; p.seed_variant = sampler.variant;
-        check(rl_render_point_normal_mis(ctx, &p, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "point-normal-mis");
-        return std::move(ctx.img);
+        return compute_point_normal(*this, sampler, scene, rl_point_normal_mis_params_default, rl_render_point_normal_mis, "point-normal-mis");
     }
 };
 

@@ -187,9 +187,10 @@ struct UPlaneConst {
     float inv_nb;                       // 1.0 / nb_primitive as f32
 };
 
-// IntegratorPointNormal (pn.hip.h).  How a lane of k_pn_pixel comes by its sampler: forked per sample from the pixel's seed (per-sample streams); the block's
-// stream entered by jump-ahead (reference order, a constant number of draws per sample); the state k_pn_chain recorded for the pixel (reference order, a
-// data-dependent number); or one lane per block walking the block's stream (reference order in a single pass)
+// IntegratorPointNormal (pn.hip.h, and with use_mis pnmis.hip.h: k_pn_pixel and k_pn_chain are templates over the sample body, PnPlain<STRATEGY> or
+// PnMis<FAMILY>).  How a lane of k_pn_pixel comes by its sampler: forked per sample from the pixel's seed (per-sample streams); the block's stream entered by
+// jump-ahead (reference order, a constant number of draws per sample); the state k_pn_chain recorded for the pixel (reference order, a data-dependent
+// number); or one lane per block walking the block's stream (reference order in a single pass)
 enum { PN_MODE_PER_SAMPLE = 0, PN_MODE_ADVANCE = 1, PN_MODE_GIVEN = 2, PN_MODE_BLOCK = 3 };
 struct PnConst {
     int use_aa;                         // 0: the pixel centre instead of the two jitter draws (-z)
@@ -270,12 +271,12 @@ void launch_plane_stream(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipS
 // IntegratorSinglePlaneUncorrelated (uplane.hip.h): k_uplane over the owned blocks, mode = PLANE_MODE_*
 void launch_uplane_lds(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const UPlaneConst& uc);
 void launch_uplane_stream(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const UPlaneConst& uc);
-// IntegratorPointNormal (pn.hip.h): chain = false k_pn_pixel over the pixel items (or, PN_MODE_BLOCK, the owned blocks), true k_pn_chain over the owned blocks;
-// strategy = rl_pn_strategy
+// IntegratorPointNormal (pn.hip.h): chain = false k_pn_pixel<.., PnPlain<strategy>> over the pixel items (or, PN_MODE_BLOCK, the owned blocks), true
+// k_pn_chain<.., PnPlain<strategy>> over the owned blocks; strategy = rl_pn_strategy
 void launch_pn_lds(bool chain, int strategy, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
 void launch_pn_stream(bool chain, int strategy, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
-// IntegratorPointNormal with use_mis (pnmis.hip.h): chain = false k_pnmis_pixel, true k_pnmis_chain (clamped and pn); family = PNMIS_* (0 tr, 1 eq, 2 clamped,
-// 3 pn); the constants are point-normal's PnConst and PN_MODE_*
+// IntegratorPointNormal with use_mis (pnmis.hip.h): chain = false k_pn_pixel<.., PnMis<family>>, true k_pn_chain<.., PnMis<family>> (clamped and pn);
+// family = PNMIS_* (0 tr, 1 eq, 2 clamped, 3 pn); the constants are point-normal's PnConst and PN_MODE_*
 void launch_pnmis_lds(bool chain, int family, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
 void launch_pnmis_stream(bool chain, int family, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)

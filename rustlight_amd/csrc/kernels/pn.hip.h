@@ -25,12 +25,13 @@
 //
 // Numerics: atan(x) = atan2f_det(x, 1), tan(x) = the IEEE quotient sinf_det(x) / cosf_det(x) (it departs from libm's tan by this construction), powi(2) = x * x.
 //
-// Drivers.  k_pn_pixel: one lane per pixel, its samples in series (the pixel sum keeps the reference's order), pixels in compute_mc's order (iy outer, ix
-// inner, mod.rs:420-435); the lane's sampler is (a) forked per sample from the pixel's seed (k_seed_pixels), (b) the block's stream entered c * spp * D draws
-// down by rng_advance when the count D is constant, (c) the state k_pn_chain recorded for the pixel when it is not; or, as the cross-check of (b) and (c), one
-// lane per block walks the block's stream in the reference's order (the form k_pixel_mc has).  k_pn_chain: one lane per block walks (pixel, sample), takes the
-// jitter, the camera ray's closest hit and the four emitter draws, decides Some | None with pn_make_sampler — the statements pn_sample decides it with — and
-// skips the 1 or 3 draws; it records the sampler at the start of every pixel (32 bytes per pixel).
+// Drivers, templates over a sample body: PnPlain<STRATEGY> here (k_pn_pixel<LDS_SCENE, PnPlain<STRATEGY>>), PnMis<FAMILY> in pnmis.hip.h.  k_pn_pixel: one
+// lane per pixel, its samples in series (the pixel sum keeps the reference's order), pixels in compute_mc's order (iy outer, ix inner, mod.rs:420-435); the
+// lane's sampler is (a) forked per sample from the pixel's seed (k_seed_pixels), (b) the block's stream entered c * spp * D draws down by rng_advance when the
+// count D is constant, (c) the state k_pn_chain recorded for the pixel when it is not; or, as the cross-check of (b) and (c), one lane per block walks the
+// block's stream in the reference's order (the form k_pixel_mc has).  k_pn_chain: one lane per block walks (pixel, sample), takes the jitter, the camera
+// ray's closest hit and the four emitter draws, decides Some | None with pn_make_sampler — the statements the body decides it with — and skips the draws the
+// body takes behind them (plain: 1 or 3 | 0); it records the sampler at the start of every pixel (32 bytes per pixel).
 #pragma once
 #include "light.hip.h"      // light_mesh_position
 #include "rngjump.h"        // rng_advance
@@ -245,17 +246,46 @@ RL_DEV Rng pn_load_state(const unsigned long long* states, unsigned slot) {
     return r;
 }
 
-// k_pn_pixel<LDS_SCENE, STRATEGY> — work item = pixel (pc.mode PN_MODE_PER_SAMPLE | _ADVANCE | _GIVEN), or block (PN_MODE_BLOCK: the single-pass walk).
+// PnPlain<STRATEGY> — what the drivers below need to know of a sample body, and nothing else (pnmis.hip.h's PnMis<FAMILY> is the other one): the waves per
+// SIMD k_pn_pixel is compiled for, the counters a lane carries, the body itself, the statistics rows, and for k_pn_chain the draws a sample takes behind
+// its four emitter draws.
+template <int STRATEGY>
+struct PnPlain {
+    static constexpr int kWaves = kPnWaves;
+    struct Counts { unsigned rays = 0, vertices = 0; };
+    template <class Stack, class Park>
+    static RL_DEV Col sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool aa, unsigned px, unsigned py, Rng& rng, Park&& park, Counts& n) {
+        return pn_sample<STRATEGY>(sc, recs, stack, aa, px, py, rng, park, n.rays, n.vertices);
+    }
+    // three rows; the host derives the five counters from them (pn_render.hip.h): a sample's draws follow from its strategy and from whether it had a
+    // sampler, n.rays are the phase rays of a phase strategy and the visibility rays of an explicit one, a transmittance sample always has its sampler
+    static RL_DEV void stats(const RenderConst& rc, unsigned samples, const Counts& n) {
+        const int which[3] = {STAT_SAMPLES, STAT_VERTICES, pn_is_phase(STRATEGY) ? STAT_EXT_RAYS : STAT_SHADOW_RAYS};
+        const unsigned vals[3] = {samples, n.vertices, n.rays};
+        block_stats<3>(rc.partials, which, vals);
+    }
+    // Some | None by pn_make_sampler, the statements pn_sample decides it with: 1 or 3 draws behind a sampler, none without
+    static RL_DEV unsigned chain_skip(const DeviceScene& sc, bool has_max, float max_dist, V3 o, V3 d, float r_sel, float r_pos, V2 uv) {
+        const PnEmitter em = pn_sample_emitter(sc, r_sel, r_pos, uv);
+        PnDist ds;
+        if (!pn_make_sampler<STRATEGY>(has_max, max_dist, o, d, em.p, em.n, &ds)) return 0u;
+        return pn_is_phase(STRATEGY) ? 3u : 1u;
+    }
+};
+
+// k_pn_pixel<LDS_SCENE, Body> — work item = pixel (pc.mode PN_MODE_PER_SAMPLE | _ADVANCE | _GIVEN), or block (PN_MODE_BLOCK: the single-pass walk).
 // What a lane keeps between two samples lives in memory, so that the second traversal of a sample runs with its value and little else in registers: the
 // sampler in pc.pixel_states[item] (per-sample streams: the pixel's forked sampler; else the block's stream where the pixel stands in it), the pixel's sum in
-// the image itself, added to in sample order and scaled behind the last sample.
-template <bool LDS_SCENE, int STRATEGY>
-__global__ void __launch_bounds__(256, kPnWaves) k_pn_pixel(RenderConst rc, DeviceScene sc, StackConf stc, PnConst pc) {
+// the image itself, added to in sample order and scaled behind the last sample.  The kernel itself is the template over the body: a __global__ wrapper per
+// body around a shared device function costs a VGPR or two, and tr_phase its fifth wave.
+template <bool LDS_SCENE, class Body>
+__global__ void __launch_bounds__(256, Body::kWaves) k_pn_pixel(RenderConst rc, DeviceScene sc, StackConf stc, PnConst pc) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneRecs recs;
     const unsigned item = blockIdx.x * blockDim.x + threadIdx.x;
     const TravStackT<LDS_SCENE> stack = open_scene<LDS_SCENE>(sc, stc, smem, item, &recs);
-    unsigned n_pix = 0, n_rays = 0, n_vertices = 0;
+    unsigned n_pix = 0;
+    typename Body::Counts counts;
     if (item < rc.n_items) {
         unsigned bx = 0, by = 0, bw = 1;
         n_pix = 1;
@@ -290,7 +320,7 @@ __global__ void __launch_bounds__(256, kPnWaves) k_pn_pixel(RenderConst rc, Devi
                     rng = rng_seed(seed, rc.seed_variant);
                 }
                 const auto park = [&](const Rng& r) { if (pc.mode != PN_MODE_PER_SAMPLE) pn_store_state(pc.pixel_states, item, r); };
-                const Col l = pn_sample<STRATEGY>(sc, recs, stack, pc.use_aa != 0, px, py, rng, park, n_rays, n_vertices);
+                const Col l = Body::sample(sc, recs, stack, pc.use_aa != 0, px, py, rng, park, counts);
                 const float r = out[0] + l.r, g = out[1] + l.g, b = out[2] + l.b;      // im_block.accumulate, in sample order
                 out[0] = r; out[1] = g; out[2] = b;
             }
@@ -298,18 +328,12 @@ __global__ void __launch_bounds__(256, kPnWaves) k_pn_pixel(RenderConst rc, Devi
             out[0] = r; out[1] = g; out[2] = b;
         }
     }
-    {
-        // three rows; the host derives the five counters from them (pn_render.hip.h): a sample's draws follow from its strategy and from whether it had a
-        // sampler, n_rays are the phase rays of a phase strategy and the visibility rays of an explicit one, a transmittance sample always has its sampler
-        const int which[3] = {STAT_SAMPLES, STAT_VERTICES, pn_is_phase(STRATEGY) ? STAT_EXT_RAYS : STAT_SHADOW_RAYS};
-        const unsigned vals[3] = {n_pix * rc.spp, n_vertices, n_rays};
-        block_stats<3>(rc.partials, which, vals);
-    }
+    Body::stats(rc, n_pix * rc.spp, counts);
 }
 
-// k_pn_chain<LDS_SCENE, STRATEGY> — the strategies whose count depends on the data: one lane per owned block, the chains dealt to every 2^item_shift-th lane
-// as k_mc_chain deals them, records where every pixel starts in its block's stream.  Its rays are not counted.
-template <bool LDS_SCENE, int STRATEGY>
+// k_pn_chain<LDS_SCENE, Body> — the bodies whose count depends on the data: one lane per owned block, the chains dealt to every 2^item_shift-th lane as
+// k_mc_chain deals them, records where every pixel starts in its block's stream.  Its rays are not counted.
+template <bool LDS_SCENE, class Body>
 __global__ void __launch_bounds__(256, kPnWaves) k_pn_chain(RenderConst rc, DeviceScene sc, StackConf stc, PnConst pc) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneRecs recs;
@@ -323,7 +347,6 @@ __global__ void __launch_bounds__(256, kPnWaves) k_pn_chain(RenderConst rc, Devi
     Rng rng = rng_seed(rc.block_seeds[b], rc.seed_variant);
     const unsigned base = rc.block_item_base[item];
     const V3 o = mk3(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]);
-    const unsigned after_some = pn_is_phase(STRATEGY) ? 3u : 1u;
     for (unsigned c = 0; c < bw * bh; c++) {
         const unsigned px = bx + c % bw, py = by + c / bw;
         pn_store_state(pc.pixel_states, base + c, rng);
@@ -335,10 +358,8 @@ __global__ void __launch_bounds__(256, kPnWaves) k_pn_chain(RenderConst rc, Devi
             const bool has_max = trace_closest(sc, recs, stack, o, d, hit);
             const float r_sel = rng_next_f32(rng), r_pos = rng_next_f32(rng);
             const V2 uv = smp_next2d(rng);
-            const PnEmitter em = pn_sample_emitter(sc, r_sel, r_pos, uv);
-            PnDist ds;
-            if (pn_make_sampler<STRATEGY>(has_max, hit.t, o, d, em.p, em.n, &ds))
-                for (unsigned k = 0; k < after_some; k++) rng_next_u64(rng);
+            const unsigned skip = Body::chain_skip(sc, has_max, hit.t, o, d, r_sel, r_pos, uv);
+            for (unsigned k = 0; k < skip; k++) rng_next_u64(rng);
         }
     }
 }
@@ -359,12 +380,12 @@ static void with_pn_strategy(int strategy, F&& f) {
 template <bool LDS_SCENE>
 static void launch_pn_impl(bool chain, int strategy, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc) {
     if (!chain) {
-        with_pn_strategy(strategy, [&](auto s) { hipLaunchKernelGGL((k_pn_pixel<LDS_SCENE, decltype(s)::value>), grid, block, lds_bytes, st, rc, ds, stc, pc); });
+        with_pn_strategy(strategy, [&](auto s) { hipLaunchKernelGGL((k_pn_pixel<LDS_SCENE, PnPlain<decltype(s)::value>>), grid, block, lds_bytes, st, rc, ds, stc, pc); });
         return;
     }
-    if (strategy == RL_PN_EQ_CLAMPED_EX) hipLaunchKernelGGL((k_pn_chain<LDS_SCENE, RL_PN_EQ_CLAMPED_EX>), grid, block, lds_bytes, st, rc, ds, stc, pc);
-    else if (strategy == RL_PN_EQ_CLAMPED_PHASE) hipLaunchKernelGGL((k_pn_chain<LDS_SCENE, RL_PN_EQ_CLAMPED_PHASE>), grid, block, lds_bytes, st, rc, ds, stc, pc);
-    else if (strategy == RL_PN_PN_EX) hipLaunchKernelGGL((k_pn_chain<LDS_SCENE, RL_PN_PN_EX>), grid, block, lds_bytes, st, rc, ds, stc, pc);
+    if (strategy == RL_PN_EQ_CLAMPED_EX) hipLaunchKernelGGL((k_pn_chain<LDS_SCENE, PnPlain<RL_PN_EQ_CLAMPED_EX>>), grid, block, lds_bytes, st, rc, ds, stc, pc);
+    else if (strategy == RL_PN_EQ_CLAMPED_PHASE) hipLaunchKernelGGL((k_pn_chain<LDS_SCENE, PnPlain<RL_PN_EQ_CLAMPED_PHASE>>), grid, block, lds_bytes, st, rc, ds, stc, pc);
+    else if (strategy == RL_PN_PN_EX) hipLaunchKernelGGL((k_pn_chain<LDS_SCENE, PnPlain<RL_PN_PN_EX>>), grid, block, lds_bytes, st, rc, ds, stc, pc);
 }
 
 }  // namespace rl

@@ -31,19 +31,18 @@
 // The power heuristic is plain IEEE arithmetic, pdf_current^2 / (((0 + v0^2) + v1^2) + v2^2) + v3^2) in the order of the vec!: a 0 / 0 or inf / inf weight is
 // NaN and flows into the colour through f32 * Color, which has no guard, as the reference's does.
 //
-// Drivers, as pn.hip.h's: k_pnmis_pixel, one lane per pixel with its samples in series, in the four sampler modes of k_pn_pixel (per-sample fork; jump-ahead
-// for tr and eq; the states k_pnmis_chain recorded for clamped and pn; the single-pass block walk); k_pnmis_chain, one lane per block, takes the jitter, the
-// camera ray's closest hit and the four emitter draws, decides Some | None with pn_make_sampler — the statements pnmis_sample decides with — and skips 4 or 5
-// draws.  The order of a sample's four contributions is chosen for the registers: the two explicit ones first, each a finished value that its visibility ray
-// keeps or drops, then the two phase ones, whose weights need the hit; the sum is taken in the reference's order.
+// Drivers: pn.hip.h's, over the body PnMis<FAMILY> at the end of this header — k_pn_pixel<LDS_SCENE, PnMis<FAMILY>>, one lane per pixel with its samples in
+// series, in its four sampler modes (per-sample fork; jump-ahead for tr and eq; the states the chain pass recorded for clamped and pn; the single-pass block
+// walk); k_pn_chain<LDS_SCENE, PnMis<FAMILY>>, one lane per block, takes the jitter, the camera ray's closest hit and the four emitter draws, decides Some |
+// None with pn_make_sampler — the statements pnmis_sample decides with — and skips 4 or 5 draws.  The order of a sample's four contributions is chosen for
+// the registers: the two explicit ones first, each a finished value that its visibility ray keeps or drops, then the two phase ones, whose weights need the
+// hit; the sum is taken in the reference's order.
 #pragma once
 #include "pn.hip.h"
 
 namespace rl {
 
 enum { PNMIS_TR = 0, PNMIS_EQ = 1, PNMIS_CLAMPED = 2, PNMIS_PN = 3 };
-// waves per SIMD the kernels are compiled for (the resource rows record what each family reached)
-template <int FAMILY> struct PnMisWaves { static constexpr int value = FAMILY == PNMIS_TR ? 4 : 3; };
 
 // EmitterSampler::random_sample_emitter_position (emitter.rs:1752-1762) without a correct_flux: flux = w / pdf_sel, pdf = sampled_pos.pdf * pdf_sel
 struct PnMisEmitter { V3 p, n; Col flux; float pdf; bool surface; };
@@ -316,113 +315,43 @@ RL_DEV Col pnmis_sample(const DeviceScene& sc, const SceneRecs& recs, const Stac
     }
 }
 
-// k_pnmis_pixel<LDS_SCENE, FAMILY> — k_pn_pixel's driver around pnmis_sample: work item = pixel (pc.mode PN_MODE_PER_SAMPLE | _ADVANCE | _GIVEN), or block
-// (PN_MODE_BLOCK: the single-pass walk).  The sampler lives in pc.pixel_states[item] and the pixel's sum in the image between two samples.
-template <bool LDS_SCENE, int FAMILY>
-__global__ void __launch_bounds__(256, PnMisWaves<FAMILY>::value) k_pnmis_pixel(RenderConst rc, DeviceScene sc, StackConf stc, PnConst pc) {
-    extern __shared__ __attribute__((aligned(16))) float4 smem[];
-    SceneRecs recs;
-    const unsigned item = blockIdx.x * blockDim.x + threadIdx.x;
-    const TravStackT<LDS_SCENE> stack = open_scene<LDS_SCENE>(sc, stc, smem, item, &recs);
-    unsigned n_pix = 0, n_phase = 0, n_vis = 0, n_vertices = 0;
-    if (item < rc.n_items) {
-        unsigned bx = 0, by = 0, bw = 1;
-        n_pix = 1;
-        if (pc.mode == PN_MODE_BLOCK) {
-            unsigned bh;
-            const unsigned b = rc.owned_blocks[item];
-            block_geometry(rc, b, &bx, &by, &bw, &bh);
-            n_pix = bw * bh;
-            pn_store_state(pc.pixel_states, item, rng_seed(rc.block_seeds[b], rc.seed_variant));
-        } else {
-            const unsigned pix = rc.item_pixel[item];
-            bx = pix % rc.W; by = pix / rc.W;
-            if (pc.mode == PN_MODE_PER_SAMPLE) pn_store_state(pc.pixel_states, item, rng_seed(rc.item_seed[item], rc.seed_variant));
-            else if (pc.mode == PN_MODE_ADVANCE) {
-                // the pixel's place c in its block's loop (iy outer, ix inner), c * spp * D draws down the block's stream (the host holds 256 * spp * D to 32 bits)
-                const unsigned ox = bx & ~15u, oy = by & ~15u;
-                const unsigned c = (by - oy) * min(16u, rc.W - ox) + (bx - ox);
-                Rng rng = rng_seed(rc.block_seeds[(ox >> 4) * rc.nby + (oy >> 4)], rc.seed_variant);
-                rng_advance<false>(rng, c * rc.spp * pc.draws);
-                pn_store_state(pc.pixel_states, item, rng);
-            }
-        }
-        for (unsigned c = 0; c < n_pix; c++) {
-            const unsigned px = bx + c % bw, py = by + c / bw;
-            volatile float* out = rc.out + 3 * ((size_t)py * rc.W + px);
-            out[0] = 0.0f; out[1] = 0.0f; out[2] = 0.0f;
-            for (unsigned s = 0; s < rc.spp; s++) {
-                Rng rng = pn_load_state(pc.pixel_states, item);
-                if (pc.mode == PN_MODE_PER_SAMPLE) {
-                    const unsigned long long seed = rng_next_u64(rng);
-                    pn_store_state(pc.pixel_states, item, rng);
-                    rng = rng_seed(seed, rc.seed_variant);
-                }
-                const auto park = [&](const Rng& r) { if (pc.mode != PN_MODE_PER_SAMPLE) pn_store_state(pc.pixel_states, item, r); };
-                const Col l = pnmis_sample<FAMILY>(sc, recs, stack, pc.use_aa != 0, px, py, rng, park, n_phase, n_vis, n_vertices);
-                const float r = out[0] + l.r, g = out[1] + l.g, b = out[2] + l.b;      // im_block.accumulate, in sample order
-                out[0] = r; out[1] = g; out[2] = b;
-            }
-            const float r = out[0] * rc.inv_spp, g = out[1] * rc.inv_spp, b = out[2] * rc.inv_spp;      // im_block.scale(1 / spp)
-            out[0] = r; out[1] = g; out[2] = b;
-        }
+// PnMis<FAMILY> — pnmis_sample as a body of pn.hip.h's drivers (PnPlain<STRATEGY> is the other one).
+template <int FAMILY>
+struct PnMis {
+    // waves per SIMD k_pn_pixel is compiled for (the resource rows record what each family reached)
+    static constexpr int kWaves = FAMILY == PNMIS_TR ? 4 : 3;
+    struct Counts { unsigned phase = 0, vis = 0, vertices = 0; };
+    template <class Stack, class Park>
+    static RL_DEV Col sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool aa, unsigned px, unsigned py, Rng& rng, Park&& park, Counts& n) {
+        return pnmis_sample<FAMILY>(sc, recs, stack, aa, px, py, rng, park, n.phase, n.vis, n.vertices);
     }
-    {
-        // four rows; the host derives the five counters from them (pnmis_render.hip.h): a sample's draws follow from its family and from whether its third
-        // sampler was Some (STAT_VERTICES for clamped and pn; for tr and eq that row counts the samples no defined panic ended)
+    // four rows; the host derives the five counters from them (pnmis_render.hip.h): a sample's draws follow from its family and from whether its third
+    // sampler was Some (STAT_VERTICES for clamped and pn; for tr and eq that row counts the samples no defined panic ended)
+    static RL_DEV void stats(const RenderConst& rc, unsigned samples, const Counts& n) {
         const int which[4] = {STAT_SAMPLES, STAT_VERTICES, STAT_EXT_RAYS, STAT_SHADOW_RAYS};
-        const unsigned vals[4] = {n_pix * rc.spp, n_vertices, n_phase, n_vis};
+        const unsigned vals[4] = {samples, n.vertices, n.phase, n.vis};
         block_stats<4>(rc.partials, which, vals);
     }
-}
-
-// k_pnmis_chain<LDS_SCENE, FAMILY> — clamped and pn: one lane per owned block, dealt as k_pn_chain deals them, records where every pixel starts in its block's
-// stream.  Its rays are not counted.
-template <bool LDS_SCENE, int FAMILY>
-__global__ void __launch_bounds__(256, kPnWaves) k_pnmis_chain(RenderConst rc, DeviceScene sc, StackConf stc, PnConst pc) {
-    extern __shared__ __attribute__((aligned(16))) float4 smem[];
-    SceneRecs recs;
-    const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const TravStackT<LDS_SCENE> stack = open_scene<LDS_SCENE>(sc, stc, smem, tid, &recs);
-    const unsigned item = (tid & ((1u << rc.item_shift) - 1u)) == 0u ? (tid >> rc.item_shift) : 0xffffffffu;
-    if (item >= rc.n_items) return;
-    unsigned bx, by, bw, bh;
-    const unsigned b = rc.owned_blocks[item];
-    block_geometry(rc, b, &bx, &by, &bw, &bh);
-    Rng rng = rng_seed(rc.block_seeds[b], rc.seed_variant);
-    const unsigned base = rc.block_item_base[item];
-    const V3 o = mk3(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]);
-    for (unsigned c = 0; c < bw * bh; c++) {
-        const unsigned px = bx + c % bw, py = by + c / bw;
-        pn_store_state(pc.pixel_states, base + c, rng);
-        for (unsigned s = 0; s < rc.spp; s++) {
-            float u = (float)px + 0.5f, v = (float)py + 0.5f;
-            if (pc.use_aa) { u = (float)px + rng_next_f32(rng); v = (float)py + rng_next_f32(rng); }
-            const V3 d = camera_direction(sc, u, v);
-            Hit hit;
-            const bool has_max = trace_closest(sc, recs, stack, o, d, hit);
-            const float r_sel = rng_next_f32(rng), r_pos = rng_next_f32(rng);
-            const V2 uv = smp_next2d(rng);
-            const PnMisEmitter em = pnmis_sample_emitter(sc, r_sel, r_pos, uv);
-            PnDist ds;
-            const unsigned skip = pn_make_sampler<PnMisThird<FAMILY>::strategy>(has_max, hit.t, o, d, em.p, em.n, &ds) ? 5u : 4u;
-            for (unsigned k = 0; k < skip; k++) rng_next_u64(rng);
-        }
+    // clamped and pn: Some | None of the third sampler by pn_make_sampler, the statements pnmis_sample decides it with; 4 draws, and one more behind a sampler
+    static RL_DEV unsigned chain_skip(const DeviceScene& sc, bool has_max, float max_dist, V3 o, V3 d, float r_sel, float r_pos, V2 uv) {
+        const PnMisEmitter em = pnmis_sample_emitter(sc, r_sel, r_pos, uv);
+        PnDist ds;
+        return pn_make_sampler<PnMisThird<FAMILY>::strategy>(has_max, max_dist, o, d, em.p, em.n, &ds) ? 5u : 4u;
     }
-}
+};
 
-// chain = true: k_pnmis_chain (clamped and pn only; any other family launches nothing), false: k_pnmis_pixel
+// chain = true: k_pn_chain (clamped and pn only; any other family launches nothing), false: k_pn_pixel
 template <bool LDS_SCENE>
 static void launch_pnmis_impl(bool chain, int family, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc) {
     if (chain) {
-        if (family == PNMIS_CLAMPED) hipLaunchKernelGGL((k_pnmis_chain<LDS_SCENE, PNMIS_CLAMPED>), grid, block, lds_bytes, st, rc, ds, stc, pc);
-        else if (family == PNMIS_PN) hipLaunchKernelGGL((k_pnmis_chain<LDS_SCENE, PNMIS_PN>), grid, block, lds_bytes, st, rc, ds, stc, pc);
+        if (family == PNMIS_CLAMPED) hipLaunchKernelGGL((k_pn_chain<LDS_SCENE, PnMis<PNMIS_CLAMPED>>), grid, block, lds_bytes, st, rc, ds, stc, pc);
+        else if (family == PNMIS_PN) hipLaunchKernelGGL((k_pn_chain<LDS_SCENE, PnMis<PNMIS_PN>>), grid, block, lds_bytes, st, rc, ds, stc, pc);
         return;
     }
-    if (family == PNMIS_TR) hipLaunchKernelGGL((k_pnmis_pixel<LDS_SCENE, PNMIS_TR>), grid, block, lds_bytes, st, rc, ds, stc, pc);
-    else if (family == PNMIS_EQ) hipLaunchKernelGGL((k_pnmis_pixel<LDS_SCENE, PNMIS_EQ>), grid, block, lds_bytes, st, rc, ds, stc, pc);
-    else if (family == PNMIS_CLAMPED) hipLaunchKernelGGL((k_pnmis_pixel<LDS_SCENE, PNMIS_CLAMPED>), grid, block, lds_bytes, st, rc, ds, stc, pc);
-    else hipLaunchKernelGGL((k_pnmis_pixel<LDS_SCENE, PNMIS_PN>), grid, block, lds_bytes, st, rc, ds, stc, pc);
+    if (family == PNMIS_TR) hipLaunchKernelGGL((k_pn_pixel<LDS_SCENE, PnMis<PNMIS_TR>>), grid, block, lds_bytes, st, rc, ds, stc, pc);
+    else if (family == PNMIS_EQ) hipLaunchKernelGGL((k_pn_pixel<LDS_SCENE, PnMis<PNMIS_EQ>>), grid, block, lds_bytes, st, rc, ds, stc, pc);
+    else if (family == PNMIS_CLAMPED) hipLaunchKernelGGL((k_pn_pixel<LDS_SCENE, PnMis<PNMIS_CLAMPED>>), grid, block, lds_bytes, st, rc, ds, stc, pc);
+    else hipLaunchKernelGGL((k_pn_pixel<LDS_SCENE, PnMis<PNMIS_PN>>), grid, block, lds_bytes, st, rc, ds, stc, pc);
 }
 
 }  // namespace rl

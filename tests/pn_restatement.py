@@ -487,125 +487,161 @@ def _finish(sd, spp, px, py, rad, cnt, img, st):
     st["vertices"] += int(cnt["vertices"].sum())
 
 
-def walk_block(fr, b, seed, strategy, spp, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0):
-    """The reference's loop over one block, camera sample after camera sample, draw after draw on orc.Rng: (px, py, radiance [pixels * spp, 3], counts,
-    start offsets [pixels] — the draws the block's stream has given when the pixel starts, reference order only)."""
-    px, py = block_pixels(fr.sd, b)
-    block_rng = orc.Rng(int(seed), seed_variant)
-    taken = [0]
-    rads, cnts, starts = [], [], []
-    for c in range(px.shape[0]):
-        starts.append(taken[0])
-        pixel_rng = orc.Rng(block_rng.next_u64(), seed_variant) if stream_mode == api.STREAM_PER_SAMPLE else None
-        for s in range(spp):
-            rng = orc.Rng(pixel_rng.next_u64(), seed_variant) if pixel_rng is not None else block_rng
+class Drivers:
+    """The block drivers around one kind of estimator — the plain strategies here (PLAIN below), the MIS families in tests/pnmis_restatement.py.  A kind is its
+    evaluate, draws_per_sample, max_draws and check_params; chain(strategy) -> (the strategy whose make_sampler is the None test, the draws a sample takes behind
+    the jitter without a sampler, with one), which is all the chain walk knows of a sample; extra_counts, the per-sample flags it reports beside "some", each
+    also summed into detail; frame_class; and fixture_key(strategy), under which a fixture's render is cached."""
+
+    def __init__(self, evaluate, draws_per_sample, max_draws, check_params, chain, frame_class, extra_counts=(), fixture_key=lambda strategy: strategy):
+        self.evaluate, self.draws_per_sample, self.max_draws, self.check_params, self.chain = evaluate, draws_per_sample, max_draws, check_params, chain
+        self.frame_class, self.extra_counts, self.fixture_key = frame_class, tuple(extra_counts), fixture_key
+        self.cache = {}
+
+    def _new_detail(self):
+        return {"starts": {}, "some": 0, "none": 0, **{k: 0 for k in self.extra_counts}}
+
+    def _add_detail(self, detail, cnt):
+        detail["some"] += int(cnt["some"].sum()); detail["none"] += int((~cnt["some"]).sum())
+        for k in self.extra_counts:
+            detail[k] += int(cnt[k].sum())
+
+    def walk_block(self, fr, b, seed, strategy, spp, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0):
+        """The reference's loop over one block, camera sample after camera sample, draw after draw on orc.Rng: (px, py, radiance [pixels * spp, 3], counts,
+        start offsets [pixels] — the draws the block's stream has given when the pixel starts, reference order only)."""
+        px, py = block_pixels(fr.sd, b)
+        block_rng = orc.Rng(int(seed), seed_variant)
+        taken = [0]
+        rads, cnts, starts = [], [], []
+        for c in range(px.shape[0]):
+            starts.append(taken[0])
+            pixel_rng = orc.Rng(block_rng.next_u64(), seed_variant) if stream_mode == api.STREAM_PER_SAMPLE else None
+            for s in range(spp):
+                rng = orc.Rng(pixel_rng.next_u64(), seed_variant) if pixel_rng is not None else block_rng
+
+                def draw():
+                    taken[0] += 1
+                    return np.asarray([rng.next_f32()], np.float32)
+
+                before = taken[0]
+                rad, cnt = self.evaluate(fr, strategy, use_aa, px[c:c + 1], py[c:c + 1], draw)
+                assert taken[0] - before == int(cnt["draws"][0]), (strategy, taken[0] - before, cnt["draws"])
+                rads.append(rad[0]); cnts.append(cnt)
+        counts = {k: np.concatenate([c[k] for c in cnts]) for k in ("draws", "ext", "shadow", "vertices", "some") + self.extra_counts}
+        return px, py, np.asarray(rads, np.float32), counts, np.asarray(starts, np.int64)
+
+    def chain_offsets(self, fr, b, seed, strategy, spp, use_aa, seed_variant, s_stream):
+        """Where every camera sample of block b starts in the block's stream when the count depends on the data: the walk of the None test alone (the jitter,
+        the camera ray's closest hit, the four emitter draws, make_sampler), sample after sample.  [pixels * spp] int64."""
+        px, py = block_pixels(fr.sd, b)
+        px, py = np.repeat(px, spp), np.repeat(py, spp)
+        aa = 2 if use_aa else 0
+        decides, without, with_sampler = self.chain(strategy)
+        offs, at = np.zeros(px.shape[0], np.int64), 0
+        sc = fr.sc
+        for i in range(px.shape[0]):
+            offs[i] = at
+            if use_aa:
+                u, v = F32(px[i]) + s_stream[at], F32(py[i]) + s_stream[at + 1]
+            else:
+                u, v = F32(px[i]) + F32(0.5), F32(py[i]) + F32(0.5)
+            o, d = sc.camera_generate(float(u), float(v))
+            o, d = o.reshape(1, 3), d.reshape(1, 3)
+            t, _, _, mesh, _ = sc.trace(o, d)
+            q = s_stream[at + aa:at + aa + 4]
+            pos, nrm, _, _ = fr.emitters.sample(q[0:1], q[1:2], q[2:3], q[3:4])
+            _, ok = make_sampler(decides, mesh >= 0, t.astype(np.float32), o, d, pos, nrm)
+            at += aa + (with_sampler if ok[0] else without)
+        return offs, at
+
+    def render(self, fr, seeds, strategy, spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
+        """(image HxWx3 f32, the five counters, detail) with every camera sample of a block as one array element.  detail: "starts" {block: [pixels] the draws
+        the block's stream has given when each pixel starts} (reference order), "some" / "none": how many samples had / lacked the distance sampler that can
+        be None, and the kind's extra counts."""
+        self.check_params(strategy, spp, stream_mode, shard_index, shard_count, use_aa)
+        sd = fr.sd
+        img = np.zeros((sd.height, sd.width, 3), np.float32)
+        st = {k: 0 for k in COUNTERS}
+        detail = self._new_detail()
+        kmax = self.max_draws(strategy, use_aa)
+        for b, seed in enumerate(np.asarray(seeds, np.uint64)):
+            if b % max(shard_count, 1) != shard_index:
+                continue
+            px, py = block_pixels(sd, b)
+            n_pix = px.shape[0]
+            spx, spy = np.repeat(px, spp), np.repeat(py, spp)
+            n = n_pix * spp
+            if stream_mode == api.STREAM_PER_SAMPLE:
+                block_rng = orc.Rng(int(seed), seed_variant)
+                table = np.zeros((n, kmax), np.float32)
+                for c in range(n_pix):
+                    pixel_rng = orc.Rng(block_rng.next_u64(), seed_variant)
+                    for s in range(spp):
+                        rng = orc.Rng(pixel_rng.next_u64(), seed_variant)
+                        table[c * spp + s] = [rng.next_f32() for _ in range(kmax)]
+            else:
+                s_stream = U.stream(int(seed), seed_variant, n * kmax + kmax)
+                dconst = self.draws_per_sample(strategy, use_aa)
+                if dconst is not None:
+                    offs = np.arange(n, dtype=np.int64) * dconst
+                else:
+                    offs, _ = self.chain_offsets(fr, b, int(seed), strategy, spp, use_aa, seed_variant, s_stream)
+                table = s_stream[offs[:, None] + np.arange(kmax)[None, :]]
+                detail["starts"][b] = offs[::spp].copy()
+            col = [0]
 
             def draw():
-                taken[0] += 1
-                return np.asarray([rng.next_f32()], np.float32)
+                col[0] += 1
+                return table[:, col[0] - 1].copy()
 
-            before = taken[0]
-            rad, cnt = evaluate(fr, strategy, use_aa, px[c:c + 1], py[c:c + 1], draw)
-            assert taken[0] - before == int(cnt["draws"][0]), (strategy, taken[0] - before, cnt["draws"])
-            rads.append(rad[0]); cnts.append(cnt)
-    counts = {k: np.concatenate([c[k] for c in cnts]) for k in ("draws", "ext", "shadow", "vertices", "some")}
-    return px, py, np.asarray(rads, np.float32), counts, np.asarray(starts, np.int64)
+            rad, cnt = self.evaluate(fr, strategy, use_aa, spx, spy, draw)
+            _finish(sd, spp, px, py, rad, cnt, img, st)
+            self._add_detail(detail, cnt)
+        return img, st, detail
 
+    def render_walk(self, fr, seeds, strategy, spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
+        """render through walk_block: (image, counters, detail)."""
+        self.check_params(strategy, spp, stream_mode, shard_index, shard_count, use_aa)
+        sd = fr.sd
+        img = np.zeros((sd.height, sd.width, 3), np.float32)
+        st = {k: 0 for k in COUNTERS}
+        detail = self._new_detail()
+        for b, seed in enumerate(np.asarray(seeds, np.uint64)):
+            if b % max(shard_count, 1) != shard_index:
+                continue
+            px, py, rad, cnt, starts = self.walk_block(fr, b, int(seed), strategy, spp, use_aa, stream_mode, seed_variant)
+            _finish(sd, spp, px, py, rad, cnt, img, st)
+            if stream_mode == api.STREAM_REFERENCE_ORDER:
+                detail["starts"][b] = starts
+            self._add_detail(detail, cnt)
+        return img, st, detail
 
-def chain_offsets(fr, b, seed, strategy, spp, use_aa, seed_variant, s_stream):
-    """Where every camera sample of block b starts in the block's stream for a data-dependent strategy: the walk of the None test alone (the jitter, the camera
-    ray's closest hit, the four emitter draws, make_sampler), sample after sample.  [pixels * spp] int64."""
-    px, py = block_pixels(fr.sd, b)
-    px, py = np.repeat(px, spp), np.repeat(py, spp)
-    aa = 2 if use_aa else 0
-    extra = 3 if is_phase(strategy) else 1
-    offs, at = np.zeros(px.shape[0], np.int64), 0
-    sc = fr.sc
-    for i in range(px.shape[0]):
-        offs[i] = at
-        if use_aa:
-            u, v = F32(px[i]) + s_stream[at], F32(py[i]) + s_stream[at + 1]
-        else:
-            u, v = F32(px[i]) + F32(0.5), F32(py[i]) + F32(0.5)
-        o, d = sc.camera_generate(float(u), float(v))
-        o, d = o.reshape(1, 3), d.reshape(1, 3)
-        t, _, _, mesh, _ = sc.trace(o, d)
-        q = s_stream[at + aa:at + aa + 4]
-        pos, nrm, _, _ = fr.emitters.sample(q[0:1], q[1:2], q[2:3], q[3:4])
-        _, ok = make_sampler(strategy, mesh >= 0, t.astype(np.float32), o, d, pos, nrm)
-        at += aa + 4 + (extra if ok[0] else 0)
-    return offs, at
+    def compute(self, sd, seed=0, strategy="tr_ex", spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0):
+        """IntegratorPointNormal::compute seed for seed: the block seeds straight from the main sampler seeded as `-r independent:SEED`."""
+        fr = self.frame_class(sd)
+        seeds = orc.block_seeds(seed, sd.width, sd.height, seed_variant)
+        img, st, detail = self.render(fr, seeds, strategy, spp, use_aa, stream_mode, seed_variant)
+        return {"seeds": seeds, "image": img, "stats": st, "detail": detail, "frame": fr}
 
+    # the fixtures the CPU and the GPU tests share, each computed once and left unchanged
+    def frame(self, name, w=24, h=18):
+        if (name, w, h) not in self.cache:
+            self.cache[(name, w, h)] = self.frame_class(scene(name, w, h))
+        return self.cache[(name, w, h)]
 
-def render(fr, seeds, strategy, spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
-    """(image HxWx3 f32, the five counters, detail) with every camera sample of a block as one array element.  detail: "starts" {block: [pixels] the draws the
-    block's stream has given when each pixel starts} (reference order), "some" / "none": how many samples had / lacked a distance sampler."""
-    check_params(strategy, spp, stream_mode, shard_index, shard_count, use_aa)
-    sd = fr.sd
-    img = np.zeros((sd.height, sd.width, 3), np.float32)
-    st = {k: 0 for k in COUNTERS}
-    detail = {"starts": {}, "some": 0, "none": 0}
-    kmax = max_draws(strategy, use_aa)
-    for b, seed in enumerate(np.asarray(seeds, np.uint64)):
-        if b % max(shard_count, 1) != shard_index:
-            continue
-        px, py = block_pixels(sd, b)
-        n_pix = px.shape[0]
-        spx, spy = np.repeat(px, spp), np.repeat(py, spp)
-        n = n_pix * spp
-        if stream_mode == api.STREAM_PER_SAMPLE:
-            block_rng = orc.Rng(int(seed), seed_variant)
-            table = np.zeros((n, kmax), np.float32)
-            for c in range(n_pix):
-                pixel_rng = orc.Rng(block_rng.next_u64(), seed_variant)
-                for s in range(spp):
-                    rng = orc.Rng(pixel_rng.next_u64(), seed_variant)
-                    table[c * spp + s] = [rng.next_f32() for _ in range(kmax)]
-        else:
-            s_stream = U.stream(int(seed), seed_variant, n * kmax + kmax)
-            dconst = draws_per_sample(strategy, use_aa)
-            if dconst is not None:
-                offs = np.arange(n, dtype=np.int64) * dconst
-            else:
-                offs, _ = chain_offsets(fr, b, int(seed), strategy, spp, use_aa, seed_variant, s_stream)
-            table = s_stream[offs[:, None] + np.arange(kmax)[None, :]]
-            detail["starts"][b] = offs[::spp].copy()
-        col = [0]
-
-        def draw():
-            col[0] += 1
-            return table[:, col[0] - 1].copy()
-
-        rad, cnt = evaluate(fr, strategy, use_aa, spx, spy, draw)
-        _finish(sd, spp, px, py, rad, cnt, img, st)
-        detail["some"] += int(cnt["some"].sum()); detail["none"] += int((~cnt["some"]).sum())
-    return img, st, detail
+    def fixture(self, name, strategy, spp=3, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, w=24, h=18, seed=7, shard_index=0, shard_count=1):
+        """(frame, seeds, image, counters, detail) of one render of scene(name), computed once."""
+        key = ("render", name, self.fixture_key(strategy), spp, use_aa, stream_mode, w, h, seed, shard_index, shard_count)
+        if key not in self.cache:
+            fr = self.frame(name, w, h)
+            seeds = orc.block_seeds(seed, w, h)
+            self.cache[key] = (fr, seeds) + self.render(fr, seeds, strategy, spp, use_aa, stream_mode, 0, shard_index, shard_count)
+        return self.cache[key]
 
 
-def render_walk(fr, seeds, strategy, spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
-    """render through walk_block: (image, counters, detail)."""
-    check_params(strategy, spp, stream_mode, shard_index, shard_count, use_aa)
-    sd = fr.sd
-    img = np.zeros((sd.height, sd.width, 3), np.float32)
-    st = {k: 0 for k in COUNTERS}
-    detail = {"starts": {}, "some": 0, "none": 0}
-    for b, seed in enumerate(np.asarray(seeds, np.uint64)):
-        if b % max(shard_count, 1) != shard_index:
-            continue
-        px, py, rad, cnt, starts = walk_block(fr, b, int(seed), strategy, spp, use_aa, stream_mode, seed_variant)
-        _finish(sd, spp, px, py, rad, cnt, img, st)
-        if stream_mode == api.STREAM_REFERENCE_ORDER:
-            detail["starts"][b] = starts
-        detail["some"] += int(cnt["some"].sum()); detail["none"] += int((~cnt["some"]).sum())
-    return img, st, detail
-
-
-def compute(sd, seed=0, strategy="tr_ex", spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0):
-    """IntegratorPointNormal::compute seed for seed: the block seeds straight from the main sampler seeded as `-r independent:SEED`."""
-    fr = Frame(sd)
-    seeds = orc.block_seeds(seed, sd.width, sd.height, seed_variant)
-    img, st, detail = render(fr, seeds, strategy, spp, use_aa, stream_mode, seed_variant)
-    return {"seeds": seeds, "image": img, "stats": st, "detail": detail, "frame": fr}
+PLAIN = Drivers(evaluate, draws_per_sample, max_draws, check_params, lambda strategy: (strategy, 4, 4 + (3 if is_phase(strategy) else 1)), Frame)
+walk_block, chain_offsets, render, render_walk, compute, frame, fixture = (PLAIN.walk_block, PLAIN.chain_offsets, PLAIN.render, PLAIN.render_walk, PLAIN.compute,
+                                                                           PLAIN.frame, PLAIN.fixture)
 
 
 def camera_rays(fr, seeds, strategy, spp, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0):
@@ -684,22 +720,3 @@ def scene(name, w=24, h=18):
     if name == "floating":
         return floating_light(w, h)
     raise KeyError(name)
-
-
-_CACHE = {}
-
-
-def frame(name, w=24, h=18):
-    if (name, w, h) not in _CACHE:
-        _CACHE[(name, w, h)] = Frame(scene(name, w, h))
-    return _CACHE[(name, w, h)]
-
-
-def fixture(name, strategy, spp=3, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, w=24, h=18, seed=7, shard_index=0, shard_count=1):
-    """(frame, seeds, image, counters, detail) of one render of scene(name), computed once."""
-    key = ("render", name, strategy, spp, use_aa, stream_mode, w, h, seed, shard_index, shard_count)
-    if key not in _CACHE:
-        fr = frame(name, w, h)
-        seeds = orc.block_seeds(seed, w, h)
-        _CACHE[key] = (fr, seeds) + render(fr, seeds, strategy, spp, use_aa, stream_mode, 0, shard_index, shard_count)
-    return _CACHE[key]

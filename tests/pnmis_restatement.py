@@ -26,19 +26,18 @@ Counters: camera_samples; rng_draws; extension_rays = camera rays + phase rays t
 when n . (-d) <= 0, none when t_light is zero or not finite); vertices = for tr and eq the samples no defined panic ended, for clamped and pn the samples whose
 third sampler was Some.
 
-As in pn_restatement, evaluate() is one set of elementwise float32 statements over arrays of camera samples; render_walk calls it sample by sample (arrays of
-one element) on one orc.Rng per block, every draw taken where the reference takes it, and render calls it once per block with the draws read from the
-block's stream at each sample's offset (chain_offsets walks the None test alone for clamped and pn, which is what the device's chain pass does).
+As in pn_restatement, evaluate() is one set of elementwise float32 statements over arrays of camera samples, and the drivers are pn_restatement.Drivers around
+it (MIS at the end of this module): render_walk calls it sample by sample (arrays of one element) on one orc.Rng per block, every draw taken where the
+reference takes it, and render calls it once per block with the draws read from the block's stream at each sample's offset (chain_offsets walks the None
+test alone for clamped and pn, which is what the device's chain pass does).
 
 MUTATION (None in every test of the product) breaks one statement on purpose, for the quadrature test's proof that its assertion has teeth."""
 
 import numpy as np
 
-from oracle import orc
 from rustlight_amd import api
 from tests import plane_single_restatement as R
 from tests import pn_restatement as P
-from tests import uplane_restatement as U
 from tests.pn_restatement import F32, FRAC_1_PI, ONE, PI, ZERO, Refused, _col, _mul_guarded  # noqa: F401
 
 STRATEGIES = P.STRATEGIES
@@ -375,7 +374,7 @@ def evaluate(fr, strategy, use_aa, px, py, draw):
         return (((ph_tr + ph_eq) + ex_tr) + ex_ot).astype(np.float32), cnt
 
 
-# ---- drivers (pn_restatement's, around evaluate above)
+# ---- drivers: pn_restatement.Drivers around evaluate above
 block_pixels, _finish, check_scene = P.block_pixels, P._finish, P.check_scene
 
 
@@ -386,149 +385,11 @@ def check_params(strategy, spp, stream_mode, shard_index, shard_count, use_aa=Tr
         raise Refused(P.RL_ERR_UNSUPPORTED, "jump-ahead reach")
 
 
-def walk_block(fr, b, seed, strategy, spp, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0):
-    """The reference's loop over one block, camera sample after camera sample, draw after draw on orc.Rng."""
-    px, py = block_pixels(fr.sd, b)
-    block_rng = orc.Rng(int(seed), seed_variant)
-    taken = [0]
-    rads, cnts, starts = [], [], []
-    for c in range(px.shape[0]):
-        starts.append(taken[0])
-        pixel_rng = orc.Rng(block_rng.next_u64(), seed_variant) if stream_mode == api.STREAM_PER_SAMPLE else None
-        for s in range(spp):
-            rng = orc.Rng(pixel_rng.next_u64(), seed_variant) if pixel_rng is not None else block_rng
-
-            def draw():
-                taken[0] += 1
-                return np.asarray([rng.next_f32()], np.float32)
-
-            before = taken[0]
-            rad, cnt = evaluate(fr, strategy, use_aa, px[c:c + 1], py[c:c + 1], draw)
-            assert taken[0] - before == int(cnt["draws"][0]), (strategy, taken[0] - before, cnt["draws"])
-            rads.append(rad[0]); cnts.append(cnt)
-    counts = {k: np.concatenate([c[k] for c in cnts]) for k in ("draws", "ext", "shadow", "vertices", "some", "panic")}
-    return px, py, np.asarray(rads, np.float32), counts, np.asarray(starts, np.int64)
+def _chain(strategy):
+    """The third sampler decides; 8 draws behind the jitter, and one more with it."""
+    return third(family(strategy)), 8, 9
 
 
-def chain_offsets(fr, b, seed, strategy, spp, use_aa, seed_variant, s_stream):
-    """Where every camera sample of block b starts in the block's stream for clamped and pn: the walk of the None test alone."""
-    px, py = block_pixels(fr.sd, b)
-    px, py = np.repeat(px, spp), np.repeat(py, spp)
-    aa = 2 if use_aa else 0
-    offs, at = np.zeros(px.shape[0], np.int64), 0
-    sc = fr.sc
-    for i in range(px.shape[0]):
-        offs[i] = at
-        if use_aa:
-            u, v = F32(px[i]) + s_stream[at], F32(py[i]) + s_stream[at + 1]
-        else:
-            u, v = F32(px[i]) + F32(0.5), F32(py[i]) + F32(0.5)
-        o, d = sc.camera_generate(float(u), float(v))
-        o, d = o.reshape(1, 3), d.reshape(1, 3)
-        t, _, _, mesh, _ = sc.trace(o, d)
-        q = s_stream[at + aa:at + aa + 4]
-        pos, nrm, _, _ = fr.emitters.sample(q[0:1], q[1:2], q[2:3], q[3:4])
-        _, ok = P.make_sampler(third(family(strategy)), mesh >= 0, t.astype(np.float32), o, d, pos, nrm)
-        at += aa + 8 + (1 if ok[0] else 0)
-    return offs, at
-
-
-def _new_detail():
-    return {"starts": {}, "some": 0, "none": 0, "panic": 0}
-
-
-def _add_detail(detail, cnt):
-    detail["some"] += int(cnt["some"].sum()); detail["none"] += int((~cnt["some"]).sum()); detail["panic"] += int(cnt["panic"].sum())
-
-
-def render(fr, seeds, strategy, spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
-    """(image HxWx3 f32, the five counters, detail) with every camera sample of a block as one array element.  detail: "starts" {block: [pixels] the draws the
-    block's stream has given when each pixel starts} (reference order), "some" / "none": how many samples had / lacked a third sampler (clamped, pn),
-    "panic": how many a defined panic ended."""
-    check_params(strategy, spp, stream_mode, shard_index, shard_count, use_aa)
-    sd = fr.sd
-    img = np.zeros((sd.height, sd.width, 3), np.float32)
-    st = {k: 0 for k in COUNTERS}
-    detail = _new_detail()
-    kmax = max_draws(strategy, use_aa)
-    for b, seed in enumerate(np.asarray(seeds, np.uint64)):
-        if b % max(shard_count, 1) != shard_index:
-            continue
-        px, py = block_pixels(sd, b)
-        n_pix = px.shape[0]
-        spx, spy = np.repeat(px, spp), np.repeat(py, spp)
-        n = n_pix * spp
-        if stream_mode == api.STREAM_PER_SAMPLE:
-            block_rng = orc.Rng(int(seed), seed_variant)
-            table = np.zeros((n, kmax), np.float32)
-            for c in range(n_pix):
-                pixel_rng = orc.Rng(block_rng.next_u64(), seed_variant)
-                for s in range(spp):
-                    rng = orc.Rng(pixel_rng.next_u64(), seed_variant)
-                    table[c * spp + s] = [rng.next_f32() for _ in range(kmax)]
-        else:
-            s_stream = U.stream(int(seed), seed_variant, n * kmax + kmax)
-            dconst = draws_per_sample(strategy, use_aa)
-            if dconst is not None:
-                offs = np.arange(n, dtype=np.int64) * dconst
-            else:
-                offs, _ = chain_offsets(fr, b, int(seed), strategy, spp, use_aa, seed_variant, s_stream)
-            table = s_stream[offs[:, None] + np.arange(kmax)[None, :]]
-            detail["starts"][b] = offs[::spp].copy()
-        col = [0]
-
-        def draw():
-            col[0] += 1
-            return table[:, col[0] - 1].copy()
-
-        rad, cnt = evaluate(fr, strategy, use_aa, spx, spy, draw)
-        _finish(sd, spp, px, py, rad, cnt, img, st)
-        _add_detail(detail, cnt)
-    return img, st, detail
-
-
-def render_walk(fr, seeds, strategy, spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
-    """render through walk_block: (image, counters, detail)."""
-    check_params(strategy, spp, stream_mode, shard_index, shard_count, use_aa)
-    sd = fr.sd
-    img = np.zeros((sd.height, sd.width, 3), np.float32)
-    st = {k: 0 for k in COUNTERS}
-    detail = _new_detail()
-    for b, seed in enumerate(np.asarray(seeds, np.uint64)):
-        if b % max(shard_count, 1) != shard_index:
-            continue
-        px, py, rad, cnt, starts = walk_block(fr, b, int(seed), strategy, spp, use_aa, stream_mode, seed_variant)
-        _finish(sd, spp, px, py, rad, cnt, img, st)
-        if stream_mode == api.STREAM_REFERENCE_ORDER:
-            detail["starts"][b] = starts
-        _add_detail(detail, cnt)
-    return img, st, detail
-
-
-def compute(sd, seed=0, strategy="tr_ex", spp=1, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, seed_variant=0):
-    """IntegratorPointNormal::compute with use_mis, seed for seed: the block seeds straight from the main sampler seeded as `-r independent:SEED`."""
-    fr = Frame(sd)
-    seeds = orc.block_seeds(seed, sd.width, sd.height, seed_variant)
-    img, st, detail = render(fr, seeds, strategy, spp, use_aa, stream_mode, seed_variant)
-    return {"seeds": seeds, "image": img, "stats": st, "detail": detail, "frame": fr}
-
-
-# ---- the scenes and fixtures the CPU and the GPU tests share, each computed once and left unchanged
+MIS = P.Drivers(evaluate, draws_per_sample, max_draws, check_params, _chain, Frame, extra_counts=("panic",), fixture_key=family)      # a family's names share a render
+walk_block, chain_offsets, render, render_walk, compute, frame, fixture = MIS.walk_block, MIS.chain_offsets, MIS.render, MIS.render_walk, MIS.compute, MIS.frame, MIS.fixture
 scene = P.scene
-_CACHE = {}
-
-
-def frame(name, w=24, h=18):
-    if (name, w, h) not in _CACHE:
-        _CACHE[(name, w, h)] = Frame(scene(name, w, h))
-    return _CACHE[(name, w, h)]
-
-
-def fixture(name, strategy, spp=3, use_aa=True, stream_mode=api.STREAM_REFERENCE_ORDER, w=24, h=18, seed=7, shard_index=0, shard_count=1):
-    """(frame, seeds, image, counters, detail) of one render of scene(name), computed once.  The two names of a family share one render."""
-    key = ("render", name, family(strategy), spp, use_aa, stream_mode, w, h, seed, shard_index, shard_count)
-    if key not in _CACHE:
-        fr = frame(name, w, h)
-        seeds = orc.block_seeds(seed, w, h)
-        _CACHE[key] = (fr, seeds) + render(fr, seeds, strategy, spp, use_aa, stream_mode, 0, shard_index, shard_count)
-    return _CACHE[key]
