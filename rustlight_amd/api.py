@@ -579,23 +579,28 @@ class Context(_ImageCalls):
         d["splats"], d["splats_invalid"], d["splats_saturated"] = (int(v) for v in st.reserved[:3])
         return img, d
 
+    def _light_pass(self, name, set_class, sampler, nb, max_depth, rr_depth, streams, *option):
+        """rl_<name>_generate (streams="reference") or rl_<name>_generate_paths ("per_path") behind vpl_generate, beam_generate and pplane_generate:
+        (set_class handle, stats dict).  `option`: what the call takes between the count and the sampler."""
+        if streams not in LIGHT_STREAMS:
+            raise ValueError(f"streams must be one of {LIGHT_STREAMS}, not {streams!r}")
+        p = path_params(1, 0, max_depth, rr_depth, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=sampler.variant)
+        st = abi.RenderStats()
+        h = C.c_void_p()
+        fn = getattr(lib(), f"rl_{name}_generate" if streams == "reference" else f"rl_{name}_generate_paths")
+        _check(fn(self.h, C.byref(p), nb, *option, C.byref(sampler.s), C.byref(h), C.byref(st)))
+        d = st.as_dict()
+        if streams == "per_path":
+            d["paths_walked"] = int(st.reserved[0])
+        return set_class(h, self), d
+
     def vpl_generate(self, sampler: "IndependentSampler", nb_vpl=128, max_depth=None, rr_depth=0, option_vpl=VPL_ALL, streams="reference"):
         """IntegratorVPL's generation (vpl.rs:182-210): (VplSet, stats dict).  streams="reference": rl_vpl_generate, one lane on the main sampler's serial stream,
         seed for seed the reference; `sampler` is advanced as the reference's main sampler is.  streams="per_path": rl_vpl_generate_paths, one light path per lane
         on the stream of the k-th clone_box of `sampler` (include/rustlight_amd.h has the contract): statistically, not seed-for-seed, the
         same image; `sampler` is advanced by one next_u64 per kept path.  stats: camera_samples = light paths shot (kept), vertices, extension_rays, rng_draws,
         ms_prepass = the generation kernels' time; per_path adds iterations = rounds and paths_walked = reserved[0]."""
-        if streams not in LIGHT_STREAMS:
-            raise ValueError(f"streams must be one of {LIGHT_STREAMS}, not {streams!r}")
-        p = path_params(1, 0, max_depth, rr_depth, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=sampler.variant)
-        st = abi.RenderStats()
-        h = C.c_void_p()
-        fn = lib().rl_vpl_generate if streams == "reference" else lib().rl_vpl_generate_paths
-        _check(fn(self.h, C.byref(p), nb_vpl, option_vpl, C.byref(sampler.s), C.byref(h), C.byref(st)))
-        d = st.as_dict()
-        if streams == "per_path":
-            d["paths_walked"] = int(st.reserved[0])
-        return VplSet(h, self), d
+        return self._light_pass("vpl", VplSet, sampler, nb_vpl, max_depth, rr_depth, streams, option_vpl)
 
     def render_vpl(self, vpls: "VplSet", seeds, spp=1, option_lt=VPL_ALL, seed_variant=0, shard_index=0, shard_count=1, stream_mode=STREAM_REFERENCE_ORDER,
                    numerics=NUMERICS_EXACT):
@@ -607,23 +612,32 @@ class Context(_ImageCalls):
         d["gather_surface"], d["gather_volume"] = int(st.reserved[0]), int(st.reserved[1])
         return img, d
 
+    def _map(self, fn, map_class, *args, after=()):
+        """fn(context, *args, &handle, *after) behind the *_map and *_map_from_words methods: the map_class over the handle."""
+        h = C.c_void_p()
+        _check(fn(self.h, *args, C.byref(h), *after))
+        return map_class(h, self)
+
+    def _timed_map(self, name, map_class, build, records, *args):
+        """photon_map / plane_map: the map from <name>(context, records, *args, &handle) or, build="device", <name>_device(.., &handle, &ms) — with ms_build,
+        the wall clock of the call, and ms_kernels, the device build's kernel time (None: host).  `build` is checked before anything else is touched."""
+        if build not in TREE_BUILDS:
+            raise ValueError(f"build must be one of {TREE_BUILDS}, not {build!r}")
+        ms = C.c_float(0.0)
+        t0 = time.perf_counter()
+        if build == "device":
+            m = self._map(getattr(lib(), name + "_device"), map_class, records.h, *args, after=(C.byref(ms),))
+        else:
+            m = self._map(getattr(lib(), name), map_class, records.h, *args)
+        m.ms_build = (time.perf_counter() - t0) * 1e3
+        m.ms_kernels = float(ms.value) if build == "device" else None
+        return m
+
     def photon_map(self, vpls: "VplSet", radius=PHOTON_RADIUS_DEFAULT, build="host"):
         """rl_photon_map_build: the photon tree of the beam radiance estimate over a set generated with option_vpl = VPL_VOLUME (its records are the reference's
         photons).  radius: the reference hard-codes PHOTON_RADIUS_DEFAULT.  build="device": rl_photon_map_build_device, the same map byte for byte from device
         kernels, no record leaving the GPU.  PhotonMap.ms_build: wall clock of the call; PhotonMap.ms_kernels: the device build's kernel time (None: host)."""
-        if build not in TREE_BUILDS:
-            raise ValueError(f"build must be one of {TREE_BUILDS}, not {build!r}")
-        h = C.c_void_p()
-        ms = C.c_float(0.0)
-        t0 = time.perf_counter()
-        if build == "device":
-            _check(lib().rl_photon_map_build_device(self.h, vpls.h, radius, C.byref(h), C.byref(ms)))
-        else:
-            _check(lib().rl_photon_map_build(self.h, vpls.h, radius, C.byref(h)))
-        m = PhotonMap(h, self)
-        m.ms_build = (time.perf_counter() - t0) * 1e3
-        m.ms_kernels = float(ms.value) if build == "device" else None
-        return m
+        return self._timed_map("rl_photon_map_build", PhotonMap, build, vpls, radius)
 
     def photon_tree_build_device(self, words, radius):
         """rl_photon_tree_build_device: photon_tree_build's arrays, computed by the kernels of the device build on this context's device."""
@@ -646,31 +660,17 @@ class Context(_ImageCalls):
         """The photon beams' beam pass (vol_primitives.rs:437-523, 608-630): (BeamSet, stats dict).  streams="reference": rl_beam_generate, one lane on the main
         sampler's serial stream, seed for seed the reference; streams="per_path": rl_beam_generate_paths under rl_vpl_generate_paths' stream contract.  `sampler`
         and the stats follow Context.vpl_generate's rules."""
-        if streams not in LIGHT_STREAMS:
-            raise ValueError(f"streams must be one of {LIGHT_STREAMS}, not {streams!r}")
-        p = path_params(1, 0, max_depth, rr_depth, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=sampler.variant)
-        st = abi.RenderStats()
-        h = C.c_void_p()
-        fn = lib().rl_beam_generate if streams == "reference" else lib().rl_beam_generate_paths
-        _check(fn(self.h, C.byref(p), nb_primitive, C.byref(sampler.s), C.byref(h), C.byref(st)))
-        d = st.as_dict()
-        if streams == "per_path":
-            d["paths_walked"] = int(st.reserved[0])
-        return BeamSet(h, self), d
+        return self._light_pass("beam", BeamSet, sampler, nb_primitive, max_depth, rr_depth, streams)
 
     def beam_map(self, beams: "BeamSet", radius=PHOTON_RADIUS_DEFAULT):
         """rl_beam_map_build: the beams of a set split into sub-beams and sorted into the beam tree on the host, uploaded.  radius: the reference hard-codes
         PHOTON_RADIUS_DEFAULT."""
-        h = C.c_void_p()
-        _check(lib().rl_beam_map_build(self.h, beams.h, radius, C.byref(h)))
-        return BeamMap(h, self)
+        return self._map(lib().rl_beam_map_build, BeamMap, beams.h, radius)
 
     def beam_map_from_words(self, words, n_paths, radius=PHOTON_RADIUS_DEFAULT):
         """rl_beam_map_build_words: Context.beam_map over caller-supplied beam records ([n, BEAM_WORDS] u32) of n_paths light paths."""
         w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, BEAM_WORDS)
-        h = C.c_void_p()
-        _check(lib().rl_beam_map_build_words(self.h, abi.u32ptr(w), w.shape[0], n_paths, radius, C.byref(h)))
-        return BeamMap(h, self)
+        return self._map(lib().rl_beam_map_build_words, BeamMap, abi.u32ptr(w), w.shape[0], n_paths, radius)
 
     def render_beams(self, beams: "BeamMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
         """The photon beams' gather (vol_primitives.rs:140-199, 705-790) through rl_render_beams: (image HxWx3 f32, stats dict).  stats: nodes_entered /
@@ -680,16 +680,12 @@ class Context(_ImageCalls):
     def vrl_map(self, beams: "BeamSet", radius=PHOTON_RADIUS_DEFAULT):
         """rl_vrl_map_build: the beams of a beam pass partitioned by from_surface — the surface beams split and sorted into the beam tree, the others kept in
         storing order as VRLs with their roulette probabilities — and uploaded."""
-        h = C.c_void_p()
-        _check(lib().rl_vrl_map_build(self.h, beams.h, radius, C.byref(h)))
-        return VrlMap(h, self)
+        return self._map(lib().rl_vrl_map_build, VrlMap, beams.h, radius)
 
     def vrl_map_from_words(self, words, n_paths, radius=PHOTON_RADIUS_DEFAULT):
         """rl_vrl_map_build_words: Context.vrl_map over caller-supplied beam records ([n, BEAM_WORDS] u32) of n_paths light paths."""
         w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, BEAM_WORDS)
-        h = C.c_void_p()
-        _check(lib().rl_vrl_map_build_words(self.h, abi.u32ptr(w), w.shape[0], n_paths, radius, C.byref(h)))
-        return VrlMap(h, self)
+        return self._map(lib().rl_vrl_map_build_words, VrlMap, abi.u32ptr(w), w.shape[0], n_paths, radius)
 
     def render_vrl(self, vmap: "VrlMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
         """The virtual ray lights' gather (vol_primitives.rs:201-253, 741-764) through rl_render_vrl: (image HxWx3 f32, stats dict).  stats: nodes_entered /
@@ -700,33 +696,19 @@ class Context(_ImageCalls):
     def pplane_generate(self, sampler: "IndependentSampler", nb_primitive=128, max_depth=None, rr_depth=0, streams="reference"):
         """The photon planes' plane pass (vol_primitives.rs:376-523, 608-630): (PPlaneSet, stats dict).  The light paths of Context.beam_generate, stored as
         surface beams and planes while fewer than nb_primitive planes are stored.  streams, `sampler` and the stats follow Context.beam_generate's rules."""
-        if streams not in LIGHT_STREAMS:
-            raise ValueError(f"streams must be one of {LIGHT_STREAMS}, not {streams!r}")
-        p = path_params(1, 0, max_depth, rr_depth, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=sampler.variant)
-        st = abi.RenderStats()
-        h = C.c_void_p()
-        fn = lib().rl_pplane_generate if streams == "reference" else lib().rl_pplane_generate_paths
-        _check(fn(self.h, C.byref(p), nb_primitive, C.byref(sampler.s), C.byref(h), C.byref(st)))
-        d = st.as_dict()
-        if streams == "per_path":
-            d["paths_walked"] = int(st.reserved[0])
-        return PPlaneSet(h, self), d
+        return self._light_pass("pplane", PPlaneSet, sampler, nb_primitive, max_depth, rr_depth, streams)
 
     def pplane_map(self, records: "PPlaneSet", radius=PHOTON_RADIUS_DEFAULT):
         """rl_pplane_map_build: the surface beams of a set split and sorted into the beam tree, its planes sorted into the plane tree, both uploaded.  The plane
         tree is built on the host, or by the device kernels under the context option pplane_tree_device = 1 (the same bytes)."""
-        h = C.c_void_p()
-        _check(lib().rl_pplane_map_build(self.h, records.h, radius, C.byref(h)))
-        return PPlaneMap(h, self)
+        return self._map(lib().rl_pplane_map_build, PPlaneMap, records.h, radius)
 
     def pplane_map_from_words(self, beam_words, plane_words, n_paths, radius=PHOTON_RADIUS_DEFAULT):
         """rl_pplane_map_build_words: Context.pplane_map over caller-supplied beam ([n, BEAM_WORDS] u32) and plane ([m, PLANE_WORDS] u32) records of n_paths
         light paths."""
         b = np.ascontiguousarray(beam_words, dtype=np.uint32).reshape(-1, BEAM_WORDS)
         w = np.ascontiguousarray(plane_words, dtype=np.uint32).reshape(-1, PLANE_WORDS)
-        h = C.c_void_p()
-        _check(lib().rl_pplane_map_build_words(self.h, abi.u32ptr(b), b.shape[0], abi.u32ptr(w), w.shape[0], n_paths, radius, C.byref(h)))
-        return PPlaneMap(h, self)
+        return self._map(lib().rl_pplane_map_build_words, PPlaneMap, abi.u32ptr(b), b.shape[0], abi.u32ptr(w), w.shape[0], n_paths, radius)
 
     def render_photon_planes(self, pmap: "PPlaneMap", seeds, spp=1, seed_variant=0, shard_index=0, shard_count=1):
         """The photon planes' gather (vol_primitives.rs:295-373, 705-790) through rl_render_photon_planes: (image HxWx3 f32, stats dict).  stats: nodes_entered
@@ -749,19 +731,7 @@ class Context(_ImageCalls):
     def plane_map(self, planes: "PlaneSet", build="host"):
         """rl_plane_map_build: the plane tree over a generated set, built on the host and uploaded.  build="device": rl_plane_map_build_device, the same map
         byte for byte from device kernels.  PlaneMap.ms_build: wall clock of the call, ms; PlaneMap.ms_kernels: the device build's kernel time (None: host)."""
-        if build not in TREE_BUILDS:
-            raise ValueError(f"build must be one of {TREE_BUILDS}, not {build!r}")
-        h = C.c_void_p()
-        ms = C.c_float(0.0)
-        t0 = time.perf_counter()
-        if build == "device":
-            _check(lib().rl_plane_map_build_device(self.h, planes.h, C.byref(h), C.byref(ms)))
-        else:
-            _check(lib().rl_plane_map_build(self.h, planes.h, C.byref(h)))
-        m = PlaneMap(h, self)
-        m.ms_build = (time.perf_counter() - t0) * 1e3
-        m.ms_kernels = float(ms.value) if build == "device" else None
-        return m
+        return self._timed_map("rl_plane_map_build", PlaneMap, build, planes)
 
     def plane_tree_build_device(self, words):
         """rl_plane_tree_build_device: plane_tree_build's arrays, computed by the kernels of the device build on this context's device."""
@@ -1036,6 +1006,27 @@ def _tree_arrays(build, n_elements):
     return boxes, links, order
 
 
+class _MapIntegrator(_Integrator):
+    """compute of the integrators that gather a map of light-pass records: _generate(ctx, sampler) -> (set, stats), _build(ctx, set) -> map, the block seeds
+    from the sampler the generation leaves, _render(ctx, map, seeds, nb_samples, seed_variant) -> (image, stats); map and set are closed, in that order, on
+    every path."""
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        ctx = self._context(scene)
+        records, self.last_generation_stats = self._generate(ctx, sampler)
+        built = None
+        try:
+            built = self._build(ctx, records)
+            w, h = scene.size
+            seeds = sampler.block_seeds(w, h)
+            img, self.last_stats = self._render(ctx, built, seeds, nb_samples, sampler.variant)
+        finally:
+            if built is not None:
+                built.close()
+            records.close()
+        return img
+
+
 class VplSet(_DeviceHandle):
     """rl_vpl_set: the VPLs of one generation, on the device of the context that made them (kept alive with it)."""
     _destroy = "rl_vpl_destroy"
@@ -1096,7 +1087,7 @@ def photon_tree_build(words, radius):
     return _tree_arrays(lambda *out: lib().rl_photon_tree_build(abi.u32ptr(w), w.shape[0], radius, *out), w.shape[0])
 
 
-class IntegratorVolPrimitives(_Integrator):
+class IntegratorVolPrimitives(_MapIntegrator):
     """struct IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute for
     primitives = BRE, seed for seed the reference: the photons from the main sampler, the block seeds from the sampler they leave, the gather on
     reference-order streams.  radius: the reference's constant unless given.  light_streams="per_path": the photons from rl_vpl_generate_paths (one light path
@@ -1117,20 +1108,35 @@ class IntegratorVolPrimitives(_Integrator):
         self.nb_primitive, self.max_depth, self.rr_depth, self.radius = nb_primitive, max_depth, rr_depth, radius
         self.last_generation_stats = None
 
-    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
-        ctx = self._context(scene)
-        vpls, self.last_generation_stats = ctx.vpl_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, VPL_VOLUME, self.light_streams)
-        photons = None
-        try:
-            photons = ctx.photon_map(vpls, self.radius, self.tree_build)
-            w, h = scene.size
-            seeds = sampler.block_seeds(w, h)
-            img, self.last_stats = ctx.render_bre(photons, seeds, nb_samples, sampler.variant)
-        finally:
-            if photons is not None:
-                photons.close()
-            vpls.close()
-        return img
+    def _generate(self, ctx, sampler):
+        return ctx.vpl_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, VPL_VOLUME, self.light_streams)
+
+    def _build(self, ctx, vpls):
+        return ctx.photon_map(vpls, self.radius, self.tree_build)
+
+    _render = staticmethod(Context.render_bre)
+
+
+class _BeamPassIntegrator(_MapIntegrator):
+    """IntegratorPhotonBeams, IntegratorVirtualRayLights and IntegratorPhotonPlanes: the same fields, and _MapIntegrator's compute over the three Context
+    methods `_calls` names (the beam or plane pass, the map build, the gather)."""
+    _calls = None
+
+    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, radius=PHOTON_RADIUS_DEFAULT, light_streams="reference", device=0, options=None):
+        if light_streams not in LIGHT_STREAMS:
+            raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
+        super().__init__(device, options)
+        self.nb_primitive, self.max_depth, self.rr_depth, self.radius, self.light_streams = nb_primitive, max_depth, rr_depth, radius, light_streams
+        self.last_generation_stats = None
+
+    def _generate(self, ctx, sampler):
+        return getattr(ctx, self._calls[0])(sampler, self.nb_primitive, self.max_depth, self.rr_depth, self.light_streams)
+
+    def _build(self, ctx, records):
+        return getattr(ctx, self._calls[1])(records, self.radius)
+
+    def _render(self, ctx, *args):
+        return getattr(ctx, self._calls[2])(*args)
 
 
 class BeamSet(_DeviceHandle):
@@ -1195,33 +1201,13 @@ def beam_tree_build(sub_words, radius):
     return _tree_arrays(lambda *out: lib().rl_beam_tree_build(abi.u32ptr(w), w.shape[0], radius, *out), w.shape[0])
 
 
-class IntegratorPhotonBeams(_Integrator):
+class IntegratorPhotonBeams(_BeamPassIntegrator):
     """IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: Beams } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute, seed
     for seed the reference: the beams from the main sampler, the split, the beam tree, the block seeds from the sampler the beam pass leaves, the gather on
     reference-order streams.  A class of its own: IntegratorVolPrimitives keeps refusing every primitive but bre.  radius: the reference's constant unless
     given.  light_streams="per_path": the beams from rl_beam_generate_paths: statistically, not seed-for-seed, the same image."""
 
-    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, radius=PHOTON_RADIUS_DEFAULT, light_streams="reference", device=0, options=None):
-        if light_streams not in LIGHT_STREAMS:
-            raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
-        super().__init__(device, options)
-        self.nb_primitive, self.max_depth, self.rr_depth, self.radius, self.light_streams = nb_primitive, max_depth, rr_depth, radius, light_streams
-        self.last_generation_stats = None
-
-    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
-        ctx = self._context(scene)
-        beams, self.last_generation_stats = ctx.beam_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, self.light_streams)
-        bmap = None
-        try:
-            bmap = ctx.beam_map(beams, self.radius)
-            w, h = scene.size
-            seeds = sampler.block_seeds(w, h)
-            img, self.last_stats = ctx.render_beams(bmap, seeds, nb_samples, sampler.variant)
-        finally:
-            if bmap is not None:
-                bmap.close()
-            beams.close()
-        return img
+    _calls = ("beam_generate", "beam_map", "render_beams")
 
 
 class VrlMap(_DeviceHandle):
@@ -1245,33 +1231,13 @@ class VrlMap(_DeviceHandle):
         return boxes, links, beams, vrls
 
 
-class IntegratorVirtualRayLights(_Integrator):
+class IntegratorVirtualRayLights(_BeamPassIntegrator):
     """IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: VRL } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute, seed for
     seed the reference: the beams from the main sampler, the partition, the split and tree of the surface beams, the block seeds from the sampler the beam pass
     leaves, the gather on reference-order streams.  A class of its own: IntegratorVolPrimitives keeps refusing every primitive but bre.  radius: the reference's
     constant unless given.  light_streams="per_path": the beams from rl_beam_generate_paths: statistically, not seed-for-seed, the same image."""
 
-    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, radius=PHOTON_RADIUS_DEFAULT, light_streams="reference", device=0, options=None):
-        if light_streams not in LIGHT_STREAMS:
-            raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
-        super().__init__(device, options)
-        self.nb_primitive, self.max_depth, self.rr_depth, self.radius, self.light_streams = nb_primitive, max_depth, rr_depth, radius, light_streams
-        self.last_generation_stats = None
-
-    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
-        ctx = self._context(scene)
-        beams, self.last_generation_stats = ctx.beam_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, self.light_streams)
-        vmap = None
-        try:
-            vmap = ctx.vrl_map(beams, self.radius)
-            w, h = scene.size
-            seeds = sampler.block_seeds(w, h)
-            img, self.last_stats = ctx.render_vrl(vmap, seeds, nb_samples, sampler.variant)
-        finally:
-            if vmap is not None:
-                vmap.close()
-            beams.close()
-        return img
+    _calls = ("beam_generate", "vrl_map", "render_vrl")
 
 
 class PPlaneSet(_DeviceHandle):
@@ -1328,33 +1294,13 @@ class PPlaneMap(_DeviceHandle):
         return boxes, links, el
 
 
-class IntegratorPhotonPlanes(_Integrator):
+class IntegratorPhotonPlanes(_BeamPassIntegrator):
     """IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives: Planes } (src/integrators/explicit/vol_primitives.rs) + Integrator::compute, seed
     for seed the reference: surface beams and planes from the main sampler, the split, the two trees, the block seeds from the sampler the plane pass leaves,
     the gather on reference-order streams.  A class of its own: IntegratorVolPrimitives keeps refusing every primitive but bre.  radius: the reference's
     constant unless given.  light_streams="per_path": the records from rl_pplane_generate_paths: statistically, not seed-for-seed, the same image."""
 
-    def __init__(self, nb_primitive=128, max_depth=None, rr_depth=0, radius=PHOTON_RADIUS_DEFAULT, light_streams="reference", device=0, options=None):
-        if light_streams not in LIGHT_STREAMS:
-            raise ValueError(f"light_streams must be one of {LIGHT_STREAMS}, not {light_streams!r}")
-        super().__init__(device, options)
-        self.nb_primitive, self.max_depth, self.rr_depth, self.radius, self.light_streams = nb_primitive, max_depth, rr_depth, radius, light_streams
-        self.last_generation_stats = None
-
-    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
-        ctx = self._context(scene)
-        records, self.last_generation_stats = ctx.pplane_generate(sampler, self.nb_primitive, self.max_depth, self.rr_depth, self.light_streams)
-        pmap = None
-        try:
-            pmap = ctx.pplane_map(records, self.radius)
-            w, h = scene.size
-            seeds = sampler.block_seeds(w, h)
-            img, self.last_stats = ctx.render_photon_planes(pmap, seeds, nb_samples, sampler.variant)
-        finally:
-            if pmap is not None:
-                pmap.close()
-            records.close()
-        return img
+    _calls = ("pplane_generate", "pplane_map", "render_photon_planes")
 
 
 def plane_strategy(strategy):
@@ -1416,7 +1362,7 @@ def plane_tree_build(words):
     return _tree_arrays(lambda *out: lib().rl_plane_tree_build(abi.u32ptr(w), w.shape[0], *out), w.shape[0])
 
 
-class IntegratorSinglePlane(_Integrator):
+class IntegratorSinglePlane(_MapIntegrator):
     """struct IntegratorSinglePlane { nb_primitive, strategy } (src/integrators/explicit/plane_single.rs:291-294) + Integrator::compute, seed for seed the
     reference: the planes from the main sampler, the plane tree, the block seeds from the sampler the generation leaves, the gather on reference-order streams.
     generate="lanes" / tree_build="device": the plane pass on one lane per iteration and the tree from device kernels, byte for byte the same planes and map."""
@@ -1431,20 +1377,13 @@ class IntegratorSinglePlane(_Integrator):
         self.nb_primitive, self.strategy = nb_primitive, PLANE_STRATEGIES[plane_strategy(strategy)]
         self.last_generation_stats = None
 
-    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
-        ctx = self._context(scene)
-        planes, self.last_generation_stats = ctx.plane_generate(sampler, self.nb_primitive, self.strategy, self.generate)
-        pmap = None
-        try:
-            pmap = ctx.plane_map(planes, self.tree_build)
-            w, h = scene.size
-            seeds = sampler.block_seeds(w, h)
-            img, self.last_stats = ctx.render_plane_single(pmap, seeds, nb_samples, sampler.variant)
-        finally:
-            if pmap is not None:
-                pmap.close()
-            planes.close()
-        return img
+    def _generate(self, ctx, sampler):
+        return ctx.plane_generate(sampler, self.nb_primitive, self.strategy, self.generate)
+
+    def _build(self, ctx, planes):
+        return ctx.plane_map(planes, self.tree_build)
+
+    _render = staticmethod(Context.render_plane_single)
 
 
 class IntegratorSinglePlaneUncorrelated(_Integrator):

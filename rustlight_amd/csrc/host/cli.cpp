@@ -289,52 +289,32 @@ int main(int argc, char** argv) {
         volp.device = device;
         volp.options = options;
     }
-    // photon-beams: the limits of vol-primitivies, and the medium the reference panics without
+    // photon-beams, virtual-ray-lights, photon-planes: the limits of vol-primitivies, and the medium the reference panics without; photon-planes also has the
+    // depth below which no plane exists (min_max_depth)
+    auto fill_beam_pass = [&](const char* name, auto& it, uint32_t min_max_depth) -> bool {
+        if (refused(name, RL_STREAM_REFERENCE_ORDER, true)) return false;
+        if (!parse_count("--nb-primitive", nb_primitive, &it.nb_primitive)) return false;
+        if (it.nb_primitive > (uint32_t)RL_BEAM_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", nb_primitive.c_str(), (int)RL_BEAM_MAX); return false; }
+        if (!parse_radius(&it.radius)) return false;
+        const Medium m = parse_medium(medium);
+        if (m.sigma_a + m.sigma_s == 0.0f) { std::fprintf(stderr, "%s: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n", name); return false; }
+        it.max_depth = match_infinity(max_depth);
+        if (it.max_depth.has_value() && *it.max_depth < min_max_depth) {
+            std::fprintf(stderr, "%s: -m %s is too small (no light path holds a plane below a max depth of %u)\n", name, max_depth.c_str(), min_max_depth);
+            return false;
+        }
+        it.rr_depth = match_infinity(rr_depth);
+        it.light_streams = light_streams_mode;
+        it.device = device;
+        it.options = options;
+        return true;
+    };
     IntegratorPhotonBeams pbeams;
-    if (cmd == "photon-beams") {
-        if (refused("photon-beams", RL_STREAM_REFERENCE_ORDER, true)) return 2;
-        if (!parse_count("--nb-primitive", nb_primitive, &pbeams.nb_primitive)) return 2;
-        if (pbeams.nb_primitive > (uint32_t)RL_BEAM_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", nb_primitive.c_str(), (int)RL_BEAM_MAX); return 2; }
-        if (!parse_radius(&pbeams.radius)) return 2;
-        const Medium m = parse_medium(medium);
-        if (m.sigma_a + m.sigma_s == 0.0f) { std::fprintf(stderr, "photon-beams: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n"); return 2; }
-        pbeams.max_depth = match_infinity(max_depth);
-        pbeams.rr_depth = match_infinity(rr_depth);
-        pbeams.light_streams = light_streams_mode;
-        pbeams.device = device;
-        pbeams.options = options;
-    }
-    // virtual-ray-lights: photon-beams' limits
+    if (cmd == "photon-beams" && !fill_beam_pass("photon-beams", pbeams, 0u)) return 2;
     IntegratorVirtualRayLights vrls;
-    if (cmd == "virtual-ray-lights") {
-        if (refused("virtual-ray-lights", RL_STREAM_REFERENCE_ORDER, true)) return 2;
-        if (!parse_count("--nb-primitive", nb_primitive, &vrls.nb_primitive)) return 2;
-        if (vrls.nb_primitive > (uint32_t)RL_BEAM_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", nb_primitive.c_str(), (int)RL_BEAM_MAX); return 2; }
-        if (!parse_radius(&vrls.radius)) return 2;
-        const Medium m = parse_medium(medium);
-        if (m.sigma_a + m.sigma_s == 0.0f) { std::fprintf(stderr, "virtual-ray-lights: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n"); return 2; }
-        vrls.max_depth = match_infinity(max_depth);
-        vrls.rr_depth = match_infinity(rr_depth);
-        vrls.light_streams = light_streams_mode;
-        vrls.device = device;
-        vrls.options = options;
-    }
-    // photon-planes: photon-beams' limits, and the depth below which no plane exists
+    if (cmd == "virtual-ray-lights" && !fill_beam_pass("virtual-ray-lights", vrls, 0u)) return 2;
     IntegratorPhotonPlanes pplanes;
-    if (cmd == "photon-planes") {
-        if (refused("photon-planes", RL_STREAM_REFERENCE_ORDER, true)) return 2;
-        if (!parse_count("--nb-primitive", nb_primitive, &pplanes.nb_primitive)) return 2;
-        if (pplanes.nb_primitive > (uint32_t)RL_BEAM_MAX) { std::fprintf(stderr, "invalid --nb-primitive: %s (1 .. %d)\n", nb_primitive.c_str(), (int)RL_BEAM_MAX); return 2; }
-        if (!parse_radius(&pplanes.radius)) return 2;
-        const Medium m = parse_medium(medium);
-        if (m.sigma_a + m.sigma_s == 0.0f) { std::fprintf(stderr, "photon-planes: the integrator needs a medium (add -m SIGMA_S[:SIGMA_A[:G]])\n"); return 2; }
-        pplanes.max_depth = match_infinity(max_depth);
-        if (pplanes.max_depth.has_value() && *pplanes.max_depth <= 3u) { std::fprintf(stderr, "photon-planes: -m %s is too small (no light path holds a plane below a max depth of 4)\n", max_depth.c_str()); return 2; }
-        pplanes.rr_depth = match_infinity(rr_depth);
-        pplanes.light_streams = light_streams_mode;
-        pplanes.device = device;
-        pplanes.options = options;
-    }
+    if (cmd == "photon-planes" && !fill_beam_pass("photon-planes", pplanes, 4u)) return 2;
     // plane-single needs the medium
     IntegratorSinglePlane plane;
     if (cmd == "plane-single") {

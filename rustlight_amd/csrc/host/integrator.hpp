@@ -71,9 +71,6 @@ template <class T, void (*Destroy)(T*)> struct HandleDeleter { void operator()(T
 template <class T, void (*Destroy)(T*)> using Handle = std::unique_ptr<T, HandleDeleter<T, Destroy>>;
 using ContextHandle = Handle<rl_context, rl_context_destroy>;
 using VplSetHandle = Handle<rl_vpl_set, rl_vpl_destroy>;
-using PhotonMapHandle = Handle<rl_photon_map, rl_photon_map_destroy>;
-using PlaneSetHandle = Handle<rl_plane_set, rl_plane_destroy>;
-using PlaneMapHandle = Handle<rl_plane_map, rl_plane_map_destroy>;
 inline ContextHandle create_context(const Scene& scene, int device) {
     rl_context* c = nullptr;
     check(rl_context_create(scene.handle, device, &c), "rl_context_create");
@@ -336,6 +333,35 @@ struct IntegratorVPL {
     }
 };
 
+// compute of the integrators that gather a map of light-pass records, written once: generate(&set) on the main sampler, build(set, &map), the block seeds from
+// the sampler the generation leaves, `render` on reference-order streams into ctx.img.  Set and map are destroyed with the call, also when a later step throws;
+// every message stands under `what`.
+template <class Set, class Map, class Generate, class Build>
+BufferCollection compute_with_map(RenderContext& ctx, IndependentSampler& sampler, const Scene& scene, const char* what, Generate&& generate, void (*destroy_set)(Set*), Build&& build,
+                                  void (*destroy_map)(Map*), int (*render)(rl_context*, const Map*, uint32_t, int32_t, uint32_t, uint32_t, const uint64_t*, size_t, float*, rl_render_stats*),
+                                  rl_render_stats* last_stats) {
+    Set* generated = nullptr;
+    check(generate(&generated), what);
+    const std::unique_ptr<Set, void (*)(Set*)> set(generated, destroy_set);
+    Map* built = nullptr;
+    check(build(set.get(), &built), what);
+    const std::unique_ptr<Map, void (*)(Map*)> map(built, destroy_map);
+    const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
+    check(render(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), last_stats), what);
+    return std::move(ctx.img);
+}
+// the light paths' parameters of IntegratorVolPrimitives and the three structs made of it: `self`'s depths, the reference's stream order
+template <class Self>
+rl_path_params light_path_params(const Self& self, const IndependentSampler& sampler) {
+    rl_path_params p;
+    rl_path_params_default(&p);
+    p.has_max_depth = self.max_depth.has_value(); p.max_depth = self.max_depth.value_or(0);
+    p.has_rr_depth = self.rr_depth.has_value(); p.rr_depth = self.rr_depth.value_or(0);
+    p.stream_mode = RL_STREAM_REFERENCE_ORDER;
+    p.seed_variant = sampler.variant;
+    return p;
+}
+
 // struct IntegratorVolPrimitives { nb_primitive, max_depth, rr_depth, primitives } (src/integrators/explicit/vol_primitives.rs:12-24) + Integrator::compute
 // for the beam radiance estimate, seed for seed the reference: the photons from the main sampler (rl_vpl_generate with RL_VPL_VOLUME: the records convert_photons
 // stores), the photon tree (rl_photon_map_build), the block seeds from the sampler the generation leaves, the gather on reference-order streams (rl_render_bre).
@@ -356,28 +382,35 @@ struct IntegratorVolPrimitives {
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
         if (primitives != VolPrimitivies::BRE) throw std::runtime_error("vol-primitives: only the beam radiance estimate (bre) is built");
         RenderContext ctx(scene, device, options);
-        rl_path_params p;
-        rl_path_params_default(&p);
-        p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
-        p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
-        p.stream_mode = RL_STREAM_REFERENCE_ORDER;
-        p.seed_variant = sampler.variant;
-        const VplSetHandle photons = generate_light_records(light_streams, ctx, p, nb_primitive, RL_VPL_VOLUME, sampler, &last_generation_stats, "vol-primitives");
-        rl_photon_map* built = nullptr;
-        check(tree_build == TreeBuild::Device ? rl_photon_map_build_device(ctx, photons.get(), radius, &built, nullptr) : rl_photon_map_build(ctx, photons.get(), radius, &built), "vol-primitives");
-        const PhotonMapHandle map(built);
-        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
-        check(rl_render_bre(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "vol-primitives");
-        return std::move(ctx.img);
+        const rl_path_params p = light_path_params(*this, sampler);
+        return compute_with_map(ctx, sampler, scene, "vol-primitives",
+            [&](rl_vpl_set** out) { return (light_streams == LightStreams::PerPath ? rl_vpl_generate_paths : rl_vpl_generate)(ctx, &p, nb_primitive, RL_VPL_VOLUME, &sampler.rnd, out, &last_generation_stats); },
+            rl_vpl_destroy,
+            [&](const rl_vpl_set* photons, rl_photon_map** out) {
+                return tree_build == TreeBuild::Device ? rl_photon_map_build_device(ctx, photons, radius, out, nullptr) : rl_photon_map_build(ctx, photons, radius, out);
+            },
+            rl_photon_map_destroy, rl_render_bre, &last_stats);
     }
 };
+
+// compute of the three structs below, which have the same fields: the context, light_path_params, then compute_with_map over the beam or plane pass of
+// `self.light_streams` (generate / generate_paths), `build` at self.radius and `render`
+template <class Self, class Set, class Map>
+BufferCollection compute_beam_pass(Self& self, IndependentSampler& sampler, Scene& scene, const char* what,
+                                   int (*generate)(rl_context*, const rl_path_params*, uint32_t, rl_sampler*, Set**, rl_render_stats*), decltype(generate) generate_paths,
+                                   void (*destroy_set)(Set*), int (*build)(rl_context*, const Set*, float, Map**), void (*destroy_map)(Map*),
+                                   int (*render)(rl_context*, const Map*, uint32_t, int32_t, uint32_t, uint32_t, const uint64_t*, size_t, float*, rl_render_stats*)) {
+    RenderContext ctx(scene, self.device, self.options);
+    const rl_path_params p = light_path_params(self, sampler);
+    return compute_with_map(ctx, sampler, scene, what,
+        [&](Set** out) { return (self.light_streams == LightStreams::PerPath ? generate_paths : generate)(ctx, &p, self.nb_primitive, &sampler.rnd, out, &self.last_generation_stats); },
+        destroy_set, [&](const Set* set, Map** out) { return build(ctx, set, self.radius, out); }, destroy_map, render, &self.last_stats);
+}
 
 // IntegratorVolPrimitives with primitives = Beams (vol_primitives.rs:437-523, 608-790) as a struct of its own — IntegratorVolPrimitives above keeps refusing every
 // primitive but BRE, and nothing above refers to this one — + Integrator::compute, seed for seed the reference: the beams from the main sampler
 // (rl_beam_generate: the light paths of rl_vpl_generate stored by convert_beams(false, ..)), the split and the beam tree (rl_beam_map_build), the block seeds
 // from the sampler the generation leaves, the gather on reference-order streams (rl_render_beams).  light_streams = PerPath: rl_beam_generate_paths.
-using BeamSetHandle = Handle<rl_beam_set, rl_beam_destroy>;
-using BeamMapHandle = Handle<rl_beam_map, rl_beam_map_destroy>;
 struct IntegratorPhotonBeams {
     uint32_t nb_primitive = 128;
     std::optional<uint32_t> max_depth, rr_depth = 0u;
@@ -387,32 +420,14 @@ struct IntegratorPhotonBeams {
     Options options;
     rl_render_stats last_stats{}, last_generation_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
-        RenderContext ctx(scene, device, options);
-        rl_path_params p;
-        rl_path_params_default(&p);
-        p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
-        p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
-        p.stream_mode = RL_STREAM_REFERENCE_ORDER;
-        p.seed_variant = sampler.variant;
-        rl_beam_set* generated = nullptr;
-        check((light_streams == LightStreams::PerPath ? rl_beam_generate_paths : rl_beam_generate)(ctx, &p, nb_primitive, &sampler.rnd, &generated, &last_generation_stats), "photon-beams");
-        const BeamSetHandle beams(generated);
-        rl_beam_map* built = nullptr;
-        check(rl_beam_map_build(ctx, beams.get(), radius, &built), "photon-beams");
-        const BeamMapHandle map(built);
-        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
-        check(rl_render_beams(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "photon-beams");
-        return std::move(ctx.img);
+        return compute_beam_pass(*this, sampler, scene, "photon-beams", rl_beam_generate, rl_beam_generate_paths, rl_beam_destroy, rl_beam_map_build, rl_beam_map_destroy, rl_render_beams);
     }
 };
 
 // IntegratorVolPrimitives with primitives = Planes (vol_primitives.rs:256-435, 608-790) as a struct of its own, for the reason IntegratorPhotonBeams is one, +
-// Integrator::compute, seed for seed the reference, with IntegratorPhotonBeams' host sequence: the surface beams and the planes from the main sampler
-// (rl_pplane_generate: the light paths of rl_beam_generate stored by convert_beams(true, ..) and convert_planes), the split and the two trees
-// (rl_pplane_map_build), the block seeds from the sampler the generation leaves, the gather on reference-order streams (rl_render_photon_planes).
-// light_streams = PerPath: rl_pplane_generate_paths.
-using PPlaneSetHandle = Handle<rl_pplane_set, rl_pplane_destroy>;
-using PPlaneMapHandle = Handle<rl_pplane_map, rl_pplane_map_destroy>;
+// Integrator::compute, seed for seed the reference: the surface beams and the planes from the main sampler (rl_pplane_generate: the light paths of
+// rl_beam_generate stored by convert_beams(true, ..) and convert_planes), the split and the two trees (rl_pplane_map_build), the block seeds from the sampler
+// the generation leaves, the gather on reference-order streams (rl_render_photon_planes).  light_streams = PerPath: rl_pplane_generate_paths.
 struct IntegratorPhotonPlanes {
     uint32_t nb_primitive = 128;
     std::optional<uint32_t> max_depth, rr_depth = 0u;
@@ -422,30 +437,15 @@ struct IntegratorPhotonPlanes {
     Options options;
     rl_render_stats last_stats{}, last_generation_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
-        RenderContext ctx(scene, device, options);
-        rl_path_params p;
-        rl_path_params_default(&p);
-        p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
-        p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
-        p.stream_mode = RL_STREAM_REFERENCE_ORDER;
-        p.seed_variant = sampler.variant;
-        rl_pplane_set* generated = nullptr;
-        check((light_streams == LightStreams::PerPath ? rl_pplane_generate_paths : rl_pplane_generate)(ctx, &p, nb_primitive, &sampler.rnd, &generated, &last_generation_stats), "photon-planes");
-        const PPlaneSetHandle records(generated);
-        rl_pplane_map* built = nullptr;
-        check(rl_pplane_map_build(ctx, records.get(), radius, &built), "photon-planes");
-        const PPlaneMapHandle map(built);
-        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
-        check(rl_render_photon_planes(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "photon-planes");
-        return std::move(ctx.img);
+        return compute_beam_pass(*this, sampler, scene, "photon-planes", rl_pplane_generate, rl_pplane_generate_paths, rl_pplane_destroy, rl_pplane_map_build, rl_pplane_map_destroy,
+                                 rl_render_photon_planes);
     }
 };
 
 // IntegratorVolPrimitives with primitives = VRL (vol_primitives.rs:201-253, 608-699, 741-764) as a struct of its own, for the reason IntegratorPhotonBeams is one,
-// + Integrator::compute, seed for seed the reference, with IntegratorPhotonBeams' host sequence: the beams from the main sampler (rl_beam_generate: the VRL arm
-// shoots what the Beams arm shoots), the partition by from_surface with the surface beams' split and tree (rl_vrl_map_build), the block seeds from the sampler
-// the generation leaves, the chain pass and the gather on reference-order streams (rl_render_vrl).  light_streams = PerPath: rl_beam_generate_paths.
-using VrlMapHandle = Handle<rl_vrl_map, rl_vrl_map_destroy>;
+// + Integrator::compute, seed for seed the reference: the beams from the main sampler (rl_beam_generate: the VRL arm shoots what the Beams arm shoots), the
+// partition by from_surface with the surface beams' split and tree (rl_vrl_map_build), the block seeds from the sampler the generation leaves, the chain pass
+// and the gather on reference-order streams (rl_render_vrl).  light_streams = PerPath: rl_beam_generate_paths.
 struct IntegratorVirtualRayLights {
     uint32_t nb_primitive = 128;
     std::optional<uint32_t> max_depth, rr_depth = 0u;
@@ -455,22 +455,7 @@ struct IntegratorVirtualRayLights {
     Options options;
     rl_render_stats last_stats{}, last_generation_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
-        RenderContext ctx(scene, device, options);
-        rl_path_params p;
-        rl_path_params_default(&p);
-        p.has_max_depth = max_depth.has_value(); p.max_depth = max_depth.value_or(0);
-        p.has_rr_depth = rr_depth.has_value(); p.rr_depth = rr_depth.value_or(0);
-        p.stream_mode = RL_STREAM_REFERENCE_ORDER;
-        p.seed_variant = sampler.variant;
-        rl_beam_set* generated = nullptr;
-        check((light_streams == LightStreams::PerPath ? rl_beam_generate_paths : rl_beam_generate)(ctx, &p, nb_primitive, &sampler.rnd, &generated, &last_generation_stats), "virtual-ray-lights");
-        const BeamSetHandle beams(generated);
-        rl_vrl_map* built = nullptr;
-        check(rl_vrl_map_build(ctx, beams.get(), radius, &built), "virtual-ray-lights");
-        const VrlMapHandle map(built);
-        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
-        check(rl_render_vrl(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "virtual-ray-lights");
-        return std::move(ctx.img);
+        return compute_beam_pass(*this, sampler, scene, "virtual-ray-lights", rl_beam_generate, rl_beam_generate_paths, rl_beam_destroy, rl_vrl_map_build, rl_vrl_map_destroy, rl_render_vrl);
     }
 };
 
@@ -490,17 +475,11 @@ struct IntegratorSinglePlane {
     rl_render_stats last_stats{}, last_generation_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
         RenderContext ctx(scene, device, options);
-        rl_plane_set* generated = nullptr;
         if (generate == PlaneGenerate::Lanes) check(rl_context_set_option(ctx, "plane_generate_lanes", "1"), "plane-single");
         if (tree_build == TreeBuild::Device) check(rl_context_set_option(ctx, "plane_tree_device", "1"), "plane-single");
-        check(rl_plane_generate(ctx, nb_primitive, strategy, &sampler.rnd, &generated, &last_generation_stats), "plane-single");
-        const PlaneSetHandle planes(generated);
-        rl_plane_map* built = nullptr;
-        check(rl_plane_map_build(ctx, planes.get(), &built), "plane-single");
-        const PlaneMapHandle map(built);
-        const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
-        check(rl_render_plane_single(ctx, map.get(), (uint32_t)scene.nb_samples, sampler.variant, 0, 1, seeds.data(), seeds.size(), ctx.img.primal.data(), &last_stats), "plane-single");
-        return std::move(ctx.img);
+        return compute_with_map(ctx, sampler, scene, "plane-single",
+            [&](rl_plane_set** out) { return rl_plane_generate(ctx, nb_primitive, strategy, &sampler.rnd, out, &last_generation_stats); }, rl_plane_destroy,
+            [&](const rl_plane_set* planes, rl_plane_map** out) { return rl_plane_map_build(ctx, planes, out); }, rl_plane_map_destroy, rl_render_plane_single, &last_stats);
     }
 };
 

@@ -28,6 +28,29 @@ static void unpack_tree_nodes(const std::vector<float4>& h_nodes, size_t n_nodes
         node_links[3 * i] = skip; node_links[3 * i + 1] = fc >> 3; node_links[3 * i + 2] = fc & 7u;
     }
 }
+// a tree's nodes and its elements in leaf order, to the current device ...
+static int upload_tree(const std::vector<float4>& h_nodes, const std::vector<float4>& h_elements, HipBuffer<float4>* nodes, HipBuffer<float4>* elements) {
+    int rcode;
+    if ((rcode = nodes->ensure(h_nodes.size())) != RL_OK || (rcode = elements->ensure(h_elements.size())) != RL_OK) return rcode;
+    HIP_OK(hipMemcpy(nodes->get(), h_nodes.data(), h_nodes.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(elements->get(), h_elements.data(), h_elements.size() * sizeof(float4), hipMemcpyHostToDevice));
+    return RL_OK;
+}
+// ... and back from it: the nodes unpacked, the n_quads float4 of the elements as they are
+static int read_tree(const HipBuffer<float4>& nodes, size_t n_nodes, const HipBuffer<float4>& elements, size_t n_quads, float* node_boxes, uint32_t* node_links, float* out) {
+    std::vector<float4> h_nodes(2 * n_nodes);
+    HIP_OK(hipMemcpy(h_nodes.data(), nodes.get(), h_nodes.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out, elements.get(), n_quads * sizeof(float4), hipMemcpyDeviceToHost));
+    unpack_tree_nodes(h_nodes, n_nodes, node_boxes, node_links);
+    return RL_OK;
+}
+// what every rl_*_destroy of a set or a map on a device does
+template <class T>
+static void destroy_handle(T* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    delete h;
+}
 
 // What the two gathers do not share beyond their constants and their launch
 struct GatherKind {
@@ -124,9 +147,7 @@ extern "C" int rl_photon_map_build(rl_context* ctx, const rl_vpl_set* set, float
     }
     auto map = std::make_unique<rl_photon_map>();
     map->ctx = ctx; map->device = ctx->device;
-    if ((rcode = map->nodes.ensure(h_nodes.size())) != RL_OK || (rcode = map->photons.ensure(h_photons.size())) != RL_OK) return rcode;
-    HIP_OK(hipMemcpy(map->nodes.get(), h_nodes.data(), h_nodes.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(map->photons.get(), h_photons.data(), h_photons.size() * sizeof(float4), hipMemcpyHostToDevice));
+    if ((rcode = upload_tree(h_nodes, h_photons, &map->nodes, &map->photons)) != RL_OK) return rcode;
     map->n_photons = set->n_vpl; map->n_nodes = n_nodes; map->n_paths = set->n_paths; map->radius = radius;
     *out = map.release();
     return RL_OK;
@@ -215,11 +236,7 @@ extern "C" int rl_photon_map_info(const rl_photon_map* map, uint64_t* n_photons,
     if (radius) *radius = map->radius;
     return RL_OK;
 }
-extern "C" void rl_photon_map_destroy(rl_photon_map* map) {
-    if (!map) return;
-    (void)hipSetDevice(map->device);
-    delete map;
-}
+extern "C" void rl_photon_map_destroy(rl_photon_map* map) { destroy_handle(map); }
 extern "C" int rl_render_bre(rl_context* ctx, const rl_photon_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
                              const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats) {
     if (!map) return RL_ERR_INVALID_ARGUMENT;
@@ -507,17 +524,9 @@ extern "C" int rl_plane_map_read(const rl_plane_map* map, size_t node_capacity, 
     if (!map || !node_boxes || !node_links || !planes) return RL_ERR_INVALID_ARGUMENT;
     if (node_capacity < map->n_nodes || plane_capacity < map->n_planes) { rl_set_error("rl_plane_map_read: a capacity is too small"); return RL_ERR_INVALID_ARGUMENT; }
     HIP_OK(hipSetDevice(map->device));
-    std::vector<float4> h_nodes(2 * (size_t)map->n_nodes);
-    HIP_OK(hipMemcpy(h_nodes.data(), map->nodes.get(), h_nodes.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(planes, map->planes.get(), (size_t)map->n_planes * 4 * sizeof(float4), hipMemcpyDeviceToHost));
-    unpack_tree_nodes(h_nodes, (size_t)map->n_nodes, node_boxes, node_links);
-    return RL_OK;
+    return read_tree(map->nodes, (size_t)map->n_nodes, map->planes, (size_t)map->n_planes * 4, node_boxes, node_links, planes);
 }
-extern "C" void rl_plane_map_destroy(rl_plane_map* map) {
-    if (!map) return;
-    (void)hipSetDevice(map->device);
-    delete map;
-}
+extern "C" void rl_plane_map_destroy(rl_plane_map* map) { destroy_handle(map); }
 extern "C" int rl_render_plane_single(rl_context* ctx, const rl_plane_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
                                       const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats) {
     if (!map) return RL_ERR_INVALID_ARGUMENT;

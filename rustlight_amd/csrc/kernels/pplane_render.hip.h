@@ -1,6 +1,6 @@
 // pplane_render.hip.h — the host side of the photon planes (included by wavefront.hip after beam_render.hip.h; host code only): the plane pass (rl_pplane_generate,
 // rl_pplane_generate_paths: the light-pass sequences of the beam pass with a second record array, over k_pplane_generate / k_pplane_shoot, pplanegen.hip.h), the
-// map of two trees (rl_pplane_map_*: the surface beams through split_beams / build_beam_tree, the planes through the plane tree of plane-single, on the host or —
+// map of two trees (rl_pplane_map_*: the surface beams into a BeamHalf, beam_render.hip.h, the planes through the plane tree of plane-single, on the host or —
 // option pplane_tree_device — by plane_tree_run's kernels) and rl_render_photon_planes, which goes through render_gather with k_pplane_gather (pplane.hip.h).
 // IntegratorVolPrimitives with primitives = Planes: src/integrators/explicit/vol_primitives.rs:256-435, 608-790.
 
@@ -14,21 +14,17 @@ struct rl_pplane_set {
 struct rl_pplane_map {
     const rl_context* ctx;
     int device;
-    HipBuffer<float4> beam_nodes;     // [n_beam_nodes][2]
-    HipBuffer<float4> beams;          // [n_sub][3], in leaf order
+    BeamHalf half;                    // the surface beams' sub-beams and the beam tree over them
     HipBuffer<float4> plane_nodes;    // [n_plane_nodes][2]
     HipBuffer<float4> planes;         // [n_planes][4], in leaf order
-    uint64_t n_beams = 0, n_sub = 0, n_beam_nodes = 0, n_planes = 0, n_plane_nodes = 0, n_paths = 0;
+    uint64_t n_beams = 0, n_planes = 0, n_plane_nodes = 0, n_paths = 0;
     float radius = 0.0f;
 };
 static const LightPassKind kPPlanePass{RL_PLANE_WORDS, "photon-planes: fewer than nb_primitive planes stored within RL_VPL_MAX_PATHS light paths"};
 static constexpr unsigned kPPlaneBeamMax = (unsigned)RL_BEAM_MAX + kDepthCap;      // the surface beams a plane pass may store before its last path
 static const char* const kPPlaneTooManyBeams =
     "photon-planes: more than RL_BEAM_MAX + 2048 surface beams arose before nb_primitive planes were stored (the medium scatters too seldom for this nb_primitive)";
-static int check_pplane_scene(const rl_context* ctx) {
-    if (ctx->ds.medium.enabled == 0) { rl_set_error("photon planes need a medium (add -m; the reference panics, vol_primitives.rs:575)"); return RL_ERR_UNSUPPORTED; }
-    return RL_OK;
-}
+static int check_pplane_scene(const rl_context* ctx) { return check_medium(ctx, "photon planes"); }
 // what both generation entry points refuse before any kernel runs: what check_beam_generate refuses, with its codes, and a depth limit under which no plane exists
 static int check_pplane_generate(const rl_context* ctx, const rl_path_params* params, uint32_t nb_primitive, const rl_sampler* sampler, rl_pplane_set** out) {
     if (!ctx || !params || !sampler || !out) return RL_ERR_INVALID_ARGUMENT;
@@ -42,40 +38,26 @@ static int check_pplane_generate(const rl_context* ctx, const rl_path_params* pa
     if (ctx->has_directional) { rl_set_error("photon planes do not take a directional light (with a medium the light paths of vpl refuse it)"); return RL_ERR_UNSUPPORTED; }
     return RL_OK;
 }
-static PPlaneGenConst pplane_gen_const(const LightPassSecond& second) {
-    PPlaneGenConst xc{};
-    xc.beam_words = second.d_words; xc.beam_cap = second.cap; xc.beam_max = second.max_records; xc.beam_offsets = second.d_offsets;
-    return xc;
+static int pplane_generate(bool per_path, rl_context* ctx, const rl_path_params* params, uint32_t nb_primitive, rl_sampler* sampler, rl_pplane_set** out, rl_render_stats* stats) {
+    int rcode;
+    if ((rcode = check_pplane_generate(ctx, params, nb_primitive, sampler, out)) != RL_OK) return rcode;
+    HIP_OK(hipSetDevice(ctx->device));
+    auto set = new_handle<rl_pplane_set>(ctx);
+    LightPassSecond second{RL_BEAM_WORDS, kPPlaneBeamMax, kPPlaneTooManyBeams, &set->beams, &set->n_beams};
+    if ((rcode = light_pass(per_path, ctx, params, nb_primitive, kPPlanePass, sampler, &set->planes, &set->n_planes, &set->n_paths, stats, &second,
+                            [&](int which, unsigned groups, size_t lds, const RenderConst& rc, const StackConf& stc, const VplConst& vc, const VplPathsConst& pc) {
+            PPlaneGenConst xc{};
+            xc.beam_words = second.d_words; xc.beam_cap = second.cap; xc.beam_max = second.max_records; xc.beam_offsets = second.d_offsets;
+            (ctx->lds_scene ? launch_pplanegen_lds : launch_pplanegen_stream)(which, ctx->single_bsdf ? ctx->bsdf_type : -1, dim3(groups), dim3(256), lds, ctx->stream, rc, ctx->ds, stc, vc, pc, xc);
+        })) != RL_OK) return rcode;
+    *out = set.release();
+    return RL_OK;
 }
 extern "C" int rl_pplane_generate(rl_context* ctx, const rl_path_params* params, uint32_t nb_primitive, rl_sampler* sampler, rl_pplane_set** out, rl_render_stats* stats) {
-    int rcode;
-    if ((rcode = check_pplane_generate(ctx, params, nb_primitive, sampler, out)) != RL_OK) return rcode;
-    HIP_OK(hipSetDevice(ctx->device));
-    auto set = std::make_unique<rl_pplane_set>();
-    set->ctx = ctx; set->device = ctx->device;
-    LightPassSecond second{RL_BEAM_WORDS, kPPlaneBeamMax, kPPlaneTooManyBeams, &set->beams, &set->n_beams};
-    if ((rcode = light_pass_serial(ctx, params, nb_primitive, RL_VPL_ALL, kPPlanePass, sampler, &set->planes, &set->n_planes, &set->n_paths, stats,
-                                   [&](size_t lds, const RenderConst& rc, const StackConf& stc, const VplConst& vc) {
-            (ctx->lds_scene ? launch_pplanegen_lds : launch_pplanegen_stream)(0, ctx->single_bsdf ? ctx->bsdf_type : -1, dim3(1), dim3(256), lds, ctx->stream, rc, ctx->ds, stc, vc,
-                                                                              VplPathsConst{}, pplane_gen_const(second));
-        }, &second)) != RL_OK) return rcode;
-    *out = set.release();
-    return RL_OK;
+    return pplane_generate(false, ctx, params, nb_primitive, sampler, out, stats);
 }
 extern "C" int rl_pplane_generate_paths(rl_context* ctx, const rl_path_params* params, uint32_t nb_primitive, rl_sampler* sampler, rl_pplane_set** out, rl_render_stats* stats) {
-    int rcode;
-    if ((rcode = check_pplane_generate(ctx, params, nb_primitive, sampler, out)) != RL_OK) return rcode;
-    HIP_OK(hipSetDevice(ctx->device));
-    auto set = std::make_unique<rl_pplane_set>();
-    set->ctx = ctx; set->device = ctx->device;
-    LightPassSecond second{RL_BEAM_WORDS, kPPlaneBeamMax, kPPlaneTooManyBeams, &set->beams, &set->n_beams};
-    if ((rcode = light_pass_paths(ctx, params, nb_primitive, RL_VPL_ALL, kPPlanePass, sampler, &set->planes, &set->n_planes, &set->n_paths, stats,
-                                  [&](bool write, unsigned groups, size_t lds, const RenderConst& rc, const StackConf& stc, const VplPathsConst& pc) {
-            (ctx->lds_scene ? launch_pplanegen_lds : launch_pplanegen_stream)(write ? 2 : 1, ctx->single_bsdf ? ctx->bsdf_type : -1, dim3(groups), dim3(256), lds, ctx->stream, rc, ctx->ds,
-                                                                              stc, VplConst{}, pc, pplane_gen_const(second));
-        }, &second)) != RL_OK) return rcode;
-    *out = set.release();
-    return RL_OK;
+    return pplane_generate(true, ctx, params, nb_primitive, sampler, out, stats);
 }
 extern "C" int rl_pplane_info(const rl_pplane_set* set, uint64_t* n_planes, uint64_t* n_beams, uint64_t* n_paths) {
     if (!set) return RL_ERR_INVALID_ARGUMENT;
@@ -91,11 +73,7 @@ extern "C" int rl_pplane_read(const rl_pplane_set* set, uint32_t* plane_words, s
     HIP_OK(hipMemcpy(beam_words, set->beams.get(), n_beam_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RL_OK;
 }
-extern "C" void rl_pplane_destroy(rl_pplane_set* set) {
-    if (!set) return;
-    (void)hipSetDevice(set->device);
-    delete set;
-}
+extern "C" void rl_pplane_destroy(rl_pplane_set* set) { destroy_handle(set); }
 // both trees.  The beams are host records.  The planes are host records (plane_words), or records on the device (d_plane_words, plane_words NULL) when the
 // device build is to read a set in place.  Words 16 and 17 of a plane record are 0: a caller's record that sets them is refused, so that the type word the
 // device build packs beside d1 is the 0 the host build packs and both builds give the same bytes.
@@ -108,27 +86,10 @@ static int pplane_map_build(rl_context* ctx, const uint32_t* beam_words, size_t 
     if (plane_words)
         for (size_t i = 0; i < n_planes; i++)
             if (plane_words[i * RL_PLANE_WORDS + 16] | plane_words[i * RL_PLANE_WORDS + 17]) { rl_set_error("words 16 and 17 of a photon-plane record must be 0"); return RL_ERR_INVALID_ARGUMENT; }
-    // ---- the surface beams: split and beam tree, as rl_beam_map_build_words
-    std::vector<uint32_t> sub;
-    ElementTree beam_tree;
-    if ((rcode = split_beams(beam_words, n_beams, &sub)) != RL_OK) return rcode;
-    const size_t n_sub = sub.size() / RL_BEAM_WORDS;
-    if ((rcode = build_beam_tree(sub.data(), n_sub, radius, &beam_tree)) != RL_OK) return rcode;
-    const std::vector<float4> h_beam_nodes = pack_tree_nodes(beam_tree);
-    std::vector<float4> h_beams(3 * n_sub);
-    for (size_t i = 0; i < n_sub; i++) {
-        float f[RL_BEAM_WORDS];
-        std::memcpy(f, &sub[(size_t)beam_tree.order[i] * RL_BEAM_WORDS], sizeof f);       // o, length | d, flags | radiance, path
-        h_beams[3 * i] = make_float4(f[0], f[1], f[2], f[3]);
-        h_beams[3 * i + 1] = make_float4(f[4], f[5], f[6], 0.0f);
-        h_beams[3 * i + 2] = make_float4(f[8], f[9], f[10], 0.0f);
-    }
-    HIP_OK(hipSetDevice(ctx->device));
-    auto map = std::make_unique<rl_pplane_map>();
-    map->ctx = ctx; map->device = ctx->device;
-    if ((rcode = map->beam_nodes.ensure(h_beam_nodes.size())) != RL_OK || (rcode = map->beams.ensure(h_beams.size())) != RL_OK) return rcode;
-    HIP_OK(hipMemcpy(map->beam_nodes.get(), h_beam_nodes.data(), h_beam_nodes.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(map->beams.get(), h_beams.data(), h_beams.size() * sizeof(float4), hipMemcpyHostToDevice));
+    // ---- the surface beams: split and beam tree
+    auto map = new_handle<rl_pplane_map>(ctx);
+    BeamHalfHost host;                                      // lives until the plane half is built too
+    if ((rcode = beam_half_build(&map->half, &host, ctx->device, beam_words, n_beams, radius)) != RL_OK) return rcode;
     // ---- the planes: plane-single's tree over the same geometry layout
     size_t n_plane_nodes = 0;
     if (knob_on(ctx, K_PPLANE_TREE_DEVICE) && n_planes > 0) {
@@ -157,12 +118,9 @@ static int pplane_map_build(rl_context* ctx, const uint32_t* beam_words, size_t 
             h_planes[4 * i + 2] = make_float4(f[6], f[7], f[8], 0.0f);
             h_planes[4 * i + 3] = make_float4(f[11], f[12], f[13], 0.0f);
         }
-        if ((rcode = map->plane_nodes.ensure(h_nodes.size())) != RL_OK || (rcode = map->planes.ensure(h_planes.size())) != RL_OK) return rcode;
-        HIP_OK(hipMemcpy(map->plane_nodes.get(), h_nodes.data(), h_nodes.size() * sizeof(float4), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(map->planes.get(), h_planes.data(), h_planes.size() * sizeof(float4), hipMemcpyHostToDevice));
+        if ((rcode = upload_tree(h_nodes, h_planes, &map->plane_nodes, &map->planes)) != RL_OK) return rcode;
     }
-    map->n_beams = n_beams; map->n_sub = n_sub; map->n_beam_nodes = beam_tree.n_nodes(); map->n_planes = n_planes; map->n_plane_nodes = n_plane_nodes;
-    map->n_paths = n_paths; map->radius = radius;
+    map->n_beams = n_beams; map->n_planes = n_planes; map->n_plane_nodes = n_plane_nodes; map->n_paths = n_paths; map->radius = radius;
     *out = map.release();
     return RL_OK;
 }
@@ -175,15 +133,11 @@ extern "C" int rl_pplane_map_build_words(rl_context* ctx, const uint32_t* beam_w
 extern "C" int rl_pplane_map_build(rl_context* ctx, const rl_pplane_set* set, float radius, rl_pplane_map** out) {
     if (!ctx || !set || !out) return RL_ERR_INVALID_ARGUMENT;
     *out = nullptr;
-    if (set->ctx != ctx) { rl_set_error("the photon-plane set belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
-    HIP_OK(hipSetDevice(ctx->device));
-    std::vector<uint32_t> beams((size_t)set->n_beams * RL_BEAM_WORDS), planes;
-    HIP_OK(hipMemcpy(beams.data(), set->beams.get(), beams.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    int rcode;
+    std::vector<uint32_t> beams, planes;
+    if ((rcode = set_words_to_host(ctx, set->ctx, "photon-plane set", set->beams, (size_t)set->n_beams * RL_BEAM_WORDS, &beams)) != RL_OK) return rcode;
     const bool in_place = knob_on(ctx, K_PPLANE_TREE_DEVICE) && set->n_planes > 0;      // the device build reads the set's planes where they are
-    if (!in_place) {
-        planes.resize((size_t)set->n_planes * RL_PLANE_WORDS);
-        HIP_OK(hipMemcpy(planes.data(), set->planes.get(), planes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
+    if (!in_place && (rcode = set_words_to_host(ctx, set->ctx, "photon-plane set", set->planes, (size_t)set->n_planes * RL_PLANE_WORDS, &planes)) != RL_OK) return rcode;
     return pplane_map_build(ctx, beams.data(), (size_t)set->n_beams, in_place ? nullptr : planes.data(), (size_t)set->n_planes, in_place ? set->planes.get() : nullptr, set->n_paths,
                             radius, out);
 }
@@ -191,8 +145,8 @@ extern "C" int rl_pplane_map_info(const rl_pplane_map* map, uint64_t* n_beams, u
                                   uint64_t* n_paths, float* radius) {
     if (!map) return RL_ERR_INVALID_ARGUMENT;
     if (n_beams) *n_beams = map->n_beams;
-    if (n_sub) *n_sub = map->n_sub;
-    if (n_beam_nodes) *n_beam_nodes = map->n_beam_nodes;
+    if (n_sub) *n_sub = map->half.n_sub;
+    if (n_beam_nodes) *n_beam_nodes = map->half.n_nodes;
     if (n_planes) *n_planes = map->n_planes;
     if (n_plane_nodes) *n_plane_nodes = map->n_plane_nodes;
     if (n_paths) *n_paths = map->n_paths;
@@ -202,20 +156,13 @@ extern "C" int rl_pplane_map_info(const rl_pplane_map* map, uint64_t* n_beams, u
 // which: 0 = the beam tree and the sub-beams ([n_sub][12] f32), 1 = the plane tree and the planes ([n_planes][16] f32)
 extern "C" int rl_pplane_map_read(const rl_pplane_map* map, int which, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t element_capacity, float* elements) {
     if (!map || !node_boxes || !node_links || !elements || which < 0 || which > 1) return RL_ERR_INVALID_ARGUMENT;
-    const size_t n_nodes = (size_t)(which ? map->n_plane_nodes : map->n_beam_nodes), n_elements = (size_t)(which ? map->n_planes : map->n_sub);
+    const size_t n_nodes = (size_t)(which ? map->n_plane_nodes : map->half.n_nodes), n_elements = (size_t)(which ? map->n_planes : map->half.n_sub);
     if (node_capacity < n_nodes || element_capacity < n_elements) { rl_set_error("rl_pplane_map_read: a capacity is too small"); return RL_ERR_INVALID_ARGUMENT; }
     HIP_OK(hipSetDevice(map->device));
-    std::vector<float4> h_nodes(2 * n_nodes);
-    HIP_OK(hipMemcpy(h_nodes.data(), (which ? map->plane_nodes : map->beam_nodes).get(), h_nodes.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(elements, (which ? map->planes : map->beams).get(), n_elements * (which ? 4 : 3) * sizeof(float4), hipMemcpyDeviceToHost));
-    unpack_tree_nodes(h_nodes, n_nodes, node_boxes, node_links);
-    return RL_OK;
+    if (which) return read_tree(map->plane_nodes, n_nodes, map->planes, n_elements * 4, node_boxes, node_links, elements);
+    return beam_half_read(map->half, node_boxes, node_links, elements);
 }
-extern "C" void rl_pplane_map_destroy(rl_pplane_map* map) {
-    if (!map) return;
-    (void)hipSetDevice(map->device);
-    delete map;
-}
+extern "C" void rl_pplane_map_destroy(rl_pplane_map* map) { destroy_handle(map); }
 extern "C" int rl_render_photon_planes(rl_context* ctx, const rl_pplane_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
                                        const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats) {
     if (!map) return RL_ERR_INVALID_ARGUMENT;
@@ -225,10 +172,7 @@ extern "C" int rl_render_photon_planes(rl_context* ctx, const rl_pplane_map* map
     const int rcode = render_gather(ctx, kind, map->ctx, spp, seed_variant, shard_index, shard_count, block_seeds, n_blocks, out_rgb, stats,
                                     [&](bool lds_scene, dim3 grid, size_t lds, hipStream_t st, const RenderConst& rc, const StackConf& stc) {
         PPlaneConst pc{};
-        pc.beam.nodes = map->beam_nodes.get(); pc.beam.beams = map->beams.get(); pc.beam.n_nodes = (unsigned)map->n_beam_nodes;
-        pc.beam.radius2 = map->radius * map->radius;                            // self.radius * self.radius
-        pc.beam.half_inv_radius = 0.5f / map->radius;                           // 0.5 / self.radius
-        pc.beam.norm_photon = 1.0f / (float)map->n_paths;                       // 1.0 / nb_path_shot as f32 (vol_primitives.rs:707)
+        pc.beam = beam_half_const(map->half, map->radius, map->n_paths);
         pc.nodes = map->plane_nodes.get(); pc.planes = map->planes.get(); pc.n_nodes = (unsigned)map->n_plane_nodes;
         (lds_scene ? launch_pplane_lds : launch_pplane_stream)(grid, dim3(256), lds, st, rc, ctx->ds, stc, pc);
     });

@@ -1,22 +1,18 @@
 // vrl_render.hip.h — the host side of the virtual ray lights (included by wavefront.hip after beam_render.hip.h; host code only).  The beams are those of the
 // beam pass (rl_beam_generate / rl_beam_generate_paths: the reference's VRL arm calls convert_beams(false, ..) and stops on the same count).  rl_vrl_map_*: the
-// partition by from_surface (word 7 bit 0), avg and rr, the surface beams through split_beams / build_beam_tree; rl_render_vrl: render_gather's frame around
+// partition by from_surface (word 7 bit 0), avg and rr, the surface beams into a BeamHalf (beam_render.hip.h); rl_render_vrl: render_gather's frame around
 // two launches, k_vrl_chain and k_vrl_gather (vrl.hip.h).  IntegratorVolPrimitives with primitives = VRL: src/integrators/explicit/vol_primitives.rs:201-253,
 // 608-699, 741-764.
 
 struct rl_vrl_map {
     const rl_context* ctx;            // the context that made it (compared, never dereferenced)
     int device;
-    HipBuffer<float4> nodes;          // [n_nodes][2]: the beam tree over the surface beams' sub-beams
-    HipBuffer<float4> beams;          // [n_sub][3], in leaf order
+    BeamHalf half;                    // the surface beams' sub-beams and the beam tree over them
     HipBuffer<float4> vrls;           // [n_vrl][3]: o, length | d, rr | radiance, 0, in storing order
-    uint64_t n_surface = 0, n_sub = 0, n_nodes = 0, n_vrl = 0, n_paths = 0;
+    uint64_t n_surface = 0, n_vrl = 0, n_paths = 0;
     float radius = 0.0f, avg = 0.0f;
 };
-static int check_vrl_scene(const rl_context* ctx) {
-    if (ctx->ds.medium.enabled == 0) { rl_set_error("virtual ray lights need a medium (add -m; the reference panics, vol_primitives.rs:575)"); return RL_ERR_UNSUPPORTED; }
-    return RL_OK;
-}
+static int check_vrl_scene(const rl_context* ctx) { return check_medium(ctx, "virtual ray lights"); }
 // the worst case of a block's draws, every VRL surviving in every sample: what rng_advance's 32-bit count must hold
 static int check_vrl_draws(uint32_t spp, uint64_t n_vrl) {
     if (256ull * spp * (2ull + 3ull * n_vrl) >= (1ull << 32)) {
@@ -58,47 +54,28 @@ extern "C" int rl_vrl_map_build_words(rl_context* ctx, const uint32_t* words, si
         const float4 r = h_vrls[3 * i + 2];
         h_vrls[3 * i + 1].w = std::fmin((std::fmax(r.x, std::fmax(r.y, r.z)) / avg) * 0.01f, 1.0f);
     }
-    // ---- the surface beams: split and beam tree, as rl_beam_map_build_words (avg_split over the surface beams alone)
-    std::vector<uint32_t> sub;
-    ElementTree tree;
-    if ((rcode = split_beams(surface.data(), n_surface, &sub)) != RL_OK) return rcode;
-    const size_t n_sub = sub.size() / RL_BEAM_WORDS;
-    if ((rcode = build_beam_tree(sub.data(), n_sub, radius, &tree)) != RL_OK) return rcode;
-    const std::vector<float4> h_nodes = pack_tree_nodes(tree);
-    std::vector<float4> h_beams(3 * n_sub);
-    for (size_t i = 0; i < n_sub; i++) {
-        float f[RL_BEAM_WORDS];
-        std::memcpy(f, &sub[(size_t)tree.order[i] * RL_BEAM_WORDS], sizeof f);
-        h_beams[3 * i] = make_float4(f[0], f[1], f[2], f[3]);
-        h_beams[3 * i + 1] = make_float4(f[4], f[5], f[6], 0.0f);
-        h_beams[3 * i + 2] = make_float4(f[8], f[9], f[10], 0.0f);
-    }
-    HIP_OK(hipSetDevice(ctx->device));
-    auto map = std::make_unique<rl_vrl_map>();
-    map->ctx = ctx; map->device = ctx->device;
-    if ((rcode = map->nodes.ensure(h_nodes.size())) != RL_OK || (rcode = map->beams.ensure(h_beams.size())) != RL_OK || (rcode = map->vrls.ensure(std::max<size_t>(h_vrls.size(), 1))) != RL_OK)
-        return rcode;
-    HIP_OK(hipMemcpy(map->nodes.get(), h_nodes.data(), h_nodes.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(map->beams.get(), h_beams.data(), h_beams.size() * sizeof(float4), hipMemcpyHostToDevice));
+    // ---- the surface beams: split and beam tree (avg_split over the surface beams alone)
+    auto map = new_handle<rl_vrl_map>(ctx);
+    BeamHalfHost host;
+    if ((rcode = beam_half_build(&map->half, &host, ctx->device, surface.data(), n_surface, radius)) != RL_OK || (rcode = map->vrls.ensure(std::max<size_t>(h_vrls.size(), 1))) != RL_OK) return rcode;
     if (n_vrl) HIP_OK(hipMemcpy(map->vrls.get(), h_vrls.data(), h_vrls.size() * sizeof(float4), hipMemcpyHostToDevice));
-    map->n_surface = n_surface; map->n_sub = n_sub; map->n_nodes = tree.n_nodes(); map->n_vrl = n_vrl; map->n_paths = n_paths; map->radius = radius; map->avg = avg;
+    map->n_surface = n_surface; map->n_vrl = n_vrl; map->n_paths = n_paths; map->radius = radius; map->avg = avg;
     *out = map.release();
     return RL_OK;
 }
 extern "C" int rl_vrl_map_build(rl_context* ctx, const rl_beam_set* set, float radius, rl_vrl_map** out) {
     if (!ctx || !set || !out) return RL_ERR_INVALID_ARGUMENT;
     *out = nullptr;
-    if (set->ctx != ctx) { rl_set_error("the beam set belongs to another context"); return RL_ERR_INVALID_ARGUMENT; }
-    HIP_OK(hipSetDevice(ctx->device));
-    std::vector<uint32_t> words((size_t)set->n_beams * RL_BEAM_WORDS);
-    HIP_OK(hipMemcpy(words.data(), set->words.get(), words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    int rcode;
+    std::vector<uint32_t> words;
+    if ((rcode = set_words_to_host(ctx, set->ctx, "beam set", set->words, (size_t)set->n_beams * RL_BEAM_WORDS, &words)) != RL_OK) return rcode;
     return rl_vrl_map_build_words(ctx, words.data(), (size_t)set->n_beams, set->n_paths, radius, out);
 }
 extern "C" int rl_vrl_map_info(const rl_vrl_map* map, uint64_t* n_surface, uint64_t* n_sub, uint64_t* n_nodes, uint64_t* n_vrl, uint64_t* n_paths, float* radius, float* avg) {
     if (!map) return RL_ERR_INVALID_ARGUMENT;
     if (n_surface) *n_surface = map->n_surface;
-    if (n_sub) *n_sub = map->n_sub;
-    if (n_nodes) *n_nodes = map->n_nodes;
+    if (n_sub) *n_sub = map->half.n_sub;
+    if (n_nodes) *n_nodes = map->half.n_nodes;
     if (n_vrl) *n_vrl = map->n_vrl;
     if (n_paths) *n_paths = map->n_paths;
     if (radius) *radius = map->radius;
@@ -107,20 +84,12 @@ extern "C" int rl_vrl_map_info(const rl_vrl_map* map, uint64_t* n_surface, uint6
 }
 extern "C" int rl_vrl_map_read(const rl_vrl_map* map, size_t node_capacity, float* node_boxes, uint32_t* node_links, size_t beam_capacity, float* beams, size_t vrl_capacity, float* vrls) {
     if (!map || !node_boxes || !node_links || !beams || (map->n_vrl && !vrls)) return RL_ERR_INVALID_ARGUMENT;
-    if (node_capacity < map->n_nodes || beam_capacity < map->n_sub || vrl_capacity < map->n_vrl) { rl_set_error("rl_vrl_map_read: a capacity is too small"); return RL_ERR_INVALID_ARGUMENT; }
+    if (node_capacity < map->half.n_nodes || beam_capacity < map->half.n_sub || vrl_capacity < map->n_vrl) { rl_set_error("rl_vrl_map_read: a capacity is too small"); return RL_ERR_INVALID_ARGUMENT; }
     HIP_OK(hipSetDevice(map->device));
-    std::vector<float4> h_nodes(2 * (size_t)map->n_nodes);
-    HIP_OK(hipMemcpy(h_nodes.data(), map->nodes.get(), h_nodes.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(beams, map->beams.get(), (size_t)map->n_sub * 3 * sizeof(float4), hipMemcpyDeviceToHost));
     if (map->n_vrl) HIP_OK(hipMemcpy(vrls, map->vrls.get(), (size_t)map->n_vrl * 3 * sizeof(float4), hipMemcpyDeviceToHost));
-    unpack_tree_nodes(h_nodes, (size_t)map->n_nodes, node_boxes, node_links);
-    return RL_OK;
+    return beam_half_read(map->half, node_boxes, node_links, beams);
 }
-extern "C" void rl_vrl_map_destroy(rl_vrl_map* map) {
-    if (!map) return;
-    (void)hipSetDevice(map->device);
-    delete map;
-}
+extern "C" void rl_vrl_map_destroy(rl_vrl_map* map) { destroy_handle(map); }
 extern "C" int rl_render_vrl(rl_context* ctx, const rl_vrl_map* map, uint32_t spp, int32_t seed_variant, uint32_t shard_index, uint32_t shard_count,
                              const uint64_t* block_seeds, size_t n_blocks, float* out_rgb, rl_render_stats* stats) {
     if (!map) return RL_ERR_INVALID_ARGUMENT;
@@ -144,10 +113,7 @@ extern "C" int rl_render_vrl(rl_context* ctx, const rl_vrl_map* map, uint32_t sp
     rcode = render_gather(ctx, kind, map->ctx, spp, seed_variant, shard_index, shard_count, block_seeds, n_blocks, out_rgb, stats,
                           [&](bool lds_scene, dim3 grid, size_t lds, hipStream_t st, const RenderConst& rc, const StackConf& stc) {
         VrlConst vc{};
-        vc.beam.nodes = map->nodes.get(); vc.beam.beams = map->beams.get(); vc.beam.n_nodes = (unsigned)map->n_nodes;
-        vc.beam.radius2 = map->radius * map->radius;                            // self.radius * self.radius
-        vc.beam.half_inv_radius = 0.5f / map->radius;                           // 0.5 / self.radius
-        vc.beam.norm_photon = 1.0f / (float)map->n_paths;                       // 1.0 / nb_path_shot as f32 (vol_primitives.rs:707)
+        vc.beam = beam_half_const(map->half, map->radius, map->n_paths);
         vc.vrls = map->vrls.get(); vc.n_vrl = (unsigned)map->n_vrl;
         vc.starts = d_starts.get(); vc.totals = d_totals.get();
         n_owned = grid.x;

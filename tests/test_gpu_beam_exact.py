@@ -13,7 +13,7 @@ import pytest
 from oracle import orc
 from rustlight_amd import api, scenes
 from tests import beam_restatement as R
-from tests.photon_tree_cases import assert_trees_equal
+from tests.beam_half_cases import assert_beam_half
 from tests.scene_helpers import context as _context
 from tests.test_gpu_gather_edges import SIGMA_S_ZERO, coloured
 
@@ -38,15 +38,8 @@ def _exact(sd, seed=3, nb=120, spp=3, radius=0.1, max_depth=None, rr_depth=0, va
     beams, _ = ctx.beam_generate(sampler, nb, max_depth, rr_depth, streams)
     words, (n_beams, n_paths) = beams.words(), beams.info()
     bmap = ctx.beam_map(beams, radius)
-    sub = api.beam_split(words)
-    boxes, links, order = api.beam_tree_build(sub, radius)
-    got = bmap.read()
-    assert_trees_equal(got[:2], (boxes, links), "map")
-    f = sub[order].view(np.float32)
-    want = np.zeros((sub.shape[0], 12), np.float32)
-    want[:, 0:4], want[:, 4:7], want[:, 8:11] = f[:, 0:4], f[:, 4:7], f[:, 8:11]
-    np.testing.assert_array_equal(got[2].view(np.uint32), want.view(np.uint32))
-    assert bmap.info() == (n_beams, sub.shape[0], boxes.shape[0], n_paths, pytest.approx(radius))
+    n_sub, n_nodes = assert_beam_half(bmap.read(), words, radius)
+    assert bmap.info() == (n_beams, n_sub, n_nodes, n_paths, pytest.approx(radius))
     seeds = sampler.block_seeds(sd.width, sd.height)
     img, st, detail = _render_both(sd, ctx, sc, words, n_paths, bmap, seeds, spp, radius, variant)
     assert st["beams_accepted"] > 0 and img.any()                 # no case passes empty

@@ -14,6 +14,7 @@ from oracle import orc
 from rustlight_amd import api, scenes
 from tests import beam_restatement as R
 from tests import pplane_restatement as Q
+from tests.beam_half_cases import assert_beam_half
 from tests.photon_tree_cases import assert_trees_equal
 from tests.scene_helpers import context as _context
 from tests.test_gpu_gather_edges import coloured
@@ -44,19 +45,12 @@ def _packed_planes(planes, order):
 
 def _check_map(pmap, beams, planes, n_paths, radius):
     """Both trees and both element arrays of a map against the host-only builds."""
-    sub = api.beam_split(beams)
-    boxes, links, order = api.beam_tree_build(sub, radius)
-    got = pmap.read("beams")
-    assert_trees_equal(got[:2], (boxes, links), "beam tree")
-    f = sub[order].view(np.float32)
-    want = np.zeros((sub.shape[0], 12), np.float32)
-    want[:, 0:4], want[:, 4:7], want[:, 8:11] = f[:, 0:4], f[:, 4:7], f[:, 8:11]
-    np.testing.assert_array_equal(got[2].view(np.uint32), want.view(np.uint32))
+    n_sub, n_beam_nodes = assert_beam_half(pmap.read("beams"), beams, radius, "beam tree")
     pboxes, plinks, porder = api.plane_tree_build(planes)
     got = pmap.read("planes")
     assert_trees_equal(got[:2], (pboxes, plinks), "plane tree")
     np.testing.assert_array_equal(got[2].view(np.uint32), _packed_planes(planes, porder).view(np.uint32))
-    assert pmap.info() == (beams.shape[0], sub.shape[0], boxes.shape[0], planes.shape[0], pboxes.shape[0], n_paths, pytest.approx(radius))
+    assert pmap.info() == (beams.shape[0], n_sub, n_beam_nodes, planes.shape[0], pboxes.shape[0], n_paths, pytest.approx(radius))
 
 
 def _exact(sd, seed=3, nb=60, spp=3, radius=0.1, max_depth=None, rr_depth=0, variant=0, streaming=False, streams="reference", options=None):

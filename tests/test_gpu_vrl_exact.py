@@ -15,7 +15,7 @@ from oracle import orc
 from rustlight_amd import api, scenes
 from tests import beam_restatement as R
 from tests import vrl_restatement as V
-from tests.photon_tree_cases import assert_trees_equal
+from tests.beam_half_cases import assert_beam_half
 from tests.scene_helpers import context as _context
 from tests.test_gpu_gather_edges import SIGMA_S_ZERO, coloured
 
@@ -27,21 +27,15 @@ RL_ERR_INVALID_ARGUMENT = -1
 def _check_map(vmap, words, n_paths, radius):
     """The map read back: the host-only split and tree over the surface beams, the VRLs in storing order with the restatement's rr, avg."""
     surface, vrl_words = V.partition(words)
-    sub = api.beam_split(surface)
-    boxes, links, order = api.beam_tree_build(sub, radius)
     got = vmap.read()
-    assert_trees_equal(got[:2], (boxes, links), "map")
-    f = sub[order].view(np.float32)
-    want = np.zeros((sub.shape[0], 12), np.float32)
-    want[:, 0:4], want[:, 4:7], want[:, 8:11] = f[:, 0:4], f[:, 4:7], f[:, 8:11]
-    np.testing.assert_array_equal(got[2].view(np.uint32), want.view(np.uint32))
+    n_sub, n_nodes = assert_beam_half(got, surface, radius)
     avg, rr = V.roulette(vrl_words)
     f = vrl_words.view(np.float32)
     want = np.zeros((vrl_words.shape[0], 12), np.float32)
     want[:, 0:4], want[:, 4:7], want[:, 7], want[:, 8:11] = f[:, 0:4], f[:, 4:7], rr, f[:, 8:11]
     np.testing.assert_array_equal(got[3].view(np.uint32), want.view(np.uint32))
     info = vmap.info()
-    assert info[:5] == (surface.shape[0], sub.shape[0], boxes.shape[0], vrl_words.shape[0], n_paths) and info[5] == pytest.approx(radius)
+    assert info[:5] == (surface.shape[0], n_sub, n_nodes, vrl_words.shape[0], n_paths) and info[5] == pytest.approx(radius)
     assert np.float32(info[6]) == avg
     return vrl_words.shape[0]
 
