@@ -10,6 +10,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import api, scenes
+from tests import cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -57,14 +58,13 @@ def test_no_gpu_means_loud_failure_not_fallback(built, cbox64):
         api.MultiContext(api.Scene(cbox64), 2)
     # the CLI (C++ mirror of examples/cli.rs) parses, loads and builds the scene, then refuses to render without a device
     import subprocess
-    cli = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     for args in (["-n", "1", "-o", "/tmp/never.pfm", "path"], ["-x", "ats", "-n", "1", "-o", "/tmp/never.pfm", "direct", "-b", "1"]):
-        r = subprocess.run([cli, os.path.join(ROOT, "data", "cbox.pbrt"), *args], capture_output=True, text=True)
+        r = subprocess.run([cli.EXE, os.path.join(ROOT, "data", "cbox.pbrt"), *args], capture_output=True, text=True)
         assert r.returncode != 0 and "no CPU fallback" in r.stderr and not os.path.exists("/tmp/never.pfm")
     # `-x hvs-light` (EmissionType::HSV on every light mesh, cli.rs:410-429) is parsed and applied, then the same refusal; an unknown extra option is an error
-    r = subprocess.run([cli, os.path.join(ROOT, "data", "cbox.pbrt"), "-x", "hvs-light", "-n", "1", "-o", "/tmp/never.pfm", "path"], capture_output=True, text=True)
+    r = subprocess.run([cli.EXE, os.path.join(ROOT, "data", "cbox.pbrt"), "-x", "hvs-light", "-n", "1", "-o", "/tmp/never.pfm", "path"], capture_output=True, text=True)
     assert r.returncode != 0 and "no CPU fallback" in r.stderr and not os.path.exists("/tmp/never.pfm")
-    r = subprocess.run([cli, os.path.join(ROOT, "data", "cbox.pbrt"), "-x", "no-such-option", "-n", "1", "-o", "/tmp/never.pfm", "path"], capture_output=True, text=True)
+    r = subprocess.run([cli.EXE, os.path.join(ROOT, "data", "cbox.pbrt"), "-x", "no-such-option", "-n", "1", "-o", "/tmp/never.pfm", "path"], capture_output=True, text=True)
     assert r.returncode == 2 and "not supported" in r.stderr
 
 

@@ -1,17 +1,7 @@
 """`rustlight-amd ... photon-beams`: the argument errors the CLI reports before it opens a device (no GPU needed), the lines that parse, and
 `vol-primitivies -p beam`, which stays refused: the photon beams have a subcommand of their own."""
-import os
-import subprocess
-
 from rustlight_amd import api
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE = os.path.join(ROOT, "data", "cbox.pbrt")
-
-
-def _cli(tmp_path, *args, medium=("-m", "1.0")):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "2", *medium, "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
+from tests import cli
 
 
 def test_photon_beams_argument_errors(built, tmp_path):
@@ -36,18 +26,16 @@ def test_photon_beams_argument_errors(built, tmp_path):
                        (("photon-beams", "-s", "all"), "photon-beams option"),
                        (("--light-streams", "per-path", "photon-beams"), "after the subcommand"),
                        (("vol-primitivies", "-p", "beam"), "not built")):
-        r = _cli(tmp_path, *args)
-        assert r.returncode == 2 and word in r.stderr and r.stderr.count("\n") == 1, (args, r.stderr)
-        assert not os.path.exists(tmp_path / "out.pfm")
+        cli.assert_refused(tmp_path, args, word)
 
 
 def test_photon_beams_need_a_medium(built, tmp_path):
-    r = _cli(tmp_path, "photon-beams", medium=())
+    r = cli.run_cli(tmp_path, "photon-beams", medium=())
     assert r.returncode == 2 and "needs a medium" in r.stderr and r.stderr.count("\n") == 1, r.stderr
 
 
 def test_unknown_subcommand_lists_photon_beams(built, tmp_path):
-    r = _cli(tmp_path, "photon-beam")
+    r = cli.run_cli(tmp_path, "photon-beam")
     assert r.returncode == 2 and "`photon-beams`" in r.stderr and "`plane-single`" in r.stderr and r.stderr.count("\n") == 1, r.stderr
 
 
@@ -55,9 +43,4 @@ def test_photon_beams_options_parse_up_to_the_device(built, tmp_path):
     """Well-formed lines (-n parsed and ignored, both stream modes) get as far as opening a device: without one, the no-fallback refusal."""
     for args in (("photon-beams",), ("photon-beams", "--nb-primitive", str(api.BEAM_MAX), "--radius", "0.2", "-n", "3", "-m", "6", "-r", "inf"),
                  ("photon-beams", "--nb-primitive", "64", "--light-streams", "per-path"), ("photon-beams", "--light-streams", "reference", "-m", "inf")):
-        r = _cli(tmp_path, *args)
-        if r.returncode == 0:                                  # a machine with a GPU renders it
-            assert os.path.exists(tmp_path / "out.pfm")
-            os.remove(tmp_path / "out.pfm")
-        else:
-            assert r.returncode != 2 and "no CPU fallback" in r.stderr, (args, r.stderr)
+        cli.assert_reaches_device(tmp_path, args)

@@ -1,17 +1,6 @@
 """`rustlight-amd ... vol-primitivies`: the argument errors the CLI reports before it opens a device (no GPU needed), the primitives that are not built,
 and the lines that parse."""
-import os
-import subprocess
-
-from rustlight_amd import api
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE = os.path.join(ROOT, "data", "cbox.pbrt")
-
-
-def _cli(tmp_path, *args):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "2", "-m", "1.0", "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
+from tests import cli
 
 
 def test_vol_primitives_argument_errors(built, tmp_path):
@@ -34,17 +23,10 @@ def test_vol_primitives_argument_errors(built, tmp_path):
                        (("vol-primitivies", "--radius", "inf"), "--radius"),
                        (("vol-primitivies", "--radius", "0.1x"), "--radius"),
                        (("vol-primitivies", "-s", "all"), "vol-primitivies option")):
-        r = _cli(tmp_path, *args)
-        assert r.returncode == 2 and word in r.stderr and r.stderr.count("\n") == 1, (args, r.stderr)
-        assert not os.path.exists(tmp_path / "out.pfm")
+        cli.assert_refused(tmp_path, args, word)
 
 
 def test_vol_primitives_options_parse_up_to_the_device(built, tmp_path):
     """Well-formed lines (-p defaults to bre, -n parsed and ignored, the alias) get as far as opening a device: without one, the no-fallback refusal."""
     for args in (("vol-primitivies",), ("vol-primitives", "-p", "bre", "--nb-primitive", "64", "--radius", "0.2", "-n", "3", "-m", "6", "-r", "inf")):
-        r = _cli(tmp_path, *args)
-        if r.returncode == 0:                                  # a machine with a GPU renders it
-            assert os.path.exists(tmp_path / "out.pfm")
-            os.remove(tmp_path / "out.pfm")
-        else:
-            assert r.returncode != 2 and "no CPU fallback" in r.stderr, (args, r.stderr)
+        cli.assert_reaches_device(tmp_path, args)

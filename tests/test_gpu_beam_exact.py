@@ -12,6 +12,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import api, scenes
+from tests import cli
 from tests import beam_restatement as R
 from tests.beam_half_cases import assert_beam_half
 from tests.scene_helpers import context as _context
@@ -191,10 +192,9 @@ def test_integrator_compute(built):
 
 def test_cli_renders_what_the_api_renders(built, tmp_path):
     """`photon-beams` goes through the C++ mirror (integrator.hpp: IntegratorPhotonBeams::compute): the same bytes as the Python mirror."""
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cbox.pbrt")
     out = str(tmp_path / "out.pfm")
-    args = [exe, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out]
+    args = [cli.EXE, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out]
     for extra, streams in (([], "reference"), (["--light-streams", "per-path"], "per_path")):
         r = subprocess.run(args + ["photon-beams", "--nb-primitive", "200", "--radius", "0.1", "-m", "6", "-r", "3"] + extra, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr

@@ -13,6 +13,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import api, scenes
+from tests import cli
 from tests import bre_restatement as R
 from tests.gather_exact import BRE_KEYS as KEYS, bre_exact as _exact
 from tests.scene_helpers import context as _context
@@ -133,10 +134,9 @@ def test_integrator_compute(built):
 
 def test_cli_renders_what_the_api_renders(built, tmp_path):
     """`vol-primitivies` goes through the C++ mirror (integrator.hpp: IntegratorVolPrimitives::compute): the same bytes as the Python mirror; -p beam is not built."""
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cbox.pbrt")
     out = str(tmp_path / "out.pfm")
-    args = [exe, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out]
+    args = [cli.EXE, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out]
     r = subprocess.run(args + ["vol-primitivies", "--nb-primitive", "200", "--radius", "0.2", "-n", "3"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     img = api.load_pfm(out)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from rustlight_amd import api, scenes
+from tests import cli
 
 pytestmark = pytest.mark.gpu
 
@@ -189,10 +190,9 @@ def test_refusals(built):
 
 
 def test_cli_renders_what_the_api_renders(built, tmp_path):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = os.path.join(ROOT, "data", "cbox.pbrt")
     out = str(tmp_path / "out.pfm")
-    r = subprocess.run([exe, scn, "-n", "4", "-r", "independent:7", "-o", out, "light-tracing"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cli.EXE, scn, "-n", "4", "-r", "independent:7", "-o", out, "light-tracing"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     img = api.load_pfm(out)
     want = api.IntegratorLightTracing().compute(api.IndependentSampler(7), api.Scene.load(scn), 4)

@@ -10,6 +10,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import api, scenes
+from tests import cli
 
 pytestmark = pytest.mark.gpu
 
@@ -483,14 +484,13 @@ def test_cli_renders_what_the_api_renders(built, tmp_path):
     import os
     import subprocess
     from rustlight_amd import export
-    cli = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     sd = scenes.many_lights(40, 32, 2)
     sd.flip, sd.fov_axis = True, 0
     xml = str(tmp_path / "lights.xml")
     export.write_mitsuba(sd, xml, "ply")
     def run(*args):
         out = str(tmp_path / "out.pfm")
-        r = subprocess.run([cli, xml, "-n", "3", "-r", "independent:11", "-o", out, "--stream-mode", "per-sample", *args], capture_output=True, text=True)
+        r = subprocess.run([cli.EXE, xml, "-n", "3", "-r", "independent:11", "-o", out, "--stream-mode", "per-sample", *args], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr
         return api.load_pfm(out)
     seeds = lambda: api.IndependentSampler(11).block_seeds(40, 32)
@@ -507,7 +507,7 @@ def test_cli_renders_what_the_api_renders(built, tmp_path):
     # name is an error, not a silently ignored flag
     np.testing.assert_array_equal(run("--stream-mode", "reference", "--option", "ref_single_pass=1", "--option", "no_events", "path"),
                                   flat.render(seeds(), api.path_params(spp=3, stream_mode=api.STREAM_REFERENCE_ORDER))[0])
-    bad = subprocess.run([cli, xml, "-n", "1", "-o", str(tmp_path / "bad.pfm"), "--option", "no_such_option=1", "path"], capture_output=True, text=True)
+    bad = subprocess.run([cli.EXE, xml, "-n", "1", "-o", str(tmp_path / "bad.pfm"), "--option", "no_such_option=1", "path"], capture_output=True, text=True)
     assert bad.returncode != 0 and "no_such_option" in (bad.stderr + bad.stdout)
     # --gpus N: N device contexts (round-robin over the visible devices — three on the one GPU here), one host thread each,
     # per-shard framebuffers added on the host: the single-context image again
@@ -576,13 +576,12 @@ def test_frames_in_flight_render_the_same_frames(built, cbox64, tmp_path):
     # the C++ mirror through the CLI: -a 0 stops after the first pass of the first batch; its image is the plain render's
     import subprocess
     from rustlight_amd import export
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = str(tmp_path / "cbox.xml")
     export.write_mitsuba(cbox64, scn, "ply")
     outs = []
     for extra in ([], ["--frames-in-flight", "3", "-a", "0"]):
         out = str(tmp_path / f"cli{len(outs)}.pfm")
-        r = subprocess.run([exe, scn, "-n", "2", "-r", "independent:5", "-o", out, *extra, "path"], capture_output=True, text=True)
+        r = subprocess.run([cli.EXE, scn, "-n", "2", "-r", "independent:5", "-o", out, *extra, "path"], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr
         outs.append(api.load_pfm(out))
     np.testing.assert_array_equal(outs[1], outs[0])

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from rustlight_amd import api, scenes
+from tests import cli
 from tests import bre_restatement as R
 from tests import photon_tree_cases as P
 from tests.scene_helpers import context as _context
@@ -204,12 +205,11 @@ def test_integrator_compute(built):
 
 def test_cli_writes_the_same_bytes(built, tmp_path):
     """`--tree-build device` goes through the C++ mirror (integrator.hpp: IntegratorVolPrimitives::tree_build): the PFM of the same line without it, byte for byte."""
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cbox.pbrt")
     outs = []
     for name, extra in (("host.pfm", []), ("device.pfm", ["--tree-build", "device"])):
         out = str(tmp_path / name)
-        r = subprocess.run([exe, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out, "vol-primitivies", "--nb-primitive", "200", "--radius", "0.2", "-n", "3"] + extra,
+        r = subprocess.run([cli.EXE, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out, "vol-primitivies", "--nb-primitive", "200", "--radius", "0.2", "-n", "3"] + extra,
                            capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr
         outs.append(open(out, "rb").read())

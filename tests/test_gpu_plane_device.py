@@ -16,6 +16,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import abi, api, scenes
+from tests import cli
 from tests import plane_single_restatement as R
 from tests import plane_tree_cases as P
 from tests.scene_helpers import context as _context, two_lights
@@ -295,12 +296,11 @@ def test_integrator_compute(built):
 def test_cli_writes_the_same_bytes(built, tmp_path):
     """`--option plane_generate_lanes=1 --option plane_tree_device=1` goes through the C++ mirror's options (integrator.hpp): the PFM of the same line without
     them, byte for byte."""
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cbox.pbrt")
     outs = []
     for name, extra in (("plain.pfm", []), ("device.pfm", ["--option", "plane_generate_lanes=1", "--option", "plane_tree_device=1"])):
         out = str(tmp_path / name)
-        r = subprocess.run([exe, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out] + extra + ["plane-single", "-n", "128", "-s", "average"],
+        r = subprocess.run([cli.EXE, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out] + extra + ["plane-single", "-n", "128", "-s", "average"],
                            capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr
         outs.append(open(out, "rb").read())

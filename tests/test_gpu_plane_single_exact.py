@@ -14,6 +14,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import abi, api, scenes
+from tests import cli
 from tests import plane_single_restatement as R
 from tests.gather_exact import PLANE_KEYS as KEYS, plane_exact as _exact
 from tests.scene_helpers import context as _context, two_lights
@@ -237,10 +238,9 @@ def test_integrator_compute(built, strategy):
 def test_cli_renders_what_the_api_renders(built, tmp_path):
     """`data/cbox.pbrt -m 1.0 -r independent:7 plane-single -n 64 -s cmis` goes through the C++ mirror (integrator.hpp: IntegratorSinglePlane::compute): the
     same bytes as the Python mirror.  The scene file's light is the quad the integrator needs, as it stands."""
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cbox.pbrt")
     out = str(tmp_path / "out.pfm")
-    r = subprocess.run([exe, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out, "plane-single", "-n", "64", "-s", "cmis"],
+    r = subprocess.run([cli.EXE, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out, "plane-single", "-n", "64", "-s", "cmis"],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     img = api.load_pfm(out)

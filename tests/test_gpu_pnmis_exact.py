@@ -13,6 +13,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import api, scenes
+from tests import cli
 from tests import pn_restatement as P
 from tests import pnmis_restatement as M
 from tests.scene_helpers import context as _context
@@ -183,10 +184,9 @@ def test_integrator_compute(built, strategy, use_aa, mode):
 
 
 def _run_cli(tmp_path, *args):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cbox.pbrt")
     out = str(tmp_path / "pnmis.pfm")
-    r = subprocess.run([exe, scn, *args[0], "-m", "1.0", "-r", "independent:7", "-o", out, "point-normal-mis", *args[1]], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cli.EXE, scn, *args[0], "-m", "1.0", "-r", "independent:7", "-o", out, "point-normal-mis", *args[1]], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     return scn, api.load_pfm(out)
 

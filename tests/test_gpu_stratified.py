@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from rustlight_amd import api, export, scenes
+from tests import cli
 
 pytestmark = pytest.mark.gpu
 
@@ -211,7 +212,6 @@ def test_mse_against_the_independent_sampler(built, cbox64, kind):
 
 
 def test_cli_renders_what_the_api_renders(built, tmp_path):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     sd = scenes.cbox(64, 64)
     sd.flip, sd.fov_axis = True, 0           # the camera conventions the Mitsuba writer / reader pair round-trips
     scn = str(tmp_path / "cbox.xml")
@@ -221,7 +221,7 @@ def test_cli_renders_what_the_api_renders(built, tmp_path):
 
     def run(spp, *args):
         out = str(tmp_path / "out.pfm")
-        r = subprocess.run([exe, scn, "-n", str(spp), "-r", "stratified:11", "-o", out, *args], capture_output=True, text=True, timeout=300)
+        r = subprocess.run([cli.EXE, scn, "-n", str(spp), "-r", "stratified:11", "-o", out, *args], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr
         return api.load_pfm(out), r.stderr
     want = ctx.render(seeds(), api.path_params(spp=16, stream_mode=api.STREAM_STRATIFIED))[0]

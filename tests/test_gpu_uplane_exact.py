@@ -13,6 +13,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import api, scenes
+from tests import cli
 from tests import uplane_restatement as U
 from tests.scene_helpers import context as _context, two_lights
 
@@ -177,10 +178,9 @@ def test_integrator_compute(built, strategy):
 def test_cli_renders_what_the_api_renders(built, tmp_path):
     """`data/cbox.pbrt -n 2 -m 1.0 -r independent:7 plane-single --uncorrelated -n 64 -s cmis` goes through the C++ mirror (integrator.hpp:
     IntegratorSinglePlaneUncorrelated::compute): the same bytes as the Python mirror."""
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cbox.pbrt")
     out = str(tmp_path / "out.pfm")
-    r = subprocess.run([exe, scn, "-n", "2", "-m", "1.0", "-r", "independent:7", "-o", out, "plane-single", "--uncorrelated", "-n", "64", "-s", "cmis"],
+    r = subprocess.run([cli.EXE, scn, "-n", "2", "-m", "1.0", "-r", "independent:7", "-o", out, "plane-single", "--uncorrelated", "-n", "64", "-s", "cmis"],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     img = api.load_pfm(out)

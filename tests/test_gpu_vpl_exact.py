@@ -10,6 +10,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import api, scenes
+from tests import cli
 from tests.scene_helpers import context as _context, glass_and_mirror as _glass_and_mirror, single_bsdf as _single_bsdf, with_back_triangle as _with_back_triangle
 
 pytestmark = pytest.mark.gpu
@@ -170,10 +171,9 @@ def test_integrator_compute_and_records(built):
 
 def test_cli_renders_what_the_api_renders(built, tmp_path):
     import subprocess
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cbox.pbrt")
     out = str(tmp_path / "out.pfm")
-    r = subprocess.run([exe, scn, "-n", "2", "-r", "independent:7", "-o", out, "vpl", "--nb-vpl", "48", "-b", "1.5"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cli.EXE, scn, "-n", "2", "-r", "independent:7", "-o", out, "vpl", "--nb-vpl", "48", "-b", "1.5"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     img = api.load_pfm(out)
     want = api.IntegratorVPL(nb_vpl=48).compute(api.IndependentSampler(7), api.Scene.load(scn), 2)

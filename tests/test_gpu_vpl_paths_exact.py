@@ -11,6 +11,7 @@ import pytest
 
 from oracle import orc
 from rustlight_amd import api, scenes
+from tests import cli
 from tests import bre_restatement as B
 from tests import vpl_paths_restatement as R
 from tests.scene_helpers import context as _context
@@ -190,10 +191,9 @@ def test_integrators_compute_the_composition(built):
 def test_cli_writes_what_the_api_renders(built, tmp_path):
     """Both subcommands go through the C++ mirror (integrator.hpp: light_streams = LightStreams::PerPath): the same bytes as the Python mirror, and not the
     serial mode's."""
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
     scn = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cbox.pbrt")
     out = str(tmp_path / "out.pfm")
-    r = subprocess.run([exe, scn, "-n", "2", "-r", "independent:7", "-o", out, "vpl", "--nb-vpl", "48", "--light-streams", "per-path"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cli.EXE, scn, "-n", "2", "-r", "independent:7", "-o", out, "vpl", "--nb-vpl", "48", "--light-streams", "per-path"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     img = api.load_pfm(out)
     want = api.IntegratorVPL(nb_vpl=48, light_streams="per_path").compute(api.IndependentSampler(7), api.Scene.load(scn), 2)
@@ -201,7 +201,7 @@ def test_cli_writes_what_the_api_renders(built, tmp_path):
     assert img.shape == want.shape and want.any()
     np.testing.assert_array_equal(img, want)
     assert not np.array_equal(want, serial)
-    r = subprocess.run([exe, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out, "vol-primitivies", "--nb-primitive", "200", "--radius", "0.2",
+    r = subprocess.run([cli.EXE, scn, "-n", "2", "-r", "independent:7", "-m", "1.0", "-o", out, "vol-primitivies", "--nb-primitive", "200", "--radius", "0.2",
                         "--light-streams", "per-path"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     img = api.load_pfm(out)

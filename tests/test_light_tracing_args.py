@@ -3,17 +3,12 @@ values against the Python constants, and the new entry point among the library's
 import ctypes
 import os
 import re
-import subprocess
 
 from rustlight_amd import api
+from tests import cli
+from tests.cli import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE = os.path.join(ROOT, "data", "cbox.pbrt")
-
-
-def _cli(tmp_path, *args):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "4", "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
+PLAIN = dict(medium=(), spp="4")      # these lines: 4 spp and no medium
 
 
 def test_light_tracing_argument_errors(built, tmp_path):
@@ -23,10 +18,8 @@ def test_light_tracing_argument_errors(built, tmp_path):
                        (("--numerics", "fast", "light-tracing"), "fast"),
                        (("light-tracing", "-s", "bsdf"), "bsdf"),
                        (("light-tracing", "-s", "emitter"), "emitter")):
-        r = _cli(tmp_path, *args)
-        assert r.returncode == 2 and word in r.stderr and r.stderr.count("\n") == 1, (args, r.stderr)
-        assert not os.path.exists(tmp_path / "out.pfm")
-    r = _cli(tmp_path, "light-tracing", "-x")
+        cli.assert_refused(tmp_path, args, word, **PLAIN)
+    r = cli.run_cli(tmp_path, "light-tracing", "-x", **PLAIN)
     assert r.returncode == 2 and "light-tracing option" in r.stderr, r.stderr
 
 

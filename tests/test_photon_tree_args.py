@@ -3,20 +3,14 @@ needed), the lines that parse, and the declarations of rl_photon_map_build_devic
 ctypes mirror, the Rust block, the option table and the C++ mirror."""
 import os
 import re
-import subprocess
 
 import pytest
 
 from rustlight_amd import api
+from tests import cli
+from tests.cli import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE = os.path.join(ROOT, "data", "cbox.pbrt")
 NEW = ("rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read")
-
-
-def _cli(tmp_path, *args):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "2", "-m", "1.0", "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
 
 
 def test_tree_build_argument_errors(built, tmp_path):
@@ -24,21 +18,14 @@ def test_tree_build_argument_errors(built, tmp_path):
                  ("--tree-build", "device", "vol-primitivies"),
                  ("vpl", "--tree-build", "device"), ("path", "--tree-build", "device"), ("ao", "--tree-build", "host"),
                  ("direct", "--tree-build", "device"), ("light-tracing", "--tree-build", "device")):
-        r = _cli(tmp_path, *args)
-        assert r.returncode == 2 and "--tree-build" in r.stderr and r.stderr.count("\n") == 1, (args, r.stderr)
-        assert not os.path.exists(tmp_path / "out.pfm")
+        cli.assert_refused(tmp_path, args, "--tree-build")
 
 
 def test_tree_build_parses_up_to_the_device(built, tmp_path):
     """Well-formed lines get as far as opening a device: without one, the no-fallback refusal."""
     for args in (("vol-primitivies", "--tree-build", "device", "--nb-primitive", "64", "--radius", "0.2"),
                  ("vol-primitives", "--nb-primitive", "64", "--radius", "0.2", "--light-streams", "per-path", "--tree-build", "host")):
-        r = _cli(tmp_path, *args)
-        if r.returncode == 0:                                  # a machine with a GPU renders it
-            assert os.path.exists(tmp_path / "out.pfm")
-            os.remove(tmp_path / "out.pfm")
-        else:
-            assert r.returncode != 2 and "no CPU fallback" in r.stderr, (args, r.stderr)
+        cli.assert_reaches_device(tmp_path, args)
 
 
 def test_python_mirrors_take_only_the_two_values():

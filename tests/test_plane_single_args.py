@@ -1,16 +1,6 @@
 """`rustlight-amd ... plane-single`: the argument errors the CLI reports before it opens a device (no GPU needed) and the lines that parse."""
-import os
-import subprocess
-
 from rustlight_amd import api
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE = os.path.join(ROOT, "data", "cbox.pbrt")
-
-
-def _cli(tmp_path, *args, medium=("-m", "1.0")):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "2", *medium, "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
+from tests import cli
 
 
 def test_plane_single_argument_errors(built, tmp_path):
@@ -30,20 +20,16 @@ def test_plane_single_argument_errors(built, tmp_path):
                        (("plane-single", "--tree-build", "device"), "vol-primitivies only"),
                        (("plane-single", "-m", "3"), "plane-single option"),
                        (("plane-single", "-p", "plane"), "plane-single option")):
-        r = _cli(tmp_path, *args)
-        assert r.returncode == 2 and word in r.stderr and r.stderr.count("\n") == 1, (args, r.stderr)
-        assert not os.path.exists(tmp_path / "out.pfm")
+        cli.assert_refused(tmp_path, args, word)
 
 
 def test_plane_single_needs_a_medium(built, tmp_path):
     for medium in ((), ("-m", "0.0"), ("-m", "0:0")):
-        r = _cli(tmp_path, "plane-single", medium=medium)
-        assert r.returncode == 2 and "medium" in r.stderr and r.stderr.count("\n") == 1, (medium, r.stderr)
-        assert not os.path.exists(tmp_path / "out.pfm")
+        cli.assert_refused(tmp_path, ("plane-single",), "medium", medium=medium)
 
 
 def test_unknown_subcommand_lists_plane_single(built, tmp_path):
-    r = _cli(tmp_path, "uncorrelated-plane-single")
+    r = cli.run_cli(tmp_path, "uncorrelated-plane-single")
     assert r.returncode == 2 and "`plane-single`" in r.stderr and r.stderr.count("\n") == 1, r.stderr
 
 
@@ -52,9 +38,4 @@ def test_plane_single_options_parse_up_to_the_device(built, tmp_path):
     lines = [("plane-single",), ("plane-single", "--nb-primitive", "16", "--strategy", "cmis")]
     lines += [("plane-single", "-n", "8", "-s", s) for s in api.PLANE_STRATEGIES]
     for args in lines:
-        r = _cli(tmp_path, *args)
-        if r.returncode == 0:                                  # a machine with a GPU renders it
-            assert os.path.exists(tmp_path / "out.pfm")
-            os.remove(tmp_path / "out.pfm")
-        else:
-            assert r.returncode != 2 and "no CPU fallback" in r.stderr, (args, r.stderr)
+        cli.assert_reaches_device(tmp_path, args)

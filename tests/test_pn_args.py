@@ -1,31 +1,18 @@
 """`rustlight-amd ... point-normal`: the argument errors the CLI reports before it opens a device (no GPU needed), each on one line that names the word, exit
 code 2, no file written; and the well-formed lines, which get as far as the device."""
 import os
-import subprocess
 
 from rustlight_amd import api
+from tests import cli
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE = os.path.join(ROOT, "data", "cbox.pbrt")
 CMD = "point-normal"
 FLAVOURED = ("eq_best_ex", "eq_warp_ex", "eq_phase_taylor_ex", "eq_tr_taylor_ex", "eq_clamped_best_ex", "eq_clamped_warp_ex", "eq_clamped_phase_taylor_ex",
              "eq_clamped_tr_taylor_ex", "pn_tr_taylor_ex", "pn_phase_taylor_ex", "pn_warp_ex", "pn_best_ex")      # examples/cli.rs:455-492, the names with a flavour bit
 
 
-def _cli(tmp_path, *args, medium=("-m", "1.0")):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "2", *medium, "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
-
-
-def _refused(tmp_path, args, word, medium=("-m", "1.0")):
-    r = _cli(tmp_path, *args, medium=medium)
-    assert r.returncode == 2 and word in r.stderr and r.stderr.count("\n") == 1, (args, r.stderr)
-    assert not os.path.exists(tmp_path / "out.pfm")
-
-
 def test_flavoured_strategies_are_not_built(built, tmp_path):
     for name in FLAVOURED:
-        r = _cli(tmp_path, CMD, "-s", name)
+        r = cli.run_cli(tmp_path, CMD, "-s", name)
         assert r.returncode == 2 and name in r.stderr and "not built" in r.stderr and r.stderr.count("\n") == 1, (name, r.stderr)
         assert not os.path.exists(tmp_path / "out.pfm")
 
@@ -55,19 +42,19 @@ def test_point_normal_argument_errors(built, tmp_path):
                        ((CMD, "-m", "3"), "point-normal option"),
                        (("-z", CMD), "unknown option -z"),
                        (("path", "-z"), "unknown path option -z")):
-        _refused(tmp_path, args, word)
+        cli.assert_refused(tmp_path, args, word)
     # an invalid strategy lists the seven that are built
-    r = _cli(tmp_path, CMD, "-s", "nope")
+    r = cli.run_cli(tmp_path, CMD, "-s", "nope")
     assert all(name in r.stderr for name in api.PN_STRATEGIES)
 
 
 def test_point_normal_needs_a_medium(built, tmp_path):
     for medium in ((), ("-m", "0.0"), ("-m", "0:0")):
-        _refused(tmp_path, (CMD,), "medium", medium=medium)
+        cli.assert_refused(tmp_path, (CMD,), "medium", medium=medium)
 
 
 def test_unknown_subcommand_lists_point_normal(built, tmp_path):
-    r = _cli(tmp_path, "point_normal")
+    r = cli.run_cli(tmp_path, "point_normal")
     assert r.returncode == 2 and "`point-normal`" in r.stderr and "`plane-single`" in r.stderr and r.stderr.count("\n") == 1, r.stderr
 
 
@@ -78,9 +65,4 @@ def test_point_normal_options_parse_up_to_the_device(built, tmp_path):
              ("--stream-mode", "reference", CMD, "-s", "eq_phase")]
     lines += [(CMD, "-s", s) for s in api.PN_STRATEGIES]
     for args in lines:
-        r = _cli(tmp_path, *args)
-        if r.returncode == 0:                                  # a machine with a GPU renders it
-            assert os.path.exists(tmp_path / "out.pfm")
-            os.remove(tmp_path / "out.pfm")
-        else:
-            assert r.returncode != 2 and "no CPU fallback" in r.stderr, (args, r.stderr)
+        cli.assert_reaches_device(tmp_path, args)

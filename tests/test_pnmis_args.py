@@ -1,28 +1,17 @@
 """`rustlight-amd ... point-normal-mis`: the argument errors the CLI reports before it opens a device (no GPU needed), each on one line that names the word,
 exit code 2, no file written; and the well-formed lines, which get as far as the device."""
 import os
-import subprocess
 
 from rustlight_amd import api
-from tests.test_pn_args import FLAVOURED, SCENE
+from tests import cli
+from tests.test_pn_args import FLAVOURED
 
 CMD = "point-normal-mis"
 
 
-def _cli(tmp_path, *args, medium=("-m", "1.0")):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "2", *medium, "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
-
-
-def _refused(tmp_path, args, word, medium=("-m", "1.0")):
-    r = _cli(tmp_path, *args, medium=medium)
-    assert r.returncode == 2 and word in r.stderr and r.stderr.count("\n") == 1, (args, r.stderr)
-    assert not os.path.exists(tmp_path / "out.pfm")
-
-
 def test_flavoured_strategies_are_not_built(built, tmp_path):
     for name in FLAVOURED:
-        r = _cli(tmp_path, CMD, "-s", name)
+        r = cli.run_cli(tmp_path, CMD, "-s", name)
         assert r.returncode == 2 and name in r.stderr and "not built" in r.stderr and CMD in r.stderr and r.stderr.count("\n") == 1, (name, r.stderr)
         assert not os.path.exists(tmp_path / "out.pfm")
 
@@ -51,19 +40,19 @@ def test_point_normal_mis_argument_errors(built, tmp_path):
                        ((CMD, "-n", "3"), "point-normal-mis option"),
                        ((CMD, "-m", "3"), "point-normal-mis option"),
                        (("-z", CMD), "unknown option -z")):
-        _refused(tmp_path, args, word)
+        cli.assert_refused(tmp_path, args, word)
     # an invalid strategy lists the seven names
-    r = _cli(tmp_path, CMD, "-s", "nope")
+    r = cli.run_cli(tmp_path, CMD, "-s", "nope")
     assert all(name in r.stderr for name in api.PN_STRATEGIES)
 
 
 def test_point_normal_mis_needs_a_medium(built, tmp_path):
     for medium in ((), ("-m", "0.0"), ("-m", "0:0")):
-        _refused(tmp_path, (CMD,), "medium", medium=medium)
+        cli.assert_refused(tmp_path, (CMD,), "medium", medium=medium)
 
 
 def test_unknown_subcommand_lists_point_normal_mis(built, tmp_path):
-    r = _cli(tmp_path, "point_normal_mis")
+    r = cli.run_cli(tmp_path, "point_normal_mis")
     assert r.returncode == 2 and "`point-normal-mis`" in r.stderr and "`point-normal`" in r.stderr and r.stderr.count("\n") == 1, r.stderr
 
 
@@ -74,9 +63,4 @@ def test_point_normal_mis_options_parse_up_to_the_device(built, tmp_path):
              ("--stream-mode", "reference", CMD, "-s", "eq_phase")]
     lines += [(CMD, "-s", s) for s in api.PN_STRATEGIES]
     for args in lines:
-        r = _cli(tmp_path, *args)
-        if r.returncode == 0:                                  # a machine with a GPU renders it
-            assert os.path.exists(tmp_path / "out.pfm")
-            os.remove(tmp_path / "out.pfm")
-        else:
-            assert r.returncode != 2 and "no CPU fallback" in r.stderr, (args, r.stderr)
+        cli.assert_reaches_device(tmp_path, args)

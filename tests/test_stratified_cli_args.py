@@ -2,35 +2,30 @@
 and the Python constant of the new rl_stream_mode value."""
 import os
 import re
-import subprocess
 
 from rustlight_amd import api
+from tests import cli
+from tests.cli import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE = os.path.join(ROOT, "data", "cbox.pbrt")
-
-
-def _cli(tmp_path, *args):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "4", "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
+PLAIN = dict(medium=(), spp="4")      # these lines: 4 spp and no medium
 
 
 def test_stratified_argument_errors(built, tmp_path):
-    r = _cli(tmp_path, "-r", "stratified:abc", "path")
+    r = cli.run_cli(tmp_path, "-r", "stratified:abc", "path", **PLAIN)
     assert r.returncode == 2 and "seed" in r.stderr and "abc" in r.stderr and r.stderr.count("\n") == 1, r.stderr
     for bad in ("stratified:-1", "stratified:", "stratified:18446744073709551616"):
-        r = _cli(tmp_path, "-r", bad, "ao")
+        r = cli.run_cli(tmp_path, "-r", bad, "ao", **PLAIN)
         assert r.returncode == 2 and "seed" in r.stderr, (bad, r.stderr)
-    r = _cli(tmp_path, "-r", "stratified", "--stream-mode", "per-sample", "path")
+    r = cli.run_cli(tmp_path, "-r", "stratified", "--stream-mode", "per-sample", "path", **PLAIN)
     assert r.returncode == 2 and "--stream-mode" in r.stderr and r.stderr.count("\n") == 1, r.stderr
-    r = _cli(tmp_path, "--stream-mode", "reference", "-r", "stratified:3", "direct")
+    r = cli.run_cli(tmp_path, "--stream-mode", "reference", "-r", "stratified:3", "direct", **PLAIN)
     assert r.returncode == 2 and "--stream-mode" in r.stderr, r.stderr
-    r = _cli(tmp_path, "-r", "stratified:7", "--numerics", "fast", "path")
+    r = cli.run_cli(tmp_path, "-r", "stratified:7", "--numerics", "fast", "path", **PLAIN)
     assert r.returncode == 2 and "fast" in r.stderr and r.stderr.count("\n") == 1, r.stderr
 
 
 def test_unknown_sampler_names_both_samplers(built, tmp_path):
-    r = _cli(tmp_path, "-r", "bogus", "path")
+    r = cli.run_cli(tmp_path, "-r", "bogus", "path", **PLAIN)
     assert r.returncode == 2 and "bogus" in r.stderr and "stratified" in r.stderr and "independent" in r.stderr, r.stderr
 
 

@@ -1,17 +1,8 @@
 """`rustlight-amd ... plane-single --uncorrelated`: the argument errors the CLI reports before it opens a device (no GPU needed) and the lines that parse."""
-import os
-import subprocess
-
 from rustlight_amd import api
+from tests import cli
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE = os.path.join(ROOT, "data", "cbox.pbrt")
 CMD = ("plane-single", "--uncorrelated")
-
-
-def _cli(tmp_path, *args, medium=("-m", "1.0")):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "2", *medium, "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
 
 
 def test_uncorrelated_argument_errors(built, tmp_path):
@@ -34,16 +25,12 @@ def test_uncorrelated_argument_errors(built, tmp_path):
                        ((*CMD, "--uncorrelated=1"), "plane-single option"),
                        (("--uncorrelated", "plane-single"), "unknown option --uncorrelated"),
                        (("path", "--uncorrelated"), "unknown path option --uncorrelated")):
-        r = _cli(tmp_path, *args)
-        assert r.returncode == 2 and word in r.stderr and r.stderr.count("\n") == 1, (args, r.stderr)
-        assert not os.path.exists(tmp_path / "out.pfm")
+        cli.assert_refused(tmp_path, args, word)
 
 
 def test_uncorrelated_needs_a_medium(built, tmp_path):
     for medium in ((), ("-m", "0.0"), ("-m", "0:0")):
-        r = _cli(tmp_path, *CMD, medium=medium)
-        assert r.returncode == 2 and "medium" in r.stderr and r.stderr.count("\n") == 1, (medium, r.stderr)
-        assert not os.path.exists(tmp_path / "out.pfm")
+        cli.assert_refused(tmp_path, CMD, "medium", medium=medium)
 
 
 def test_uncorrelated_options_parse_up_to_the_device(built, tmp_path):
@@ -52,9 +39,4 @@ def test_uncorrelated_options_parse_up_to_the_device(built, tmp_path):
     lines = [CMD, (*CMD, "--nb-primitive", "16", "--strategy", "cmis"), ("plane-single", "-n", "4", "--uncorrelated", "-s", "ut")]
     lines += [(*CMD, "-n", "8", "-s", s) for s in api.PLANE_STRATEGIES]
     for args in lines:
-        r = _cli(tmp_path, *args)
-        if r.returncode == 0:                                  # a machine with a GPU renders it
-            assert os.path.exists(tmp_path / "out.pfm")
-            os.remove(tmp_path / "out.pfm")
-        else:
-            assert r.returncode != 2 and "no CPU fallback" in r.stderr, (args, r.stderr)
+        cli.assert_reaches_device(tmp_path, args)

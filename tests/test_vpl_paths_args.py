@@ -2,19 +2,12 @@
 that parse, and the declarations of rl_vpl_generate_paths in the header, the ctypes mirror, the Rust block and the option table."""
 import os
 import re
-import subprocess
 
 import pytest
 
 from rustlight_amd import api
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE = os.path.join(ROOT, "data", "cbox.pbrt")
-
-
-def _cli(tmp_path, *args):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "2", "-m", "1.0", "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
+from tests import cli
+from tests.cli import ROOT
 
 
 def test_light_streams_argument_errors(built, tmp_path):
@@ -30,9 +23,7 @@ def test_light_streams_argument_errors(built, tmp_path):
                        # the gather stays in reference order: the camera streams' flag is still refused beside the new one
                        (("--stream-mode", "per-sample", "vpl", "--light-streams", "per-path"), "per-sample"),
                        (("--stream-mode", "per-sample", "vol-primitivies", "--light-streams", "per-path"), "per-sample")):
-        r = _cli(tmp_path, *args)
-        assert r.returncode == 2 and word in r.stderr and r.stderr.count("\n") == 1, (args, r.stderr)
-        assert not os.path.exists(tmp_path / "out.pfm")
+        cli.assert_refused(tmp_path, args, word)
 
 
 def test_light_streams_parse_up_to_the_device(built, tmp_path):
@@ -40,12 +31,7 @@ def test_light_streams_parse_up_to_the_device(built, tmp_path):
     for args in (("vpl", "--light-streams", "per-path", "--nb-vpl", "16"), ("vpl", "--light-streams", "reference", "--nb-vpl", "16"),
                  ("vol-primitivies", "--light-streams", "per-path", "--nb-primitive", "64", "--radius", "0.2"),
                  ("vol-primitives", "--nb-primitive", "64", "--radius", "0.2", "--light-streams", "reference")):
-        r = _cli(tmp_path, *args)
-        if r.returncode == 0:                                  # a machine with a GPU renders it
-            assert os.path.exists(tmp_path / "out.pfm")
-            os.remove(tmp_path / "out.pfm")
-        else:
-            assert r.returncode != 2 and "no CPU fallback" in r.stderr, (args, r.stderr)
+        cli.assert_reaches_device(tmp_path, args)
 
 
 def test_python_mirrors_take_only_the_two_values():

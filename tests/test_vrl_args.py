@@ -1,17 +1,7 @@
 """`rustlight-amd ... virtual-ray-lights`: the argument errors the CLI reports before it opens a device (no GPU needed), the lines that parse, and
 `vol-primitivies -p vrl`, which stays refused: the virtual ray lights have a subcommand of their own; and the new names in api.PUBLIC_SYMBOLS."""
-import os
-import subprocess
-
 from rustlight_amd import api
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE = os.path.join(ROOT, "data", "cbox.pbrt")
-
-
-def _cli(tmp_path, *args, medium=("-m", "1.0")):
-    exe = os.path.join(os.path.dirname(api.LIB_PATH), "rustlight-amd")
-    return subprocess.run([exe, SCENE, "-n", "2", *medium, "-o", str(tmp_path / "out.pfm"), *args], capture_output=True, text=True, timeout=60)
+from tests import cli
 
 
 def test_virtual_ray_lights_argument_errors(built, tmp_path):
@@ -36,18 +26,16 @@ def test_virtual_ray_lights_argument_errors(built, tmp_path):
                        (("virtual-ray-lights", "-s", "all"), "virtual-ray-lights option"),
                        (("--light-streams", "per-path", "virtual-ray-lights"), "after the subcommand"),
                        (("vol-primitivies", "-p", "vrl"), "not built")):
-        r = _cli(tmp_path, *args)
-        assert r.returncode == 2 and word in r.stderr and r.stderr.count("\n") == 1, (args, r.stderr)
-        assert not os.path.exists(tmp_path / "out.pfm")
+        cli.assert_refused(tmp_path, args, word)
 
 
 def test_virtual_ray_lights_need_a_medium(built, tmp_path):
-    r = _cli(tmp_path, "virtual-ray-lights", medium=())
+    r = cli.run_cli(tmp_path, "virtual-ray-lights", medium=())
     assert r.returncode == 2 and "needs a medium" in r.stderr and r.stderr.count("\n") == 1, r.stderr
 
 
 def test_unknown_subcommand_lists_virtual_ray_lights(built, tmp_path):
-    r = _cli(tmp_path, "virtual-ray-light")
+    r = cli.run_cli(tmp_path, "virtual-ray-light")
     assert r.returncode == 2 and "`virtual-ray-lights`" in r.stderr and "`plane-single`" in r.stderr and r.stderr.count("\n") == 1, r.stderr
 
 
@@ -55,12 +43,7 @@ def test_virtual_ray_lights_options_parse_up_to_the_device(built, tmp_path):
     """Well-formed lines (-n parsed and ignored, both stream modes) get as far as opening a device: without one, the no-fallback refusal."""
     for args in (("virtual-ray-lights",), ("virtual-ray-lights", "--nb-primitive", "512", "--radius", "0.2", "-n", "3", "-m", "6", "-r", "inf"),
                  ("virtual-ray-lights", "--nb-primitive", "64", "--light-streams", "per-path"), ("virtual-ray-lights", "--light-streams", "reference", "-m", "inf")):
-        r = _cli(tmp_path, *args)
-        if r.returncode == 0:                                  # a machine with a GPU renders it
-            assert os.path.exists(tmp_path / "out.pfm")
-            os.remove(tmp_path / "out.pfm")
-        else:
-            assert r.returncode != 2 and "no CPU fallback" in r.stderr, (args, r.stderr)
+        cli.assert_reaches_device(tmp_path, args)
 
 
 def test_the_new_names_are_public(built):
