@@ -738,6 +738,36 @@ void rl_point_normal_mis_params_default(rl_point_normal_mis_params* params);   /
 int rl_render_point_normal_mis(rl_context* ctx, const rl_point_normal_mis_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
                                rl_render_stats* stats);
 
+/* ---- IntegratorPointNormal's Taylor strategies (the six `*_taylor_ex` names of cli.rs:455-492; CLI `point-normal-taylor`: `point-normal -s <flavoured>` stays
+ * refused): compute_single_strategy's EX arm (:2336-2453) over create_distance_sampling's Taylor arms (:1276-1290, :1404-1418).  The scattering angle is drawn
+ * from a degree-six Taylor polynomial of the transmittance (`tr`) or of the Henyey-Greenstein phase function (`phase`) up to a clamp angle, by a Newton /
+ * bisection inversion of at most 30 steps (math::newton_raphson_iterate, math.rs:136-225), and beyond it uniformly (eq, eq_clamped: TaylorSampling, :401-518)
+ * or by the point-normal pdf (pn: PointNormalTaylorSampling with warp = None, :757-976).  Poly6 is point_normal_poly.rs:178-393.  Not built: the warp and
+ * "best" flavours, Poly6::tr_phase, PolyClamped, Poly4, HybridSampling.
+ * Draws of one camera sample: 2 jitter (none without AA), 4 emitter, then 1 distance only when the sampler is Some — either `new` can return None, so every
+ * strategy takes the chain pass on reference-order streams (stats->ms_prepass, kernel_launches = 3).
+ * RL_PN_TAYLOR_EQ_PHASE and RL_PN_TAYLOR_EQ_CLAMPED_PHASE in an Isotropic medium are the reference's plain eq_ex / eq_clamped_ex (:1278): the call forwards to
+ * rl_render_point_normal, image and counters are its bytes.  RL_PN_TAYLOR_PN_PHASE with g = 0 (Isotropic counts as g = 0) meets assert!(g != 0.0) (:1414) at
+ * every sample: RL_ERR_UNSUPPORTED.  Defined (kernels/pntaylor.hip.h has the list): powi is __powisf2's order, Newton's factor is 2^-9, a div_zero solver
+ * gives the distance and pdf (0, 0) and so zero, EquiAngularSampling::new's assert (:42) is None.
+ * Stream modes, shards, the other refusals and their codes are rl_render_point_normal's.  Counters: camera_samples; rng_draws, the exact count; extension_rays =
+ * camera rays; shadow_rays = visible() calls; vertices = samples whose distance sampler was Some; ms_other = k_pn_pixel.
+ * The struct has rl_point_normal_params' fields and is declared in two statements like it; tests/test_pntaylor_abi.py holds it to its mirrors. */
+typedef enum rl_pn_taylor_strategy { RL_PN_TAYLOR_EQ_PHASE = 0, RL_PN_TAYLOR_EQ_TR = 1, RL_PN_TAYLOR_EQ_CLAMPED_PHASE = 2, RL_PN_TAYLOR_EQ_CLAMPED_TR = 3,
+                                     RL_PN_TAYLOR_PN_TR = 4, RL_PN_TAYLOR_PN_PHASE = 5 } rl_pn_taylor_strategy;
+struct rl_point_normal_taylor_params {
+    uint32_t spp;               /* scene.nb_samples */
+    int32_t strategy;           /* rl_pn_taylor_strategy */
+    int32_t use_aa;             /* !disable_aa */
+    int32_t stream_mode;        /* rl_stream_mode: reference order or per sample */
+    int32_t seed_variant;
+    uint32_t shard_index, shard_count;
+};
+typedef struct rl_point_normal_taylor_params rl_point_normal_taylor_params;
+void rl_point_normal_taylor_params_default(rl_point_normal_taylor_params* params);   /* strategy eq_tr_taylor_ex, AA on; spp 1, reference order, one shard */
+int rl_render_point_normal_taylor(rl_context* ctx, const rl_point_normal_taylor_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
+                                  rl_render_stats* stats);
+
 /* Frames in flight behind one call (the progressive wrappers' passes, avg.rs:5-131 / equal_time.rs:4-66: N independent renders of one scene): frame f — block
  * seeds `block_seeds[f]`, host image `out_rgb[f]` (W*H*3 f32) — renders on `ctxs[f % k]` from host thread f % k, k = min(n_ctx, n_frames); `ctxs` are distinct
  * contexts of the same scene.  Returns when every frame is done; the images (and `stats[f]`, if not NULL) are those of `n_frames` rl_render_path calls one after

@@ -42,6 +42,8 @@ PLANE_WORDS = 18                                          # RL_PLANE_WORDS: u32 
 PLANE_UV, PLANE_VT, PLANE_UT, PLANE_UALPHAT = 0, 1, 2, 3  # rl_plane_type
 PLANE_STRATEGIES = ("uv", "vt", "ut", "average", "discrete_mis", "ualpha", "cmis")      # rl_plane_strategy, by value: `plane-single -s`
 PN_STRATEGIES = ("tr_ex", "tr_phase", "eq_ex", "eq_phase", "eq_clamped_ex", "eq_clamped_phase", "pn_ex")      # rl_pn_strategy, by value: `point-normal -s`
+# rl_pn_taylor_strategy, by value: `point-normal-taylor -s`
+PN_TAYLOR_STRATEGIES = ("eq_phase_taylor_ex", "eq_tr_taylor_ex", "eq_clamped_phase_taylor_ex", "eq_clamped_tr_taylor_ex", "pn_tr_taylor_ex", "pn_phase_taylor_ex")
 RL_ERR_UNSUPPORTED, RL_ERR_NO_EMITTER = -7, -8
 
 # every symbol include/rustlight_amd.h declares (tests check the .so exports all of them)
@@ -51,7 +53,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_pplane_generate", "rl_pplane_generate_paths", "rl_pplane_info", "rl_pplane_read", "rl_pplane_destroy", "rl_pplane_map_build", "rl_pplane_map_build_words", "rl_pplane_map_info", "rl_pplane_map_read", "rl_pplane_map_destroy", "rl_render_photon_planes", "rl_vrl_map_build", "rl_vrl_map_build_words", "rl_vrl_map_info", "rl_vrl_map_read", "rl_vrl_map_destroy", "rl_render_vrl", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_point_normal_params_default", "rl_render_point_normal", "rl_point_normal_mis_params_default", "rl_render_point_normal_mis", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_pplane_generate", "rl_pplane_generate_paths", "rl_pplane_info", "rl_pplane_read", "rl_pplane_destroy", "rl_pplane_map_build", "rl_pplane_map_build_words", "rl_pplane_map_info", "rl_pplane_map_read", "rl_pplane_map_destroy", "rl_render_photon_planes", "rl_vrl_map_build", "rl_vrl_map_build_words", "rl_vrl_map_info", "rl_vrl_map_read", "rl_vrl_map_destroy", "rl_render_vrl", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_point_normal_params_default", "rl_render_point_normal", "rl_point_normal_mis_params_default", "rl_render_point_normal_mis", "rl_point_normal_taylor_params_default", "rl_render_point_normal_taylor", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -63,6 +65,12 @@ class PointNormalParams(C.Structure):
 
 class PointNormalMisParams(C.Structure):
     """rl_point_normal_mis_params (include/rustlight_amd.h): rl_point_normal_params' fields for IntegratorPointNormal with use_mis."""
+    _fields_ = [("spp", C.c_uint32), ("strategy", C.c_int32), ("use_aa", C.c_int32), ("stream_mode", C.c_int32), ("seed_variant", C.c_int32),
+                ("shard_index", C.c_uint32), ("shard_count", C.c_uint32)]
+
+
+class PointNormalTaylorParams(C.Structure):
+    """rl_point_normal_taylor_params (include/rustlight_amd.h): rl_point_normal_params' fields for IntegratorPointNormal's Taylor strategies."""
     _fields_ = [("spp", C.c_uint32), ("strategy", C.c_int32), ("use_aa", C.c_int32), ("stream_mode", C.c_int32), ("seed_variant", C.c_int32),
                 ("shard_index", C.c_uint32), ("shard_count", C.c_uint32)]
 
@@ -206,6 +214,9 @@ def lib():
     L.rl_point_normal_mis_params_default.argtypes = [C.POINTER(PointNormalMisParams)]
     L.rl_point_normal_mis_params_default.restype = None
     L.rl_render_point_normal_mis.argtypes = [vp, C.POINTER(PointNormalMisParams), u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
+    L.rl_point_normal_taylor_params_default.argtypes = [C.POINTER(PointNormalTaylorParams)]
+    L.rl_point_normal_taylor_params_default.restype = None
+    L.rl_render_point_normal_taylor.argtypes = [vp, C.POINTER(PointNormalTaylorParams), u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
     for fn in (L.rl_render_ao, L.rl_render_direct):
         fn.argtypes = [vp, C.POINTER(abi.McParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_multi_create.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -769,8 +780,17 @@ class Context(_ImageCalls):
         return self._render_pn(PointNormalMisParams(), lib().rl_point_normal_mis_params_default, lib().rl_render_point_normal_mis, seeds, strategy, spp, use_aa,
                                stream_mode, seed_variant, shard_index, shard_count)
 
+    def render_point_normal_taylor(self, seeds, strategy="eq_tr_taylor_ex", spp=1, use_aa=True, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0,
+                                   shard_count=1):
+        """IntegratorPointNormal's Taylor strategies (PN_TAYLOR_STRATEGIES) behind their block seeds through rl_render_point_normal_taylor: (image HxWx3 f32,
+        stats dict).  stats: camera_samples, rng_draws, extension_rays = camera rays, shadow_rays = visibility rays, vertices = samples whose distance sampler
+        was Some; ms_prepass = the chain pass in reference order, ms_other = k_pn_pixel.  The two eq phase polynomials in an isotropic medium are
+        render_point_normal's eq_ex / eq_clamped_ex; pn_phase_taylor_ex with g = 0 is refused."""
+        return self._render_pn(PointNormalTaylorParams(), lib().rl_point_normal_taylor_params_default, lib().rl_render_point_normal_taylor, seeds,
+                               pn_taylor_strategy(strategy), spp, use_aa, stream_mode, seed_variant, shard_index, shard_count)
+
     def _render_pn(self, p, defaults, render, seeds, strategy, spp, use_aa, stream_mode, seed_variant, shard_index, shard_count):
-        """render_point_normal and render_point_normal_mis: the params struct `p` filled by `defaults` and the arguments, one call of `render`."""
+        """render_point_normal, render_point_normal_mis and render_point_normal_taylor (which hands its strategy's value): the params struct `p` filled by `defaults` and the arguments, one call of `render`."""
         defaults(C.byref(p))
         p.spp, p.strategy, p.use_aa, p.stream_mode, p.seed_variant = spp, pn_strategy(strategy), int(bool(use_aa)), stream_mode, seed_variant
         p.shard_index, p.shard_count = shard_index, shard_count
@@ -1411,6 +1431,15 @@ def pn_strategy(strategy):
     return int(strategy)
 
 
+def pn_taylor_strategy(strategy):
+    """rl_pn_taylor_strategy of a name of PN_TAYLOR_STRATEGIES (or of its value)."""
+    if isinstance(strategy, str):
+        if strategy not in PN_TAYLOR_STRATEGIES:
+            raise ValueError(f"invalid strategy: {strategy} ({', '.join(PN_TAYLOR_STRATEGIES)})")
+        return PN_TAYLOR_STRATEGIES.index(strategy)
+    return int(strategy)
+
+
 class IntegratorPointNormal(_Integrator):
     """struct IntegratorPointNormal { strategy, use_mis, warps, warps_strategy, splitting, use_aa } (src/integrators/explicit/point_normal.rs:1172-1179) +
     Integrator::compute -> compute_mc, seed for seed the reference: the block seeds straight from the main sampler, then rl_render_point_normal.  The seven
@@ -1442,6 +1471,22 @@ class IntegratorPointNormalMis(_Integrator):
         w, h = scene.size
         seeds = sampler.block_seeds(w, h)
         img, self.last_stats = ctx.render_point_normal_mis(seeds, self.strategy, nb_samples, self.use_aa, self.stream_mode, sampler.variant)
+        return img
+
+
+class IntegratorPointNormalTaylor(_Integrator):
+    """IntegratorPointNormal with one of the six Taylor strategies of PN_TAYLOR_STRATEGIES (src/integrators/explicit/point_normal.rs:1276-1290, 1404-1418) +
+    Integrator::compute -> compute_mc, seed for seed the reference: the block seeds straight from the main sampler, then rl_render_point_normal_taylor."""
+
+    def __init__(self, strategy="eq_tr_taylor_ex", use_aa=True, stream_mode=STREAM_REFERENCE_ORDER, device=0, options=None):
+        super().__init__(device, options)
+        self.strategy, self.use_aa, self.stream_mode = PN_TAYLOR_STRATEGIES[pn_taylor_strategy(strategy)], use_aa, stream_mode
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        ctx = self._context(scene)
+        w, h = scene.size
+        seeds = sampler.block_seeds(w, h)
+        img, self.last_stats = ctx.render_point_normal_taylor(seeds, self.strategy, nb_samples, self.use_aa, self.stream_mode, sampler.variant)
         return img
 
 

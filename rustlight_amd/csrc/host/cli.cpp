@@ -35,6 +35,9 @@
 //               | point-normal-mis [-s|--strategy NAME] [-z|--disable-aa]   (the reference's `point-normal -x`: IntegratorPointNormal with use_mis; NAME is one
 //                 of point-normal's seven, of which only the distance family matters; the limits and refusals of point-normal; -x, -k, -w, --warps-strategy
 //                 and the flavoured strategies are refused by name)
+//               | point-normal-taylor [-s|--strategy eq_phase_taylor_ex|eq_tr_taylor_ex|eq_clamped_phase_taylor_ex|eq_clamped_tr_taylor_ex|pn_tr_taylor_ex|
+//                 pn_phase_taylor_ex] [-z|--disable-aa]   (the reference's `point-normal -s <a Taylor name>`; default eq_tr_taylor_ex; the limits and refusals
+//                 of point-normal; -x, -k, -w, --warps-strategy, the plain names and the warp / best names are refused by name)
 // Note `-n` / `-m` / `-r` / `-s` mean spp / medium / sampler / scale before the subcommand and
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 //
@@ -475,7 +478,8 @@ static Rendered run_plane(const Args& s, IndependentSampler& sampler, Scene& sce
 }
 
 // ---- IntegratorPointNormal (cli.rs:209-224) and IntegratorPointNormalMis, the reference's `-x`: the seven plain strategies on either kind of streams — of
-// which the MIS estimators read the distance family —; everything else of the reference's subcommand is refused by name
+// which the MIS estimators read the distance family —, and IntegratorPointNormalTaylor, the six Taylor strategies; everything else of the reference's
+// subcommand is refused by name
 
 static bool option_point_normal(Args& s, const std::string& a, Words& w) {
     if (a == "-s" || a == "--strategy") s.strategy = w.value();
@@ -500,10 +504,28 @@ static void check_point_normal(Args& s) {
     refuse_limits(s, s.mode, true);      // both stream modes: the one given passes
     refuse_no_medium(s);
 }
+// point-normal-taylor: the six Taylor names of cli.rs:455-492 and nothing else of the reference's -s
+static void check_point_normal_taylor(Args& s) {
+    static const char* const names[] = {"eq_phase_taylor_ex", "eq_tr_taylor_ex", "eq_clamped_phase_taylor_ex", "eq_clamped_tr_taylor_ex", "pn_tr_taylor_ex",
+                                        "pn_phase_taylor_ex"};      // rl_pn_taylor_strategy, by value
+    static const char* const others[] = {"tr_ex", "tr_phase", "eq_ex", "eq_phase", "eq_clamped_ex", "eq_clamped_phase", "pn_ex", "eq_best_ex", "eq_warp_ex",
+                                         "eq_clamped_best_ex", "eq_clamped_warp_ex", "pn_warp_ex", "pn_best_ex"};
+    const char* list = "eq_phase_taylor_ex, eq_tr_taylor_ex, eq_clamped_phase_taylor_ex, eq_clamped_tr_taylor_ex, pn_tr_taylor_ex, pn_phase_taylor_ex";
+    const std::string strategy = s.strategy.value_or("eq_tr_taylor_ex");
+    if (find_name(strategy, others) >= 0) quit(2, "%s: -s %s is not built (%s)\n", s.cmd->name, strategy.c_str(), list);
+    if ((s.strategy_index = find_name(strategy, names)) < 0) quit(2, "invalid strategy: %s (%s)\n", strategy.c_str(), list);
+    if (!s.unbuilt.empty()) quit(2, "point-normal-taylor: %s is not built (MIS, splitting and the warps are left out)\n", s.unbuilt.c_str());
+    if (s.use_ats) quit(2, "%s: -x ats is not built (the light tree's emitter sampling is left out)\n", s.cmd->name);
+    refuse_limits(s, s.mode, true);      // both stream modes: the one given passes
+    refuse_no_medium(s);
+    const Medium m = parse_medium(s.medium);
+    if (s.strategy_index == RL_PN_TAYLOR_PN_PHASE && (m.n_parts < 3 || m.g == 0.0f))
+        quit(2, "%s: -s pn_phase_taylor_ex needs a Henyey-Greenstein medium with g != 0 (-m SIGMA_S:SIGMA_A:G; the reference asserts g != 0.0, point_normal.rs:1414)\n", s.cmd->name);
+}
 template <class Integrator>
 static Rendered run_point_normal(const Args& s, IndependentSampler& sampler, Scene& scene) {
     Integrator it;
-    it.strategy = (rl_pn_strategy)s.strategy_index;
+    it.strategy = (decltype(it.strategy))s.strategy_index;
     it.use_aa = !s.disable_aa;
     it.stream_mode = s.mode;
     it.device = s.device;
@@ -525,6 +547,7 @@ static const Subcommand SUBCOMMANDS[] = {
     {"plane-single", nullptr, false, false, option_plane, check_plane, run_plane},
     {"point-normal", nullptr, false, false, option_point_normal, check_point_normal<IntegratorPointNormal>, run_point_normal<IntegratorPointNormal>},
     {"point-normal-mis", nullptr, false, false, option_point_normal, check_point_normal<IntegratorPointNormalMis>, run_point_normal<IntegratorPointNormalMis>},
+    {"point-normal-taylor", nullptr, false, false, option_point_normal, check_point_normal_taylor, run_point_normal<IntegratorPointNormalTaylor>},
 };
 static const Subcommand* find_subcommand(const std::string& a) {
     for (const Subcommand& c : SUBCOMMANDS) if (a == c.name || (c.alias && a == c.alias)) return &c;

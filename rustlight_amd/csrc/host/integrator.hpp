@@ -500,7 +500,7 @@ struct IntegratorSinglePlaneUncorrelated {
     }
 };
 
-// compute of the two point-normal structs below: the block seeds straight from the main sampler, `self`'s fields into the params `defaults` fills, `render`
+// compute of the three point-normal structs below: the block seeds straight from the main sampler, `self`'s fields into the params `defaults` fills, `render`
 template <class Self, class Params>
 BufferCollection compute_point_normal(Self& self, IndependentSampler& sampler, Scene& scene, void (*defaults)(Params*),
                                       int (*render)(rl_context*, const Params*, const uint64_t*, size_t, float*, rl_render_stats*), const char* what) {
@@ -539,6 +539,20 @@ struct IntegratorPointNormalMis {
     rl_render_stats last_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
         return compute_point_normal(*this, sampler, scene, rl_point_normal_mis_params_default, rl_render_point_normal_mis, "point-normal-mis");
+    }
+};
+
+// IntegratorPointNormal with one of its six Taylor strategies (point_normal.rs:1276-1290, 1404-1418): TaylorSampling or PointNormalTaylorSampling behind
+// compute_single_strategy's EX arm, through rl_render_point_normal_taylor.  A struct of its own, as IntegratorPointNormalMis is.
+struct IntegratorPointNormalTaylor {
+    rl_pn_taylor_strategy strategy = RL_PN_TAYLOR_EQ_TR;
+    bool use_aa = true;
+    rl_stream_mode stream_mode = RL_STREAM_REFERENCE_ORDER;
+    int device = 0;
+    Options options;
+    rl_render_stats last_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        return compute_point_normal(*this, sampler, scene, rl_point_normal_taylor_params_default, rl_render_point_normal_taylor, "point-normal-taylor");
     }
 };
 

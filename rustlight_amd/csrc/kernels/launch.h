@@ -1,5 +1,5 @@
 // launch.h — host-side launchers of the kernel families that live in their own translation units (fused_*.hip, fusedq_*.hip, fused_strat_*.hip,
-// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, beamgen_*.hip, beam_*.hip, pplanegen_*.hip, pplane_*.hip, vrl_*.hip, plane_*.hip, uplane_*.hip, pn_*.hip, pnmis_*.hip), so that the families compile in parallel, and
+// chain_*.hip, spec_*.hip, shade.hip, shade_strat.hip, mc.hip, mc_strat.hip, light_*.hip, vpl_*.hip, vpl_paths_*.hip, bre_*.hip, beamgen_*.hip, beam_*.hip, pplanegen_*.hip, pplane_*.hip, vrl_*.hip, plane_*.hip, uplane_*.hip, pn_*.hip, pnmis_*.hip, pntaylor_*.hip), so that the families compile in parallel, and
 // the dispatcher every one of them maps its run-time arguments to template arguments with (with_bsdf, with_flag).  Launch errors are picked up by
 // the caller's hipGetLastError().
 #pragma once
@@ -197,6 +197,7 @@ struct PnConst {
     int mode;                           // PN_MODE_*
     unsigned draws;                     // PN_MODE_ADVANCE: D, the draws of one camera sample
     unsigned long long* pixel_states;   // [pixel item][4] the block sampler's state at the pixel's first sample: k_pn_chain writes, k_pn_pixel reads (PN_MODE_GIVEN)
+    float taylor[8];                    // PnTaylor's phase strategies: Poly6::phase(g)'s seven coefficients and clamp_angle_phase(g), which the frame fixes (pntaylor_render.hip.h)
 };
 
 // mat: the scene's one BSDF type, or -1 = run-time switch per vertex.  area_only: every emitter is a mesh area light and there is no light
@@ -279,6 +280,10 @@ void launch_pn_stream(bool chain, int strategy, dim3 grid, dim3 block, size_t ld
 // family = PNMIS_* (0 tr, 1 eq, 2 clamped, 3 pn); the constants are point-normal's PnConst and PN_MODE_*
 void launch_pnmis_lds(bool chain, int family, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
 void launch_pnmis_stream(bool chain, int family, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
+// IntegratorPointNormal's Taylor strategies (pntaylor.hip.h): chain = false k_pn_pixel<.., PnTaylor<strategy>>, true k_pn_chain<.., PnTaylor<strategy>> (every
+// strategy's count depends on the data); strategy = rl_pn_taylor_strategy; the constants are point-normal's PnConst, with pc.taylor for the phase polynomials
+void launch_pntaylor_lds(bool chain, int strategy, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
+void launch_pntaylor_stream(bool chain, int strategy, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)
 void dump_stage_timers_stream();
 void dump_chain_timers_lds();      // dev-only (-DRL_STAGE_TIMERS): cycle shares of k_stream_chain's stages

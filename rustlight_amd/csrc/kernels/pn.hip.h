@@ -25,7 +25,8 @@
 //
 // Numerics: atan(x) = atan2f_det(x, 1), tan(x) = the IEEE quotient sinf_det(x) / cosf_det(x) (it departs from libm's tan by this construction), powi(2) = x * x.
 //
-// Drivers, templates over a sample body: PnPlain<STRATEGY> here (k_pn_pixel<LDS_SCENE, PnPlain<STRATEGY>>), PnMis<FAMILY> in pnmis.hip.h.  k_pn_pixel: one
+// Drivers, templates over a sample body: PnPlain<STRATEGY> here (k_pn_pixel<LDS_SCENE, PnPlain<STRATEGY>>), PnMis<FAMILY> in pnmis.hip.h, PnTaylor<STRATEGY>
+// in pntaylor.hip.h; a body is handed the launch's PnConst, which only PnTaylor reads.  k_pn_pixel: one
 // lane per pixel, its samples in series (the pixel sum keeps the reference's order), pixels in compute_mc's order (iy outer, ix inner, mod.rs:420-435); the
 // lane's sampler is (a) forked per sample from the pixel's seed (k_seed_pixels), (b) the block's stream entered c * spp * D draws down by rng_advance when the
 // count D is constant, (c) the state k_pn_chain recorded for the pixel when it is not; or, as the cross-check of (b) and (c), one lane per block walks the
@@ -254,7 +255,7 @@ struct PnPlain {
     static constexpr int kWaves = kPnWaves;
     struct Counts { unsigned rays = 0, vertices = 0; };
     template <class Stack, class Park>
-    static RL_DEV Col sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool aa, unsigned px, unsigned py, Rng& rng, Park&& park, Counts& n) {
+    static RL_DEV Col sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool aa, unsigned px, unsigned py, Rng& rng, Park&& park, Counts& n, const PnConst&) {
         return pn_sample<STRATEGY>(sc, recs, stack, aa, px, py, rng, park, n.rays, n.vertices);
     }
     // three rows; the host derives the five counters from them (pn_render.hip.h): a sample's draws follow from its strategy and from whether it had a
@@ -265,7 +266,7 @@ struct PnPlain {
         block_stats<3>(rc.partials, which, vals);
     }
     // Some | None by pn_make_sampler, the statements pn_sample decides it with: 1 or 3 draws behind a sampler, none without
-    static RL_DEV unsigned chain_skip(const DeviceScene& sc, bool has_max, float max_dist, V3 o, V3 d, float r_sel, float r_pos, V2 uv) {
+    static RL_DEV unsigned chain_skip(const DeviceScene& sc, bool has_max, float max_dist, V3 o, V3 d, float r_sel, float r_pos, V2 uv, const PnConst&) {
         const PnEmitter em = pn_sample_emitter(sc, r_sel, r_pos, uv);
         PnDist ds;
         if (!pn_make_sampler<STRATEGY>(has_max, max_dist, o, d, em.p, em.n, &ds)) return 0u;
@@ -320,7 +321,7 @@ __global__ void __launch_bounds__(256, Body::kWaves) k_pn_pixel(RenderConst rc, 
                     rng = rng_seed(seed, rc.seed_variant);
                 }
                 const auto park = [&](const Rng& r) { if (pc.mode != PN_MODE_PER_SAMPLE) pn_store_state(pc.pixel_states, item, r); };
-                const Col l = Body::sample(sc, recs, stack, pc.use_aa != 0, px, py, rng, park, counts);
+                const Col l = Body::sample(sc, recs, stack, pc.use_aa != 0, px, py, rng, park, counts, pc);
                 const float r = out[0] + l.r, g = out[1] + l.g, b = out[2] + l.b;      // im_block.accumulate, in sample order
                 out[0] = r; out[1] = g; out[2] = b;
             }
@@ -358,7 +359,7 @@ __global__ void __launch_bounds__(256, kPnWaves) k_pn_chain(RenderConst rc, Devi
             const bool has_max = trace_closest(sc, recs, stack, o, d, hit);
             const float r_sel = rng_next_f32(rng), r_pos = rng_next_f32(rng);
             const V2 uv = smp_next2d(rng);
-            const unsigned skip = Body::chain_skip(sc, has_max, hit.t, o, d, r_sel, r_pos, uv);
+            const unsigned skip = Body::chain_skip(sc, has_max, hit.t, o, d, r_sel, r_pos, uv, pc);
             for (unsigned k = 0; k < skip; k++) rng_next_u64(rng);
         }
     }

@@ -1,5 +1,6 @@
 // pn_render.hip.h — the host side of the point-normal single-scattering integrator (included by wavefront.hip after pplane_render.hip.h; host code only):
-// rl_render_point_normal, patterned on render_mc, and render_pn, the one frame sequence it shares with rl_render_point_normal_mis (pnmis_render.hip.h).
+// rl_render_point_normal, patterned on render_mc, and render_pn, the one frame sequence it shares with rl_render_point_normal_mis (pnmis_render.hip.h) and
+// rl_render_point_normal_taylor (pntaylor_render.hip.h).
 // IntegratorPointNormal: src/integrators/explicit/point_normal.rs:1172-1199, 2584-2633; the kernels are k_pn_pixel and k_pn_chain over the body
 // PnPlain<STRATEGY> (pn.hip.h).
 
@@ -36,13 +37,14 @@ static int check_pn_scene(const rl_context* ctx) {
     return RL_OK;
 }
 
-// What tells rl_render_point_normal and rl_render_point_normal_mis apart; render_pn below is everything else.
+// What tells rl_render_point_normal, rl_render_point_normal_mis and rl_render_point_normal_taylor apart; render_pn below is everything else.
 using PnLauncher = void (*)(bool, int, dim3, dim3, size_t, hipStream_t, const RenderConst&, const DeviceScene&, const StackConf&, const PnConst&);
 struct PnKind {
-    const char* name;                           // "point-normal" | "point-normal-mis", as the error strings say it
+    const char* name;                           // "point-normal" | "point-normal-mis" | "point-normal-taylor", as the error strings say it
     int selector;                               // what the launchers take: the strategy | the family
     unsigned draws;                             // the draws of one camera sample, the jitter's included; 0: the count depends on the data and the chain pass runs
     PnLauncher launch_lds, launch_stream;
+    float taylor[8] = {};                       // PnConst::taylor: point-normal-taylor's phase polynomial (pntaylor_render.hip.h); zero for the other kinds
 };
 
 // One frame of either kind: the checks, the four sampler modes (PN_MODE_*), the chain pass where the draw count depends on the data, the pixel kernel, and the
@@ -89,6 +91,7 @@ static int render_pn(rl_context* ctx, const Params* params, const uint64_t* bloc
     pc.mode = per_sample ? PN_MODE_PER_SAMPLE : single_pass ? PN_MODE_BLOCK : chain ? PN_MODE_GIVEN : PN_MODE_ADVANCE;
     pc.draws = kind.draws;
     pc.pixel_states = ctx->d_sample_states.get();
+    std::memcpy(pc.taylor, kind.taylor, sizeof(pc.taylor));
     StackConf stc;
     if ((rcode = stack_conf(ctx, n_threads, &stc)) != RL_OK) return rcode;
     const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);

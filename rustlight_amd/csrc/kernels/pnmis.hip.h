@@ -322,7 +322,7 @@ struct PnMis {
     static constexpr int kWaves = FAMILY == PNMIS_TR ? 4 : 3;
     struct Counts { unsigned phase = 0, vis = 0, vertices = 0; };
     template <class Stack, class Park>
-    static RL_DEV Col sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool aa, unsigned px, unsigned py, Rng& rng, Park&& park, Counts& n) {
+    static RL_DEV Col sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool aa, unsigned px, unsigned py, Rng& rng, Park&& park, Counts& n, const PnConst&) {
         return pnmis_sample<FAMILY>(sc, recs, stack, aa, px, py, rng, park, n.phase, n.vis, n.vertices);
     }
     // four rows; the host derives the five counters from them (pnmis_render.hip.h): a sample's draws follow from its family and from whether its third
@@ -333,7 +333,7 @@ struct PnMis {
         block_stats<4>(rc.partials, which, vals);
     }
     // clamped and pn: Some | None of the third sampler by pn_make_sampler, the statements pnmis_sample decides it with; 4 draws, and one more behind a sampler
-    static RL_DEV unsigned chain_skip(const DeviceScene& sc, bool has_max, float max_dist, V3 o, V3 d, float r_sel, float r_pos, V2 uv) {
+    static RL_DEV unsigned chain_skip(const DeviceScene& sc, bool has_max, float max_dist, V3 o, V3 d, float r_sel, float r_pos, V2 uv, const PnConst&) {
         const PnMisEmitter em = pnmis_sample_emitter(sc, r_sel, r_pos, uv);
         PnDist ds;
         return pn_make_sampler<PnMisThird<FAMILY>::strategy>(has_max, max_dist, o, d, em.p, em.n, &ds) ? 5u : 4u;

@@ -1,0 +1,9 @@
+// pntaylor_lds.hip — the point-normal integrator's Taylor strategies for scenes staged in LDS; see pntaylor.hip.h
+#include "common.hip.h"
+#include "pntaylor.hip.h"
+
+namespace rl {
+void launch_pntaylor_lds(bool chain, int strategy, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc) {
+    launch_pntaylor_impl<true>(chain, strategy, grid, block, lds_bytes, st, rc, ds, stc, pc);
+}
+}  // namespace rl

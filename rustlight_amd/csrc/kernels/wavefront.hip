@@ -1339,6 +1339,7 @@ extern "C" int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_pa
 #include "pplane_render.hip.h"
 #include "pn_render.hip.h"
 #include "pnmis_render.hip.h"
+#include "pntaylor_render.hip.h"
 
 // ---- batched Acceleration::{trace, visible}
 namespace {
