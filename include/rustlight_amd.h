@@ -768,6 +768,37 @@ void rl_point_normal_taylor_params_default(rl_point_normal_taylor_params* params
 int rl_render_point_normal_taylor(rl_context* ctx, const rl_point_normal_taylor_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
                                   rl_render_stats* stats);
 
+/* ---- IntegratorPointNormal over the light tree (the reference's `-x ats point-normal`; CLI `point-normal-ats`: `point-normal -x ats` stays refused).  The
+ * scene's emitters are built with the tree (rl_scene_build_emitters with build_ats); the sample bodies are rl_render_point_normal's (family RL_PN_ATS_PLAIN,
+ * strategy an rl_pn_strategy) and rl_render_point_normal_taylor's (RL_PN_ATS_TAYLOR, an rl_pn_taylor_strategy) but for where the emitter position comes from.
+ * Every strategy but the two tr_*: fix_random_sample_emitter's ATS arm (point_normal.rs:1217-1228) — next, next2d, LightSamplerATS::sample from the root with
+ * LightBounds::importance_ray(ray, max_dist) (emitter.rs:975-1032: the closest point of the segment, acos_fast, the stored angles theta_o and theta_e), then
+ * sample_position_tri.  tr_ex: the distance first, then random_sample_emitter_position_point(&p, None, ..) at the scattering point (:2237-2243).  tr_phase
+ * takes no emitter sample and renders rl_render_point_normal's bytes of the same scene without the tree.
+ * Draws of one camera sample behind the jitter's 2: tr_ex 4, tr_phase 3, eq_ex 4, eq_phase 6, eq_clamped_ex and pn_ex 3 | 4, eq_clamped_phase 3 | 6, the
+ * Taylor names 3 | 4 (one less than over the power pick); the data-dependent ones take the chain pass, which walks the tree as the sample does.
+ * Defined where the reference panics: importance_ray's assert!(cos_phi_0.is_finite()) (emitter.rs:1008; the cluster's centre on the ray's line, or its axis
+ * normal to the plane of the segment's ends seen from the centre) gives the node importance 0; LightSamplerATS::new's assert that every emitter is a surface:
+ * a scene with a point, directional or environment light is RL_ERR_UNSUPPORTED, as is a scene without the tree.  Kept: two children of importance 0 give
+ * prob_left = 0.5.  The Taylor names' forward in an Isotropic medium (to the plain strategy over the tree) and the g = 0 refusal are
+ * rl_render_point_normal_taylor's; stream modes, shards, the other refusals, their codes and the counters are rl_render_point_normal's (D in the reach check
+ * 256 * spp * D is the count above plus the jitter's).  Not built: MIS over the tree, splitting, the warp and best flavours, point lights in the tree.
+ * The struct has rl_point_normal_params' fields, then the family, and is declared in two statements like it; tests/test_pnats_abi.py holds it to its mirrors. */
+typedef enum rl_pn_ats_family { RL_PN_ATS_PLAIN = 0, RL_PN_ATS_TAYLOR = 1 } rl_pn_ats_family;
+struct rl_point_normal_ats_params {
+    uint32_t spp;               /* scene.nb_samples */
+    int32_t strategy;           /* family plain: an rl_pn_strategy | family Taylor: an rl_pn_taylor_strategy */
+    int32_t use_aa;             /* !disable_aa */
+    int32_t stream_mode;        /* rl_stream_mode: reference order or per sample */
+    int32_t seed_variant;
+    uint32_t shard_index, shard_count;
+    int32_t family;             /* rl_pn_ats_family: which names `strategy` is one of */
+};
+typedef struct rl_point_normal_ats_params rl_point_normal_ats_params;
+void rl_point_normal_ats_params_default(rl_point_normal_ats_params* params);   /* family plain, strategy eq_ex, AA on; spp 1, reference order, one shard */
+int rl_render_point_normal_ats(rl_context* ctx, const rl_point_normal_ats_params* params, const uint64_t* block_seeds, size_t n_blocks, float* out_rgb,
+                               rl_render_stats* stats);
+
 /* Frames in flight behind one call (the progressive wrappers' passes, avg.rs:5-131 / equal_time.rs:4-66: N independent renders of one scene): frame f — block
  * seeds `block_seeds[f]`, host image `out_rgb[f]` (W*H*3 f32) — renders on `ctxs[f % k]` from host thread f % k, k = min(n_ctx, n_frames); `ctxs` are distinct
  * contexts of the same scene.  Returns when every frame is done; the images (and `stats[f]`, if not NULL) are those of `n_frames` rl_render_path calls one after

@@ -44,6 +44,8 @@ PLANE_STRATEGIES = ("uv", "vt", "ut", "average", "discrete_mis", "ualpha", "cmis
 PN_STRATEGIES = ("tr_ex", "tr_phase", "eq_ex", "eq_phase", "eq_clamped_ex", "eq_clamped_phase", "pn_ex")      # rl_pn_strategy, by value: `point-normal -s`
 # rl_pn_taylor_strategy, by value: `point-normal-taylor -s`
 PN_TAYLOR_STRATEGIES = ("eq_phase_taylor_ex", "eq_tr_taylor_ex", "eq_clamped_phase_taylor_ex", "eq_clamped_tr_taylor_ex", "pn_tr_taylor_ex", "pn_phase_taylor_ex")
+# `point-normal-ats -s`: the plain names (rl_pn_ats_family 0) and the Taylor names (1), each with its family's strategy value
+PN_ATS_STRATEGIES = PN_STRATEGIES + PN_TAYLOR_STRATEGIES
 RL_ERR_UNSUPPORTED, RL_ERR_NO_EMITTER = -7, -8
 
 # every symbol include/rustlight_amd.h declares (tests check the .so exports all of them)
@@ -53,7 +55,7 @@ PUBLIC_SYMBOLS = [
     "rl_scene_set_environment", "rl_scene_set_environment_map", "rl_scene_build_emitters", "rl_scene_enable_ats", "rl_scene_load_pbrt", "rl_scene_load_mitsuba", "rl_scene_load",
     "rl_scene_image_size", "rl_scene_counts", "rl_sampler_seed", "rl_sampler_next_u64", "rl_sampler_next_f32",
     "rl_path_params_default", "rl_device_count", "rl_context_create", "rl_context_destroy", "rl_context_set_option", "rl_context_get_option", "rl_last_error", "rl_block_count",
-    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_pplane_generate", "rl_pplane_generate_paths", "rl_pplane_info", "rl_pplane_read", "rl_pplane_destroy", "rl_pplane_map_build", "rl_pplane_map_build_words", "rl_pplane_map_info", "rl_pplane_map_read", "rl_pplane_map_destroy", "rl_render_photon_planes", "rl_vrl_map_build", "rl_vrl_map_build_words", "rl_vrl_map_info", "rl_vrl_map_read", "rl_vrl_map_destroy", "rl_render_vrl", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_point_normal_params_default", "rl_render_point_normal", "rl_point_normal_mis_params_default", "rl_render_point_normal_mis", "rl_point_normal_taylor_params_default", "rl_render_point_normal_taylor", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
+    "rl_generate_block_seeds", "rl_render_path", "rl_render_path_frames", "rl_multi_create", "rl_multi_destroy", "rl_multi_info", "rl_multi_describe", "rl_multi_shard_stats", "rl_multi_render_path", "rl_render_ao", "rl_render_direct", "rl_render_light", "rl_vpl_generate", "rl_vpl_generate_paths", "rl_vpl_info", "rl_vpl_read", "rl_vpl_destroy", "rl_render_vpl", "rl_photon_map_build", "rl_photon_map_info", "rl_photon_map_destroy", "rl_render_bre", "rl_photon_tree_build", "rl_photon_map_build_device", "rl_photon_tree_build_device", "rl_photon_map_read", "rl_beam_generate", "rl_beam_generate_paths", "rl_beam_info", "rl_beam_read", "rl_beam_destroy", "rl_beam_split", "rl_beam_tree_build", "rl_beam_map_build", "rl_beam_map_build_words", "rl_beam_map_info", "rl_beam_map_read", "rl_beam_map_destroy", "rl_render_beams", "rl_pplane_generate", "rl_pplane_generate_paths", "rl_pplane_info", "rl_pplane_read", "rl_pplane_destroy", "rl_pplane_map_build", "rl_pplane_map_build_words", "rl_pplane_map_info", "rl_pplane_map_read", "rl_pplane_map_destroy", "rl_render_photon_planes", "rl_vrl_map_build", "rl_vrl_map_build_words", "rl_vrl_map_info", "rl_vrl_map_read", "rl_vrl_map_destroy", "rl_render_vrl", "rl_plane_generate", "rl_plane_info", "rl_plane_read", "rl_plane_destroy", "rl_plane_tree_build", "rl_plane_map_build", "rl_plane_map_info", "rl_plane_map_read", "rl_plane_map_destroy", "rl_plane_generate_lanes", "rl_plane_map_build_device", "rl_plane_tree_build_device", "rl_render_plane_single", "rl_render_plane_uncorrelated", "rl_point_normal_params_default", "rl_render_point_normal", "rl_point_normal_mis_params_default", "rl_render_point_normal_mis", "rl_point_normal_taylor_params_default", "rl_render_point_normal_taylor", "rl_point_normal_ats_params_default", "rl_render_point_normal_ats", "rl_trace_batch", "rl_visible_batch", "rl_load_pfm", "rl_load_image", "rl_save_pfm", "rl_save_png", "rl_save_exr", "rl_save_image", "rl_build_info",
 ]
 
 
@@ -73,6 +75,12 @@ class PointNormalTaylorParams(C.Structure):
     """rl_point_normal_taylor_params (include/rustlight_amd.h): rl_point_normal_params' fields for IntegratorPointNormal's Taylor strategies."""
     _fields_ = [("spp", C.c_uint32), ("strategy", C.c_int32), ("use_aa", C.c_int32), ("stream_mode", C.c_int32), ("seed_variant", C.c_int32),
                 ("shard_index", C.c_uint32), ("shard_count", C.c_uint32)]
+
+
+class PointNormalAtsParams(C.Structure):
+    """rl_point_normal_ats_params (include/rustlight_amd.h): rl_point_normal_params' fields, then the name family, for IntegratorPointNormal over the light tree."""
+    _fields_ = [("spp", C.c_uint32), ("strategy", C.c_int32), ("use_aa", C.c_int32), ("stream_mode", C.c_int32), ("seed_variant", C.c_int32),
+                ("shard_index", C.c_uint32), ("shard_count", C.c_uint32), ("family", C.c_int32)]
 
 
 class RustlightError(RuntimeError):
@@ -217,6 +225,9 @@ def lib():
     L.rl_point_normal_taylor_params_default.argtypes = [C.POINTER(PointNormalTaylorParams)]
     L.rl_point_normal_taylor_params_default.restype = None
     L.rl_render_point_normal_taylor.argtypes = [vp, C.POINTER(PointNormalTaylorParams), u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
+    L.rl_point_normal_ats_params_default.argtypes = [C.POINTER(PointNormalAtsParams)]
+    L.rl_point_normal_ats_params_default.restype = None
+    L.rl_render_point_normal_ats.argtypes = [vp, C.POINTER(PointNormalAtsParams), u64p, C.c_size_t, f32p, C.POINTER(abi.RenderStats)]
     for fn in (L.rl_render_ao, L.rl_render_direct):
         fn.argtypes = [vp, C.POINTER(abi.McParams), u64p, C.c_size_t, vp, C.c_int, vp, C.POINTER(abi.RenderStats)]
     L.rl_multi_create.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -458,6 +469,16 @@ class Scene:
         nodes = np.zeros((nn.value, 16), np.float32); le = np.zeros(nl.value, np.int32); lp = np.zeros(nl.value, np.int32)
         _check(L.rl_debug_ats(self.h, C.byref(nn), abi.fptr(nodes), C.byref(nl), le.ctypes.data_as(i32p), lp.ctypes.data_as(i32p)))
         return nodes, le, lp
+
+    def debug_ats_angles(self):
+        """[n, 2] f32: LightBounds::theta_o, theta_e of debug_ats' nodes, as the host tree stores them (LightNode keeps their cosines)."""
+        L = lib()
+        L.rl_debug_ats_angles.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+        nn = C.c_uint64()
+        _check(L.rl_debug_ats_angles(self.h, C.byref(nn), None))
+        angles = np.zeros((nn.value, 2), np.float32)
+        _check(L.rl_debug_ats_angles(self.h, C.byref(nn), abi.fptr(angles)))
+        return angles
 
     def camera_ray(self, px, py):
         o = (C.c_float * 3)()
@@ -789,9 +810,20 @@ class Context(_ImageCalls):
         return self._render_pn(PointNormalTaylorParams(), lib().rl_point_normal_taylor_params_default, lib().rl_render_point_normal_taylor, seeds,
                                pn_taylor_strategy(strategy), spp, use_aa, stream_mode, seed_variant, shard_index, shard_count)
 
-    def _render_pn(self, p, defaults, render, seeds, strategy, spp, use_aa, stream_mode, seed_variant, shard_index, shard_count):
-        """render_point_normal, render_point_normal_mis and render_point_normal_taylor (which hands its strategy's value): the params struct `p` filled by `defaults` and the arguments, one call of `render`."""
+    def render_point_normal_ats(self, seeds, strategy="eq_ex", spp=1, use_aa=True, stream_mode=STREAM_REFERENCE_ORDER, seed_variant=0, shard_index=0, shard_count=1):
+        """IntegratorPointNormal over the light tree (a scene built with use_ats) behind its block seeds through rl_render_point_normal_ats: (image HxWx3 f32,
+        stats dict).  strategy: one of PN_ATS_STRATEGIES, or (family, value).  The emitter comes from the tree walked with the ray importance (tr_ex: with the
+        point importance at the scattering point) and takes three draws; the rest of a sample, the stats and the refusals are render_point_normal's and
+        render_point_normal_taylor's.  A scene without the tree, or with an emitter that is no surface, is refused."""
+        family, value = pn_ats_strategy(strategy)
+        return self._render_pn(PointNormalAtsParams(), lib().rl_point_normal_ats_params_default, lib().rl_render_point_normal_ats, seeds, value, spp, use_aa,
+                               stream_mode, seed_variant, shard_index, shard_count, family=family)
+
+    def _render_pn(self, p, defaults, render, seeds, strategy, spp, use_aa, stream_mode, seed_variant, shard_index, shard_count, family=None):
+        """render_point_normal, render_point_normal_mis, render_point_normal_taylor and render_point_normal_ats (which hand their strategy's value; the last also its family): the params struct `p` filled by `defaults` and the arguments, one call of `render`."""
         defaults(C.byref(p))
+        if family is not None:
+            p.family = family
         p.spp, p.strategy, p.use_aa, p.stream_mode, p.seed_variant = spp, pn_strategy(strategy), int(bool(use_aa)), stream_mode, seed_variant
         p.shard_index, p.shard_count = shard_index, shard_count
         img, st = self._image_call(seeds, lambda sp, n, out, st: render(self.h, C.byref(p), sp, n, out, st))
@@ -1431,6 +1463,16 @@ def pn_strategy(strategy):
     return int(strategy)
 
 
+def pn_ats_strategy(strategy):
+    """(rl_pn_ats_family, the strategy's value within it) of a name of PN_ATS_STRATEGIES, or of such a pair."""
+    if isinstance(strategy, str):
+        if strategy not in PN_ATS_STRATEGIES:
+            raise ValueError(f"invalid strategy: {strategy} ({', '.join(PN_ATS_STRATEGIES)})")
+        return (0, PN_STRATEGIES.index(strategy)) if strategy in PN_STRATEGIES else (1, PN_TAYLOR_STRATEGIES.index(strategy))
+    family, value = strategy
+    return int(family), int(value)
+
+
 def pn_taylor_strategy(strategy):
     """rl_pn_taylor_strategy of a name of PN_TAYLOR_STRATEGIES (or of its value)."""
     if isinstance(strategy, str):
@@ -1487,6 +1529,24 @@ class IntegratorPointNormalTaylor(_Integrator):
         w, h = scene.size
         seeds = sampler.block_seeds(w, h)
         img, self.last_stats = ctx.render_point_normal_taylor(seeds, self.strategy, nb_samples, self.use_aa, self.stream_mode, sampler.variant)
+        return img
+
+
+class IntegratorPointNormalAts(_Integrator):
+    """IntegratorPointNormal over the light tree with one of the names of PN_ATS_STRATEGIES (fix_random_sample_emitter's ATS arm,
+    src/integrators/explicit/point_normal.rs:1217-1228, and compute_single_tr's, :2237-2243) + Integrator::compute -> compute_mc, seed for seed the reference:
+    the block seeds straight from the main sampler, then rl_render_point_normal_ats.  The scene's emitters are built with the tree (use_ats)."""
+
+    def __init__(self, strategy="eq_ex", use_aa=True, stream_mode=STREAM_REFERENCE_ORDER, device=0, options=None):
+        super().__init__(device, options)
+        pn_ats_strategy(strategy)
+        self.strategy, self.use_aa, self.stream_mode = strategy, use_aa, stream_mode
+
+    def compute(self, sampler: IndependentSampler, scene: Scene, nb_samples: int = 1):
+        ctx = self._context(scene)
+        w, h = scene.size
+        seeds = sampler.block_seeds(w, h)
+        img, self.last_stats = ctx.render_point_normal_ats(seeds, self.strategy, nb_samples, self.use_aa, self.stream_mode, sampler.variant)
         return img
 
 

@@ -12,7 +12,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "librustlight_amd.so")
 BIN = os.path.join(LIB_DIR, "rustlight-amd")
 
-HIP_SOURCES = ["kernels/wavefront.hip", "kernels/fused_lds.hip", "kernels/fused_stream.hip", "kernels/fusedq_lds.hip", "kernels/fusedq_stream.hip", "kernels/fused_lds_fast.hip", "kernels/fused_stream_fast.hip", "kernels/chain_lds.hip", "kernels/chain_stream.hip", "kernels/chain_lds_fast.hip", "kernels/chain_stream_fast.hip", "kernels/spec_lds.hip", "kernels/spec_stream.hip", "kernels/shade.hip", "kernels/mc.hip", "kernels/fused_strat_lds.hip", "kernels/fused_strat_stream.hip", "kernels/shade_strat.hip", "kernels/mc_strat.hip", "kernels/light_lds.hip", "kernels/light_stream.hip", "kernels/vpl_lds.hip", "kernels/vpl_stream.hip", "kernels/vpl_paths_lds.hip", "kernels/vpl_paths_stream.hip", "kernels/bre_lds.hip", "kernels/bre_stream.hip", "kernels/beamgen_lds.hip", "kernels/beamgen_stream.hip", "kernels/beam_lds.hip", "kernels/beam_stream.hip", "kernels/pplanegen_lds.hip", "kernels/pplanegen_stream.hip", "kernels/pplane_lds.hip", "kernels/pplane_stream.hip", "kernels/vrl_lds.hip", "kernels/vrl_stream.hip", "kernels/plane_lds.hip", "kernels/plane_stream.hip", "kernels/plane_generate.hip", "kernels/uplane_lds.hip", "kernels/uplane_stream.hip", "kernels/pn_lds.hip", "kernels/pn_stream.hip", "kernels/pnmis_lds.hip", "kernels/pnmis_stream.hip", "kernels/pntaylor_lds.hip", "kernels/pntaylor_stream.hip", "kernels/phototree.hip", "kernels/planetree.hip", "host/multigpu.hip"]     # multigpu.hip: N device contexts + the RCCL framebuffer reduce
+HIP_SOURCES = ["kernels/wavefront.hip", "kernels/fused_lds.hip", "kernels/fused_stream.hip", "kernels/fusedq_lds.hip", "kernels/fusedq_stream.hip", "kernels/fused_lds_fast.hip", "kernels/fused_stream_fast.hip", "kernels/chain_lds.hip", "kernels/chain_stream.hip", "kernels/chain_lds_fast.hip", "kernels/chain_stream_fast.hip", "kernels/spec_lds.hip", "kernels/spec_stream.hip", "kernels/shade.hip", "kernels/mc.hip", "kernels/fused_strat_lds.hip", "kernels/fused_strat_stream.hip", "kernels/shade_strat.hip", "kernels/mc_strat.hip", "kernels/light_lds.hip", "kernels/light_stream.hip", "kernels/vpl_lds.hip", "kernels/vpl_stream.hip", "kernels/vpl_paths_lds.hip", "kernels/vpl_paths_stream.hip", "kernels/bre_lds.hip", "kernels/bre_stream.hip", "kernels/beamgen_lds.hip", "kernels/beamgen_stream.hip", "kernels/beam_lds.hip", "kernels/beam_stream.hip", "kernels/pplanegen_lds.hip", "kernels/pplanegen_stream.hip", "kernels/pplane_lds.hip", "kernels/pplane_stream.hip", "kernels/vrl_lds.hip", "kernels/vrl_stream.hip", "kernels/plane_lds.hip", "kernels/plane_stream.hip", "kernels/plane_generate.hip", "kernels/uplane_lds.hip", "kernels/uplane_stream.hip", "kernels/pn_lds.hip", "kernels/pn_stream.hip", "kernels/pnmis_lds.hip", "kernels/pnmis_stream.hip", "kernels/pntaylor_lds.hip", "kernels/pntaylor_stream.hip", "kernels/pnats_lds.hip", "kernels/pnats_stream.hip", "kernels/phototree.hip", "kernels/planetree.hip", "host/multigpu.hip"]     # multigpu.hip: N device contexts + the RCCL framebuffer reduce
 CXX_SOURCES = ["host/frames.cpp", "host/scene.cpp", "host/bvh.cpp", "host/io.cpp", "host/pbrt.cpp", "host/meshio.cpp", "host/mitsuba.cpp", "host/lighttree.cpp", "host/photontree.cpp", "host/planetree.cpp", "host/beamtree.cpp"]
 # -ffp-contract=off: rustlight's f32 arithmetic is never contracted into FMAs
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-value", "-Wno-unused-function"]

@@ -38,6 +38,10 @@
 //               | point-normal-taylor [-s|--strategy eq_phase_taylor_ex|eq_tr_taylor_ex|eq_clamped_phase_taylor_ex|eq_clamped_tr_taylor_ex|pn_tr_taylor_ex|
 //                 pn_phase_taylor_ex] [-z|--disable-aa]   (the reference's `point-normal -s <a Taylor name>`; default eq_tr_taylor_ex; the limits and refusals
 //                 of point-normal; -x, -k, -w, --warps-strategy, the plain names and the warp / best names are refused by name)
+//               | point-normal-ats [-s|--strategy NAME] [-z|--disable-aa]   (the reference's `-x ats point-normal`: the emitter from the light tree, walked
+//                 with the ray importance; NAME is one of point-normal's seven or of point-normal-taylor's six, default eq_ex; the scene's emitters are built
+//                 with the tree whether or not `-x ats` is given; the limits and refusals of point-normal-taylor; -x (MIS), -k, -w, --warps-strategy and the
+//                 warp / best names are refused by name)
 // Note `-n` / `-m` / `-r` / `-s` mean spp / medium / sampler / scale before the subcommand and
 // min-depth / max-depth / rr-depth / strategy after it, exactly as in the reference.
 //
@@ -148,6 +152,7 @@ struct Args {
     // what the subcommand's `check` and the sampler parse made of them, for `run`
     std::optional<uint32_t> max, min, rr;
     int strategy_index = 0, lt_index = 0, vpl_index = 0;
+    int family = 0;      // point-normal-ats: rl_pn_ats_family of the strategy's name
     uint32_t count = 0;
     float radius_value = 0.0f;
     LightStreams streams = LightStreams::Reference;
@@ -478,8 +483,8 @@ static Rendered run_plane(const Args& s, IndependentSampler& sampler, Scene& sce
 }
 
 // ---- IntegratorPointNormal (cli.rs:209-224) and IntegratorPointNormalMis, the reference's `-x`: the seven plain strategies on either kind of streams — of
-// which the MIS estimators read the distance family —, and IntegratorPointNormalTaylor, the six Taylor strategies; everything else of the reference's
-// subcommand is refused by name
+// which the MIS estimators read the distance family —, IntegratorPointNormalTaylor, the six Taylor strategies, and IntegratorPointNormalAts, both sets of
+// names over the light tree; everything else of the reference's subcommand is refused by name
 
 static bool option_point_normal(Args& s, const std::string& a, Words& w) {
     if (a == "-s" || a == "--strategy") s.strategy = w.value();
@@ -522,9 +527,31 @@ static void check_point_normal_taylor(Args& s) {
     if (s.strategy_index == RL_PN_TAYLOR_PN_PHASE && (m.n_parts < 3 || m.g == 0.0f))
         quit(2, "%s: -s pn_phase_taylor_ex needs a Henyey-Greenstein medium with g != 0 (-m SIGMA_S:SIGMA_A:G; the reference asserts g != 0.0, point_normal.rs:1414)\n", s.cmd->name);
 }
+// point-normal-ats: the seven plain names and the six Taylor names over the light tree; what point-normal-taylor refuses, under its own name
+static void check_point_normal_ats(Args& s) {
+    static const char* const plain[] = {"tr_ex", "tr_phase", "eq_ex", "eq_phase", "eq_clamped_ex", "eq_clamped_phase", "pn_ex"};      // rl_pn_strategy, by value
+    static const char* const taylor[] = {"eq_phase_taylor_ex", "eq_tr_taylor_ex", "eq_clamped_phase_taylor_ex", "eq_clamped_tr_taylor_ex", "pn_tr_taylor_ex",
+                                         "pn_phase_taylor_ex"};      // rl_pn_taylor_strategy, by value
+    static const char* const others[] = {"eq_best_ex", "eq_warp_ex", "eq_clamped_best_ex", "eq_clamped_warp_ex", "pn_warp_ex", "pn_best_ex"};
+    const char* list = "tr_ex, tr_phase, eq_ex, eq_phase, eq_clamped_ex, eq_clamped_phase, pn_ex, eq_phase_taylor_ex, eq_tr_taylor_ex, eq_clamped_phase_taylor_ex, "
+                       "eq_clamped_tr_taylor_ex, pn_tr_taylor_ex, pn_phase_taylor_ex";
+    const std::string strategy = s.strategy.value_or("eq_ex");
+    if (find_name(strategy, others) >= 0) quit(2, "%s: -s %s is not built (%s)\n", s.cmd->name, strategy.c_str(), list);
+    s.family = 0;
+    if ((s.strategy_index = find_name(strategy, plain)) < 0) { s.family = 1; s.strategy_index = find_name(strategy, taylor); }
+    if (s.strategy_index < 0) quit(2, "invalid strategy: %s (%s)\n", strategy.c_str(), list);
+    if (!s.unbuilt.empty()) quit(2, "point-normal-ats: %s is not built (MIS, splitting and the warps are left out)\n", s.unbuilt.c_str());
+    refuse_limits(s, s.mode, true);      // both stream modes: the one given passes
+    refuse_no_medium(s);
+    const Medium m = parse_medium(s.medium);
+    if (s.family == 1 && s.strategy_index == RL_PN_TAYLOR_PN_PHASE && (m.n_parts < 3 || m.g == 0.0f))
+        quit(2, "%s: -s pn_phase_taylor_ex needs a Henyey-Greenstein medium with g != 0 (-m SIGMA_S:SIGMA_A:G; the reference asserts g != 0.0, point_normal.rs:1414)\n", s.cmd->name);
+    s.use_ats = true;      // the subcommand is the light tree's: `-x ats point-normal-ats` is the same line
+}
 template <class Integrator>
 static Rendered run_point_normal(const Args& s, IndependentSampler& sampler, Scene& scene) {
     Integrator it;
+    if constexpr (std::is_same_v<Integrator, IntegratorPointNormalAts>) it.family = (rl_pn_ats_family)s.family;
     it.strategy = (decltype(it.strategy))s.strategy_index;
     it.use_aa = !s.disable_aa;
     it.stream_mode = s.mode;
@@ -548,6 +575,7 @@ static const Subcommand SUBCOMMANDS[] = {
     {"point-normal", nullptr, false, false, option_point_normal, check_point_normal<IntegratorPointNormal>, run_point_normal<IntegratorPointNormal>},
     {"point-normal-mis", nullptr, false, false, option_point_normal, check_point_normal<IntegratorPointNormalMis>, run_point_normal<IntegratorPointNormalMis>},
     {"point-normal-taylor", nullptr, false, false, option_point_normal, check_point_normal_taylor, run_point_normal<IntegratorPointNormalTaylor>},
+    {"point-normal-ats", nullptr, false, false, option_point_normal, check_point_normal_ats, run_point_normal<IntegratorPointNormalAts>},
 };
 static const Subcommand* find_subcommand(const std::string& a) {
     for (const Subcommand& c : SUBCOMMANDS) if (a == c.name || (c.alias && a == c.alias)) return &c;

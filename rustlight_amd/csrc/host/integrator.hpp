@@ -500,9 +500,9 @@ struct IntegratorSinglePlaneUncorrelated {
     }
 };
 
-// compute of the three point-normal structs below: the block seeds straight from the main sampler, `self`'s fields into the params `defaults` fills, `render`
-template <class Self, class Params>
-BufferCollection compute_point_normal(Self& self, IndependentSampler& sampler, Scene& scene, void (*defaults)(Params*),
+// compute of the four point-normal structs below: the block seeds straight from the main sampler, `self`'s fields into the params `defaults` fills, `render`
+template <class Self, class Params, class Defaults>
+BufferCollection compute_point_normal(Self& self, IndependentSampler& sampler, Scene& scene, Defaults&& defaults,
                                       int (*render)(rl_context*, const Params*, const uint64_t*, size_t, float*, rl_render_stats*), const char* what) {
     RenderContext ctx(scene, self.device, self.options);
     const std::vector<uint64_t> seeds = ctx.block_seeds(sampler);
@@ -553,6 +553,24 @@ struct IntegratorPointNormalTaylor {
     rl_render_stats last_stats{};
     BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
         return compute_point_normal(*this, sampler, scene, rl_point_normal_taylor_params_default, rl_render_point_normal_taylor, "point-normal-taylor");
+    }
+};
+
+// IntegratorPointNormal over the light tree (fix_random_sample_emitter's ATS arm, point_normal.rs:1217-1228, and compute_single_tr's, :2237-2243), through
+// rl_render_point_normal_ats: `strategy` is an rl_pn_strategy (family plain) or an rl_pn_taylor_strategy (family Taylor).  The scene's emitters are built
+// with the tree.
+struct IntegratorPointNormalAts {
+    rl_pn_ats_family family = RL_PN_ATS_PLAIN;
+    int32_t strategy = RL_PN_EQ_EX;
+    bool use_aa = true;
+    rl_stream_mode stream_mode = RL_STREAM_REFERENCE_ORDER;
+    int device = 0;
+    Options options;
+    rl_render_stats last_stats{};
+    BufferCollection compute(IndependentSampler& sampler, Scene& scene) {
+        // compute_point_normal fills the fields the four structs share; the family goes in behind the defaults
+        const auto defaults = [&](rl_point_normal_ats_params* p) { rl_point_normal_ats_params_default(p); p->family = family; };
+        return compute_point_normal(*this, sampler, scene, defaults, rl_render_point_normal_ats, "point-normal-ats");
     }
 };
 

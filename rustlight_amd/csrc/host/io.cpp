@@ -227,6 +227,14 @@ int rl_debug_ats(const rl_scene* scene, uint64_t* n_nodes, float* nodes16, uint6
     return RL_OK;
 }
 
+// the tree's angles beside rl_debug_ats' nodes: [node][2] LightBounds::theta_o, theta_e, which LightNode holds as cosines (its 64 bytes stay as they are)
+int rl_debug_ats_angles(const rl_scene* scene, uint64_t* n_nodes, float* angles2) {
+    if (!scene || !n_nodes || !scene->emitters_built) return RL_ERR_INVALID_ARGUMENT;
+    if (angles2) std::memcpy(angles2, scene->ats_angles.data(), scene->ats_angles.size() * sizeof(float));
+    *n_nodes = scene->ats_angles.size() / 2;
+    return RL_OK;
+}
+
 // Camera::generate on the host (src/camera.rs:81-91) — same arithmetic as k_raygen
 int rl_debug_camera_ray(const rl_scene* scene, float px, float py, float* origin, float* direction) {
     if (!scene || !scene->has_camera) return RL_ERR_INVALID_ARGUMENT;

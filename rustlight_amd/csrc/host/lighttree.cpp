@@ -169,7 +169,7 @@ struct Builder {
 
 // Fills scene->ats_* from scene->emitters (all of which must be emissive meshes: `assert!(e.is_surface())`).
 int build_light_tree(rl_scene* scene, std::string* err) {
-    scene->ats_nodes.clear(); scene->ats_light_emitter.clear(); scene->ats_light_prim.clear();
+    scene->ats_nodes.clear(); scene->ats_angles.clear(); scene->ats_light_emitter.clear(); scene->ats_light_prim.clear();
     scene->ats_leaf_of.clear(); scene->ats_emitter_base.clear();
     scene->ats_root = -1;
     std::vector<Proxy> lights;
@@ -215,6 +215,7 @@ int build_light_tree(rl_scene* scene, std::string* err) {
     Builder bld;
     bld.nodes = &scene->ats_nodes; bld.lights = &lights;
     scene->ats_root = bld.build(0, lights.size());
+    for (const Bounds& b : bld.node_bounds) { scene->ats_angles.push_back(b.theta_o); scene->ats_angles.push_back(b.theta_e); }
     scene->ats_leaf_of.assign(lights.size(), 0);
     for (size_t i = 0; i < scene->ats_nodes.size(); i++) {
         const LightNode& nd = scene->ats_nodes[i];

@@ -385,7 +385,7 @@ int rl_scene_build_emitters(rl_scene* scene) {
         float fi;
         build_cdf(flux, &scene->emitters_cdf, &fi);
     }
-    scene->ats_root = -1; scene->ats_nodes.clear();
+    scene->ats_root = -1; scene->ats_nodes.clear(); scene->ats_angles.clear();
     if (scene->want_ats) {   // emitter_sampler.build_ats() (scene.rs:118-120)
         std::string err;
         int rc = build_light_tree(scene, &err);

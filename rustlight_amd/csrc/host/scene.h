@@ -66,6 +66,7 @@ struct rl_scene {
     bool want_ats = false;
     int32_t ats_root = -1;
     std::vector<rl::LightNode> ats_nodes;
+    std::vector<float> ats_angles;                            // [node][2] LightBounds::theta_o, theta_e (LightNode keeps their cosines): importance_ray reads the angles
     std::vector<int32_t> ats_light_emitter, ats_light_prim;   // light proxies in tree order
     std::vector<uint32_t> ats_leaf_of;                        // leaf of (ats_emitter_base[emitter] + triangle)
     std::vector<uint32_t> ats_emitter_base;

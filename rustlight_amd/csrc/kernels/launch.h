@@ -198,6 +198,7 @@ struct PnConst {
     unsigned draws;                     // PN_MODE_ADVANCE: D, the draws of one camera sample
     unsigned long long* pixel_states;   // [pixel item][4] the block sampler's state at the pixel's first sample: k_pn_chain writes, k_pn_pixel reads (PN_MODE_GIVEN)
     float taylor[8];                    // PnTaylor's phase strategies: Poly6::phase(g)'s seven coefficients and clamp_angle_phase(g), which the frame fixes (pntaylor_render.hip.h)
+    const float* ats_angles;            // PnAtsPick: [light tree node][2] theta_o, theta_e as the host tree's LightBounds hold them (pnats_render.hip.h); null for the other kinds
 };
 
 // mat: the scene's one BSDF type, or -1 = run-time switch per vertex.  area_only: every emitter is a mesh area light and there is no light
@@ -284,6 +285,11 @@ void launch_pnmis_stream(bool chain, int family, dim3 grid, dim3 block, size_t l
 // strategy's count depends on the data); strategy = rl_pn_taylor_strategy; the constants are point-normal's PnConst, with pc.taylor for the phase polynomials
 void launch_pntaylor_lds(bool chain, int strategy, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
 void launch_pntaylor_stream(bool chain, int strategy, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
+// IntegratorPointNormal over the light tree (pnats.hip.h): chain = false k_pn_pixel<.., PnAts<family, strategy>>, true k_pn_chain<.., PnAts<family, strategy>>
+// (the Taylor names and the three plain strategies whose sampler can be None); selector = 8 * rl_pn_ats_family + the strategy within the family; the constants
+// are point-normal's PnConst with pc.ats_angles, and pc.taylor for the phase polynomials
+void launch_pnats_lds(bool chain, int selector, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
+void launch_pnats_stream(bool chain, int selector, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc);
 void dump_stage_timers(bool lds_scene);   // dev-only (-DRL_STAGE_TIMERS)
 void dump_stage_timers_stream();
 void dump_chain_timers_lds();      // dev-only (-DRL_STAGE_TIMERS): cycle shares of k_stream_chain's stages

@@ -31,7 +31,7 @@
 // lane's sampler is (a) forked per sample from the pixel's seed (k_seed_pixels), (b) the block's stream entered c * spp * D draws down by rng_advance when the
 // count D is constant, (c) the state k_pn_chain recorded for the pixel when it is not; or, as the cross-check of (b) and (c), one lane per block walks the
 // block's stream in the reference's order (the form k_pixel_mc has).  k_pn_chain: one lane per block walks (pixel, sample), takes the jitter, the camera
-// ray's closest hit and the four emitter draws, decides Some | None with pn_make_sampler — the statements the body decides it with — and skips the draws the
+// ray's closest hit and the body's emitter draws (four, or the light tree's three), decides Some | None with pn_make_sampler — the statements the body decides it with — and skips the draws the
 // body takes behind them (plain: 1 or 3 | 0); it records the sampler at the start of every pixel (32 bytes per pixel).
 #pragma once
 #include "light.hip.h"      // light_mesh_position
@@ -71,6 +71,21 @@ RL_DEV PnEmitter pn_sample_emitter(const DeviceScene& sc, float r_sel, float r_p
     e.flux = div_unguarded(e.flux, pdf_sel);                                // w / pdf_sel
     e.flux = e.flux * correct;
     return e;
+}
+// The emitter pick, a policy of the sample bodies: the power pick here, the light tree's PnAtsPick in pnats.hip.h.  kDraws: the draws one pick takes (next,
+// next, next2d | next, next2d); on_ray: fix_random_sample_emitter (:1201-1230), at_point: compute_single_tr's pick at the scattering point (:2237-2249)
+struct PnPowerPick {
+    static constexpr unsigned kDraws = 4;
+    static RL_DEV PnPowerPick make(const PnConst&) { return {}; }
+    RL_DEV PnEmitter on_ray(const DeviceScene& sc, V3, V3, bool, float, float r_sel, float r_pos, V2 uv) const { return pn_sample_emitter(sc, r_sel, r_pos, uv); }
+    RL_DEV PnEmitter at_point(const DeviceScene& sc, V3, float r_sel, float r_pos, V2 uv) const { return pn_sample_emitter(sc, r_sel, r_pos, uv); }
+};
+// the draws of one pick, in the order they are taken; a pick of three draws has no r_pos
+template <unsigned DRAWS>
+RL_DEV void pn_emitter_draws(Rng& rng, float* r_sel, float* r_pos, V2* uv) {
+    *r_sel = rng_next_f32(rng);
+    *r_pos = DRAWS == 4 ? rng_next_f32(rng) : 0.0f;
+    *uv = smp_next2d(rng);
 }
 
 // EquiAngularSampling (:14-24) and, for pn_ex, PointNormalSampling's a and b (:651-658)
@@ -167,9 +182,9 @@ RL_DEV bool pn_sample_transmittance(const MediumRecord& m, bool has_max, float m
 // `aa` (use_aa) is a run-time flag, uniform over the launch: with it as a template argument a kernel holds the body twice, and the explicit strategies then
 // spill 10 to 13 VGPRs at 128.  park(rng) is called once, behind the sample's last draw: every draw comes before the sample's second ray, so a driver that
 // parks the sampler in memory there carries no sampler through that traversal.
-template <int STRATEGY, class Stack, class Park>
+template <int STRATEGY, class Pick, class Stack, class Park>
 RL_DEV Col pn_sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool aa, unsigned px, unsigned py, Rng& rng, Park&& park,
-                     unsigned& n_rays, unsigned& n_vertices) {
+                     unsigned& n_rays, unsigned& n_vertices, const Pick& pick) {
     float u = (float)px + 0.5f, v = (float)py + 0.5f;
     if (aa) { u = (float)px + rng_next_f32(rng); v = (float)py + rng_next_f32(rng); }
     const V3 o = mk3(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]);
@@ -187,14 +202,14 @@ RL_DEV Col pn_sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& 
     if (pn_is_tr(STRATEGY)) {
         ok = pn_sample_transmittance(m, has_max, max_dist, rng_next_f32(rng), &t_cam, &t_pdf);
         if (STRATEGY == RL_PN_TR_EX) {
-            const float r_sel = rng_next_f32(rng), r_pos = rng_next_f32(rng);
-            const V2 uv = smp_next2d(rng);
-            em = pn_sample_emitter(sc, r_sel, r_pos, uv);
+            float r_sel, r_pos; V2 uv;
+            pn_emitter_draws<Pick::kDraws>(rng, &r_sel, &r_pos, &uv);
+            em = pick.at_point(sc, o + d * t_cam, r_sel, r_pos, uv);
         }
     } else {
-        const float r_sel = rng_next_f32(rng), r_pos = rng_next_f32(rng);
-        const V2 uv = smp_next2d(rng);
-        em = pn_sample_emitter(sc, r_sel, r_pos, uv);
+        float r_sel, r_pos; V2 uv;
+        pn_emitter_draws<Pick::kDraws>(rng, &r_sel, &r_pos, &uv);
+        em = pick.on_ray(sc, o, d, has_max, max_dist, r_sel, r_pos, uv);
         PnDist ds;
         ok = pn_make_sampler<STRATEGY>(has_max, max_dist, o, d, em.p, em.n, &ds);
         if (pn_may_fail(STRATEGY) && !ok) { park(rng); return czero(); }    // t_strategy.is_none() (:2364-2367): before the distance draw
@@ -249,14 +264,15 @@ RL_DEV Rng pn_load_state(const unsigned long long* states, unsigned slot) {
 
 // PnPlain<STRATEGY> — what the drivers below need to know of a sample body, and nothing else (pnmis.hip.h's PnMis<FAMILY> is the other one): the waves per
 // SIMD k_pn_pixel is compiled for, the counters a lane carries, the body itself, the statistics rows, and for k_pn_chain the draws a sample takes behind
-// its four emitter draws.
-template <int STRATEGY>
-struct PnPlain {
-    static constexpr int kWaves = kPnWaves;
+// its emitter draws.  PnPlainBody is the body over an emitter pick; PnPlain<STRATEGY>, the name the kernels carry, is the one over the power pick.
+template <int STRATEGY, class Pick, int WAVES = kPnWaves>
+struct PnPlainBody {
+    static constexpr int kWaves = WAVES;
+    static constexpr unsigned kEmitterDraws = Pick::kDraws;
     struct Counts { unsigned rays = 0, vertices = 0; };
     template <class Stack, class Park>
-    static RL_DEV Col sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool aa, unsigned px, unsigned py, Rng& rng, Park&& park, Counts& n, const PnConst&) {
-        return pn_sample<STRATEGY>(sc, recs, stack, aa, px, py, rng, park, n.rays, n.vertices);
+    static RL_DEV Col sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool aa, unsigned px, unsigned py, Rng& rng, Park&& park, Counts& n, const PnConst& pc) {
+        return pn_sample<STRATEGY>(sc, recs, stack, aa, px, py, rng, park, n.rays, n.vertices, Pick::make(pc));
     }
     // three rows; the host derives the five counters from them (pn_render.hip.h): a sample's draws follow from its strategy and from whether it had a
     // sampler, n.rays are the phase rays of a phase strategy and the visibility rays of an explicit one, a transmittance sample always has its sampler
@@ -266,13 +282,15 @@ struct PnPlain {
         block_stats<3>(rc.partials, which, vals);
     }
     // Some | None by pn_make_sampler, the statements pn_sample decides it with: 1 or 3 draws behind a sampler, none without
-    static RL_DEV unsigned chain_skip(const DeviceScene& sc, bool has_max, float max_dist, V3 o, V3 d, float r_sel, float r_pos, V2 uv, const PnConst&) {
-        const PnEmitter em = pn_sample_emitter(sc, r_sel, r_pos, uv);
+    static RL_DEV unsigned chain_skip(const DeviceScene& sc, bool has_max, float max_dist, V3 o, V3 d, float r_sel, float r_pos, V2 uv, const PnConst& pc) {
+        const PnEmitter em = Pick::make(pc).on_ray(sc, o, d, has_max, max_dist, r_sel, r_pos, uv);
         PnDist ds;
         if (!pn_make_sampler<STRATEGY>(has_max, max_dist, o, d, em.p, em.n, &ds)) return 0u;
         return pn_is_phase(STRATEGY) ? 3u : 1u;
     }
 };
+template <int STRATEGY>
+struct PnPlain : PnPlainBody<STRATEGY, PnPowerPick> {};
 
 // k_pn_pixel<LDS_SCENE, Body> — work item = pixel (pc.mode PN_MODE_PER_SAMPLE | _ADVANCE | _GIVEN), or block (PN_MODE_BLOCK: the single-pass walk).
 // What a lane keeps between two samples lives in memory, so that the second traversal of a sample runs with its value and little else in registers: the
@@ -357,8 +375,8 @@ __global__ void __launch_bounds__(256, kPnWaves) k_pn_chain(RenderConst rc, Devi
             const V3 d = camera_direction(sc, u, v);
             Hit hit;
             const bool has_max = trace_closest(sc, recs, stack, o, d, hit);
-            const float r_sel = rng_next_f32(rng), r_pos = rng_next_f32(rng);
-            const V2 uv = smp_next2d(rng);
+            float r_sel, r_pos; V2 uv;
+            pn_emitter_draws<Body::kEmitterDraws>(rng, &r_sel, &r_pos, &uv);
             const unsigned skip = Body::chain_skip(sc, has_max, hit.t, o, d, r_sel, r_pos, uv, pc);
             for (unsigned k = 0; k < skip; k++) rng_next_u64(rng);
         }

@@ -1,6 +1,6 @@
 // pn_render.hip.h — the host side of the point-normal single-scattering integrator (included by wavefront.hip after pplane_render.hip.h; host code only):
 // rl_render_point_normal, patterned on render_mc, and render_pn, the one frame sequence it shares with rl_render_point_normal_mis (pnmis_render.hip.h) and
-// rl_render_point_normal_taylor (pntaylor_render.hip.h).
+// rl_render_point_normal_taylor (pntaylor_render.hip.h) and rl_render_point_normal_ats (pnats_render.hip.h).
 // IntegratorPointNormal: src/integrators/explicit/point_normal.rs:1172-1199, 2584-2633; the kernels are k_pn_pixel and k_pn_chain over the body
 // PnPlain<STRATEGY> (pn.hip.h).
 
@@ -28,8 +28,17 @@ static unsigned pn_constant_draws(int strategy, bool use_aa) {
         default: return 0u;
     }
 }
-static int check_pn_scene(const rl_context* ctx) {
+// ats: rl_render_point_normal_ats, which needs the tree the other kinds refuse
+static int check_pn_scene(const rl_context* ctx, bool ats) {
     if (ctx->ds.medium.enabled == 0) { rl_set_error("point-normal needs a medium (add -m; the reference unwraps scene.volume, point_normal.rs:2221)"); return RL_ERR_UNSUPPORTED; }
+    if (ats) {
+        if (!ctx->surface_emitters_only || ctx->ds.env_emitter >= 0) {
+            rl_set_error("point-normal-ats takes surface emitters only (LightSamplerATS::new asserts e.is_surface(), emitter.rs:1292-1294)");
+            return RL_ERR_UNSUPPORTED;
+        }
+        if (ctx->ds.ats_root < 0) { rl_set_error("point-normal-ats needs the light tree (build the scene's emitters with it: -x ats)"); return RL_ERR_UNSUPPORTED; }
+        return RL_OK;
+    }
     if (ctx->ds.ats_root >= 0) { rl_set_error("point-normal with the light tree (-x ats) is not built"); return RL_ERR_UNSUPPORTED; }
     if (ctx->ds.env_emitter >= 0) { rl_set_error("point-normal does not sample environment emitters"); return RL_ERR_UNSUPPORTED; }
     if (ctx->has_directional) { rl_set_error("point-normal does not take directional lights (their correct_flux is todo!() in the reference, emitter.rs:170-172)"); return RL_ERR_UNSUPPORTED; }
@@ -40,11 +49,13 @@ static int check_pn_scene(const rl_context* ctx) {
 // What tells rl_render_point_normal, rl_render_point_normal_mis and rl_render_point_normal_taylor apart; render_pn below is everything else.
 using PnLauncher = void (*)(bool, int, dim3, dim3, size_t, hipStream_t, const RenderConst&, const DeviceScene&, const StackConf&, const PnConst&);
 struct PnKind {
-    const char* name;                           // "point-normal" | "point-normal-mis" | "point-normal-taylor", as the error strings say it
+    const char* name;                           // "point-normal" | "point-normal-mis" | "point-normal-taylor" | "point-normal-ats", as the error strings say it
     int selector;                               // what the launchers take: the strategy | the family
     unsigned draws;                             // the draws of one camera sample, the jitter's included; 0: the count depends on the data and the chain pass runs
     PnLauncher launch_lds, launch_stream;
     float taylor[8] = {};                       // PnConst::taylor: point-normal-taylor's phase polynomial (pntaylor_render.hip.h); zero for the other kinds
+    bool ats = false;                           // point-normal-ats: the scene must carry the light tree, which the other kinds refuse
+    const float* ats_angles = nullptr;          // PnConst::ats_angles: point-normal-ats' angles per tree node (pnats_render.hip.h); null for the other kinds
 };
 
 // One frame of either kind: the checks, the four sampler modes (PN_MODE_*), the chain pass where the draw count depends on the data, the pixel kernel, and the
@@ -56,7 +67,7 @@ static int render_pn(rl_context* ctx, const Params* params, const uint64_t* bloc
     const std::string name = kind.name;
     if (params->stream_mode == RL_STREAM_STRATIFIED) { rl_set_error(name + " has no stratified sampler (-r stratified is not built)"); return RL_ERR_UNSUPPORTED; }
     if ((rcode = check_streams(params->stream_mode, params->spp, RL_NUMERICS_EXACT, params->shard_index, params->shard_count)) != RL_OK) return rcode;
-    if ((rcode = check_pn_scene(ctx)) != RL_OK) return rcode;
+    if ((rcode = check_pn_scene(ctx, kind.ats)) != RL_OK) return rcode;
     const bool per_sample = params->stream_mode == RL_STREAM_PER_SAMPLE;
     const bool single_pass = !per_sample && ctx->knobs.has(K_REF_SINGLE_PASS);
     const bool chain = !per_sample && !single_pass && kind.draws == 0u;
@@ -92,6 +103,7 @@ static int render_pn(rl_context* ctx, const Params* params, const uint64_t* bloc
     pc.draws = kind.draws;
     pc.pixel_states = ctx->d_sample_states.get();
     std::memcpy(pc.taylor, kind.taylor, sizeof(pc.taylor));
+    pc.ats_angles = kind.ats_angles;
     StackConf stc;
     if ((rcode = stack_conf(ctx, n_threads, &stc)) != RL_OK) return rcode;
     const size_t lds = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false);

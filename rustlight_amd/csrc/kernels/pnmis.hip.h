@@ -320,6 +320,7 @@ template <int FAMILY>
 struct PnMis {
     // waves per SIMD k_pn_pixel is compiled for (the resource rows record what each family reached)
     static constexpr int kWaves = FAMILY == PNMIS_TR ? 4 : 3;
+    static constexpr unsigned kEmitterDraws = 4;        // the power pick's, which k_pn_chain takes before chain_skip
     struct Counts { unsigned phase = 0, vis = 0, vertices = 0; };
     template <class Stack, class Park>
     static RL_DEV Col sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool aa, unsigned px, unsigned py, Rng& rng, Park&& park, Counts& n, const PnConst&) {

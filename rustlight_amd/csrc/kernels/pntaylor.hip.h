@@ -7,7 +7,7 @@
 // (point_normal_poly.rs:178-393), clamp_angle_tr / clamp_angle_phase (:391-399), TaylorSampling::{new, sample} (:401-518), PointNormalTaylorSampling::{new,
 // sample} with warp = None (:757-976), math::newton_raphson_iterate (math.rs:136-225).  Poly6::tr_phase, PolyClamped, Poly4 and HybridSampling are not built.
 //
-// Draws per camera sample, behind the 2 of the jitter (none with -z): 4 emitter, then 1 distance only when the sampler is Some.  TaylorSampling::new and
+// Draws per camera sample, behind the 2 of the jitter (none with -z): 4 emitter (the light tree's pick, pnats.hip.h: 3), then 1 distance only when the sampler is Some.  TaylorSampling::new and
 // PointNormalTaylorSampling::new return None on norm <= 0, norm_poly_pn <= 0 or norm_poly <= 0, so every strategy's count depends on the data and every
 // strategy takes the chain pass, which decides Some | None with pntaylor_make, the statements the body decides it with.
 //
@@ -267,9 +267,9 @@ RL_DEV void pntaylor_sample_pn(const PnTaylorDist& ts, float sample, float* t_ou
 }
 
 // compute_pixel for one camera sample of pixel (px, py) with a Taylor strategy: pn_sample's explicit arm behind another distance sampler
-template <int STRATEGY, class Stack, class Park>
+template <int STRATEGY, class Pick, class Stack, class Park>
 RL_DEV Col pntaylor_sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, const PnConst& pc, unsigned px, unsigned py, Rng& rng, Park&& park,
-                           unsigned& n_rays, unsigned& n_vertices) {
+                           unsigned& n_rays, unsigned& n_vertices, const Pick& pick) {
     float u = (float)px + 0.5f, v = (float)py + 0.5f;
     if (pc.use_aa != 0) { u = (float)px + rng_next_f32(rng); v = (float)py + rng_next_f32(rng); }
     const V3 o = mk3(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]);
@@ -279,9 +279,9 @@ RL_DEV Col pntaylor_sample(const DeviceScene& sc, const SceneRecs& recs, const S
     const float max_dist = hit.t;
     const MediumRecord& m = sc.medium;
     const Col sigma_s = mkc(m.sigma_s[0], m.sigma_s[1], m.sigma_s[2]);
-    const float r_sel = rng_next_f32(rng), r_pos = rng_next_f32(rng);
-    const V2 uv = smp_next2d(rng);
-    const PnEmitter em = pn_sample_emitter(sc, r_sel, r_pos, uv);
+    float r_sel, r_pos; V2 uv;
+    pn_emitter_draws<Pick::kDraws>(rng, &r_sel, &r_pos, &uv);
+    const PnEmitter em = pick.on_ray(sc, o, d, has_max, max_dist, r_sel, r_pos, uv);
     float t_cam, t_pdf;
     {
         PnTaylorDist ts;
@@ -308,17 +308,20 @@ RL_DEV Col pntaylor_sample(const DeviceScene& sc, const SceneRecs& recs, const S
     return shadow_visible(sc, recs, stack, p, em.p) ? value : czero();
 }
 
-// PnTaylor<STRATEGY> — the sample body of the Taylor strategies for pn.hip.h's drivers (what PnPlain<STRATEGY> is for the plain ones)
-template <int STRATEGY>
-struct PnTaylor {
-    // waves per SIMD k_pn_pixel is compiled for (profiles/pntaylor_note.md records what the compiler reported at four and at three)
-    // pn_phase_taylor_ex spills 10 VGPRs (48 bytes of scratch) at four and is compiled for three; the other five fit four (121 to 128 VGPRs)
-    static constexpr int kWaves = STRATEGY == RL_PN_TAYLOR_PN_PHASE ? 3 : kPnWaves;
+// PnTaylor<STRATEGY> — the sample body of the Taylor strategies for pn.hip.h's drivers (what PnPlain<STRATEGY> is for the plain ones): PnTaylorBody over the
+// power pick
+// waves per SIMD k_pn_pixel is compiled for (profiles/pntaylor_note.md records what the compiler reported at four and at three)
+// pn_phase_taylor_ex spills 10 VGPRs (48 bytes of scratch) at four and is compiled for three; the other five fit four (121 to 128 VGPRs)
+constexpr int pntaylor_waves(int strategy) { return strategy == RL_PN_TAYLOR_PN_PHASE ? 3 : kPnWaves; }
+template <int STRATEGY, class Pick, int WAVES = pntaylor_waves(STRATEGY)>
+struct PnTaylorBody {
+    static constexpr int kWaves = WAVES;
+    static constexpr unsigned kEmitterDraws = Pick::kDraws;
     struct Counts { unsigned rays = 0, vertices = 0; };
     template <class Stack, class Park>
     static RL_DEV Col sample(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, bool, unsigned px, unsigned py, Rng& rng, Park&& park, Counts& n,
                              const PnConst& pc) {
-        return pntaylor_sample<STRATEGY>(sc, recs, stack, pc, px, py, rng, park, n.rays, n.vertices);
+        return pntaylor_sample<STRATEGY>(sc, recs, stack, pc, px, py, rng, park, n.rays, n.vertices, Pick::make(pc));
     }
     // three rows; the host derives the five counters from them (pntaylor_render.hip.h): a sample takes one draw behind its emitter draws when it had a
     // sampler, n.rays are the visibility rays
@@ -329,11 +332,13 @@ struct PnTaylor {
     }
     // Some | None by pntaylor_make, the statements pntaylor_sample decides it with: 1 draw behind a sampler, none without
     static RL_DEV unsigned chain_skip(const DeviceScene& sc, bool has_max, float max_dist, V3 o, V3 d, float r_sel, float r_pos, V2 uv, const PnConst& pc) {
-        const PnEmitter em = pn_sample_emitter(sc, r_sel, r_pos, uv);
+        const PnEmitter em = Pick::make(pc).on_ray(sc, o, d, has_max, max_dist, r_sel, r_pos, uv);
         PnTaylorDist ts;
         return pntaylor_make<STRATEGY>(sc.medium, pc, has_max, max_dist, o, d, em.p, em.n, &ts) ? 1u : 0u;
     }
 };
+template <int STRATEGY>
+struct PnTaylor : PnTaylorBody<STRATEGY, PnPowerPick> {};
 
 template <bool LDS_SCENE, int STRATEGY>
 static void launch_pntaylor_one(bool chain, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const RenderConst& rc, const DeviceScene& ds, const StackConf& stc, const PnConst& pc) {

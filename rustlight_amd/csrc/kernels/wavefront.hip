@@ -294,6 +294,9 @@ struct rl_context {
     bool lds_scene = false;
     bool area_lights_only = false;   // every emitter is a mesh area light, no light tree: the fused kernel's NEE code is specialised (same results)
     bool has_directional = false;    // a directional light among the emitters (vpl refuses it with a medium)
+    bool surface_emitters_only = true;      // every emitter is a mesh (what LightSamplerATS::new asserts; point-normal-ats refuses anything else)
+    std::vector<float> ats_angles;          // [light tree node][2] theta_o, theta_e of the host tree's LightBounds; rl_render_point_normal_ats uploads them
+    const float* d_ats_angles = nullptr;    // on first use, into one of `allocs`
     size_t scene_lds_bytes = 0;
     size_t lds_limit = 64 * 1024;     // dynamic LDS a workgroup may ask for on this device (hipDeviceAttributeMaxSharedMemoryPerBlock)
     // render scratch (grown on demand)
@@ -474,6 +477,8 @@ extern "C" int rl_context_create(const rl_scene* scene, int device, rl_context**
         ctx->area_lights_only = scene->ats_root < 0 && !ctx->knobs.has(K_GENERIC_LIGHTS);
         for (const EmitterRecord& e : scene->emitters) if (e.kind != EMITTER_MESH) ctx->area_lights_only = false;
         for (const EmitterRecord& e : scene->emitters) if (e.kind == EMITTER_DIRECTIONAL) ctx->has_directional = true;
+        for (const EmitterRecord& e : scene->emitters) if (e.kind != EMITTER_MESH) ctx->surface_emitters_only = false;
+        ctx->ats_angles = scene->ats_angles;
         for (const HostMesh& hm : scene->meshes) if (hm.is_light && hm.emission_type != RL_EMISSION_COLOR) ctx->area_lights_only = false;      // uv-dependent emission (`-x hvs-light | texture-light`): the generic instantiation
         ctx->single_bsdf = true;
         ctx->bsdf_type = flat.materials.empty() ? 0 : flat.materials[0].type;
@@ -1340,6 +1345,7 @@ extern "C" int rl_render_vpl(rl_context* ctx, const rl_vpl_set* set, const rl_pa
 #include "pn_render.hip.h"
 #include "pnmis_render.hip.h"
 #include "pntaylor_render.hip.h"
+#include "pnats_render.hip.h"
 
 // ---- batched Acceleration::{trace, visible}
 namespace {
