@@ -74,6 +74,51 @@ def open_floor(w, h, bsdf=None, environment=None, light=True, light_in_view=Fals
     return sd
 
 
+def lights_over_floor(w, h, n=3, use_ats=True):
+    """open_floor without its light under scenes.many_lights' n x n grid of small tilted quads whose emission varies over two decades, 2 above the floor and
+    beside the frustum (x 0.6 .. 2.4, z -0.9 .. 0.9): the many-light case with no ceiling and no silhouette in view; the occluder shadows some of them."""
+    sd = open_floor(w, h, light=False)
+    for i in range(n):
+        for j in range(n):
+            cx, cz, half = 0.6 + 1.8 * (i + 0.5) / n, -0.9 + 1.8 * (j + 0.5) / n, 0.06
+            tilt = 0.05 * ((i + 2 * j) % 3 - 1)
+            e = 0.5 * (1.0 + ((7 * i + 3 * j) % 11)) ** 2 / 4.0
+            corners = [cx - half, 2.0 + tilt, cz - half, cx + half, 2.0 - tilt, cz - half, cx + half, 2.0 - tilt, cz + half, cx - half, 2.0 + tilt, cz + half]
+            sd.meshes.append(scenes._quad_mesh(f"L{i * n + j}", corners, [0, -1, 0], scenes.matte((0.0, 0.0, 0.0)), emission=(e, 0.8 * e, 0.5 * e)))
+    sd.use_ats = use_ats
+    return sd
+
+
+RECEIVER_ALBEDO = (0.7, 0.5, 0.3)
+RECEIVERS = [  # (point, normal): below and beside the light at different distances and tilts, every one with the whole light above its horizon
+    ((0.0, 0.0, 0.0), (0.0, 1.0, 0.0)), ((0.9, 0.3, -0.4), (-0.3, 1.0, 0.2)), ((-1.2, 1.0, 0.6), (1.0, 0.4, -0.2)), ((0.2, 1.5, 0.1), (0.1, 1.0, -0.1)),
+    ((1.5, -0.5, 1.0), (-0.5, 1.0, -0.5)), ((-0.3, 1.75, -0.2), (0.0, 1.0, 0.0))]
+
+
+def receiver_scene(which, light_quad, emission=(3.0, 2.0, 1.0), lights=(), normals_on_receivers=False):
+    """A quad light facing down and receiver `which` of RECEIVERS, a small triangle with or without shading normals, alone: no receiver shadows another."""
+    meshes = [scenes._quad_mesh("light", light_quad, [0, -1, 0], scenes.matte((0, 0, 0)), emission=emission)]
+    for p, n in RECEIVERS[which:which + 1]:
+        p, n = np.asarray(p, np.float64), np.asarray(n, np.float64) / np.linalg.norm(n)
+        s = np.cross(n, [0.0, 0.0, 1.0] if abs(n[2]) < 0.9 else [1.0, 0.0, 0.0])
+        s /= np.linalg.norm(s)
+        t = np.cross(n, s)
+        tri = np.asarray([p + 0.01 * s, p - 0.005 * s + 0.009 * t, p - 0.005 * s - 0.009 * t], np.float32)
+        meshes.append(scenes.MeshData("receiver", tri, np.asarray([[0, 1, 2]], np.uint32), np.tile(-n, (3, 1)).astype(np.float32) if normals_on_receivers else None,
+                                      None, scenes.matte(RECEIVER_ALBEDO)))
+    to_world = np.asarray([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, -5, 1], dtype=np.float32)
+    sd = scenes.SceneData(8, 8, 40.0, 0, to_world, False, meshes)
+    sd.lights = list(lights)
+    return sd
+
+
+def ray_at_receiver(which):
+    """A ray at the receiver's centre, from its normal's side at a slant."""
+    p, n = (np.asarray(a, np.float64) for a in RECEIVERS[which])
+    start = p + 0.2 * n / np.linalg.norm(n) + 0.1 * np.cross(n / np.linalg.norm(n), [0.3, 0.5, 0.8])
+    return start[None, :], ((p - start) / np.linalg.norm(p - start))[None, :]
+
+
 DELTA_SKY = (0.3, 0.4, 0.6)
 MIRROR_TILT = 55.0
 PANE_HALF = 4.0

@@ -11,10 +11,11 @@ import pytest
 from oracle import orc
 from rustlight_amd import api, scenes
 from tests import surface_quadrature as Q
-from tests.scene_helpers import DELTA_SCENES, flat_quad, lit_through_a_pane, open_floor, single_bsdf, with_back_triangle
+from tests.scene_helpers import (DELTA_SCENES, RECEIVER_ALBEDO, RECEIVERS, flat_quad, lit_through_a_pane, open_floor, ray_at_receiver as _ray_at_receiver,
+                                 receiver_scene as _receiver_scene, single_bsdf, with_back_triangle)
 
 W, H, K = 24, 18, 8
-ALBEDO = np.asarray([0.7, 0.5, 0.3])
+ALBEDO = np.asarray(RECEIVER_ALBEDO)
 
 
 # ---- closed forms
@@ -29,35 +30,6 @@ def _polygon_irradiance(x, n, corners):
         c = np.cross(a, b)
         total += np.arccos(np.clip(a @ b, -1.0, 1.0)) * (n @ c) / np.linalg.norm(c)
     return 0.5 * abs(total)
-
-
-RECEIVERS = [  # (point, normal): below and beside the light at different distances and tilts, every one with the whole light above its horizon
-    ((0.0, 0.0, 0.0), (0.0, 1.0, 0.0)), ((0.9, 0.3, -0.4), (-0.3, 1.0, 0.2)), ((-1.2, 1.0, 0.6), (1.0, 0.4, -0.2)), ((0.2, 1.5, 0.1), (0.1, 1.0, -0.1)),
-    ((1.5, -0.5, 1.0), (-0.5, 1.0, -0.5)), ((-0.3, 1.75, -0.2), (0.0, 1.0, 0.0))]
-
-
-def _receiver_scene(which, light_quad, emission=(3.0, 2.0, 1.0), lights=(), normals_on_receivers=False):
-    """A quad light facing down and receiver `which` of RECEIVERS, a small triangle with or without shading normals, alone: no receiver shadows another."""
-    meshes = [scenes._quad_mesh("light", light_quad, [0, -1, 0], scenes.matte((0, 0, 0)), emission=emission)]
-    for p, n in RECEIVERS[which:which + 1]:
-        p, n = np.asarray(p, np.float64), np.asarray(n, np.float64) / np.linalg.norm(n)
-        s = np.cross(n, [0.0, 0.0, 1.0] if abs(n[2]) < 0.9 else [1.0, 0.0, 0.0])
-        s /= np.linalg.norm(s)
-        t = np.cross(n, s)
-        tri = np.asarray([p + 0.01 * s, p - 0.005 * s + 0.009 * t, p - 0.005 * s - 0.009 * t], np.float32)
-        meshes.append(scenes.MeshData("receiver", tri, np.asarray([[0, 1, 2]], np.uint32), np.tile(-n, (3, 1)).astype(np.float32) if normals_on_receivers else None,
-                                      None, scenes.matte(tuple(ALBEDO))))
-    to_world = np.asarray([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, -5, 1], dtype=np.float32)
-    sd = scenes.SceneData(8, 8, 40.0, 0, to_world, False, meshes)
-    sd.lights = list(lights)
-    return sd
-
-
-def _ray_at_receiver(which):
-    """A ray at the receiver's centre, from its normal's side at a slant."""
-    p, n = (np.asarray(a, np.float64) for a in RECEIVERS[which])
-    start = p + 0.2 * n / np.linalg.norm(n) + 0.1 * np.cross(n / np.linalg.norm(n), [0.3, 0.5, 0.8])
-    return start[None, :], ((p - start) / np.linalg.norm(p - start))[None, :]
 
 
 def _at_receivers(res, *args, **kw):
