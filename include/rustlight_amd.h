@@ -32,6 +32,7 @@
  *   fused_dynamic = 0|1       persistent kernel: static tile order / work items from the atomic dispenser
  *   fused_tail_blocks = T, fused_tail_split = S     persistent kernel, per-sample streams in static tile order on an LDS-staged scene without a medium: the last T
  *                             blocks that see the scene run at S lanes per pixel (S a power of two), their samples parked and folded in sample order (0: off)
+ *   shadow_pack_capacity = n  the shadow stage of the kernel with a tail: the wave tests its candidate leaves whenever a lane holds n of them (tests; 0: the stack decides)
  *   no_events = 1             no HIP events around the kernels (rl_render_stats.ms_* stay 0)
  *   vpl_batch_paths = n       rl_vpl_generate_paths: every batch of a generation holds n light paths (default: sized from the records per path measured so far)
  * rl_multi_* reads RL_MULTI_FORCE_HOST_MERGE=1, RL_MULTI_NO_FALLBACK=1, RL_MULTI_REDUCE_TIMEOUT_S=s when the communicator is built / a reduce runs: see rl_multi_describe.

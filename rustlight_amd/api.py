@@ -874,6 +874,17 @@ class Context(_ImageCalls):
         _check(lib().rl_visible_batch(self.h, a.shape[0], abi.fptr(a), abi.fptr(b), out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
+    def visible_lds(self, p0, p1, packed, capacity=0):
+        """Test hook: `visible` on a scene staged in LDS, through the per-lane any-hit loop (packed = False) or the wave's packed form (trace.hip.h: occluded_packed)
+        with option shadow_pack_capacity = capacity."""
+        a = np.ascontiguousarray(p0, dtype=np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(p1, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(a.shape[0], np.uint8)
+        fn = lib().rl_debug_visible_batch_lds
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_uint8)]
+        _check(fn(self.h, a.shape[0], abi.fptr(a), abi.fptr(b), int(bool(packed)), int(capacity), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
     def debug_sizes(self):
         a, b = C.c_uint64(), C.c_uint64()
         d = C.c_uint32()

@@ -21,7 +21,7 @@ namespace rl {
 // traversal stacks in LDS.  Same functions, same order of operations, same results as the wavefront kernels;
 // what disappears is ~1.4 KB/sample of state traffic through HBM and ~2000 kernel boundaries per render.
 #ifdef RL_STAGE_TIMERS
-__device__ unsigned long long g_stage_timers[32];      // [0..3] cycles per stage, [4..7] live lanes per stage, [8] lane slots, [16..] shadow-stage occupancy (dump_stage_timers_impl)
+__device__ unsigned long long g_stage_timers[32];      // [0..3] cycles per stage, [4..7] live lanes per stage, [8] lane slots, [9..15] the shadow stage's loops, [16..] shadow-stage occupancy (dump_stage_timers_impl)
 static constexpr unsigned kFusedWgSlots = 1u << 15;
 static __device__ unsigned long long g_fused_wgs[2 * kFusedWgSlots];      // per workgroup (start, end) on the 100 MHz wall clock: the launch's drain (dump_stage_timers_impl; as g_chain_waves of chain.hip.h)
 #endif
@@ -61,6 +61,9 @@ static void dump_stage_timers_impl() {
         const double it = (double)(h[16] + h[17] + h[18] + h[19] + h[20]), ex = it - (double)h[16], pr = (double)(h[21] + h[22] + h[23] + h[24]);
         if (it > 0) std::fprintf(stderr, "[stage] shadow stage: runs in %.1f %% of the wave-iterations; where it runs the wave holds 1-16 / 17-32 / 33-48 / 49-64 shadow rays in %.1f / %.1f / %.1f / %.1f %% (%.1f lanes on average)\n",
                                  100.0 * ex / it, 100.0 * h[17] / std::max(1.0, ex), 100.0 * h[18] / std::max(1.0, ex), 100.0 * h[19] / std::max(1.0, ex), 100.0 * h[20] / std::max(1.0, ex), (double)h[7] / std::max(1.0, ex));
+        if (ex > 0) std::fprintf(stderr, "[stage] shadow loops, means per execution of the stage: node trips the wave paid %.2f, triangle-test iterations it paid %.2f, largest per-lane node trips %.2f, "
+                                 "candidate triangles of all lanes %.2f (largest per lane %.2f), packed rounds %.2f in %.2f passes\n",
+                                 (double)h[9] / ex, (double)h[10] / ex, (double)h[11] / ex, (double)h[12] / ex, (double)h[13] / ex, (double)h[14] / ex, (double)h[15] / ex);
         if (pr > 0) std::fprintf(stderr, "[stage] pairs of consecutive iterations: neither holds shadow rays %.1f %%, one does %.1f %%, both and <= 64 together %.1f %% (one traversal could serve both), both and > 64 %.1f %%\n",
                                  100.0 * h[21] / pr, 100.0 * h[22] / pr, 100.0 * h[23] / pr, 100.0 * h[24] / pr);
     }

@@ -44,6 +44,9 @@
     // the shadow stage where it runs: wave-iterations by the number of lanes that hold a shadow ray (0 | 1-16 | 17-32 | 33-48 | 49-64), and what packing the shadow rays of
     // TWO consecutive iterations into one traversal could save: pairs of iterations by (both empty | one empty | both hold rays and together <= 64 | together > 64)
     unsigned long long sh_hist[5] = {0, 0, 0, 0, 0}, sh_pair[4] = {0, 0, 0, 0}, sh_cyc_exec = 0; unsigned sh_prev = 0, sh_parity = 0;
+    // ... and its loops, summed over the executions (PackStats): [0] node trips the wave paid, [1] triangle-test iterations it paid, [2] the largest per-lane count of inner-node
+    // trips, [3] candidate triangles of all lanes (packed form: of the full enumeration; per-lane loop: triangles tested), [4] the largest per-lane count, [5] packed rounds, [6] passes of phase B
+    unsigned long long sh_loop[7] = {0, 0, 0, 0, 0, 0, 0};
 #define RL_T0 { t0 = __builtin_readcyclecounter(); }
 #define RL_T1(K, COND) { unsigned long long t1 = __builtin_readcyclecounter(); tm[K] += t1 - t0; ln[K] += __popcll(__ballot(COND)); t0 = t1; }
     unsigned long long t0;
@@ -132,7 +135,31 @@
 #ifdef RL_STAGE_TIMERS
         const bool c3 = PU(U_FLAGS) & ST_SHADOW;
 #endif
+        // (the tail form — LDS scene, no medium, not queue-fed — runs the shadow rays of the wave together: leaves enumerated first, triangle tests packed over the lanes;
+        // trace.hip.h: occluded_packed.  -DRL_SHADOW_PACKED=0 keeps the per-lane loop there too, for the same-call comparison.  Every other form keeps its code.)
+#ifndef RL_SHADOW_PACKED
+#define RL_SHADOW_PACKED 1
+#endif
+        // (exact build only: the tolerance build contracts multiply-adds per call site, so a second site of the triangle test does not repeat the bits of the first,
+        // and a frame with a tail must equal the frame without one in either build)
+#ifdef RL_FAST_MATH
+        constexpr bool kPacked = false;
+#else
+        constexpr bool kPacked = kTail && RL_SHADOW_PACKED != 0;
+#endif
+#ifdef RL_STAGE_TIMERS
+        PackStats pst;
+        if constexpr (kPacked) {
+            const bool sh = (PU(U_FLAGS) & ST_SHADOW) != 0u;
+            if (__ballot(sh) != 0ull) shadow_slot<true>(sc, recs, stack, ps, sh, stc.pack_cap, &pst);
+        } else if (PU(U_FLAGS) & ST_SHADOW) shadow_slot(sc, recs, stack, ps, true, 0, &pst);
+#else
+        if constexpr (kPacked) {
+            const bool sh = (PU(U_FLAGS) & ST_SHADOW) != 0u;
+            if (__ballot(sh) != 0ull) shadow_slot<true>(sc, recs, stack, ps, sh, stc.pack_cap);
+        } else
         if (PU(U_FLAGS) & ST_SHADOW) shadow_slot(sc, recs, stack, ps);
+#endif
 #ifdef RL_STAGE_TIMERS
         { const unsigned nsh = (unsigned)__popcll(__ballot(c3)); sh_hist[nsh == 0u ? 0 : 1 + (nsh - 1u) / 16u]++;
           if (nsh) sh_cyc_exec += __builtin_readcyclecounter() - t0;
@@ -140,12 +167,21 @@
           sh_prev = nsh; sh_parity ^= 1u; }
 #endif
         RL_T1(3, c3)
+#ifdef RL_STAGE_TIMERS
+        if (__ballot(c3) != 0ull) {      // loop-level counters of this shadow-stage execution (after the stage's clock reading: not part of its cycles)
+            auto wsum = [](unsigned v) { for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off, 64); return v; };
+            auto wmax = [](unsigned v) { for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, off, 64)); return v; };
+            sh_loop[0] += wsum(pst.trips_paid); sh_loop[1] += wsum(pst.tests_paid); sh_loop[2] += wmax(pst.lane_trips); sh_loop[3] += wsum(pst.lane_tris);
+            sh_loop[4] += wmax(pst.lane_tris); sh_loop[5] += wsum(pst.rounds); sh_loop[6] += wsum(pst.passes);
+        }
+#endif
     } while (!qmode && !(PU(U_FLAGS) & ST_FINISHED));
     if (!qmode) break;
     }
 #ifdef RL_STAGE_TIMERS
     if ((threadIdx.x & 63u) == 0u) { for (int k = 0; k < 4; k++) { atomicAdd(&g_stage_timers[k], tm[k]); atomicAdd(&g_stage_timers[4 + k], ln[k]); } atomicAdd(&g_stage_timers[8], ln[4]);
-        for (int k = 0; k < 5; k++) atomicAdd(&g_stage_timers[16 + k], sh_hist[k]); for (int k = 0; k < 4; k++) atomicAdd(&g_stage_timers[21 + k], sh_pair[k]); atomicAdd(&g_stage_timers[25], sh_cyc_exec); }
+        for (int k = 0; k < 5; k++) atomicAdd(&g_stage_timers[16 + k], sh_hist[k]); for (int k = 0; k < 4; k++) atomicAdd(&g_stage_timers[21 + k], sh_pair[k]); atomicAdd(&g_stage_timers[25], sh_cyc_exec);
+        for (int k = 0; k < 7; k++) atomicAdd(&g_stage_timers[9 + k], sh_loop[k]); }
 #endif
     {
         const int which[5] = {STAT_SAMPLES, STAT_VERTICES, STAT_DRAWS, STAT_SHADOW_RAYS, STAT_EXT_RAYS};

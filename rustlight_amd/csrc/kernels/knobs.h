@@ -27,6 +27,7 @@ enum KnobId {
     K_FUSED_TAIL_BLOCKS,    // persistent kernel, per-sample streams in static tile order: the last T blocks that see the scene run at several lanes per pixel (0: off; default: auto)
     K_FUSED_TAIL_SPLIT,     // ... lanes per pixel of those blocks, a power of two (0 or 1: off; default: auto)
     K_FUSED_TAIL_NO_BUFFER_TEST, // test knob: the tail's parking buffer "cannot be allocated" (the render goes on without a tail)
+    K_SHADOW_PACK_CAPACITY, // test knob: the tail form's packed shadow stage (trace.hip.h: occluded_packed) tests what it has whenever a lane holds this many candidate leaves (small scenes reach the flush)
     K_EVAL_SPLIT,           // lanes per pixel of the evaluation launches beside the chain pass (default 4)
     K_EVAL_MIN, K_EVAL_DIV, // a launch when 1 / div of the blocks still to come (at least min) have come in
     K_NO_EVENTS,            // no HIP events around the kernels (rl_render_stats.ms_* stay 0)
@@ -54,7 +55,7 @@ struct Knobs {
     static const char* name_of(int k) {
         static const char* const names[K_COUNT] = {
             "ref_single_pass", "state_budget_mb", "no_overlap", "chain_serial", "chain_no_pre", "chain_no_treelets", "spec_force", "spec_draws_per_sample", "item_shift",
-            "fused_dynamic", "fused_tail_blocks", "fused_tail_split", "fused_tail_no_buffer_test", "eval_split", "eval_min", "eval_div", "no_events", "queue_debug",
+            "fused_dynamic", "fused_tail_blocks", "fused_tail_split", "fused_tail_no_buffer_test", "shadow_pack_capacity", "eval_split", "eval_min", "eval_div", "no_events", "queue_debug",
             "spec_group", "spec_sub", "spec_cap", "spec_probe", "spec_lead", "spec_lead_max", "spec_lead_var", "spec_extra", "spec_dense", "spec_dense_frac",
             "spec_probe_every", "spec_ks", "spec_ke", "spec_serial_ratio", "spec_no_trivial", "spec_lds_limit_test", "spec_stats", "spec_wave_times", "spec_lds_levels", "vpl_batch_paths", "photon_tree_group_photons",
             "plane_generate_lanes", "plane_tree_device", "plane_tree_group_planes", "pplane_tree_device",

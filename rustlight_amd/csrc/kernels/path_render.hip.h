@@ -323,7 +323,8 @@ private:
 
         lds_trav = traversal_lds_bytes(ctx, ctx->lds_scene, 256, true);
         if ((rcode = stack_conf(ctx, (size_t)((P + 255) / 256) * 256, &stc)) != RL_OK) return rcode;
-        lds_fused = traversal_lds_bytes(ctx, ctx->lds_scene, 256, false) + kFusedColdBytes;
+        stc.pack_cap = (int)std::max<long long>(0, std::min<long long>(knobs.i(K_SHADOW_PACK_CAPACITY, 0), kLdsStackLevels));
+        lds_fused =traversal_lds_bytes(ctx, ctx->lds_scene, 256, false) + kFusedColdBytes;
 
         const dim3 block(256);
         if (per_sample && !owned.empty()) hipLaunchKernelGGL(k_seed_pixels, dim3(((unsigned)owned.size() + 63) / 64), dim3(64), 0, st, rc);

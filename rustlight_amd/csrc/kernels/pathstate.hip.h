@@ -60,7 +60,8 @@ struct Counters {
 static constexpr int kLdsStackLevels = 12;   // stack levels kept in LDS per lane
 static constexpr size_t kSampleBufBudget = (size_t)16 << 30;   // bytes of HBM the per-sample parking buffer may take
 // traversal stack configuration (see TravStack)
-struct StackConf { int lds_levels; int* overflow; size_t overflow_stride; int pre_group; };   // pre_group: k_stream_chain on tiny LDS scenes — lanes per chain that precompute its ray's records (0: off; trace.hip.h: precompute_records)
+// pack_cap: option shadow_pack_capacity for the packed shadow stage of k_path_fused's tail form (0: the stack levels decide; it sits where the struct had padding)
+struct StackConf { int lds_levels; int pack_cap; int* overflow; size_t overflow_stride; int pre_group; };   // pre_group: k_stream_chain on tiny LDS scenes — lanes per chain that precompute its ray's records (0: off; trace.hip.h: precompute_records)
 
 #ifndef RL_SPEC_LDS_LEVELS_STREAMING
 #define RL_SPEC_LDS_LEVELS_STREAMING 4

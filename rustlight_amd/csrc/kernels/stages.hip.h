@@ -238,8 +238,10 @@ RL_DEV void extend_slot(const DeviceScene& sc, const SceneRecs& recs, const Stac
     if (dbg) { dbg[0] = hit.steps; dbg[1] = hit.tris; }
 }
 // Acceleration::visible(p0, p1) (accel.rs:316-343)
-template <class Stack>
-RL_DEV bool shadow_visible(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, V3 p0, V3 p1) {
+// PACKED (LDS-staged scenes; trace.hip.h: occluded_packed): the segments of a whole wave at once — every live lane of the wave calls it together, `has_ray` says
+// which lanes hold a segment (the others get false), `cap` is option shadow_pack_capacity (0: the stack's levels decide).  `dbg`: dev-only (-DRL_STAGE_TIMERS).
+template <bool PACKED = false, class Stack>
+RL_DEV bool shadow_visible(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, V3 p0, V3 p1, bool has_ray = true, int cap = 0, PackStats* dbg = nullptr) {
     V3 d = p1 - p0;
     float len = length(d);
     d = d / len;
@@ -247,8 +249,22 @@ RL_DEV bool shadow_visible(const DeviceScene& sc, const SceneRecs& recs, const S
     Hit hit; hit.t = tfar; hit.u = 0.0f; hit.v = 0.0f; hit.prim = -1;
     V3 inv_d = mk3(div_rn(1.0f, d.x), div_rn(1.0f, d.y), div_rn(1.0f, d.z));
     float te;
+    if constexpr (PACKED) {
+        // (the root-box early-out below, as a mask: a lane that misses the root box holds no query and comes out "occluded")
+        const bool query = has_ray & slab(mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]), p0, inv_d, kEps, tfar, &te);
+        const bool occluded = occluded_packed(recs, sc.root, query, p0, d, inv_d, kEps, tfar, stack, cap, dbg);
+        return query & !occluded;
+    }
     if (!slab(mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]), p0, inv_d, kEps, tfar, &te))
         return false;   // root box missed => "occluded" (accel.rs:338-340)
+#ifdef RL_STAGE_TIMERS
+    if (dbg) {
+        const bool found = traverse<true>(recs, Stack::kBvh4 ? sc.root4 : sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
+                                          p0, d, kEps, tfar, hit, stack);
+        dbg->trips_paid += (unsigned)hit.wave_trips; dbg->tests_paid += (unsigned)hit.wave_tests; dbg->lane_trips += (unsigned)hit.steps; dbg->lane_tris += (unsigned)hit.tris;
+        return !found;
+    }
+#endif
     return !traverse<true>(recs, Stack::kBvh4 ? sc.root4 : sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
                            p0, d, kEps, tfar, hit, stack);
 }
@@ -267,9 +283,9 @@ RL_DEV bool trace_none(const DeviceScene& sc, const SceneRecs& recs, const Stack
     return !traverse<true>(recs, sc.root, mk3(sc.root_min[0], sc.root_min[1], sc.root_min[2]), mk3(sc.root_max[0], sc.root_max[1], sc.root_max[2]),
                            o, d, kEps, kF32Max, hit, stack);
 }
-template <class PS, class Stack>
-RL_DEV void shadow_slot(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, PS& ps) {
-    if (shadow_visible(sc, recs, stack, load3(ps, F_OX), load3(ps, F_SX))) storec(ps, F_LR, loadc(ps, F_LR) + loadc(ps, F_CR));
+template <bool PACKED = false, class PS, class Stack>
+RL_DEV void shadow_slot(const DeviceScene& sc, const SceneRecs& recs, const Stack& stack, PS& ps, bool has_ray = true, int cap = 0, PackStats* dbg = nullptr) {
+    if (shadow_visible<PACKED>(sc, recs, stack, load3(ps, F_OX), load3(ps, F_SX), has_ray, cap, dbg)) storec(ps, F_LR, loadc(ps, F_LR) + loadc(ps, F_CR));
 }
 
 // shade_slot<MAT, MEDIUM> — one path vertex of one slot.  MAT >= 0: the hit material is known to have that

@@ -18,7 +18,11 @@
 
 namespace rl {
 
-struct Hit { float t, u, v; int prim; int steps = 0, tris = 0, fetches = 0; };   // steps / tris: dev-only traversal statistics (dead code unless read)
+struct Hit { float t, u, v; int prim; int steps = 0, tris = 0, fetches = 0;   // steps / tris: dev-only traversal statistics (dead code unless read)
+#ifdef RL_STAGE_TIMERS
+    int wave_trips = 0, wave_tests = 0;      // `traverse`: node trips / triangle-test iterations the WAVE paid, counted by the first lane that takes each
+#endif
+};
 
 // Layout of a scene staged in LDS.  A 64-byte record stride puts the same field of every node on two LDS banks (bank = dword
 // address mod 32) and the 16-byte quarters of every triangle on four bank groups, so lanes that read different records collide
@@ -288,6 +292,9 @@ RL_DEV bool traverse(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V3
     constexpr int kPop = -1;            // = ~0: a leaf code with zero triangles, which the builder never emits
     // one trip over inner nodes / stack entries for a lane in that state
     auto node_trip = [&]() {
+#ifdef RL_STAGE_TIMERS
+        if ((threadIdx.x & 63u) == (unsigned)__builtin_ctzll(__ballot(true))) hit.wave_trips++;
+#endif
         if (cur >= 0) {
             hit.steps++;
             NodePlanes p;
@@ -327,6 +334,9 @@ RL_DEV bool traverse(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V3
         if (Stack::NodeFetch::kHasUniform) uni = __ballot(cur != __builtin_amdgcn_readfirstlane(cur)) == 0ull;
         for (int k = 0; k < count; k++) {
             hit.tris++;
+#ifdef RL_STAGE_TIMERS
+            if ((threadIdx.x & 63u) == (unsigned)__builtin_ctzll(__ballot(true))) hit.wave_tests++;
+#endif
             float4 q0, q1, q2, q3;
             if (uni) {
                 const F4c* q = (const F4c*)(recs.tris) + 4 * (__builtin_amdgcn_readfirstlane(first) + k);
@@ -382,6 +392,131 @@ RL_DEV bool traverse(const SceneRecs& recs, int root, V3 root_lo, V3 root_hi, V3
         tri_uv(q[0], q[1], q[2], q[3], o, d, hit.t, &hit.u, &hit.v);
     }
     return found;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// occluded_packed — the any-hit query of `traverse<true>` for the rays of a whole wave on an LDS-staged scene, in two phases
+// (profiles/shadow_pack_note.md).  Called by every live lane of the wave together (lanes without a query pass has_ray = false).
+//
+// An any-hit query never changes its.t before it ends (the first accepted triangle ends it), so which boxes it enters does not depend on any
+// triangle result and the order of the visits is free (NEGATIVES.md round 5 already dropped the near-first order for shadow rays).  The
+// while-while loop of `traverse` charges the wave, per leaf round, the longest descent and the larger leaf; here
+//  (A) every lane enumerates the leaves whose chain of boxes passes the slab tests against the fixed [tnear, tfar] — node_trip's arithmetic
+//      on the same operands with hit.t = tfar; an entered leaf child is appended to the lane's candidate list, an entered inner child is
+//      descended or pushed.  No distances are stacked (the verdict at the push is the re-check at the pop), so the pending node takes the
+//      first dword of a stack entry and the candidates the second: [level][lane] as before, `rows` = the lane's stack levels of each.
+//  (B) the wave's candidates are compacted in place, row by row (ballot + mbcnt; entry k of the compacted list lies at row k / 64, column
+//      k % 64 of the wave's columns — never behind the row being read), and dealt to the live lanes densely: a lane fetches the owner's
+//      ray with ds_bpermute and runs tri_test over the leaf's triangles, in their order, with hit.t = tfar.  An accepted pair stores 1 to
+//      the owner's flag word (the first dword of the last stack row: the pending nodes never reach it, bvh.cpp: stack_depth = inner levels + 1).
+// A lane takes a node trip only while its list has room for the trip's two children; when the lists are full the wave runs (B) on what it
+// has and goes on with (A) (`cap` lowers that threshold: option shadow_pack_capacity, tests).  The verdict is the OR over the very
+// triangle tests the reference makes before its first accepted one, plus tests it would have skipped — same booleans, any order.
+struct PackStats { unsigned trips_paid = 0, tests_paid = 0, rounds = 0, passes = 0, lane_trips = 0, lane_tris = 0; };      // dev-only (-DRL_STAGE_TIMERS)
+RL_DEV int lane_rank(unsigned long long mask) { return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u)); }
+template <class Stack>
+RL_DEV bool occluded_packed(const SceneRecs& recs, int root, bool has_ray, V3 o, V3 d, V3 inv_d, float tnear, float tfar, const Stack& st, int cap, PackStats* stats = nullptr) {
+    static_assert(Stack::kLdsOnly, "the packed any-hit query keeps its lists in the LDS stack of an LDS-staged scene");
+    typedef __attribute__((address_space(3))) int LdsInt;
+    constexpr int kRow = 2 * Stack::lds_stride;                           // dwords between two rows of a column
+    LdsInt* const col = reinterpret_cast<LdsInt*>(st.lds);               // this lane's column: [kRow * level] pending node, [kRow * level + 1] candidate leaf
+    const unsigned long long live = __ballot(true);
+    const int lane = lane_rank(~0ull), rank = lane_rank(live), n_live = __popcll(live);
+    LdsInt* const wave = col - 2 * lane;                                  // the wave's 64 columns
+    bool occ = false;
+    if (root < 0) {         // (uniform) the scene is one leaf, or empty: nothing to enumerate
+        if (has_ray && root != RL_CHILD_NONE) {
+            const unsigned code = (unsigned)(~root);
+            Hit h; h.t = tfar; h.u = 0.0f; h.v = 0.0f; h.prim = -1;
+            for (int k = 0; k < (int)(code & 3u); k++) {
+                const float4* q = recs.tris + Stack::kTriStride4 * ((int)(code >> 2) + k);
+                occ |= tri_test(q[0], q[1], q[2], q[3], o, d, h, (int)(code >> 2) + k);
+            }
+        }
+        return occ;
+    }
+    const int rows = st.lds_levels;                                       // >= 2 when the root is an inner node
+    const int room = min(cap > 0 ? cap : rows, rows - 1);                 // a trip appends at most two leaves: taken while the list holds fewer than `room`
+    LdsInt* const flag = col + kRow * (rows - 1);
+    *flag = 0;
+    typename Stack::NodeFetch fetch(recs, inv_d);
+    int cur = has_ray ? root * Stack::kNodeRefScale : RL_CHILD_NONE, sp = 0, nl = 0;
+    for (;;) {
+        // ---- (A)
+        while (cur >= 0 && nl < room) {
+#ifdef RL_STAGE_TIMERS
+            if (stats) { stats->lane_trips++; if (lane == (int)__builtin_ctzll(__ballot(true))) stats->trips_paid++; }
+#endif
+            const NodePlanes p = fetch(cur);
+            const float d1 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf((p.lnx - o.x) * inv_d.x, (p.lny - o.y) * inv_d.y), (p.lnz - o.z) * inv_d.z), tnear);
+            const float f1 = __builtin_fminf(__builtin_fminf(__builtin_fminf((p.lfx - o.x) * inv_d.x, (p.lfy - o.y) * inv_d.y), (p.lfz - o.z) * inv_d.z), tfar);
+            const float d2 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf((p.rnx - o.x) * inv_d.x, (p.rny - o.y) * inv_d.y), (p.rnz - o.z) * inv_d.z), tnear);
+            const float f2 = __builtin_fminf(__builtin_fminf(__builtin_fminf((p.rfx - o.x) * inv_d.x, (p.rfy - o.y) * inv_d.y), (p.rfz - o.z) * inv_d.z), tfar);
+            const bool v1 = !(f1 <= d1), v2 = !(f2 <= d2);
+            const bool leaf1 = v1 & (p.id1 < 0), leaf2 = v2 & (p.id2 < 0), in1 = v1 & (p.id1 >= 0), in2 = v2 & (p.id2 >= 0);
+#ifdef RL_STAGE_TIMERS
+            if (stats) stats->lane_tris += (leaf1 ? (unsigned)(~p.id1) & 3u : 0u) + (leaf2 ? (unsigned)(~p.id2) & 3u : 0u);
+#endif
+            // (stores without a branch: a slot only counts when its counter moves past it; nl + 1 <= rows - 1 and sp <= rows - 2 here)
+            col[kRow * nl + 1] = p.id1; nl += leaf1 ? 1 : 0;
+            col[kRow * nl + 1] = p.id2; nl += leaf2 ? 1 : 0;
+            col[kRow * sp] = p.id2; sp += (in1 & in2) ? 1 : 0;
+            cur = in1 ? p.id1 : (in2 ? p.id2 : RL_CHILD_NONE);
+            if (!(in1 | in2) && sp > 0) { sp--; cur = col[kRow * sp]; }
+        }
+        // ---- (B)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        int total = 0;
+        for (int j = 0;; j++) {
+            const bool has = j < nl;
+            const unsigned long long m = __ballot(has);
+            if (m == 0ull) break;
+            if (has) {
+                const int code = col[kRow * j + 1];
+                const int pos = total + lane_rank(m);
+                wave[(pos >> 6) * kRow + 2 * (pos & 63) + 1] = (lane << 24) | (int)((unsigned)(~code) & 0xffffffu);
+            }
+            total += __popcll(m);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#ifdef RL_STAGE_TIMERS
+        if (stats && total > 0 && rank == 0) stats->passes++;
+#endif
+        for (int base = 0; base < total; base += n_live) {
+            const int g = base + rank;
+            const bool valid = g < total;
+            int owner = lane; unsigned code = 0u;
+            if (valid) { const int e = wave[(g >> 6) * kRow + 2 * (g & 63) + 1]; owner = (int)((unsigned)e >> 24); code = (unsigned)e & 0xffffffu; }
+            // (the fetches outside the branch: a lane whose owner sat in the false arm would read nothing)
+            const int sel = owner << 2;
+#define RL_FROM(x) __int_as_float(__builtin_amdgcn_ds_bpermute(sel, __float_as_int(x)))
+            const V3 oo = mk3(RL_FROM(o.x), RL_FROM(o.y), RL_FROM(o.z)), od = mk3(RL_FROM(d.x), RL_FROM(d.y), RL_FROM(d.z));
+            const float otf = RL_FROM(tfar);
+#undef RL_FROM
+#ifdef RL_STAGE_TIMERS
+            if (stats && rank == 0) stats->rounds++;
+#endif
+            if (valid) {
+                const int first = (int)(code >> 2), count = (int)(code & 3u);
+                Hit h; h.t = otf; h.u = 0.0f; h.v = 0.0f; h.prim = -1;
+                bool acc = false;
+                for (int k = 0; k < count; k++) {
+#ifdef RL_STAGE_TIMERS
+                    if (stats) { if (lane == (int)__builtin_ctzll(__ballot(true))) stats->tests_paid++; }
+#endif
+                    const float4* q = recs.tris + Stack::kTriStride4 * (first + k);
+                    acc |= tri_test(q[0], q[1], q[2], q[3], oo, od, h, first + k);
+                }
+                if (acc) wave[kRow * (rows - 1) + 2 * owner] = 1;      // (several lanes may store the same 1)
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        occ = *flag != 0;
+        nl = 0;
+        if (occ) { cur = RL_CHILD_NONE; sp = 0; }
+        if (__ballot(cur >= 0) == 0ull) break;
+    }
+    return occ;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -25,6 +25,9 @@ int rl_debug_trace_batch_fast(rl_context* ctx, size_t n, const float* origins, c
 // rl_trace_batch through the two-level node records (trace.hip.h: traverse2, which no renderer uses) + node trips per ray; any_hit: t_inout = segment lengths in, 1 / 0 out
 int rl_debug_trace_batch_two_level(rl_context* ctx, size_t n, const float* origins, const float* directions, float* t_inout, float* u_out, float* v_out,
                                    int32_t* mesh_out, int32_t* tri_out, int32_t* steps_out, int any_hit);
+// rl_visible_batch on a scene staged in LDS (RL_ERR_UNSUPPORTED otherwise): packed = 0 the per-lane any-hit loop, != 0 the wave's packed form (trace.hip.h: occluded_packed)
+// with option shadow_pack_capacity = capacity (0: the stack's levels decide)
+int rl_debug_visible_batch_lds(rl_context* ctx, size_t n, const float* p0, const float* p1, int packed, int capacity, uint8_t* visible_out);
 // host only: the two-level records against the BVH2 they are derived from (bvh.cpp)
 int rl_debug_check_two_level(const rl_scene* scene, uint64_t* out6);
 // rng_advance (kernels/rngjump.h) on the device: states_out[i] = sampler states_in[i] (4 x u64) after counts[i] more draws

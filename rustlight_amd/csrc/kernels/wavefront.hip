@@ -230,6 +230,22 @@ __global__ void __launch_bounds__(256) k_visible_batch(DeviceScene sc, StackConf
     out[i] = shadow_visible(sc, recs, stack, p0, p1) ? 1 : 0;
 }
 
+// test hook: batched Acceleration::visible on a scene staged in LDS — the per-lane any-hit loop (packed = 0) or the wave's packed form (occluded_packed: every lane of
+// the workgroup stays to the end, lanes past the batch hold no segment)
+__global__ void __launch_bounds__(256) k_visible_batch_lds(DeviceScene sc, StackConf stc, unsigned n, const float* p0a, const float* p1a, unsigned char* out, int packed) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem[];
+    SceneRecs recs;
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    const TravStackT<true> stack = open_scene<true>(sc, stc, smem, i, &recs);
+    const bool has = i < n;
+    const unsigned j = has ? i : 0u;
+    const V3 p0 = mk3(p0a[3 * j], p0a[3 * j + 1], p0a[3 * j + 2]), p1 = mk3(p1a[3 * j], p1a[3 * j + 1], p1a[3 * j + 2]);
+    bool vis = false;
+    if (packed) vis = shadow_visible<true>(sc, recs, stack, p0, p1, has, stc.pack_cap);
+    else if (has) vis = shadow_visible(sc, recs, stack, p0, p1);
+    if (has) out[i] = vis ? 1 : 0;
+}
+
 // device self-test of the numerics contract: IEEE divide / sqrt, denormals, no contraction
 __global__ void k_numerics_probe(unsigned n, const float* a, const float* b, float* out_div, float* out_sqrt, float* out_mad, float* out_sin,
                                  float* out_cos, float* out_exp, float* out_log, float* out_pow, float* out_acos, float* out_atan2) {
@@ -545,6 +561,7 @@ static int stack_conf(rl_context* ctx, size_t n_threads, StackConf* out, bool se
     HipBuffer<int>& d_overflow = second ? ctx->d_overflow2 : ctx->d_overflow;
     out->lds_levels = lds_levels >= 0 ? std::min(lds_levels, lds_levels_of(ctx)) : lds_levels_of(ctx);
     out->pre_group = 0;          // only k_stream_chain uses it (its launch code sets it)
+    out->pack_cap = 0;           // only k_path_fused's tail form uses it (path_render.hip.h sets it)
     out->overflow = nullptr;
     out->overflow_stride = n_threads;
     int extra = (int)std::max(ctx->ds.stack_depth, ctx->ds.stack_depth4) - out->lds_levels;     // (the tolerance build's BVH4 stacks are the deeper ones)
@@ -1399,6 +1416,27 @@ extern "C" int rl_visible_batch(rl_context* ctx, size_t n, const float* p0, cons
 }
 
 // ---- debug / test hooks (declared in wavefront.h, exported for the test-suite)
+extern "C" int rl_debug_visible_batch_lds(rl_context* ctx, size_t n, const float* p0, const float* p1, int packed, int capacity, uint8_t* visible_out) {
+    if (!ctx || (n && (!p0 || !p1 || !visible_out)) || capacity < 0) return RL_ERR_INVALID_ARGUMENT;
+    if (!ctx->lds_scene) { rl_set_error("rl_debug_visible_batch_lds: the scene is not staged in LDS"); return RL_ERR_UNSUPPORTED; }
+    if (n == 0) return RL_OK;
+    if (n > kMaxBatch) { rl_set_error("batch too large"); return RL_ERR_INVALID_ARGUMENT; }
+    HIP_OK(hipSetDevice(ctx->device));
+    HipBuffer<float> b_a, b_b; HipBuffer<unsigned char> b_o;
+    int rcode;
+    if ((rcode = b_a.ensure(3 * n)) != RL_OK || (rcode = b_b.ensure(3 * n)) != RL_OK || (rcode = b_o.ensure(n)) != RL_OK) return rcode;
+    HIP_OK(hipMemcpy(b_a.get(), p0, 3 * n * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(b_b.get(), p1, 3 * n * 4, hipMemcpyHostToDevice));
+    const size_t lds = traversal_lds_bytes(ctx, true, 256, false);
+    StackConf stc;
+    if ((rcode = stack_conf(ctx, (n + 255) / 256 * 256, &stc)) != RL_OK) return rcode;
+    stc.pack_cap = std::min(capacity, kLdsStackLevels);
+    hipLaunchKernelGGL(k_visible_batch_lds, dim3((unsigned)((n + 255) / 256)), dim3(256), lds, ctx->stream, ctx->ds, stc, (unsigned)n, b_a.get(), b_b.get(), b_o.get(), packed);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    HIP_OK(hipMemcpy(visible_out, b_o.get(), n, hipMemcpyDeviceToHost));
+    return RL_OK;
+}
 extern "C" int rl_debug_numerics(int device, size_t n, const float* a, const float* b, float* out8) {
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return RL_ERR_NO_DEVICE;
